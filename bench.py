@@ -15,11 +15,20 @@ layer per cut; assembly needs no collective, the BiCGStab solve (the library's f
 pfv_solve_sharded) exchanges halo entries of the SpMV input point-to-point and fuses every pair of
 dot products into one all-reduce - this process only serves those two hooks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with ``roofline`` for the
-dominant kernel (CSR SpMV of the solve; live HIP-event timing through pfv_time_kernel) and
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the
+``--steps`` steps, optionally writes their outputs (``--dump-outputs DIR``) and prints the headline
+(``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, the configuration of the timed
+step).  Everything else is measured only with ``--full``: ``roofline`` for the dominant kernel (CSR SpMV of the
+solve; live HIP-event timing through pfv_time_kernel), the cold step, the assembly figures, the field check,
 ``cpu_baseline`` = PorePy's own CPU path (the reference, byte-compiled by ``oracle/make_ref.py`` into
-``oracle/_ref/``) timed on this box's host cores at 196 608 cells of the same workload family; the oracle
-port only where no reference is importable.
+``oracle/_ref/``) timed on the host cores at 196 608 cells of the same workload family (the oracle port only where
+no reference is importable), the whole-grid parity datum and the secondary configurations.
+
+``--dump-outputs DIR`` writes what the last timed step handed its caller, cell by cell in the order of the global
+cell ids (the same arrays at any number of ranks): ``pressure.npy`` (the solution), ``rhs.npy`` (the assembled
+right-hand side) and ``system_matrix_times_probe.npy`` (the assembled matrix applied to a fixed pseudo-random
+vector), float64.  Above 64 MB in all a fixed, seeded sample of the cells is written, their ids in ``cell_ids.npy``.
+The inputs of every warmup and timed step are the same from run to run.
 """
 from __future__ import annotations
 
@@ -169,6 +178,15 @@ def _hash_normal(gid: np.ndarray, salt: int) -> np.ndarray:
     u1 = ((a >> np.uint64(11)).astype(np.float64) + 0.5) / float(1 << 53)
     u2 = ((b >> np.uint64(11)).astype(np.float64) + 0.5) / float(1 << 53)
     return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+
+def permeability_factors(gid: np.ndarray, n_fields: int) -> list:
+    """Log-normal factors 1 .. n_fields - 1 of the per-step permeability fields, exp(0.5 N(0,1)) per global cell id,
+    drawn by a few host threads (numpy's ufuncs release the GIL): the same arrays as drawn one after the other."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        return list(ex.map(lambda i: np.exp(0.5 * _hash_normal(gid, 1000 + 2 * i)), range(1, n_fields)))
 
 
 def block_grid(world: int):
@@ -734,6 +752,42 @@ def bench_operator_api(pa, lp, Kvals, flags, bv, src, eta, device_index: int):
     return out
 
 
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: at most 64 MB in all
+DUMP_PROBE_SALT = 4242     # the probe vector the assembled matrix is applied to: _hash_normal(global cell id, salt)
+DUMP_SAMPLE_SEED = 20250611
+
+
+def dump_outputs(out_dir: str, pa, ctx, x, lp, dist, rank: int):
+    """--dump-outputs: what the last timed step handed its caller -- the solution, the assembled right-hand side and the
+    assembled matrix applied to a fixed probe vector (a function of the global cell id) -- for the cells each rank owns,
+    gathered on rank 0 and written in the order of the global cell ids as float64.  Above DUMP_BYTES_MAX in all: a
+    fixed, seeded sample of the cells, their global ids in cell_ids.npy."""
+    n = lp.n_own
+    gid = np.asarray(lp.cell_gid, dtype=np.int64)
+    xh = x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+    probe = _hash_normal(gid, DUMP_PROBE_SALT)
+    mine = (gid[:n], {"pressure": np.array(xh[:n], dtype=np.float64),
+                      "rhs": np.array(ctx.rhs()[:n], dtype=np.float64),
+                      "system_matrix_times_probe": np.array(ctx.spmv(pa._lib.MAT_SYSTEM, probe)[:n], dtype=np.float64)})
+    parts = [mine]
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, mine)
+    if rank != 0:
+        return
+    ids = np.concatenate([p[0] for p in parts])
+    order = np.argsort(ids, kind="stable")
+    out = {k: np.concatenate([p[1][k] for p in parts])[order] for k in mine[1]}
+    if 8 * len(out) * ids.size > DUMP_BYTES_MAX:
+        m = DUMP_BYTES_MAX // (8 * (len(out) + 1))
+        pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(ids.size, m, replace=False))
+        out = {k: v[pick] for k, v in out.items()}
+        out["cell_ids"] = ids[order][pick].astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def self_launch_if_needed():
     """``python bench.py --gpus N`` with N > 1 and no launcher around it (WORLD_SIZE unset): start the N ranks of
     this node here -- the same ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
@@ -807,6 +861,12 @@ def main():
                          "split into N slabs; weak: every GPU owns an n x n x n lattice slab of a box that grows with N")
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the N > 1 code path (torch-driven sharded solver) on one GPU, for validation")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline: cold step, "
+                         "rooflines, assembly figures, field check, CPU baselines, whole-grid datum, secondary "
+                         "configurations (the --no-* / --cpu-* / --c5 options tune these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
 
     import torch
@@ -874,7 +934,7 @@ def main():
         n_fields = 1 if args.fixed_k else min(64, 6 + args.warmup + args.steps + 1)
         base_scale = np.exp(0.5 * _hash_normal(lp.cell_gid, 7))
         d_aniso = torch.from_numpy(np.ascontiguousarray(Kvals / base_scale[None, None, :])).to(dev)   # (3, 3, nloc)
-        fields = [base_scale] + [np.exp(0.5 * _hash_normal(lp.cell_gid, 1000 + 2 * i)) for i in range(1, n_fields)]
+        fields = [base_scale] + permeability_factors(lp.cell_gid, n_fields)
         d_fac = torch.from_numpy(np.ascontiguousarray(np.stack(fields))).to(dev)                      # (n_fields, nloc)
         d_K = torch.empty_like(d_aniso)
         del fields
@@ -911,7 +971,7 @@ def main():
         n_fields = 1 if args.fixed_k else min(32, 6 + args.warmup + args.steps + 1)
         base_scale = np.exp(0.5 * _hash_normal(lp.cell_gid, 7))
         d_aniso = torch.from_numpy(np.ascontiguousarray(Kvals / base_scale[None, None, :])).to(devs)
-        fields = [base_scale] + [np.exp(0.5 * _hash_normal(lp.cell_gid, 1000 + 2 * i)) for i in range(1, n_fields)]
+        fields = [base_scale] + permeability_factors(lp.cell_gid, n_fields)
         d_fac = torch.from_numpy(np.ascontiguousarray(np.stack(fields))).to(devs)
         d_K = torch.empty_like(d_aniso)
         del fields
@@ -950,6 +1010,7 @@ def main():
             last = dtp
             if stable:
                 break
+    step_no[0] = 0  # (the warmup and timed steps draw the same fields in every run, however long the pre-warm took)
     for _ in range(args.warmup):
         x, info = step()
     barrier()
@@ -968,10 +1029,12 @@ def main():
         elapsed = float(t.item())
     st = ctx.stats()
     ms_per_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pa, ctx, x, lp, dist, rank)
     # ---- the same step with NOTHING kept between steps (aggregate maps, SpMV windows, filter layout, Galerkin sizes
     # all rebuilt): the cold figure beside the headline
     cold = None
-    if not args.no_cold:
+    if args.full and not args.no_cold:
         off = {"PFV_AMG_REUSE_REBUILT": "0", "PFV_WIN_REUSE": "0", "PFV_AMG_FILTER_LAYOUT_REUSE": "0", "PFV_AMG_SIZES_REUSE": "0",
                "PFV_SYMB_REUSE": "0"}
         saved = {k: os.environ.get(k) for k in off}
@@ -1015,225 +1078,223 @@ def main():
         ncells_total = int(tcount.item())
     value = ncells_total * args.steps / elapsed
 
-    # ---- rooflines: every kernel that matters, the one with the most time per step is `roofline` ----
     its = int(info["iterations"]) if isinstance(info, dict) and "iterations" in info else 0
-    triad_ms = ctx.time_kernel(4, reps=10)
-    triad_gbs = 3.0 * 8.0 * (1 << 27) / (triad_ms * 1e-3) / 1e9  # a = b + s c on 3 x 2^27 doubles
-    read_gbs = 8.0 * (1 << 28) / (ctx.time_kernel(5, reps=10) * 1e-3) / 1e9  # read-only stream over 2^28 doubles
-    pmc = load_pmc(args.n_side, world)
+    # ---- everything beside the headline (--full): cold step above, rooflines, assembly figures, checks, baselines,
+    # secondary configurations
+    kernels, roofline, per_step_ms, triad_gbs, read_gbs, assembly = [], None, None, None, None, None
+    cpu = c2 = c4 = opapi = field = cpu_headline = whole_grid = per_rank = None
+    if args.full:
+        # ---- rooflines: every kernel that matters, the one with the most time per step is `roofline` ----
+        triad_ms = ctx.time_kernel(4, reps=10)
+        triad_gbs = 3.0 * 8.0 * (1 << 27) / (triad_ms * 1e-3) / 1e9  # a = b + s c on 3 x 2^27 doubles
+        read_gbs = 8.0 * (1 << 28) / (ctx.time_kernel(5, reps=10) * 1e-3) / 1e9  # read-only stream over 2^28 doubles
+        pmc = load_pmc(args.n_side, world)
 
-    def hbm_entry(name, kernel, bytes_per_launch, ms, launches_per_step, note, pmc_key=None, extra=None):
-        ach = bytes_per_launch / (ms * 1e-3) / 1e9
-        e = {"bound": "hbm", "kernel": kernel, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-             "frac": ach / HBM_PEAK_GBS, "frac_of_measured_triad": ach / triad_gbs,
-             "frac_of_measured_read_stream": ach / read_gbs,
-             "traffic": (pmc.get(pmc_key, {}) or {}).get("traffic_bytes_per_launch") if pmc_key else None,
-             "bytes_per_launch": bytes_per_launch, "ms_per_launch": ms, "launches_per_step": launches_per_step,
-             "ms_per_step": ms * launches_per_step, "note": note, "name": name}
-        if extra:
-            e.update(extra)
-        return e
+        def hbm_entry(name, kernel, bytes_per_launch, ms, launches_per_step, note, pmc_key=None, extra=None):
+            ach = bytes_per_launch / (ms * 1e-3) / 1e9
+            e = {"bound": "hbm", "kernel": kernel, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                 "frac": ach / HBM_PEAK_GBS, "frac_of_measured_triad": ach / triad_gbs,
+                 "frac_of_measured_read_stream": ach / read_gbs,
+                 "traffic": (pmc.get(pmc_key, {}) or {}).get("traffic_bytes_per_launch") if pmc_key else None,
+                 "bytes_per_launch": bytes_per_launch, "ms_per_launch": ms, "launches_per_step": launches_per_step,
+                 "ms_per_step": ms * launches_per_step, "note": note, "name": name}
+            if extra:
+                e.update(extra)
+            return e
 
-    _, _, nnzA = ctx.matrix_info(pa._lib.MAT_SYSTEM)
-    kernels = []
-    spmv_ms = ctx.time_kernel(0, reps=50)
-    spmv_bytes = 12.0 * nnzA + 4.0 * (nloc + 1) + 8.0 * nloc + 8.0 * nloc  # values+indices, indptr, x, y
-    # launches per step: two products per BiCGStab iteration + the product of the true-residual check that ends every
-    # solve (linalg.inc: krylov_solve, PFV_TRUE_RESIDUAL) -- the same kernel on the same matrix
-    true_residual_products = 0 if (sh is not None or os.environ.get("PFV_TRUE_RESIDUAL", "1") == "0") else 1
-    kernels.append(hbm_entry(
-        "krylov_f64_product", "k_spmv_win<double> (CSR SpMV with A in f64, x window staged in LDS, fused dots)",
-        spmv_bytes, spmv_ms, 2 * its + true_residual_products,
-        "achieved = SURVEY 8(d) CSR bytes (12 B per entry) / time; the kernel itself streams ~10 B per entry "
-        "(16-bit window-local column indices)", "krylov",
-        {"streamed_GBs": (10.0 * nnzA + 4.0 * (nloc + 1) + 8.0 * nloc + 12.0 * nloc * 0.36) / (spmv_ms * 1e-3) / 1e9}))
-    if args.precond in ("amg", "amg_block") and os.environ.get("PFV_AMG_FP32", "1") != "0":
-        sm_ms = ctx.time_kernel(3, reps=50)
-        st_amg = ctx.stats()
-        nnzS = int(st_amg.get("amg_level0_nnz", 0)) or nnzA  # the cycle's finest level: the strength-filtered operator
-        sm_bytes = 8.0 * nnzS + 4.0 * (nloc + 1) + 4 * 8.0 * nloc  # f32 values + indices, indptr, x, y, b, dinv
+        _, _, nnzA = ctx.matrix_info(pa._lib.MAT_SYSTEM)
+        kernels = []
+        spmv_ms = ctx.time_kernel(0, reps=50)
+        spmv_bytes = 12.0 * nnzA + 4.0 * (nloc + 1) + 8.0 * nloc + 8.0 * nloc  # values+indices, indptr, x, y
+        # launches per step: two products per BiCGStab iteration + the product of the true-residual check that ends every
+        # solve (linalg.inc: krylov_solve, PFV_TRUE_RESIDUAL) -- the same kernel on the same matrix
+        true_residual_products = 0 if (sh is not None or os.environ.get("PFV_TRUE_RESIDUAL", "1") == "0") else 1
         kernels.append(hbm_entry(
-            "amg_f32_smoothing_product", "k_spmv_win<float, smooth> (finest-level smoothing product of the AMG cycle: "
-            "y = x + w D^-1 (b - A_s x), f32 matrix values, f64 vectors)", sm_bytes, sm_ms, 4 * its,
-            f"achieved = CSR bytes with f32 values (8 B per entry) / time; the kernel streams ~6 B per entry.  A_s = the "
-            f"strength-filtered copy of A the cycle works on (theta {st_amg.get('amg_filter_theta', 0.0):.3f}: {nnzS} of "
-            f"{nnzA} entries; the Krylov product keeps A)", "smooth",
-            {"streamed_GBs": (6.0 * nnzS + 4.0 * (nloc + 1) + 4 * 8.0 * nloc + 12.0 * nloc * 0.36) / (sm_ms * 1e-3) / 1e9,
-             "entries": nnzS}))
-    nnz = {k: ctx.matrix_info(i)[2] for i, k in enumerate(("flux", "bound_flux", "bpc", "bpf", "vs", "bpvs"))}
-    face_ms = ctx.time_kernel(2, reps=3)
-    face_bytes = 8.0 * sum(nnz.values())  # every value of the six matrices written once; inputs are intermediate tables
-    kernels.append(hbm_entry(
-        "face_kernel", "k_face_pipe<3> (rows of the per-node response tables -> CSR values of the six matrices; "
-        "software-pipelined persistent kernel)", face_bytes, face_ms, 1,
-        "achieved = 8 B x nnz of the six output matrices / time (SURVEY 8(d) B_out values); the kernel also reads "
-        "the response tables (node_table_doubles x 8 B, once if L2 / Infinity Cache hold the re-reads)", "face",
-        {"table_bytes_read_once": 8.0 * st["node_table_doubles"]}))
-    node_ms = ctx.time_kernel(1, reps=3)
-    fp64_peak = 78.6e12  # MI355X vector FP64; FP64 MFMA has no higher rate on this part
-    nnodes = st["num_nodes"]
-    ref_flops = 1.2e6 * nnodes * (st["sum_block_sq"] / max(nnodes, 1) / 36.0 ** 2) ** 1.5  # ~1.2 MFLOP per 36-sub-face node
-    # bound "mfma" = the compute roofline of the dtype: on MI355X the dense FP64 MFMA peak IS the vector FP64 peak
-    # (78.6 TFLOP/s, MI355X_MICROARCH.md); the kernel issues vector FMAs (see "note")
-    node_entry = {"bound": "mfma", "compute_unit": "FP64 vector FMA (FP64 MFMA has the same peak on this part)", "name": "node_kernel",
-                  "kernel": "launch_node_class_reg<64,3,40> (interaction regions: nK, D^-1, condensed system, register "
-                            "Gauss-Jordan with partial pivoting, response table A^-1 G)",
-                  "achieved": st["node_flops"] / (node_ms * 1e-3) / 1e12, "peak": fp64_peak / 1e12, "unit": "TFLOP/s",
-                  "frac": st["node_flops"] / (node_ms * 1e-3) / fp64_peak,
-                  "flops_per_launch_executed": st["node_flops"],
-                  "flops_per_launch_reference_formulation": ref_flops,
-                  "frac_on_reference_formulation_flops": ref_flops / (node_ms * 1e-3) / fp64_peak,
-                  "bytes_written_per_launch": 8.0 * st["node_table_doubles"],
-                  "written_GBs": 8.0 * st["node_table_doubles"] / (node_ms * 1e-3) / 1e9,
-                  "ms_per_launch": node_ms, "launches_per_step": 1, "ms_per_step": node_ms,
-                  "traffic": (pmc.get("node", {}) or {}).get("traffic_bytes_per_launch"),
-                  "note": "executed flops: the condensed n x n systems (n = 36 at an interior node of a tetrahedral grid) "
-                          "are 8x less arithmetic than the reference's (nd deg)^2 gradient systems whose count SURVEY 8(d) "
-                          "states; both fractions are given.  36 of 64 lanes hold a matrix row: the kernel is bound by "
-                          "VALU issue (2 v_readlane + 1 v_fma_f64 per entry and pivot step), not by flops or bytes"}
-    kernels.append(node_entry)
-    kernels.sort(key=lambda e: -e["ms_per_step"])
-    roofline = kernels[0]
-    per_step_ms = {e["name"]: e["ms_per_step"] for e in kernels}
+            "krylov_f64_product", "k_spmv_win<double> (CSR SpMV with A in f64, x window staged in LDS, fused dots)",
+            spmv_bytes, spmv_ms, 2 * its + true_residual_products,
+            "achieved = SURVEY 8(d) CSR bytes (12 B per entry) / time; the kernel itself streams ~10 B per entry "
+            "(16-bit window-local column indices)", "krylov",
+            {"streamed_GBs": (10.0 * nnzA + 4.0 * (nloc + 1) + 8.0 * nloc + 12.0 * nloc * 0.36) / (spmv_ms * 1e-3) / 1e9}))
+        if args.precond in ("amg", "amg_block") and os.environ.get("PFV_AMG_FP32", "1") != "0":
+            sm_ms = ctx.time_kernel(3, reps=50)
+            st_amg = ctx.stats()
+            nnzS = int(st_amg.get("amg_level0_nnz", 0)) or nnzA  # the cycle's finest level: the strength-filtered operator
+            sm_bytes = 8.0 * nnzS + 4.0 * (nloc + 1) + 4 * 8.0 * nloc  # f32 values + indices, indptr, x, y, b, dinv
+            kernels.append(hbm_entry(
+                "amg_f32_smoothing_product", "k_spmv_win<float, smooth> (finest-level smoothing product of the AMG cycle: "
+                "y = x + w D^-1 (b - A_s x), f32 matrix values, f64 vectors)", sm_bytes, sm_ms, 4 * its,
+                f"achieved = CSR bytes with f32 values (8 B per entry) / time; the kernel streams ~6 B per entry.  A_s = the "
+                f"strength-filtered copy of A the cycle works on (theta {st_amg.get('amg_filter_theta', 0.0):.3f}: {nnzS} of "
+                f"{nnzA} entries; the Krylov product keeps A)", "smooth",
+                {"streamed_GBs": (6.0 * nnzS + 4.0 * (nloc + 1) + 4 * 8.0 * nloc + 12.0 * nloc * 0.36) / (sm_ms * 1e-3) / 1e9,
+                 "entries": nnzS}))
+        nnz = {k: ctx.matrix_info(i)[2] for i, k in enumerate(("flux", "bound_flux", "bpc", "bpf", "vs", "bpvs"))}
+        face_ms = ctx.time_kernel(2, reps=3)
+        face_bytes = 8.0 * sum(nnz.values())  # every value of the six matrices written once; inputs are intermediate tables
+        kernels.append(hbm_entry(
+            "face_kernel", "k_face_pipe<3> (rows of the per-node response tables -> CSR values of the six matrices; "
+            "software-pipelined persistent kernel)", face_bytes, face_ms, 1,
+            "achieved = 8 B x nnz of the six output matrices / time (SURVEY 8(d) B_out values); the kernel also reads "
+            "the response tables (node_table_doubles x 8 B, once if L2 / Infinity Cache hold the re-reads)", "face",
+            {"table_bytes_read_once": 8.0 * st["node_table_doubles"]}))
+        node_ms = ctx.time_kernel(1, reps=3)
+        fp64_peak = 78.6e12  # MI355X vector FP64; FP64 MFMA has no higher rate on this part
+        nnodes = st["num_nodes"]
+        ref_flops = 1.2e6 * nnodes * (st["sum_block_sq"] / max(nnodes, 1) / 36.0 ** 2) ** 1.5  # ~1.2 MFLOP per 36-sub-face node
+        # bound "mfma" = the compute roofline of the dtype: on MI355X the dense FP64 MFMA peak IS the vector FP64 peak
+        # (78.6 TFLOP/s, MI355X_MICROARCH.md); the kernel issues vector FMAs (see "note")
+        node_entry = {"bound": "mfma", "compute_unit": "FP64 vector FMA (FP64 MFMA has the same peak on this part)", "name": "node_kernel",
+                      "kernel": "launch_node_class_reg<64,3,40> (interaction regions: nK, D^-1, condensed system, register "
+                                "Gauss-Jordan with partial pivoting, response table A^-1 G)",
+                      "achieved": st["node_flops"] / (node_ms * 1e-3) / 1e12, "peak": fp64_peak / 1e12, "unit": "TFLOP/s",
+                      "frac": st["node_flops"] / (node_ms * 1e-3) / fp64_peak,
+                      "flops_per_launch_executed": st["node_flops"],
+                      "flops_per_launch_reference_formulation": ref_flops,
+                      "frac_on_reference_formulation_flops": ref_flops / (node_ms * 1e-3) / fp64_peak,
+                      "bytes_written_per_launch": 8.0 * st["node_table_doubles"],
+                      "written_GBs": 8.0 * st["node_table_doubles"] / (node_ms * 1e-3) / 1e9,
+                      "ms_per_launch": node_ms, "launches_per_step": 1, "ms_per_step": node_ms,
+                      "traffic": (pmc.get("node", {}) or {}).get("traffic_bytes_per_launch"),
+                      "note": "executed flops: the condensed n x n systems (n = 36 at an interior node of a tetrahedral grid) "
+                              "are 8x less arithmetic than the reference's (nd deg)^2 gradient systems whose count SURVEY 8(d) "
+                              "states; both fractions are given.  36 of 64 lanes hold a matrix row: the kernel is bound by "
+                              "VALU issue (2 v_readlane + 1 v_fma_f64 per entry and pivot step), not by flops or bytes"}
+        kernels.append(node_entry)
+        kernels.sort(key=lambda e: -e["ms_per_step"])
+        roofline = kernels[0]
+        per_step_ms = {e["name"]: e["ms_per_step"] for e in kernels}
 
-    # assembly phases (HBM-bound on their CSR output): algorithmic bytes = inputs once + outputs once
-    # (the index array of vector_source -- nd x the flux pattern, a pure function of it -- is written on first use
-    # and the timed step never asks for it: its 4 B x nnz are NOT counted, PFV_VS_INDICES_EAGER=1 restores both)
-    vs_index_bytes = 4.0 * nnz["vs"] if os.environ.get("PFV_VS_INDICES_EAGER", "0") not in ("", "0") else 0.0
-    out_bytes = 8.0 * sum(nnz.values()) + 4.0 * (nnz["flux"] + nnz["bound_flux"]) + vs_index_bytes + 12.0 * nnzA
-    nfl, nnl = lp.raw["face_centers"].shape[1], lp.raw["nodes"].shape[1]
-    in_bytes = 8.0 * (3 * nnl + 3 * nloc + 7 * nfl) + 72.0 * nloc + 5.0 * 4 * nloc + 4.0 * 3 * nfl
-    # the interaction-region kernel runs beside the symbolic phase (second stream): the phases overlap, the
-    # assembly time is the span of the discretize call plus div@flux / rhs
-    asm_ms = st["discretize_ms"] + st["assemble_ms"]
-    assembly = {"algorithmic_bytes": out_bytes + in_bytes, "ms": asm_ms,
-                "achieved_GBs": (out_bytes + in_bytes) / (asm_ms * 1e-3) / 1e9,
-                "frac_of_hbm_peak": (out_bytes + in_bytes) / (asm_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "frac_of_measured_triad": (out_bytes + in_bytes) / (asm_ms * 1e-3) / 1e9 / triad_gbs,
-                "phases_ms": {k: st[k] for k in ("topology_ms", "symbolic_ms", "node_ms", "face_ms",
-                                                 "assemble_ms", "solve_ms", "discretize_ms")},
-                "phases_note": "symbolic_ms and node_ms are overlapping spans (two streams); discretize_ms is the whole call",
-                "cells_per_s_assembly_only": nloc / (asm_ms * 1e-3)}
-    if world == 1 and not args.force_sharded:
-        # the same grid with new parameter values (what a nonlinear model does every iteration): topology and
-        # CSR patterns are kept, only the values are recomputed -- index bytes are then not part of the output
-        ctx.discretize(rebuild_topology=False)
-        ctx.sync()
-        tw = time.perf_counter()
-        for _ in range(3):
+        # assembly phases (HBM-bound on their CSR output): algorithmic bytes = inputs once + outputs once
+        # (the index array of vector_source -- nd x the flux pattern, a pure function of it -- is written on first use
+        # and the timed step never asks for it: its 4 B x nnz are NOT counted, PFV_VS_INDICES_EAGER=1 restores both)
+        vs_index_bytes = 4.0 * nnz["vs"] if os.environ.get("PFV_VS_INDICES_EAGER", "0") not in ("", "0") else 0.0
+        out_bytes = 8.0 * sum(nnz.values()) + 4.0 * (nnz["flux"] + nnz["bound_flux"]) + vs_index_bytes + 12.0 * nnzA
+        nfl, nnl = lp.raw["face_centers"].shape[1], lp.raw["nodes"].shape[1]
+        in_bytes = 8.0 * (3 * nnl + 3 * nloc + 7 * nfl) + 72.0 * nloc + 5.0 * 4 * nloc + 4.0 * 3 * nfl
+        # the interaction-region kernel runs beside the symbolic phase (second stream): the phases overlap, the
+        # assembly time is the span of the discretize call plus div@flux / rhs
+        asm_ms = st["discretize_ms"] + st["assemble_ms"]
+        assembly = {"algorithmic_bytes": out_bytes + in_bytes, "ms": asm_ms,
+                    "achieved_GBs": (out_bytes + in_bytes) / (asm_ms * 1e-3) / 1e9,
+                    "frac_of_hbm_peak": (out_bytes + in_bytes) / (asm_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                    "frac_of_measured_triad": (out_bytes + in_bytes) / (asm_ms * 1e-3) / 1e9 / triad_gbs,
+                    "phases_ms": {k: st[k] for k in ("topology_ms", "symbolic_ms", "node_ms", "face_ms",
+                                                     "assemble_ms", "solve_ms", "discretize_ms")},
+                    "phases_note": "symbolic_ms and node_ms are overlapping spans (two streams); discretize_ms is the whole call",
+                    "cells_per_s_assembly_only": nloc / (asm_ms * 1e-3)}
+        if world == 1 and not args.force_sharded:
+            # the same grid with new parameter values (what a nonlinear model does every iteration): topology and
+            # CSR patterns are kept, only the values are recomputed -- index bytes are then not part of the output
             ctx.discretize(rebuild_topology=False)
-            ctx.assemble_device(d_bv.data_ptr(), 0, d_src.data_ptr())
-        ctx.sync()
-        warm_ms = 1e3 * (time.perf_counter() - tw) / 3
-        warm_bytes = 8.0 * sum(nnz.values()) + 8.0 * nnzA + in_bytes
-        assembly["values_only_rediscretization"] = {
-            "ms": warm_ms, "algorithmic_bytes": warm_bytes, "achieved_GBs": warm_bytes / (warm_ms * 1e-3) / 1e9,
-            "frac_of_hbm_peak": warm_bytes / (warm_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            "note": "pfv_mpfa_discretize without PFV_DISCR_REBUILD_TOPOLOGY + div@flux: interaction-region kernel, face "
-                    "kernel, system matrix; not the headline (the timed step rebuilds everything)"}
-        # ... and the whole step of such an iteration: values-only discretization, assembly, and a solve whose AMG
-        # setup keeps the aggregates of the previous matrix (only the Galerkin products are redone)
-        d_xw = torch.zeros(nloc, dtype=torch.float64, device=dev)
+            ctx.sync()
+            tw = time.perf_counter()
+            for _ in range(3):
+                ctx.discretize(rebuild_topology=False)
+                ctx.assemble_device(d_bv.data_ptr(), 0, d_src.data_ptr())
+            ctx.sync()
+            warm_ms = 1e3 * (time.perf_counter() - tw) / 3
+            warm_bytes = 8.0 * sum(nnz.values()) + 8.0 * nnzA + in_bytes
+            assembly["values_only_rediscretization"] = {
+                "ms": warm_ms, "algorithmic_bytes": warm_bytes, "achieved_GBs": warm_bytes / (warm_ms * 1e-3) / 1e9,
+                "frac_of_hbm_peak": warm_bytes / (warm_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "note": "pfv_mpfa_discretize without PFV_DISCR_REBUILD_TOPOLOGY + div@flux: interaction-region kernel, face "
+                        "kernel, system matrix; not the headline (the timed step rebuilds everything)"}
+            # ... and the whole step of such an iteration: values-only discretization, assembly, and a solve whose AMG
+            # setup keeps the aggregates of the previous matrix (only the Galerkin products are redone)
+            d_xw = torch.zeros(nloc, dtype=torch.float64, device=dev)
 
-        def warm_step():
-            ctx.discretize(rebuild_topology=False)
-            ctx.assemble_device(d_bv.data_ptr(), 0, d_src.data_ptr())
-            return ctx.solve_device(d_xw.data_ptr(), "bicgstab", rtol=args.rtol, maxit=20000, raise_on_fail=False,
-                                    precond=args.precond)
+            def warm_step():
+                ctx.discretize(rebuild_topology=False)
+                ctx.assemble_device(d_bv.data_ptr(), 0, d_src.data_ptr())
+                return ctx.solve_device(d_xw.data_ptr(), "bicgstab", rtol=args.rtol, maxit=20000, raise_on_fail=False,
+                                        precond=args.precond)
 
-        warm_step()
-        ctx.sync()
-        tw = time.perf_counter()
-        for _ in range(3):
-            winfo = warm_step()
-        ctx.sync()
-        wstep_ms = 1e3 * (time.perf_counter() - tw) / 3
-        stw = ctx.stats()
-        assembly["values_only_step"] = {
-            "ms_per_step": wstep_ms, "cells_per_s": nloc / (wstep_ms * 1e-3), "iterations": winfo["iterations"],
-            "rel_residual": winfo["rel_residual"], "amg_setup_ms": stw["amg_setup_ms"], "amg_maps_reused": int(stw["amg_maps_reused"]),
-            "rel_l2_vs_timed_solution": float(torch.linalg.norm(d_xw - x) / torch.linalg.norm(x)),
-            "note": "secondary figure, not the headline: the step of a nonlinear iteration on a fixed grid (patterns, "
-                    "topology and AMG aggregates kept; all values, the Galerkin products and the solve redone)"}
+            warm_step()
+            ctx.sync()
+            tw = time.perf_counter()
+            for _ in range(3):
+                winfo = warm_step()
+            ctx.sync()
+            wstep_ms = 1e3 * (time.perf_counter() - tw) / 3
+            stw = ctx.stats()
+            assembly["values_only_step"] = {
+                "ms_per_step": wstep_ms, "cells_per_s": nloc / (wstep_ms * 1e-3), "iterations": winfo["iterations"],
+                "rel_residual": winfo["rel_residual"], "amg_setup_ms": stw["amg_setup_ms"], "amg_maps_reused": int(stw["amg_maps_reused"]),
+                "rel_l2_vs_timed_solution": float(torch.linalg.norm(d_xw - x) / torch.linalg.norm(x)),
+                "note": "secondary figure, not the headline: the step of a nonlinear iteration on a fixed grid (patterns, "
+                        "topology and AMG aggregates kept; all values, the Galerkin products and the solve redone)"}
 
-    cpu = None
-    c2 = c4 = None
-    opapi = None
-    field = None
-    if rank == 0 and world == 1 and not args.force_sharded:
-        # field-level check of the timed configuration: the same system solved again (untimed) to the limit of
-        # the arithmetic; the difference of the two solutions bounds the algebraic error of the timed one
-        try:
-            d_x2 = torch.zeros(nloc, dtype=torch.float64, device=dev)
-            info2 = ctx.solve_device(d_x2.data_ptr(), "bicgstab", rtol=2e-15, maxit=400, raise_on_fail=False,
-                                     precond=args.precond)
-            xa, xb = x.cpu().numpy(), d_x2.cpu().numpy()
-            field = {"rel_l2_change_vs_solve_to_2e-15": float(np.linalg.norm(xa - xb) / np.linalg.norm(xb)),
-                     "max_abs_change": float(np.max(np.abs(xa - xb))), "max_abs_field": float(np.max(np.abs(xb))),
-                     "tight_solve_true_rel_residual": info2["rel_residual"], "tight_solve_iterations": info2["iterations"]}
-        except Exception as e:  # diagnostics only
-            field = {"error": repr(e)}
-    cpu_headline = None
-    whole_grid = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(args.cpu_n_side, args.cpu_port_n_side)
-    if rank == 0 and world == 1 and args.cpu_headline > 0:
-        cpu_headline = cpu_baseline_reference(args.n_side, timeout_s=3000.0, num_sub=args.cpu_headline, solve_cap_s=600.0)
-    elif rank == 0 and world == 1 and args.n_side == 69:
-        cpu_headline = cached_cpu_headline()
-    if rank == 0 and world == 1 and not args.force_sharded and args.n_side == 69 and not args.no_whole_grid_check:
-        try:
-            whole_grid = whole_grid_check(pa, local_rank, args.rtol, args.precond)
-            whole_grid.pop("_pattern", None)
-        except Exception as e:  # diagnostics only
-            whole_grid = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.force_sharded and args.n_side == 69 and not args.no_extra_configs:
-        try:
-            opapi = bench_operator_api(pa, lp, Kvals, flags, bv, src, eta, local_rank)
-        except Exception as e:  # secondary line only
-            opapi = {"error": repr(e)}
-        try:
-            c2 = bench_config_c2(pa, local_rank, args.rtol, args.precond)
-        except Exception as e:  # secondary line only
-            c2 = {"error": repr(e)}
-        try:
-            c4 = bench_config_c4(pa, local_rank, args.rtol, args.precond)
-        except Exception as e:  # secondary line only
-            c4 = {"error": repr(e)}
+        if rank == 0 and world == 1 and not args.force_sharded:
+            # field-level check of the timed configuration: the same system solved again (untimed) to the limit of
+            # the arithmetic; the difference of the two solutions bounds the algebraic error of the timed one
+            try:
+                d_x2 = torch.zeros(nloc, dtype=torch.float64, device=dev)
+                info2 = ctx.solve_device(d_x2.data_ptr(), "bicgstab", rtol=2e-15, maxit=400, raise_on_fail=False,
+                                         precond=args.precond)
+                xa, xb = x.cpu().numpy(), d_x2.cpu().numpy()
+                field = {"rel_l2_change_vs_solve_to_2e-15": float(np.linalg.norm(xa - xb) / np.linalg.norm(xb)),
+                         "max_abs_change": float(np.max(np.abs(xa - xb))), "max_abs_field": float(np.max(np.abs(xb))),
+                         "tight_solve_true_rel_residual": info2["rel_residual"], "tight_solve_iterations": info2["iterations"]}
+            except Exception as e:  # diagnostics only
+                field = {"error": repr(e)}
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(args.cpu_n_side, args.cpu_port_n_side)
+        if rank == 0 and world == 1 and args.cpu_headline > 0:
+            cpu_headline = cpu_baseline_reference(args.n_side, timeout_s=3000.0, num_sub=args.cpu_headline, solve_cap_s=600.0)
+        elif rank == 0 and world == 1 and args.n_side == 69:
+            cpu_headline = cached_cpu_headline()
+        if rank == 0 and world == 1 and not args.force_sharded and args.n_side == 69 and not args.no_whole_grid_check:
+            try:
+                whole_grid = whole_grid_check(pa, local_rank, args.rtol, args.precond)
+                whole_grid.pop("_pattern", None)
+            except Exception as e:  # diagnostics only
+                whole_grid = {"error": repr(e)}
+        if rank == 0 and world == 1 and not args.force_sharded and args.n_side == 69 and not args.no_extra_configs:
+            try:
+                opapi = bench_operator_api(pa, lp, Kvals, flags, bv, src, eta, local_rank)
+            except Exception as e:  # secondary line only
+                opapi = {"error": repr(e)}
+            try:
+                c2 = bench_config_c2(pa, local_rank, args.rtol, args.precond)
+            except Exception as e:  # secondary line only
+                c2 = {"error": repr(e)}
+            try:
+                c4 = bench_config_c4(pa, local_rank, args.rtol, args.precond)
+            except Exception as e:  # secondary line only
+                c4 = {"error": repr(e)}
 
-    # ---- every rank's view of the run (N > 1; VERDICT r5 item 8: the first run on several GPUs must yield a diagnosable
-    # curve, not one number): phases of the last timed step by the library's own HIP events, the step times by this rank's
-    # clock, sizes, what the process group looks like from here, what travelled.  One all_gather_object after the clock stopped.
-    per_rank = None
-    if dist is not None:
-        try:
-            mine = {
-                "rank": rank, "local_rank": local_rank,
-                "device": torch.cuda.get_device_name(local_rank) if torch.cuda.is_available() else "cpu",
-                "ranks_seen_by_rccl": int(dist.get_world_size()), "backend": str(dist.get_backend()),
-                "cells_owned": int(nc), "cells_with_halo": int(nloc), "halo_fraction": float(nloc - nc) / max(float(nloc), 1.0),
-                "phases_ms": {k: float(st[k]) for k in ("topology_ms", "symbolic_ms", "node_ms", "face_ms", "assemble_ms",
-                                                        "solve_ms", "discretize_ms", "amg_setup_ms") if k in st},
-                "kept": {"csr_patterns": int(st.get("symbolic_reused", 0)), "spmv_windows": int(st.get("win_reused", 0)),
-                         "amg_aggregate_maps": int(st.get("amg_maps_reused", 0))},
-                "amg": {"levels": int(st.get("amg_levels", 0)), "coarsest_rows": int(st.get("amg_coarsest_rows", 0)),
-                        "operator_complexity": float(st.get("amg_operator_complexity", 0.0))},
-                "launches": {"krylov_loop": int(st.get("solve_launches", 0)), "amg_setup": int(st.get("amg_setup_launches", 0))},
-                "step_ms_by_this_ranks_clock": [round(t, 2) for t, _ in each[:32]],
-                "iterations": [i for _, i in each[:32]],
-                "transport": (info.get("transport") if isinstance(info, dict) else None),
-                "halo_bytes_per_exchange": (info.get("halo_bytes_per_exchange") if isinstance(info, dict) else None),
-                "overlap_interior_boundary": os.environ.get("PFV_SHARD_OVERLAP", "0"),
-            }
-            per_rank = [None] * world
-            dist.all_gather_object(per_rank, mine)
-        except Exception as e:  # (diagnostics only: never costs the line)
-            per_rank = [{"error": repr(e)}]
+        # ---- every rank's view of the run (N > 1; VERDICT r5 item 8: the first run on several GPUs must yield a diagnosable
+        # curve, not one number): phases of the last timed step by the library's own HIP events, the step times by this rank's
+        # clock, sizes, what the process group looks like from here, what travelled.  One all_gather_object after the clock stopped.
+        if dist is not None:
+            try:
+                mine = {
+                    "rank": rank, "local_rank": local_rank,
+                    "device": torch.cuda.get_device_name(local_rank) if torch.cuda.is_available() else "cpu",
+                    "ranks_seen_by_rccl": int(dist.get_world_size()), "backend": str(dist.get_backend()),
+                    "cells_owned": int(nc), "cells_with_halo": int(nloc), "halo_fraction": float(nloc - nc) / max(float(nloc), 1.0),
+                    "phases_ms": {k: float(st[k]) for k in ("topology_ms", "symbolic_ms", "node_ms", "face_ms", "assemble_ms",
+                                                            "solve_ms", "discretize_ms", "amg_setup_ms") if k in st},
+                    "kept": {"csr_patterns": int(st.get("symbolic_reused", 0)), "spmv_windows": int(st.get("win_reused", 0)),
+                             "amg_aggregate_maps": int(st.get("amg_maps_reused", 0))},
+                    "amg": {"levels": int(st.get("amg_levels", 0)), "coarsest_rows": int(st.get("amg_coarsest_rows", 0)),
+                            "operator_complexity": float(st.get("amg_operator_complexity", 0.0))},
+                    "launches": {"krylov_loop": int(st.get("solve_launches", 0)), "amg_setup": int(st.get("amg_setup_launches", 0))},
+                    "step_ms_by_this_ranks_clock": [round(t, 2) for t, _ in each[:32]],
+                    "iterations": [i for _, i in each[:32]],
+                    "transport": (info.get("transport") if isinstance(info, dict) else None),
+                    "halo_bytes_per_exchange": (info.get("halo_bytes_per_exchange") if isinstance(info, dict) else None),
+                    "overlap_interior_boundary": os.environ.get("PFV_SHARD_OVERLAP", "0"),
+                }
+                per_rank = [None] * world
+                dist.all_gather_object(per_rank, mine)
+            except Exception as e:  # (diagnostics only: never costs the line)
+                per_rank = [{"error": repr(e)}]
 
     if rank == 0:
         res_true = None
         try:
-            if world == 1 and not args.force_sharded:
+            if args.full and world == 1 and not args.force_sharded:
                 b = ctx.rhs()
                 xh = x if isinstance(x, np.ndarray) else x.cpu().numpy()
                 res_true = float(np.linalg.norm(b - ctx.spmv(pa._lib.MAT_SYSTEM, xh)) / np.linalg.norm(b))
@@ -1243,7 +1304,7 @@ def main():
             "metric": "cells/sec MPFA assemble+solve, 3D unstructured grid",
             "value": value, "unit": "cells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic", "prewarm_steps_untimed": prewarm,
+            "dtype": "f64", "data": "synthetic", "prewarm_steps_untimed": prewarm, "full": args.full,
             "config": {"workload": f"BASELINE configs[2] (the 2 M-cell grid the north_star target is quoted on): "
                                    f"3D simplex box, {nc} owned tetrahedra per GPU (n_side={args.n_side}), perturbed "
                                    "nodes, full-tensor anisotropic heterogeneous K, Dirichlet x-faces; every step: sub-cell "
@@ -1293,7 +1354,7 @@ def main():
                        "true_rel_residual": res_true,
                        # (N > 1: the residual the sharded loop stopped on -- |b - A x| over all ranks by the recursion,
                        # re-evaluated from the definition every check interval; no rank holds the whole system)
-                       "rel_residual_of_the_sharded_loop": (float(info["rel_residual"]) if res_true is None and isinstance(info, dict)
+                       "rel_residual_of_the_sharded_loop": (float(info["rel_residual"]) if sh is not None and isinstance(info, dict)
                                                             and info.get("rel_residual") is not None else None),
                        "field_error": field,
                        "global_cells": ncells_total,
@@ -1303,9 +1364,6 @@ def main():
                        "layer of halo cells recomputed per cut), assembly "
                        "without collectives, BiCGStab with RCCL point-to-point halo exchange + fused all-reduces; "
                        "AMG: per level and visit 2 point-to-point halo exchanges, one all-gather at the gathered level"},
-            "roofline": roofline, "roofline_kernels": kernels[1:], "kernel_ms_per_step": per_step_ms,
-            "hbm_triad_measured_GBs": triad_gbs, "hbm_read_stream_measured_GBs": read_gbs,
-            "ms_per_step_cold": (cold or {}).get("ms_per_step_cold"), "cold_step": cold,
             "each_timed_step": {"ms": [round(t, 2) for t, _ in each[:64]], "iterations": [i for _, i in each[:64]],
                                 "note": "rank 0; the permeability field differs from step to step, and so do the iteration "
                                         "count and the sizes of everything the strength filter produces"},
@@ -1314,12 +1372,18 @@ def main():
             "launches_per_iteration": (st.get("solve_launches", 0) / max(its, 1)) if its else None,
             "solve_launches": {"krylov_loop": int(st.get("solve_launches", 0)), "amg_setup": int(st.get("amg_setup_launches", 0)),
                                "note": "this library's kernel dispatches of the last timed solve (rocPRIM primitives, memsets and copies not counted)"},
-            "whole_grid_check": whole_grid,
-            "per_rank": per_rank,
-            "assembly": assembly, "operator_api": opapi, "cpu_baseline": cpu, "cpu_baseline_headline_grid": cpu_headline,
-            "config_c2": c2, "config_c4": c4,
-            "config_c5": (config_c5(args.c5) if (world == 1 and args.n_side == 69 and (args.c5 or not args.no_extra_configs)) else None),
         }
+        if args.full:
+            line.update({
+                "roofline": roofline, "roofline_kernels": kernels[1:], "kernel_ms_per_step": per_step_ms,
+                "hbm_triad_measured_GBs": triad_gbs, "hbm_read_stream_measured_GBs": read_gbs,
+                "ms_per_step_cold": (cold or {}).get("ms_per_step_cold"), "cold_step": cold,
+                "whole_grid_check": whole_grid,
+                "per_rank": per_rank,
+                "assembly": assembly, "operator_api": opapi, "cpu_baseline": cpu, "cpu_baseline_headline_grid": cpu_headline,
+                "config_c2": c2, "config_c4": c4,
+                "config_c5": (config_c5(args.c5) if (world == 1 and args.n_side == 69 and (args.c5 or not args.no_extra_configs)) else None),
+            })
         if args.phases:
             print(json.dumps(st, indent=1), file=sys.stderr)
         record_out.write(json.dumps(line) + "\n")

@@ -12,7 +12,7 @@ if [ "$1" == "--tests" ]; then
 fi
 for v in "$@"; do
   n="${v%%:*}"; e="${v#*:}"
-  env $e timeout 300 python bench.py --no-cpu-baseline --no-extra-configs > $O/ab_$n.json 2> $O/ab_$n.err
+  env $e timeout 300 python bench.py --full --no-cpu-baseline --no-extra-configs > $O/ab_$n.json 2> $O/ab_$n.err
   python - "$n" <<'PY'
 import json, sys
 n = sys.argv[1]

@@ -6,7 +6,7 @@ O=gpurun_out
 mkdir -p $O
 for v in "$@"; do
   n="${v%%:*}"; e="${v#*:}"
-  env $e timeout 400 python bench.py --no-cpu-baseline > $O/abc_$n.json 2> $O/abc_$n.err
+  env $e timeout 400 python bench.py --full --no-cpu-baseline > $O/abc_$n.json 2> $O/abc_$n.err
   python - "$n" <<'PY'
 import json, sys
 n = sys.argv[1]

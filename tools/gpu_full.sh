@@ -10,7 +10,7 @@ stamp() { echo "[$(( $(date +%s) - t0 )) s] $*" >> $O/timeline.log; }
 timeout 900 python -m pytest tests -m gpu -q --timeout 400 --durations=8 > $O/pytest_gpu.log 2>&1
 echo "pytest exit $?" >> $O/pytest_gpu.log
 stamp pytest
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 stamp bench_default
 for c in "$@"; do
   bash -c "$c"

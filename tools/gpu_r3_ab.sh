@@ -18,7 +18,7 @@ STEPS=5
 if [ "$1" == "--steps" ]; then STEPS=$2; shift; shift; fi
 for v in "$@"; do
   n="${v%%:*}"; e="${v#*:}"
-  env $e timeout 300 python bench.py --no-cpu-baseline --no-extra-configs --steps $STEPS > $O/ab_$n.json 2> $O/ab_$n.err
+  env $e timeout 300 python bench.py --full --no-cpu-baseline --no-extra-configs --steps $STEPS > $O/ab_$n.json 2> $O/ab_$n.err
   stamp "$n"
   python - "$O" "$n" <<'PY'
 import json, sys

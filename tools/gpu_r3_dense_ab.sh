@@ -3,7 +3,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/r3u; mkdir -p $O
 for v in lds1:PFV_AMG_DENSE_LDS=1 lds0:PFV_AMG_DENSE_LDS=0 lds1b:PFV_AMG_DENSE_LDS=1; do
   n="${v%%:*}"; e="${v#*:}"
-  env $e timeout 400 python bench.py --no-cpu-baseline --steps 6 > $O/ab_$n.json 2> $O/ab_$n.err
+  env $e timeout 400 python bench.py --full --no-cpu-baseline --steps 6 > $O/ab_$n.json 2> $O/ab_$n.err
   python - "$O" "$n" <<'PY'
 import json, sys
 o, n = sys.argv[1], sys.argv[2]

@@ -17,7 +17,7 @@ cp gpurun_out/pmc_traffic.json profiles/r03_pmc_traffic.json 2>/dev/null   # (so
 stamp pmc
 bash tools/gpu_r3_trace.sh $1 final: > $O/trace_console.log 2>&1
 stamp trace
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 stamp bench_default
 # device fuzz against PorePy itself (byte-compiled archive): plain cases, then the special ones (conditions per sub-face,
 # partial discretization, tilted 2-D grids, TPFA, continuity points per sub-face)

@@ -8,18 +8,18 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/${1:-r3s}
 mkdir -p $O
 for pc in amg amg_block; do
-  timeout 300 python bench.py --force-sharded --precond $pc --no-cpu-baseline --no-extra-configs > $O/sharded_rccl_1rank_$pc.json 2> $O/sharded_rccl_1rank_$pc.err
+  timeout 300 python bench.py --full --force-sharded --precond $pc --no-cpu-baseline --no-extra-configs > $O/sharded_rccl_1rank_$pc.json 2> $O/sharded_rccl_1rank_$pc.err
   echo "1-rank native RCCL $pc exit $?"; tail -c 200 $O/sharded_rccl_1rank_$pc.err
 done
 for ns in 40 69; do
   for pc in amg amg_block; do
     PFV_BENCH_SHARE_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-      --master-port 29517 bench.py --gpus 2 --n-side $ns --precond $pc --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs \
+      --master-port 29517 bench.py --full --gpus 2 --n-side $ns --precond $pc --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs \
       > $O/gloo_2rank_n${ns}_$pc.json 2> $O/gloo_2rank_n${ns}_$pc.err
     echo "2-rank gloo n_side $ns $pc exit $?"; tail -c 300 $O/gloo_2rank_n${ns}_$pc.err | tail -2
   done
 done
-python bench.py --n-side 40 --no-cpu-baseline --no-extra-configs --steps 5 --warmup 2 > $O/single_n40.json 2> $O/single_n40.err
+python bench.py --full --n-side 40 --no-cpu-baseline --no-extra-configs --steps 5 --warmup 2 > $O/single_n40.json 2> $O/single_n40.err
 python - "$O" <<'PY'
 import json, sys, glob, os
 for f in sorted(glob.glob(sys.argv[1] + "/*.json")):

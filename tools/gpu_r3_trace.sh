@@ -8,14 +8,14 @@ cd /tmp
 for v in "$@"; do
   n="${v%%:*}"; e="${v#*:}"
   rm -rf $O/tr_$n
-  env $e timeout 400 rocprofv3 --kernel-trace --stats -d $O/tr_$n -o t --output-format csv -- python $R/bench.py --no-cpu-baseline --no-extra-configs --steps 3 --warmup 1 > $O/traced_$n.json 2> $O/trace_$n.log
+  env $e timeout 400 rocprofv3 --kernel-trace --stats -d $O/tr_$n -o t --output-format csv -- python $R/bench.py --full --no-cpu-baseline --no-extra-configs --steps 3 --warmup 1 > $O/traced_$n.json 2> $O/trace_$n.log
   python - "$O" "$n" <<'PY'
 import csv, os, re, sys, glob
 o, n = sys.argv[1], sys.argv[2]
 p = glob.glob(os.path.join(o, f"tr_{n}", "**", "t_kernel_stats.csv"), recursive=True)[0]
 rows = list(csv.DictReader(open(p)))
 tot = sum(float(r["TotalDurationNs"]) for r in rows)
-out = [f"rocprofv3 --kernel-trace --stats -- [{n}] python bench.py --no-cpu-baseline --no-extra-configs --steps 3 --warmup 1",
+out = [f"rocprofv3 --kernel-trace --stats -- [{n}] python bench.py --full --no-cpu-baseline --no-extra-configs --steps 3 --warmup 1",
        f"total kernel time {tot/1e6:.2f} ms over {sum(int(r['Calls']) for r in rows)} dispatches (pre-warm + warmup + 3 timed steps + kernel timing loops)",
        f"{'total_ms':>10} {'pct':>6} {'calls':>7} {'avg_us':>10} {'min_us':>9} {'max_us':>10}  kernel"]
 small = [0, 0.0]

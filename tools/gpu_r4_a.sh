@@ -39,7 +39,7 @@ PY
 cat $O/pmc_face.txt
 rm -rf $O/pmc_*/
 stamp pmc
-timeout 400 python bench.py --no-cpu-baseline --no-extra-configs --steps 5 > $O/bench_base.json 2> $O/bench_base.err
+timeout 400 python bench.py --full --no-cpu-baseline --no-extra-configs --steps 5 > $O/bench_base.json 2> $O/bench_base.err
 python - "$O" <<'PY'
 import json, sys
 o = sys.argv[1]

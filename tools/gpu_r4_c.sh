@@ -12,7 +12,7 @@ fi
 STEPS=5
 for v in "$@"; do
   n="${v%%:*}"; e="${v#*:}"
-  env $e timeout 400 python bench.py --no-cpu-baseline --no-extra-configs --steps $STEPS > $O/ab_$n.json 2> $O/ab_$n.err
+  env $e timeout 400 python bench.py --full --no-cpu-baseline --no-extra-configs --steps $STEPS > $O/ab_$n.json 2> $O/ab_$n.err
   python - "$O" "$n" <<'PY'
 import json, sys
 o, n = sys.argv[1], sys.argv[2]

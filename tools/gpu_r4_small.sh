@@ -3,10 +3,10 @@
 export TMPDIR=/tmp
 R="${GRAFT_REPO_ROOT:-/root/repo}"; cd "$R"
 O=gpurun_out/r4small; mkdir -p $O
-echo "# bench.py --no-cpu-baseline --no-extra-configs --steps 5 --n-side N [--force-sharded]: shares of the headline grid on one MI355X (round 4, final tree)" > $O/small_steps.log
+echo "# bench.py --full --no-cpu-baseline --no-extra-configs --steps 5 --n-side N [--force-sharded]: shares of the headline grid on one MI355X (round 4, final tree)" > $O/small_steps.log
 for v in "n35:--n-side 35" "n35_sharded:--n-side 35 --force-sharded" "n44:--n-side 44" "n55:--n-side 55" "n69_sharded:--force-sharded"; do
   n="${v%%:*}"; a="${v#*:}"
-  timeout 400 python bench.py --no-cpu-baseline --no-extra-configs --steps 5 $a > $O/$n.json 2> $O/$n.err
+  timeout 400 python bench.py --full --no-cpu-baseline --no-extra-configs --steps 5 $a > $O/$n.json 2> $O/$n.err
   python - "$O" "$n" >> $O/small_steps.log <<'PY'
 import json, sys
 o, n = sys.argv[1], sys.argv[2]

@@ -11,8 +11,8 @@ t0=$(date +%s)
 stamp() { echo "[$(( $(date +%s) - t0 )) s] $*" >> $O/timeline.log; }
 timeout 900 python -m pytest tests -m gpu -q -x --timeout 800 -k "whole_headline or config_c3_all_four or batch_matches_single or device_build_loaded" > $O/pytest_subset.log 2>&1
 echo "pytest exit $?" >> $O/pytest_subset.log; tail -5 $O/pytest_subset.log; stamp tests
-timeout 420 python bench.py --no-cpu-baseline --no-extra-configs --no-whole-grid-check --steps 10 > $O/bench_moving.json 2> $O/bench_moving.err; stamp bench_moving
-timeout 300 python bench.py --no-cpu-baseline --no-extra-configs --no-whole-grid-check --steps 10 --fixed-k > $O/bench_fixed.json 2> $O/bench_fixed.err; stamp bench_fixed
+timeout 420 python bench.py --full --no-cpu-baseline --no-extra-configs --no-whole-grid-check --steps 10 > $O/bench_moving.json 2> $O/bench_moving.err; stamp bench_moving
+timeout 300 python bench.py --full --no-cpu-baseline --no-extra-configs --no-whole-grid-check --steps 10 --fixed-k > $O/bench_fixed.json 2> $O/bench_fixed.err; stamp bench_fixed
 python - "$O" <<'PY'
 import json, sys
 o = sys.argv[1]

@@ -12,7 +12,7 @@ PFV_NODE_GJ=5 timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q -x
 echo "pytest exit $?" >> $O/pytest_gj5.log; tail -4 $O/pytest_gj5.log; stamp tests
 run() {  # tag, env...
   tag=$1; shift
-  env "$@" timeout 300 python bench.py --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold --steps 6 > $O/bench_$tag.json 2> $O/bench_$tag.err
+  env "$@" timeout 300 python bench.py --full --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold --steps 6 > $O/bench_$tag.json 2> $O/bench_$tag.err
   python - "$O" "$tag" <<'PY'
 import json, sys
 o, tag = sys.argv[1], sys.argv[2]

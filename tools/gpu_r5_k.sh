@@ -7,7 +7,7 @@ O=gpurun_out/r5k
 mkdir -p $O
 run() {  # tag, args, env...
   tag=$1; shift; args=$1; shift
-  env "$@" timeout 300 python bench.py --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold $args > $O/bench_$tag.json 2> $O/bench_$tag.err
+  env "$@" timeout 300 python bench.py --full --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold $args > $O/bench_$tag.json 2> $O/bench_$tag.err
   python - "$O" "$tag" <<'PY'
 import json, sys
 o, tag = sys.argv[1], sys.argv[2]

@@ -7,7 +7,7 @@ O=gpurun_out/r5m
 mkdir -p $O
 for v in "s3:--steps 3 --warmup 1" "s20:--steps 20 --warmup 1" "s20b:--steps 20 --warmup 1"; do
   tag="${v%%:*}"; a="${v#*:}"
-  timeout 300 python bench.py --no-cpu-baseline --no-extra-configs --no-whole-grid-check $a > $O/bench_$tag.json 2> $O/bench_$tag.err
+  timeout 300 python bench.py --full --no-cpu-baseline --no-extra-configs --no-whole-grid-check $a > $O/bench_$tag.json 2> $O/bench_$tag.err
   python - "$O" "$tag" <<'PY'
 import json, sys
 o, tag = sys.argv[1], sys.argv[2]

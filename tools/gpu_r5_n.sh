@@ -7,7 +7,7 @@ O=gpurun_out/r5n
 mkdir -p $O
 run() {
   tag=$1; shift
-  env "$@" timeout 300 python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-extra-configs --no-whole-grid-check > $O/$tag.json 2> $O/$tag.err
+  env "$@" timeout 300 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-extra-configs --no-whole-grid-check > $O/$tag.json 2> $O/$tag.err
   python - "$O/$tag.json" "$tag" <<'PY'
 import json, sys
 try:
@@ -21,7 +21,7 @@ run direct PFV_AMG_GALERKIN_DIRECT=1
 run passes PFV_AMG_GALERKIN_DIRECT=0
 run members_rebuilt PFV_AMG_MEMBERS_REUSE=0
 run direct2 PFV_AMG_GALERKIN_DIRECT=1
-timeout 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-whole-grid-check --no-cold > $O/with_configs.json 2> $O/with_configs.err
+timeout 300 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-whole-grid-check --no-cold > $O/with_configs.json 2> $O/with_configs.err
 python - "$O/with_configs.json" <<'PY'
 import json, sys
 try:
@@ -31,7 +31,7 @@ except Exception as e:
     print("with configs FAILED", e, open(sys.argv[1].replace('.json', '.err')).read()[-800:])
 PY
 for mr in 1; do
-  PFV_AMG_MEMBERS_REUSE=$mr timeout 300 python bench.py --force-sharded --steps 6 --warmup 3 --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold > $O/sharded_$mr.json 2> $O/sharded_$mr.err
+  PFV_AMG_MEMBERS_REUSE=$mr timeout 300 python bench.py --full --force-sharded --steps 6 --warmup 3 --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold > $O/sharded_$mr.json 2> $O/sharded_$mr.err
   python - "$O/sharded_$mr.json" "sharded members_reuse=$mr" <<'PY'
 import json, sys
 try:

@@ -7,7 +7,7 @@ O=gpurun_out/r5o
 mkdir -p $O
 run() {
   tag=$1; shift
-  env "$@" timeout 300 python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold > $O/$tag.json 2> $O/$tag.err
+  env "$@" timeout 300 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold > $O/$tag.json 2> $O/$tag.err
   python - "$O/$tag.json" "$tag" <<'PY'
 import json, sys
 try:

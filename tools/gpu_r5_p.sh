@@ -7,7 +7,7 @@ O=gpurun_out/r5p
 mkdir -p $O
 run() {
   tag=$1; shift
-  env "$@" timeout 300 python bench.py --force-sharded --steps 8 --warmup 3 --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold > $O/$tag.json 2> $O/$tag.err
+  env "$@" timeout 300 python bench.py --full --force-sharded --steps 8 --warmup 3 --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold > $O/$tag.json 2> $O/$tag.err
   python - "$O/$tag.json" "$tag" <<'PY'
 import json, sys
 try:
@@ -23,7 +23,7 @@ run sharded_no_child PFV_AMG_REUSE_CHILD=0
 run sharded_no_win0 PFV_SHARD_WIN0=0
 run sharded_old PFV_AMG_REUSE_CHILD=0 PFV_SHARD_WIN0=0
 run sharded_new2 PFV_X=0
-timeout 300 python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold > $O/single.json 2> $O/single.err
+timeout 300 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold > $O/single.json 2> $O/single.err
 python - "$O/single.json" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -6,7 +6,7 @@ O=$R/gpurun_out/r5shard
 mkdir -p $O
 cd $R
 rm -rf /tmp/r5s
-timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/r5s -o t --output-format csv -- python bench.py --force-sharded --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold > $O/traced.json 2> $O/traced.err
+timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/r5s -o t --output-format csv -- python bench.py --full --force-sharded --steps 2 --warmup 1 --no-cpu-baseline --no-extra-configs --no-whole-grid-check --no-cold > $O/traced.json 2> $O/traced.err
 python tools/step_timeline.py /tmp/r5s 0 > $O/timeline_full.txt 2>&1
 python - "$O" <<'PY'
 import sys

@@ -10,7 +10,7 @@ t0=$(date +%s)
 stamp() { echo "[$(( $(date +%s) - t0 )) s] $*" >> $O/timeline.log; }
 timeout 1500 python -m pytest tests -m gpu -q --timeout 900 > $O/pytest_gpu.log 2>&1
 echo "pytest exit $?" >> $O/pytest_gpu.log; tail -8 $O/pytest_gpu.log; stamp pytest
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; stamp bench
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; stamp bench
 python - "$O" <<'PY'
 import json, sys
 o = sys.argv[1]
@@ -24,7 +24,7 @@ except Exception as e:
     print("bench FAILED", e, open(f"{o}/bench_default.err").read()[-1500:])
 PY
 for lab in 0 1; do
-  PFV_LAB_NODE_FACE_OVERLAP=$lab timeout 600 python bench.py --steps 6 --warmup 3 --no-cold --no-cpu-baseline --no-whole-grid-check --no-extra-configs > $O/bench_lab$lab.json 2> $O/bench_lab$lab.err
+  PFV_LAB_NODE_FACE_OVERLAP=$lab timeout 600 python bench.py --full --steps 6 --warmup 3 --no-cold --no-cpu-baseline --no-whole-grid-check --no-extra-configs > $O/bench_lab$lab.json 2> $O/bench_lab$lab.err
   python - "$O" "$lab" <<'PY'
 import json, sys
 o, lab = sys.argv[1], sys.argv[2]

@@ -12,7 +12,7 @@ timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q --timeout 600 -k
 echo "pytest exit $?" >> $O/pytest_subset.log; tail -6 $O/pytest_subset.log; stamp pytest
 for v in "default:" "pipe0:PFV_PIPE=0" "chunks4:PFV_PIPE_CHUNKS=4" "chunks16:PFV_PIPE_CHUNKS=16" "chunks30:PFV_PIPE_CHUNKS=30"; do
   name=${v%%:*}; envs=${v#*:}
-  env $envs timeout 600 python bench.py --steps 8 --warmup 3 --no-cold --no-cpu-baseline --no-whole-grid-check --no-extra-configs > $O/bench_$name.json 2> $O/bench_$name.err
+  env $envs timeout 600 python bench.py --full --steps 8 --warmup 3 --no-cold --no-cpu-baseline --no-whole-grid-check --no-extra-configs > $O/bench_$name.json 2> $O/bench_$name.err
   python - "$O" "$name" <<'PY'
 import json, sys
 o, name = sys.argv[1], sys.argv[2]

@@ -13,7 +13,7 @@ echo "pytest exit $?" >> $O/pytest_subset.log; tail -4 $O/pytest_subset.log; sta
 timeout 1500 python tools/big_handle_check.py 110 24 > $O/big_handle_110.json 2> $O/big_handle_110.err
 tail -c 1500 $O/big_handle_110.json; tail -c 600 $O/big_handle_110.err; stamp big_handle
 for n in 104 110; do
-  timeout 1200 python bench.py --n-side $n --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs --no-whole-grid-check > $O/bench_$n.json 2> $O/bench_$n.err
+  timeout 1200 python bench.py --full --n-side $n --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs --no-whole-grid-check > $O/bench_$n.json 2> $O/bench_$n.err
   python - "$O" "$n" <<'PY'
 import json, sys
 o, n = sys.argv[1], sys.argv[2]

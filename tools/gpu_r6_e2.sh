@@ -23,11 +23,11 @@ except Exception as e:
     print(p, "FAILED", e, open(p.replace(".json", ".err")).read()[-1500:])
 PY
 }
-timeout 900 python bench.py --force-sharded --steps 4 --warmup 2 --no-cold --no-cpu-baseline --no-whole-grid-check --no-extra-configs > $O/sharded_one_rank_rccl.json 2> $O/sharded_one_rank_rccl.err
+timeout 900 python bench.py --full --force-sharded --steps 4 --warmup 2 --no-cold --no-cpu-baseline --no-whole-grid-check --no-extra-configs > $O/sharded_one_rank_rccl.json 2> $O/sharded_one_rank_rccl.err
 show $O/sharded_one_rank_rccl.json
 for cfg in "2:weak:48" "2:strong:69"; do
   n=${cfg%%:*}; rest=${cfg#*:}; sc=${rest%%:*}; ns=${rest#*:}
   PFV_BENCH_SHARE_GPU=1 timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n + ${#sc})) \
-      bench.py --gpus $n --scaling $sc --n-side $ns --steps 3 --warmup 1 --no-cold --no-cpu-baseline --no-whole-grid-check --no-extra-configs > $O/share_${n}_${sc}.json 2> $O/share_${n}_${sc}.err
+      bench.py --full --gpus $n --scaling $sc --n-side $ns --steps 3 --warmup 1 --no-cold --no-cpu-baseline --no-whole-grid-check --no-extra-configs > $O/share_${n}_${sc}.json 2> $O/share_${n}_${sc}.err
   show $O/share_${n}_${sc}.json
 done

@@ -9,7 +9,7 @@ t0=$(date +%s)
 stamp() { echo "[$(( $(date +%s) - t0 )) s] $*" >> $O/timeline.log; }
 timeout 1500 python -m pytest tests -m gpu -q --timeout 900 > $O/pytest_gpu.log 2>&1
 echo "pytest exit $?" >> $O/pytest_gpu.log; tail -5 $O/pytest_gpu.log; stamp pytest
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; stamp bench
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; stamp bench
 python - "$O" <<'PY'
 import json, sys
 o = sys.argv[1]
@@ -45,7 +45,7 @@ if [ -n "$ENVF" ] && [ -z "${SKIP_FUZZ:-}" ]; then
 fi
 stamp fuzz
 # the command the driver runs at round end
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
 python - "$O" <<'PY'
 import json, sys
 o = sys.argv[1]

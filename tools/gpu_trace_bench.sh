@@ -6,14 +6,14 @@ O=$R/gpurun_out
 mkdir -p $O
 cd /tmp
 rm -rf $O/btrace
-timeout 400 rocprofv3 --kernel-trace --stats -d $O/btrace -o t --output-format csv -- python $R/bench.py --no-cpu-baseline --no-extra-configs --steps 3 --warmup 1 > $O/bench_traced.json 2> $O/btrace.log
+timeout 400 rocprofv3 --kernel-trace --stats -d $O/btrace -o t --output-format csv -- python $R/bench.py --full --no-cpu-baseline --no-extra-configs --steps 3 --warmup 1 > $O/bench_traced.json 2> $O/btrace.log
 python - <<'PY'
 import csv, os, re
 root = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
 p = os.path.join(root, "gpurun_out/btrace/t_kernel_stats.csv")
 rows = list(csv.DictReader(open(p)))
 tot = sum(float(r["TotalDurationNs"]) for r in rows)
-out = [f"rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-extra-configs --steps 3 --warmup 1",
+out = [f"rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-extra-configs --steps 3 --warmup 1",
        f"total kernel time {tot/1e6:.2f} ms over {sum(int(r['Calls']) for r in rows)} dispatches (pre-warm + warmup + 3 timed steps + kernel timing loops)",
        f"{'total_ms':>10} {'pct':>6} {'calls':>7} {'avg_us':>10} {'min_us':>9} {'max_us':>10}  kernel"]
 small = [0, 0.0]

@@ -7,7 +7,7 @@ O=gpurun_out/r6lab6
 mkdir -p $O
 run() {
   local name=$1; shift
-  env "$@" timeout 900 python bench.py --no-cpu-baseline --no-whole-grid-check --no-cold --steps 6 --warmup 2 \
+  env "$@" timeout 900 python bench.py --full --no-cpu-baseline --no-whole-grid-check --no-cold --steps 6 --warmup 2 \
     > $O/$name.json 2> $O/$name.err
   python - "$O/$name.json" "$name" <<'PY'
 import json, sys

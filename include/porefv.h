@@ -70,7 +70,9 @@ enum { PFV_SOLVE_CG = 0, PFV_SOLVE_BICGSTAB = 1, PFV_SOLVE_GMRES = 2 };
 /* preconditioners of pfv_solve: Jacobi (default), or one V(1,1) cycle of a plain-aggregation
  * algebraic multigrid built on the device from the assembled matrix (pairwise matching on the
  * strength graph, piecewise-constant prolongation, Galerkin coarse matrices) */
-enum { PFV_PRECOND_JACOBI = 0, PFV_PRECOND_AMG = 1, PFV_PRECOND_BLOCK = 2 };
+enum { PFV_PRECOND_JACOBI = 0, PFV_PRECOND_AMG = 1, PFV_PRECOND_BLOCK = 2,
+       PFV_PRECOND_AMG_NNS = 3 /* aggregation AMG whose tentative prolongator carries a near-null space
+                                  (pfv_set_near_null_space; rigid-body modes for elasticity) */ };
 
 /* flags for pfv_mpfa_discretize */
 enum {
@@ -144,6 +146,8 @@ typedef struct {
   int64_t pipeline_runs;          /* > 0: the last pfv_mpfa_discretize ran the interaction-region kernel in this many runs on the
                                      second stream with the face kernel following run by run on the first (node_ms is then the
                                      span of the whole pipeline, face_ms what came after it); 0: one after the other */
+  int64_t amg_nns_modes;          /* modes per aggregate of the last PFV_PRECOND_AMG_NNS setup (0: none); that setup also
+                                     fills amg_setup_ms, amg_operator_complexity, amg_levels and amg_coarsest_rows */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -338,6 +342,23 @@ pfv_status pfv_set_vectors_on_device(pfv_ctx* h, int on);
 
 /* Select the preconditioner of the following pfv_solve calls on this handle. */
 pfv_status pfv_set_preconditioner(pfv_ctx* h, int kind);
+
+/* Near-null space of PFV_PRECOND_AMG_NNS for the active system: B is a host array of n x k values, column-major, in
+ * the caller's numbering of the n unknowns (bs per cell, cell-major / component-minor).  B == NULL: the rigid-body
+ * modes of the handle's grid, built on the device from its cell centres -- 2-D: 2 translations + the rotation (k = 3),
+ * 3-D: 3 translations + 3 rotations (k = 6); only for the assembled mechanics system (bs = nd).  k = 0 clears the modes.
+ * k > 8: PFV_ERR_UNSUPPORTED.  The modes follow the renumbering pfv_solve applies to grid systems.  The hierarchy of
+ * PFV_PRECOND_AMG_NNS is kept apart from the one of PFV_PRECOND_AMG; it has no sharded form (pfv_amg_setup,
+ * pfv_amg_setup_sharded and pfv_solve_sharded with it selected return PFV_ERR_UNSUPPORTED). */
+pfv_status pfv_set_near_null_space(pfv_ctx* h, int bs, int k, const double* B);
+
+/* Introspection of the PFV_PRECOND_AMG_NNS hierarchy built by the last pfv_solve (tests): for level `level`,
+ * info[6] = {rows n_l, block size bs_l, modes k, aggregates (0 on the coarsest level), nnz of A_l, levels}; then, each
+ * optional (NULL: skipped): agg [n_l / bs_l] cell -> aggregate, P [n_l][k] tentative prolongator (row-major),
+ * B [n_l][k] the level's near-null space, Bc [aggregates * k][k] the next level's (R of the QR per aggregate),
+ * A_l as CSR (indptr [n_l + 1], indices and val [nnz], FP64).  Level 0 is in the numbering the solve worked in. */
+pfv_status pfv_amg_nns_level(pfv_ctx* h, int level, int64_t* info, int32_t* agg, double* P, double* B, double* Bc,
+                             int32_t* indptr, int32_t* indices, double* val);
 
 /* Block preconditioner (PFV_PRECOND_BLOCK) for the coupled Jacobians of mixed-dimensional / multi-physics models
  * that the reference solves directly (models/solution_strategy.py:830-884; mortar coupling

@@ -10,7 +10,7 @@ from ._lib import Context, PorefvError
 from .grid import (CartGrid, Grid, StructuredTetrahedralGrid, StructuredTriangleGrid, TetrahedralGrid, grid_from_raw,
                    grid_to_raw, perturb_interior_nodes)
 from .mpfa import Mpfa, as_porepy_discretization, determine_eta
-from .mpsa import Mpsa, as_porepy_mpsa
+from .mpsa import Mpsa, as_porepy_mpsa, rigid_body_modes
 from .biot import Biot, as_porepy_biot
 from .partial import active_indices
 from .solvers import DeviceAssembly, HipLinearSolver, solve_block_system, solve_csr
@@ -24,7 +24,7 @@ from .params import (DISCRETIZATION_MATRICES, PARAMETERS, BoundaryCondition, Bou
 __all__ = [
     "Context", "PorefvError", "Grid", "CartGrid", "StructuredTriangleGrid",
     "StructuredTetrahedralGrid", "TetrahedralGrid", "perturb_interior_nodes", "grid_to_raw", "grid_from_raw", "Mpfa",
-    "as_porepy_discretization", "determine_eta", "SecondOrderTensor", "BoundaryCondition", "Mpsa",
+    "as_porepy_discretization", "determine_eta", "SecondOrderTensor", "BoundaryCondition", "Mpsa", "rigid_body_modes",
     "FourthOrderTensor", "BoundaryConditionVectorial",
     "initialize_data", "bc_to_raw", "bc_flags", "PARAMETERS", "DISCRETIZATION_MATRICES", "_lib", "active_indices", "HipLinearSolver", "solve_csr", "Tpfa", "DifferentiableTpfa", "as_porepy_ad_tpfa_flux", "Biot", "as_porepy_mpsa", "as_porepy_biot", "DeviceCsr", "block_diag", "bmat", "merged_matrix", "vstack", "ad", "solve_block_system", "md_sharding", "DeviceAssembly",
 ]

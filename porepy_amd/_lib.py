@@ -22,6 +22,7 @@ MAT_USER_SYSTEM = 12
 MAT_FLUX_JACOBIAN = 13
 BC_DIR, BC_NEU, BC_ROB, BC_INTERNAL = 1, 2, 4, 8
 SOLVE_CG, SOLVE_BICGSTAB, SOLVE_GMRES = 0, 1, 2
+PRECOND_JACOBI, PRECOND_AMG, PRECOND_BLOCK, PRECOND_AMG_NNS = 0, 1, 2, 3
 DISCR_REBUILD_TOPOLOGY, DISCR_SKIP_VECTOR_SOURCE = 1, 2
 
 STATUS_NAMES = {
@@ -43,7 +44,7 @@ EXPORTS = [
     "pfv_rccl_unique_id", "pfv_rccl_comm_create", "pfv_rccl_set_halo_plan", "pfv_rccl_hooks", "pfv_rccl_stats",
     "pfv_rccl_last_error", "pfv_rccl_comm_destroy", "pfv_mpfa_ad_flux_system", "pfv_host_alloc", "pfv_host_free",
     "pfv_mpsa_set_subface_eta", "pfv_mpsa_set_reconstruction_eta", "pfv_mpsa_set_reconstruction_eta_subface", "pfv_get_stats_n", "pfv_set_block_preconditioner",
-    "pfv_mpfa_set_permeability",
+    "pfv_mpfa_set_permeability", "pfv_set_near_null_space", "pfv_amg_nns_level",
 ]
 
 
@@ -66,7 +67,7 @@ class Stats(C.Structure):
                 ("solve_launches", C.c_int64), ("amg_setup_launches", C.c_int64), ("node_redo", C.c_int64),
                 ("symbolic_reused", C.c_int64), ("amg_stale_rematches", C.c_int64),
                 ("mpsa_contrast_regions", C.c_int64), ("mpsa_max_contrast", C.c_double), ("assemble_positions_kept", C.c_int64),
-                ("pipeline_runs", C.c_int64)]
+                ("pipeline_runs", C.c_int64), ("amg_nns_modes", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -213,6 +214,10 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_get_stats.restype = C.c_int
     lib.pfv_set_block_preconditioner.argtypes = [_h, C.c_int64, C.POINTER(C.c_int64), C.c_int]
     lib.pfv_set_block_preconditioner.restype = C.c_int
+    lib.pfv_set_near_null_space.argtypes = [_h, C.c_int, C.c_int, _dp]
+    lib.pfv_set_near_null_space.restype = C.c_int
+    lib.pfv_amg_nns_level.argtypes = [_h, C.c_int, _lp, _ip, _dp, _dp, _dp, _ip, _ip, _dp]
+    lib.pfv_amg_nns_level.restype = C.c_int
     lib.pfv_get_stats_n.argtypes = [_h, C.c_void_p, C.c_size_t]
     lib.pfv_get_stats_n.restype = C.c_int
     lib.pfv_time_kernel.argtypes = [_h, C.c_int, C.c_int, _dp]
@@ -921,7 +926,7 @@ class Context:
                      raise_on_fail=True, restart=0, precond="jacobi"):
         """``solve`` writing the solution into the device buffer at ``x_ptr`` (n doubles); returns info."""
         code = {"cg": SOLVE_CG, "bicgstab": SOLVE_BICGSTAB, "gmres": SOLVE_GMRES}[method]
-        self._check(self.lib.pfv_set_preconditioner(self._h, {"jacobi": 0, "amg": 1, "block": 2}[precond]))
+        self._select_precond(precond)
         info = SolveInfo()
         self._dev(True)
         try:
@@ -952,7 +957,7 @@ class Context:
         """Solve the system assembled last (flow: n = Nc; mechanics: pass n = nd * Nc).
         ``restart``: GMRES cycle length (0 = 30); ``precond``: "jacobi" or "amg"."""
         code = {"cg": SOLVE_CG, "bicgstab": SOLVE_BICGSTAB, "gmres": SOLVE_GMRES}[method]
-        self._check(self.lib.pfv_set_preconditioner(self._h, {"jacobi": 0, "amg": 1, "block": 2}[precond]))
+        self._select_precond(precond)
         x = pinned_pool(self.lib).empty(self._active_n(n), np.float64)
         x0a = None if x0 is None else _f64(x0)
         if x0a is not None and x0a.shape != x.shape:
@@ -982,6 +987,55 @@ class Context:
         bb = _f64(b)
         self._check(self.lib.pfv_set_system(self._h, n, _ptr(ip, _ip), _ptr(ix, _ip), _ptr(dv, _dp), _ptr(bb, _dp)))
         self._user_n = n
+
+    def _select_precond(self, precond: str):
+        """pfv_set_preconditioner.  "amg_rbm": aggregation AMG with the rigid-body modes of the grid (the assembled
+        mechanics system); "amg_nns": with the modes of the last ``set_near_null_space``."""
+        if precond == "amg_rbm":
+            if self.nd < 2 or self.active_size() != self.nd * self.nc:
+                raise ValueError('precond="amg_rbm" needs the assembled mechanics system of the grid on this handle')
+            self.set_near_null_space(None, self.nd)
+        kind = {"jacobi": PRECOND_JACOBI, "amg": PRECOND_AMG, "block": PRECOND_BLOCK, "amg_rbm": PRECOND_AMG_NNS,
+                "amg_nns": PRECOND_AMG_NNS}[precond]
+        self._check(self.lib.pfv_set_preconditioner(self._h, kind))
+
+    def set_near_null_space(self, B, block_size: int):
+        """Near-null space of ``precond="amg_nns"`` for the active system (pfv_set_near_null_space): ``B`` an n x k
+        array in the system's unknown order (k <= 8), or None for the rigid-body modes of the grid (mechanics system,
+        block_size = nd); k = 0 columns clear it."""
+        n = self.active_size()
+        if B is None:
+            k = 3 if self.nd == 2 else 6
+            self._check(self.lib.pfv_set_near_null_space(self._h, int(block_size), k, None))
+            return
+        Bf = np.asfortranarray(np.asarray(B, dtype=np.float64))
+        if Bf.ndim != 2 or Bf.shape[0] != n:
+            raise ValueError(f"the near-null space must be an array of {n} x k values")
+        flat = np.ascontiguousarray(Bf.ravel(order="F"))
+        self._check(self.lib.pfv_set_near_null_space(self._h, int(block_size), int(Bf.shape[1]), _ptr(flat, _dp)))
+
+    def amg_nns_level(self, level: int) -> dict:
+        """The PFV_PRECOND_AMG_NNS hierarchy of the last solve, level ``level`` (pfv_amg_nns_level): the aggregate
+        map, tentative prolongator P (n_l x k), the level's near-null space B (n_l x k), the next level's Bc
+        (aggregates * k x k) and the level matrix A (scipy CSR, FP64)."""
+        import scipy.sparse as sps
+
+        info = np.zeros(6, dtype=np.int64)
+        lp = info.ctypes.data_as(_lp)
+        self._check(self.lib.pfv_amg_nns_level(self._h, int(level), lp, None, None, None, None, None, None, None))
+        n, bs, k, nagg, nnz, nlev = (int(v) for v in info)
+        agg = np.empty(n // bs if nagg else 0, dtype=np.int32)
+        P = np.empty((n, k) if nagg else (0, k))
+        B = np.empty((n, k))
+        Bc = np.empty((nagg * k, k))
+        ip = np.empty(n + 1, dtype=np.int32)
+        ix = np.empty(nnz, dtype=np.int32)
+        v = np.empty(nnz)
+        self._check(self.lib.pfv_amg_nns_level(self._h, int(level), lp, _ptr(agg, _ip) if nagg else None,
+                                               _ptr(P, _dp) if nagg else None, _ptr(B, _dp),
+                                               _ptr(Bc, _dp) if nagg else None, _ptr(ip, _ip), _ptr(ix, _ip), _ptr(v, _dp)))
+        return {"n": n, "block_size": bs, "k": k, "aggregates": nagg, "levels": nlev, "agg": agg, "P": P, "B": B,
+                "Bc": Bc, "A": sps.csr_matrix((v, ix, ip), shape=(n, n))}
 
     def set_block_preconditioner(self, block_ptr, gauss_seidel: bool = True):
         """Contiguous blocks [block_ptr[k], block_ptr[k+1]) of the system of ``set_system``: the following solves with
@@ -1041,7 +1095,7 @@ class Context:
         enqueue work on the handle's stream.  ``work_ptr``: 2 n_local + 8 doubles of device memory (the
         addresses the hooks see point into it), ``x_ptr``: n_own doubles for the solution."""
         code = {"cg": SOLVE_CG, "bicgstab": SOLVE_BICGSTAB}[method]
-        self._check(self.lib.pfv_set_preconditioner(self._h, {"jacobi": 0, "amg": 1, "block": 2}[precond]))
+        self._select_precond(precond)
         failure = []
 
         def _halo(_user, d_x, _stream):

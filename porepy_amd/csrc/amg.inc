@@ -956,6 +956,92 @@ static void amg_safeguard_rows(pfv_ctx_impl& c, const CsrPattern& P, const doubl
 
 #include "amg_dist.inc"
 
+// Explicit inverse of a small matrix (the coarsest level, at most kAmgDenseMax rows) into `dense` (row-major n x n);
+// false when a pivot vanished (the caller then falls back to smoothing sweeps)
+static bool amg_dense_invert(pfv_ctx_impl& c, AmgWork& wk, const CsrPattern& P, const double* v, Buf<double>& dense) {
+  stream_t s = c.stream;
+  const int n = (int)P.nrows, ld = n | 1;
+  double* D = wk.dense_work.ensure((size_t)n * ld + 3 * (size_t)n);
+  double* rsc = D + (size_t)n * ld + 2 * (size_t)n;  // row scales
+  int32_t* ipiv = wk.piv.ensure(n + 4);
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  be_memset(D, 0, sizeof(double) * ((size_t)n * ld + 3 * (size_t)n), s);
+  // rows scaled to unit 1-norm before the inversion, (S D)^-1 S = D^-1: the pivot test of node_gj_lds is an
+  // absolute one made for such rows -- on the raw Galerkin matrix of a system in SI units (entries ~1e-15) every
+  // pivot counted as singular and the level silently fell back to Jacobi sweeps (solver behaviour depended on
+  // the units of the matrix)
+  parallel_for(s, n, PFV_LAMBDA(int64_t r) {
+    double sum = 0.0;
+    for (int e = ip[r]; e < ip[r + 1]; ++e) sum += fabs(v[e]);
+    const double sc = (sum > 0.0 && sum < 1.0e300) ? 1.0 / sum : 1.0;
+    rsc[r] = sc;
+    for (int e = ip[r]; e < ip[r + 1]; ++e) D[(size_t)r * ld + ix[e]] += v[e] * sc;
+  });
+  int32_t* st = c.status.ensure(16);
+  be_memset(st, 0, sizeof(int32_t), s);
+  // one workgroup on a matrix in global memory: every pivot step is a round of dependent accesses -- 1024 threads
+  // keep four times the loads of 256 in flight (the strength filter leaves coarsest levels of ~500 rows: 1.6 ms)
+  auto invert = PFV_LAMBDA(const WaveCtx& w) {
+    NodeLds G;
+    G.A = D;
+    G.rowk = D + (size_t)n * ld;
+    G.colk = G.rowk + n;
+    G.ipiv = ipiv;
+    node_gj_lds(w, G, n, ld, 0, st);
+  };
+  // the matrix staged in LDS when it fits (n <= ~136: 143 KB of the 160): a pivot step is then a few LDS round trips
+  // instead of a chain of dependent global accesses -- the 132-row coarsest level of the 2 M-cell system took 1.2 ms
+  // per step in global memory, a tenth of the whole step at 200 k cells
+  const size_t lds_need = sizeof(double) * ((size_t)n * ld + 2 * (size_t)n) + 64;
+  auto invert_lds = PFV_LAMBDA(const WaveCtx& w) {
+    double* A = reinterpret_cast<double*>(w.lds);
+    PFV_LANES(q, n * ld) A[q] = D[q];
+    w.sync();
+    NodeLds G;
+    G.A = A;
+    G.rowk = A + (size_t)n * ld;
+    G.colk = G.rowk + n;
+    G.ipiv = ipiv;
+    node_gj_lds(w, G, n, ld, 0, st);
+    w.sync();
+    PFV_LANES(q, n * ld) D[q] = A[q];
+    w.sync();
+  };
+  if (lds_need <= 150 * 1024 && env_int("PFV_AMG_DENSE_LDS", 1) != 0) {
+    if (n > 128) block_for<1024>(s, 1, lds_need, invert_lds);
+    else block_for<256>(s, 1, lds_need, invert_lds);
+  } else if (n > 128) block_for<1024>(s, 1, 0, invert);
+  else block_for<256>(s, 1, 0, invert);
+  if (read_scalar<int32_t>(s, st) == 0) {
+    double* inv = dense.ensure((size_t)n * n);
+    parallel_for(s, (int64_t)n * n, PFV_LAMBDA(int64_t q) {
+      const int64_t r = q / n, cc = q - r * n;
+      inv[q] = D[(size_t)r * ld + cc] * rsc[cc];
+    });
+    return true;
+  }
+  return false;
+}
+
+// x = inv b with the explicit inverse of amg_dense_invert (one wavefront per row, lane sums in lane order)
+static void amg_dense_apply(pfv_ctx_impl& c, const double* inv, int64_t n, const double* b, double* x) {
+  wave_for(c.stream, n, 64 * sizeof(double) + 16, PFV_LAMBDA(const WaveCtx& w) {
+    double* sh = reinterpret_cast<double*>(w.lds);
+    const int64_t r = w.item;
+    double a = 0.0;
+    PFV_LANES(j, (int)n) a += inv[r * n + j] * b[j];
+    sh[w.lane] = a;
+    w.sync();
+    if (w.lane0()) {
+      double sum = 0.0;
+      for (int j = 0; j < w.width; ++j) sum += sh[j];
+      x[r] = sum;
+    }
+    w.sync();
+  });
+}
+
 static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const double* val, int bs,
                       const double* diag, const WinCsr* win0) {
   stream_t s = c.stream;
@@ -1346,68 +1432,7 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
   if (D) {
     amg_build_global(c, amg, *D, Lc, *D->plan[amg.nlev - 1]);
   } else if (Lc.n <= kAmgDenseMax) {
-    const int n = (int)Lc.n, ld = n | 1;
-    double* D = wk.dense_work.ensure((size_t)n * ld + 3 * (size_t)n);
-    double* rsc = D + (size_t)n * ld + 2 * (size_t)n;  // row scales
-    int32_t* ipiv = wk.piv.ensure(n + 4);
-    const int32_t* ip = Lc.P->indptr;
-    const int32_t* ix = Lc.P->indices;
-    const double* v = Lc.val;
-    be_memset(D, 0, sizeof(double) * ((size_t)n * ld + 3 * (size_t)n), s);
-    // rows scaled to unit 1-norm before the inversion, (S D)^-1 S = D^-1: the pivot test of node_gj_lds is an
-    // absolute one made for such rows -- on the raw Galerkin matrix of a system in SI units (entries ~1e-15) every
-    // pivot counted as singular and the level silently fell back to Jacobi sweeps (solver behaviour depended on
-    // the units of the matrix)
-    parallel_for(s, n, PFV_LAMBDA(int64_t r) {
-      double sum = 0.0;
-      for (int e = ip[r]; e < ip[r + 1]; ++e) sum += fabs(v[e]);
-      const double sc = (sum > 0.0 && sum < 1.0e300) ? 1.0 / sum : 1.0;
-      rsc[r] = sc;
-      for (int e = ip[r]; e < ip[r + 1]; ++e) D[(size_t)r * ld + ix[e]] += v[e] * sc;
-    });
-    int32_t* st = c.status.ensure(16);
-    be_memset(st, 0, sizeof(int32_t), s);
-    // one workgroup on a matrix in global memory: every pivot step is a round of dependent accesses -- 1024 threads
-    // keep four times the loads of 256 in flight (the strength filter leaves coarsest levels of ~500 rows: 1.6 ms)
-    auto invert = PFV_LAMBDA(const WaveCtx& w) {
-      NodeLds G;
-      G.A = D;
-      G.rowk = D + (size_t)n * ld;
-      G.colk = G.rowk + n;
-      G.ipiv = ipiv;
-      node_gj_lds(w, G, n, ld, 0, st);
-    };
-    // the matrix staged in LDS when it fits (n <= ~136: 143 KB of the 160): a pivot step is then a few LDS round trips
-    // instead of a chain of dependent global accesses -- the 132-row coarsest level of the 2 M-cell system took 1.2 ms
-    // per step in global memory, a tenth of the whole step at 200 k cells
-    const size_t lds_need = sizeof(double) * ((size_t)n * ld + 2 * (size_t)n) + 64;
-    auto invert_lds = PFV_LAMBDA(const WaveCtx& w) {
-      double* A = reinterpret_cast<double*>(w.lds);
-      PFV_LANES(q, n * ld) A[q] = D[q];
-      w.sync();
-      NodeLds G;
-      G.A = A;
-      G.rowk = A + (size_t)n * ld;
-      G.colk = G.rowk + n;
-      G.ipiv = ipiv;
-      node_gj_lds(w, G, n, ld, 0, st);
-      w.sync();
-      PFV_LANES(q, n * ld) D[q] = A[q];
-      w.sync();
-    };
-    if (lds_need <= 150 * 1024 && env_int("PFV_AMG_DENSE_LDS", 1) != 0) {
-      if (n > 128) block_for<1024>(s, 1, lds_need, invert_lds);
-      else block_for<256>(s, 1, lds_need, invert_lds);
-    } else if (n > 128) block_for<1024>(s, 1, 0, invert);
-    else block_for<256>(s, 1, 0, invert);
-    if (read_scalar<int32_t>(s, st) == 0) {
-      double* inv = amg.dense.ensure((size_t)n * n);
-      parallel_for(s, (int64_t)n * n, PFV_LAMBDA(int64_t q) {
-        const int64_t r = q / n, cc = q - r * n;
-        inv[q] = D[(size_t)r * ld + cc] * rsc[cc];
-      });
-      amg.dense_ok = true;
-    }
+    amg.dense_ok = amg_dense_invert(c, wk, *Lc.P, Lc.val, amg.dense);
   }
   amg.op_complexity = nnz_sum / (double)A.nnz;
   for (size_t k = 0; k < amg.nlev; ++k) {
@@ -1938,21 +1963,7 @@ static double* amg_cycle(pfv_ctx_impl& c, Amg& amg, size_t l, const double* b, d
   }
   if (l + 1 == amg.nlev) {
     if (amg.dense_ok) {
-      const double* inv = amg.dense;
-      wave_for(s, n, 64 * sizeof(double) + 16, PFV_LAMBDA(const WaveCtx& w) {
-        double* sh = reinterpret_cast<double*>(w.lds);
-        const int64_t r = w.item;
-        double a = 0.0;
-        PFV_LANES(j, (int)n) a += inv[r * n + j] * b[j];
-        sh[w.lane] = a;
-        w.sync();
-        if (w.lane0()) {
-          double sum = 0.0;
-          for (int j = 0; j < w.width; ++j) sum += sh[j];
-          x[r] = sum;
-        }
-        w.sync();
-      });
+      amg_dense_apply(c, amg.dense, n, b, x);
     } else {
       // stalled coarsening above the dense limit: a few damped Jacobi sweeps
       parallel_for(s, n, PFV_LAMBDA(int64_t i) { x[i] = omega * dinv[i] * b[i]; });
@@ -2161,8 +2172,11 @@ static void blockpc_apply(pfv_ctx_impl& c, BlockPc& M, const CsrPattern& P, cons
 }
 
 // ---- preconditioner handle used by the Krylov loops
+struct AmgNns;  // amg_nns.inc
+static void amg_nns_cycle(pfv_ctx_impl& c, AmgNns& H, size_t l, const double* b, double* x);
 struct Precond {
   Amg* amg = nullptr;          // nullptr: Jacobi
+  AmgNns* nns = nullptr;       // aggregation AMG with a near-null space (PFV_PRECOND_AMG_NNS)
   const double* diag = nullptr;
   BlockPc* blocks = nullptr;   // block lower-triangular preconditioner (takes precedence)
   const CsrPattern* P = nullptr;  // ... and the system it couples through
@@ -2171,6 +2185,8 @@ struct Precond {
 static void precond_apply(pfv_ctx_impl& c, const Precond& M, int64_t n, const double* in, double* out) {
   if (M.blocks) {
     blockpc_apply(c, *M.blocks, *M.P, M.val, n, in, out);
+  } else if (M.nns) {
+    amg_nns_cycle(c, *M.nns, 0, in, out);
   } else if (M.amg && M.amg->dist) {
     amg_apply_dist(c, *M.amg, in, out);
   } else if (M.amg) {

@@ -758,6 +758,7 @@ pfv_status pfv_csr_set_system(pfv_ctx* h, const pfv_csr* A, const double* rhs, i
     h->active.n = n;
     h->active_bs = 1;
     if (h->amg) h->amg->valid = false;
+    h->nns_stale = true;  // (the near-null-space hierarchy too)
     if (h->amg_block) h->amg_block->valid = false;
     if (h->block_pc) h->block_pc->for_val = nullptr;  // (the user-system buffer is reused: same pointer, new matrix)
     h->perm_for_val = nullptr;

@@ -86,6 +86,7 @@ struct LinSys {
 
 struct Amg;      // amg.inc
 struct BlockPc;  // amg.inc
+struct AmgNns;   // amg_nns.inc
 
 struct pfv_ctx_impl {
   MemPool pool;     // first member: destroyed last, after every buffer has been handed back
@@ -289,6 +290,20 @@ struct pfv_ctx_impl {
   unsigned long long symb_key = 0;   // ... of the topology the symbolic outputs on the handle were built from (0: none / replaced)
   std::unique_ptr<BlockPc> block_pc;  // pfv_set_block_preconditioner
   std::unique_ptr<Amg> amg_block;    // pfv_amg_setup: hierarchy of the leading block (sharded solves)
+  // PFV_PRECOND_AMG_NNS (pfv_set_near_null_space): its hierarchy lives apart from `amg`, so setting or clearing the modes
+  // never touches the plain one
+  std::unique_ptr<AmgNns> amg_nns;
+  const double* amg_nns_for_val = nullptr;  // the matrix values it was built from
+  unsigned long long amg_nns_key = 0;       // ... and the nns_key of the modes
+  unsigned long long grid_serial = 0;       // bumped by every pfv_set_grid
+  bool nns_stale = true;                    // the active system's values changed since it was built
+  std::vector<double> nns_B;                // the caller's modes, column-major n x k (empty: rigid-body modes of the grid)
+  int nns_k = 0, nns_bs = 0;                // modes (0: none), block size
+  int64_t nns_n = 0;                        // rows of the system they were given for
+  unsigned long long nns_key = 0;           // digest of the modes (device-made: of the grid's cell centres and epoch)
+  Buf<double> nns_col, nns_row;             // device copies: column-major in the caller's order / row-major permuted
+  Buf<double> nns_cc;                       // cell centres in the solve's numbering (device-made modes)
+  unsigned long long amg_nns_cfg = 0;       // amg_nns_cfg() of the switches it was built with
   CsrPattern pat_block;
   Buf<double> val_block;
   // set only while pfv_solve_sharded runs: the caller's exchange hooks and work space

@@ -633,6 +633,7 @@ static void launch_spmv_dot_u(stream_t s, int blocks, int U, int64_t nrows, cons
 }  // namespace pfv
 #include "spmv_win.inc"
 #include "amg.inc"
+#include "amg_nns.inc"
 namespace pfv {
 
 // ---- sharded BiCGStab with merged reductions.  The textbook iteration has three global synchronisation points,

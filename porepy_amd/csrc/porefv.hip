@@ -257,6 +257,7 @@ pfv_status pfv_set_grid(pfv_ctx* h, int nd, int64_t nc, int64_t nf, int64_t nn, 
     upload(h->fnorm, face_normals, 3 * (size_t)nf, s);
     upload(h->fcen, face_centers, 3 * (size_t)nf, s);
     upload(h->ccen, cell_centers, 3 * (size_t)nc, s);
+    ++h->grid_serial;  // (device-made near-null spaces follow the cell centres)
     upload(h->farea, face_areas, (size_t)nf, s);
     upload(h->cf_ptr, cf_indptr, (size_t)nc + 1, s);
     upload(h->cf_idx, cf_indices, (size_t)h->ncf, s);
@@ -791,6 +792,7 @@ pfv_status pfv_mpfa_assemble(pfv_ctx* h, const double* bc_values, const double* 
     if (!h->have_system) {
       pfv::assemble_system(*h);
       if (h->amg) h->amg->valid = false;
+      h->nns_stale = true;  // (the near-null-space hierarchy too)
       if (h->block_pc) h->block_pc->for_val = nullptr;
       if (h->amg_block) h->amg_block->valid = false;
       h->perm_for_val = nullptr;
@@ -849,6 +851,7 @@ pfv_status pfv_mpfa_ad_flux_system(pfv_ctx* h, const double* p, const double* dk
     pfv::be_sync(s);
     h->have_system = false;  // PFV_MAT_SYSTEM now holds J, not div flux: pfv_mpfa_assemble rebuilds it
     if (h->amg) h->amg->valid = false;
+    h->nns_stale = true;  // (the near-null-space hierarchy too)
       if (h->block_pc) h->block_pc->for_val = nullptr;
     if (h->amg_block) h->amg_block->valid = false;
     h->perm_for_val = nullptr;
@@ -1272,6 +1275,7 @@ pfv_status pfv_mpsa_assemble(pfv_ctx* h, const double* bc_values, const double* 
     if (!h->have_mech_system) {
       pfv::mpsa_assemble_system(*h);
       if (h->amg) h->amg->valid = false;
+      h->nns_stale = true;  // (the near-null-space hierarchy too)
       if (h->block_pc) h->block_pc->for_val = nullptr;
       if (h->amg_block) h->amg_block->valid = false;
       h->perm_for_val = nullptr;
@@ -1508,6 +1512,7 @@ pfv_status pfv_set_system(pfv_ctx* h, int64_t n, const int32_t* indptr, const in
     h->active.n = n;
     h->active_bs = 1;
     if (h->amg) h->amg->valid = false;
+    h->nns_stale = true;  // (the near-null-space hierarchy too)
       if (h->block_pc) h->block_pc->for_val = nullptr;
     if (h->amg_block) h->amg_block->valid = false;
     h->perm_for_val = nullptr;
@@ -1519,6 +1524,9 @@ pfv_status pfv_set_system(pfv_ctx* h, int64_t n, const int32_t* indptr, const in
 
 pfv_status pfv_amg_setup(pfv_ctx* h, int64_t n_own) {
   return guarded(h, [&] {
+    if (h->precond == PFV_PRECOND_AMG_NNS)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "PFV_PRECOND_AMG_NNS has no sharded form: pfv_set_preconditioner(PFV_PRECOND_AMG) "
+                                            "or PFV_PRECOND_JACOBI for sharded solves");
     require(h->active.valid, "assemble first");
     const int bs = h->active_bs;
     const int64_t n = h->active.n;
@@ -1585,6 +1593,9 @@ pfv_status pfv_amg_setup_sharded(pfv_ctx* h, int64_t n_own, const pfv_shard_hook
                                  int n_peers, const int32_t* peers, const int64_t* send_ptr,
                                  const int32_t* send_idx, const int64_t* recv_ptr, const int32_t* recv_pos) {
   return guarded(h, [&] {
+    if (h->precond == PFV_PRECOND_AMG_NNS)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "PFV_PRECOND_AMG_NNS has no sharded form: pfv_set_preconditioner(PFV_PRECOND_AMG) "
+                                            "or PFV_PRECOND_JACOBI for sharded solves");
     require(h->active.valid, "assemble first");
     const int bs = h->active_bs;
     const int64_t n = h->active.n;
@@ -1663,8 +1674,10 @@ pfv_status pfv_amg_apply_device(pfv_ctx* h, const double* d_r, double* d_z) {
 
 pfv_status pfv_set_preconditioner(pfv_ctx* h, int kind) {
   return guarded(h, [&] {
-    require(kind == PFV_PRECOND_JACOBI || kind == PFV_PRECOND_AMG || (kind == PFV_PRECOND_BLOCK && h->block_pc),
-            "unknown preconditioner (PFV_PRECOND_BLOCK: pfv_set_block_preconditioner first)");
+    require(kind == PFV_PRECOND_JACOBI || kind == PFV_PRECOND_AMG || (kind == PFV_PRECOND_BLOCK && h->block_pc) ||
+                (kind == PFV_PRECOND_AMG_NNS && h->nns_k > 0),
+            "unknown preconditioner (PFV_PRECOND_BLOCK: pfv_set_block_preconditioner first; PFV_PRECOND_AMG_NNS: "
+            "pfv_set_near_null_space first)");
     h->precond = kind;
   });
 }
@@ -1678,6 +1691,107 @@ pfv_status pfv_set_block_preconditioner(pfv_ctx* h, int64_t n_blocks, const int6
     h->block_pc->gs = gauss_seidel != 0;
     h->block_pc->for_val = nullptr;
     h->precond = PFV_PRECOND_BLOCK;
+  });
+}
+
+pfv_status pfv_set_near_null_space(pfv_ctx* h, int bs, int k, const double* B) {
+  return guarded(h, [&] {
+    require(h->active.valid, "assemble first");
+    require(k >= 0, "k must not be negative");
+    if (k > pfv::kNnsMaxModes) throw pfv::Error(PFV_ERR_UNSUPPORTED, "near-null space: at most 8 modes");
+    const int64_t n = h->active.n;
+    if (k == 0) {
+      h->nns_k = h->nns_bs = 0;
+      h->nns_n = 0;
+      h->nns_B.clear();
+      h->nns_key = 0;
+      if (h->precond == PFV_PRECOND_AMG_NNS) h->precond = PFV_PRECOND_JACOBI;
+      return;
+    }
+    require(bs >= 1 && bs <= pfv::kNnsMaxModes && n % bs == 0, "near-null space: bad block size");
+    unsigned long long key = 1469598103934665603ull;  // FNV-1a over what the modes are made of
+    auto mix = [&key](const void* p, size_t bytes) {
+      const unsigned char* c = static_cast<const unsigned char*>(p);
+      for (size_t q = 0; q < bytes; ++q) key = (key ^ c[q]) * 1099511628211ull;
+    };
+    mix(&k, sizeof k);
+    mix(&bs, sizeof bs);
+    mix(&n, sizeof n);
+    if (B == nullptr) {
+      require(h->active_is_grid && h->nd >= 2 && bs == h->nd && h->active_bs == h->nd && n == h->nc * h->nd,
+              "near-null space B == NULL: rigid-body modes of the grid need the assembled mechanics system (bs = nd)");
+      require(k == (h->nd == 2 ? 3 : 6), "near-null space B == NULL: k must be 3 in 2-D, 6 in 3-D");
+      h->nns_B.clear();
+      const unsigned long long tag = 0x67726964ull;  // device-made: the grid the centres belong to
+      mix(&tag, sizeof tag);
+      mix(&h->grid_serial, sizeof h->grid_serial);
+    } else {
+      h->nns_B.assign(B, B + (size_t)n * k);
+      mix(B, sizeof(double) * (size_t)n * k);
+    }
+    h->nns_k = k;
+    h->nns_bs = bs;
+    h->nns_n = n;
+    h->nns_key = key;
+  });
+}
+
+// the near-null space in the numbering of the system the Krylov loop works on, row-major [n][k]
+static const double* nns_modes(pfv_ctx* h, bool permuted) {
+  auto s = h->stream;
+  const int64_t n = h->nns_n;
+  const int k = h->nns_k, bs = h->nns_bs;
+  double* col = h->nns_col.ensure((size_t)(n * k));
+  if (h->nns_B.empty()) pfv::nns_rigid_body_modes(*h, h->nd, h->nc, h->ccen, col);
+  else pfv::be_h2d(col, h->nns_B.data(), sizeof(double) * (size_t)(n * k), s);
+  double* tmp = h->nns_row.ensure((size_t)(n * k));
+  const double* src = col;
+  if (permuted) {  // the renumbering of the system (reorder.inc), column by column
+    for (int j = 0; j < k; ++j) pfv::permute_vector(*h, n, bs, col + (size_t)j * n, tmp + (size_t)j * n, true);
+    pfv::be_d2d(col, tmp, sizeof(double) * (size_t)(n * k), s);
+  }
+  pfv::parallel_for(s, n, PFV_LAMBDA(int64_t r) {
+    for (int j = 0; j < k; ++j) tmp[r * k + j] = src[(int64_t)j * n + r];
+  });
+  return tmp;
+}
+
+// the cell centres in the numbering of the system (device-made modes only; nullptr for the caller's modes)
+static const double* nns_centres(pfv_ctx* h, bool permuted) {
+  if (!h->nns_B.empty()) return nullptr;
+  const int64_t nc = h->nc;
+  double* cc = h->nns_cc.ensure((size_t)(3 * nc));
+  for (int d = 0; d < 3; ++d) {
+    if (permuted) pfv::permute_vector(*h, nc, 1, h->ccen.p + d * nc, cc + d * nc, true);
+    else pfv::be_d2d(cc + d * nc, h->ccen.p + d * nc, sizeof(double) * (size_t)nc, h->stream);
+  }
+  return cc;
+}
+
+pfv_status pfv_amg_nns_level(pfv_ctx* h, int level, int64_t* info, int32_t* agg, double* P, double* B, double* Bc,
+                             int32_t* indptr, int32_t* indices, double* val) {
+  return guarded(h, [&] {
+    require(info != nullptr, "info is required");
+    require(h->amg_nns && h->amg_nns->valid, "no near-null-space hierarchy (solve with PFV_PRECOND_AMG_NNS first)");
+    pfv::AmgNns& H = *h->amg_nns;
+    require(level >= 0 && (size_t)level < H.nlev, "level out of range");
+    const pfv::NnsLevel& L = *H.lev[(size_t)level];
+    const int k = H.k;
+    info[0] = L.n;
+    info[1] = L.bs;
+    info[2] = k;
+    info[3] = L.nagg;
+    info[4] = L.P->nnz;
+    info[5] = (int64_t)H.nlev;
+    auto s = h->stream;
+    if (agg && L.nagg > 0) be_d2h(agg, L.agg.p, sizeof(int32_t) * (size_t)L.cells, s);
+    if (P && L.nagg > 0) be_d2h(P, L.Pt.p, sizeof(double) * (size_t)(L.n * k), s);
+    if (B) be_d2h(B, L.B.p, sizeof(double) * (size_t)(L.n * k), s);
+    if (Bc && L.nagg > 0) be_d2h(Bc, L.Bc.p, sizeof(double) * (size_t)(L.nagg * k * k), s);
+    if (indptr) be_d2h(indptr, L.P->indptr.p, sizeof(int32_t) * (size_t)(L.n + 1), s);
+    if (indices) be_d2h(indices, L.P->indices.p, sizeof(int32_t) * (size_t)L.P->nnz, s);
+    if (val) be_d2h(val, L.val, sizeof(double) * (size_t)L.P->nnz, s);
+    pfv::be_sync(s);
   });
 }
 
@@ -1699,6 +1813,7 @@ static pfv::LinSys solver_system(pfv_ctx* h, bool& permuted) {
       h->perm_for_val = sys.val;
       h->win_for = h->win_rows_for = nullptr;
       if (h->amg) h->amg->valid = false;
+      h->nns_stale = true;  // (the near-null-space hierarchy too)
       if (h->block_pc) h->block_pc->for_val = nullptr;  // (the copy's buffers are shared by the flow and mechanics systems)
     }
     pfv::permute_vector(*h, sys.n, bs, sys.rhs, h->rhs_perm.ensure(sys.n), true);
@@ -1764,6 +1879,32 @@ pfv_status pfv_solve(pfv_ctx* h, int method, double rtol, int maxit, int restart
       }
       M.amg = h->amg.get();
       Mp = &M;
+    } else if (h->precond == PFV_PRECOND_AMG_NNS) {
+      require(h->nns_k > 0 && h->nns_n == (int64_t)n && (!permuted || h->nns_bs == h->active_bs),
+              "the near-null space does not fit the active system (pfv_set_near_null_space again)");
+      require(!h->nns_B.empty() || h->active_is_grid, "rigid-body modes of the grid need the assembled mechanics system");
+      if (!h->amg_nns) h->amg_nns = std::make_unique<pfv::AmgNns>();
+      const unsigned long long cfg = pfv::amg_nns_cfg();
+      if (!h->amg_nns->valid || h->nns_stale || h->amg_nns_for_val != sys.val || h->amg_nns_key != h->nns_key ||
+          h->amg_nns_cfg != cfg) {
+        const double* B0 = nns_modes(h, permuted);
+        pfv::amg_nns_setup(*h, *h->amg_nns, *sys.P, sys.val, h->nns_bs, h->nns_k, B0, nns_centres(h, permuted));
+        h->amg_nns_for_val = sys.val;
+        h->amg_nns_key = h->nns_key;
+        h->amg_nns_cfg = cfg;
+        h->nns_stale = false;
+        const pfv::AmgNns& H = *h->amg_nns;
+        h->stats.amg_setup_ms = H.setup_ms;
+        h->stats.amg_operator_complexity = H.op_complexity;
+        h->stats.amg_levels = (int64_t)H.nlev;
+        h->stats.amg_coarsest_rows = H.lev[H.nlev - 1]->n;
+        h->stats.amg_maps_reused = 0;
+        h->stats.amg_level0_nnz = sys.P->nnz;
+        h->stats.amg_filter_theta = 0.0;
+        h->stats.amg_nns_modes = H.k;
+      }
+      M.nns = h->amg_nns.get();
+      Mp = &M;
     } else if (h->precond == PFV_PRECOND_BLOCK) {
       require(h->block_pc && !permuted, "pfv_set_block_preconditioner first (user systems only)");
       require(h->block_pc->ptr.back() == (int64_t)n, "the block layout does not cover the system");
@@ -1807,6 +1948,9 @@ pfv_status pfv_solve_sharded(pfv_ctx* h, int method, double rtol, int maxit, int
                              pfv_solve_info* info) {
   pfv::SolveResult res;
   pfv_status st = guarded(h, [&] {
+    if (h->precond == PFV_PRECOND_AMG_NNS)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "PFV_PRECOND_AMG_NNS has no sharded form: pfv_set_preconditioner(PFV_PRECOND_AMG) "
+                                            "or PFV_PRECOND_JACOBI for sharded solves");
     require(h->active.valid, "assemble first");
     require(hooks && hooks->exchange_halo && hooks->allreduce_sum, "both hooks are required");
     require(d_work && d_x_owned, "work space and x are required");

@@ -365,6 +365,9 @@ class Mpsa:
             A, b = self._split_system(sd, data)
             if getattr(self, "_split_ctx", None) is None:
                 self._split_ctx = _lib.Context(self.device, self._library)  # kept between solves
+            if precond == "amg_rbm":  # (the split system is a host matrix: the modes go in explicitly)
+                return solve_csr(A, b, method=method, rtol=rtol, maxit=maxit, restart=restart, precond="amg_nns",
+                                 x0=x0, context=self._split_ctx, near_null_space=rigid_body_modes(sd), block_size=sd.dim)
             return solve_csr(A, b, method=method, rtol=rtol, maxit=maxit, restart=restart, precond=precond, x0=x0,
                              context=self._split_ctx)
         if getattr(self, "_pieces_without_system", {}).get(id(sd)) is sd:
@@ -373,8 +376,35 @@ class Mpsa:
                 "bound): the mechanics system is not kept on the device -- assemble the coupled system from "
                 "data[DISCRETIZATION_MATRICES] and hand it to porepy_amd.solve_csr")
         ctx = self._assemble(sd, data)
+        if precond == "amg_rbm":
+            _check_in_plane(sd)
         return ctx.solve(method=method, rtol=rtol, maxit=maxit, x0=x0, n=sd.dim * sd.num_cells, restart=restart,
                          precond=precond)
+
+
+def _check_in_plane(sd):
+    cc = np.asarray(sd.cell_centers, dtype=float)
+    if sd.dim == 2 and cc.shape[1] > 0 and np.ptp(cc[2]) > 1e-12 * max(1.0, float(np.abs(cc).max())):
+        raise ValueError("rigid-body modes of a 2-D grid are built from its x and y coordinates: the grid must lie in "
+                         "a plane z = const")
+
+
+def rigid_body_modes(sd) -> np.ndarray:
+    """Rigid-body modes of the cells of ``sd``: an (nd * nc) x k array in PorePy's order of a vector field (cell-major,
+    component-minor: what ``u.reshape(nd, -1, order="F")`` undoes).  Columns: the nd translations, then the rotations
+    -- 2-D (k = 3): (-y, x); 3-D (k = 6): about x (0, -z, y), about y (z, 0, -x), about z (-y, x, 0).  The same modes
+    ``precond="amg_rbm"`` builds on the device.  2-D grids must lie in a plane z = const."""
+    nd, nc = int(sd.dim), int(sd.num_cells)
+    if nd not in (2, 3):
+        raise ValueError("rigid-body modes are defined for 2-D and 3-D grids")
+    _check_in_plane(sd)
+    x, y, z = (np.asarray(sd.cell_centers, dtype=float)[a] for a in range(3))
+    one, zero = np.ones(nc), np.zeros(nc)
+    if nd == 2:
+        cols = [(one, zero), (zero, one), (-y, x)]
+    else:
+        cols = [(one, zero, zero), (zero, one, zero), (zero, zero, one), (zero, -z, y), (z, zero, -x), (-y, x, zero)]
+    return np.column_stack([np.column_stack(c).ravel() for c in cols])
 
 
 def as_porepy_mpsa(device: int = 0, library=None):

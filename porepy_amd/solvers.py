@@ -28,12 +28,23 @@ _METHODS = {"hip_bicgstab": "bicgstab", "hip_gmres": "gmres", "hip_cg": "cg"}
 
 
 def solve_csr(A, b, method: str = "bicgstab", rtol: float = 1e-12, maxit: int = 50000, restart: int = 0,
-              device: int = 0, library=None, context: _lib.Context | None = None, precond: str = "jacobi", x0=None):
+              device: int = 0, library=None, context: _lib.Context | None = None, precond: str = "jacobi", x0=None,
+              near_null_space=None, block_size: int = 1):
     """x with ||b - A x|| <= rtol ||b||, computed on the device; returns (x, info).  ``A``: scipy sparse, or a
     ``DeviceCsr`` (solved where it lives).  ``context``: a handle to reuse (its buffers, streams and memory pool)
-    instead of a fresh one per call; ``x0``: initial guess."""
+    instead of a fresh one per call; ``x0``: initial guess.  ``precond="amg_nns"``: aggregation AMG whose coarse
+    levels carry the n x k ``near_null_space`` (e.g. ``rigid_body_modes(sd)`` for elasticity), ``block_size``
+    unknowns per node / cell (A is padded to full blocks with explicit zeros)."""
     from .device_csr import DeviceCsr
 
+    if precond == "amg_nns":
+        if isinstance(A, DeviceCsr):
+            raise NotImplementedError('precond="amg_nns" takes a host (scipy) matrix')
+        A, B, bs = _nns_system(A, near_null_space, block_size)
+        ctx = context if context is not None else _lib.Context(device, library)
+        ctx.set_system(A, b)
+        ctx.set_near_null_space(B, bs)
+        return ctx.solve(method=method, rtol=rtol, maxit=maxit, x0=x0, restart=restart, n=A.shape[0], precond=precond)
     if isinstance(A, DeviceCsr):
         # a system assembled on the device (device_csr.py): it becomes the active system of the solving handle without
         # a host copy (pfv_csr_set_system)
@@ -42,6 +53,38 @@ def solve_csr(A, b, method: str = "bicgstab", rtol: float = 1e-12, maxit: int = 
         ctx = context if context is not None else _lib.Context(device, library)
         ctx.set_system(A, b)
     return ctx.solve(method=method, rtol=rtol, maxit=maxit, x0=x0, restart=restart, n=A.shape[0], precond=precond)
+
+
+def _nns_system(A, B, bs: int):
+    """(A padded to full bs x bs blocks with explicit zeros, B as float64 n x k, bs) for precond="amg_nns"."""
+    import scipy.sparse as sps
+
+    A = sps.csr_matrix(A)
+    n = A.shape[0]
+    bs = int(bs)
+    if A.shape[0] != A.shape[1]:
+        raise ValueError("square matrix expected")
+    if bs < 1 or n % bs != 0:
+        raise ValueError(f"the system size {n} is not a multiple of the block size {bs}")
+    if B is None:
+        raise ValueError('precond="amg_nns" needs near_null_space (n x k)')
+    B = np.asarray(B, dtype=np.float64)
+    if B.ndim != 2 or B.shape[0] != n or not 1 <= B.shape[1] <= 8:
+        raise ValueError(f"near_null_space must be an array of {n} x k values, 1 <= k <= 8")
+    if bs > 1:
+        coo = A.tocoo()
+        blk = sps.coo_matrix((np.ones(coo.nnz), (coo.row // bs, coo.col // bs)), shape=(n // bs, n // bs)).tocsr()
+        blk.sum_duplicates()
+        bc = blk.tocoo()
+        off = np.arange(bs)
+        rows = (bc.row[:, None, None] * bs + off[None, :, None]).repeat(bs, axis=2).ravel()
+        cols = (bc.col[:, None, None] * bs + off[None, None, :]).repeat(bs, axis=1).ravel()
+        # every entry of every touched block, A's values where it has them (explicit zeros elsewhere)
+        full = sps.coo_matrix((np.concatenate((coo.data, np.zeros(rows.size))),
+                               (np.concatenate((coo.row, rows)), np.concatenate((coo.col, cols)))), shape=A.shape).tocsr()
+        full.sort_indices()
+        A = full
+    return A, B, bs
 
 
 def match_rows(A):

@@ -1,0 +1,67 @@
+"""CPU suite for the near-null-space AMG (PFV_PRECOND_AMG_NNS: precond="amg_rbm" / "amg_nns") on the host-emulation
+build of the same kernels; tests/test_gpu_amg_nns.py runs the same cases on the HIP library."""
+import pytest
+
+from tests import _amg_nns_cases as C
+from tests import _parity as P
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return P.emulation_library()
+
+
+def test_rigid_body_modes_are_a_null_space_2d(lib):
+    C.modes_are_null_space(lib, C.grid_2d(8))
+
+
+def test_rigid_body_modes_are_a_null_space_3d(lib):
+    C.modes_are_null_space(lib, C.grid_3d(5))
+
+
+def test_hierarchy_identities_mpsa(lib):
+    C.mpsa_hierarchy(lib, 8)
+
+
+def test_hierarchy_identities_user_system_with_singleton(lib):
+    C.user_system_hierarchy(lib)
+
+
+def test_device_modes_follow_the_renumbering(lib):
+    C.reordering(lib, 8)
+
+
+def test_split_path(lib):
+    C.split_path(lib, 6)
+
+
+def test_uniaxial_exact_3d(lib):
+    P.mpsa_uniaxial_exact(lib, C.grid_3d(4, perturb=False), tol=1e-9, precond="amg_rbm")
+
+
+def test_uniaxial_exact_2d(lib):
+    P.mpsa_uniaxial_exact(lib, C.grid_2d(8), tol=1e-9, precond="amg_rbm")
+
+
+def test_clamped_heterogeneous_against_direct(lib):
+    C.clamped_against_direct(lib, 4)
+
+
+def test_fewer_iterations_than_plain_amg(lib):
+    C.fewer_iterations(lib, 16)
+
+
+def test_deterministic(lib):
+    C.deterministic(lib, 6)
+
+
+def test_plain_amg_untouched(lib):
+    C.nothing_else_moved(lib, 6)
+
+
+def test_sharded_unsupported(lib):
+    C.sharded_unsupported(lib)
+
+
+def test_bad_arguments(lib):
+    C.bad_arguments(lib)

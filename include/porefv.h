@@ -129,7 +129,7 @@ typedef struct {
   int64_t amg_setup_launches;     /* ... of the last preconditioner setup */
   int64_t node_redo;              /* interaction regions the first launch of the last discretization handed to the
                                      pivoted full body: those whose unpivoted elimination failed its a-posteriori check
-                                     (PFV_NODE_GJ=5), or whose condition asked for refinement in a lean launch */
+                                     (PFV_NODE_GJ=5) */
   int64_t symbolic_reused;        /* 1: the last discretize with PFV_DISCR_REBUILD_TOPOLOGY rebuilt the topology, proved it
                                      equal (64-bit digest of what the symbolic phase reads + sizes) to the one the CSR
                                      patterns on the handle were built from, and kept them; symbolic_ms then is the time of
@@ -143,9 +143,7 @@ typedef struct {
   double mpsa_max_contrast;       /* MPSA: the largest such ratio over all interaction regions (1: homogeneous) */
   int64_t assemble_positions_kept; /* 1: the last div @ flux replayed the positions of its entries recorded under the same
                                       kept patterns (no column indices read, no searches); 0: searched */
-  int64_t pipeline_runs;          /* > 0: the last pfv_mpfa_discretize ran the interaction-region kernel in this many runs on the
-                                     second stream with the face kernel following run by run on the first (node_ms is then the
-                                     span of the whole pipeline, face_ms what came after it); 0: one after the other */
+  int64_t pipeline_runs;          /* always 0 (kept so that the fields after it keep their offsets) */
   int64_t amg_nns_modes;          /* modes per aggregate of the last PFV_PRECOND_AMG_NNS setup (0: none); that setup also
                                      fills amg_setup_ms, amg_operator_complexity, amg_levels and amg_coarsest_rows */
 } pfv_stats;

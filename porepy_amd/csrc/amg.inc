@@ -119,7 +119,6 @@ struct Amg {
   std::unique_ptr<AmgDist> dist;  // set: coupled hierarchy
   bool no_filter = false;         // (the replicated hierarchy below a gathered level)
   int64_t finest_cells_parent = 0;  // ... cells of the finest level of the hierarchy it continues (0: it is its own)
-  bool follow_parent_maps = false;  // ... whose maps are kept when the parent kept its own (set by the parent per setup)
   std::vector<std::unique_ptr<AmgLevel>> lev;
   size_t nlev = 0;     // levels in use (lev may hold more, kept for their buffers)
   AmgWork wk;
@@ -183,7 +182,6 @@ struct Amg {
   int gamma = 2, gamma_levels = 1;
   int coarse_target = 0;  // > 0: stop coarsening at this many rows instead of PFV_AMG_COARSE_TARGET (block preconditioner:
                           // blocks of at most kAmgDenseMax rows get an exact dense inverse, one level)
-  int64_t tail_rows = 0;  // levels up to this many rows (and everything below them) run in one workgroup: amg_tail_cycle
   int64_t fuse_rows = 0;  // levels up to this many rows run the fused launches (amg_restrict_residual / amg_prolong_smooth)
   bool fuse_cycle = true;  // larger coarse levels: prolongation inside the post-smoothing product, the second visit's residual
                            // and first smoothing step in one product, its correction folded into the parent's prolongation
@@ -1086,8 +1084,7 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
   // decision to "re-match", never send ranks down different branches of the setup's collectives.
   const int64_t cfg = ((((int64_t)amg.passes * 16 + env_int("PFV_AMG_ROUNDS", kAmgRounds)) * 16 +
                         env_int("PFV_AMG_PASSES_COARSE", -1) + 1) * 4 + env_int("PFV_AMG_STRENGTH_NEG", 0)) * 65536 +
-                      kAmgCoarseTarget * 8 + bs + (int64_t)(1000.0 * amg.filter_theta + 0.5) * (int64_t(1) << 40) +
-                      ((int64_t)env_int("PFV_AMG_SMALL_ROWS", 0) * 8 + env_int("PFV_AMG_PASSES_SMALL", 4)) * (int64_t(1) << 50);
+                      kAmgCoarseTarget * 8 + bs + (int64_t)(1000.0 * amg.filter_theta + 0.5) * (int64_t(1) << 40);
   unsigned long long csum_dist = 0;
   bool reuse_all_ranks = false;
   if (D) {
@@ -1119,10 +1116,6 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
   // fused launches on the small levels (neutral at 2 M cells, -2 ms per step at 200-260 k cells)
   amg.fuse_rows = env_int("PFV_AMG_FUSE_ROWS", 30000);
   amg.fuse_cycle = env_int("PFV_AMG_FUSE_CYCLE", 1) != 0;
-  // OFF by default -- measured on the MI355X (profiles/r04_ab_runs.txt): solve 46.4 ms without, 48.7 / 54.4 / 54.1 / 89.8 ms
-  // with tails of <= 2048 / 4096 / 9000 / 20000 rows: one CU walks a row's ~20 entries as a chain of dependent L2 trips
-  // (~150 us per tail visit) where the launches it replaces spread every level over the chip (~5 us each)
-  amg.tail_rows = env_int("PFV_AMG_TAIL_ROWS", 0);
   amg.filt_nnz = 0;
   // measured (profiles/r02_ab_runs.txt): -1.5 ms per step on the 2 M-cell scalar system, +5 ms on the 1.5 M-dof
   // block system of configs[3] -> lanes for scalar systems only
@@ -1143,15 +1136,7 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
     reuse = reuse_all_ranks;  // (maps_cfg == cfg went through the vote)
   } else if (env_int("PFV_AMG_REUSE", 1) != 0) {
     csum = amg_pattern_checksum(c, wk, A);
-    // (the replicated hierarchy below a gathered level: its finest matrix is a Galerkin product of filtered operators,
-    // whose pattern follows the values, so its own digest never matches on moving values.  PFV_AMG_REUSE_CHILD=1 lets it
-    // replay its maps when the hierarchy above it replays its own -- same rows, same parameters; every rank takes the
-    // same branch because the parent's decision went through the gather.  Measured on one rank over RCCL, 2 M cells,
-    // moving K (profiles/r05_ab_runs.txt, call P): setup 8.6 -> 8.2 ms but 24 -> 28 iterations, step 71.4 -> 72.0 ms: off.)
-    const bool follow = amg.follow_parent_maps && amg.finest_cells_parent > 0 && amg.maps_ok && amg.maps_n == A.nrows &&
-                        amg.maps_cfg == cfg && env_int("PFV_AMG_REUSE_CHILD", 0) != 0;
-    reuse = follow ||
-            amg.maps_ok && amg.maps_n == A.nrows && amg.maps_nnz == A.nnz && amg.maps_cfg == cfg &&
+    reuse = amg.maps_ok && amg.maps_n == A.nrows && amg.maps_nnz == A.nnz && amg.maps_cfg == cfg &&
             amg.maps_sum == csum &&
             // a re-built symbolic phase only invalidates the maps if its pattern differs: equal sizes, parameters and
             // checksum of the index arrays prove the pattern equal (PFV_AMG_REUSE_REBUILT=0: the epoch must match too)
@@ -1294,41 +1279,12 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
     const int64_t finest_cells = amg.finest_cells_parent > 0 ? amg.finest_cells_parent
                                                               : (D ? D->global_rows0 : amg.lev[0]->n) / bs;
     const int coarse_default = finest_cells >= kAmgGentleCells ? std::min(2, amg.passes) : amg.passes;
-    // ... and the small levels at the bottom, whose every visit is a chain of ~5 us launches whatever their size
-    // (a cycle of the 2 M-cell system spends 280 of its 830 us in 36 such launches), coarsen fast again: fewer levels
-    const int64_t small_rows = env_int("PFV_AMG_SMALL_ROWS", 0);
-    const int passes_small = std::max(1, std::min(6, env_int("PFV_AMG_PASSES_SMALL", 4)));
     const int passes_here = (l == 0 && amg.finest_cells_parent <= 0)
                                 ? amg.passes
-                                : (cells <= small_rows ? passes_small
-                                                       : std::max(1, std::min(6, env_int("PFV_AMG_PASSES_COARSE", coarse_default))));
+                                : std::max(1, std::min(6, env_int("PFV_AMG_PASSES_COARSE", coarse_default)));
     if (!reuse) L.pmap_count = 0;
     if (!reuse) L.members_kept = false;
-    // Kept maps: the intermediate products of the passes only served the matching of the next pass -- with nothing to
-    // match, the level's coarse matrix can be ONE product with the composed map (kept with its member lists) instead of
-    // one per pass: 7 instead of 17 products per setup of the 2 M-cell system (PFV_AMG_GALERKIN_DIRECT=1).  Measured
-    // (profiles/r05_ab_runs.txt): flow setup 6.11 -> 6.02 ms (78 -> 50 launches) -- the one big sort per coarse row costs
-    // what the three small ones did --, the MPSA block system 226 -> 253 ms per step (rows of 8 x 200 entries leave the
-    // batched gather).  Off; same sums in a different association when on.
-    const bool direct = reuse && L.members_kept && keep_members && L.pmap_count > 0 &&
-                        env_int("PFV_AMG_GALERKIN_DIRECT", 0) != 0;
-    if (direct) {
-      const int64_t nagg = L.pmap_n[L.pmap_count - 1];
-      const int32_t* amap = aggL;
-      if (D) {
-        const int64_t nh = D->plan[l]->n_halo;
-        int32_t* ae = D->aext.ensure((size_t)(cells + nh));
-        parallel_for(s, cells + nh, PFV_LAMBDA(int64_t i) { ae[i] = i < cells ? aggL[i] : (int32_t)(nagg + (i - cells)); });
-        amap = ae;
-      }
-      amg_galerkin(c, wk, *curP, curV, bs, amap, L.mptr, L.mem, nagg, wk.P[0], wk.V[0], wk.D[0], D ? nullptr : &amg);
-      if (D) wk.P[0].ncols = (nagg + D->plan[l]->n_halo) * bs;
-      slot = 0;
-      curP = &wk.P[0];
-      curV = wk.V[0].p;
-      cur_cells = nagg;
-    }
-    for (int pass = 0; !direct && pass < (reuse ? L.pmap_count : passes_here); ++pass) {
+    for (int pass = 0; pass < (reuse ? L.pmap_count : passes_here); ++pass) {
       int64_t nagg;
       const int32_t* a1p;
       if (reuse) {
@@ -1826,127 +1782,6 @@ static void amg_restrict(pfv_ctx_impl& c, const Amg& amg, const AmgLevel& L, con
   }
 }
 
-// ---- The tail of the hierarchy in ONE launch.  Levels of a few thousand rows are bound by the number of dependent
-// launches (~5 us each: two to four per level visit, every level below the first coarse one visited twice per cycle);
-// a grid-wide barrier is no cheaper than a launch on this part (DESIGN 5), but levels this small do not need a grid:
-// from the first level with at most `tail_rows` rows down to the coarsest and back up the whole V-leg runs in one
-// 1024-thread workgroup, phases separated by __syncthreads(), vectors in global memory (L2-resident, a few tens of
-// KB).  One thread per row, every row sum in entry order: deterministic, identical on every rank of a sharded solve
-// (the replicated part of a coupled hierarchy takes this path too).
-constexpr int kAmgTailMaxLevels = 8;
-struct AmgTailLevel {
-  int64_t n;
-  const int32_t *ip, *ix, *mptr, *mem, *agg;
-  const float* v32;
-  const double *val, *dinv;
-  double *b, *x, *t;
-  double omega;
-};
-struct AmgTailArgs {
-  AmgTailLevel L[kAmgTailMaxLevels];
-  int nl, bs, dense_ok, presmoothed;
-  double alpha;
-  const double* dense;
-};
-
-PFV_FN double amg_tail_row_product(const AmgTailLevel& L, int64_t r, const double* x) {
-  double sum = 0.0;
-  const int p1 = L.ip[r + 1];
-  if (L.v32) {
-    for (int p = L.ip[r]; p < p1; ++p) sum += (double)L.v32[p] * x[L.ix[p]];
-  } else {
-    for (int p = L.ip[r]; p < p1; ++p) sum += L.val[p] * x[L.ix[p]];
-  }
-  return sum;
-}
-
-// solution of level `l0` (right-hand side b, first iterate x: omega D^-1 b already applied by the caller if
-// `presmoothed`) left in x
-static void amg_tail_cycle(pfv_ctx_impl& c, Amg& amg, size_t l0, const double* b, double* x, bool presmoothed) {
-  AmgTailArgs A;
-  A.nl = (int)(amg.nlev - l0);
-  A.bs = amg.bs;
-  A.dense_ok = amg.dense_ok ? 1 : 0;
-  A.presmoothed = presmoothed ? 1 : 0;
-  A.alpha = amg.alpha;
-  A.dense = amg.dense;
-  for (int k = 0; k < A.nl; ++k) {
-    AmgLevel& L = *amg.lev[l0 + k];
-    AmgTailLevel& T = A.L[k];
-    T.n = L.n;
-    T.ip = L.P->indptr;
-    T.ix = L.P->indices;
-    T.mptr = L.mptr;
-    T.mem = L.mem;
-    T.agg = L.agg;
-    T.v32 = L.v32;
-    T.val = L.val;
-    T.dinv = L.dinv;
-    T.b = k == 0 ? const_cast<double*>(b) : L.b.p;
-    T.x = k == 0 ? x : L.x.p;
-    T.t = L.t;
-    T.omega = L.omega;
-  }
-  block_for<1024>(c.stream, 1, 16, PFV_LAMBDA(const WaveCtx& w) {
-    const int nl = A.nl, bs = A.bs;
-    if (!A.presmoothed) {
-      const AmgTailLevel& L = A.L[0];
-      PFV_LANES(i, L.n) L.x[i] = L.omega * L.dinv[i] * L.b[i];
-      w.sync();
-    }
-    for (int k = 0; k + 1 < nl; ++k) {  // down: residual, restriction, first smoothing step of the next level
-      const AmgTailLevel& L = A.L[k];
-      const AmgTailLevel& Ln = A.L[k + 1];
-      PFV_LANES(r, L.n) L.t[r] = L.b[r] - amg_tail_row_product(L, r, L.x);
-      w.sync();
-      const bool next_smooths = k + 2 < nl;
-      PFV_LANES(R, Ln.n) {
-        const int I = R / bs, a = R - I * bs;
-        double sum = 0.0;
-        for (int q = L.mptr[I]; q < L.mptr[I + 1]; ++q) sum += L.t[(int64_t)L.mem[q] * bs + a];
-        Ln.b[R] = sum;
-        if (next_smooths) Ln.x[R] = Ln.omega * Ln.dinv[R] * sum;
-      }
-      w.sync();
-    }
-    {  // coarsest level
-      const AmgTailLevel& L = A.L[nl - 1];
-      const int n = (int)L.n;
-      if (nl == 1 && !A.dense_ok) {
-        // (a one-level tail without a dense inverse: the caller's Jacobi sweeps -- not taken, see amg_cycle)
-      } else if (A.dense_ok) {
-        const double* inv = A.dense;
-        PFV_LANES(r, n) {
-          double sum = 0.0;
-          for (int j = 0; j < n; ++j) sum += inv[(int64_t)r * n + j] * L.b[j];
-          L.x[r] = sum;
-        }
-        w.sync();
-      } else {  // stalled coarsening above the dense limit: damped Jacobi sweeps, x -> t -> x twice
-        PFV_LANES(i, n) L.x[i] = L.omega * L.dinv[i] * L.b[i];
-        w.sync();
-        for (int sweep = 0; sweep < 2; ++sweep) {
-          PFV_LANES(r, n) L.t[r] = L.x[r] + L.omega * L.dinv[r] * (L.b[r] - amg_tail_row_product(L, r, L.x));
-          w.sync();
-          PFV_LANES(r, n) L.x[r] = L.t[r] + L.omega * L.dinv[r] * (L.b[r] - amg_tail_row_product(L, r, L.t));
-          w.sync();
-        }
-      }
-    }
-    for (int k = nl - 2; k >= 0; --k) {  // up: coarse correction, post-smoothing
-      const AmgTailLevel& L = A.L[k];
-      const AmgTailLevel& Ln = A.L[k + 1];
-      PFV_LANES(r, L.n) {
-        const int i = r / bs;
-        L.t[r] = L.x[r] + A.alpha * Ln.x[(int64_t)L.agg[i] * bs + (r - i * bs)];
-      }
-      w.sync();
-      PFV_LANES(r, L.n) L.x[r] = L.t[r] + L.omega * L.dinv[r] * (L.b[r] - amg_tail_row_product(L, r, L.t));
-      w.sync();
-    }
-  });
-}
-
 // approximate solution of A_l x = b; returns where it was left: x, or -- fused small levels -- the level's t
 static double* amg_cycle(pfv_ctx_impl& c, Amg& amg, size_t l, const double* b, double* x, bool x_is_presmoothed,
                          int visit) {
@@ -1956,11 +1791,6 @@ static double* amg_cycle(pfv_ctx_impl& c, Amg& amg, size_t l, const double* b, d
   const double omega = L.omega, alpha = amg.alpha;
   const double* dinv = L.dinv;
   double* t = L.t;
-  if (l >= 1 && n <= amg.tail_rows && !amg.dist && (int)(amg.nlev - l) <= kAmgTailMaxLevels &&
-      (amg.dense_ok || l + 1 < amg.nlev)) {
-    amg_tail_cycle(c, amg, l, b, x, x_is_presmoothed);
-    return x;
-  }
   if (l + 1 == amg.nlev) {
     if (amg.dense_ok) {
       amg_dense_apply(c, amg.dense, n, b, x);

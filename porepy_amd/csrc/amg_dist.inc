@@ -222,7 +222,6 @@ static void amg_build_global(pfv_ctx_impl& c, Amg& amg, AmgDist& D, AmgLevel& LK
   if (!D.glob) D.glob = std::make_unique<Amg>();
   D.glob->no_filter = true;
   D.glob->finest_cells_parent = std::max<int64_t>(1, D.global_rows0 / bs);
-  D.glob->follow_parent_maps = amg.reused;
   amg_setup(c, *D.glob, D.gP, D.gV.p, bs);
   D.gb.ensure((size_t)N);
   D.gx.ensure((size_t)N);

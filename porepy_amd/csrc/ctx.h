@@ -16,12 +16,6 @@ constexpr int kMaxBlock = 255;     // local sub-face / sub-cell indices are stor
 // block-size classes of the interaction-region kernel (one launch, one LDS size per class)
 static const int kClassBounds[] = {4, 8, 12, 16, 24, 32, 40, 48, 64, 96, 128, 192, 255};
 constexpr int kNumClasses = 13;
-// PFV_PIPE_CHUNKS: runs of the node || face pipeline (0 / 1: off).  OFF -- measured on the MI355X at 2 M cells
-// (profiles/r06_ab_runs.txt): the pipeline's span 14.9 ms (K = 4 / 8 / 16 / 30: 14.8 / 14.9 / 15.2 / 16.0) against
-// 6.6 + 7.1 = 13.7 ms back to back: the two kernels share the device work-conservingly (the interaction-region kernel
-// holds 154 of the 160 KB of LDS of a CU, the face kernel's wavefronts wait for whole workgroups of it to retire), and the
-// ready-run-major face order the pipeline needs costs the face kernel 1.4 ms of table locality (8.5 against 7.1 ms).
-constexpr int kPipeChunksDefault = 0;
 
 // Per sub-face (face, node) record consumed by the face kernel: one 64-byte line, written whole by the
 // interaction-region kernel (by the lane of the sub-cell the flux is evaluated from).  It replaces the
@@ -97,9 +91,6 @@ struct pfv_ctx_impl {
   stream_t own_stream{};  // the stream created with the handle (stream may point elsewhere, pfv_set_stream)
   Buf<double> sys_rowmax;            // largest off-diagonal |a_ij| of every row of A, left by assemble_system
   const double* sys_rowmax_for = nullptr;  // ... for this value array (nullptr: none)
-  bool face_order_cell_major = false;  // face_order: faces of one first-side cell back to back (PFV_FACE_ORDER / PFV_FACE_CACHE)
-  stream_t low_stream{};  // a stream of the LOWEST priority the device offers (PFV_NODE_LOWPRIO: the interaction-region
-                          // kernel goes there, so that the short symbolic kernels beside it are dispatched first)
   stream_t aux_stream{};  // second stream of the handle: the interaction-region kernel runs there while the
                           // symbolic phase runs on `stream` (both only need the sub-cell topology)
   std::string err;
@@ -160,11 +151,6 @@ struct pfv_ctx_impl {
   double bbox_lo[3] = {0, 0, 0}, bbox_hi[3] = {1, 1, 1};
   Buf<int32_t> node_order;    // [nn] nodes sorted by block-size class
   std::vector<int64_t> class_begin;  // host: first position of each size class in node_order
-  // node || face pipeline (topology.inc): runs of the largest size class, the faces that are ready after each of them
-  int pipe_chunks = 0, pipe_class = -1;     // 0: no pipeline on this grid
-  std::vector<int64_t> pipe_node_begin;     // [K + 1] positions in node_order: run q = [begin[q], begin[q + 1]) , q = 0 .. K - 1
-  std::vector<int32_t> pipe_face_begin;     // [K + 2] positions in face_order: faces ready after run q (0: the other classes) = [begin[q], begin[q + 1])
-  Buf<uint8_t> pipe_node_chunk;             // [nn] 0: not in the pipelined class, q + 1: run q of it
   int max_block = 0, max_deg = 0, max_face_nodes = 0, max_cell_faces = 0, max_bnd_per_node = 0;
   int64_t sum_block_sq = 0;   // sum of n(v)^2 (statistics)
   int64_t tab_len = 0, tabb_len = 0;
@@ -217,7 +203,6 @@ struct pfv_ctx_impl {
   Buf<double> mpsa_basis_sub;        // [nd*nd][Nsf] the same per sub-face (conditions per sub-face, mpsa.py:712-720)
   bool have_mpsa_basis_sub = false;
   Buf<char> mpsa_scratch;            // global-memory work space of interaction regions too large for the LDS
-  Buf<long long> mpsa_clk;           // timing lab (PFV_MPSA_CLOCK): s_memtime stamps of one workgroup
   // conditions per sub-face (mpsa.py:712-720): flags / weights per sub-face replace the per-face ones, stress and
   // bound_stress keep sub-face rows, the boundary matrices sub-face columns
   bool mpsa_subface_bc = false, have_mpsa_sub_symbolic = false;
@@ -311,8 +296,7 @@ struct pfv_ctx_impl {
   bool shard_overlap = false;        // sharded SpMV: halo exchange on aux_stream beside the interior row blocks
   Buf<int32_t> shard_blocks;         // [interior row blocks | boundary row blocks] of win_rows
   int64_t shard_n_interior = 0, shard_n_boundary = 0;
-  LaggedScalar lag_rr;               // residual norm of the Krylov loop, read half an iteration late (linalg.inc)
-  Buf<int32_t> node_redo;            // nodes the lean MPFA launches hand to the full body (mpfa_numeric.inc)
+  Buf<int32_t> node_redo;            // nodes the unpivoted MPFA elimination hands to the pivoted body (mpfa_numeric.inc)
   std::function<void(stream_t, int64_t)> node_redo_launch;  // ... and the launch that takes them (set by launch_node_kernel)
   int64_t stats_node_redo = 0;
   Buf<int32_t> mpsa_redo;            // nodes the lean MPSA launches hand to the full body (mpsa.inc)

@@ -945,15 +945,6 @@ static SolveResult krylov_solve(pfv_ctx_impl& c, const LinSys& sys, int method, 
   constexpr int kTrueResidualRestarts = 3;
   int restarts = 0;
   int it = 1;
-  // Non-sharded loops read the residual HALF AN ITERATION LATE: the copy of (r, r) is enqueued behind the iteration's last
-  // kernel, the first half of the next iteration goes out, and only then the host looks at the value -- the GPU works
-  // on that half meanwhile instead of idling through the host round trip of a blocking read (120 us per iteration at
-  // 2 M cells).  If the value says "converged", the half iteration is dropped: it has touched p, v, y, z and r (= s) but
-  // not x, and the true-residual check below recomputes r from x.  OFF by default (PFV_LAGGED_CHECK=1 switches it on):
-  // measured 72.0 against 70.8 ms per step -- outside the profiler the blocking read costs less than the half iteration
-  // that is thrown away at the end (0.8 ms).
-  const bool lagged = !sharded && env_int("PFV_LAGGED_CHECK", 0) != 0;
-  c.lag_rr.pending = false;
 restart_bicgstab:
   be_d2d(rhat, r, sizeof(double) * n, s);
   be_memset(p, 0, sizeof(double) * n, s);
@@ -982,12 +973,6 @@ restart_bicgstab:
         r[i] = si;
         z[i] = si / diag[i];
       });
-    }
-    if (lagged && c.lag_rr.pending) {
-      const double rr = c.lag_rr.take();  // (r, r) of iteration it - 1
-      res.relres = std::sqrt(rr / bb);
-      if (rr <= tol2) { res.converged = true; res.iterations = it - 1; break; }
-      if (!(rr == rr)) { res.iterations = it - 1; break; }
     }
     if (merged) {
       // t = A z; the five sums in one all-reduce; omega, rho, beta, (r,r) on the device; the vector update needs no
@@ -1022,16 +1007,13 @@ restart_bicgstab:
 #endif
     }
     res.iterations = it;
-    if (lagged && it < maxit) {
-      c.lag_rr.issue(S + S_RR, s);
-    } else if (it % check_every == 0 || it == maxit) {
+    if (it % check_every == 0 || it == maxit) {
       const double rr = read_scalar<double>(s, S + S_RR);
       res.relres = std::sqrt(rr / bb);
       if (rr <= tol2) { res.converged = true; break; }
       if (!(rr == rr)) break;
     }
   }
-  c.lag_rr.pending = false;
   if (res.converged && !sharded && env_int("PFV_TRUE_RESIDUAL", 1) != 0) {
     sys_spmv(c, sys, d_x, t);
     parallel_for(s, n, PFV_LAMBDA(int64_t i) { r[i] = d_b[i] - t[i]; });

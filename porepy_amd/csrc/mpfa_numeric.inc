@@ -55,11 +55,9 @@ struct Carver {
   }
 };
 
-// lean: without the three vectors only the refinement stage, the LDS Gauss-Jordan and the LDS pivot-row variant use
-// (an interior node of a tetrahedral grid then needs 16 188 instead of 17 116 bytes: 10 instead of 9 nodes per CU)
-static size_t node_lds_bytes(int nmax, int degmax, int nd, bool lean = false) {
+static size_t node_lds_bytes(int nmax, int degmax, int nd) {
   const size_t ld = (size_t)nmax | 1;
-  size_t d = (size_t)nmax * ld + (lean ? 4 * (size_t)nmax : 7 * (size_t)nmax + 8) + 2 * (size_t)degmax * nd * nd;  // doubles
+  size_t d = (size_t)nmax * ld + 7 * (size_t)nmax + 8 + 2 * (size_t)degmax * nd * nd;  // doubles
   size_t i = 4 * (size_t)nmax + 8;                                                 // int32 (ipiv is padded; 2 flag words)
   size_t b = (size_t)nmax + 3 * (size_t)degmax * nd;                               // bytes
   return d * 8 + i * 4 + b + 64;
@@ -200,7 +198,7 @@ struct NodeArgs {
   const uint8_t* active;  // partial discretization: only nodes with active[v] != 0 (nullptr = all)
   int sub_bc;             // conditions per sub-face: bcflag / robin are indexed by sub-face id
   int refine;             // 0: refine where kappa asks for it; -1 never; k > 0: always k steps
-  int32_t* redo;          // lean launches: nodes whose kappa asks for refinement, left to the full body (count in st[2])
+  int32_t* redo;          // unpivoted elimination: nodes that fail its check, left to the pivoted body (count in st[2])
 };
 
 // L.bg: right-hand side of sub-face lf(j, k) per unit source component b in sub-cell j, stored sub-cell by sub-cell,
@@ -217,18 +215,18 @@ struct NodeLds {
   int8_t* sgL;
 };
 
-PFV_FN void node_carve(char* lds, int n, int ld, int nh, int nd, NodeLds& L, bool lean = false) {
+PFV_FN void node_carve(char* lds, int n, int ld, int nh, int nd, NodeLds& L) {
   Carver cv(lds);
   L.A = cv.take<double>((size_t)n * ld);
   L.scale = cv.take<double>(n);
-  L.rowk = lean ? nullptr : cv.take<double>(n);
-  L.colk = lean ? nullptr : cv.take<double>(n);
+  L.rowk = cv.take<double>(n);
+  L.colk = cv.take<double>(n);
   L.robw = cv.take<double>(n);
   L.etal = cv.take<double>(n);
   L.beta = cv.take<double>(n);
   L.om = cv.take<double>((size_t)nh * nd);
   L.bg = cv.take<double>((size_t)nh * nd);  // [j][k][b]: rhs of sub-face lf(j,k) per unit source b in cell j (bg_index)
-  L.prow = lean ? nullptr : cv.take<double>(n + 8);  // pivot row of the register Gauss-Jordan (16-byte aligned: A is)
+  L.prow = cv.take<double>(n + 8);  // pivot row of the register Gauss-Jordan (16-byte aligned: A is)
   L.fid = cv.take<int32_t>(n);
   L.sfid = cv.take<int32_t>(n);
   L.ipiv = cv.take<int32_t>(n + 4);  // the register Gauss-Jordan pads n up to a multiple of 4
@@ -862,7 +860,7 @@ __device__ __forceinline__ void node_gj_reg2d(const WaveCtx& w, const NodeLds& L
 // its own flux-continuity row), but nothing guarantees it: the caller checks the inverse a posteriori -- one
 // Freivalds-type product, r = v - A (X v) evaluated from the defining coefficients (node_residual_update), against
 // a tolerance that admits the rounding of a stable elimination with growth <= 64 and nothing more -- and hands a node
-// that fails to the pivoted body (the redo list of the lean launches).  Returns X = A^-1 in L.A (natural order),
+// that fails to the pivoted body (the redo list).  Returns X = A^-1 in L.A (natural order),
 // t = X v in tv[0..n), kappa = ||X||_inf (wave-uniform); `degenerate`: a pivot was zero / tiny / non-finite.
 PFV_HD inline double freivalds_v(int c) { return 1.0 + 0.0625 * (double)((c * 11) & 15); }
 
@@ -968,26 +966,6 @@ __device__ __forceinline__ double node_gj_reg2d_np(const WaveCtx& w, const NodeL
   const unsigned long long kb = group_max_u64<64>((unsigned long long)__double_as_longlong(kmax), 0);
   w.lsync();
   return __longlong_as_double((long long)kb);
-}
-#endif
-
-#ifndef PFV_EMULATE
-// The elimination on the FP64 matrix cores (gj_mfma.inc): blocked by 4 pivot columns, the update of the 48 x 48 padded
-// matrix is 9 v_mfma_f64_16x16x4 per panel.  Same contract as node_gj_reg2d: A^-1 in L.A, pivot rows in L.ipiv, the
-// refinement steps kappa = ||A^-1||_inf asks for in L.flag[0], singular systems flagged in st[0].
-__device__ __forceinline__ void node_gj_mfma(const WaveCtx& w, const NodeLds& L, int n, int ld, int v, int32_t* st,
-                                             int refine) {
-  bool bad;
-  const double kappa = gj_mfma48(L.A, n, ld, L.ipiv, kPivotTiny, bad);
-  const int lane = (int)threadIdx.x & 63;
-  if (bad && lane == 0) atomicMax(st + 0, v + 1);
-  if (refine >= 0) {
-    const int steps = refine_steps_for(kappa, refine);  // (monotone in kappa: the largest row decides)
-    if (steps >= 1) L.flag[0] = 1;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    if (steps >= 2) L.flag[0] = 2;
-  }
-  w.lsync();
 }
 #endif
 
@@ -1223,9 +1201,7 @@ PFV_FN void node_finish(const NodeArgs& a, const WaveCtx& w, const NodeLds& L, i
 
 // MODE 0: LDS Gauss-Jordan (portable); MODE G > 0: register Gauss-Jordan, G lanes per node, NR column
 // registers per lane, pivot row broadcast through LDS if BC
-// LEAN (lane-grid Gauss-Jordan only): the LDS block without the refinement scratch; a node whose kappa asks for
-// refinement is appended to a.redo and left to a launch of the full body (check_node_status)
-template <int MODE, int ND, int NR = 64, int BC = 0, bool LEAN = false>
+template <int MODE, int ND, int NR = 64, int BC = 0>
 PFV_FN void node_body(const NodeArgs& a, const WaveCtx& w, int64_t first) {
   int v = a.order[first + w.item];
   if (a.active && !a.active[v]) return;
@@ -1245,7 +1221,7 @@ PFV_FN void node_body(const NodeArgs& a, const WaveCtx& w, int64_t first) {
   const int ld = n | 1;
   const int64_t t0 = a.tptr[v];
   NodeLds L;
-  node_carve(w.lds, n, ld, nh, a.nd, L, LEAN);
+  node_carve(w.lds, n, ld, nh, a.nd, L);
   if (!(a.ablate & 4)) node_setup<ND>(a, w, L, v, h0, nh, f0, n, ld, t0);
   if (!(a.ablate & 1)) {
 #ifndef PFV_EMULATE
@@ -1269,10 +1245,6 @@ PFV_FN void node_body(const NodeArgs& a, const WaveCtx& w, int64_t first) {
         if (w.lane0()) L.flag[0] = steps;
       }
       w.lsync();
-    } else if constexpr (MODE == 64 && BC == 4) {
-      // (n x ld doubles of L.A serve as the scratch of the blocked elimination: 33 x 33 at the least in these classes)
-      if (n <= 48 && n * ld >= kGjmScratchDoubles) node_gj_mfma(w, L, n, ld, v, a.st, a.refine);
-      else node_gj_reg2d<(NR + 7) / 8>(w, L, n, ld, v, a.st, a.refine);
     } else if constexpr (MODE == 64 && BC == 3) {
       node_gj_reg2d<(NR + 7) / 8>(w, L, n, ld, v, a.st, a.refine);
     } else if constexpr (MODE > 0) {
@@ -1300,12 +1272,6 @@ PFV_FN void node_body(const NodeArgs& a, const WaveCtx& w, int64_t first) {
       w.lsync();
     }
   }
-  if constexpr (LEAN) {
-    if (a.refine >= 0 && L.flag[0] > 0) {  // (wave-uniform: read from LDS after the Gauss-Jordan's fence)
-      if (w.lane0()) a.redo[atomic_fetch_add_i32(a.st + 2, 1)] = v;
-      return;
-    }
-  }
   if (!(a.ablate & 2)) node_finish<ND>(a, w, L, v, nh, n, ld, t0);
 }
 
@@ -1314,27 +1280,18 @@ static void launch_node_class_reg(stream_t s, const NodeArgs& a, int64_t b0, int
 #ifdef PFV_EMULATE
   wave_for<64>(s, count, lds, PFV_LAMBDA(const WaveCtx& w) { node_body<0, ND>(a, w, b0); });
 #else
-  if constexpr (G == 64 && BC == 5) {
-    // (unpivoted lane grid: full LDS block -- the acceptance test uses the refinement scratch --, failures go to a.redo)
+  if constexpr (G == 64 && BC >= 3) {
+    // (the lane-grid forms: 3 wavefronts per SIMD kept by the register allocation; the unpivoted one, BC 5, hands the
+    // nodes that fail its check to a.redo)
     wave_for_occ<G, 3>(s, count, lds, PFV_LAMBDA(const WaveCtx& w) { node_body<G, ND, NR, BC>(a, w, b0); });
   } else {
-  if constexpr (G == 64 && BC >= 3) {
-    // (the lane-grid form: 3 wavefronts per SIMD kept by the register allocation, PFV_NODE_OCC=0: as the compiler likes)
-    if (a.redo) {  // lean LDS block (the caller sized `lds` for it)
-      wave_for_occ<G, 3>(s, count, lds, PFV_LAMBDA(const WaveCtx& w) { node_body<G, ND, NR, BC, true>(a, w, b0); });
-      return;
-    }
-    if (env_int("PFV_NODE_OCC", 1) != 0) {
-      wave_for_occ<G, 3>(s, count, lds, PFV_LAMBDA(const WaveCtx& w) { node_body<G, ND, NR, BC>(a, w, b0); });
-      return;
-    }
-  }
-  wave_for<G>(s, count, lds, PFV_LAMBDA(const WaveCtx& w) { node_body<G, ND, NR, BC>(a, w, b0); });
+    wave_for<G>(s, count, lds, PFV_LAMBDA(const WaveCtx& w) { node_body<G, ND, NR, BC>(a, w, b0); });
   }
 #endif
 }
 // mode: 0 LDS Gauss-Jordan, 1 register Gauss-Jordan with lane broadcasts, 2 with the pivot row through
-// LDS, 3 lane broadcasts + 32-bit pivot search, 4 as 3 with the 8 x 8 lane grid for one-node wavefronts
+// LDS, 3 lane broadcasts + 32-bit pivot search, 4 as 3 with the 8 x 8 lane grid for one-node wavefronts,
+// 5 as 4 without row exchanges for 32 < n <= 48 (verified, failures to a.redo)
 template <int G, int NR = G>
 static void launch_node_class(stream_t s, const NodeArgs& a, int64_t b0, int64_t count, size_t lds, int mode) {
   if (mode == 0) {
@@ -1346,17 +1303,12 @@ static void launch_node_class(stream_t s, const NodeArgs& a, int64_t b0, int64_t
   } else if (mode == 3) {
     if (a.nd == 2) launch_node_class_reg<G, 2, NR, 2>(s, a, b0, count, lds);
     else launch_node_class_reg<G, 3, NR, 2>(s, a, b0, count, lds);
-  } else if (mode == 6 && G == 64 && NR <= 48) {
+  } else if (mode == 5 && G == 64 && NR <= 48) {
     if constexpr (G == 64 && NR <= 48) {  // unpivoted lane grid, verified (node_gj_reg2d_np)
       if (a.nd == 2) launch_node_class_reg<G, 2, NR, 5>(s, a, b0, count, lds);
       else launch_node_class_reg<G, 3, NR, 5>(s, a, b0, count, lds);
     }
-  } else if (mode == 5 && G == 64 && NR <= 48) {
-    if constexpr (G == 64 && NR <= 48) {  // matrix-core elimination (node_gj_mfma)
-      if (a.nd == 2) launch_node_class_reg<G, 2, NR, 4>(s, a, b0, count, lds);
-      else launch_node_class_reg<G, 3, NR, 4>(s, a, b0, count, lds);
-    }
-  } else if (mode == 4 || mode == 5 || mode == 6) {
+  } else if (mode == 4 || mode == 5) {
     if constexpr (G == 64) {
       if (a.nd == 2) launch_node_class_reg<G, 2, NR, 3>(s, a, b0, count, lds);
       else launch_node_class_reg<G, 3, NR, 3>(s, a, b0, count, lds);
@@ -1371,10 +1323,7 @@ static void launch_node_class(stream_t s, const NodeArgs& a, int64_t b0, int64_t
 }
 
 // launches only (on stream s, which may be the handle's second stream); check_node_status reads the flags.
-// after_run != nullptr (node || face pipeline, c.pipe_chunks > 0): the classes other than c.pipe_class are launched first,
-// then (*after_run)(0); then the runs of c.pipe_class one launch each, (*after_run)(q + 1) after run q.
-static void launch_node_kernel(pfv_ctx_impl& c, const uint8_t* active, stream_t s,
-                               const std::function<void(int)>* after_run = nullptr) {
+static void launch_node_kernel(pfv_ctx_impl& c, const uint8_t* active, stream_t s) {
   const int nd = c.nd;
   c.tab.ensure(std::max<int64_t>(c.tab_len, 2));
   c.tabb.ensure(std::max<int64_t>(c.tabb_len, 2));
@@ -1410,34 +1359,24 @@ static void launch_node_kernel(pfv_ctx_impl& c, const uint8_t* active, stream_t 
   c.node_redo_launch = nullptr;
   size_t redo_lds = 0;
   int redo_nr = 0;
-  const bool piped = after_run != nullptr && c.pipe_chunks > 0 && c.pipe_class >= 0;
-  for (int pass = 0; pass < (piped ? 2 : 1); ++pass) {
   for (int cls = 0; cls < kNumClasses; ++cls) {
-    if (piped && ((pass == 0) == (cls == c.pipe_class))) continue;  // pass 0: the other classes, pass 1: the pipelined one
     const int64_t b0 = c.class_begin[cls], b1 = c.class_begin[cls + 1];
     if (b1 <= b0) continue;
     const int nmax = std::min(kClassBounds[cls], std::max(c.max_block, 1));
     const int degmax = std::max(1, std::min(c.max_deg, 2 * nmax / nd));
-    size_t lds = node_lds_bytes(nmax, degmax, nd);
+    const size_t lds = node_lds_bytes(nmax, degmax, nd);
     if (lds > 160 * 1024)
       throw Error(PFV_ERR_UNSUPPORTED, "interaction region too large for LDS (more than ~140 faces meet in a node)");
 #ifndef PFV_EMULATE
     {
-      // lean launches of the lane-grid classes (PFV_NODE_LEAN=1): no refinement scratch in LDS (16 188 instead of
-      // 17 116 bytes: one more node per CU); the few nodes whose kappa asks for refinement are redone by the full body
-      // (check_node_status).  OFF: measured 10.05 against 10.10 ms -- the tenth wavefront per CU buys nothing, the
-      // kernel is bound by instruction issue, not by latency at this occupancy
-      const int gj0 = env_int("PFV_NODE_GJ", kNodeGjDefault);
-      const bool lean = !force_lds && gj0 == 3 && nmax > 32 && nmax <= 64 && a.refine == 0 && a.ablate == 0 &&
-                        env_int("PFV_NODE_LEAN", 0) != 0;
       // PFV_NODE_GJ=5: the classes with 32 < n <= 48 eliminate without row exchanges and verify (node_gj_reg2d_np);
-      // nodes that fail the check go to the redo list like the ones a lean launch leaves
-      const bool optimistic = !force_lds && gj0 == 5 && nmax > 32 && nmax <= 48 && (a.ablate & 1) == 0;
-      a.redo = (lean || optimistic) ? c.node_redo.ensure(std::max<int64_t>(c.nn, 1)) : nullptr;
-      if (lean || optimistic) {
+      // nodes that fail the check go to the redo list, which check_node_status hands to the pivoted body
+      const bool optimistic = !force_lds && env_int("PFV_NODE_GJ", kNodeGjDefault) == 5 && nmax > 32 && nmax <= 48 &&
+                              (a.ablate & 1) == 0;
+      a.redo = optimistic ? c.node_redo.ensure(std::max<int64_t>(c.nn, 1)) : nullptr;
+      if (optimistic) {
         redo_lds = std::max(redo_lds, lds);
-        redo_nr = std::max(redo_nr, nmax <= 40 ? 40 : (nmax <= 48 ? 48 : 64));
-        if (lean) lds = node_lds_bytes(nmax, degmax, nd, true);
+        redo_nr = std::max(redo_nr, nmax <= 40 ? 40 : 48);
       }
     }
 #endif
@@ -1446,28 +1385,15 @@ static void launch_node_kernel(pfv_ctx_impl& c, const uint8_t* active, stream_t 
     // irrelevant for partial pivoting on the row-scaled systems): 11.0 against 11.3 ms, same parity
     const int gjv = env_int("PFV_NODE_GJ", kNodeGjDefault);
     // 3: as 2, and the one-node-per-wavefront classes (32 < n <= 64) on the 8 x 8 lane grid (node_gj_reg2d)
-    // 4: as 3, and the classes with 32 < n <= 48 eliminate on the FP64 matrix cores (node_gj_mfma, gj_mfma.inc)
     // 5: as 3, and the classes with 32 < n <= 48 WITHOUT the pivot search, verified afterwards (node_gj_reg2d_np)
-    const int mode = (force_lds || nmax > 64) ? 0 : (gjv == 1 ? 2 : (gjv == 2 ? 3 : (gjv == 3 ? 4 : (gjv == 4 ? 5 : (gjv == 5 ? 6 : 1)))));
-    auto launch_range = [&](int64_t lo, int64_t cnt) {
-      if (cnt <= 0) return;
-      if (nmax <= 8) launch_node_class<8>(s, a, lo, cnt, lds, mode);
-      else if (nmax <= 16) launch_node_class<16>(s, a, lo, cnt, lds, mode);
-      else if (nmax <= 32) launch_node_class<32>(s, a, lo, cnt, lds, mode);
-      else if (nmax <= 40) launch_node_class<64, 40>(s, a, lo, cnt, lds, mode);
-      else if (nmax <= 48) launch_node_class<64, 48>(s, a, lo, cnt, lds, mode);
-      else launch_node_class<64, 64>(s, a, lo, cnt, lds, mode);
-    };
-    if (piped && pass == 1) {
-      for (int q = 0; q < c.pipe_chunks; ++q) {
-        launch_range(c.pipe_node_begin[q], c.pipe_node_begin[q + 1] - c.pipe_node_begin[q]);
-        (*after_run)(q + 1);
-      }
-    } else {
-      launch_range(b0, b1 - b0);
-    }
-  }
-  if (piped && pass == 0) (*after_run)(0);
+    const int mode = (force_lds || nmax > 64) ? 0 : (gjv == 1 ? 2 : (gjv == 2 ? 3 : (gjv == 3 ? 4 : (gjv == 5 ? 5 : 1))));
+    const int64_t cnt = b1 - b0;
+    if (nmax <= 8) launch_node_class<8>(s, a, b0, cnt, lds, mode);
+    else if (nmax <= 16) launch_node_class<16>(s, a, b0, cnt, lds, mode);
+    else if (nmax <= 32) launch_node_class<32>(s, a, b0, cnt, lds, mode);
+    else if (nmax <= 40) launch_node_class<64, 40>(s, a, b0, cnt, lds, mode);
+    else if (nmax <= 48) launch_node_class<64, 48>(s, a, b0, cnt, lds, mode);
+    else launch_node_class<64, 64>(s, a, b0, cnt, lds, mode);
   }
 #ifndef PFV_EMULATE
   if (redo_lds > 0) {
@@ -1478,8 +1404,7 @@ static void launch_node_kernel(pfv_ctx_impl& c, const uint8_t* active, stream_t 
     const size_t lds2 = redo_lds;
     c.node_redo_launch = [a2, nr, lds2](stream_t s2, int64_t count) {
       if (nr <= 40) launch_node_class<64, 40>(s2, a2, 0, count, lds2, 4);
-      else if (nr <= 48) launch_node_class<64, 48>(s2, a2, 0, count, lds2, 4);
-      else launch_node_class<64, 64>(s2, a2, 0, count, lds2, 4);
+      else launch_node_class<64, 48>(s2, a2, 0, count, lds2, 4);
     };
   }
 #endif
@@ -1490,7 +1415,7 @@ static void check_node_status(pfv_ctx_impl& c, stream_t s) {
   be_d2h(sth, c.status.p, sizeof(sth), s);
   c.stats_node_redo = 0;
   if (c.node_redo_launch && sth[2] > 0 && !sth[0] && !sth[1]) {
-    // nodes the lean launches left (kappa above kRefineKappa): the full body with its refinement stage
+    // nodes the unpivoted elimination left (its check failed): the pivoted body
     c.stats_node_redo = sth[2];
     c.node_redo_launch(s, sth[2]);
     be_d2h(sth, c.status.p, sizeof(sth), s);
@@ -1714,21 +1639,11 @@ struct FacePipeArgs {
   int maxfn;
   FaceLds SL;
   size_t cpw_off;  // LDS offset of the column-map words
-  int nt;          // non-temporal stores of the CSR values (PFV_FACE_NT): the 14 GB of output do not displace the
-                   // table rows the neighbouring faces are about to re-read from L2
   int run;         // consecutive faces of the processing order one wavefront takes per grab (PFV_FACE_RUN)
   int32_t* ctr;    // != nullptr: runs are handed out by one atomic counter per XCD (64 bytes apart) instead of by a
                    // fixed stride -- the wavefronts of an XCD then stay within one narrow window of the order
                    // whatever their individual speeds (PFV_FACE_DYN)
-  int cache;       // > 0: slots of the wavefront's LDS cache of raw table rows (PFV_FACE_CACHE), see k_face_pipe
-  size_t raw_off;  // LDS offset of the cache: [slot][nd + 1 rows][ldtmax doubles]
-  int ldtmax;      // doubles per cached row
 };
-
-__device__ __forceinline__ void face_store(double* p, double v, int nt) {
-  if (nt) __builtin_nontemporal_store(v, p);
-  else *p = v;
-}
 
 __device__ __forceinline__ void wave_sync_lds() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -1784,8 +1699,8 @@ __device__ __forceinline__ void face_pipe_columns(const FacePipeArgs& P, const u
           }
         }
       }
-      face_store(P.vq + p0 + k, q, P.nt);
-      face_store(P.vt + p0 + k, t, P.nt);
+      P.vq[p0 + k] = q;
+      P.vt[p0 + k] = t;
     }
   }
   if (P.vqv) {
@@ -1817,19 +1732,13 @@ __device__ __forceinline__ void face_pipe_columns(const FacePipeArgs& P, const u
           }
         }
       }
-      face_store(P.vqv + (int64_t)p0 * ND + x, qv, P.nt);
-      face_store(P.vtv + (int64_t)p0 * ND + x, tv, P.nt);
+      P.vqv[(int64_t)p0 * ND + x] = qv;
+      P.vtv[(int64_t)p0 * ND + x] = tv;
     }
   }
 }
 
-// CACHE: the faces come in CELL-MAJOR order (topology.inc: PFV_FACE_ORDER=1: the faces whose flux is taken from the same cell
-// back to back) and the wavefront keeps the raw table rows of the last few (node, sub-cell) pairs in LDS -- the three
-// rows r_k of the sub-cell and the node's e-row, 4 x ldt doubles per slot.  The <= 3 faces of a cell at one node read the
-// SAME rows: what the L2 cannot provide at this concurrency (512 wavefronts per XCD stream 3.6 MB per face time through
-// a 4 MB cache: a row is gone before the next face of the same wavefront asks for it) the slot provides -- 42 % of the
-// row reads of a tetrahedral grid are hits.  A miss costs one more LDS round trip (global -> LDS -> registers).
-template <int ND, bool CACHE = false>
+template <int ND>
 __global__ void __launch_bounds__(64) k_face_pipe(const FacePipeArgs P) {
   extern __shared__ __attribute__((aligned(16))) char pfv_lds[];
   const int lane = (int)threadIdx.x;
@@ -1881,15 +1790,6 @@ __global__ void __launch_bounds__(64) k_face_pipe(const FacePipeArgs P) {
     --left;
     return cur++;
   };
-  // cache state (wave-uniform): key of every slot = table offset of the node * 256 + sub-cell, next victim
-  double* RAW = reinterpret_cast<double*>(pfv_lds + P.raw_off);
-  constexpr int kSlotsMax = 8;
-  long long ckey[kSlotsMax];
-#pragma unroll
-  for (int q = 0; q < kSlotsMax; ++q) ckey[q] = -1;
-  int crr = 0;
-  const int nslots = CACHE ? (P.cache < kSlotsMax ? P.cache : kSlotsMax) : 0;
-  const int slot_doubles = (ND + 1) * P.ldtmax;
   FaceRec F0 = load_frec(next_pos());
   FaceRec F1 = load_frec(next_pos());
   double R0 = 0.0;
@@ -1944,72 +1844,24 @@ __global__ void __launch_bounds__(64) k_face_pipe(const FacePipeArgs P) {
       offs[kMaxFaceNodes] = m;
       offs2[kMaxFaceNodes] = m2;
     }
-    int nslot[kMaxFaceNodes];
-    if constexpr (CACHE) {
-      // which slot holds the rows of every node's (node, sub-cell) pair; misses are loaded now (all lanes, 16 bytes
-      // each), victims taken round robin among the slots no node of THIS face uses
-      unsigned used = 0u;
-#pragma unroll
-      for (int i = 0; i < kMaxFaceNodes; ++i) {
-        nslot[i] = 0;
-        if (i < nnf) {
-          const SfRec& R = recL[i];
-          const long long toff = __builtin_amdgcn_readfirstlane((int)(R.toff & 0xffffffffll)) & 0xffffffffll |
-                                 ((long long)__builtin_amdgcn_readfirstlane((int)(R.toff >> 32)) << 32);
-          const int js = __builtin_amdgcn_readfirstlane((int)R.jstar);
-          const long long key = toff * 256 + js;
-          int hit = -1;
-#pragma unroll
-          for (int q = 0; q < kSlotsMax; ++q) hit = (q < nslots && ckey[q] == key) ? q : hit;
-          if (hit < 0) {
-            int vq = crr;
-            for (int tries = 0; tries < kSlotsMax && ((used >> vq) & 1u); ++tries) vq = vq + 1 < nslots ? vq + 1 : 0;
-            hit = vq;
-            crr = vq + 1 < nslots ? vq + 1 : 0;
-#pragma unroll
-            for (int q = 0; q < kSlotsMax; ++q) ckey[q] = (q == hit) ? key : ckey[q];
-            const int nh = ND * (int)R.deg, ldt = (nh + 1) & ~1, half = ldt >> 1;
-            const double* base = P.tab + toff;
-            double* dst = RAW + (size_t)hit * slot_doubles;
-            for (int u = lane; u < (ND + 1) * half; u += 64) {
-              const int row = u / half, x0 = 2 * (u - row * half);
-              const int srow = row < ND ? (int)R.r[row < ND ? row : 0] : (int)R.n;
-              *reinterpret_cast<D2*>(dst + row * P.ldtmax + x0) = *reinterpret_cast<const D2*>(base + srow * ldt + x0);
-            }
-          }
-          used |= 1u << hit;
-          nslot[i] = hit;
-        }
-      }
-      wave_sync_lds();
-    }
     for (int t = lane; t < m2; t += 64) {
       int i = 0;
 #pragma unroll
       for (int ii = 1; ii < kMaxFaceNodes; ++ii) i += (ii < nnf && t >= offs2[ii]) ? 1 : 0;
-      int o2 = 0, o1 = 0, sl = 0;
+      int o2 = 0, o1 = 0;
 #pragma unroll
       for (int ii = 0; ii < kMaxFaceNodes; ++ii) {
         o2 = (ii == i) ? offs2[ii] : o2;
         o1 = (ii == i) ? offs[ii] : o1;
-        if constexpr (CACHE) sl = (ii == i) ? nslot[ii] : sl;
       }
       const int x0 = 2 * (t - o2);
       const SfRec& R = recL[i];
       const int nh = ND * (int)R.deg, ldt = (nh + 1) & ~1;
       const double* base = P.tab + R.toff;
       D2 rv[ND];
-      D2 ee;
-      if constexpr (CACHE) {
-        const double* src = RAW + (size_t)sl * slot_doubles + x0;
 #pragma unroll
-        for (int k = 0; k < ND; ++k) rv[k] = *reinterpret_cast<const D2*>(src + k * P.ldtmax);
-        ee = *reinterpret_cast<const D2*>(src + ND * P.ldtmax);
-      } else {
-#pragma unroll
-        for (int k = 0; k < ND; ++k) rv[k] = *reinterpret_cast<const D2*>(base + (int)R.r[k] * ldt + x0);
-        ee = *reinterpret_cast<const D2*>(base + (int)R.n * ldt + x0);
-      }
+      for (int k = 0; k < ND; ++k) rv[k] = *reinterpret_cast<const D2*>(base + (int)R.r[k] * ldt + x0);
+      const D2 ee = *reinterpret_cast<const D2*>(base + (int)R.n * ldt + x0);
       const int ls = R.ls, js = R.jstar;
       int ksel = 0;
 #pragma unroll
@@ -2072,54 +1924,44 @@ __global__ void __launch_bounds__(64) k_face_pipe(const FacePipeArgs P) {
   }
 }
 
-static bool launch_face_pipe(pfv_ctx_impl& c, const FaceArgs& A, const FaceLds& SL, int64_t nitems, int64_t first = 0,
-                             bool any_size = false) {
+static bool launch_face_pipe(pfv_ctx_impl& c, const FaceArgs& A, const FaceLds& SL, int64_t nitems) {
   // limits of the register-parked prefetches: 8 nodes per face, 512 bytes of column map per row
-  if (c.nd != 3 || (nitems < 4096 && !any_size) || A.maxfn > kMaxFaceNodes || (int64_t)A.maxrow * A.maxfn + 3 > 512) return false;
+  if (c.nd != 3 || nitems < 4096 || A.maxfn > kMaxFaceNodes || (int64_t)A.maxrow * A.maxfn + 3 > 512) return false;
   FacePipeArgs P;
-  P.frec = c.face_rec.p + first; P.rec = A.rec; P.colpairs = A.colpairs; P.tab = A.tab; P.tabb = A.tabb; P.tbptr = A.tbptr;
+  P.frec = c.face_rec.p; P.rec = A.rec; P.colpairs = A.colpairs; P.tab = A.tab; P.tabb = A.tabb; P.tbptr = A.tbptr;
   P.fn_idx = A.fn_idx; P.bix = A.bix; P.bp = A.bp; P.bfc = A.bfc;
   P.vq = A.vq; P.vt = A.vt; P.vqb = A.vqb; P.vtb = A.vtb; P.vqv = A.vqv; P.vtv = A.vtv;
   P.n = nitems; P.maxfn = A.maxfn; P.SL = SL; P.cp_stride = A.cp_stride;
   P.cpw_off = SL.total;
-  P.nt = env_int("PFV_FACE_NT", 0);
   P.run = std::max(1, env_int("PFV_FACE_RUN", 4));
   P.ctr = nullptr;
   if (env_int("PFV_FACE_DYN", 1) != 0) {
-    // (one set of 8 counters per launch in flight: the runs of the node || face pipeline follow each other on the stream,
-    // but a counter set is zeroed by a memset ENQUEUED before its launch -- 32 sets, cycled)
+    // (one set of 8 counters per launch in flight: face kernels may follow each other on the stream, but a counter set
+    // is zeroed by a memset ENQUEUED before its launch -- 32 sets, cycled)
     int32_t* base = c.face_ctr.ensure(32 * 8 * 16);
     P.ctr = base + (size_t)(c.face_ctr_next++ % 32) * 8 * 16;
     be_memset(P.ctr, 0, sizeof(int32_t) * 8 * 16, c.stream);
   }
-  // PFV_FACE_CACHE = slots of the LDS cache of raw table rows (0: off); needs the cell-major face order
-  P.cache = (c.face_order_cell_major && c.nd == 3) ? std::max(0, std::min(8, env_int("PFV_FACE_CACHE", 0))) : 0;
-  P.ldtmax = (c.nd * std::max(c.max_deg, 1) + 1) & ~1;
-  P.raw_off = (SL.total + 512 + 15) & ~size_t(15);
-  const size_t lds = P.cache > 0 ? P.raw_off + (size_t)P.cache * (c.nd + 1) * P.ldtmax * sizeof(double) : SL.total + 512;
+  const size_t lds = SL.total + 512;
   if (lds > 64 * 1024) return false;
   // persistent: exactly the wavefronts that are resident at once, so that the 8 ranges are swept once
   // (a second generation of workgroups would walk the tables a second time, long after L2 dropped them)
   static int num_cu = 0;
   if (!num_cu) PFV_HIP_CHECK(hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, c.device));
   int occ = 0;
-  if (P.cache > 0) PFV_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_face_pipe<3, true>, 64, lds));
-  else PFV_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_face_pipe<3>, 64, lds));
+  PFV_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_face_pipe<3>, 64, lds));
   if (occ < 1) return false;
   int64_t blocks = (int64_t)num_cu * occ;
   blocks = std::min<int64_t>(blocks, env_int("PFV_FACE_PIPE_BLOCKS", 1 << 30));
   blocks = std::max<int64_t>((blocks + 7) & ~int64_t(7), 8);
-  if (P.cache > 0) PFV_LAUNCH(HIP_KERNEL_NAME(k_face_pipe<3, true>), dim3((unsigned)blocks), dim3(64), lds, c.stream, P);
-  else PFV_LAUNCH(HIP_KERNEL_NAME(k_face_pipe<3>), dim3((unsigned)blocks), dim3(64), lds, c.stream, P);
+  PFV_LAUNCH(HIP_KERNEL_NAME(k_face_pipe<3>), dim3((unsigned)blocks), dim3(64), lds, c.stream, P);
   PFV_HIP_CHECK(hipGetLastError());
   return true;
 }
 #endif
 
 // subset != nullptr: only the n_subset listed faces (partial discretization)
-// range_count >= 0 (node || face pipeline): the faces at positions [range_first, range_first + range_count) of face_order
-static void run_face_kernel(pfv_ctx_impl& c, bool with_vs, const int32_t* subset = nullptr,
-                            int64_t n_subset = 0, int64_t range_first = 0, int64_t range_count = -1) {
+static void run_face_kernel(pfv_ctx_impl& c, bool with_vs, const int32_t* subset = nullptr, int64_t n_subset = 0) {
   stream_t s = c.stream;
   const int nd = c.nd;
   FaceArgs A;
@@ -2134,7 +1976,7 @@ static void run_face_kernel(pfv_ctx_impl& c, bool with_vs, const int32_t* subset
   A.fn_ptr = c.fn_ptr; A.fn_idx = c.fn_idx;
   A.ip = c.pat_flux.indptr;
   A.bip = c.pat_bound.indptr; A.bix = c.pat_bound.indices;
-  A.order = subset ? subset : c.face_order.p + (range_count >= 0 ? range_first : 0);
+  A.order = subset ? subset : c.face_order.p;
   A.bp = c.node_bptr; A.bfc = c.node_bfaces;
   A.colpairs = c.flux_colpairs;
   A.cp_stride = c.cp_stride;
@@ -2144,7 +1986,7 @@ static void run_face_kernel(pfv_ctx_impl& c, bool with_vs, const int32_t* subset
   A.maxfn = std::max(c.max_face_nodes, 1);
   A.maxpairs = A.maxfn * std::max(c.max_deg, 1);
   const FaceLds SL = face_lds_layout(A.maxfn, A.maxpairs, A.maxbrow, nd);
-  const int64_t nitems = subset ? n_subset : (range_count >= 0 ? range_count : c.nf);
+  const int64_t nitems = subset ? n_subset : c.nf;
   if (nitems <= 0) return;
   // faces run along the Morton curve (face_order): one contiguous range of it per XCD keeps the tables of
   // the nodes a range shares in that XCD's L2
@@ -2152,8 +1994,7 @@ static void run_face_kernel(pfv_ctx_impl& c, bool with_vs, const int32_t* subset
   bool launched = false;
 #ifndef PFV_EMULATE
   // all faces of a 3-D grid: the software-pipelined persistent kernel (k_face_pipe)
-  launched = !subset && env_int("PFV_FACE_PIPE", 1) != 0 &&
-             launch_face_pipe(c, A, SL, nitems, range_count >= 0 ? range_first : 0, range_count >= 0);
+  launched = !subset && env_int("PFV_FACE_PIPE", 1) != 0 && launch_face_pipe(c, A, SL, nitems);
 #endif
   if (launched) {
   } else if (nd == 2) {
@@ -2166,31 +2007,6 @@ static void run_face_kernel(pfv_ctx_impl& c, bool with_vs, const int32_t* subset
   c.filled[PFV_MAT_FLUX] = c.filled[PFV_MAT_BOUND_PRESSURE_CELL] = true;
   c.filled[PFV_MAT_BOUND_FLUX] = c.filled[PFV_MAT_BOUND_PRESSURE_FACE] = true;
   c.filled[PFV_MAT_VECTOR_SOURCE] = c.filled[PFV_MAT_BOUND_PRESSURE_VECTOR_SOURCE] = with_vs;
-}
-
-// node || face pipeline: the faces around the nodes of the redo list (c.node_redo[0 .. n_redo)) recomputed after the redo
-// launch -- their rows were formed from tables the first launch had not finished.  A face two redo nodes share is listed
-// (and recomputed) twice: the same values stored twice.
-static void redo_faces_around_nodes(pfv_ctx_impl& c, bool with_vs, int64_t n_redo) {
-  stream_t s = c.stream;
-  if (n_redo <= 0) return;
-  const int32_t* redo = c.node_redo.p;
-  const int32_t* fp = c.node_fptr;
-  const int32_t* nface = c.node_face;
-  Buf<int32_t> cnt, list;
-  int32_t* cn = cnt.ensure(2);
-  be_memset(cn, 0, sizeof(int32_t) * 2, s);
-  const int64_t cap = n_redo * (int64_t)std::max(c.max_block, 1);
-  int32_t* lst = list.ensure(std::max<int64_t>(cap, 1));
-  parallel_for(s, n_redo, PFV_LAMBDA(int64_t i) {
-    const int v = redo[i];
-    const int n = fp[v + 1] - fp[v];
-    const int o = atomic_fetch_add_i32(cn, n);
-    for (int l = 0; l < n; ++l) lst[o + l] = nface[fp[v] + l];
-  });
-  const int32_t total = read_scalar<int32_t>(s, cn);
-  run_face_kernel(c, with_vs, lst, total);
-  be_sync(s);  // (the list is a local buffer: it must outlive the launch)
 }
 
 // ---- boundary conditions per sub-face (mpfa.py:761-768, 1117-1125): flux / bound_flux / the two trace

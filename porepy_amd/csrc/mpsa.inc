@@ -52,8 +52,6 @@ struct MpsaArgs {
   int64_t tot_p, tot_d, tot_db, tot_c;  // per-key strides of the arrays below
   double *Esp, *Etp, *DD, *BDD, *CONS;
   int ablate;  // profiling only (PFV_MPSA_ABLATE = k): leave the kernel after stage k
-  long long* clk;  // timing lab only (PFV_MPSA_CLOCK): s_memtime stamps of one workgroup
-  int64_t clk_item;
   int lds_gj;  // A/B switch (PFV_MPSA_LDS_GJ): LDS-resident Gauss-Jordan on the device too
   const uint8_t* active;  // partial discretization: only nodes with active[v] != 0 (nullptr = all)
   int refine;             // iterative refinement of the inverse: 0 where kappa asks for it, -1 never, k > 0 always k steps
@@ -479,11 +477,6 @@ PFV_FN void gj_wide(const WaveCtx& w, T* A, T* rowk, T* colk, double* keyd, int3
 
 // BASIS: boundary conditions in a face-wise basis (rows of a boundary sub-face mix the Cartesian
 // components); without it every row involves its own component only and the inner loops collapse
-#ifndef PFV_EMULATE
-#define PFV_MPSA_STAMP(k) do { if (a.clk && w.item == a.clk_item && threadIdx.x == 0) a.clk[k] = (long long)__builtin_readcyclecounter(); } while (0)
-#else
-#define PFV_MPSA_STAMP(k) do { } while (0)
-#endif
 // LEAN: the body without the stages that only special inputs take -- iterative refinement of ill-conditioned regions,
 // continuity points per sub-face, reconstruction_eta, the Biot terms.  Compiled in, they cost the common path registers
 // (256 VGPRs, 322 spilled SGPRs: 63 -> 68 ms at configs[3]).  A lean launch hands the nodes whose kappa asks for
@@ -497,7 +490,6 @@ PFV_FN void mpsa_node_body(const MpsaArgs& a, const WaveCtx& w, int64_t first) {
   double* const arg_Et2 = LEAN ? nullptr : a.Et2;
   double* const arg_Etb2 = LEAN ? nullptr : a.Etb2;
   const int arg_nalpha = LEAN ? 0 : a.nalpha;
-  PFV_MPSA_STAMP(0);
   const int v = a.order[first + w.item];
   if (a.active && !a.active[v]) return;
   if constexpr (!kWide) {
@@ -610,7 +602,6 @@ PFV_FN void mpsa_node_body(const MpsaArgs& a, const WaveCtx& w, int64_t first) {
     }
   }
   w.sync();
-  PFV_MPSA_STAMP(1);
   if (a.ablate == 1) return;
   T wsum = 0.0;
   for (int j = 0; j < deg; ++j) wsum += L.wj[j];
@@ -710,7 +701,6 @@ PFV_FN void mpsa_node_body(const MpsaArgs& a, const WaveCtx& w, int64_t first) {
     for (int cc = 0; cc < n; ++cc) L.A[r * ld + cc] *= sc;
   }
   w.sync();
-  PFV_MPSA_STAMP(2);
   if (a.ablate == 2) return;
   bool np_used = false, np_ok = true;
 #ifndef PFV_EMULATE
@@ -737,7 +727,6 @@ PFV_FN void mpsa_node_body(const MpsaArgs& a, const WaveCtx& w, int64_t first) {
     G.A = L.A; G.rowk = L.rowk; G.colk = L.colk; G.ipiv = L.ipiv;
     node_gj_lds(w, G, n, ld, v, a.st);
   }
-  PFV_MPSA_STAMP(3);
   // kappa = ||(S A)^-1||_inf of the row-scaled system (mpfa_numeric.inc: kRefineKappa)
   if (!kWide && a.refine >= 0) {
     // (row sums once, four independent partial sums per lane: a plain loop waits for every LDS load before it issues
@@ -920,7 +909,6 @@ PFV_FN void mpsa_node_body(const MpsaArgs& a, const WaveCtx& w, int64_t first) {
       w.sync();
     }
   }
-  PFV_MPSA_STAMP(4);
   if (a.ablate == 3) return;
 
   // ---- AG = Ainv Gamma (response of Lambda to the averaged-asymmetric rhs of the Neumann rows),
@@ -955,7 +943,6 @@ PFV_FN void mpsa_node_body(const MpsaArgs& a, const WaveCtx& w, int64_t first) {
     L.PLAG[x] = acc;
   }
   w.sync();
-  PFV_MPSA_STAMP(5);
   if (a.ablate == 4) return;
 
   // ---- Lambda response to unit cell displacements (= trace rows), and P response
@@ -1071,7 +1058,6 @@ PFV_FN void mpsa_node_body(const MpsaArgs& a, const WaveCtx& w, int64_t first) {
     L.Pb[x] = L.PLA[(size_t)q * n + col] * L.beta[col];
   }
   w.sync();  // Et / Etb of this node are read back below by other lanes of the workgroup
-  PFV_MPSA_STAMP(6);
   if (a.ablate == 5) return;
 
   // ---- tractions from the first side of every sub-face
@@ -1167,7 +1153,6 @@ PFV_FN void mpsa_node_body(const MpsaArgs& a, const WaveCtx& w, int64_t first) {
       else Etb2[(size_t)rho * ncb + (col - ncu)] = t_dbl(acc);
     }
   }
-  PFV_MPSA_STAMP(7);
   if (arg_nalpha == 0) return;
 
   // ---- Biot coupling terms, per coupling tensor alpha (biot.py:714-878, 880-1135).  Pressure enters
@@ -1524,19 +1509,13 @@ static void mpsa_run_node_kernel(pfv_ctx_impl& c, const uint8_t* active = nullpt
     a.Et2 = c.Et2.ensure(te + 1);
     a.Etb2 = c.Etb2.ensure(tb + 1);
   }
-  a.clk = nullptr;
-  a.clk_item = env_int("PFV_MPSA_CLOCK", -1);
-  if (a.clk_item >= 0) {
-    a.clk = c.mpsa_clk.ensure(16);
-    be_memset(a.clk, 0, sizeof(long long) * 16, s);
-  }
   a.nalpha = c.have_biot_symbolic ? c.biot_nalpha : 0;
   a.alpha = c.biot_alpha; a.dptr = c.node_dptr; a.dbptr = c.node_dbptr; a.cptr = c.node_cptr;
   a.tot_p = c.biot_tot_p; a.tot_d = c.biot_tot_d; a.tot_db = c.biot_tot_db; a.tot_c = c.biot_tot_c;
   a.Esp = c.bEsp; a.Etp = c.bEtp; a.DD = c.bDD; a.BDD = c.bBDD; a.CONS = c.bCONS;
   // Lean launches (see mpsa_node_body): whenever none of the special stages is asked for.  Nodes whose kappa wants
   // refinement are collected in a.redo and taken by one launch of the full body afterwards.
-  const bool lean = a.eta_sub == nullptr && a.Et2 == nullptr && a.nalpha == 0 && a.refine == 0 && a.clk == nullptr &&
+  const bool lean = a.eta_sub == nullptr && a.Et2 == nullptr && a.nalpha == 0 && a.refine == 0 &&
                     env_int("PFV_MPSA_LEAN", 1) != 0;
   a.redo = lean ? c.mpsa_redo.ensure(std::max<int64_t>(c.nn, 1)) : nullptr;
   a.nopivot = (lean && a.ablate == 0 && env_int("PFV_MPSA_GJ_NP", kMpsaNoPivotDefault) != 0) ? 1 : 0;
@@ -1672,13 +1651,6 @@ static void mpsa_run_node_kernel(pfv_ctx_impl& c, const uint8_t* active = nullpt
     be_d2h(st3, c.status.p, sizeof(st3), s);
     sth[0] = std::max(sth[0], st3[0]);
     sth[1] = std::max(sth[1], st3[1]);
-  }
-  if (a.clk) {
-    long long ck[16];
-    be_d2h(ck, a.clk, sizeof(ck), s);
-    std::fprintf(stderr, "mpsa node clocks:");
-    for (int i = 1; i < 8; ++i) std::fprintf(stderr, " %lld", ck[i] ? ck[i] - ck[i - 1] : 0ll);
-    std::fprintf(stderr, "\n");
   }
   if (a.ablate) return;
   if (sth[1]) throw Error(PFV_ERR_ARGUMENT, "every boundary component needs a Dirichlet or Neumann condition");

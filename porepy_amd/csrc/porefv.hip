@@ -11,9 +11,6 @@ namespace pfv {
 static int rccl_exchange_halo(void* user, double* d_x, void* stream);  // rccl_hooks.inc
 }
 #include "topology.inc"
-#ifndef PFV_EMULATE
-#include "gj_mfma.inc"
-#endif
 #include "mpfa_numeric.inc"
 #include "linalg.inc"
 #include "reorder.inc"
@@ -167,13 +164,6 @@ pfv_status pfv_create(int device, pfv_ctx** out) {
     PFV_HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->own_stream = h->stream;
     PFV_HIP_CHECK(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
-    {
-      int least = 0, greatest = 0;
-      if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
-        if (hipStreamCreateWithPriority(&h->low_stream, hipStreamNonBlocking, least) != hipSuccess) h->low_stream = nullptr;
-      }
-      (void)hipGetLastError();
-    }
 #endif
   } catch (...) {
     delete h;
@@ -190,16 +180,14 @@ void pfv_destroy(pfv_ctx* h) {
   if (h->stream) {
     (void)hipStreamSynchronize(h->stream);
   }
-  hipStream_t s = h->own_stream, s2 = h->aux_stream, s3 = h->low_stream;
+  hipStream_t s = h->own_stream, s2 = h->aux_stream;
   if (s2) (void)hipStreamSynchronize(s2);
-  if (s3) (void)hipStreamSynchronize(s3);
   {
     pfv::PoolScope pool_scope(&h->pool);
     delete h;
   }
   if (s) (void)hipStreamDestroy(s);
   if (s2) (void)hipStreamDestroy(s2);
-  if (s3) (void)hipStreamDestroy(s3);
 #else
   {
     pfv::PoolScope pool_scope(&h->pool);
@@ -390,9 +378,7 @@ pfv_status pfv_mpfa_discretize(pfv_ctx* h, uint32_t flags) {
     pfv::Timer tm, tall;
     tall.start(s);
     bool node_done = false;
-    bool face_done = false;       // the face kernel ran inside the node || face pipeline
     const bool with_vs = !(flags & PFV_DISCR_SKIP_VECTOR_SOURCE);
-    bool cells_deferred = false;  // part 2 of the symbolic phase (pattern of A) still to be built
     if (!h->have_topology || !h->have_symbolic || (flags & PFV_DISCR_REBUILD_TOPOLOGY)) {
       tm.start(s);
       pfv::build_topology(*h);
@@ -401,7 +387,6 @@ pfv_status pfv_mpfa_discretize(pfv_ctx* h, uint32_t flags) {
       const bool keep_symbolic = symbolic_outputs_still_valid(h);
       if (keep_symbolic) {
         h->stats.symbolic_ms = tm.stop(s);  // (the digest and its read-back)
-        node_done = false;                  // the interaction-region kernel has the device to itself, below
       } else {
 #ifndef PFV_EMULATE
       // The symbolic phase (CSR patterns) and the interaction-region kernel (local inverses) both
@@ -410,19 +395,14 @@ pfv_status pfv_mpfa_discretize(pfv_ctx* h, uint32_t flags) {
       // symbolic kernels.  Its buffers live in the handle (nothing it touches passes through the block
       // cache while the other stream runs); the status words of the two phases are disjoint.
       if (h->aux_stream && pfv::env_int("PFV_OVERLAP_NODE", 1) != 0) {
-        // (PFV_NODE_LOWPRIO=1: on the handle's lowest-priority stream -- the symbolic kernels, short and many, then win
-        // the dispatch slots the long kernel frees instead of queueing behind its ~300 k wavefronts)
-        pfv::stream_t ns = (h->low_stream && pfv::env_int("PFV_NODE_LOWPRIO", 0) != 0) ? h->low_stream : h->aux_stream;
+        pfv::stream_t ns = h->aux_stream;
         pfv::StreamFork fork(s, ns);   // ns waits for everything enqueued on s so far
         pfv::Timer tn;
         tn.start(ns);
         pfv::launch_node_kernel(*h, nullptr, ns);
         tn.mark(ns);
         tm.start(s);
-        // (the pattern of A is only needed by the assembly: PFV_SYMB_DEFER_CELLS=1 builds it beside the face kernel,
-        // below -- measured: interaction-region span 14.2 -> 13.2 ms, face span 7.2 -> 9.1 ms, step +0.5 ms: off)
-        cells_deferred = !h->subface_bc && pfv::env_int("PFV_SYMB_DEFER_CELLS", 0) != 0;
-        pfv::build_symbolic(*h, cells_deferred ? 1 : 3);
+        pfv::build_symbolic(*h);
         h->stats.symbolic_ms = tm.stop(s);
         fork.join();                              // s waits for the node kernel
         h->stats.node_ms = tn.elapsed_after_sync();
@@ -439,46 +419,6 @@ pfv_status pfv_mpfa_discretize(pfv_ctx* h, uint32_t flags) {
       h->have_sub_symbolic = h->have_mpsa_sub_symbolic = false;
       }  // !keep_symbolic
     }
-#ifndef PFV_EMULATE
-    h->stats.pipeline_runs = 0;
-    if (!node_done && !h->subface_bc && h->aux_stream && h->pipe_chunks > 1 && h->have_symbolic &&
-        pfv::env_int("PFV_PIPE", 1) != 0) {
-      // ---- node || face pipeline (patterns in place: kept after a proved-equal topology, or a values-only call).  The
-      // interaction-region kernel is bound by instruction issue, the face kernel by memory traffic; back to back each
-      // leaves the other's resource idle.  The node kernel goes to the second stream in K runs of its largest size class
-      // (topology.inc); after run q an event releases, on the main stream, the face kernel over the faces whose nodes are
-      // all through -- one contiguous range of the ready-run-major face order.  The host enqueues node run, event, face
-      // range alternately; the device overlaps face range q with node run q + 1.  Same kernels on the same data: the
-      // matrices are bit for bit those of the sequential order (tests: PFV_PIPE=0 against 1).
-      // Interaction regions the unpivoted elimination hands to the redo list are only known once every run is through:
-      // they are redone then, and the faces around them recomputed (a handful per million nodes).
-      tm.start(s);
-      const int K = h->pipe_chunks;
-      std::vector<hipEvent_t> ev((size_t)K + 1, nullptr);
-      for (auto& e : ev) PFV_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      pfv::stream_t ns = h->aux_stream;
-      try {
-        pfv::StreamFork fork(s, ns);
-        const std::function<void(int)> after = [&](int q) {
-          PFV_HIP_CHECK(hipEventRecord(ev[q], ns));
-          PFV_HIP_CHECK(hipStreamWaitEvent(s, ev[q], 0));
-          const int64_t f0 = h->pipe_face_begin[q], f1 = h->pipe_face_begin[q + 1];
-          pfv::run_face_kernel(*h, with_vs, nullptr, 0, f0, f1 - f0);
-        };
-        pfv::launch_node_kernel(*h, nullptr, ns, &after);
-        fork.join();
-      } catch (...) {
-        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-        throw;
-      }
-      for (auto& e : ev) (void)hipEventDestroy(e);
-      pfv::check_node_status(*h, s);  // (reads the flags: everything above is through; runs the redo list, if any)
-      if (h->stats.node_redo > 0) pfv::redo_faces_around_nodes(*h, with_vs, h->stats.node_redo);
-      h->stats.node_ms = tm.stop(s);
-      h->stats.pipeline_runs = K;
-      node_done = face_done = true;
-    }
-#endif
     if (!node_done) {
       tm.start(s);
       pfv::run_node_kernel(*h);
@@ -495,32 +435,19 @@ pfv_status pfv_mpfa_discretize(pfv_ctx* h, uint32_t flags) {
       // when the solve is going to work on the system in place (grid numbered along the Morton curve),
       // it is built now on the second stream, beside the face kernel, instead of inside pfv_solve.
       h->win_sys_prebuilt = h->win_rows_prebuilt = false;
-      // (sizes of A's pattern: known now, or -- pattern deferred -- an upper estimate that only decides whether the
-      // second stream is used at all; the exact test follows once the pattern exists)
-      const int64_t nnzA_guess = cells_deferred ? h->pat_flux.nnz : h->pat_A.nnz;
-      bool prebuild = h->aux_stream && h->have_cell_order && h->cell_order_identity &&
-                      pfv::env_int("PFV_OVERLAP_WINDOW", 1) != 0 && pfv::env_int("PFV_REORDER", 1) != 0 &&
-                      nnzA_guess >= pfv::env_int("PFV_SPMV_WINDOW_MIN_NNZ", 20000);
+      const bool big = h->pat_A.nnz >= pfv::env_int("PFV_SPMV_WINDOW_MIN_NNZ", 20000);
+      const bool prebuild = h->aux_stream && h->have_cell_order && h->cell_order_identity &&
+                            pfv::env_int("PFV_OVERLAP_WINDOW", 1) != 0 && pfv::env_int("PFV_REORDER", 1) != 0 && big;
       // (a sharded solve multiplies the rows of the owned cells: the window of those rows, for the
       // number of owned rows of the previous solve on this handle)
-      h->win_rows_prebuilt = false;
-      bool prebuild_rows = !prebuild && h->aux_stream && h->win_rows_n > 0 && h->win_rows_n <= h->nc &&
-                           pfv::env_int("PFV_OVERLAP_WINDOW", 1) != 0 &&
-                           nnzA_guess >= pfv::env_int("PFV_SPMV_WINDOW_MIN_NNZ", 20000);
-      if (prebuild || prebuild_rows || cells_deferred) {
+      const bool prebuild_rows = !prebuild && h->aux_stream && h->win_rows_n > 0 && h->win_rows_n <= h->nc &&
+                                 pfv::env_int("PFV_OVERLAP_WINDOW", 1) != 0 && big;
+      if (prebuild || prebuild_rows) {
         pfv::StreamFork fork(s, h->aux_stream);
-        if (!face_done) pfv::run_face_kernel(*h, with_vs);  // (face_done: it ran inside the node || face pipeline)
+        pfv::run_face_kernel(*h, with_vs);
         h->stream = h->aux_stream;
         try {
-          if (cells_deferred) {
-            pfv::build_symbolic(*h, 2);
-            cells_deferred = false;
-            const bool big = h->pat_A.nnz >= pfv::env_int("PFV_SPMV_WINDOW_MIN_NNZ", 20000);
-            prebuild = prebuild && big;
-            prebuild_rows = prebuild_rows && big;
-          }
-          if (!prebuild && !prebuild_rows) {
-          } else if (prebuild) {
+          if (prebuild) {
             // the windows are a function of A's pattern alone: kept when the symbolic phase has just proved the
             // pattern equal to the one they were built for (sizes + checksum of the index arrays)
             const bool keep = h->win_sys.ok && h->pat_A_checksum != 0 && h->win_sys_checksum == h->pat_A_checksum &&
@@ -553,15 +480,14 @@ pfv_status pfv_mpfa_discretize(pfv_ctx* h, uint32_t flags) {
         if (prebuild) {
           h->win_for = h->pat_A.indices.p;
           h->win_sys_prebuilt = true;
-        } else if (prebuild_rows) {
+        } else {
           h->win_rows_for = h->pat_A.indices.p;
           h->win_rows_prebuilt = true;
         }
       } else
 #endif
-      if (!face_done) pfv::run_face_kernel(*h, with_vs);
+      pfv::run_face_kernel(*h, with_vs);
     }
-    if (cells_deferred) pfv::build_symbolic(*h, 2);  // (no second stream was used)
     h->stats.face_ms = tm.stop(s);
     h->stats.discretize_ms = tall.stop(s);
     h->have_numeric = true;

@@ -354,33 +354,11 @@ static void build_topology(pfv_ctx_impl& c) {
       sc[d] = ext > 0 ? 1023.999 / ext : 0.0;
     }
     const double lo0 = lo[0], lo1 = lo[1], lo2 = lo[2], sc0 = sc[0], sc1 = sc[1], sc2 = sc[2];
-    const int hilbert = env_int("PFV_FACE_CURVE", 0);  // 1: Hilbert curve instead of the Morton curve (A/B)
     parallel_for(s, nf, PFV_LAMBDA(int64_t f) {
       uint32_t q[3];
       q[0] = (uint32_t)((fc[f] - lo0) * sc0);
       q[1] = (uint32_t)((fc[nf + f] - lo1) * sc1);
       q[2] = (uint32_t)((fc[2 * nf + f] - lo2) * sc2);
-      if (hilbert) {
-        // Skilling's axes -> transposed Hilbert index (10 bits per axis); the Morton interleave below then
-        // yields the Hilbert key
-        const uint32_t M = 1u << 9;
-        for (int d = 0; d < 3; ++d) q[d] &= 0x3ffu;
-        for (uint32_t Q = M; Q > 1; Q >>= 1) {
-          const uint32_t Pm = Q - 1;
-          for (int i = 0; i < 3; ++i) {
-            if (q[i] & Q) q[0] ^= Pm;
-            else { const uint32_t t = (q[0] ^ q[i]) & Pm; q[0] ^= t; q[i] ^= t; }
-          }
-        }
-        for (int i = 1; i < 3; ++i) q[i] ^= q[i - 1];
-        uint32_t t = 0;
-        for (uint32_t Q = M; Q > 1; Q >>= 1)
-          if (q[2] & Q) t ^= Q - 1;
-        for (int i = 0; i < 3; ++i) q[i] ^= t;
-        // transposed form: q[0] carries the most significant bit of every triple
-        const uint32_t a = q[0], b = q[1], cc = q[2];
-        q[2] = a; q[1] = b; q[0] = cc;
-      }
       uint32_t code = 0;
       for (int d = 0; d < 3; ++d) {
         uint32_t x = q[d] & 0x3ffu;  // spread 10 bits to every third position
@@ -394,44 +372,6 @@ static void build_topology(pfv_ctx_impl& c) {
       v[f] = (int32_t)f;
     });
     sort_pairs(s, c.scratch, key_in.p, key_out.p, val_in.p, c.face_order.p, (size_t)nf, 30);
-    c.face_order_cell_major = false;
-    if (nd == 3 && (env_int("PFV_FACE_ORDER", 0) == 1 || env_int("PFV_FACE_CACHE", 0) > 0)) {
-      c.face_order_cell_major = true;
-      // Cell-major order: the faces whose flux is taken from the same cell (its first side) become neighbours, cells
-      // along the Morton curve through their centres.  The sub-faces of one cell at one node read the same three
-      // rows of the node's response table: in this order they are read back to back (by one wavefront with
-      // PFV_FACE_RUN > 1) instead of thousands of positions apart.  Two stable sorts: by cell, then by the cell's code.
-      int cbits = 1;
-      while ((int64_t(1) << cbits) < nc + 1 && cbits < 32) ++cbits;
-      const int32_t* ff = face_first;
-      const double* cc = c.ccen;
-      Buf<int32_t> tmp_order;
-      int32_t* o1 = tmp_order.ensure(nf);
-      parallel_for(s, nf, PFV_LAMBDA(int64_t f) {
-        k[f] = (uint32_t)ff[f];
-        v[f] = (int32_t)f;
-      });
-      sort_pairs(s, c.scratch, key_in.p, key_out.p, val_in.p, o1, (size_t)nf, cbits);
-      parallel_for(s, nf, PFV_LAMBDA(int64_t i) {
-        const int cell = ff[o1[i]];
-        uint32_t q[3];
-        q[0] = (uint32_t)((cc[cell] - lo0) * sc0);
-        q[1] = (uint32_t)((cc[nc + cell] - lo1) * sc1);
-        q[2] = (uint32_t)((cc[2 * nc + cell] - lo2) * sc2);
-        uint32_t code = 0;
-        for (int d = 0; d < 3; ++d) {
-          uint32_t x = q[d] & 0x3ffu;
-          x = (x | (x << 16)) & 0x030000ffu;
-          x = (x | (x << 8)) & 0x0300f00fu;
-          x = (x | (x << 4)) & 0x030c30c3u;
-          x = (x | (x << 2)) & 0x09249249u;
-          code |= x << d;
-        }
-        k[i] = code;
-        v[i] = o1[i];
-      });
-      sort_pairs(s, c.scratch, key_in.p, key_out.p, val_in.p, c.face_order.p, (size_t)nf, 30);
-    }
   }
 
   // --- launch order of the interaction-region kernel: nodes bucketed by block size
@@ -464,63 +404,6 @@ static void build_topology(pfv_ctx_impl& c) {
     be_d2h(cbh.data(), cbd, sizeof(int32_t) * (nclass + 1), s);
     c.class_begin.assign(nclass + 1, nn);
     for (int cls = 0; cls <= nclass; ++cls) c.class_begin[cls] = cbh[cls];
-  }
-  // --- chunks of the node || face pipeline (porefv.hip: pfv_mpfa_discretize).  The interaction-region kernel is bound by
-  // instruction issue, the face kernel by memory traffic: run back to back they leave the other's resource idle.  The
-  // nodes of the largest size class are cut into K runs of the launch order; a face is READY once the last of its nodes'
-  // runs is through (nodes of the other classes are launched first: run 0).  The processing order of the faces becomes
-  // ready-run major (the curve through the face centres inside a run), so that the faces of run k are one contiguous
-  // range the face kernel can take while the node kernel works on run k + 1.  One more stable sort pass over the faces.
-  c.pipe_chunks = 0;
-  {
-    const int K = std::min(30, env_int("PFV_PIPE_CHUNKS", kPipeChunksDefault));
-    int main_cls = -1;
-    int64_t main_n = 0;
-    for (int cls = 0; cls < kNumClasses; ++cls) {
-      const int64_t cnt = c.class_begin[cls + 1] - c.class_begin[cls];
-      if (cnt > main_n) { main_n = cnt; main_cls = cls; }
-    }
-    if (nd == 3 && K > 1 && main_cls >= 0 && 2 * main_n >= nn && nf >= env_int("PFV_PIPE_MIN_FACES", 400000) &&
-        !c.face_order_cell_major) {
-      const int64_t b0 = c.class_begin[main_cls], b1 = c.class_begin[main_cls + 1];
-      uint8_t* nch = c.pipe_node_chunk.ensure(nn);
-      const int32_t* no = c.node_order;
-      parallel_for(s, nn, PFV_LAMBDA(int64_t i) {
-        nch[no[i]] = (i >= b0 && i < b1) ? (uint8_t)(1 + ((i - b0) * K) / (b1 - b0)) : (uint8_t)0;
-      });
-      uint32_t* k = key_in.ensure(nf);
-      int32_t* v = val_in.ensure(nf);
-      key_out.ensure(nf);
-      int32_t* fo = c.face_order;
-      parallel_for(s, nf, PFV_LAMBDA(int64_t i) {
-        const int f = fo[i];
-        unsigned m = 0;
-        for (int e = fn_ptr[f]; e < fn_ptr[f + 1]; ++e) {
-          const unsigned q = nch[fn_idx[e]];
-          m = q > m ? q : m;
-        }
-        k[i] = m;
-        v[i] = f;
-      });
-      int32_t* sorted = val_out.ensure(nf);
-      sort_pairs(s, c.scratch, key_in.p, key_out.p, val_in.p, sorted, (size_t)nf, 5);
-      be_d2d(fo, sorted, sizeof(int32_t) * (size_t)nf, s);
-      Buf<int32_t> fb_dev;
-      int32_t* fbd = fb_dev.ensure(K + 2);
-      const uint32_t* ks = key_out;
-      parallel_for(s, K + 2, PFV_LAMBDA(int64_t q) { fbd[q] = lower_bound_idx<uint32_t>(ks, (int)nf, (uint32_t)q); });
-      std::vector<int32_t> fbh(K + 2);
-      be_d2h(fbh.data(), fbd, sizeof(int32_t) * (K + 2), s);
-      c.pipe_chunks = K;
-      c.pipe_class = main_cls;
-      c.pipe_face_begin.assign(fbh.begin(), fbh.end());
-      c.pipe_node_begin.resize(K + 1);
-      for (int q = 0; q <= K; ++q) {
-        // first position i of the class with 1 + (i - b0) K / (b1 - b0) > q, i.e. the smallest i with (i - b0) K >= q (b1 - b0)
-        c.pipe_node_begin[q] = b0 + ((int64_t)q * (b1 - b0) + K - 1) / K;
-      }
-      c.pipe_node_begin[K] = b1;
-    }
   }
   c.have_topology = true;
   c.topo_key = 0;
@@ -1052,7 +935,7 @@ static unsigned long long topology_digest(pfv_ctx_impl& c) {
   // host-side scalars: sizes and the maxima the launches are shaped by
   const long long sc[] = {(long long)nd, (long long)c.nc, (long long)nf, (long long)nn, (long long)c.ncf, (long long)c.nsf,
                           (long long)c.nh, (long long)c.max_face_nodes, (long long)c.max_deg,
-                          (long long)c.max_bnd_per_node, (long long)c.max_cell_faces, c.face_order_cell_major ? 1ll : 0ll};
+                          (long long)c.max_bnd_per_node, (long long)c.max_cell_faces};
   int k = 0;
   for (long long v : sc) dev += mix64((unsigned long long)v ^ (0xD6E8FEB86659FD93ull * (unsigned long long)(++k)));
   return dev ? dev : 1ull;  // (0 means "no key")
@@ -1076,13 +959,11 @@ static void ensure_vs_indices(pfv_ctx_impl& c) {
   c.vs_indices_pending = false;
 }
 
-// parts: 1 = the patterns of the face matrices (flux, bound_flux, vector_source) and the face records -- what the face
-// kernel needs; 2 = the pattern of A = div flux and its checksum -- what the assembly needs.  3 = both (default).  The
-// discretize call runs part 2 on the handle's second stream beside the face kernel (porefv.hip): beside the
-// interaction-region kernel, which owns the LDS of every CU, its kernels crawl (4.4 ms instead of 1.2).
-static void build_symbolic(pfv_ctx_impl& c, int parts = 3) {
-  if (parts & 1) ++c.symbolic_epoch;
-  if (parts & 1) c.symb_key = 0;  // (the outputs are being replaced: valid again once part 2 is through)
+// The patterns of the face matrices (flux, bound_flux, vector_source) and the face records -- what the face kernel
+// needs --, then the pattern of A = div flux and its checksum -- what the assembly needs.
+static void build_symbolic(pfv_ctx_impl& c) {
+  ++c.symbolic_epoch;
+  c.symb_key = 0;  // (the outputs are being replaced: valid again once the pattern of A is through)
   stream_t s = c.stream;
   const int nd = c.nd;
   const int64_t nc = c.nc, nf = c.nf;
@@ -1095,14 +976,12 @@ static void build_symbolic(pfv_ctx_impl& c, int parts = 3) {
   const int32_t* bp = c.node_bptr;
   const int32_t* bf = c.node_bfaces;
   int32_t* st = c.status;
-  if (parts & 1) {
-    be_memset(st + 4, 0, sizeof(int32_t) * 3, s);
-    // the patterns are replaced: values computed for the old ones must not be handed out against them
-    for (int m = PFV_MAT_FLUX; m <= PFV_MAT_SYSTEM; ++m) c.filled[m] = false;
-    c.have_symbolic = false;
-  }
-  if (parts & 2) be_memset(st + 7, 0, sizeof(int32_t), s);
-  Buf<int32_t> stage_ix;  // staging areas of the one-pass row builds (both parts)
+  be_memset(st + 4, 0, sizeof(int32_t) * 3, s);
+  // the patterns are replaced: values computed for the old ones must not be handed out against them
+  for (int m = PFV_MAT_FLUX; m <= PFV_MAT_SYSTEM; ++m) c.filled[m] = false;
+  c.have_symbolic = false;
+  be_memset(st + 7, 0, sizeof(int32_t), s);
+  Buf<int32_t> stage_ix;  // staging areas of the one-pass row builds (face rows, then the rows of A)
   Buf<uint8_t> stage_cp;
 
   Buf<int32_t> len;
@@ -1121,7 +1000,7 @@ static void build_symbolic(pfv_ctx_impl& c, int parts = 3) {
   if (maxfn > 18) throw Error(PFV_ERR_UNSUPPORTED, "faces with more than 18 nodes");
   const int G_face = env_int("PFV_SYMB_G", 16);
 
-  if (parts & 1) {
+  {  // patterns of the face matrices and the face records
   // faces that see a boundary face through one of their nodes (rows of bound_flux /
   // bound_pressure_face that are not empty): compact list, ascending
   Buf<int32_t> near_bnd;
@@ -1310,8 +1189,7 @@ static void build_symbolic(pfv_ctx_impl& c, int parts = 3) {
       fr[i] = r;
     });
   }
-  }  // parts & 1
-  if (!(parts & 2)) return;
+  }
   // A = div @ flux: row c = union of the flux rows of the faces of c = cells around the nodes of c
   {
     const int maxcf = std::max(c.max_cell_faces, 1);

@@ -84,10 +84,6 @@ def test_rebuilt_topology_keeps_the_patterns_it_proves_unchanged(lib):
     assert P.symbolic_reuse_on_rebuilt_topology(lib, n=10)
 
 
-def test_node_face_pipeline_leaves_the_bits_of_the_sequential_order(lib):
-    assert P.node_face_pipeline_leaves_the_same_bits(lib, 16, device=True)
-
-
 def test_config_c2_scale_properties(lib):
     """BASELINE config 2 (196 608 tetrahedra): exact linear field, zero flux for constant
     pressure — size-independent properties; the oracle is too slow at this size."""
@@ -201,11 +197,6 @@ def test_tpfa_and_1d_delegation(lib, name):
 
 def test_zero_dimensional_grid(lib):
     P.check_zero_dimensional_grid(lib)
-
-
-def test_elimination_on_the_fp64_matrix_cores_gives_the_same_matrices(lib):
-    worst = P.matrix_core_elimination_matches(lib)
-    assert worst > 0.0  # (a different summation order: if the two runs agree to the bit the switch did nothing)
 
 
 def test_grids_discretized_as_disjoint_unions_leave_the_bits_of_the_single_grid_path(lib):

@@ -36,16 +36,8 @@ VARIANTS = {
     "dyn_run2": {"PFV_FACE_DYN": 1, "PFV_FACE_RUN": 2},
     "dyn_run4": {"PFV_FACE_DYN": 1, "PFV_FACE_RUN": 4},
     "run2": {"PFV_FACE_RUN": 2},
-    "cell": {"PFV_FACE_ORDER": 1},
-    "cell_run2": {"PFV_FACE_ORDER": 1, "PFV_FACE_RUN": 2},
-    "cell_run4": {"PFV_FACE_ORDER": 1, "PFV_FACE_RUN": 4},
-    "cell_dyn": {"PFV_FACE_ORDER": 1, "PFV_FACE_DYN": 1},
-    "cell_dyn_run2": {"PFV_FACE_ORDER": 1, "PFV_FACE_DYN": 1, "PFV_FACE_RUN": 2},
-    "cell_dyn_run4": {"PFV_FACE_ORDER": 1, "PFV_FACE_DYN": 1, "PFV_FACE_RUN": 4},
-    "cell_dyn_run8": {"PFV_FACE_ORDER": 1, "PFV_FACE_DYN": 1, "PFV_FACE_RUN": 8},
-    "cell_dyn_run4_nt": {"PFV_FACE_ORDER": 1, "PFV_FACE_DYN": 1, "PFV_FACE_RUN": 4, "PFV_FACE_NT": 1},
 }
-KEYS = ("PFV_FACE_DYN", "PFV_FACE_RUN", "PFV_FACE_ORDER", "PFV_FACE_NT", "PFV_NODE_GJ")
+KEYS = ("PFV_FACE_DYN", "PFV_FACE_RUN", "PFV_NODE_GJ")
 one = os.environ.get("PFV_LAB_ONE")
 only = sys.argv[3] if len(sys.argv) > 3 and sys.argv[2] == "only" else None
 

@@ -56,7 +56,13 @@ enum {
   PFV_MAT_MECH_SYSTEM = 11,
   PFV_MAT_USER_SYSTEM = 12, /* matrix handed over by pfv_set_system */
   PFV_MAT_FLUX_JACOBIAN = 13, /* d flux / d p of pfv_mpfa_ad_flux_system, on the pattern of flux */
-  PFV_NUM_MATS = 14
+  /* Upwind.discretize (numerics/fv/upwind.py:165-335): "transport" (k Nf x k Nc), "rhs_dir", "rhs_neu" (k Nf x k Nf),
+   * and the advective system A = div diag(q) U of Upwind.assemble_matrix_rhs (upwind.py:67-163) */
+  PFV_MAT_UPWIND = 14,
+  PFV_MAT_UPWIND_RHS_DIR = 15,
+  PFV_MAT_UPWIND_RHS_NEU = 16,
+  PFV_MAT_TRANSPORT_SYSTEM = 17,
+  PFV_NUM_MATS = 18
 };
 
 /* boundary-condition flag bits per face (params/bc.py:68-190: is_dir/is_neu/is_rob/
@@ -146,6 +152,13 @@ typedef struct {
   int64_t pipeline_runs;          /* always 0 (kept so that the fields after it keep their offsets) */
   int64_t amg_nns_modes;          /* modes per aggregate of the last PFV_PRECOND_AMG_NNS setup (0: none); that setup also
                                      fills amg_setup_ms, amg_operator_complexity, amg_levels and amg_coarsest_rows */
+  double face_flux_ms;            /* last pfv_mpfa_face_flux (kernel only, HIP events) */
+  double upwind_ms;               /* last pfv_upwind_discretize */
+  double transport_assemble_ms;   /* last pfv_upwind_assemble */
+  double transport_advance_ms;    /* last pfv_transport_advance, all steps */
+  int64_t transport_iterations;   /* ... Krylov iterations summed over its steps */
+  int64_t transport_gmres_retries; /* ... steps whose BiCGStab solve broke down (NaN residual) and were solved again with
+                                      GMRES from the kept state */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -443,6 +456,47 @@ pfv_status pfv_mpsa_discretize_faces(pfv_ctx* h, uint32_t flags, int64_t n_faces
  * column-major), source nd*Nc or NULL.  Makes the mechanics system the one pfv_solve works on
  * (pfv_mpfa_assemble switches back to the flow system). */
 pfv_status pfv_mpsa_assemble(pfv_ctx* h, const double* bc_values, const double* source);
+
+/* ---- Upwind advection and the transport step on the device (csrc/upwind.inc; numerics/fv/upwind.py) ----------
+ * The chain discretize flow -> solve -> Darcy flux -> upwind -> transport step without leaving the device.  Vectors
+ * (p, bc_values, vector_source, q, accumulation, c_old, source, c and the outputs) are host or device memory as
+ * selected by pfv_set_vectors_on_device; the flag array is host memory.  Periodic grids, conditions per sub-face and
+ * the sharded solve are not covered (PFV_ERR_UNSUPPORTED).  pfv_set_grid clears all of it.
+ *
+ * Face flux q = flux p + bound_flux bc_values (+ vector_source g) from the MPFA / TPFA matrices on the handle, each
+ * row summed in stored order (flux, then bound_flux, then vector_source).  The result stays on the handle as the
+ * resident face flux; q_out (Nf, may be NULL) receives a copy. */
+pfv_status pfv_mpfa_face_flux(pfv_ctx* h, const double* p, const double* bc_values, const double* vector_source,
+                              double* q_out);
+/* Boundary conditions of the transport keyword: Nf bytes of PFV_BC_* bits; NULL = Dirichlet on every boundary face
+ * (the reference's default, upwind.py:232-238). */
+pfv_status pfv_upwind_set_bc(pfv_ctx* h, const uint8_t* bc_flags);
+/* Upwind.discretize for the face flux q (Nf; NULL = the resident face flux): fills PFV_MAT_UPWIND,
+ * PFV_MAT_UPWIND_RHS_DIR and PFV_MAT_UPWIND_RHS_NEU with the patterns the reference stores (num_components = k: a
+ * full k x k block per entry, as scipy's kron with eye(k) leaves it -- zeros off the block diagonal stored).  The upstream side
+ * follows numpy's sign(q) >= 0: +0 and -0 count as positive, NaN as negative.  A boundary face that is neither
+ * Dirichlet nor Neumann and has inflow has no upstream cell: PFV_ERR_ARGUMENT (the reference: ValueError). */
+pfv_status pfv_upwind_discretize(pfv_ctx* h, const double* q, int num_components);
+/* Upwind.assemble_matrix_rhs, fused: A = div diag(q) U + diag(accumulation) as PFV_MAT_TRANSPORT_SYSTEM on the
+ * pattern {cell, its face neighbours} (explicit zeros where the reference stores nothing), and the boundary part of
+ * the flux divergence b_ref = div (rhs_neu + rhs_dir diag(q)) bc_values, which is what the reference returns as
+ * "rhs": the balance reads accumulation o (c - c_old) + A c + b_ref = source.  (A, r) with
+ * r = accumulation o c_old - b_ref + source become the active system of pfv_solve.  q = NULL: the flux of the
+ * discretization; accumulation, c_old, source (Nc each) and bound_rhs_out (Nc, receives b_ref) may be NULL.
+ * c_old without accumulation has nothing to multiply and is ignored.
+ * num_components must be 1. */
+pfv_status pfv_upwind_assemble(pfv_ctx* h, const double* q, const double* bc_values, const double* accumulation,
+                               const double* c_old, const double* source, double* bound_rhs_out);
+/* n_steps implicit Euler steps with the system of pfv_upwind_assemble: per step r = accumulation o c - b_ref + source
+ * on the device, Jacobi-preconditioned solve (method: PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES; the matrix is not
+ * symmetric) started from c, c <- x.  BiCGStab breaks down (rho = 0, the residual turns NaN) when the first residual
+ * sits in cells nothing flows back into -- injection into a field at rest: the matrix of an acyclic flow is triangular;
+ * such a step is solved again with GMRES from the kept state and counted in pfv_stats.transport_gmres_retries.
+ * c holds c_0 on entry and the last computed state on return.  Stops at the first
+ * step that does not converge (PFV_ERR_NOT_CONVERGED; steps_done counts the converged ones).  last (may be NULL)
+ * receives the info of the last solve. */
+pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rtol, int maxit, double* c,
+                                 int32_t* steps_done, pfv_solve_info* last);
 
 /* Device-pointer variants for multi-GPU drivers that keep vectors in HBM
  * (torch tensors): y = A x on the handle's stream; d_x has num_cols entries. */

@@ -20,6 +20,7 @@ MAT_VECTOR_SOURCE, MAT_BOUND_PRESSURE_VECTOR_SOURCE, MAT_SYSTEM = 4, 5, 6
 MAT_STRESS, MAT_BOUND_STRESS, MAT_BOUND_DISPLACEMENT_CELL, MAT_BOUND_DISPLACEMENT_FACE, MAT_MECH_SYSTEM = 7, 8, 9, 10, 11
 MAT_USER_SYSTEM = 12
 MAT_FLUX_JACOBIAN = 13
+MAT_UPWIND, MAT_UPWIND_RHS_DIR, MAT_UPWIND_RHS_NEU, MAT_TRANSPORT_SYSTEM = 14, 15, 16, 17
 BC_DIR, BC_NEU, BC_ROB, BC_INTERNAL = 1, 2, 4, 8
 SOLVE_CG, SOLVE_BICGSTAB, SOLVE_GMRES = 0, 1, 2
 PRECOND_JACOBI, PRECOND_AMG, PRECOND_BLOCK, PRECOND_AMG_NNS = 0, 1, 2, 3
@@ -45,6 +46,7 @@ EXPORTS = [
     "pfv_rccl_last_error", "pfv_rccl_comm_destroy", "pfv_mpfa_ad_flux_system", "pfv_host_alloc", "pfv_host_free",
     "pfv_mpsa_set_subface_eta", "pfv_mpsa_set_reconstruction_eta", "pfv_mpsa_set_reconstruction_eta_subface", "pfv_get_stats_n", "pfv_set_block_preconditioner",
     "pfv_mpfa_set_permeability", "pfv_set_near_null_space", "pfv_amg_nns_level",
+    "pfv_mpfa_face_flux", "pfv_upwind_set_bc", "pfv_upwind_discretize", "pfv_upwind_assemble", "pfv_transport_advance",
 ]
 
 
@@ -67,7 +69,10 @@ class Stats(C.Structure):
                 ("solve_launches", C.c_int64), ("amg_setup_launches", C.c_int64), ("node_redo", C.c_int64),
                 ("symbolic_reused", C.c_int64), ("amg_stale_rematches", C.c_int64),
                 ("mpsa_contrast_regions", C.c_int64), ("mpsa_max_contrast", C.c_double), ("assemble_positions_kept", C.c_int64),
-                ("pipeline_runs", C.c_int64), ("amg_nns_modes", C.c_int64)]
+                ("pipeline_runs", C.c_int64), ("amg_nns_modes", C.c_int64),
+                ("face_flux_ms", C.c_double), ("upwind_ms", C.c_double), ("transport_assemble_ms", C.c_double),
+                ("transport_advance_ms", C.c_double), ("transport_iterations", C.c_int64),
+                ("transport_gmres_retries", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -268,6 +273,17 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_mpsa_discretize.restype = C.c_int
     lib.pfv_mpsa_assemble.argtypes = [_h, _dp, _dp]
     lib.pfv_mpsa_assemble.restype = C.c_int
+    lib.pfv_mpfa_face_flux.argtypes = [_h, _dp, _dp, _dp, _dp]
+    lib.pfv_mpfa_face_flux.restype = C.c_int
+    lib.pfv_upwind_set_bc.argtypes = [_h, _up]
+    lib.pfv_upwind_set_bc.restype = C.c_int
+    lib.pfv_upwind_discretize.argtypes = [_h, _dp, C.c_int]
+    lib.pfv_upwind_discretize.restype = C.c_int
+    lib.pfv_upwind_assemble.argtypes = [_h, _dp, _dp, _dp, _dp, _dp, _dp]
+    lib.pfv_upwind_assemble.restype = C.c_int
+    lib.pfv_transport_advance.argtypes = [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(C.c_int32),
+                                          C.POINTER(SolveInfo)]
+    lib.pfv_transport_advance.restype = C.c_int
     return lib
 
 
@@ -1153,6 +1169,105 @@ class Context:
         self._check(self.lib.pfv_mpfa_ad_flux_system(self._h, _ptr(pa_, _dp), _ptr(dk, _dp), _ptr(bc, _dp), _ptr(vs, _dp),
                                                      _ptr(src, _dp), _ptr(q, _dp), 1 if flux_jacobian else 0))
         return q
+
+    # ---- upwind advection and the transport step (include/porefv.h: pfv_upwind_*) ----
+    def _vec(self, a, n, name, device):
+        """A vector argument of the transport calls: a host array of n entries, or (device) the address of one."""
+        if a is None:
+            return None, None
+        if device:
+            return None, C.cast(int(a), _dp)
+        arr = _f64(a)
+        if arr.shape != (n,):
+            raise ValueError(f"{name} must have {n} entries")
+        return arr, _ptr(arr, _dp)
+
+    def face_flux(self, p, bc_values, vector_source=None, out=True, device=False, q_ptr: int = 0):
+        """q = flux p + bound_flux bc_values (+ vector_source g) from the flow discretization on this handle
+        (pfv_mpfa_face_flux).  The flux stays on the handle as the resident face flux; ``out``: also return it as
+        an array.  ``device``: p / bc_values / vector_source are addresses of device buffers, q goes to ``q_ptr``."""
+        k1, pp_ = self._vec(p, self.nc, "p", device)
+        k2, pb = self._vec(bc_values, self.nf, "bc_values", device)
+        nvs = None if vector_source is None or device else self.matrix_info(MAT_VECTOR_SOURCE)[1]
+        k3, pv = self._vec(vector_source, nvs, "vector_source", device)
+        q = np.empty(self.nf, dtype=np.float64) if (out and not device) else None
+        qp = C.cast(q_ptr or None, _dp) if device else _ptr(q, _dp)
+        if device:
+            self._dev(True)
+        try:
+            self._check(self.lib.pfv_mpfa_face_flux(self._h, pp_, pb, pv, qp))
+        finally:
+            if device:
+                self._dev(False)
+        return q
+
+    def upwind_set_bc(self, flags):
+        """PFV_BC_* bits per face of the transport keyword; None = Dirichlet on every boundary face."""
+        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint8)
+        if fl is not None and fl.shape != (self.nf,):
+            raise ValueError("bc flags must have one entry per face")
+        self._check(self.lib.pfv_upwind_set_bc(self._h, _ptr(fl, _up)))
+
+    def upwind_discretize(self, q=None, num_components: int = 1, device=False):
+        """Upwind.discretize for the face flux ``q`` (None: the resident face flux)."""
+        kq, pq = self._vec(q, self.nf, "the flux array", device)
+        if device:
+            self._dev(True)
+        try:
+            self._check(self.lib.pfv_upwind_discretize(self._h, pq, int(num_components)))
+        finally:
+            if device:
+                self._dev(False)
+
+    def upwind_assemble(self, bc_values, q=None, accumulation=None, c_old=None, source=None, bound_rhs=False,
+                        device=False, bound_rhs_ptr: int = 0):
+        """A = div diag(q) U + diag(accumulation) and r = accumulation o c_old - b_ref + source become the active
+        system (pfv_upwind_assemble).  ``bound_rhs``: return b_ref, what the reference returns as the rhs
+        (``device``: written to ``bound_rhs_ptr``)."""
+        kq, pq = self._vec(q, self.nf, "the flux array", device)
+        kb, pb = self._vec(bc_values, self.nf, "bc_values", device)
+        ka, pa_ = self._vec(accumulation, self.nc, "accumulation", device)
+        kc, pc = self._vec(c_old, self.nc, "c_old", device)
+        ks, ps = self._vec(source, self.nc, "source", device)
+        if pb is None:
+            raise ValueError("bc_values is required")
+        b = np.empty(self.nc, dtype=np.float64) if (bound_rhs and not device) else None
+        pbr = C.cast(bound_rhs_ptr or None, _dp) if device else _ptr(b, _dp)
+        if device:
+            self._dev(True)
+        try:
+            self._check(self.lib.pfv_upwind_assemble(self._h, pq, pb, pa_, pc, ps, pbr))
+        finally:
+            if device:
+                self._dev(False)
+        return b
+
+    def transport_advance(self, c0, n_steps: int, method="bicgstab", rtol=1e-12, maxit=10000, raise_on_fail=True,
+                          device=False):
+        """``n_steps`` implicit Euler steps of the assembled transport system (pfv_transport_advance).  Returns
+        (c, info); ``device``: ``c0`` is the address of Nc doubles on the device, advanced in place (c is None)."""
+        code = {"bicgstab": SOLVE_BICGSTAB, "gmres": SOLVE_GMRES}[method]
+        if device:
+            c, pc = None, C.cast(int(c0), _dp)
+        else:
+            c = np.array(c0, dtype=np.float64, copy=True).ravel()
+            if c.shape != (self.nc,):
+                raise ValueError("c0 must have one entry per cell")
+            pc = _ptr(c, _dp)
+        done, info = C.c_int32(0), SolveInfo()
+        if device:
+            self._dev(True)
+        try:
+            st = self.lib.pfv_transport_advance(self._h, int(n_steps), code, float(rtol), int(maxit), pc, C.byref(done),
+                                                C.byref(info))
+        finally:
+            if device:
+                self._dev(False)
+        out = {"steps_done": done.value, "iterations": info.iterations, "converged": bool(info.converged),
+               "rel_residual": info.rel_residual, "solve_ms": info.solve_ms}
+        if st != 0 and (raise_on_fail or st != 6):
+            self._check(st)
+        return c, out
 
     def tpfa_transmissibility_ad(self, perm):
         """Two-point face transmissibilities and their derivatives with respect to the permeability entries

@@ -309,6 +309,23 @@ struct pfv_ctx_impl {
   double* shard_work = nullptr;      // [2 * shard_nloc + 8]: the two SpMV inputs (owned + halo entries), reduction scratch
   int64_t shard_nloc = 0;
 
+  // ---- upwind advection and the transport step (upwind.inc) ---------------------------
+  bool have_q_res = false;           // q_res holds a face flux (pfv_mpfa_face_flux)
+  Buf<double> q_res;                 // [nf] the resident face flux
+  bool have_upw_bc = false;          // upw_bc given (else: Dirichlet on every boundary face)
+  Buf<uint8_t> upw_bc;               // [nf] PFV_BC_* bits of the transport keyword
+  bool have_upwind = false, have_transport = false, have_pat_T = false;
+  bool have_upw_cells = false;       // upw_side / upw_cnt hold the face -> cells map of the grid on the handle
+  int upw_ncomp = 0;                 // num_components of the discretization
+  Buf<double> upw_q;                 // [nf] the flux the discretization was made for
+  Buf<int32_t> upw_side, upw_cnt;    // [2][nf] cell on the +1 / -1 side of every face (-1: none); cells per side
+  Buf<int32_t> upw_up;               // [nf] upstream cell (-1: outside)
+  Buf<uint8_t> upw_cls;              // [nf] UPW_KEPT | UPW_NEU | UPW_DIRIN
+  CsrPattern pat_upw, pat_upw_dir, pat_upw_neu, pat_T;  // transport, rhs_dir, rhs_neu; the transport system
+  Buf<double> rhs_t, diag_t, bref_t, acc_t, src_t, c_t, c_keep, q_t, bc_t;
+  bool have_acc_t = false, have_src_t = false;
+  int64_t transport_zero_diag = -1;  // first row of the transport system with a zero diagonal (-1: none)
+
   pfv_stats stats{};
 
   const CsrPattern& pattern_of(int which) const {
@@ -337,6 +354,14 @@ struct pfv_ctx_impl {
         return pat_Am;
       case PFV_MAT_USER_SYSTEM:
         return pat_user;
+      case PFV_MAT_UPWIND:
+        return pat_upw;
+      case PFV_MAT_UPWIND_RHS_DIR:
+        return pat_upw_dir;
+      case PFV_MAT_UPWIND_RHS_NEU:
+        return pat_upw_neu;
+      case PFV_MAT_TRANSPORT_SYSTEM:
+        return pat_T;
       default:
         return pat_A;
     }

@@ -19,6 +19,7 @@ static int rccl_exchange_halo(void* user, double* d_x, void* stream);  // rccl_h
 #include "tpfa.inc"
 #include "biot.inc"
 #include "ad_flux.inc"
+#include "upwind.inc"
 
 namespace pfv {
 #ifndef PFV_EMULATE
@@ -101,6 +102,8 @@ void require(bool ok, const char* msg) {
 
 bool pattern_ready(const pfv_ctx* h, int which) {
   if (which == PFV_MAT_USER_SYSTEM) return h->filled[which];
+  if (which == PFV_MAT_TRANSPORT_SYSTEM) return h->have_transport;
+  if (which >= PFV_MAT_UPWIND && which <= PFV_MAT_UPWIND_RHS_NEU) return h->have_upwind;
   if (which == PFV_MAT_FLUX_JACOBIAN) return h->have_symbolic;
   return which >= PFV_MAT_STRESS ? h->have_mpsa_symbolic : h->have_symbolic;
 }
@@ -269,6 +272,9 @@ pfv_status pfv_set_grid(pfv_ctx* h, int nd, int64_t nc, int64_t nf, int64_t nn, 
     h->have_mpsa_numeric = h->have_mpsa_symbolic = h->have_mech_system = false;
     h->active.valid = false;
     for (bool& f : h->filled) f = false;
+    h->have_q_res = h->have_upw_bc = h->have_upwind = h->have_transport = h->have_pat_T = h->have_upw_cells = false;
+    h->have_acc_t = h->have_src_t = false;
+    h->transport_zero_diag = -1;
   });
 }
 
@@ -794,6 +800,208 @@ pfv_status pfv_mpfa_ad_flux_system(pfv_ctx* h, const double* p, const double* dk
   });
 }
 
+// ---- upwind advection and the transport step (upwind.inc) ------------------------------------------------------
+static void upwind_supported(pfv_ctx* h) {
+  require(h->have_grid, "pfv_set_grid first");
+  if (h->periodic) throw pfv::Error(PFV_ERR_UNSUPPORTED, "upwind on periodic grids is not covered");
+  if (h->shard) throw pfv::Error(PFV_ERR_UNSUPPORTED, "the transport calls have no sharded form");
+}
+
+// the transport system no longer belongs to the discretization on the handle: it must not stay the active system
+static void upwind_drop_transport(pfv_ctx* h) {
+  if (h->active.valid && h->active.val == h->val[PFV_MAT_TRANSPORT_SYSTEM].p && h->have_transport) h->active.valid = false;
+  h->have_transport = false;
+  h->filled[PFV_MAT_TRANSPORT_SYSTEM] = false;
+  h->transport_zero_diag = -1;
+}
+
+pfv_status pfv_mpfa_face_flux(pfv_ctx* h, const double* p, const double* bc_values, const double* vector_source,
+                              double* q_out) {
+  return guarded(h, [&] {
+    upwind_supported(h);
+    require(h->have_numeric && h->filled[PFV_MAT_FLUX] && h->filled[PFV_MAT_BOUND_FLUX], "discretize the flow first");
+    if (h->subface_bc)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "flux has sub-face rows (conditions per sub-face): no face flux");
+    require(p && bc_values, "p and bc_values are required");
+    require(!vector_source || h->filled[PFV_MAT_VECTOR_SOURCE], "vector_source matrix was skipped");
+    auto s = h->stream;
+    const size_t nf = (size_t)h->nf, nc = (size_t)h->nc, nvs = (size_t)h->pat_vs.ncols;
+    pfv::Buf<double> in_;
+    double* in = in_.ensure(nc + nf + nvs);
+    double* d_p = in;
+    double* d_bc = in + nc;
+    double* d_vs = vector_source ? in + nc + nf : nullptr;
+    vec_in(h, d_p, p, nc);
+    vec_in(h, d_bc, bc_values, nf);
+    if (d_vs) vec_in(h, d_vs, vector_source, nvs);
+    pfv::Timer tm;
+    tm.start(s);
+    pfv::upwind_face_flux(*h, d_p, d_bc, d_vs);
+    h->stats.face_flux_ms = tm.stop(s);
+    h->have_q_res = true;
+    if (q_out) {
+      if (h->vectors_on_device) pfv::be_d2d(q_out, h->q_res.p, nf * sizeof(double), s);
+      else be_d2h(q_out, h->q_res.p, nf * sizeof(double), s);
+    }
+    pfv::be_sync(s);  // (the staging buffer is freed on return)
+  });
+}
+
+pfv_status pfv_upwind_set_bc(pfv_ctx* h, const uint8_t* bc_flags) {
+  return guarded(h, [&] {
+    upwind_supported(h);
+    h->have_upw_bc = bc_flags != nullptr;
+    if (bc_flags) upload(h->upw_bc, bc_flags, (size_t)h->nf, h->stream);
+    upwind_drop_transport(h);
+    h->have_upwind = false;
+  });
+}
+
+// the flux argument of the upwind calls: the caller's array staged into `stage`, or the fallback when it is NULL
+static const double* upwind_flux_in(pfv_ctx* h, const double* q, pfv::Buf<double>& stage) {
+  if (!q) return nullptr;
+  double* d = stage.ensure((size_t)h->nf);
+  vec_in(h, d, q, (size_t)h->nf);
+  return d;
+}
+
+pfv_status pfv_upwind_discretize(pfv_ctx* h, const double* q, int num_components) {
+  return guarded(h, [&] {
+    upwind_supported(h);
+    require(num_components >= 1, "num_components must be at least 1");
+    require(q || h->have_q_res, "no face flux given and no resident face flux on the handle (pfv_mpfa_face_flux)");
+    auto s = h->stream;
+    const double* d_q = upwind_flux_in(h, q, h->q_t);
+    if (!d_q) d_q = h->q_res.p;
+    upwind_drop_transport(h);
+    h->have_upwind = false;
+    for (int m = PFV_MAT_UPWIND; m <= PFV_MAT_UPWIND_RHS_NEU; ++m) h->filled[m] = false;
+    pfv::Timer tm;
+    tm.start(s);
+    pfv::upwind_discretize(*h, d_q, num_components);
+    h->stats.upwind_ms = tm.stop(s);
+    h->upw_ncomp = num_components;
+    h->have_upwind = true;
+  });
+}
+
+pfv_status pfv_upwind_assemble(pfv_ctx* h, const double* q, const double* bc_values, const double* accumulation,
+                               const double* c_old, const double* source, double* bound_rhs_out) {
+  return guarded(h, [&] {
+    upwind_supported(h);
+    require(h->have_upwind, "pfv_upwind_discretize first");
+    require(h->upw_ncomp == 1, "Dimension mismatch in assembly of discretization term: upwinding with multiple "
+                               "components only discretizes");
+    require(bc_values != nullptr, "bc_values is required");
+    auto s = h->stream;
+    const size_t nf = (size_t)h->nf, nc = (size_t)h->nc;
+    const double* d_q = upwind_flux_in(h, q, h->q_t);
+    if (!d_q) d_q = h->upw_q.p;
+    double* d_bc = h->bc_t.ensure(nf);
+    vec_in(h, d_bc, bc_values, nf);
+    h->have_acc_t = accumulation != nullptr;
+    h->have_src_t = source != nullptr;
+    if (accumulation) vec_in(h, h->acc_t.ensure(nc), accumulation, nc);
+    if (source) vec_in(h, h->src_t.ensure(nc), source, nc);
+    const double* d_cold = nullptr;
+    if (c_old) {
+      vec_in(h, h->c_t.ensure(nc), c_old, nc);
+      d_cold = h->c_t.p;
+    }
+    pfv::Timer tm;
+    tm.start(s);
+    pfv::upwind_assemble(*h, d_q, d_bc, h->have_acc_t ? h->acc_t.p : nullptr, d_cold,
+                         h->have_src_t ? h->src_t.p : nullptr);
+    h->stats.transport_assemble_ms = tm.stop(s);
+    if (bound_rhs_out) {
+      if (h->vectors_on_device) pfv::be_d2d(bound_rhs_out, h->bref_t.p, nc * sizeof(double), s);
+      else be_d2h(bound_rhs_out, h->bref_t.p, nc * sizeof(double), s);
+    }
+    pfv::be_sync(s);
+    h->have_transport = true;
+    // the values under the solver's caches changed (they are keyed on the value pointer)
+    if (h->amg) h->amg->valid = false;
+    h->nns_stale = true;
+    if (h->block_pc) h->block_pc->for_val = nullptr;
+    if (h->amg_block) h->amg_block->valid = false;
+    h->perm_for_val = nullptr;
+    h->win_for = h->win_rows_for = nullptr;
+    h->win_sys_prebuilt = h->win_rows_prebuilt = false;
+    h->active.P = &h->pat_T;
+    h->active.val = h->val[PFV_MAT_TRANSPORT_SYSTEM].p;
+    h->active.diag = h->diag_t.p;
+    h->active.rhs = h->rhs_t.p;
+    h->active.n = h->nc;
+    h->active_bs = 1;
+    h->active_is_grid = true;
+    h->active.valid = true;
+  });
+}
+
+pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rtol, int maxit, double* c,
+                                 int32_t* steps_done, pfv_solve_info* last) {
+  if (steps_done) *steps_done = 0;
+  std::unique_ptr<pfv::Timer> tm;
+  pfv_status st = guarded(h, [&] {
+    upwind_supported(h);
+    require(h->have_transport && h->active.valid && h->active.val == h->val[PFV_MAT_TRANSPORT_SYSTEM].p,
+            "pfv_upwind_assemble first (the transport system must be the active one)");
+    require(n_steps >= 0 && c != nullptr, "bad argument");
+    require(method == PFV_SOLVE_BICGSTAB || method == PFV_SOLVE_GMRES,
+            "method must be PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES (the transport matrix is not symmetric)");
+    vec_in(h, h->c_t.ensure((size_t)h->nc), c, (size_t)h->nc);
+    tm = std::make_unique<pfv::Timer>();
+    tm->start(h->stream);
+  });
+  if (st != PFV_OK) return st;
+  const bool caller_on_device = h->vectors_on_device;
+  const int precond = h->precond;
+  h->vectors_on_device = true;  // the state stays in c_t between the steps
+  h->precond = PFV_PRECOND_JACOBI;
+  int64_t iters = 0, retries = 0;
+  const size_t nbytes = (size_t)h->nc * sizeof(double);
+  for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
+    // BiCGStab can break down (rho = (r_hat, r) = 0: the residual turns NaN) where the first residual sits in cells
+    // nothing flows back into -- injection into a field at rest, the matrix of an acyclic flow being triangular.  The
+    // state is kept, and such a step is solved again with GMRES from it; transport_gmres_retries counts them.
+    st = guarded(h, [&] {
+      pfv::upwind_step_rhs(*h, h->c_t.p);
+      if (method == PFV_SOLVE_BICGSTAB) pfv::be_d2d(h->c_keep.ensure((size_t)h->nc), h->c_t.p, nbytes, h->stream);
+    });
+    if (st != PFV_OK) break;
+    pfv_solve_info info{};
+    st = pfv_solve(h, method, rtol, maxit, 0, h->c_t.p, h->c_t.p, &info);
+    iters += info.iterations;
+    if (st == PFV_ERR_NOT_CONVERGED && method == PFV_SOLVE_BICGSTAB && !(info.rel_residual == info.rel_residual)) {
+      st = guarded(h, [&] { pfv::be_d2d(h->c_t.p, h->c_keep.p, nbytes, h->stream); });
+      if (st != PFV_OK) break;
+      ++retries;
+      st = pfv_solve(h, PFV_SOLVE_GMRES, rtol, maxit, 0, h->c_t.p, h->c_t.p, &info);
+      iters += info.iterations;
+    }
+    if (last) *last = info;
+    if (st == PFV_OK && steps_done) ++*steps_done;
+  }
+  h->vectors_on_device = caller_on_device;
+  h->precond = precond;
+  const std::string err = h->err;
+  const pfv_status st2 = guarded(h, [&] {
+    h->stats.transport_advance_ms = tm->stop(h->stream);
+    tm.reset();
+    h->stats.transport_iterations = iters;
+    h->stats.transport_gmres_retries = retries;
+    const size_t nc = (size_t)h->nc;
+    if (h->vectors_on_device) pfv::be_d2d(c, h->c_t.p, nc * sizeof(double), h->stream);
+    else be_d2h(c, h->c_t.p, nc * sizeof(double), h->stream);
+    pfv::be_sync(h->stream);
+  });
+  if (st != PFV_OK) {
+    h->err = err;
+    return st;
+  }
+  return st2;
+}
+
 pfv_status pfv_mpsa_set_params(pfv_ctx* h, const double* stiffness_99n, const double* cell_volumes,
                                const uint8_t* bc_dir_bits, const uint8_t* bc_neu_bits, double eta) {
   return guarded(h, [&] {
@@ -1273,7 +1481,8 @@ pfv_status pfv_get_rhs(pfv_ctx* h, double* b) {
 pfv_status pfv_spmv(pfv_ctx* h, int which, const double* x, double* y) {
   return guarded(h, [&] {
     require(which >= 0 && which < PFV_NUM_MATS && x && y, "bad argument");
-    require((h->have_symbolic || which == PFV_MAT_USER_SYSTEM) && h->filled[which], "matrix values have not been computed");
+    require((h->have_symbolic || which == PFV_MAT_USER_SYSTEM || which >= PFV_MAT_UPWIND) && h->filled[which],
+            "matrix values have not been computed");
     const bool vs = which == PFV_MAT_VECTOR_SOURCE || which == PFV_MAT_BOUND_PRESSURE_VECTOR_SOURCE;
     if (!(vs && h->vs_implicit)) materialize_pattern(h, which);
     const pfv::CsrPattern& P = h->pattern_of(which);
@@ -1291,7 +1500,8 @@ pfv_status pfv_spmv(pfv_ctx* h, int which, const double* x, double* y) {
 pfv_status pfv_spmv_device(pfv_ctx* h, int which, const double* d_x, double* d_y) {
   return guarded(h, [&] {
     require(which >= 0 && which < PFV_NUM_MATS && d_x && d_y, "bad argument");
-    require((h->have_symbolic || which == PFV_MAT_USER_SYSTEM) && h->filled[which], "matrix values have not been computed");
+    require((h->have_symbolic || which == PFV_MAT_USER_SYSTEM || which >= PFV_MAT_UPWIND) && h->filled[which],
+            "matrix values have not been computed");
     if ((which == PFV_MAT_VECTOR_SOURCE || which == PFV_MAT_BOUND_PRESSURE_VECTOR_SOURCE) && h->vs_implicit) {
       pfv::spmv_vs_implicit(*h, h->val[which], d_x, d_y);
       return;
@@ -1304,7 +1514,8 @@ pfv_status pfv_spmv_device(pfv_ctx* h, int which, const double* d_x, double* d_y
 pfv_status pfv_spmv_device_rows(pfv_ctx* h, int which, int64_t nrows, const double* d_x, double* d_y) {
   return guarded(h, [&] {
     require(which >= 0 && which < PFV_NUM_MATS && d_x && d_y, "bad argument");
-    require((h->have_symbolic || which == PFV_MAT_USER_SYSTEM) && h->filled[which], "matrix values have not been computed");
+    require((h->have_symbolic || which == PFV_MAT_USER_SYSTEM || which >= PFV_MAT_UPWIND) && h->filled[which],
+            "matrix values have not been computed");
     materialize_pattern(h, which);
     const pfv::CsrPattern& P = h->pattern_of(which);
     require(nrows >= 0 && nrows <= P.nrows, "nrows out of range");
@@ -1771,6 +1982,10 @@ pfv_status pfv_solve(pfv_ctx* h, int method, double rtol, int maxit, int restart
     require(method == PFV_SOLVE_CG || method == PFV_SOLVE_BICGSTAB || method == PFV_SOLVE_GMRES,
             "method must be PFV_SOLVE_CG, PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES");
     require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
+    if (h->have_transport && h->active.val == h->val[PFV_MAT_TRANSPORT_SYSTEM].p && h->transport_zero_diag >= 0)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(h->transport_zero_diag) +
+                                                " of the transport system (a cell without outflow and without an "
+                                                "accumulation term): the Jacobi-preconditioned solver does not apply");
     auto s = h->stream;
     const size_t n = (size_t)h->active.n;
     double* dx = h->xsol.ensure(n);

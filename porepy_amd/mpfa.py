@@ -885,6 +885,22 @@ class Mpfa:
             raise RuntimeError("ad_flux_system(sd, ...) first")
         return ent[1].solve(method=method, rtol=rtol, maxit=maxit, precond=precond)
 
+    def darcy_flux(self, sd, data: dict, p, resident: bool = False):
+        """Face flux ``flux @ p + bound_flux @ bc_values (+ vector_source @ g)`` of the discretization on the device
+        (pfv_mpfa_face_flux).  ``resident``: the flux stays in HBM and a ``ResidentFlux`` handle comes back instead
+        of the array: store it as ``data[PARAMETERS][kw]["darcy_flux"]`` of an ``Upwind(kw, flow=self)``."""
+        from .upwind import flow_darcy_flux
+
+        if sd.dim < 2:
+            return self._tpfa().darcy_flux(sd, data, p, resident=resident)
+        pd = data[PARAMETERS][self.keyword]
+        ent = self._contexts.get(id(sd))
+        if ent is None or ent[0] is not sd:
+            raise RuntimeError("discretize(sd, data) must run on this object before darcy_flux")
+        if self._periodic.get(id(sd)) is not None:
+            raise _lib.PorefvError(5, "the device face flux does not cover periodic grids")
+        return flow_darcy_flux(ent[1], pd, p, self._vector_source(sd, pd), resident)
+
     def _vector_source(self, sd, pd):
         """Cell-wise vector source in the coordinates the device discretized in."""
         vs = pd.get("vector_source", None)

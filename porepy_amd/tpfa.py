@@ -109,6 +109,15 @@ class Tpfa:
         ctx.assemble(np.asarray(pd["bc_values"], dtype=float), pd.get("vector_source", None), None)
         return ctx.matrix(_lib.MAT_SYSTEM), ctx.rhs()
 
+    def darcy_flux(self, sd, data: dict, p, resident: bool = False):
+        """Face flux of the discretization on the device; see ``Mpfa.darcy_flux``."""
+        from .upwind import flow_darcy_flux
+
+        pd = data[PARAMETERS][self.keyword]
+        if self._periodic.get(id(sd)) is not None:
+            raise _lib.PorefvError(5, "the device face flux does not cover periodic grids")
+        return flow_darcy_flux(self._ctx(sd), pd, p, pd.get("vector_source", None), resident)
+
     def solve(self, sd, data: dict, source=None, method: str = "cg", rtol: float = 1e-12, maxit: int = 20000,
               x0=None, restart: int = 0, precond: str = "jacobi"):
         pd = data[PARAMETERS][self.keyword]

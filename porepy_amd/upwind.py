@@ -1,0 +1,204 @@
+"""``Upwind`` — first-order upwind advection on the device with the operator API of the reference's
+``pp.Upwind`` (numerics/fv/upwind.py:15-375): same keys, same stored patterns, and beyond it a transport
+solve and implicit Euler stepping that stay in HBM (csrc/upwind.inc).
+
+Sign convention of ``assemble_matrix_rhs`` (the reference's): it returns ``(A, b_ref)`` with
+``A = div @ diag(q) @ U`` and ``b_ref = div @ (rhs_neu + rhs_dir @ diag(q)) @ bc_values``, the boundary part of the
+flux divergence -- not a solver right-hand side.  The balance reads ``acc * (c - c_old) + A c + b_ref = source``;
+``solve`` / ``advance`` solve ``(diag(acc) + A) c = acc * c_old - b_ref + source``."""
+from __future__ import annotations
+
+import numpy as np
+import scipy.sparse as sps
+
+from . import _lib
+from .grid import grid_to_raw
+from .params import DISCRETIZATION_MATRICES, PARAMETERS, bc_flags
+
+
+class ResidentFlux:
+    """Stands for the face flux kept on a device handle (``Mpfa.darcy_flux(..., resident=True)``): put it where the
+    flux array goes, ``data[PARAMETERS][keyword]["darcy_flux"]``, and ``Upwind(flow=...)`` reads the flux in HBM."""
+
+    def __init__(self, context):
+        self.context = context
+
+    def __repr__(self):
+        return "ResidentFlux(<device handle>)"
+
+
+def flow_darcy_flux(ctx, pd: dict, p, vector_source=None, resident: bool = False):
+    """Face flux of the flow discretization on ``ctx`` for the cell pressures ``p``."""
+    q = ctx.face_flux(p, np.asarray(pd["bc_values"], dtype=float), vector_source, out=not resident)
+    return ResidentFlux(ctx) if resident else q
+
+
+class Upwind:
+    """Upwind discretization of ``keyword`` on the device.  ``flow``: an ``Mpfa`` / ``Tpfa`` object whose device
+    handle of a grid is shared, so that the flux it left resident can be taken without a copy."""
+
+    def __init__(self, keyword: str = "transport", device: int = 0, library=None, flow=None):
+        self.keyword = keyword
+        self.device = device
+        self._library = library
+        self._flow = flow
+        self.upwind_matrix_key = "transport"
+        self.bound_transport_dir_matrix_key = "rhs_dir"
+        self.bound_transport_neu_matrix_key = "rhs_neu"
+        self._flux_array_key = "darcy_flux"
+        self._contexts: dict = {}
+
+    @property
+    def flux_array_key(self) -> str:
+        return self._flux_array_key
+
+    @flux_array_key.setter
+    def flux_array_key(self, value: str) -> None:
+        self._flux_array_key = value
+
+    def ndof(self, sd) -> int:
+        return sd.num_cells
+
+    def context(self, sd) -> _lib.Context:
+        if self._flow is not None:
+            if hasattr(sd, "periodic_face_map"):
+                raise _lib.PorefvError(5, "upwind on periodic grids is not covered")
+            if sd.dim < 2 and hasattr(self._flow, "_tpfa"):  # (Mpfa hands 1-D grids to its Tpfa object)
+                return self._flow._tpfa().context(sd)
+            return self._flow.context(sd)
+        ent = self._contexts.get(id(sd))
+        if ent is None or ent[0] is not sd:
+            if hasattr(sd, "periodic_face_map"):
+                raise _lib.PorefvError(5, "upwind on periodic grids is not covered")
+            ctx = _lib.Context(self.device, self._library)
+            ctx.set_grid(grid_to_raw(sd))
+            self._contexts[id(sd)] = (sd, ctx)
+            return ctx
+        return ent[1]
+
+    # ---- the reference's API ---------------------------------------------------------
+    def _flux(self, sd, pd):
+        """The flux parameter: None for the resident one, else an array of Nf values."""
+        q = pd.get(self._flux_array_key, None)
+        if q is None or isinstance(q, ResidentFlux):
+            if self._flow is None and q is None:
+                raise KeyError(self._flux_array_key)
+            if isinstance(q, ResidentFlux) and q.context is not self.context(sd):
+                raise ValueError("the resident flux lives on another device handle: pass flow=<its discretization>")
+            return None
+        q = np.asarray(q, dtype=np.float64)
+        if q.shape != (sd.num_faces,):
+            raise ValueError(f"the flux array must have one entry per face ({sd.num_faces}), not shape {q.shape}")
+        return q
+
+    def discretize(self, sd, data: dict) -> None:
+        pd = data[PARAMETERS][self.keyword]
+        md = data.setdefault(DISCRETIZATION_MATRICES, {}).setdefault(self.keyword, {})
+        if sd.dim == 0:
+            md[self.upwind_matrix_key] = sps.csr_matrix((0, 1))
+            md[self.bound_transport_dir_matrix_key] = sps.csr_matrix((0, 0))
+            md[self.bound_transport_neu_matrix_key] = sps.csr_matrix((0, 0))
+            return
+        k = int(pd.get("num_components", 1))
+        if k < 1:
+            raise ValueError("num_components must be at least 1")
+        q = self._flux(sd, pd)
+        ctx = self.context(sd)
+        ctx.upwind_set_bc(bc_flags(pd["bc"]) if "bc" in pd else None)
+        try:
+            ctx.upwind_discretize(q, k)
+        except _lib.PorefvError as e:
+            if e.status == 4:  # (the reference fails in scipy's coo -> csr conversion with the same words)
+                raise ValueError(e.message) from None
+            raise
+        for key, which in ((self.upwind_matrix_key, _lib.MAT_UPWIND),
+                           (self.bound_transport_dir_matrix_key, _lib.MAT_UPWIND_RHS_DIR),
+                           (self.bound_transport_neu_matrix_key, _lib.MAT_UPWIND_RHS_NEU)):
+            md[key] = ctx.matrix(which)
+
+    def _assemble(self, sd, data, accumulation=None, c_old=None, source=None, bound_rhs=False):
+        pd = data[PARAMETERS][self.keyword]
+        ctx = self.context(sd)
+        try:
+            return ctx.upwind_assemble(np.asarray(pd["bc_values"], dtype=float), self._flux(sd, pd), accumulation, c_old,
+                                       source, bound_rhs=bound_rhs)
+        except _lib.PorefvError as e:
+            if e.status == 4:
+                raise ValueError(e.message) from None
+            raise
+
+    def assemble_matrix_rhs(self, sd, data: dict):
+        """``(A, b_ref)`` as the reference returns them (see the module text for the sign of ``b_ref``)."""
+        b = self._assemble(sd, data, bound_rhs=True)
+        return self.context(sd).matrix(_lib.MAT_TRANSPORT_SYSTEM), b
+
+    def darcy_flux(self, sd, beta, cell_apertures=None) -> np.ndarray:
+        """Flux of a constant velocity ``beta`` (3 values) through every face: ``beta . n_f`` with the area-weighted
+        normals of the grid, times the face aperture -- the mean of ``cell_apertures`` over the one or two cells of the
+        face, 1 where none are given.  One value per face (a point grid without faces gives an empty array)."""
+        vel = np.asarray(beta, dtype=np.float64).reshape(-1)
+        if vel.shape != (3,):
+            raise ValueError("beta must hold the three components of the velocity")
+        normals = np.asarray(sd.face_normals, dtype=np.float64).reshape(3, -1)
+        nf = normals.shape[1]
+        flux = vel @ normals
+        if cell_apertures is not None and nf:
+            inc = abs(sps.csr_matrix(sd.cell_faces))  # faces x cells incidence
+            cells_per_face = np.diff(inc.indptr)
+            flux = flux * ((inc @ np.asarray(cell_apertures, dtype=np.float64)) / cells_per_face)
+        return flux
+
+    # ---- beyond the reference: the transport step on the device -------------------------
+    def solve(self, sd, data: dict, accumulation=None, c_old=None, source=None, method: str = "bicgstab",
+              rtol: float = 1e-12, maxit: int = 20000, x0=None, restart: int = 0, precond: str = "jacobi"):
+        """Solve ``(diag(accumulation) + A) c = accumulation * c_old - b_ref + source``.  Returns (c, info).
+
+        The matrix of an acyclic flow field is triangular up to a permutation; BiCGStab (the default) breaks down on
+        it when the right-hand side sits in cells nothing flows back into -- injection into a field at rest, in any
+        dimension.  ``method="gmres"`` solves those; ``advance`` switches by itself."""
+        self._assemble(sd, data, accumulation, c_old, source)
+        return self.context(sd).solve(method=method, rtol=rtol, maxit=maxit, x0=x0, restart=restart, precond=precond)
+
+    def advance(self, sd, data: dict, c0, n_steps: int, accumulation, source=None, method: str = "bicgstab",
+                rtol: float = 1e-12, maxit: int = 20000, raise_on_fail: bool = True):
+        """``n_steps`` implicit Euler steps from ``c0`` with ``accumulation`` = porosity x volume / dt per cell, all
+        on the device.  Returns (c_n, info); info["steps_done"] counts the converged steps.  A step whose BiCGStab solve
+        breaks down (see ``solve``) is solved again with GMRES from the kept state; ``context(sd).stats()
+        ["transport_gmres_retries"]`` counts them."""
+        self._assemble(sd, data, accumulation, None, source)
+        return self.context(sd).transport_advance(c0, n_steps, method=method, rtol=rtol, maxit=maxit,
+                                                  raise_on_fail=raise_on_fail)
+
+
+def as_porepy_upwind(device: int = 0, library=None):
+    """Subclass of the reference's ``pp.Upwind`` whose discretization and assembly run on the device; rebind with
+    ``pp.Upwind = porepy_amd.as_porepy_upwind()`` before the model is built."""
+    import porepy as pp  # the reference; absent on the GPU box
+
+    _device, _library = device, library
+    _Ref = pp.Upwind
+
+    class HipUpwind(_Ref):  # type: ignore[misc]
+        def __init__(self, keyword: str = "transport"):
+            _Ref.__init__(self, keyword)
+            self._hip = Upwind(keyword, _device, _library)
+
+        def _sync_keys(self):
+            h = self._hip
+            h.keyword = self.keyword
+            h.upwind_matrix_key = self.upwind_matrix_key
+            h.bound_transport_dir_matrix_key = self.bound_transport_dir_matrix_key
+            h.bound_transport_neu_matrix_key = self.bound_transport_neu_matrix_key
+            h.flux_array_key = self.flux_array_key
+
+        def discretize(self, sd, data):
+            self._sync_keys()
+            return self._hip.discretize(sd, data)
+
+        def assemble_matrix_rhs(self, sd, data):
+            self._sync_keys()
+            if data[pp.PARAMETERS][self.keyword].get("num_components", 1) != 1 or sd.dim == 0:
+                return _Ref.assemble_matrix_rhs(self, sd, data)
+            return self._hip.assemble_matrix_rhs(sd, data)
+
+    return HipUpwind

@@ -1,0 +1,151 @@
+"""Times of the resident transport chain on the headline grid (6 * n^3 tetrahedra, n = 69: 1 971 054 cells), next to
+the same chain on the host with scipy, measured in the same run:
+
+    face flux -> upwind discretize -> assemble -> 20 implicit Euler steps
+
+Device times are HIP-event times from pfv_stats; the host times are wall clock.  Prints one JSON line.  A measurement,
+not a test: no thresholds.
+
+    python tools/bench_transport.py [--n-side 69] [--steps 20] [--no-host]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import scipy.sparse as sps
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import porepy_amd as pa  # noqa: E402
+from porepy_amd import _lib  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n-side", type=int, default=69)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--emulation", action="store_true", help="run on the host-emulation build (plumbing check)")
+    a = ap.parse_args()
+    lib = None
+    if a.emulation:
+        from tests import _parity as P
+
+        lib = P.emulation_library()
+    n = a.n_side
+    g = pa.StructuredTetrahedralGrid([n, n, n], [1.0, 1.0, 1.0])
+    g.compute_geometry()
+    g = pa.perturb_interior_nodes(g, 0.2 / n)
+    nc, nf = g.num_cells, g.num_faces
+    rng = np.random.default_rng(0)
+    k = 1 + rng.random(nc)
+    K = pa.SecondOrderTensor(kxx=k, kyy=1.5 * k, kzz=0.7 * k, kxy=0.1 * k)
+    bf = g.get_all_boundary_faces()
+    bc = pa.BoundaryCondition(g, bf, ["dir"] * bf.size)
+    fbv = np.zeros(nf)
+    fbv[bf] = g.face_centers[:, bf].sum(axis=0)
+    fdata = pa.initialize_data({}, "flow", {"second_order_tensor": K, "bc": bc, "bc_values": fbv})
+    ctx = pa.Context(0, lib)
+    ctx.set_grid(pa.grid_to_raw(g))
+    ctx.set_params(K.values, pa.bc_flags(bc), None, 1.0 / 3.0, None)
+    ctx.discretize(rebuild_topology=True, skip_vector_source=True)
+    ctx.assemble(fbv)
+    p, info = ctx.solve("bicgstab", rtol=1e-10, maxit=20000, precond="amg", raise_on_fail=False)
+    out = {"cells": nc, "faces": nf, "flow_iterations": info["iterations"], "flow_assemble_ms": ctx.stats()["assemble_ms"]}
+    tbv = np.zeros(nf)
+    tbv[bf] = rng.random(bf.size)
+    dt = 0.5 / n  # about one cell per step at unit velocity
+    acc = 0.2 * g.cell_volumes / dt
+    c0 = np.zeros(nc)
+
+    def best(fn, key):
+        vals = []
+        for _ in range(a.reps):
+            fn()
+            vals.append(ctx.stats()[key])
+        return min(vals), float(np.median(vals))
+
+    out["face_flux_ms"] = best(lambda: ctx.face_flux(p, fbv, out=False), "face_flux_ms")
+    ctx.upwind_set_bc(None)
+    out["upwind_discretize_ms"] = best(lambda: ctx.upwind_discretize(None, 1), "upwind_ms")
+    out["transport_assemble_ms"] = best(lambda: ctx.upwind_assemble(tbv, None, accumulation=acc), "transport_assemble_ms")
+    c, ainfo = ctx.transport_advance(c0, a.steps, rtol=1e-10, raise_on_fail=False)
+    st = ctx.stats()
+    out["advance"] = {"steps_done": ainfo["steps_done"], "ms_per_step": st["transport_advance_ms"] / max(a.steps, 1),
+                      "iterations_per_step": st["transport_iterations"] / max(a.steps, 1)}
+    # bytes each kernel has to move at least ("Upwind advection"): the fraction of a stream rate follows
+    nnz_flux = ctx.matrix_info(_lib.MAT_FLUX)[2]
+    nnz_bound = ctx.matrix_info(_lib.MAT_BOUND_FLUX)[2]
+    nnz_T = ctx.matrix_info(_lib.MAT_TRANSPORT_SYSTEM)[2]
+    ncf = ctx.ncf
+    out["min_bytes"] = {
+        "face_flux": 12 * (nnz_flux + nnz_bound) + 8 * (nf + nc) + 8 * nf,
+        "upwind_discretize": nf * (8 + 8 + 8 + 1 + 4 + 12 + 16) + 3 * 4 * nf + 12 * nf,
+        "transport_assemble": 12 * nnz_T + ncf * (4 + 1 + 1 + 4 + 8) + 8 * 4 * nc,
+    }
+    if not a.no_host:
+        flux, bflux = ctx.matrix(_lib.MAT_FLUX), ctx.matrix(_lib.MAT_BOUND_FLUX)
+        t0 = time.perf_counter()
+        qh = flux @ p + bflux @ fbv
+        t1 = time.perf_counter()
+        cf = sps.csc_matrix(g.cell_faces)
+        fi, ci, sg = sps.find(cf)
+        side = -np.ones((2, nf), dtype=np.int64)
+        side[0, fi[sg > 0]] = ci[sg > 0]
+        side[1, fi[sg < 0]] = ci[sg < 0]
+        pos = np.sign(qh) >= 0
+        up = np.where(pos, side[0], side[1])
+        isd = np.zeros(nf, dtype=bool)
+        isd[bf] = True
+        dirin = isd & (up < 0)
+        f = np.flatnonzero(~dirin)
+        U = sps.coo_matrix((np.ones(f.size), (f, up[f])), shape=(nf, nc)).tocsr()
+        fd = np.flatnonzero(dirin)
+        D = sps.coo_matrix((np.ones(fd.size), (fd, fd)), shape=(nf, nf)).tocsr()
+        t2 = time.perf_counter()
+        div = cf.T.tocsr()
+        Q = sps.diags(qh)
+        Ah = (div @ Q @ U + sps.diags(acc)).tocsr()
+        bh = div @ ((D @ Q) @ tbv)
+        t3 = time.perf_counter()
+        out["host_ms"] = {"face_flux": 1e3 * (t1 - t0), "upwind_discretize": 1e3 * (t2 - t1),
+                          "assemble": 1e3 * (t3 - t2)}
+        # the host step: the same Jacobi-BiCGStab through scipy on the host matrix
+        import scipy.sparse.linalg as spla
+
+        Mj = spla.LinearOperator((nc, nc), matvec=lambda x: x / Ah.diagonal())
+        ch = c0.copy()
+        hsteps = min(a.steps, 3)
+        # every step is judged by its TRUE relative residual ||r - M c|| / ||r|| against the host matrix, for the host
+        # solve and for the device solve advanced one step at a time from the same state
+        flags, res_h, res_d, gap = [], [], [], []
+        cd = c0.copy()
+        t_host = 0.0
+        for _ in range(hsteps):
+            rh = acc * ch - bh
+            t4 = time.perf_counter()
+            ch_new, flag = spla.bicgstab(Ah, rh, x0=ch, rtol=1e-10, M=Mj, maxiter=5000)
+            t_host += time.perf_counter() - t4
+            flags.append(int(flag))
+            res_h.append(float(np.linalg.norm(rh - Ah @ ch_new) / np.linalg.norm(rh)))
+            ch = ch_new
+            rd = acc * cd - bh
+            cd, _ = ctx.transport_advance(cd, 1, rtol=1e-10, raise_on_fail=False)
+            res_d.append(float(np.linalg.norm(rd - Ah @ cd) / np.linalg.norm(rd)))
+            gap.append(float(np.abs(cd - ch).max()))
+        out["host_ms"]["step"] = 1e3 * t_host / hsteps
+        out["host_bicgstab_flags"] = flags  # scipy: 0 converged, > 0 iterations exhausted, < 0 breakdown
+        out["true_rel_residual_host"] = res_h
+        out["true_rel_residual_device"] = res_d
+        out["device_vs_host_max_diff_per_step"] = gap
+        out["gmres_retries_last_advance"] = ctx.stats()["transport_gmres_retries"]
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

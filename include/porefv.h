@@ -371,6 +371,36 @@ pfv_status pfv_set_near_null_space(pfv_ctx* h, int bs, int k, const double* B);
 pfv_status pfv_amg_nns_level(pfv_ctx* h, int level, int64_t* info, int32_t* agg, double* P, double* B, double* Bc,
                              int32_t* indptr, int32_t* indices, double* val);
 
+/* Introspection of the plain aggregation hierarchy (PFV_PRECOND_AMG) that was set up last on this handle, by
+ * pfv_amg_setup or by a pfv_solve with PFV_PRECOND_AMG (tests).  It only copies data out: no kernel, launch or buffer
+ * of the setup or the cycle depends on it.  Numbering: the hierarchy of pfv_amg_setup is built on the active system as
+ * it is, so its level 0 -- and the vectors of pfv_amg_apply_device -- are in the CALLER's numbering of the unknowns,
+ * for grid systems too (cell-major / component-minor); the hierarchy of a pfv_solve of a grid system is in the
+ * numbering the solve worked in (the renumbering along the cell order, when pfv_solve applied it).
+ * info[24] = { 0 rows n_l, 1 block size, 2 levels, 3 coarse cells (0 on the coarsest level), 4 nnz of A_l, 5 nnz of the
+ *   operator, 6 nnz of the system (level 0, else 0), 7 the cycle's products read the FP32 copy of the operator's values,
+ *   8 path bits of this level (1 residual inside the restriction, 2 prolongation inside the post-smoothing of a small
+ *   level, 4 prolongation inside the post-smoothing product of a larger level, 8 visited twice by its parent, 16 visits
+ *   the next level twice, 32 ... with residual and first smoothing step in one product, 64 coarsest level by the dense
+ *   inverse, 128 coarsest level by Jacobi sweeps), 9 dense inverse in use, 10 gamma, 11 gamma_levels, 12 fuse_rows,
+ *   13 fuse_cycle, 14 the last setup kept its aggregate maps (values-only branch), 15 filter_level0, 16 restrict_lanes,
+ *   17 the level's products go through an SpMV window, 18 mptr / mem are kept, 19 largest number of entries gathered
+ *   into one coarse row by the Galerkin products of the last setup, 20 kAmgDenseMax, 21 kGalEpl, 22 kGalMaxMembers,
+ *   23 kAmgWTopRows };  params[4] = { omega_l, alpha, filter theta, rho_l (0: not estimated) }.
+ * Each of the following is optional (NULL: skipped); CSR triples are indptr [n_l + 1], indices and FP64 values [nnz]:
+ *   sys_*  level 0 only: the matrix the setup was given (the leading block for n_own < n), before the strength filter;
+ *   a_*    A_l, the matrix the level was coarsened from (level 0: the strength-filtered copy when the filter is on);
+ *   op_*   the operator the cycle's products read on the level (level 0: the filtered copy when filter_level0 is set,
+ *          else the system); the products read its values rounded to FP32 when info[7] is set;
+ *   dinv [n_l] the smoother's inverse diagonal after the row safeguard; agg [n_l / bs] cell -> coarse cell,
+ *   mptr [coarse cells + 1] and mem [n_l / bs] the members of every coarse cell (not on the coarsest level);
+ *   dense [n_l * n_l] row-major inverse of the coarsest matrix (coarsest level, info[9] set).
+ * PFV_ERR_ARGUMENT: no hierarchy or level out of range; PFV_ERR_UNSUPPORTED: the coupled hierarchy of a sharded solve. */
+pfv_status pfv_amg_level(pfv_ctx* h, int level, int64_t* info, double* params, int32_t* sys_indptr, int32_t* sys_indices,
+                         double* sys_val, int32_t* a_indptr, int32_t* a_indices, double* a_val, int32_t* op_indptr,
+                         int32_t* op_indices, double* op_val, double* dinv, int32_t* agg, int32_t* mptr, int32_t* mem,
+                         double* dense);
+
 /* Block preconditioner (PFV_PRECOND_BLOCK) for the coupled Jacobians of mixed-dimensional / multi-physics models
  * that the reference solves directly (models/solution_strategy.py:830-884; mortar coupling
  * models/constitutive_laws.py:987-1000): the unknowns of the system given to pfv_set_system are grouped in

@@ -45,7 +45,7 @@ EXPORTS = [
     "pfv_rccl_unique_id", "pfv_rccl_comm_create", "pfv_rccl_set_halo_plan", "pfv_rccl_hooks", "pfv_rccl_stats",
     "pfv_rccl_last_error", "pfv_rccl_comm_destroy", "pfv_mpfa_ad_flux_system", "pfv_host_alloc", "pfv_host_free",
     "pfv_mpsa_set_subface_eta", "pfv_mpsa_set_reconstruction_eta", "pfv_mpsa_set_reconstruction_eta_subface", "pfv_get_stats_n", "pfv_set_block_preconditioner",
-    "pfv_mpfa_set_permeability", "pfv_set_near_null_space", "pfv_amg_nns_level",
+    "pfv_mpfa_set_permeability", "pfv_set_near_null_space", "pfv_amg_nns_level", "pfv_amg_level",
     "pfv_mpfa_face_flux", "pfv_upwind_set_bc", "pfv_upwind_discretize", "pfv_upwind_assemble", "pfv_transport_advance",
 ]
 
@@ -223,6 +223,9 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_set_near_null_space.restype = C.c_int
     lib.pfv_amg_nns_level.argtypes = [_h, C.c_int, _lp, _ip, _dp, _dp, _dp, _ip, _ip, _dp]
     lib.pfv_amg_nns_level.restype = C.c_int
+    lib.pfv_amg_level.argtypes = [_h, C.c_int, _lp, _dp, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _ip, _dp, _dp, _ip, _ip, _ip,
+                                  _dp]
+    lib.pfv_amg_level.restype = C.c_int
     lib.pfv_get_stats_n.argtypes = [_h, C.c_void_p, C.c_size_t]
     lib.pfv_get_stats_n.restype = C.c_int
     lib.pfv_time_kernel.argtypes = [_h, C.c_int, C.c_int, _dp]
@@ -1052,6 +1055,61 @@ class Context:
                                                _ptr(Bc, _dp) if nagg else None, _ptr(ip, _ip), _ptr(ix, _ip), _ptr(v, _dp)))
         return {"n": n, "block_size": bs, "k": k, "aggregates": nagg, "levels": nlev, "agg": agg, "P": P, "B": B,
                 "Bc": Bc, "A": sps.csr_matrix((v, ix, ip), shape=(n, n))}
+
+    AMG_PATH_BITS = {"restrict_residual": 1, "prolong_smooth": 2, "fused_product": 4, "visited_twice": 8,
+                     "second_visit": 16, "second_visit_fused": 32, "dense": 64, "jacobi": 128}
+
+    def amg_level(self, level: int) -> dict:
+        """Level ``level`` of the plain AMG hierarchy set up last on this handle (pfv_amg_level; read-only).  ``A``: the
+        matrix the level was coarsened from, ``op``: the operator the cycle's products read (its values rounded to FP32
+        when ``fp32``), ``sys`` (level 0): the matrix the setup was given; ``dinv`` after the row safeguard, ``omega``,
+        ``agg`` / ``mptr`` / ``mem`` (None on the coarsest level), ``dense`` (the coarsest level's inverse or None),
+        the cycle's global parameters, ``path``: the names of AMG_PATH_BITS the level takes, ``reused``: the last setup
+        kept its aggregate maps.  Level 0 of a ``amg_setup`` hierarchy is in the caller's numbering."""
+        import scipy.sparse as sps
+
+        info = np.zeros(24, dtype=np.int64)
+        par = np.zeros(4)
+        lp = info.ctypes.data_as(_lp)
+        none = [None] * 14
+        self._check(self.lib.pfv_amg_level(self._h, int(level), lp, _ptr(par, _dp), *none))
+        n, bs, nlev, ncc, nnz_a, nnz_op, nnz_sys = (int(v) for v in info[:7])
+        last = ncc == 0
+        dense_here = last and bool(info[9])
+
+        def triple(nnz):
+            return np.empty(n + 1, dtype=np.int32), np.empty(nnz, dtype=np.int32), np.empty(nnz)
+
+        s3, a3, o3 = triple(nnz_sys), triple(nnz_a), triple(nnz_op)
+        dinv = np.empty(n)
+        agg = np.empty(0 if last else n // bs, dtype=np.int32)
+        members = bool(info[18])
+        mptr = np.empty(ncc + 1 if members else 0, dtype=np.int32)
+        mem = np.empty(n // bs if members else 0, dtype=np.int32)
+        dense = np.empty((n, n) if dense_here else (0, 0))
+
+        def p3(t, on=True):
+            return [(_ptr(a, _ip if a.dtype == np.int32 else _dp) if on else None) for a in t]
+
+        self._check(self.lib.pfv_amg_level(
+            self._h, int(level), lp, _ptr(par, _dp), *p3(s3, level == 0), *p3(a3), *p3(o3), _ptr(dinv, _dp),
+            None if last else _ptr(agg, _ip), _ptr(mptr, _ip) if members else None,
+            _ptr(mem, _ip) if members else None, _ptr(dense, _dp) if dense_here else None))
+
+        def mat(t):
+            return sps.csr_matrix((t[2], t[1], t[0]), shape=(n, n))  # (as stored: unsorted columns stay unsorted)
+
+        bits = int(info[8])
+        return {"n": n, "block_size": bs, "levels": nlev, "coarse_cells": ncc, "A": mat(a3), "op": mat(o3),
+                "sys": mat(s3) if level == 0 else None, "fp32": bool(info[7]), "dinv": dinv, "omega": float(par[0]),
+                "alpha": float(par[1]), "filter_theta": float(par[2]), "rho": float(par[3]),
+                "agg": None if last else agg, "mptr": mptr if members else None, "mem": mem if members else None,
+                "dense_ok": bool(info[9]), "dense": dense if dense_here else None, "gamma": int(info[10]),
+                "gamma_levels": int(info[11]), "fuse_rows": int(info[12]), "fuse_cycle": bool(info[13]),
+                "reused": bool(info[14]), "filter_level0": bool(info[15]), "restrict_lanes": bool(info[16]),
+                "window": bool(info[17]), "galerkin_max_gather": int(info[19]), "dense_max": int(info[20]),
+                "gal_epl": int(info[21]), "gal_max_members": int(info[22]), "w_top_rows": int(info[23]),
+                "path_bits": bits, "path": {k for k, b in self.AMG_PATH_BITS.items() if bits & b}}
 
     def set_block_preconditioner(self, block_ptr, gauss_seidel: bool = True):
         """Contiguous blocks [block_ptr[k], block_ptr[k+1]) of the system of ``set_system``: the following solves with

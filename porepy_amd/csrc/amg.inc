@@ -187,7 +187,29 @@ struct Amg {
                            // and first smoothing step in one product, its correction folded into the parent's prolongation
   bool fp32 = true;    // cycle products read single-precision matrix values (vectors stay double)
   double setup_ms = 0.0, op_complexity = 0.0;
+  const CsrPattern* sysP = nullptr;  // the matrix the last setup was given (before the filter; pfv_amg_level reads it)
+  const double* sysV = nullptr;
 };
+
+// which spelling of the cycle level l takes (amg_cycle decides by it; pfv_amg_level reports it)
+struct AmgPath {
+  bool small = false;     // residual inside the restriction (amg_restrict_residual)
+  bool twice = false;     // this level is visited twice by its parent
+  bool fuse_up = false;   // prolongation inside the post-smoothing product of a small level (amg_prolong_smooth)
+  bool fuse_big = false;  // ... of a larger level (MODE 4 of the products)
+  bool second = false;    // this level visits the next one a second time
+};
+static AmgPath amg_level_path(const Amg& amg, size_t l) {
+  AmgPath p;
+  if (l + 1 >= amg.nlev) return p;
+  const AmgLevel& L = *amg.lev[l];
+  p.small = L.n <= amg.fuse_rows && !(L.win && L.win->ok);
+  p.twice = amg.gamma == 2 && l >= 1 && (int)l <= amg.gamma_levels;
+  p.fuse_up = p.small && l >= 1 && !p.twice;
+  p.fuse_big = amg.fuse_cycle && !p.small && l >= 1;
+  p.second = amg.gamma == 2 && (int)l < amg.gamma_levels && l + 2 < amg.nlev;
+  return p;
+}
 
 inline Amg::Amg() = default;
 inline Amg::~Amg() = default;
@@ -1049,6 +1071,8 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
   AmgDist* D = amg.dist.get();  // coupled hierarchy of a sharded solve (amg_dist.inc): A = owned rows x (owned + halo)
   amg.bs = bs;
   amg.valid = amg.dense_ok = false;
+  amg.sysP = &A;
+  amg.sysV = val;
   // damping of the Jacobi smoothers: PFV_AMG_OMEGA_PCT fixes it for all levels (80 was the value fitted to the benchmark
   // matrix: 70 -> 27, 80 -> 23, 90 -> 3455 iterations -- at 0.9 omega rho(D^-1 A) crosses 2 and the smoother amplifies);
   // unset, every level gets omega = PFV_AMG_OMEGA_RHO_PCT / 100 / rho_l from a power-iteration estimate of its own
@@ -1212,8 +1236,9 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
                                             ? read_scalar<unsigned long long>(s, launch_pattern_checksum(c, wk.csum, amg.filtP))
                                             : 0ull;
         level0_sum = fsum;
+        // (PFV_SPMV_WINDOW=0 switches a kept window off too, not only the building of a new one)
         const bool keep = fsum != 0 && amg.filt_win.ok && amg.filt_win_sum == fsum && amg.filt_win.nrows == amg.filtP.nrows &&
-                          amg.filt_win.nnz == amg.filtP.nnz;
+                          amg.filt_win.nnz == amg.filtP.nnz && env_int("PFV_SPMV_WINDOW", 1) != 0;
         if (!keep) {
           // (the filtered rows are subsets of A's rows: their windows come out of A's windows without hashing or
           // sorting -- spmv_win.inc: win_derive; from scratch where A has none)
@@ -1809,14 +1834,15 @@ static double* amg_cycle(pfv_ctx_impl& c, Amg& amg, size_t l, const double* b, d
   const double omega_n = Ln.omega;  // the next level's first smoothing step (from a zero guess) rides in the restriction
   // fused launches on small levels without an SpMV window; the result of a fused post-smoothing lands in t, so it is
   // kept off level 0 (the caller's x) and off the levels their parent visits twice (the second visit would reuse t)
-  const bool small = n <= amg.fuse_rows && !(L.win && L.win->ok);
-  const bool twice = amg.gamma == 2 && l >= 1 && (int)l <= amg.gamma_levels;  // (this level: visited twice by its parent)
-  const bool fuse_up = small && l >= 1 && !twice;
+  const AmgPath path = amg_level_path(amg, l);
+  const bool small = path.small;
+  const bool twice = path.twice;  // (this level: visited twice by its parent)
+  const bool fuse_up = path.fuse_up;
   // larger coarse levels (PFV_AMG_FUSE_CYCLE): the prolongation inside the post-smoothing product (k_spmv_win MODE 4).
   // The result cannot overwrite x (other row blocks still read it): it lands in t -- or, on the first visit of a level
   // visited twice, in u, which the second visit (whose scratch t is) leaves alone.  Level 0 keeps the two launches: its
   // result belongs in the caller's x, and forming t per WINDOW column there would cost more bytes than t's round trip.
-  const bool fuse_big = amg.fuse_cycle && !small && l >= 1;
+  const bool fuse_big = path.fuse_big;
   if (!x_is_presmoothed) parallel_for(s, n, PFV_LAMBDA(int64_t i) { x[i] = omega * dinv[i] * b[i]; });
   // restriction; the first smoothing step of the next level (from a zero guess) rides along
   const bool next_smooths = l + 2 < amg.nlev;
@@ -1829,7 +1855,7 @@ static double* amg_cycle(pfv_ctx_impl& c, Amg& amg, size_t l, const double* b, d
   }
   double* xc = amg_cycle(c, amg, l + 1, Ln.b, Ln.x, next_smooths, 0);
   const double* xc2 = nullptr;  // correction of the second visit, folded into this level's prolongation
-  if (amg.gamma == 2 && (int)l < amg.gamma_levels && l + 2 < amg.nlev) {
+  if (path.second) {
     // second visit: correct the coarse solution with a cycle on its residual (levels visited twice keep their
     // result in Ln.x or Ln.u: see fuse_up / fuse_big)
     double* r2 = Ln.r2.ensure(Ln.n);

@@ -275,6 +275,7 @@ struct pfv_ctx_impl {
   unsigned long long symb_key = 0;   // ... of the topology the symbolic outputs on the handle were built from (0: none / replaced)
   std::unique_ptr<BlockPc> block_pc;  // pfv_set_block_preconditioner
   std::unique_ptr<Amg> amg_block;    // pfv_amg_setup: hierarchy of the leading block (sharded solves)
+  int amg_last = 0;                  // which of the two was set up last (1: amg, 2: amg_block; pfv_amg_level reads that one)
   // PFV_PRECOND_AMG_NNS (pfv_set_near_null_space): its hierarchy lives apart from `amg`, so setting or clearing the modes
   // never touches the plain one
   std::unique_ptr<AmgNns> amg_nns;

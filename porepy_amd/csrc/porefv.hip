@@ -1723,6 +1723,7 @@ pfv_status pfv_amg_setup(pfv_ctx* h, int64_t n_own) {
     h->stats.amg_levels = (int64_t)h->amg_block->nlev;
     h->stats.amg_coarsest_rows = h->amg_block->lev[h->amg_block->nlev - 1]->n;
     h->stats.amg_maps_reused = h->amg_block->reused ? 1 : 0;
+    h->amg_last = 2;
   });
 }
 
@@ -1932,6 +1933,80 @@ pfv_status pfv_amg_nns_level(pfv_ctx* h, int level, int64_t* info, int32_t* agg,
   });
 }
 
+pfv_status pfv_amg_level(pfv_ctx* h, int level, int64_t* info, double* params, int32_t* sys_indptr, int32_t* sys_indices,
+                         double* sys_val, int32_t* a_indptr, int32_t* a_indices, double* a_val, int32_t* op_indptr,
+                         int32_t* op_indices, double* op_val, double* dinv, int32_t* agg, int32_t* mptr, int32_t* mem,
+                         double* dense) {
+  return guarded(h, [&] {
+    require(info != nullptr, "info is required");
+    const pfv::Amg* ap = h->amg_last == 1 ? h->amg.get() : (h->amg_last == 2 ? h->amg_block.get() : nullptr);
+    require(ap && ap->valid, "no AMG hierarchy (pfv_amg_setup or a solve with PFV_PRECOND_AMG first)");
+    const pfv::Amg& amg = *ap;
+    if (amg.dist) throw pfv::Error(PFV_ERR_UNSUPPORTED, "pfv_amg_level does not read the coupled hierarchy of a sharded solve");
+    require(level >= 0 && (size_t)level < amg.nlev, "level out of range");
+    const size_t l = (size_t)level;
+    const pfv::AmgLevel& L = *amg.lev[l];
+    const bool last = l + 1 == amg.nlev;
+    // the matrix the level was coarsened from: the strength-filtered copy on level 0 when the filter is on
+    const bool filtered = l == 0 && amg.filter_theta > 0.0 && amg.filt_nnz > 0;
+    const pfv::CsrPattern* Pa = filtered ? &amg.filtP : L.P;
+    const double* Va = filtered ? amg.filtV.p : L.val;
+    const pfv::AmgPath path = pfv::amg_level_path(amg, l);
+    int maxcap = 0;
+    for (const auto& g : amg.gal_sizes) maxcap = std::max(maxcap, g.maxcap);
+    info[0] = L.n;
+    info[1] = amg.bs;
+    info[2] = (int64_t)amg.nlev;
+    info[3] = last ? 0 : L.nc_cells;
+    info[4] = Pa->nnz;
+    info[5] = L.P->nnz;
+    info[6] = l == 0 ? amg.sysP->nnz : 0;
+    info[7] = L.v32 ? 1 : 0;
+    info[8] = (path.small ? 1 : 0) | (path.fuse_up ? 2 : 0) | (path.fuse_big ? 4 : 0) | (path.twice ? 8 : 0) |
+              (path.second ? 16 : 0) | (path.second && amg.fuse_cycle ? 32 : 0) | (last && amg.dense_ok ? 64 : 0) |
+              (last && !amg.dense_ok ? 128 : 0);
+    info[9] = amg.dense_ok ? 1 : 0;
+    info[10] = amg.gamma;
+    info[11] = amg.gamma_levels;
+    info[12] = amg.fuse_rows;
+    info[13] = amg.fuse_cycle ? 1 : 0;
+    info[14] = amg.reused ? 1 : 0;
+    info[15] = amg.filter_level0 ? 1 : 0;
+    info[16] = amg.restrict_lanes ? 1 : 0;
+    info[17] = (L.win && L.win->ok) ? 1 : 0;
+    info[18] = (!last && L.mptr.p && L.mem.p) ? 1 : 0;
+    info[19] = maxcap;
+    info[20] = pfv::kAmgDenseMax;
+    info[21] = pfv::kGalEpl;
+    info[22] = pfv::kGalMaxMembers;
+    info[23] = pfv::kAmgWTopRows;
+    if (params) {
+      params[0] = L.omega;
+      params[1] = amg.alpha;
+      params[2] = amg.filter_theta;
+      params[3] = L.rho;
+    }
+    auto s = h->stream;
+    auto csr = [&](const pfv::CsrPattern& P, const double* v, int32_t* ip, int32_t* ix, double* val) {
+      if (ip) be_d2h(ip, P.indptr.p, sizeof(int32_t) * (size_t)(P.nrows + 1), s);
+      if (ix && P.nnz > 0) be_d2h(ix, P.indices.p, sizeof(int32_t) * (size_t)P.nnz, s);
+      if (val && P.nnz > 0) be_d2h(val, v, sizeof(double) * (size_t)P.nnz, s);
+    };
+    if (l == 0) csr(*amg.sysP, amg.sysV, sys_indptr, sys_indices, sys_val);
+    csr(*Pa, Va, a_indptr, a_indices, a_val);
+    csr(*L.P, L.val, op_indptr, op_indices, op_val);
+    if (dinv) be_d2h(dinv, L.dinv.p, sizeof(double) * (size_t)L.n, s);
+    const int64_t cells = L.n / amg.bs;
+    if (!last) {
+      if (agg) be_d2h(agg, L.agg.p, sizeof(int32_t) * (size_t)cells, s);
+      if (mptr) be_d2h(mptr, L.mptr.p, sizeof(int32_t) * (size_t)(L.nc_cells + 1), s);
+      if (mem) be_d2h(mem, L.mem.p, sizeof(int32_t) * (size_t)cells, s);
+    }
+    if (dense && last && amg.dense_ok) be_d2h(dense, amg.dense.p, sizeof(double) * (size_t)(L.n * L.n), s);
+    pfv::be_sync(s);
+  });
+}
+
 // The system the Krylov loop works on: the active one, renumbered along the cell order when it is a
 // grid system (reorder.inc), with the SpMV windows of its pattern (spmv_win.inc).  Copies and
 // windows are kept until the matrix is assembled again.
@@ -2009,6 +2084,7 @@ pfv_status pfv_solve(pfv_ctx* h, int method, double rtol, int maxit, int restart
       if (!h->amg->valid || h->amg_for_val != sys.val) {
         pfv::amg_setup(*h, *h->amg, *sys.P, sys.val, h->active_bs, sys.diag, sys.win);
         h->amg_for_val = sys.val;
+        h->amg_last = 1;
         h->stats.amg_setup_ms = h->amg->setup_ms;
         h->stats.amg_operator_complexity = h->amg->op_complexity;
         h->stats.amg_levels = (int64_t)h->amg->nlev;

@@ -18,6 +18,10 @@
 // correction scaled by alpha (over-correction compensates the flat prolongation), damped Jacobi;
 // the first coarse level is visited twice (second visit on its residual), V-cycle below.
 // It is a fixed linear operator, so BiCGStab / CG / GMRES use it as an ordinary preconditioner.
+//
+// The PFV_AMG_* environment switches are read in ONE place, amg_read_switches, at the start of every setup (never
+// cached: callers change the environment between setups of one process); everything else takes the values from the
+// AmgSwitches it fills.  amg_maps_cfg / amg_maps_tag alone define which of them the kept aggregate maps depend on.
 
 namespace pfv {
 
@@ -32,6 +36,119 @@ constexpr int kAmgPasses = 3;        // pairwise passes per level (aggregates of
 constexpr int kAmgGentleCells = 400000;  // finest levels with at least this many cells: 2 passes per level below it
 constexpr int kGalEpl = 8;           // Galerkin product: entries of a coarse row per lane in the batched gather
 constexpr int kGalMaxMembers = 16;   // ... and member rows of an aggregate it handles (more: member-by-member gather)
+constexpr int64_t kAmgGatherRowsDefault = 32768;  // coupled hierarchy: levels of at most this many rows over all ranks are gathered
+
+// The switches of one setup of the plain hierarchy (and of the helpers the near-null-space hierarchy shares with it).
+struct AmgSwitches {
+  int bs = 1;  // block size the defaults were resolved for
+  // damping of the Jacobi smoothers: PFV_AMG_OMEGA_PCT fixes it for all levels (80 was the value fitted to the benchmark
+  // matrix: 70 -> 27, 80 -> 23, 90 -> 3455 iterations -- at 0.9 omega rho(D^-1 A) crosses 2 and the smoother amplifies);
+  // unset, every level gets omega = PFV_AMG_OMEGA_RHO_PCT / 100 / rho_l from a power-iteration estimate of its own
+  // rho(D^-1 A) (amg_estimate_omegas) when PFV_AMG_OMEGA_AUTO is on
+  bool omega_auto = false;
+  // (scalar systems run the row-wise safeguard, amg_safeguard_rows: any omega <= 1 is stable there and the iteration
+  // count falls monotonically towards 1 -- 0.7: 28, 0.8: 26, 0.9: 24, 1.0: 22 at 197 k cells; block systems keep 0.8)
+  bool safe_rows = true;  // PFV_AMG_SAFE_ROWS (block systems: switch only)
+  double omega = 0.95, alpha = 1.5;  // PFV_AMG_OMEGA_PCT (default 95 with the safeguard, else 80), PFV_AMG_ALPHA_PCT
+  int omega_power_steps = 10;        // PFV_AMG_OMEGA_POWER_STEPS, 2..30
+  double omega_sigma = 1.8;          // PFV_AMG_OMEGA_RHO_PCT / 100
+  int passes = kAmgPasses;           // PFV_AMG_PASSES, 1..6
+  // PFV_AMG_PASSES_COARSE as given (-1: unset -- the default follows the size of the finest level, amg_coarsen_level,
+  // which also clamps to 1..6)
+  bool passes_coarse_set = false;
+  int passes_coarse_raw = -1;
+  int rounds = kAmgRounds, rounds_raw = kAmgRounds;  // PFV_AMG_ROUNDS: 1..12 for the matching / as given for amg_maps_cfg
+  int strength_neg = 0;              // PFV_AMG_STRENGTH_NEG (AmgGraph::neg_only)
+  bool fp32 = true;                  // PFV_AMG_FP32
+  // PFV_AMG_FILTER_PERMIL / _BLOCK, as a fraction
+  // (block systems: blocks weaker than 0.05 of the strongest of either end.  configs[3], 1.5 M dofs: 0.03 -> 263 ms per
+  // step, 0.1 -> 243, against ~280 unfiltered; 0.2 costs 67 instead of 43 iterations and 0.3 diverges -- the block
+  // measure is cruder than the scalar one, the default keeps a factor 4 from the first degradation)
+  double filter_theta = 0.0;
+  int coarse_target = kAmgCoarseTargetDefault;  // PFV_AMG_COARSE_TARGET, 1..kAmgDenseMax
+  // W at the top (second visit of the first coarse level) pays on large systems, where the finest-level products
+  // dominate and every saved Krylov iteration is worth ~1.6 ms (2 M cells: 89.6 vs 92.4 ms per step); below
+  // kAmgWTopRows the cycle is a chain of ~5 us launches and the second visit just doubles it (197 k cells: 13.1 vs
+  // 15.1 ms, 257 k: 18.2 vs 21.8 ms with the V-cycle although it needs 3-4 iterations more)
+  // PFV_AMG_GAMMA as given: the default follows the size, which the coupled hierarchy learns from its gather (amg_setup
+  // resolves and clamps to 1..2)
+  bool gamma_set = false;
+  int gamma_raw = 0;
+  int gamma_levels = 1;              // PFV_AMG_GAMMA_LEVELS
+  // fused launches on the small levels (neutral at 2 M cells, -2 ms per step at 200-260 k cells)
+  int64_t fuse_rows = 30000;         // PFV_AMG_FUSE_ROWS
+  bool fuse_cycle = true;            // PFV_AMG_FUSE_CYCLE
+  // measured (profiles/r02_ab_runs.txt): -1.5 ms per step on the 2 M-cell scalar system, +5 ms on the 1.5 M-dof
+  // block system of configs[3] -> lanes for scalar systems only
+  bool restrict_lanes = true;        // PFV_AMG_RESTRICT_LANES
+  bool reuse = true, reuse_dist = true, reuse_rebuilt = true;  // PFV_AMG_REUSE, _REUSE_DIST, _REUSE_REBUILT (amg_decide_reuse)
+  // (measured on one rank over RCCL, new coefficients every step: 2 M rows 76.1 -> 74.5 ms per step with the maps
+  // kept, 257 k rows 18.2 -> 18.7 ms -- there the kept aggregates cost 4 iterations and save 0.4 ms of setup: small
+  // shares re-match)
+  int reuse_dist_min_rows = 500000;  // PFV_AMG_REUSE_DIST_MIN_ROWS
+  bool members_reuse = true, sizes_reuse = true;  // PFV_AMG_MEMBERS_REUSE, PFV_AMG_SIZES_REUSE
+  // PFV_AMG_FILTER_SMOOTH, _ROWMAX_REUSE, _FILTER_LAYOUT_REUSE, _SKIP_MOVED_DIGEST (amg_setup_level0)
+  bool filter_smooth = true, rowmax_reuse = true, filter_layout_reuse = true, skip_moved_digest = true;
+  // how the work is launched: PFV_AMG_GALERKIN_BATCHED, _FILTER_UNROLL, _DENSE_LDS
+  bool galerkin_batched = true, filter_unroll = true, dense_lds = true;
+  int64_t gather_rows = kAmgGatherRowsDefault;  // PFV_AMG_GATHER_ROWS, >= 1
+};
+
+static AmgSwitches amg_read_switches(int bs) {
+  auto given = [](const char* name, int& v) {  // false: unset, v untouched
+    const char* e = std::getenv(name);
+    if (e) v = std::atoi(e);
+    return e != nullptr;
+  };
+  auto on = [](const char* name, int dflt) { return env_int(name, dflt) != 0; };
+  AmgSwitches w;
+  w.bs = bs;
+  w.safe_rows = on("PFV_AMG_SAFE_ROWS", bs == 1 ? 1 : 0);
+  int omega_pct = w.safe_rows ? 95 : 80;
+  w.omega_auto = !given("PFV_AMG_OMEGA_PCT", omega_pct) && on("PFV_AMG_OMEGA_AUTO", 0);
+  w.omega = 0.01 * omega_pct;
+  w.alpha = 0.01 * env_int("PFV_AMG_ALPHA_PCT", 150);
+  w.omega_power_steps = std::max(2, std::min(30, env_int("PFV_AMG_OMEGA_POWER_STEPS", 10)));
+  w.omega_sigma = 0.01 * env_int("PFV_AMG_OMEGA_RHO_PCT", 180);
+  w.passes = std::max(1, std::min(6, env_int("PFV_AMG_PASSES", kAmgPasses)));
+  w.passes_coarse_set = given("PFV_AMG_PASSES_COARSE", w.passes_coarse_raw);
+  w.rounds_raw = env_int("PFV_AMG_ROUNDS", kAmgRounds);
+  w.rounds = std::max(1, std::min(12, w.rounds_raw));
+  w.strength_neg = env_int("PFV_AMG_STRENGTH_NEG", 0);
+  w.fp32 = on("PFV_AMG_FP32", 1);
+  w.filter_theta = 0.001 * env_int(bs == 1 ? "PFV_AMG_FILTER_PERMIL" : "PFV_AMG_FILTER_PERMIL_BLOCK",
+                                   bs == 1 ? kAmgFilterPermil : kAmgFilterPermilBlock);
+  w.coarse_target = std::max(1, std::min(kAmgDenseMax, env_int("PFV_AMG_COARSE_TARGET", kAmgCoarseTargetDefault)));
+  w.gamma_set = given("PFV_AMG_GAMMA", w.gamma_raw);
+  w.gamma_levels = env_int("PFV_AMG_GAMMA_LEVELS", 1);
+  w.fuse_rows = env_int("PFV_AMG_FUSE_ROWS", 30000);
+  w.fuse_cycle = on("PFV_AMG_FUSE_CYCLE", 1);
+  w.restrict_lanes = on("PFV_AMG_RESTRICT_LANES", bs == 1 ? 1 : 0);
+  w.reuse = on("PFV_AMG_REUSE", 1);
+  w.reuse_dist = on("PFV_AMG_REUSE_DIST", 1);
+  w.reuse_rebuilt = on("PFV_AMG_REUSE_REBUILT", 1);
+  w.reuse_dist_min_rows = env_int("PFV_AMG_REUSE_DIST_MIN_ROWS", 500000);
+  w.members_reuse = on("PFV_AMG_MEMBERS_REUSE", 1);
+  w.sizes_reuse = on("PFV_AMG_SIZES_REUSE", 1);
+  w.filter_smooth = on("PFV_AMG_FILTER_SMOOTH", 1);
+  w.rowmax_reuse = on("PFV_AMG_ROWMAX_REUSE", 1);
+  w.filter_layout_reuse = on("PFV_AMG_FILTER_LAYOUT_REUSE", 1);
+  w.skip_moved_digest = on("PFV_AMG_SKIP_MOVED_DIGEST", 1);
+  w.galerkin_batched = on("PFV_AMG_GALERKIN_BATCHED", 1);
+  w.filter_unroll = on("PFV_AMG_FILTER_UNROLL", 1);
+  w.dense_lds = on("PFV_AMG_DENSE_LDS", 1);
+  w.gather_rows = std::max<int64_t>(1, env_int("PFV_AMG_GATHER_ROWS", (int)kAmgGatherRowsDefault));
+  return w;
+}
+
+// The parameters the aggregate maps depend on, in one word: a setup whose word differs from the one the kept maps were
+// built with re-matches.  (The arithmetic is part of what the ranks of a coupled hierarchy exchange: keep it.)
+static int64_t amg_maps_cfg(const AmgSwitches& w) {
+  return ((((int64_t)w.passes * 16 + w.rounds_raw) * 16 + w.passes_coarse_raw + 1) * 4 + w.strength_neg) * 65536 +
+         w.coarse_target * 8 + w.bs + (int64_t)(1000.0 * w.filter_theta + 0.5) * (int64_t(1) << 40);
+}
+// (coupled hierarchy: the matching parameters again, compared beside the word above)
+static int amg_maps_tag(const AmgSwitches& w) { return w.rounds_raw * 64 + w.passes_coarse_raw + 1; }
 
 struct AmgLevel {
   int64_t n = 0;                 // rows of this level's matrix
@@ -123,6 +240,8 @@ struct Amg {
   size_t nlev = 0;     // levels in use (lev may hold more, kept for their buffers)
   AmgWork wk;
   int bs = 1;
+  AmgSwitches sw;  // the switches of the last setup, with this hierarchy's own overrides (no_filter, coarse_target) applied
+  // ... and what the cycle and pfv_amg_level read of them
   int passes = kAmgPasses;
   double omega = 0.8, alpha = 1.5;  // omega: fixed damping when PFV_AMG_OMEGA_PCT is set, else per level (AmgLevel::omega)
   bool omega_auto = true;
@@ -310,19 +429,18 @@ static void amg_pick_pass(pfv_ctx_impl& c, const AmgGraph g, int64_t nb, const i
 }
 
 // one pairwise pass on the cell graph of (P, val): agg[i] in [0, nagg), returns nagg
-static int64_t amg_pairwise(pfv_ctx_impl& c, AmgWork& wk, const CsrPattern& P, const double* val, int bs,
-                            Buf<int32_t>& agg_out) {
+static int64_t amg_pairwise(pfv_ctx_impl& c, const AmgSwitches& sw, AmgWork& wk, const CsrPattern& P, const double* val,
+                            int bs, Buf<int32_t>& agg_out) {
   stream_t s = c.stream;
   const int64_t nb = P.nrows / bs;
-  AmgGraph g{P.indptr, P.indices, val, bs, env_int("PFV_AMG_STRENGTH_NEG", 0)};
+  AmgGraph g{P.indptr, P.indices, val, bs, sw.strength_neg};
   int32_t* match = wk.match.ensure(nb);
   int32_t* pick = wk.pick.ensure(nb);
   int32_t* join = wk.join.ensure(nb);
   int32_t* lead = wk.lead.ensure(nb + 1);
   int64_t* pos = wk.pos.ensure(nb + 1);
   parallel_for(s, nb, PFV_LAMBDA(int64_t i) { match[i] = -1; });
-  const int rounds = std::max(1, std::min(12, env_int("PFV_AMG_ROUNDS", kAmgRounds)));
-  for (int round = 0; round < rounds; ++round) {
+  for (int round = 0; round < sw.rounds; ++round) {
     amg_pick_pass(c, g, nb, match, 0, pick);
     parallel_for(s, nb, PFV_LAMBDA(int64_t i) {
       const int p = pick[i];
@@ -375,8 +493,8 @@ static void amg_members(pfv_ctx_impl& c, AmgWork& wk, const int32_t* agg, int64_
 struct Amg;
 static bool amg_gal_cached(Amg* amg, int64_t ncr, int64_t annz, int* maxcap, int64_t* nnz);
 static void amg_gal_record(Amg* amg, int64_t ncr, int64_t annz, int maxcap, int64_t nnz);
-static void amg_galerkin(pfv_ctx_impl& c, AmgWork& wk, const CsrPattern& A, const double* val, int bs,
-                         const int32_t* agg, const int32_t* mptr, const int32_t* mem, int64_t nagg, CsrPattern& Ac,
+static void amg_galerkin(pfv_ctx_impl& c, const AmgSwitches& sw, AmgWork& wk, const CsrPattern& A, const double* val,
+                         int bs, const int32_t* agg, const int32_t* mptr, const int32_t* mem, int64_t nagg, CsrPattern& Ac,
                          Buf<double>& valc, Buf<double>& dinvc, Amg* sizes = nullptr) {
   stream_t s = c.stream;
   const int64_t ncr = nagg * bs;  // coarse rows
@@ -418,7 +536,7 @@ static void amg_galerkin(pfv_ctx_impl& c, AmgWork& wk, const CsrPattern& A, cons
   // LDS per coarse row: composite sort keys (column << 32 | gather position) | values | head mask
   const size_t lds = 8 * (size_t)capP + 8 * (size_t)capL + 8 * (size_t)nw + 4 * (2 * kGalMaxMembers + 1) + 64;
   // every lane of the group holds at most kGalEpl entries of the coarse row in registers
-  const bool batched = capL <= kGalEpl * G && env_int("PFV_AMG_GALERKIN_BATCHED", 1) != 0;
+  const bool batched = capL <= kGalEpl * G && sw.galerkin_batched;
   wave_for_g(G, s, ncr, lds, PFV_LAMBDA(const WaveCtx& w) {
     const int64_t R = w.item;
     const int64_t I = R / bs;
@@ -719,8 +837,8 @@ static void amg_filter_compact_scalar(stream_t s, int64_t n, const int32_t* ip, 
 }
 #endif
 
-static void amg_filter(pfv_ctx_impl& c, const CsrPattern& A, const double* val, double theta, CsrPattern& F,
-                       Buf<double>& FV, AmgWork& wk, int bs = 1,
+static void amg_filter(pfv_ctx_impl& c, const AmgSwitches& sw, const CsrPattern& A, const double* val, double theta,
+                       CsrPattern& F, Buf<double>& FV, AmgWork& wk, int bs = 1,
                        const std::function<void(double*)>& fill_halo = nullptr, const double* rmax_given = nullptr,
                        double* dinv_out = nullptr, bool same_layout_expected = false, bool* layout_unchanged = nullptr) {
   // Block systems (bs unknowns per cell, full bs x bs blocks): a block is kept or dropped as a whole by its strength
@@ -774,7 +892,7 @@ static void amg_filter(pfv_ctx_impl& c, const CsrPattern& A, const double* val, 
   int32_t* bad = c.status.ensure(16) + 12;
   if (spec) be_memset(bad, 0, sizeof(int32_t), s);
 #ifndef PFV_EMULATE
-  const bool fast = bs == 1 && env_int("PFV_AMG_FILTER_UNROLL", 1) != 0;
+  const bool fast = bs == 1 && sw.filter_unroll;
 #else
   const bool fast = false;
 #endif
@@ -928,7 +1046,7 @@ static void amg_filter(pfv_ctx_impl& c, const CsrPattern& A, const double* val, 
   });
   c.stats.amg_filter_layout = spec ? 1 : 0;
   if (spec && read_scalar<int32_t>(s, bad) != 0) {
-    amg_filter(c, A, val, theta, F, FV, wk, bs, fill_halo, rmax_given, dinv_out, false, nullptr);
+    amg_filter(c, sw, A, val, theta, F, FV, wk, bs, fill_halo, rmax_given, dinv_out, false, nullptr);
     c.stats.amg_filter_layout = 2;
     if (layout_unchanged) *layout_unchanged = false;
   }
@@ -978,7 +1096,8 @@ static void amg_safeguard_rows(pfv_ctx_impl& c, const CsrPattern& P, const doubl
 
 // Explicit inverse of a small matrix (the coarsest level, at most kAmgDenseMax rows) into `dense` (row-major n x n);
 // false when a pivot vanished (the caller then falls back to smoothing sweeps)
-static bool amg_dense_invert(pfv_ctx_impl& c, AmgWork& wk, const CsrPattern& P, const double* v, Buf<double>& dense) {
+static bool amg_dense_invert(pfv_ctx_impl& c, const AmgSwitches& sw, AmgWork& wk, const CsrPattern& P, const double* v,
+                             Buf<double>& dense) {
   stream_t s = c.stream;
   const int n = (int)P.nrows, ld = n | 1;
   double* D = wk.dense_work.ensure((size_t)n * ld + 3 * (size_t)n);
@@ -1028,7 +1147,7 @@ static bool amg_dense_invert(pfv_ctx_impl& c, AmgWork& wk, const CsrPattern& P, 
     PFV_LANES(q, n * ld) D[q] = A[q];
     w.sync();
   };
-  if (lds_need <= 150 * 1024 && env_int("PFV_AMG_DENSE_LDS", 1) != 0) {
+  if (lds_need <= 150 * 1024 && sw.dense_lds) {
     if (n > 128) block_for<1024>(s, 1, lds_need, invert_lds);
     else block_for<256>(s, 1, lds_need, invert_lds);
   } else if (n > 128) block_for<1024>(s, 1, 0, invert);
@@ -1062,365 +1181,242 @@ static void amg_dense_apply(pfv_ctx_impl& c, const double* inv, int64_t n, const
   });
 }
 
-static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const double* val, int bs,
-                      const double* diag, const WinCsr* win0) {
+// ---- the setup, phase by phase (amg_setup at the end reads top to bottom)
+
+static AmgLevel& amg_level(Amg& amg, size_t l) {  // level objects persist for their buffers
+  while (amg.lev.size() <= l) amg.lev.push_back(std::make_unique<AmgLevel>());
+  return *amg.lev[l];
+}
+
+// Values-only re-setup: when the matrix has the pattern the last hierarchy was built for (same
+// symbolic phase, same sizes, same checksum of the index arrays, same parameters) the aggregates
+// are kept and only the Galerkin products are redone -- the matching passes, a third of the setup,
+// are skipped.  Aggregates follow the strength of connection of the values they were built from:
+// right for the successive matrices of a nonlinear iteration; PFV_AMG_REUSE=0 always re-matches.
+// Returns the decision; csum: checksum of A's index arrays (0: not taken).
+// Coupled hierarchy: kept when the pattern of EVERY rank's rows is proved equal to the one its maps were built for.
+// This rank's answer goes through the gather of amg_dist_vote -- all ranks take the same branch, the exchanges of the
+// setup stay matched (what made the sharded path on one rank 12 instead of 6 ms of setup).  `maps_cfg == cfg` is part
+// of what every rank votes on: a rank-local difference can then only turn the common decision to "re-match", never
+// send ranks down different branches of the setup's collectives.
+static bool amg_decide_reuse(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, unsigned long long& csum) {
+  const AmgSwitches& w = amg.sw;
+  AmgDist* D = amg.dist.get();
+  csum = 0;
+  bool mine = false;
+  if (w.reuse && (!D || w.reuse_dist)) {
+    csum = amg_pattern_checksum(c, amg.wk, A);
+    mine = amg.maps_ok && amg.maps_n == A.nrows && amg.maps_nnz == A.nnz && amg.maps_cfg == amg_maps_cfg(w) &&
+           amg.maps_sum == csum &&
+           // a re-built symbolic phase only invalidates the maps if its pattern differs: equal sizes, parameters and
+           // checksum of the index arrays prove the pattern equal (PFV_AMG_REUSE_REBUILT=0: the epoch must match too)
+           (amg.maps_epoch == c.symbolic_epoch || w.reuse_rebuilt) &&
+           (!D || (A.nrows >= w.reuse_dist_min_rows && amg.maps_tag == amg_maps_tag(w)));
+  }
+  return D ? amg_dist_vote(c, *D, A.nrows, mine) : mine;
+}
+
+// full bs x bs blocks are assumed (true for div_nd @ stress); verify the row lengths at least
+static void amg_check_full_blocks(pfv_ctx_impl& c, const CsrPattern& A, int bs) {
   stream_t s = c.stream;
-  Timer tm;
-  tm.start(s);
-  AmgWork& wk = amg.wk;
-  AmgDist* D = amg.dist.get();  // coupled hierarchy of a sharded solve (amg_dist.inc): A = owned rows x (owned + halo)
-  amg.bs = bs;
-  amg.valid = amg.dense_ok = false;
-  amg.sysP = &A;
-  amg.sysV = val;
-  // damping of the Jacobi smoothers: PFV_AMG_OMEGA_PCT fixes it for all levels (80 was the value fitted to the benchmark
-  // matrix: 70 -> 27, 80 -> 23, 90 -> 3455 iterations -- at 0.9 omega rho(D^-1 A) crosses 2 and the smoother amplifies);
-  // unset, every level gets omega = PFV_AMG_OMEGA_RHO_PCT / 100 / rho_l from a power-iteration estimate of its own
-  // rho(D^-1 A) (amg_estimate_omegas)
-  amg.omega_auto = std::getenv("PFV_AMG_OMEGA_PCT") == nullptr && env_int("PFV_AMG_OMEGA_AUTO", 0) != 0;
-  // (scalar systems run the row-wise safeguard, amg_safeguard_rows: any omega <= 1 is stable there and the iteration
-  // count falls monotonically towards 1 -- 0.7: 28, 0.8: 26, 0.9: 24, 1.0: 22 at 197 k cells; block systems keep 0.8)
-  const bool safe_rows = env_int("PFV_AMG_SAFE_ROWS", bs == 1 ? 1 : 0) != 0;  // (block systems: switch only)
-  amg.omega = 0.01 * env_int("PFV_AMG_OMEGA_PCT", safe_rows ? 95 : 80);
-  amg.alpha = 0.01 * env_int("PFV_AMG_ALPHA_PCT", 150);
-  amg.passes = std::max(1, std::min(6, env_int("PFV_AMG_PASSES", kAmgPasses)));
-  amg.fp32 = env_int("PFV_AMG_FP32", 1) != 0;
-  // W at the top (second visit of the first coarse level) pays on large systems, where the finest-level products
-  // dominate and every saved Krylov iteration is worth ~1.6 ms (2 M cells: 89.6 vs 92.4 ms per step); below
-  // kAmgWTopRows the cycle is a chain of ~5 us launches and the second visit just doubles it (197 k cells: 13.1 vs
-  // 15.1 ms, 257 k: 18.2 vs 21.8 ms with the V-cycle although it needs 3-4 iterations more)
-  // (coupled hierarchy: the shape of the cycle must be the same on every rank -- decided from the gathered size)
-  int64_t rows_for_shape = A.nrows;
-  // (coupled hierarchy: the sizes of all ranks -- and, in the second word, whether EVERY rank may keep its aggregate
-  // maps, see `reuse` below -- in one gather)
-  const int reuse_tag = env_int("PFV_AMG_ROUNDS", kAmgRounds) * 64 + env_int("PFV_AMG_PASSES_COARSE", -1) + 1;
-  // (block systems: blocks weaker than 0.05 of the strongest of either end.  configs[3], 1.5 M dofs: 0.03 -> 263 ms per
-  // step, 0.1 -> 243, against ~280 unfiltered; 0.2 costs 67 instead of 43 iterations and 0.3 diverges -- the block
-  // measure is cruder than the scalar one, the default keeps a factor 4 from the first degradation)
-  amg.filter_theta = 0.001 * env_int(bs == 1 ? "PFV_AMG_FILTER_PERMIL" : "PFV_AMG_FILTER_PERMIL_BLOCK",
-                                     bs == 1 ? kAmgFilterPermil : kAmgFilterPermilBlock);
-  if (amg.no_filter) amg.filter_theta = 0.0;  // (a gathered coarse level: already the product of a filtered one)
-  const int kAmgCoarseTarget = amg.coarse_target > 0
-                                   ? std::min(kAmgDenseMax, amg.coarse_target)
-                                   : std::max(1, std::min(kAmgDenseMax, env_int("PFV_AMG_COARSE_TARGET", kAmgCoarseTargetDefault)));
-  // parameters the aggregate maps depend on, in one word.  Formed BEFORE the all-ranks decision below so that
-  // `maps_cfg == cfg` is part of what every rank votes on: a rank-local difference can then only turn the common
-  // decision to "re-match", never send ranks down different branches of the setup's collectives.
-  const int64_t cfg = ((((int64_t)amg.passes * 16 + env_int("PFV_AMG_ROUNDS", kAmgRounds)) * 16 +
-                        env_int("PFV_AMG_PASSES_COARSE", -1) + 1) * 4 + env_int("PFV_AMG_STRENGTH_NEG", 0)) * 65536 +
-                      kAmgCoarseTarget * 8 + bs + (int64_t)(1000.0 * amg.filter_theta + 0.5) * (int64_t(1) << 40);
-  unsigned long long csum_dist = 0;
-  bool reuse_all_ranks = false;
-  if (D) {
-    bool mine = false;
-    if (env_int("PFV_AMG_REUSE", 1) != 0 && env_int("PFV_AMG_REUSE_DIST", 1) != 0) {
-      csum_dist = amg_pattern_checksum(c, wk, A);
-      // (measured on one rank over RCCL, new coefficients every step: 2 M rows 76.1 -> 74.5 ms per step with the maps
-      // kept, 257 k rows 18.2 -> 18.7 ms -- there the kept aggregates cost 4 iterations and save 0.4 ms of setup: small
-      // shares re-match)
-      mine = A.nrows >= env_int("PFV_AMG_REUSE_DIST_MIN_ROWS", 500000) &&
-             amg.maps_ok && amg.maps_n == A.nrows && amg.maps_nnz == A.nnz && amg.maps_sum == csum_dist &&
-             amg.maps_tag == reuse_tag && amg.maps_cfg == cfg &&
-             (amg.maps_epoch == c.symbolic_epoch || env_int("PFV_AMG_REUSE_REBUILT", 1) != 0);
-    }
-    const std::vector<int64_t> cnt0 = amg_gather_counts(c, *D, A.nrows, mine ? 1 : 0);
-    D->global_rows0 = 0;
-    reuse_all_ranks = true;
-    for (int r = 0; r < D->world; ++r) {
-      D->global_rows0 += cnt0[2 * r];
-      reuse_all_ranks = reuse_all_ranks && cnt0[2 * r + 1] == 1;
-    }
-    rows_for_shape = D->global_rows0 / D->world;
-    D->global_rows_level = D->global_rows0;
-    D->kgather = 0;
-    D->exchanges = D->allgathers = 0;
-  }
-  amg.gamma = std::max(1, std::min(2, env_int("PFV_AMG_GAMMA", rows_for_shape >= kAmgWTopRows ? 2 : 1)));
-  amg.gamma_levels = env_int("PFV_AMG_GAMMA_LEVELS", 1);
-  // fused launches on the small levels (neutral at 2 M cells, -2 ms per step at 200-260 k cells)
-  amg.fuse_rows = env_int("PFV_AMG_FUSE_ROWS", 30000);
-  amg.fuse_cycle = env_int("PFV_AMG_FUSE_CYCLE", 1) != 0;
+  const int32_t* ip = A.indptr;
+  int32_t* st = c.status.ensure(16);
+  be_memset(st + 10, 0, sizeof(int32_t), s);
+  parallel_for(s, A.nrows / bs, PFV_LAMBDA(int64_t i) {
+    const int len = ip[i * bs + 1] - ip[i * bs];
+    bool bad = (len % bs) != 0;
+    for (int a = 1; a < bs; ++a) bad = bad || (ip[i * bs + a + 1] - ip[i * bs + a]) != len;
+    if (bad) atomic_max_i32(st + 10, 1);
+  });
+  if (read_scalar<int32_t>(s, st + 10))
+    throw Error(PFV_ERR_UNSUPPORTED, "AMG: the matrix is not made of full blocks of the given block size");
+}
+
+// Level 0: the system itself or, with the filter on (PFV_AMG_FILTER_SMOOTH), its strength-filtered copy with the kept
+// layout and SpMV window; the inverse diagonal.  Returns the checksum of the finest pattern the hierarchy is coarsened
+// from (0: unknown).
+static unsigned long long amg_setup_level0(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const double* val,
+                                           const double* diag, const WinCsr* win0, unsigned long long csum) {
+  stream_t s = c.stream;
+  const AmgSwitches& w = amg.sw;
+  AmgDist* D = amg.dist.get();
+  const int bs = amg.bs;
+  AmgLevel& L0 = amg_level(amg, 0);
+  L0.n = A.nrows;
+  L0.m = std::max(A.ncols, A.nrows);
+  L0.P = &A;
+  L0.val = val;
+  L0.win = win0;
   amg.filt_nnz = 0;
-  // measured (profiles/r02_ab_runs.txt): -1.5 ms per step on the 2 M-cell scalar system, +5 ms on the 1.5 M-dof
-  // block system of configs[3] -> lanes for scalar systems only
-  amg.restrict_lanes = env_int("PFV_AMG_RESTRICT_LANES", bs == 1 ? 1 : 0) != 0;
-  if (A.nrows % bs) throw Error(PFV_ERR_ARGUMENT, "AMG: system size is not a multiple of the block size");
-  // Values-only re-setup: when the matrix has the pattern the last hierarchy was built for (same
-  // symbolic phase, same sizes, same checksum of the index arrays, same parameters) the aggregates
-  // are kept and only the Galerkin products are redone -- the matching passes, a third of the setup,
-  // are skipped.  Aggregates follow the strength of connection of the values they were built from:
-  // right for the successive matrices of a nonlinear iteration; PFV_AMG_REUSE=0 always re-matches.
-  bool reuse = false;
-  unsigned long long csum = 0;
-  if (D) {
-    // coupled hierarchy: kept when the pattern of EVERY rank's rows is proved equal to the one its maps were built for
-    // (the decision went through the gather above: all ranks take the same branch, the exchanges of the setup stay
-    // matched) -- what made the sharded path on one rank 12 instead of 6 ms of setup
-    csum = csum_dist;
-    reuse = reuse_all_ranks;  // (maps_cfg == cfg went through the vote)
-  } else if (env_int("PFV_AMG_REUSE", 1) != 0) {
-    csum = amg_pattern_checksum(c, wk, A);
-    reuse = amg.maps_ok && amg.maps_n == A.nrows && amg.maps_nnz == A.nnz && amg.maps_cfg == cfg &&
-            amg.maps_sum == csum &&
-            // a re-built symbolic phase only invalidates the maps if its pattern differs: equal sizes, parameters and
-            // checksum of the index arrays prove the pattern equal (PFV_AMG_REUSE_REBUILT=0: the epoch must match too)
-            (amg.maps_epoch == c.symbolic_epoch || env_int("PFV_AMG_REUSE_REBUILT", 1) != 0);
+  // PFV_AMG_FILTER_SMOOTH (with the filter on): the WHOLE cycle, its finest level included, works on the filtered
+  // operator -- the smoothing and residual products of level 0 then stream a third of the entries (they are the
+  // largest kernel of the step), the Krylov loop keeps the full matrix.  M ~ A_s^-1 with A_s spectrally close to A.
+  amg.filter_level0 = amg.filter_theta > 0.0 && w.filter_smooth;
+  if (!amg.filter_level0) {  // (coarse levels get dinv from the Galerkin kernel, the filtered finest level from the filter)
+    double* dv = L0.dinv.ensure(L0.n);
+    if (diag) {
+      parallel_for(s, L0.n, PFV_LAMBDA(int64_t i) { dv[i] = diag[i] != 0.0 ? 1.0 / diag[i] : 0.0; });
+    } else {
+      amg_diag_inverse(c, A, val, dv);
+    }
+    return csum;
   }
-  amg.maps_ok = false;
-  amg.reused = reuse;
-  unsigned long long level0_sum = 0;
-  if (bs > 1) {
-    // full bs x bs blocks are assumed (true for div_nd @ stress); verify the row lengths at least
-    const int32_t* ip = A.indptr;
-    int32_t* st = c.status.ensure(16);
-    be_memset(st + 10, 0, sizeof(int32_t), s);
-    parallel_for(s, A.nrows / bs, PFV_LAMBDA(int64_t i) {
-      const int len = ip[i * bs + 1] - ip[i * bs];
-      bool bad = (len % bs) != 0;
-      for (int a = 1; a < bs; ++a) bad = bad || (ip[i * bs + a + 1] - ip[i * bs + a]) != len;
-      if (bad) atomic_max_i32(st + 10, 1);
-    });
-    if (read_scalar<int32_t>(s, st + 10))
-      throw Error(PFV_ERR_UNSUPPORTED, "AMG: the matrix is not made of full blocks of the given block size");
+  const double* rmax_given = (c.sys_rowmax_for == val && A.nrows == c.nc && w.rowmax_reuse) ? c.sys_rowmax.p : nullptr;
+  // (layout of the filtered rows kept from the previous setup when A's pattern is the one it was computed for)
+  // -- offered only after a filtering that REPRODUCED the layout before it (coefficients that do not change
+  // between setups: a linear problem stepped in time, repeated solves); values that move every time never pay
+  // for a failed try more than once
+  const bool same_pattern = !D && csum != 0 && amg.filt_layout_for == csum;
+  const bool same_layout = same_pattern && amg.filt_layout_stable && w.filter_layout_reuse;
+  if (!same_pattern) amg.filtP.nrows = 0;  // (nothing to compare the new layout with)
+  bool unchanged = false;
+  // (the diagonal of the filtered matrix carries the lumped entries: dinv comes from the filter, not from `diag`)
+  amg_filter(c, w, A, val, amg.filter_theta, amg.filtP, amg.filtV, amg.wk, bs, amg_fill_halo0(c, D, bs), rmax_given,
+             L0.dinv.ensure(L0.n), same_layout, &unchanged);
+  amg.filt_layout_stable = unchanged;
+  amg.filt_layout_for = D ? 0ull : csum;
+  amg.filt_nnz = amg.filtP.nnz;
+  L0.P = &amg.filtP;
+  L0.val = amg.filtV.p;
+  L0.win = nullptr;
+  if (amg.filtP.nnz < 200000) return 0ull;
+  // the windows are a function of the filtered PATTERN: kept when it is the one they were built for (which
+  // entries survive the filter depends on the values, so this is checked on the filtered index arrays themselves)
+  // (a local structure: every rank decides for itself, also under the coupled hierarchy)
+  // (not asked when this filtering has just been seen to differ from the previous one on the same pattern of A --
+  // values that move: the digest, three passes over the filtered indices and a read-back, could only say "no")
+  const bool moved = same_pattern && !unchanged && w.skip_moved_digest;
+  const unsigned long long fsum = (env_int("PFV_WIN_REUSE", 1) != 0 && !moved)
+                                      ? read_scalar<unsigned long long>(s, launch_pattern_checksum(c, amg.wk.csum, amg.filtP))
+                                      : 0ull;
+  // (PFV_SPMV_WINDOW=0 switches a kept window off too, not only the building of a new one)
+  const bool keep = fsum != 0 && amg.filt_win.ok && amg.filt_win_sum == fsum && amg.filt_win.nrows == amg.filtP.nrows &&
+                    amg.filt_win.nnz == amg.filtP.nnz && env_int("PFV_SPMV_WINDOW", 1) != 0;
+  if (!keep) {
+    // (the filtered rows are subsets of A's rows: their windows come out of A's windows without hashing or
+    // sorting -- spmv_win.inc: win_derive; from scratch where A has none)
+    if (!(win0 && win_derive(c, amg.filtP, *win0, amg.filt_win))) win_build(c, amg.filtP, amg.filt_win);
+    amg.filt_win_sum = amg.filt_win.ok ? fsum : 0ull;
   }
-  auto level = [&](size_t l) -> AmgLevel& {  // level objects persist for their buffers
-    while (amg.lev.size() <= l) amg.lev.push_back(std::make_unique<AmgLevel>());
-    return *amg.lev[l];
-  };
-  double nnz_sum = 0.0;
-  size_t l = 0;
-  bool dinv0_done = false;
-  const bool keep_members = env_int("PFV_AMG_MEMBERS_REUSE", 1) != 0;
-  {
-    AmgLevel& L0 = level(0);
-    L0.n = A.nrows;
-    L0.m = std::max(A.ncols, A.nrows);
-    L0.P = &A;
-    L0.val = val;
-    L0.win = win0;
-    // PFV_AMG_FILTER_SMOOTH (with the filter on): the WHOLE cycle, its finest level included, works on the filtered
-    // operator -- the smoothing and residual products of level 0 then stream a third of the entries (they are the
-    // largest kernel of the step), the Krylov loop keeps the full matrix.  M ~ A_s^-1 with A_s spectrally close to A.
-    amg.filter_level0 = false;
-    if (amg.filter_theta > 0.0 && env_int("PFV_AMG_FILTER_SMOOTH", 1) != 0) {
-      std::function<void(double*)> fill_halo;
-      if (D) fill_halo = [&c, D, bs](double* v) { amg_halo_exchange(c, *D, *D->plan[0], v, bs); };
-      const double* rmax_given = (c.sys_rowmax_for == val && A.nrows == c.nc && env_int("PFV_AMG_ROWMAX_REUSE", 1) != 0) ? c.sys_rowmax.p : nullptr;
-      // (layout of the filtered rows kept from the previous setup when A's pattern is the one it was computed for)
-      // -- offered only after a filtering that REPRODUCED the layout before it (coefficients that do not change
-      // between setups: a linear problem stepped in time, repeated solves); values that move every time never pay
-      // for a failed try more than once
-      const bool same_pattern = !D && csum != 0 && amg.filt_layout_for == csum;
-      const bool same_layout = same_pattern && amg.filt_layout_stable && env_int("PFV_AMG_FILTER_LAYOUT_REUSE", 1) != 0;
-      if (!same_pattern) amg.filtP.nrows = 0;  // (nothing to compare the new layout with)
-      bool unchanged = false;
-      amg_filter(c, A, val, amg.filter_theta, amg.filtP, amg.filtV, wk, bs, fill_halo, rmax_given, L0.dinv.ensure(L0.n), same_layout,
-                 &unchanged);
-      amg.filt_layout_stable = unchanged;
-      amg.filt_layout_for = D ? 0ull : csum;
-      dinv0_done = true;
-      amg.filt_nnz = amg.filtP.nnz;
-      amg.filter_level0 = true;
-      L0.P = &amg.filtP;
-      L0.val = amg.filtV.p;
-      L0.win = nullptr;
-      diag = nullptr;  // (the diagonal of the filtered matrix carries the lumped entries)
-      if (amg.filtP.nnz >= 200000) {
-        // the windows are a function of the filtered PATTERN: kept when it is the one they were built for (which
-        // entries survive the filter depends on the values, so this is checked on the filtered index arrays themselves)
-        // (a local structure: every rank decides for itself, also under the coupled hierarchy)
-        // (not asked when this filtering has just been seen to differ from the previous one on the same pattern of A --
-        // values that move: the digest, three passes over the filtered indices and a read-back, could only say "no")
-        const bool moved = same_pattern && !unchanged && env_int("PFV_AMG_SKIP_MOVED_DIGEST", 1) != 0;
-        const unsigned long long fsum = (env_int("PFV_WIN_REUSE", 1) != 0 && !moved)
-                                            ? read_scalar<unsigned long long>(s, launch_pattern_checksum(c, wk.csum, amg.filtP))
-                                            : 0ull;
-        level0_sum = fsum;
-        // (PFV_SPMV_WINDOW=0 switches a kept window off too, not only the building of a new one)
-        const bool keep = fsum != 0 && amg.filt_win.ok && amg.filt_win_sum == fsum && amg.filt_win.nrows == amg.filtP.nrows &&
-                          amg.filt_win.nnz == amg.filtP.nnz && env_int("PFV_SPMV_WINDOW", 1) != 0;
-        if (!keep) {
-          // (the filtered rows are subsets of A's rows: their windows come out of A's windows without hashing or
-          // sorting -- spmv_win.inc: win_derive; from scratch where A has none)
-          if (!(win0 && win_derive(c, amg.filtP, *win0, amg.filt_win))) win_build(c, amg.filtP, amg.filt_win);
-          amg.filt_win_sum = amg.filt_win.ok ? fsum : 0ull;
-        }
-        L0.win = &amg.filt_win;
-      }
-    }
+  L0.win = &amg.filt_win;
+  return fsum;
+}
+
+// cycle vectors and the single-precision copy of the values of level l
+static void amg_level_buffers(pfv_ctx_impl& c, const Amg& amg, AmgLevel& L, size_t l) {
+  if (l > 0) {
+    L.x.ensure(L.m);
+    L.b.ensure(L.n);
   }
-  // sizes of the Galerkin products known from the previous setup?  (same finest pattern the hierarchy is coarsened from
-  // -- the filtered one where the filter is on --, same aggregate maps)
-  if (!amg.filter_level0) level0_sum = csum;
-  amg.gal_use = reuse && !D && level0_sum != 0 && amg.gal_for_sum == level0_sum && env_int("PFV_AMG_SIZES_REUSE", 1) != 0;
-  amg.gal_k = 0;
-  if (!amg.gal_use) amg.gal_sizes.clear();
-  while (true) {
-    AmgLevel& L = level(l);
-    nnz_sum += (double)L.P->nnz;
-    if (l == 0 && !dinv0_done) {  // coarse levels get it from the Galerkin kernel, the filtered finest level from the filter
-      double* dv = L.dinv.ensure(L.n);
-      if (diag) {
-        parallel_for(s, L.n, PFV_LAMBDA(int64_t i) { dv[i] = diag[i] != 0.0 ? 1.0 / diag[i] : 0.0; });
-      } else {
-        amg_diag_inverse(c, *L.P, L.val, dv);
-      }
-    }
-    if (l > 0) {
-      L.x.ensure(L.m);
-      L.b.ensure(L.n);
-    }
-    L.t.ensure(L.m);
-    L.v32 = nullptr;
-    if (amg.fp32) {
-      float* v32 = L.val32.ensure(L.P->nnz);
-      const double* v64 = L.val;
-      parallel_for(s, L.P->nnz, PFV_LAMBDA(int64_t e) { v32[e] = (float)v64[e]; });
-      L.v32 = v32;
-    }
-    L.nc_cells = 0;
-    const int64_t cells = L.n / bs;
-    if (D ? (l >= 1 && l == D->kgather) : (L.n <= kAmgCoarseTarget || (int)l + 1 >= kAmgMaxLevels)) break;
-    // several pairwise passes, composing the aggregate maps; the intermediate Galerkin matrices
-    // ping-pong between the two slots of the workspace
-    const CsrPattern* curP = L.P;
-    const double* curV = L.val;
-    if (l == 0 && amg.filter_theta > 0.0 && !amg.filter_level0) {
-      std::function<void(double*)> fill_halo;
-      if (D) fill_halo = [&c, D, bs](double* v) { amg_halo_exchange(c, *D, *D->plan[0], v, bs); };
-      amg_filter(c, *L.P, L.val, amg.filter_theta, amg.filtP, amg.filtV, wk, bs, fill_halo);
-      amg.filt_nnz = amg.filtP.nnz;
-      curP = &amg.filtP;
-      curV = amg.filtV.p;
-    }
-    int32_t* aggL = L.agg.ensure(cells);
-    int64_t cur_cells = cells;
-    int slot = -1;
-    // Below the finest level a deep hierarchy coarsens more gently (aggregates of 4 instead of 8): one
-    // level more, but 15 instead of 18 BiCGStab iterations on the 2 M-cell system (step 100.6 -> 96 ms);
-    // hierarchies of small systems (4 levels or fewer) gain nothing and keep the faster coarsening.
-    // (coupled hierarchy: the size that counts is the one of the whole system, and the replicated part below the
-    // gathered level continues the parent's policy -- its own level 0 is a coarse level)
-    const int64_t finest_cells = amg.finest_cells_parent > 0 ? amg.finest_cells_parent
-                                                              : (D ? D->global_rows0 : amg.lev[0]->n) / bs;
-    const int coarse_default = finest_cells >= kAmgGentleCells ? std::min(2, amg.passes) : amg.passes;
-    const int passes_here = (l == 0 && amg.finest_cells_parent <= 0)
-                                ? amg.passes
-                                : std::max(1, std::min(6, env_int("PFV_AMG_PASSES_COARSE", coarse_default)));
-    if (!reuse) L.pmap_count = 0;
-    if (!reuse) L.members_kept = false;
-    for (int pass = 0; pass < (reuse ? L.pmap_count : passes_here); ++pass) {
-      int64_t nagg;
-      const int32_t* a1p;
-      if (reuse) {
-        nagg = L.pmap_n[pass];
-        a1p = L.pmap[pass].p;
-      } else {
-        nagg = amg_pairwise(c, wk, *curP, curV, bs, wk.a1);
-        if (nagg >= cur_cells) break;  // nothing left to merge
-        be_d2d(L.pmap[pass].ensure(cur_cells), wk.a1.p, sizeof(int32_t) * (size_t)cur_cells, s);
-        L.pmap_n[pass] = nagg;
-        L.pmap_count = pass + 1;
-        a1p = L.pmap[pass].p;
-      }
-      // (the member lists of a kept map are kept with it: a sort of cur_cells pairs per pass otherwise -- with the
-      // composed map and the level's own member lists below 1.3 ms of kernels and ~200 launches of a setup on kept maps)
-      const bool members_reuse = reuse && L.members_kept && keep_members;
-      if (!members_reuse) amg_members(c, wk, a1p, cur_cells, nagg, L.pmp[pass], L.pme[pass]);
-      const int nslot = slot < 0 ? 0 : 1 - slot;
-      const int32_t* amap = a1p;
-      if (D) {
-        // halo columns ride along unchanged through the passes of a level (renamed once, after the last pass)
-        const int64_t nh = D->plan[l]->n_halo;
-        int32_t* ae = D->aext.ensure((size_t)(cur_cells + nh));
-        parallel_for(s, cur_cells + nh, PFV_LAMBDA(int64_t i) { ae[i] = i < cur_cells ? a1p[i] : (int32_t)(nagg + (i - cur_cells)); });
-        amap = ae;
-      }
-      amg_galerkin(c, wk, *curP, curV, bs, amap, L.pmp[pass], L.pme[pass], nagg, wk.P[nslot], wk.V[nslot], wk.D[nslot], D ? nullptr : &amg);
-      if (D) wk.P[nslot].ncols = (nagg + D->plan[l]->n_halo) * bs;
-      if (members_reuse) {
-        // (aggL holds the composition of the kept maps already)
-      } else if (slot < 0) {
-        parallel_for(s, cells, PFV_LAMBDA(int64_t i) { aggL[i] = a1p[i]; });
-      } else {
-        parallel_for(s, cells, PFV_LAMBDA(int64_t i) { aggL[i] = a1p[aggL[i]]; });
-      }
-      slot = nslot;
-      curP = &wk.P[slot];
-      curV = wk.V[slot].p;
-      cur_cells = nagg;
-      if (nagg * bs <= kAmgCoarseTarget) break;
-    }
-    if (D && slot < 0) {
-      // this rank has nothing left to merge, others may: its cells go on as they are (every rank builds every level)
-      int32_t* ident = wk.a1.ensure((size_t)cells);
-      const int64_t nh = D->plan[l]->n_halo;
-      int32_t* ae = D->aext.ensure((size_t)(cells + nh));
-      parallel_for(s, cells, PFV_LAMBDA(int64_t i) { ident[i] = (int32_t)i; aggL[i] = (int32_t)i; });
-      parallel_for(s, cells + nh, PFV_LAMBDA(int64_t i) { ae[i] = (int32_t)i; });
-      amg_members(c, wk, ident, cells, cells, wk.mp, wk.me);
-      amg_galerkin(c, wk, *curP, curV, bs, ae, wk.mp, wk.me, cells, wk.P[0], wk.V[0], wk.D[0]);
-      wk.P[0].ncols = (cells + nh) * bs;
-      slot = 0;
-      cur_cells = cells;
-    }
-    if (!D && (slot < 0 || cur_cells > 0.85 * cells)) break;  // coarsening stalled: this level is the coarsest
-    L.nc_cells = cur_cells;
-    if (!(reuse && L.members_kept && keep_members && slot >= 0 && L.pmap_count > 0)) amg_members(c, wk, aggL, cells, cur_cells, L.mptr, L.mem);
-    L.members_kept = slot >= 0 && L.pmap_count > 0;
-    AmgLevel& Ln = level(l + 1);
-    Ln.n = cur_cells * bs;
-    // the last intermediate matrix becomes the new level (its old buffers go back to the slot)
-    amg_swap_pattern(Ln.P_own, wk.P[slot]);
-    amg_swap_buf(Ln.val_own, wk.V[slot]);
-    amg_swap_buf(Ln.dinv, wk.D[slot]);
-    Ln.P = &Ln.P_own;
-    Ln.val = Ln.val_own.p;
-    Ln.win = nullptr;
-    Ln.m = Ln.n;
-    if (D) {
-      // the owners' aggregates rename the halo columns; the plan of the new level; gather from here on?
-      while (D->plan.size() <= l + 1) D->plan.push_back(nullptr);
-      D->plan[l + 1] = amg_coarse_plan(c, *D, *D->plan[l], aggL, cur_cells);
-      const int64_t nh_new = D->plan[l + 1]->n_halo;
-      const int32_t* ch = D->chalo;
-      int32_t* ixn = Ln.P_own.indices;
-      const int64_t ncn = cur_cells;
-      parallel_for(s, Ln.P_own.nnz, PFV_LAMBDA(int64_t e) {
-        const int col = ixn[e];
-        const int cc = col / bs;
-        if (cc >= ncn) ixn[e] = (int32_t)((ncn + ch[cc - ncn]) * bs + (col - cc * bs));
-      });
-      Ln.P_own.ncols = (cur_cells + nh_new) * bs;
-      Ln.m = Ln.P_own.ncols;
-      const std::vector<int64_t> cn = amg_gather_counts(c, *D, Ln.n, 0);
-      int64_t tot = 0;
-      for (int r = 0; r < D->world; ++r) tot += cn[2 * r];
-      const int64_t tot_here = D->global_rows_level;
-      D->global_rows_level = tot;
-      const int64_t gather_rows = std::max<int64_t>(1, env_int("PFV_AMG_GATHER_ROWS", (int)kAmgGatherRowsDefault));
-      if (tot <= gather_rows || tot > 0.85 * tot_here || (int)l + 3 >= kAmgMaxLevels) D->kgather = l + 1;
-    }
-    if (Ln.n > kAmgCoarseTarget && Ln.P_own.nnz >= 200000) {  // worth it only for the big levels
-      win_build(c, Ln.P_own, Ln.win_own);
-      Ln.win = &Ln.win_own;
-    }
-    ++l;
+  L.t.ensure(L.m);
+  L.v32 = nullptr;
+  if (amg.fp32) {
+    float* v32 = L.val32.ensure(L.P->nnz);
+    const double* v64 = L.val;
+    parallel_for(c.stream, L.P->nnz, PFV_LAMBDA(int64_t e) { v32[e] = (float)v64[e]; });
+    L.v32 = v32;
   }
-  amg.nlev = l + 1;
-  // coarsest level: explicit inverse when small enough
+  L.nc_cells = 0;
+}
+
+// Coarsening of level l: several pairwise passes, composing the aggregate maps (L.agg, member lists, L.nc_cells); the
+// intermediate Galerkin matrices ping-pong between the two slots of the workspace.  Returns the slot that holds the
+// matrix of level l + 1, or -1 when the coarsening stalled (this level is then the coarsest).
+static int amg_coarsen_level(pfv_ctx_impl& c, Amg& amg, size_t l, bool reuse) {
+  stream_t s = c.stream;
+  const AmgSwitches& w = amg.sw;
+  AmgWork& wk = amg.wk;
+  AmgDist* D = amg.dist.get();
+  const int bs = amg.bs;
+  AmgLevel& L = *amg.lev[l];
+  const int64_t cells = L.n / bs;
+  const CsrPattern* curP = L.P;
+  const double* curV = L.val;
+  if (l == 0 && amg.filter_theta > 0.0 && !amg.filter_level0) {  // the filter for the matching only
+    amg_filter(c, w, *L.P, L.val, amg.filter_theta, amg.filtP, amg.filtV, wk, bs, amg_fill_halo0(c, D, bs));
+    amg.filt_nnz = amg.filtP.nnz;
+    curP = &amg.filtP;
+    curV = amg.filtV.p;
+  }
+  int32_t* aggL = L.agg.ensure(cells);
+  int64_t cur_cells = cells;
+  int slot = -1;
+  // Below the finest level a deep hierarchy coarsens more gently (aggregates of 4 instead of 8): one
+  // level more, but 15 instead of 18 BiCGStab iterations on the 2 M-cell system (step 100.6 -> 96 ms);
+  // hierarchies of small systems (4 levels or fewer) gain nothing and keep the faster coarsening.
+  // (coupled hierarchy: the size that counts is the one of the whole system, and the replicated part below the
+  // gathered level continues the parent's policy -- its own level 0 is a coarse level)
+  const int64_t finest_cells = amg.finest_cells_parent > 0 ? amg.finest_cells_parent
+                                                            : (D ? D->global_rows0 : amg.lev[0]->n) / bs;
+  const int coarse_default = finest_cells >= kAmgGentleCells ? std::min(2, amg.passes) : amg.passes;
+  const int passes_here = (l == 0 && amg.finest_cells_parent <= 0)
+                              ? amg.passes
+                              : std::max(1, std::min(6, w.passes_coarse_set ? w.passes_coarse_raw : coarse_default));
+  if (!reuse) L.pmap_count = 0;
+  if (!reuse) L.members_kept = false;
+  // (the member lists of a kept map are kept with it: a sort of cur_cells pairs per pass otherwise -- with the
+  // composed map and the level's own member lists below 1.3 ms of kernels and ~200 launches of a setup on kept maps)
+  const bool members_reuse = reuse && L.members_kept && w.members_reuse;
+  for (int pass = 0; pass < (reuse ? L.pmap_count : passes_here); ++pass) {
+    int64_t nagg;
+    if (reuse) {
+      nagg = L.pmap_n[pass];
+    } else {
+      nagg = amg_pairwise(c, w, wk, *curP, curV, bs, wk.a1);
+      if (nagg >= cur_cells) break;  // nothing left to merge
+      be_d2d(L.pmap[pass].ensure(cur_cells), wk.a1.p, sizeof(int32_t) * (size_t)cur_cells, s);
+      L.pmap_n[pass] = nagg;
+      L.pmap_count = pass + 1;
+    }
+    const int32_t* a1p = L.pmap[pass].p;
+    if (!members_reuse) amg_members(c, wk, a1p, cur_cells, nagg, L.pmp[pass], L.pme[pass]);
+    const int nslot = slot < 0 ? 0 : 1 - slot;
+    const int32_t* amap = D ? amg_dist_extend_map(c, *D, l, a1p, cur_cells, nagg) : a1p;
+    amg_galerkin(c, w, wk, *curP, curV, bs, amap, L.pmp[pass], L.pme[pass], nagg, wk.P[nslot], wk.V[nslot], wk.D[nslot],
+                 D ? nullptr : &amg);
+    if (D) wk.P[nslot].ncols = (nagg + D->plan[l]->n_halo) * bs;
+    if (members_reuse) {
+      // (aggL holds the composition of the kept maps already)
+    } else if (slot < 0) {
+      parallel_for(s, cells, PFV_LAMBDA(int64_t i) { aggL[i] = a1p[i]; });
+    } else {
+      parallel_for(s, cells, PFV_LAMBDA(int64_t i) { aggL[i] = a1p[aggL[i]]; });
+    }
+    slot = nslot;
+    curP = &wk.P[slot];
+    curV = wk.V[slot].p;
+    cur_cells = nagg;
+    if (nagg * bs <= w.coarse_target) break;
+  }
+  if (D && slot < 0) {
+    amg_dist_identity_level(c, amg, *D, l, *curP, curV, aggL, cells);
+    slot = 0;
+  }
+  if (!D && (slot < 0 || cur_cells > 0.85 * cells)) return -1;
+  L.nc_cells = cur_cells;
+  if (!(members_reuse && L.pmap_count > 0)) amg_members(c, wk, aggL, cells, cur_cells, L.mptr, L.mem);
+  L.members_kept = L.pmap_count > 0;
+  return slot;
+}
+
+// The closing work: the coarsest level (explicit inverse when small enough; coupled hierarchy: the gathered level and
+// the replicated hierarchy below it), the damping, the row safeguard, and what the kept maps belong to.
+static void amg_setup_finish(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, double nnz_sum, unsigned long long csum,
+                             unsigned long long level0_sum) {
+  const AmgSwitches& w = amg.sw;
+  AmgDist* D = amg.dist.get();
   AmgLevel& Lc = *amg.lev[amg.nlev - 1];
   if (D) {
     amg_build_global(c, amg, *D, Lc, *D->plan[amg.nlev - 1]);
   } else if (Lc.n <= kAmgDenseMax) {
-    amg.dense_ok = amg_dense_invert(c, wk, *Lc.P, Lc.val, amg.dense);
+    amg.dense_ok = amg_dense_invert(c, w, amg.wk, *Lc.P, Lc.val, amg.dense);
   }
   amg.op_complexity = nnz_sum / (double)A.nnz;
   for (size_t k = 0; k < amg.nlev; ++k) {
     amg.lev[k]->omega = amg.omega;
     amg.lev[k]->rho = 0.0;
   }
-  if (safe_rows) {
+  if (w.safe_rows) {
     for (size_t k = 0; k < amg.nlev; ++k) {
       AmgLevel& Lk = *amg.lev[k];
       if (k + 1 < amg.nlev || !amg.dense_ok) amg_safeguard_rows(c, *Lk.P, Lk.val, Lk.dinv);
@@ -1436,15 +1432,86 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
     std::fprintf(stderr, " reuse %d\n", (int)amg.reused);
   }
   amg.gal_for_sum = D ? 0ull : level0_sum;
-  if (env_int("PFV_AMG_REUSE", 1) != 0 && (!D || csum != 0)) {
+  if (w.reuse && (!D || csum != 0)) {
     amg.maps_ok = true;
     amg.maps_n = A.nrows;
     amg.maps_nnz = A.nnz;
-    amg.maps_cfg = cfg;
+    amg.maps_cfg = amg_maps_cfg(w);
     amg.maps_sum = csum;
     amg.maps_epoch = c.symbolic_epoch;
-    amg.maps_tag = reuse_tag;
+    amg.maps_tag = amg_maps_tag(w);
   }
+}
+
+static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const double* val, int bs,
+                      const double* diag, const WinCsr* win0) {
+  stream_t s = c.stream;
+  Timer tm;
+  tm.start(s);
+  AmgDist* D = amg.dist.get();  // coupled hierarchy of a sharded solve (amg_dist.inc): A = owned rows x (owned + halo)
+  amg.bs = bs;
+  amg.valid = amg.dense_ok = false;
+  amg.sysP = &A;
+  amg.sysV = val;
+  if (A.nrows % bs) throw Error(PFV_ERR_ARGUMENT, "AMG: system size is not a multiple of the block size");
+  AmgSwitches& w = amg.sw = amg_read_switches(bs);
+  if (amg.no_filter) w.filter_theta = 0.0;  // (a gathered coarse level: already the product of a filtered one)
+  if (amg.coarse_target > 0) w.coarse_target = std::min(kAmgDenseMax, amg.coarse_target);
+  amg.omega_auto = w.omega_auto;
+  amg.omega = w.omega;
+  amg.alpha = w.alpha;
+  amg.passes = w.passes;
+  amg.fp32 = w.fp32;
+  amg.filter_theta = w.filter_theta;
+  amg.gamma_levels = w.gamma_levels;
+  amg.fuse_rows = w.fuse_rows;
+  amg.fuse_cycle = w.fuse_cycle;
+  amg.restrict_lanes = w.restrict_lanes;
+  unsigned long long csum = 0;
+  const bool reuse = amg_decide_reuse(c, amg, A, csum);
+  // (coupled hierarchy: the shape of the cycle must be the same on every rank -- decided from the gathered size)
+  const int64_t rows_for_shape = D ? D->global_rows0 / D->world : A.nrows;
+  amg.gamma = std::max(1, std::min(2, w.gamma_set ? w.gamma_raw : (rows_for_shape >= kAmgWTopRows ? 2 : 1)));
+  amg.maps_ok = false;
+  amg.reused = reuse;
+  if (bs > 1) amg_check_full_blocks(c, A, bs);
+  unsigned long long level0_sum = amg_setup_level0(c, amg, A, val, diag, win0, csum);
+  // sizes of the Galerkin products known from the previous setup?  (same finest pattern the hierarchy is coarsened from
+  // -- the filtered one where the filter is on --, same aggregate maps)
+  amg.gal_use = reuse && !D && level0_sum != 0 && amg.gal_for_sum == level0_sum && w.sizes_reuse;
+  amg.gal_k = 0;
+  if (!amg.gal_use) amg.gal_sizes.clear();
+  double nnz_sum = 0.0;
+  size_t l = 0;
+  while (true) {
+    AmgLevel& L = amg_level(amg, l);
+    nnz_sum += (double)L.P->nnz;
+    amg_level_buffers(c, amg, L, l);
+    if (D ? (l >= 1 && l == D->kgather) : (L.n <= w.coarse_target || (int)l + 1 >= kAmgMaxLevels)) break;
+    const int slot = amg_coarsen_level(c, amg, l, reuse);
+    if (slot < 0) break;  // coarsening stalled: this level is the coarsest
+    AmgLevel& Ln = amg_level(amg, l + 1);
+    Ln.n = L.nc_cells * bs;
+    // the last intermediate matrix becomes the new level (its old buffers go back to the slot)
+    amg_swap_pattern(Ln.P_own, amg.wk.P[slot]);
+    amg_swap_buf(Ln.val_own, amg.wk.V[slot]);
+    amg_swap_buf(Ln.dinv, amg.wk.D[slot]);
+    Ln.P = &Ln.P_own;
+    Ln.val = Ln.val_own.p;
+    Ln.win = nullptr;
+    Ln.m = Ln.n;
+    if (D) {
+      amg_dist_rename_halo(c, *D, l, L.agg, L.nc_cells, bs, Ln);
+      amg_dist_decide_gather(c, *D, l, Ln.n, w.gather_rows);
+    }
+    if (Ln.n > w.coarse_target && Ln.P_own.nnz >= 200000) {  // worth it only for the big levels
+      win_build(c, Ln.P_own, Ln.win_own);
+      Ln.win = &Ln.win_own;
+    }
+    ++l;
+  }
+  amg.nlev = l + 1;
+  amg_setup_finish(c, amg, A, nnz_sum, csum, level0_sum);
   amg.setup_ms = tm.stop(s);
 }
 
@@ -1592,8 +1659,8 @@ static void amg_spmv_fused(pfv_ctx_impl& c, const AmgLevel& L, const double* x, 
 // default 1.8) keeps the margin.  Deterministic: fixed start vector, fixed-shape reductions.  ~1 ms at 2 M rows.
 static void amg_estimate_omegas(pfv_ctx_impl& c, Amg& amg) {
   stream_t s = c.stream;
-  const int K = std::max(2, std::min(30, env_int("PFV_AMG_OMEGA_POWER_STEPS", 10)));
-  const double sigma = 0.01 * env_int("PFV_AMG_OMEGA_RHO_PCT", 180);
+  const int K = amg.sw.omega_power_steps;
+  const double sigma = amg.sw.omega_sigma;
   const int64_t n0 = amg.lev[0]->n;
   double* va = amg.pw_a.ensure(n0);
   double* vb = amg.pw_b.ensure(n0);

@@ -19,8 +19,6 @@
 // The transport (pfv_shard_hooks::sendrecv / allgather) moves packed buffers; packing, plans and the gathered matrix
 // are built here with the portable kernels, so the host emulation runs the same code under gloo in the tests.
 
-constexpr int64_t kAmgGatherRowsDefault = 32768;
-
 static void amg_hook_failed(const char* what) {
   throw Error(PFV_ERR_ARGUMENT, std::string("coupled hierarchy: the ") + what + " hook reported a failure");
 }
@@ -140,6 +138,81 @@ static std::unique_ptr<AmgPlan> amg_coarse_plan(pfv_ctx_impl& c, AmgDist& D, con
   return np;
 }
 
+// ---- the steps of amg_setup that exist only under the coupled hierarchy (called behind its `if (D)`)
+
+// fetches the halo entries of a level-0 vector from their owners (empty without a coupled hierarchy)
+static std::function<void(double*)> amg_fill_halo0(pfv_ctx_impl& c, AmgDist* D, int bs) {
+  if (!D) return nullptr;
+  return [&c, D, bs](double* v) { amg_halo_exchange(c, *D, *D->plan[0], v, bs); };
+}
+
+// The sizes of all ranks and, in the second word, whether EVERY rank may keep its aggregate maps, in one gather: all
+// ranks get the same answer and take the same branch of the setup (its exchanges stay matched).
+static bool amg_dist_vote(pfv_ctx_impl& c, AmgDist& D, int64_t nrows, bool mine) {
+  const std::vector<int64_t> cnt0 = amg_gather_counts(c, D, nrows, mine ? 1 : 0);
+  D.global_rows0 = 0;
+  bool all = true;
+  for (int r = 0; r < D.world; ++r) {
+    D.global_rows0 += cnt0[2 * r];
+    all = all && cnt0[2 * r + 1] == 1;
+  }
+  D.global_rows_level = D.global_rows0;
+  D.kgather = 0;
+  D.exchanges = D.allgathers = 0;
+  return all;
+}
+
+// halo columns ride along unchanged through the passes of a level (renamed once, after the last pass): the map of a pass
+// extended by the identity on the halo cells
+static const int32_t* amg_dist_extend_map(pfv_ctx_impl& c, AmgDist& D, size_t l, const int32_t* a1p, int64_t cur_cells,
+                                          int64_t nagg) {
+  const int64_t nh = D.plan[l]->n_halo;
+  int32_t* ae = D.aext.ensure((size_t)(cur_cells + nh));
+  parallel_for(c.stream, cur_cells + nh, PFV_LAMBDA(int64_t i) { ae[i] = i < cur_cells ? a1p[i] : (int32_t)(nagg + (i - cur_cells)); });
+  return ae;
+}
+
+// this rank has nothing left to merge, others may: its cells go on as they are (every rank builds every level); the
+// level's matrix lands in slot 0 of the workspace
+static void amg_dist_identity_level(pfv_ctx_impl& c, Amg& amg, AmgDist& D, size_t l, const CsrPattern& P, const double* val,
+                                    int32_t* aggL, int64_t cells) {
+  stream_t s = c.stream;
+  AmgWork& wk = amg.wk;
+  int32_t* ident = wk.a1.ensure((size_t)cells);
+  const int64_t nh = D.plan[l]->n_halo;
+  int32_t* ae = D.aext.ensure((size_t)(cells + nh));
+  parallel_for(s, cells, PFV_LAMBDA(int64_t i) { ident[i] = (int32_t)i; aggL[i] = (int32_t)i; });
+  parallel_for(s, cells + nh, PFV_LAMBDA(int64_t i) { ae[i] = (int32_t)i; });
+  amg_members(c, wk, ident, cells, cells, wk.mp, wk.me);
+  amg_galerkin(c, amg.sw, wk, P, val, amg.bs, ae, wk.mp, wk.me, cells, wk.P[0], wk.V[0], wk.D[0]);
+  wk.P[0].ncols = (cells + nh) * amg.bs;
+}
+
+// the plan of level l + 1, and the owners' aggregates rename the halo columns of its matrix
+static void amg_dist_rename_halo(pfv_ctx_impl& c, AmgDist& D, size_t l, const int32_t* aggL, int64_t ncn, int bs, AmgLevel& Ln) {
+  while (D.plan.size() <= l + 1) D.plan.push_back(nullptr);
+  D.plan[l + 1] = amg_coarse_plan(c, D, *D.plan[l], aggL, ncn);
+  const int32_t* ch = D.chalo;
+  int32_t* ixn = Ln.P_own.indices;
+  parallel_for(c.stream, Ln.P_own.nnz, PFV_LAMBDA(int64_t e) {
+    const int col = ixn[e];
+    const int cc = col / bs;
+    if (cc >= ncn) ixn[e] = (int32_t)((ncn + ch[cc - ncn]) * bs + (col - cc * bs));
+  });
+  Ln.P_own.ncols = (ncn + D.plan[l + 1]->n_halo) * bs;
+  Ln.m = Ln.P_own.ncols;
+}
+
+// gather from level l + 1 on?  (decided from the rows of all ranks: the same on every rank)
+static void amg_dist_decide_gather(pfv_ctx_impl& c, AmgDist& D, size_t l, int64_t rows_next, int64_t gather_rows) {
+  const std::vector<int64_t> cn = amg_gather_counts(c, D, rows_next, 0);
+  int64_t tot = 0;
+  for (int r = 0; r < D.world; ++r) tot += cn[2 * r];
+  const int64_t tot_here = D.global_rows_level;
+  D.global_rows_level = tot;
+  if (tot <= gather_rows || tot > 0.85 * tot_here || (int)l + 3 >= kAmgMaxLevels) D.kgather = l + 1;
+}
+
 // Rows of all ranks at the gathered level -> one matrix in global numbering (rank-major), sorted and merged; then the
 // replicated hierarchy on it.
 static void amg_build_global(pfv_ctx_impl& c, Amg& amg, AmgDist& D, AmgLevel& LK, const AmgPlan& plK) {
@@ -218,7 +291,7 @@ static void amg_build_global(pfv_ctx_impl& c, Amg& amg, AmgDist& D, AmgLevel& LK
   int32_t* ident = D.gagg.ensure((size_t)std::max<int64_t>(Ncell, 1));
   parallel_for(s, Ncell, PFV_LAMBDA(int64_t i) { ident[i] = (int32_t)i; });
   amg_members(c, amg.wk, ident, Ncell, Ncell, D.gmp, D.gme);
-  amg_galerkin(c, amg.wk, T, tv, bs, ident, D.gmp, D.gme, Ncell, D.gP, D.gV, D.gD);
+  amg_galerkin(c, amg.sw, amg.wk, T, tv, bs, ident, D.gmp, D.gme, Ncell, D.gP, D.gV, D.gD);
   if (!D.glob) D.glob = std::make_unique<Amg>();
   D.glob->no_filter = true;
   D.glob->finest_cells_parent = std::max<int64_t>(1, D.global_rows0 / bs);

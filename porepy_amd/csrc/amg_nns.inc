@@ -42,10 +42,54 @@ struct NnsLevel {
   Buf<double> x, b, t, r2, x2;     // cycle vectors
 };
 
+// The switches of one setup: read in ONE place, nns_read_switches, at the start of every setup; amg_nns_cfg hashes them.
+struct NnsSwitches {
+  int passes = kNnsPasses, passes_coarse = kNnsPassesCoarse;  // PFV_AMG_NNS_PASSES, _PASSES_COARSE: 1..6
+  int omega_pct = 70, alpha_pct = 130;                        // PFV_AMG_NNS_OMEGA_PCT, _ALPHA_PCT
+  bool fp32 = true;                                           // PFV_AMG_NNS_FP32
+  // PFV_AMG_NNS_GAMMA as given: the default follows the size of the system (amg_nns_setup resolves and clamps to 1..2)
+  bool gamma_set = false;
+  int gamma_raw = 0;
+  int gamma_levels = 1;                    // PFV_AMG_NNS_GAMMA_LEVELS, >= 1
+  int sweeps = 1;                          // PFV_AMG_NNS_SWEEPS, 1..4
+  int coarse_target = kNnsCoarseTarget;    // PFV_AMG_NNS_COARSE_TARGET, 1..kAmgDenseMax
+  int filter_permil = 0;                   // PFV_AMG_NNS_FILTER_PERMIL (block sizes above 4: no filter)
+};
+
+static NnsSwitches nns_read_switches(int bs) {
+  NnsSwitches w;
+  w.passes = std::max(1, std::min(6, env_int("PFV_AMG_NNS_PASSES", kNnsPasses)));
+  w.passes_coarse = std::max(1, std::min(6, env_int("PFV_AMG_NNS_PASSES_COARSE", kNnsPassesCoarse)));
+  w.omega_pct = env_int("PFV_AMG_NNS_OMEGA_PCT", 70);
+  w.alpha_pct = env_int("PFV_AMG_NNS_ALPHA_PCT", 130);
+  w.fp32 = env_int("PFV_AMG_NNS_FP32", 1) != 0;
+  const char* gamma = std::getenv("PFV_AMG_NNS_GAMMA");
+  w.gamma_set = gamma != nullptr;
+  if (gamma) w.gamma_raw = std::atoi(gamma);
+  w.gamma_levels = std::max(1, env_int("PFV_AMG_NNS_GAMMA_LEVELS", 1));
+  w.sweeps = std::max(1, std::min(4, env_int("PFV_AMG_NNS_SWEEPS", 1)));
+  w.coarse_target = std::max(1, std::min(kAmgDenseMax, env_int("PFV_AMG_NNS_COARSE_TARGET", kNnsCoarseTarget)));
+  const int permil = env_int("PFV_AMG_NNS_FILTER_PERMIL", bs == 1 ? kAmgFilterPermil : kAmgFilterPermilBlock);
+  w.filter_permil = bs <= 4 ? permil : 0;
+  return w;
+}
+
+// the switches a hierarchy is built with, in one word (a changed effective value rebuilds it; PFV_AMG_NNS_GAMMA, whose
+// default follows the size, as given)
+static unsigned long long amg_nns_cfg(int bs) {
+  const NnsSwitches w = nns_read_switches(bs);
+  unsigned long long h = 1469598103934665603ull;
+  for (int v : {w.passes, w.passes_coarse, w.omega_pct, w.alpha_pct, (int)w.fp32, w.gamma_set ? w.gamma_raw : -1,
+                (int)w.gamma_set, w.gamma_levels, w.sweeps, w.coarse_target, w.filter_permil})
+    h = (h ^ (unsigned long long)(v + 7)) * 1099511628211ull;
+  return h;
+}
+
 struct AmgNns {
   std::vector<std::unique_ptr<NnsLevel>> lev;
   size_t nlev = 0;
   AmgWork wk;
+  AmgSwitches plain;  // the plain hierarchy's switches the shared helpers read (matching, Galerkin pattern, filter, dense inverse)
   int k = 0;
   int passes = kNnsPasses, passes_coarse = kNnsPassesCoarse;
   double omega = 0.7, alpha = 1.3, filter_theta = 0.0;
@@ -234,7 +278,7 @@ static void nns_galerkin(pfv_ctx_impl& c, AmgNns& H, NnsLevel& L, NnsLevel& Ln) 
   const int bs = L.bs, k = H.k, kk = k * k;
   const int64_t nagg = L.nagg;
   nns_cell_graph(c, H, *L.P, bs);
-  amg_galerkin(c, H.wk, H.cellP, H.ones.p, 1, L.agg, L.mptr, L.mem, nagg, H.cellC, H.cellCV, H.cellCD, nullptr);
+  amg_galerkin(c, H.plain, H.wk, H.cellP, H.ones.p, 1, L.agg, L.mptr, L.mem, nagg, H.cellC, H.cellCV, H.cellCD, nullptr);
   const int32_t* cp = H.cellC.indptr;
   const int32_t* cx = H.cellC.indices;
   int32_t* st = c.status.ensure(16);
@@ -377,7 +421,7 @@ static bool nns_aggregate(pfv_ctx_impl& c, AmgNns& H, NnsLevel& L, const CsrPatt
   int slot = 0;
   bool any = false;
   for (int pass = 0; pass < passes; ++pass) {
-    const int64_t nagg = amg_pairwise(c, wk, *curP, curV, bs, wk.a1);
+    const int64_t nagg = amg_pairwise(c, H.plain, wk, *curP, curV, bs, wk.a1);
     if (nagg >= cur) break;
     const int32_t* a1 = wk.a1;
     if (!any) parallel_for(s, cells, PFV_LAMBDA(int64_t i) { aggL[i] = a1[i]; });
@@ -386,7 +430,7 @@ static bool nns_aggregate(pfv_ctx_impl& c, AmgNns& H, NnsLevel& L, const CsrPatt
     if (pass + 1 < passes && nagg * bs > kNnsCoarseTarget) {
       // the aggregated graph the next pass matches on (piecewise-constant Galerkin product, bs kept)
       amg_members(c, wk, a1, cur, nagg, wk.mp, wk.me);
-      amg_galerkin(c, wk, *curP, curV, bs, a1, wk.mp, wk.me, nagg, wk.P[slot], wk.V[slot], wk.D[slot], nullptr);
+      amg_galerkin(c, H.plain, wk, *curP, curV, bs, a1, wk.mp, wk.me, nagg, wk.P[slot], wk.V[slot], wk.D[slot], nullptr);
       curP = &wk.P[slot];
       curV = wk.V[slot].p;
       slot = 1 - slot;
@@ -413,16 +457,17 @@ static void amg_nns_setup(pfv_ctx_impl& c, AmgNns& H, const CsrPattern& A, const
   H.k = k;
   if (k < 1 || k > kNnsMaxModes) throw Error(PFV_ERR_UNSUPPORTED, "AMG near-null space: 1 to 8 modes");
   if (bs < 1 || bs > kNnsMaxModes || A.nrows % bs) throw Error(PFV_ERR_ARGUMENT, "AMG near-null space: bad block size");
-  H.passes = std::max(1, std::min(6, env_int("PFV_AMG_NNS_PASSES", kNnsPasses)));
-  H.passes_coarse = std::max(1, std::min(6, env_int("PFV_AMG_NNS_PASSES_COARSE", kNnsPassesCoarse)));
-  H.omega = 0.01 * env_int("PFV_AMG_NNS_OMEGA_PCT", 70);
-  H.alpha = 0.01 * env_int("PFV_AMG_NNS_ALPHA_PCT", 130);
-  H.fp32 = env_int("PFV_AMG_NNS_FP32", 1) != 0;
-  H.gamma = std::max(1, std::min(2, env_int("PFV_AMG_NNS_GAMMA", A.nrows >= kAmgWTopRows ? 2 : 1)));
-  H.gamma_levels = std::max(1, env_int("PFV_AMG_NNS_GAMMA_LEVELS", 1));
-  H.sweeps = std::max(1, std::min(4, env_int("PFV_AMG_NNS_SWEEPS", 1)));
-  const int coarse_target = std::max(1, std::min(kAmgDenseMax, env_int("PFV_AMG_NNS_COARSE_TARGET", kNnsCoarseTarget)));
-  H.filter_theta = bs <= 4 ? 0.001 * env_int("PFV_AMG_NNS_FILTER_PERMIL", bs == 1 ? kAmgFilterPermil : kAmgFilterPermilBlock) : 0.0;
+  const NnsSwitches w = nns_read_switches(bs);
+  H.plain = amg_read_switches(bs);
+  H.passes = w.passes;
+  H.passes_coarse = w.passes_coarse;
+  H.omega = 0.01 * w.omega_pct;
+  H.alpha = 0.01 * w.alpha_pct;
+  H.fp32 = w.fp32;
+  H.gamma = std::max(1, std::min(2, w.gamma_set ? w.gamma_raw : (A.nrows >= kAmgWTopRows ? 2 : 1)));
+  H.gamma_levels = w.gamma_levels;
+  H.sweeps = w.sweeps;
+  H.filter_theta = 0.001 * w.filter_permil;
   if (bs > 1) {  // full bs x bs blocks (the cell graph and the Galerkin kernel address them so)
     const int32_t* ip = A.indptr;
     int32_t* st = c.status.ensure(16);
@@ -474,11 +519,11 @@ static void amg_nns_setup(pfv_ctx_impl& c, AmgNns& H, const CsrPattern& A, const
       parallel_for(s, L.P->nnz, PFV_LAMBDA(int64_t e) { v32[e] = (float)v64[e]; });
       L.v32 = v32;
     }
-    if (L.n <= coarse_target || (int)l + 1 >= kAmgMaxLevels) break;
+    if (L.n <= w.coarse_target || (int)l + 1 >= kAmgMaxLevels) break;
     const CsrPattern* G = L.P;
     const double* gv = L.val;
     if (l == 0 && H.filter_theta > 0.0) {  // strength filter (amg.inc: amg_filter) for the matching only
-      amg_filter(c, *L.P, L.val, H.filter_theta, H.filtP, H.filtV, H.wk, bs);
+      amg_filter(c, H.plain, *L.P, L.val, H.filter_theta, H.filtP, H.filtV, H.wk, bs);
       G = &H.filtP;
       gv = H.filtV.p;
     }
@@ -491,7 +536,7 @@ static void amg_nns_setup(pfv_ctx_impl& c, AmgNns& H, const CsrPattern& A, const
   }
   H.nlev = l + 1;
   NnsLevel& Lc = *H.lev[H.nlev - 1];
-  if (Lc.n <= kAmgDenseMax) H.dense_ok = amg_dense_invert(c, H.wk, *Lc.P, Lc.val, H.dense);
+  if (Lc.n <= kAmgDenseMax) H.dense_ok = amg_dense_invert(c, H.plain, H.wk, *Lc.P, Lc.val, H.dense);
   H.op_complexity = nnz_sum / (double)std::max<int64_t>(A.nnz, 1);
   H.valid = true;
   if (env_int("PFV_DEBUG_AMG", 0)) {
@@ -611,17 +656,6 @@ static void amg_nns_cycle(pfv_ctx_impl& c, AmgNns& H, size_t l, const double* b,
     nns_spmv(c, L, x, t);
     nns_smooth(c, L, H.omega, x, b, t, x);
   }
-}
-
-// the switches a hierarchy is built with, in one word (a changed switch rebuilds it)
-static unsigned long long amg_nns_cfg() {
-  static const char* const keys[] = {"PFV_AMG_NNS_PASSES", "PFV_AMG_NNS_PASSES_COARSE", "PFV_AMG_NNS_OMEGA_PCT",
-                                     "PFV_AMG_NNS_ALPHA_PCT", "PFV_AMG_NNS_FP32", "PFV_AMG_NNS_GAMMA",
-                                     "PFV_AMG_NNS_GAMMA_LEVELS", "PFV_AMG_NNS_SWEEPS", "PFV_AMG_NNS_COARSE_TARGET",
-                                     "PFV_AMG_NNS_FILTER_PERMIL"};
-  unsigned long long h = 1469598103934665603ull;
-  for (const char* k : keys) h = (h ^ (unsigned long long)(env_int(k, -1) + 7)) * 1099511628211ull;
-  return h;
 }
 
 // rigid-body modes of the grid's cells, column-major [k][nc * nd] in the grid's numbering (cell-major,

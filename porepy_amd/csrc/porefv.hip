@@ -114,6 +114,16 @@ void upload(pfv::Buf<T>& buf, const T* host, size_t n, pfv::stream_t s) {
   be_h2d(buf.p, host, n * sizeof(T), s);
 }
 
+// what the setup of a hierarchy H (Amg, AmgNns) leaves in the statistics
+template <class H>
+void amg_setup_stats(pfv_ctx* h, const H& amg, int64_t levels, int64_t coarsest_rows, bool maps_reused) {
+  h->stats.amg_setup_ms = amg.setup_ms;
+  h->stats.amg_operator_complexity = amg.op_complexity;
+  h->stats.amg_levels = levels;
+  h->stats.amg_coarsest_rows = coarsest_rows;
+  h->stats.amg_maps_reused = maps_reused ? 1 : 0;
+}
+
 }  // namespace
 
 namespace {
@@ -1718,11 +1728,7 @@ pfv_status pfv_amg_setup(pfv_ctx* h, int64_t n_own) {
       bw = &h->win_block;
     }
     pfv::amg_setup(*h, *h->amg_block, *P, val, bs, h->active.diag, bw);  // the leading block keeps its diagonal
-    h->stats.amg_setup_ms = h->amg_block->setup_ms;
-    h->stats.amg_operator_complexity = h->amg_block->op_complexity;
-    h->stats.amg_levels = (int64_t)h->amg_block->nlev;
-    h->stats.amg_coarsest_rows = h->amg_block->lev[h->amg_block->nlev - 1]->n;
-    h->stats.amg_maps_reused = h->amg_block->reused ? 1 : 0;
+    amg_setup_stats(h, *h->amg_block, (int64_t)h->amg_block->nlev, h->amg_block->lev[h->amg_block->nlev - 1]->n, h->amg_block->reused);
     h->amg_last = 2;
   });
 }
@@ -1793,11 +1799,7 @@ pfv_status pfv_amg_setup_sharded(pfv_ctx* h, int64_t n_own, const pfv_shard_hook
                                   ? &h->win_rows
                                   : nullptr;
     pfv::amg_setup(*h, amg, V, h->active.val, bs, nullptr, win0);
-    h->stats.amg_setup_ms = amg.setup_ms;
-    h->stats.amg_operator_complexity = amg.op_complexity;
-    h->stats.amg_levels = (int64_t)(amg.nlev + (amg.dist->glob ? amg.dist->glob->nlev - 1 : 0));
-    h->stats.amg_coarsest_rows = amg.dist->gN;
-    h->stats.amg_maps_reused = amg.reused ? 1 : 0;
+    amg_setup_stats(h, amg, (int64_t)(amg.nlev + (amg.dist->glob ? amg.dist->glob->nlev - 1 : 0)), amg.dist->gN, amg.reused);
   });
 }
 
@@ -2085,11 +2087,7 @@ pfv_status pfv_solve(pfv_ctx* h, int method, double rtol, int maxit, int restart
         pfv::amg_setup(*h, *h->amg, *sys.P, sys.val, h->active_bs, sys.diag, sys.win);
         h->amg_for_val = sys.val;
         h->amg_last = 1;
-        h->stats.amg_setup_ms = h->amg->setup_ms;
-        h->stats.amg_operator_complexity = h->amg->op_complexity;
-        h->stats.amg_levels = (int64_t)h->amg->nlev;
-        h->stats.amg_coarsest_rows = h->amg->lev[h->amg->nlev - 1]->n;
-        h->stats.amg_maps_reused = h->amg->reused ? 1 : 0;
+        amg_setup_stats(h, *h->amg, (int64_t)h->amg->nlev, h->amg->lev[h->amg->nlev - 1]->n, h->amg->reused);
         h->stats.amg_stale_rematches = h->amg->stale_rematches;
         h->stats.amg_level0_nnz = h->amg->lev[0]->P->nnz;
         h->stats.amg_filter_theta = h->amg->filter_level0 ? h->amg->filter_theta : 0.0;
@@ -2101,7 +2099,7 @@ pfv_status pfv_solve(pfv_ctx* h, int method, double rtol, int maxit, int restart
               "the near-null space does not fit the active system (pfv_set_near_null_space again)");
       require(!h->nns_B.empty() || h->active_is_grid, "rigid-body modes of the grid need the assembled mechanics system");
       if (!h->amg_nns) h->amg_nns = std::make_unique<pfv::AmgNns>();
-      const unsigned long long cfg = pfv::amg_nns_cfg();
+      const unsigned long long cfg = pfv::amg_nns_cfg(h->nns_bs);
       if (!h->amg_nns->valid || h->nns_stale || h->amg_nns_for_val != sys.val || h->amg_nns_key != h->nns_key ||
           h->amg_nns_cfg != cfg) {
         const double* B0 = nns_modes(h, permuted);
@@ -2111,11 +2109,7 @@ pfv_status pfv_solve(pfv_ctx* h, int method, double rtol, int maxit, int restart
         h->amg_nns_cfg = cfg;
         h->nns_stale = false;
         const pfv::AmgNns& H = *h->amg_nns;
-        h->stats.amg_setup_ms = H.setup_ms;
-        h->stats.amg_operator_complexity = H.op_complexity;
-        h->stats.amg_levels = (int64_t)H.nlev;
-        h->stats.amg_coarsest_rows = H.lev[H.nlev - 1]->n;
-        h->stats.amg_maps_reused = 0;
+        amg_setup_stats(h, H, (int64_t)H.nlev, H.lev[H.nlev - 1]->n, false);
         h->stats.amg_level0_nnz = sys.P->nnz;
         h->stats.amg_filter_theta = 0.0;
         h->stats.amg_nns_modes = H.k;

@@ -713,6 +713,35 @@ def state_sequence(lib, n=8):
     return log
 
 
+def matching_switch_change_rematches(lib, n=8):
+    """A switch the matching depends on invalidates the kept maps, both when it is set and when it is removed again:
+    the setup after the change re-matches, and its maps are those of a fresh handle under the same switches."""
+    g = tet_grid(n)
+    S = FlowSystem(lib, g, seed=4)
+
+    def setup(sysm, reused, env=None):
+        with environment(env or {}):
+            sysm.ctx.amg_setup(0)
+            H = read_hierarchy(sysm.ctx)
+            assert H[0]["reused"] == reused, (env, H[0]["reused"])
+            check_setup(H)
+        return H
+
+    def same_maps(Ha, Hb):
+        assert len(Ha) == len(Hb)
+        for a, b in zip(Ha, Hb):
+            for k in ("agg", "mptr", "mem"):
+                assert (a[k] is None) == (b[k] is None) and (a[k] is None or np.array_equal(a[k], b[k])), k
+
+    first = setup(S, False)
+    assert len(first) >= 3
+    same_maps(setup(S, True), first)
+    for env in ({"PFV_AMG_ROUNDS": "1"}, {"PFV_AMG_STRENGTH_NEG": "1"}, {"PFV_AMG_PASSES_COARSE": "1"}):
+        same_maps(setup(S, False, env), setup(FlowSystem(lib, g, seed=4), False, env))
+        same_maps(setup(S, False), first)
+    return len(first)
+
+
 def different_pattern_same_sizes(lib, n=900, seed=12):
     """Two user systems with equal rows and nnz but different patterns on one handle: the maps must be rebuilt."""
     rng = np.random.default_rng(seed)

@@ -81,6 +81,10 @@ def test_state_sequence(lib):
         _report("state / " + tag, out)
 
 
+def test_matching_switch_change_rematches(lib):
+    assert C.matching_switch_change_rematches(lib, 8) >= 3
+
+
 def test_different_pattern_with_equal_sizes_rebuilds_the_maps(lib):
     C.different_pattern_same_sizes(lib)
 

@@ -62,7 +62,9 @@ enum {
   PFV_MAT_UPWIND_RHS_DIR = 15,
   PFV_MAT_UPWIND_RHS_NEU = 16,
   PFV_MAT_TRANSPORT_SYSTEM = 17,
-  PFV_NUM_MATS = 18
+  PFV_MAT_ADVDIFF_SYSTEM = 18, /* diag(acc) + div flux + w div diag(q) U of pfv_advdiff_assemble, on the pattern of
+                                  PFV_MAT_SYSTEM */
+  PFV_NUM_MATS = 19
 };
 
 /* boundary-condition flag bits per face (params/bc.py:68-190: is_dir/is_neu/is_rob/
@@ -159,6 +161,14 @@ typedef struct {
   int64_t transport_iterations;   /* ... Krylov iterations summed over its steps */
   int64_t transport_gmres_retries; /* ... steps whose BiCGStab solve broke down (NaN residual) and were solved again with
                                       GMRES from the kept state */
+  double advdiff_assemble_ms;     /* last pfv_advdiff_assemble: the refresh (and, on the first call after a discretization,
+                                     the diffusion part of the right-hand side and the pattern check) */
+  double advdiff_advance_ms;      /* last pfv_advdiff_advance, all steps */
+  int64_t advdiff_iterations;     /* ... Krylov iterations summed over its steps */
+  int64_t advdiff_precond_fallbacks; /* ... steps whose AMG-preconditioned solve did not converge and were solved again
+                                        with Jacobi-GMRES from the kept state */
+  int64_t advdiff_gmres_retries;  /* ... steps whose BiCGStab solve broke down (NaN residual) and were solved again with
+                                     GMRES from the kept state (pfv_transport_advance keeps its own count) */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -527,6 +537,43 @@ pfv_status pfv_upwind_assemble(pfv_ctx* h, const double* q, const double* bc_val
  * receives the info of the last solve. */
 pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rtol, int maxit, double* c,
                                  int32_t* steps_done, pfv_solve_info* last);
+
+/* ---- Advection-diffusion step on the device (csrc/advdiff.inc) ---------------------------------------------------
+ * One handle carries the transport keyword: its diffusion discretization (pfv_mpfa_discretize or pfv_tpfa_discretize
+ * of the keyword's tensor and conditions) and the upwind classification of its faces, decided from sign(q) with the
+ * same flags (pfv_mpfa_set_params) by the rules of pfv_upwind_discretize.  The system
+ *     S = diag(accumulation) + div flux_D + w div diag(q) U            (PFV_MAT_ADVDIFF_SYSTEM, pattern of PFV_MAT_SYSTEM)
+ *     r = accumulation o c_old - b_ref + b_D + source
+ * with b_D = -div bound_flux_D bc_values and b_ref = div (rhs_neu + rhs_dir diag(w q)) bc_values becomes the active
+ * system of pfv_solve.  div flux_D and b_D are formed once per discretization and kept; every later call refreshes the
+ * values of S, its diagonal and r in one kernel, without symbolic work and without pfv_upwind_discretize.
+ * q (Nf): NULL = the resident face flux of this handle; with vectors on the device it may be the resident flux of
+ * another handle on the same device (pfv_resident_flux).  flux_scale w must be positive and finite.  bc_values (Nf):
+ * NULL = those of the previous call on this discretization.  accumulation, c_old, source (Nc) and bound_rhs_out (Nc,
+ * receives b_ref) may be NULL.  A boundary face with inflow that is neither Dirichlet nor Neumann: PFV_ERR_ARGUMENT.
+ * Periodic grids, conditions per sub-face, Robin faces and the sharded solve: PFV_ERR_UNSUPPORTED.  The solver caches
+ * are invalidated as by pfv_upwind_assemble; the AMG aggregate maps are kept, so the next setup reuses them. */
+pfv_status pfv_advdiff_assemble(pfv_ctx* h, const double* q, double flux_scale, const double* bc_values,
+                                const double* accumulation, const double* c_old, const double* source,
+                                double* bound_rhs_out);
+/* n_steps implicit Euler steps with the system of pfv_advdiff_assemble, the state resident between the steps: per step
+ * r = accumulation o c - b_ref + b_D + source, then a solve with the preconditioner selected on the handle
+ * (pfv_set_preconditioner: PFV_PRECOND_JACOBI or PFV_PRECOND_AMG; the hierarchy is set up once and reused by all steps)
+ * started from c.  method: PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES.  A BiCGStab step that breaks down (NaN residual) is
+ * solved again with GMRES from the kept state, as in pfv_transport_advance (counted in pfv_stats.
+ * advdiff_gmres_retries); a step whose AMG-preconditioned solve does not converge is restored from the kept state and
+ * solved with Jacobi-GMRES (pfv_stats.advdiff_precond_fallbacks counts those).  Stops at the first step that still
+ * does not converge (PFV_ERR_NOT_CONVERGED; steps_done counts the converged ones). */
+pfv_status pfv_advdiff_advance(pfv_ctx* h, int n_steps, int method, double rtol, int maxit, double* c,
+                               int32_t* steps_done, pfv_solve_info* last);
+/* Total face flux (Nf) of the transported quantity for the state c (Nc), with q, w and bc_values of the last
+ * pfv_advdiff_assemble: w q c_upstream (+ the Dirichlet-inflow / Neumann boundary parts) + flux_D c + bound_flux_D
+ * bc_values.  Its divergence over a step equals source - accumulation o (c_new - c_old). */
+pfv_status pfv_advdiff_face_flux(pfv_ctx* h, const double* c, double* out);
+/* The resident face flux (pfv_mpfa_face_flux) of this handle: d_q (may be NULL) receives its device address -- Nf
+ * doubles, valid until the next pfv_mpfa_face_flux or pfv_set_grid on the handle --, q_out (Nf, may be NULL) a copy,
+ * in host or device memory as selected by pfv_set_vectors_on_device.  PFV_ERR_ARGUMENT when there is none. */
+pfv_status pfv_resident_flux(pfv_ctx* h, double** d_q, double* q_out);
 
 /* Device-pointer variants for multi-GPU drivers that keep vectors in HBM
  * (torch tensors): y = A x on the handle's stream; d_x has num_cols entries. */

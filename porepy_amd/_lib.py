@@ -21,6 +21,7 @@ MAT_STRESS, MAT_BOUND_STRESS, MAT_BOUND_DISPLACEMENT_CELL, MAT_BOUND_DISPLACEMEN
 MAT_USER_SYSTEM = 12
 MAT_FLUX_JACOBIAN = 13
 MAT_UPWIND, MAT_UPWIND_RHS_DIR, MAT_UPWIND_RHS_NEU, MAT_TRANSPORT_SYSTEM = 14, 15, 16, 17
+MAT_ADVDIFF_SYSTEM = 18
 BC_DIR, BC_NEU, BC_ROB, BC_INTERNAL = 1, 2, 4, 8
 SOLVE_CG, SOLVE_BICGSTAB, SOLVE_GMRES = 0, 1, 2
 PRECOND_JACOBI, PRECOND_AMG, PRECOND_BLOCK, PRECOND_AMG_NNS = 0, 1, 2, 3
@@ -47,6 +48,7 @@ EXPORTS = [
     "pfv_mpsa_set_subface_eta", "pfv_mpsa_set_reconstruction_eta", "pfv_mpsa_set_reconstruction_eta_subface", "pfv_get_stats_n", "pfv_set_block_preconditioner",
     "pfv_mpfa_set_permeability", "pfv_set_near_null_space", "pfv_amg_nns_level", "pfv_amg_level",
     "pfv_mpfa_face_flux", "pfv_upwind_set_bc", "pfv_upwind_discretize", "pfv_upwind_assemble", "pfv_transport_advance",
+    "pfv_advdiff_assemble", "pfv_advdiff_advance", "pfv_advdiff_face_flux", "pfv_resident_flux",
 ]
 
 
@@ -72,7 +74,10 @@ class Stats(C.Structure):
                 ("pipeline_runs", C.c_int64), ("amg_nns_modes", C.c_int64),
                 ("face_flux_ms", C.c_double), ("upwind_ms", C.c_double), ("transport_assemble_ms", C.c_double),
                 ("transport_advance_ms", C.c_double), ("transport_iterations", C.c_int64),
-                ("transport_gmres_retries", C.c_int64)]
+                ("transport_gmres_retries", C.c_int64),
+                ("advdiff_assemble_ms", C.c_double), ("advdiff_advance_ms", C.c_double),
+                ("advdiff_iterations", C.c_int64), ("advdiff_precond_fallbacks", C.c_int64),
+                ("advdiff_gmres_retries", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -287,6 +292,15 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_transport_advance.argtypes = [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(C.c_int32),
                                           C.POINTER(SolveInfo)]
     lib.pfv_transport_advance.restype = C.c_int
+    lib.pfv_advdiff_assemble.argtypes = [_h, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]
+    lib.pfv_advdiff_assemble.restype = C.c_int
+    lib.pfv_advdiff_advance.argtypes = [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(C.c_int32),
+                                        C.POINTER(SolveInfo)]
+    lib.pfv_advdiff_advance.restype = C.c_int
+    lib.pfv_advdiff_face_flux.argtypes = [_h, _dp, _dp]
+    lib.pfv_advdiff_face_flux.restype = C.c_int
+    lib.pfv_resident_flux.argtypes = [_h, C.POINTER(C.c_void_p), _dp]
+    lib.pfv_resident_flux.restype = C.c_int
     return lib
 
 
@@ -1326,6 +1340,93 @@ class Context:
         if st != 0 and (raise_on_fail or st != 6):
             self._check(st)
         return c, out
+
+    # ---- advection-diffusion on one handle (include/porefv.h: pfv_advdiff_*) ----
+    def resident_flux_ptr(self) -> int:
+        """Device address of the resident face flux of this handle (pfv_resident_flux)."""
+        p = C.c_void_p()
+        self._check(self.lib.pfv_resident_flux(self._h, C.byref(p), None))
+        return int(p.value)
+
+    def resident_flux(self) -> np.ndarray:
+        """A host copy of the resident face flux of this handle."""
+        q = np.empty(self.nf, dtype=np.float64)
+        self._check(self.lib.pfv_resident_flux(self._h, None, _ptr(q, _dp)))
+        return q
+
+    def advdiff_assemble(self, bc_values=None, q=None, flux_scale: float = 1.0, accumulation=None, c_old=None,
+                         source=None, bound_rhs=False, device=False, q_device_ptr: int = 0, bound_rhs_ptr: int = 0):
+        """S = diag(accumulation) + div flux_D + w div diag(q) U and r = accumulation o c_old - b_ref + b_D + source
+        become the active system (pfv_advdiff_assemble).  ``q`` None: the resident flux of this handle;
+        ``q_device_ptr``: the address of Nf doubles on the device (the resident flux of another handle), the other
+        vectors staying where ``device`` says.  ``bc_values`` None: those of the previous call.  ``bound_rhs``:
+        return b_ref (``device``: written to ``bound_rhs_ptr``)."""
+        kb, pb = self._vec(bc_values, self.nf, "bc_values", device)
+        ka, pa_ = self._vec(accumulation, self.nc, "accumulation", device)
+        kc, pc = self._vec(c_old, self.nc, "c_old", device)
+        ks, ps = self._vec(source, self.nc, "source", device)
+        kq = None
+        if q_device_ptr and not device:
+            raise ValueError("q_device_ptr needs device=True (every vector an address of device memory)")
+        if q_device_ptr:
+            pq = C.cast(int(q_device_ptr), _dp)
+        else:
+            kq, pq = self._vec(q, self.nf, "the flux array", device)
+        b = np.empty(self.nc, dtype=np.float64) if (bound_rhs and not device) else None
+        pbr = C.cast(bound_rhs_ptr or None, _dp) if device else _ptr(b, _dp)
+        if device:
+            self._dev(True)
+        try:
+            self._check(self.lib.pfv_advdiff_assemble(self._h, pq, float(flux_scale), pb, pa_, pc, ps, pbr))
+        finally:
+            if device:
+                self._dev(False)
+        return b
+
+    def advdiff_advance(self, c0, n_steps: int, method="bicgstab", rtol=1e-12, maxit=10000, precond="amg",
+                        raise_on_fail=True, device=False):
+        """``n_steps`` implicit Euler steps of the assembled advection-diffusion system (pfv_advdiff_advance) with
+        the preconditioner ``precond`` ("amg" or "jacobi").  Returns (c, info); ``device``: ``c0`` is the address of
+        Nc doubles on the device, advanced in place (c is None)."""
+        code = {"bicgstab": SOLVE_BICGSTAB, "gmres": SOLVE_GMRES}[method]
+        if precond not in ("amg", "jacobi"):
+            raise ValueError('precond must be "amg" or "jacobi"')
+        self._select_precond(precond)
+        if device:
+            c, pc = None, C.cast(int(c0), _dp)
+        else:
+            c = np.array(c0, dtype=np.float64, copy=True).ravel()
+            if c.shape != (self.nc,):
+                raise ValueError("c0 must have one entry per cell")
+            pc = _ptr(c, _dp)
+        done, info = C.c_int32(0), SolveInfo()
+        if device:
+            self._dev(True)
+        try:
+            st = self.lib.pfv_advdiff_advance(self._h, int(n_steps), code, float(rtol), int(maxit), pc, C.byref(done),
+                                              C.byref(info))
+        finally:
+            if device:
+                self._dev(False)
+        out = {"steps_done": done.value, "iterations": info.iterations, "converged": bool(info.converged),
+               "rel_residual": info.rel_residual, "solve_ms": info.solve_ms}
+        if st != 0 and (raise_on_fail or st != 6):
+            self._check(st)
+        return c, out
+
+    def advdiff_face_flux(self, c, device=False, out_ptr: int = 0):
+        """Total face flux of the transported quantity for the state ``c`` (pfv_advdiff_face_flux)."""
+        kc, pc = self._vec(c, self.nc, "c", device)
+        out = None if device else np.empty(self.nf, dtype=np.float64)
+        po = C.cast(out_ptr or None, _dp) if device else _ptr(out, _dp)
+        if device:
+            self._dev(True)
+        try:
+            self._check(self.lib.pfv_advdiff_face_flux(self._h, pc, po))
+        finally:
+            if device:
+                self._dev(False)
+        return out
 
     def tpfa_transmissibility_ad(self, perm):
         """Two-point face transmissibilities and their derivatives with respect to the permeability entries

@@ -170,6 +170,8 @@ struct pfv_ctx_impl {
 
   // ---- outputs --------------------------------------------------------------------
   bool have_symbolic = false, have_numeric = false, have_system = false;
+  bool have_flow_rhs = false;  // with have_system: `rhs` was formed by pfv_mpfa_assemble for the div @ flux on the handle
+                               // (pfv_advdiff_assemble forms div @ flux without a flow right-hand side)
   bool rows_complete = false;  // every row of the six MPFA matrices holds a discretization (maybe of older parameters)
   CsrPattern pat_flux, pat_bound, pat_vs, pat_A;  // bound_pressure_* share flux / bound patterns
   bool vs_indices_pending = false;  // pat_vs.indices not written yet (topology.inc: ensure_vs_indices)
@@ -326,6 +328,17 @@ struct pfv_ctx_impl {
   Buf<double> rhs_t, diag_t, bref_t, acc_t, src_t, c_t, c_keep, q_t, bc_t;
   bool have_acc_t = false, have_src_t = false;
   int64_t transport_zero_diag = -1;  // first row of the transport system with a zero diagonal (-1: none)
+
+  // ---- advection-diffusion (advdiff.inc): S = diag(acc) + div flux_D + w div diag(q) U on pat_A -------------------
+  bool have_advdiff = false;         // val[PFV_MAT_ADVDIFF_SYSTEM], adv_diag, adv_rhs hold a system of the discretization
+  bool have_adv_bD = false;          // adv_fb / adv_bD / adv_bc belong to the diffusion discretization on the handle, and
+                                     // pat_A was checked to contain the face neighbours
+  double adv_w = 1.0;                // flux scale of the last assembly
+  Buf<double> adv_fb, adv_bD;        // [nf] bound_flux_D bc; [nc] b_D = -div of it
+  Buf<double> adv_q, adv_bc;         // [nf] flux and boundary values of the last assembly
+  Buf<double> adv_acc, adv_src, adv_c, adv_keep, adv_rhs, adv_diag, adv_bref;
+  bool have_adv_acc = false, have_adv_src = false;
+  int64_t advdiff_zero_diag = -1;    // first row of S with a zero or NaN diagonal (-1: none)
 
   pfv_stats stats{};
 

@@ -20,6 +20,7 @@ static int rccl_exchange_halo(void* user, double* d_x, void* stream);  // rccl_h
 #include "biot.inc"
 #include "ad_flux.inc"
 #include "upwind.inc"
+#include "advdiff.inc"
 
 namespace pfv {
 #ifndef PFV_EMULATE
@@ -103,6 +104,7 @@ void require(bool ok, const char* msg) {
 bool pattern_ready(const pfv_ctx* h, int which) {
   if (which == PFV_MAT_USER_SYSTEM) return h->filled[which];
   if (which == PFV_MAT_TRANSPORT_SYSTEM) return h->have_transport;
+  if (which == PFV_MAT_ADVDIFF_SYSTEM) return h->have_advdiff;
   if (which >= PFV_MAT_UPWIND && which <= PFV_MAT_UPWIND_RHS_NEU) return h->have_upwind;
   if (which == PFV_MAT_FLUX_JACOBIAN) return h->have_symbolic;
   return which >= PFV_MAT_STRESS ? h->have_mpsa_symbolic : h->have_symbolic;
@@ -285,6 +287,8 @@ pfv_status pfv_set_grid(pfv_ctx* h, int nd, int64_t nc, int64_t nf, int64_t nn, 
     h->have_q_res = h->have_upw_bc = h->have_upwind = h->have_transport = h->have_pat_T = h->have_upw_cells = false;
     h->have_acc_t = h->have_src_t = false;
     h->transport_zero_diag = -1;
+    h->have_advdiff = h->have_adv_bD = h->have_adv_acc = h->have_adv_src = false;
+    h->advdiff_zero_diag = -1;
   });
 }
 
@@ -733,6 +737,7 @@ pfv_status pfv_mpfa_assemble(pfv_ctx* h, const double* bc_values, const double* 
     tm.start(s);
     if (!h->have_system) {
       pfv::assemble_system(*h);
+      h->have_advdiff = h->have_adv_bD = false;  // (advdiff.inc: built on the previous div @ flux)
       if (h->amg) h->amg->valid = false;
       h->nns_stale = true;  // (the near-null-space hierarchy too)
       if (h->block_pc) h->block_pc->for_val = nullptr;
@@ -747,6 +752,7 @@ pfv_status pfv_mpfa_assemble(pfv_ctx* h, const double* bc_values, const double* 
     pfv::assemble_rhs(*h, d_bc, d_vs, d_src);
     h->stats.assemble_ms = tm.stop(s);
     h->have_system = true;
+    h->have_flow_rhs = true;
     h->active.P = &h->pat_A;
     h->active.val = h->val[PFV_MAT_SYSTEM].p;
     h->active.diag = h->diag.p;
@@ -1010,6 +1016,195 @@ pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rto
     return st;
   }
   return st2;
+}
+
+// ---- advection-diffusion on one handle (advdiff.inc) -----------------------------------------------------------
+static void advdiff_supported(pfv_ctx* h) {
+  require(h->have_grid, "pfv_set_grid first");
+  if (h->periodic) throw pfv::Error(PFV_ERR_UNSUPPORTED, "advection-diffusion on periodic grids is not covered");
+  if (h->shard) throw pfv::Error(PFV_ERR_UNSUPPORTED, "the advection-diffusion calls have no sharded form");
+  if (h->subface_bc) throw pfv::Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
+}
+
+static bool advdiff_is_active(const pfv_ctx* h) {
+  return h->have_advdiff && h->have_system && h->have_adv_bD && h->active.valid &&
+         h->active.val == h->val[PFV_MAT_ADVDIFF_SYSTEM].p;
+}
+
+pfv_status pfv_resident_flux(pfv_ctx* h, double** d_q, double* q_out) {
+  return guarded(h, [&] {
+    require(h->have_grid && h->have_q_res, "no resident face flux on the handle (pfv_mpfa_face_flux)");
+    const size_t bytes = (size_t)h->nf * sizeof(double);
+    if (q_out) {
+      if (h->vectors_on_device) pfv::be_d2d(q_out, h->q_res.p, bytes, h->stream);
+      else be_d2h(q_out, h->q_res.p, bytes, h->stream);
+    }
+    pfv::be_sync(h->stream);  // (a reader on another handle's stream must find it complete)
+    if (d_q) *d_q = h->q_res.p;
+  });
+}
+
+pfv_status pfv_advdiff_assemble(pfv_ctx* h, const double* q, double flux_scale, const double* bc_values,
+                                const double* accumulation, const double* c_old, const double* source,
+                                double* bound_rhs_out) {
+  return guarded(h, [&] {
+    advdiff_supported(h);
+    require(h->have_numeric && h->have_params && h->filled[PFV_MAT_FLUX] && h->filled[PFV_MAT_BOUND_FLUX],
+            "discretize the diffusion first (pfv_mpfa_discretize / pfv_tpfa_discretize)");
+    require(flux_scale > 0.0 && flux_scale < HUGE_VAL, "flux_scale must be positive and finite");
+    require(q || h->have_q_res, "no face flux given and no resident face flux on the handle (pfv_mpfa_face_flux)");
+    auto s = h->stream;
+    const size_t nf = (size_t)h->nf, nc = (size_t)h->nc;
+    if (h->active.valid && h->active.val == h->val[PFV_MAT_ADVDIFF_SYSTEM].p) h->active.valid = false;
+    h->have_advdiff = false;
+    h->filled[PFV_MAT_ADVDIFF_SYSTEM] = false;
+    h->advdiff_zero_diag = -1;
+    double* d_q = h->adv_q.ensure(nf);
+    if (q) vec_in(h, d_q, q, nf);
+    else pfv::be_d2d(d_q, h->q_res.p, nf * sizeof(double), s);
+    h->have_adv_acc = accumulation != nullptr;
+    h->have_adv_src = source != nullptr;
+    if (accumulation) vec_in(h, h->adv_acc.ensure(nc), accumulation, nc);
+    if (source) vec_in(h, h->adv_src.ensure(nc), source, nc);
+    const double* d_cold = nullptr;
+    if (c_old) {
+      vec_in(h, h->adv_c.ensure(nc), c_old, nc);
+      d_cold = h->adv_c.p;
+    }
+    pfv::Timer tm;
+    if (!h->have_system) {  // div @ flux_D: once per discretization, by the flow assembly
+      pfv::assemble_system(*h);
+      h->have_adv_bD = false;
+      if (h->win_rows_prebuilt) h->win_rows_prebuilt = false;
+      else h->win_rows_for = nullptr;
+      if (h->win_sys_prebuilt) h->win_sys_prebuilt = false;
+      else h->win_for = nullptr;
+      h->have_system = true;      // PFV_MAT_SYSTEM and its diagonal hold div @ flux ...
+      h->have_flow_rhs = false;   // ... but no flow right-hand side was formed with them
+    }
+    require(bc_values || h->have_adv_bD, "bc_values is required in the first call after a discretization");
+    if (bc_values) vec_in(h, h->adv_bc.ensure(nf), bc_values, nf);
+    tm.start(s);
+    if (!h->have_adv_bD) pfv::advdiff_check_pattern(*h);
+    if (bc_values || !h->have_adv_bD) pfv::advdiff_diffusion_rhs(*h, h->adv_bc.p);
+    h->have_adv_bD = true;
+    h->adv_w = flux_scale;
+    pfv::advdiff_refresh(*h, d_q, flux_scale, h->adv_bc.p, h->have_adv_acc ? h->adv_acc.p : nullptr, d_cold,
+                         h->have_adv_src ? h->adv_src.p : nullptr);
+    h->stats.advdiff_assemble_ms = tm.stop(s);
+    if (bound_rhs_out) {
+      if (h->vectors_on_device) pfv::be_d2d(bound_rhs_out, h->adv_bref.p, nc * sizeof(double), s);
+      else be_d2h(bound_rhs_out, h->adv_bref.p, nc * sizeof(double), s);
+    }
+    pfv::be_sync(s);
+    h->have_advdiff = true;
+    // the values under the solver's caches changed (they are keyed on the value pointer); the aggregate maps stay
+    if (h->amg) h->amg->valid = false;
+    h->nns_stale = true;
+    if (h->block_pc) h->block_pc->for_val = nullptr;
+    if (h->amg_block) h->amg_block->valid = false;
+    h->perm_for_val = nullptr;
+    h->active.P = &h->pat_A;
+    h->active.val = h->val[PFV_MAT_ADVDIFF_SYSTEM].p;
+    h->active.diag = h->adv_diag.p;
+    h->active.rhs = h->adv_rhs.p;
+    h->active.n = h->nc;
+    h->active_bs = 1;
+    h->active_is_grid = true;
+    h->active.valid = true;
+  });
+}
+
+pfv_status pfv_advdiff_advance(pfv_ctx* h, int n_steps, int method, double rtol, int maxit, double* c,
+                               int32_t* steps_done, pfv_solve_info* last) {
+  if (steps_done) *steps_done = 0;
+  std::unique_ptr<pfv::Timer> tm;
+  pfv_status st = guarded(h, [&] {
+    advdiff_supported(h);
+    require(advdiff_is_active(h), "pfv_advdiff_assemble first (the advection-diffusion system must be the active one)");
+    require(n_steps >= 0 && c != nullptr, "bad argument");
+    require(method == PFV_SOLVE_BICGSTAB || method == PFV_SOLVE_GMRES,
+            "method must be PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES (the matrix is not symmetric)");
+    require(h->precond == PFV_PRECOND_JACOBI || h->precond == PFV_PRECOND_AMG,
+            "the advection-diffusion step takes PFV_PRECOND_JACOBI or PFV_PRECOND_AMG");
+    vec_in(h, h->adv_c.ensure((size_t)h->nc), c, (size_t)h->nc);
+    tm = std::make_unique<pfv::Timer>();
+    tm->start(h->stream);
+  });
+  if (st != PFV_OK) return st;
+  const bool caller_on_device = h->vectors_on_device;
+  const int precond = h->precond;
+  h->vectors_on_device = true;  // the state stays in adv_c between the steps
+  int64_t iters = 0, retries = 0, fallbacks = 0;
+  const size_t nbytes = (size_t)h->nc * sizeof(double);
+  for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
+    st = guarded(h, [&] {
+      pfv::advdiff_step_rhs(*h, h->adv_c.p);
+      pfv::be_d2d(h->adv_keep.ensure((size_t)h->nc), h->adv_c.p, nbytes, h->stream);
+    });
+    if (st != PFV_OK) break;
+    pfv_solve_info info{};
+    st = pfv_solve(h, method, rtol, maxit, 0, h->adv_c.p, h->adv_c.p, &info);
+    iters += info.iterations;
+    // BiCGStab breakdown (NaN residual): again with GMRES from the kept state, as pfv_transport_advance does
+    if (st == PFV_ERR_NOT_CONVERGED && method == PFV_SOLVE_BICGSTAB && !(info.rel_residual == info.rel_residual)) {
+      st = guarded(h, [&] { pfv::be_d2d(h->adv_c.p, h->adv_keep.p, nbytes, h->stream); });
+      if (st != PFV_OK) break;
+      ++retries;
+      st = pfv_solve(h, PFV_SOLVE_GMRES, rtol, maxit, 0, h->adv_c.p, h->adv_c.p, &info);
+      iters += info.iterations;
+    }
+    // the AMG-preconditioned solve did not get there: the step again with Jacobi-GMRES from the kept state
+    if (st == PFV_ERR_NOT_CONVERGED && precond == PFV_PRECOND_AMG) {
+      st = guarded(h, [&] { pfv::be_d2d(h->adv_c.p, h->adv_keep.p, nbytes, h->stream); });
+      if (st != PFV_OK) break;
+      ++fallbacks;
+      h->precond = PFV_PRECOND_JACOBI;
+      st = pfv_solve(h, PFV_SOLVE_GMRES, rtol, maxit, 0, h->adv_c.p, h->adv_c.p, &info);
+      h->precond = precond;
+      iters += info.iterations;
+    }
+    if (last) *last = info;
+    if (st == PFV_OK && steps_done) ++*steps_done;
+  }
+  h->vectors_on_device = caller_on_device;
+  h->precond = precond;
+  const std::string err = h->err;
+  const pfv_status st2 = guarded(h, [&] {
+    h->stats.advdiff_advance_ms = tm->stop(h->stream);
+    tm.reset();
+    h->stats.advdiff_iterations = iters;
+    h->stats.advdiff_gmres_retries = retries;
+    h->stats.advdiff_precond_fallbacks = fallbacks;
+    const size_t nc = (size_t)h->nc;
+    if (h->vectors_on_device) pfv::be_d2d(c, h->adv_c.p, nc * sizeof(double), h->stream);
+    else be_d2h(c, h->adv_c.p, nc * sizeof(double), h->stream);
+    pfv::be_sync(h->stream);
+  });
+  if (st != PFV_OK) {
+    h->err = err;
+    return st;
+  }
+  return st2;
+}
+
+pfv_status pfv_advdiff_face_flux(pfv_ctx* h, const double* c, double* out) {
+  return guarded(h, [&] {
+    advdiff_supported(h);
+    require(h->have_advdiff && h->have_system && h->have_adv_bD && h->have_numeric,
+            "pfv_advdiff_assemble first (and no new discretization since)");
+    require(c && out, "null argument");
+    auto s = h->stream;
+    const size_t nf = (size_t)h->nf, nc = (size_t)h->nc;
+    pfv::Buf<double> in_;
+    double* d_c = in_.ensure(nc + nf);
+    double* d_out = d_c + nc;
+    vec_in(h, d_c, c, nc);
+    pfv::advdiff_face_flux(*h, d_c, d_out);
+    if (h->vectors_on_device) pfv::be_d2d(out, d_out, nf * sizeof(double), s);
+    else be_d2h(out, d_out, nf * sizeof(double), s);
+    pfv::be_sync(s);  // (the staging buffer is freed on return)
+  });
 }
 
 pfv_status pfv_mpsa_set_params(pfv_ctx* h, const double* stiffness_99n, const double* cell_volumes,
@@ -1598,7 +1793,7 @@ pfv_status pfv_reset_stream(pfv_ctx* h) {
 
 pfv_status pfv_get_device_rhs(pfv_ctx* h, double** d_b, double** d_diag) {
   return guarded(h, [&] {
-    require(h->have_system, "assemble first");
+    require(h->have_system && h->have_flow_rhs, "assemble first");
     if (d_b) *d_b = h->rhs.p;
     if (d_diag) *d_diag = h->diag.p;
   });
@@ -2063,6 +2258,9 @@ pfv_status pfv_solve(pfv_ctx* h, int method, double rtol, int maxit, int restart
       throw pfv::Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(h->transport_zero_diag) +
                                                 " of the transport system (a cell without outflow and without an "
                                                 "accumulation term): the Jacobi-preconditioned solver does not apply");
+    if (h->have_advdiff && h->active.val == h->val[PFV_MAT_ADVDIFF_SYSTEM].p && h->advdiff_zero_diag >= 0)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(h->advdiff_zero_diag) +
+                                                " of the advection-diffusion system: the solver does not apply");
     auto s = h->stream;
     const size_t n = (size_t)h->active.n;
     double* dx = h->xsol.ensure(n);
@@ -2294,13 +2492,14 @@ pfv_status pfv_time_kernel(pfv_ctx* h, int kernel, int reps, double* avg_ms) {
     auto s = h->stream;
     pfv::Timer tm;
     if (kernel == PFV_KERNEL_SPMV_A) {
-      require(h->have_system, "assemble first");
+      require(h->have_system && h->have_flow_rhs, "assemble first");
       const size_t n = (size_t)h->nc;
       double* x = h->kry[7].ensure(n);
       double* y = h->kry[8].ensure(n);
       pfv::be_d2d(x, h->rhs.p, n * sizeof(double), s);
       // what the Krylov loop launches (renumbered system, windowed kernel when the pattern allows it)
-      require(h->active.valid && h->active.P == &h->pat_A, "the flow system must be the active one");
+      require(h->active.valid && h->active.P == &h->pat_A && h->active.val == h->val[PFV_MAT_SYSTEM].p,
+              "the flow system must be the active one");
       bool permuted = false;
       const pfv::LinSys sys = solver_system(h, permuted);
       pfv::sys_spmv(*h, sys, x, y);

@@ -79,8 +79,10 @@ enum { PFV_SOLVE_CG = 0, PFV_SOLVE_BICGSTAB = 1, PFV_SOLVE_GMRES = 2 };
  * algebraic multigrid built on the device from the assembled matrix (pairwise matching on the
  * strength graph, piecewise-constant prolongation, Galerkin coarse matrices) */
 enum { PFV_PRECOND_JACOBI = 0, PFV_PRECOND_AMG = 1, PFV_PRECOND_BLOCK = 2,
-       PFV_PRECOND_AMG_NNS = 3 /* aggregation AMG whose tentative prolongator carries a near-null space
-                                  (pfv_set_near_null_space; rigid-body modes for elasticity) */ };
+       PFV_PRECOND_AMG_NNS = 3, /* aggregation AMG whose tentative prolongator carries a near-null space
+                                   (pfv_set_near_null_space; rigid-body modes for elasticity) */
+       PFV_PRECOND_SWEEP = 4    /* one substitution in flow order (csrc/sweep.inc): transport and advection-diffusion
+                                   systems only; exact for the transport system of an acyclic flux (see pfv_sweep_info) */ };
 
 /* flags for pfv_mpfa_discretize */
 enum {
@@ -169,6 +171,15 @@ typedef struct {
                                         with Jacobi-GMRES from the kept state */
   int64_t advdiff_gmres_retries;  /* ... steps whose BiCGStab solve broke down (NaN residual) and were solved again with
                                      GMRES from the kept state (pfv_transport_advance keeps its own count) */
+  int64_t sweep_levels;           /* PFV_PRECOND_SWEEP, last pfv_solve: levels of the flow order (0: another preconditioner) */
+  int64_t sweep_core_cells;       /* ... cells of its cyclic core (0: the flux graph is acyclic) */
+  int64_t sweep_launches;         /* ... kernel dispatches of one application of the sweep */
+  double sweep_order_ms;          /* ... time that solve spent building the flow order (0: it was there already); after
+                                     pfv_transport_advance / pfv_advdiff_advance: summed over the steps */
+  int64_t sweep_direct_steps;     /* ... 1 when that solve was the direct one (one sweep + one true-residual check, no Krylov
+                                     loop); after pfv_transport_advance: the number of such steps */
+  int64_t sweep_direct_fallbacks; /* ... direct solves whose residual check failed and that went on with sweep-preconditioned
+                                     GMRES from the swept x (counted the same way) */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -364,6 +375,24 @@ pfv_status pfv_set_vectors_on_device(pfv_ctx* h, int on);
 /* Select the preconditioner of the following pfv_solve calls on this handle. */
 pfv_status pfv_set_preconditioner(pfv_ctx* h, int kind);
 
+/* PFV_PRECOND_SWEEP (csrc/sweep.inc): z = M^-1 r by one substitution in flow order.  The order is built on the device
+ * from the face flux q of the active transport (PFV_MAT_TRANSPORT_SYSTEM) or advection-diffusion
+ * (PFV_MAT_ADVDIFF_SYSTEM) system: an interior face with q != 0 (and not NaN) is an edge upstream cell -> downstream
+ * cell.  A forward peel gives every cell its longest upstream path as level; a backward peel of what is left takes the
+ * cells without outflow into the rest, which get the highest levels; what both leave is the cyclic core, one level
+ * between the two (no core: the flux graph is acyclic).  M holds the diagonal of S and the entries S[i,j] with
+ * level[j] < level[i].  For the transport system of an acyclic flux M = S: pfv_solve and every step of
+ * pfv_transport_advance then do one sweep and one true-residual check instead of a Krylov loop (iterations = 1;
+ * should the check fail, GMRES preconditioned by the sweep goes on from there).  Otherwise the sweep preconditions the
+ * requested method.  Any other active system, pfv_solve_sharded and pfv_amg_setup*: PFV_ERR_UNSUPPORTED.  The order is
+ * built by the first solve that needs it and kept until an assembly brings a flux with other edges (or pfv_set_grid).
+ * PFV_SWEEP_MERGE=0: one launch per level instead of runs of small levels in single-workgroup launches.
+ *
+ * pfv_sweep_info (tests): info = {cells, levels, core cells, index of the core level or -1}; level (Nc) and order (Nc:
+ * the cells sorted by level, ascending inside a level) in the caller's cell numbering, either may be NULL.  It only
+ * copies out.  PFV_ERR_ARGUMENT when no order has been built. */
+pfv_status pfv_sweep_info(pfv_ctx* h, int64_t info[4], int32_t* level, int32_t* order);
+
 /* Near-null space of PFV_PRECOND_AMG_NNS for the active system: B is a host array of n x k values, column-major, in
  * the caller's numbering of the n unknowns (bs per cell, cell-major / component-minor).  B == NULL: the rigid-body
  * modes of the handle's grid, built on the device from its cell centres -- 2-D: 2 translations + the rotation (k = 3),
@@ -534,7 +563,9 @@ pfv_status pfv_upwind_assemble(pfv_ctx* h, const double* q, const double* bc_val
  * such a step is solved again with GMRES from the kept state and counted in pfv_stats.transport_gmres_retries.
  * c holds c_0 on entry and the last computed state on return.  Stops at the first
  * step that does not converge (PFV_ERR_NOT_CONVERGED; steps_done counts the converged ones).  last (may be NULL)
- * receives the info of the last solve. */
+ * receives the info of the last solve.  With PFV_PRECOND_SWEEP selected on the handle the steps use it (any other
+ * selection: Jacobi, as ever): for an acyclic flux every step is one sweep and one residual check
+ * (pfv_stats.sweep_direct_steps), and the order is built by the first step. */
 pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rtol, int maxit, double* c,
                                  int32_t* steps_done, pfv_solve_info* last);
 
@@ -558,7 +589,8 @@ pfv_status pfv_advdiff_assemble(pfv_ctx* h, const double* q, double flux_scale, 
                                 double* bound_rhs_out);
 /* n_steps implicit Euler steps with the system of pfv_advdiff_assemble, the state resident between the steps: per step
  * r = accumulation o c - b_ref + b_D + source, then a solve with the preconditioner selected on the handle
- * (pfv_set_preconditioner: PFV_PRECOND_JACOBI or PFV_PRECOND_AMG; the hierarchy is set up once and reused by all steps)
+ * (pfv_set_preconditioner: PFV_PRECOND_JACOBI, PFV_PRECOND_AMG -- the hierarchy is set up once and reused by all steps --
+ * or PFV_PRECOND_SWEEP, the flow order built once and, like AMG, backed by the Jacobi-GMRES fallback below)
  * started from c.  method: PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES.  A BiCGStab step that breaks down (NaN residual) is
  * solved again with GMRES from the kept state, as in pfv_transport_advance (counted in pfv_stats.
  * advdiff_gmres_retries); a step whose AMG-preconditioned solve does not converge is restored from the kept state and

@@ -24,7 +24,7 @@ MAT_UPWIND, MAT_UPWIND_RHS_DIR, MAT_UPWIND_RHS_NEU, MAT_TRANSPORT_SYSTEM = 14, 1
 MAT_ADVDIFF_SYSTEM = 18
 BC_DIR, BC_NEU, BC_ROB, BC_INTERNAL = 1, 2, 4, 8
 SOLVE_CG, SOLVE_BICGSTAB, SOLVE_GMRES = 0, 1, 2
-PRECOND_JACOBI, PRECOND_AMG, PRECOND_BLOCK, PRECOND_AMG_NNS = 0, 1, 2, 3
+PRECOND_JACOBI, PRECOND_AMG, PRECOND_BLOCK, PRECOND_AMG_NNS, PRECOND_SWEEP = 0, 1, 2, 3, 4
 DISCR_REBUILD_TOPOLOGY, DISCR_SKIP_VECTOR_SOURCE = 1, 2
 
 STATUS_NAMES = {
@@ -49,6 +49,7 @@ EXPORTS = [
     "pfv_mpfa_set_permeability", "pfv_set_near_null_space", "pfv_amg_nns_level", "pfv_amg_level",
     "pfv_mpfa_face_flux", "pfv_upwind_set_bc", "pfv_upwind_discretize", "pfv_upwind_assemble", "pfv_transport_advance",
     "pfv_advdiff_assemble", "pfv_advdiff_advance", "pfv_advdiff_face_flux", "pfv_resident_flux",
+    "pfv_sweep_info",
 ]
 
 
@@ -77,7 +78,10 @@ class Stats(C.Structure):
                 ("transport_gmres_retries", C.c_int64),
                 ("advdiff_assemble_ms", C.c_double), ("advdiff_advance_ms", C.c_double),
                 ("advdiff_iterations", C.c_int64), ("advdiff_precond_fallbacks", C.c_int64),
-                ("advdiff_gmres_retries", C.c_int64)]
+                ("advdiff_gmres_retries", C.c_int64),
+                ("sweep_levels", C.c_int64), ("sweep_core_cells", C.c_int64), ("sweep_launches", C.c_int64),
+                ("sweep_order_ms", C.c_double), ("sweep_direct_steps", C.c_int64),
+                ("sweep_direct_fallbacks", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -300,6 +304,8 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_advdiff_face_flux.argtypes = [_h, _dp, _dp]
     lib.pfv_advdiff_face_flux.restype = C.c_int
     lib.pfv_resident_flux.argtypes = [_h, C.POINTER(C.c_void_p), _dp]
+    lib.pfv_sweep_info.argtypes = [_h, _lp, _ip, _ip]
+    lib.pfv_sweep_info.restype = C.c_int
     lib.pfv_resident_flux.restype = C.c_int
     return lib
 
@@ -988,7 +994,8 @@ class Context:
     def solve(self, method="bicgstab", rtol=1e-12, maxit=10000, x0=None, raise_on_fail=True, n=None,
               restart=0, precond="jacobi"):
         """Solve the system assembled last (flow: n = Nc; mechanics: pass n = nd * Nc).
-        ``restart``: GMRES cycle length (0 = 30); ``precond``: "jacobi" or "amg"."""
+        ``restart``: GMRES cycle length (0 = 30); ``precond``: "jacobi", "amg", or -- transport and
+        advection-diffusion systems only -- "sweep" (see ``sweep_info``)."""
         code = {"cg": SOLVE_CG, "bicgstab": SOLVE_BICGSTAB, "gmres": SOLVE_GMRES}[method]
         self._select_precond(precond)
         x = pinned_pool(self.lib).empty(self._active_n(n), np.float64)
@@ -1029,8 +1036,21 @@ class Context:
                 raise ValueError('precond="amg_rbm" needs the assembled mechanics system of the grid on this handle')
             self.set_near_null_space(None, self.nd)
         kind = {"jacobi": PRECOND_JACOBI, "amg": PRECOND_AMG, "block": PRECOND_BLOCK, "amg_rbm": PRECOND_AMG_NNS,
-                "amg_nns": PRECOND_AMG_NNS}[precond]
+                "amg_nns": PRECOND_AMG_NNS, "sweep": PRECOND_SWEEP}[precond]
         self._check(self.lib.pfv_set_preconditioner(self._h, kind))
+
+    def sweep_info(self) -> dict:
+        """The flow order the last ``precond="sweep"`` solve on this handle worked with (pfv_sweep_info; read-only), in
+        the caller's cell numbering: ``level`` of every cell, ``order`` (the cells sorted by level, ascending inside a
+        level), ``levels``, ``core_cells`` (0: the flux graph is acyclic) and ``core_level`` (-1: none)."""
+        info = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.pfv_sweep_info(self._h, info.ctypes.data_as(_lp), None, None))
+        nc = int(info[0])
+        level = np.empty(nc, dtype=np.int32)
+        order = np.empty(nc, dtype=np.int32)
+        self._check(self.lib.pfv_sweep_info(self._h, info.ctypes.data_as(_lp), _ptr(level, _ip), _ptr(order, _ip)))
+        return {"cells": nc, "levels": int(info[1]), "core_cells": int(info[2]), "core_level": int(info[3]),
+                "level": level, "order": order}
 
     def set_near_null_space(self, B, block_size: int):
         """Near-null space of ``precond="amg_nns"`` for the active system (pfv_set_near_null_space): ``B`` an n x k
@@ -1315,10 +1335,15 @@ class Context:
         return b
 
     def transport_advance(self, c0, n_steps: int, method="bicgstab", rtol=1e-12, maxit=10000, raise_on_fail=True,
-                          device=False):
+                          device=False, precond="jacobi"):
         """``n_steps`` implicit Euler steps of the assembled transport system (pfv_transport_advance).  Returns
-        (c, info); ``device``: ``c0`` is the address of Nc doubles on the device, advanced in place (c is None)."""
+        (c, info); ``device``: ``c0`` is the address of Nc doubles on the device, advanced in place (c is None).
+        ``precond``: "jacobi", or "sweep" -- one substitution in flow order per step when the flux graph is acyclic
+        (no Krylov loop: ``method`` then only names the loop a failed residual check or a cyclic core falls to)."""
         code = {"bicgstab": SOLVE_BICGSTAB, "gmres": SOLVE_GMRES}[method]
+        if precond not in ("jacobi", "sweep"):
+            raise ValueError('precond must be "jacobi" or "sweep"')
+        self._select_precond(precond)
         if device:
             c, pc = None, C.cast(int(c0), _dp)
         else:
@@ -1386,11 +1411,11 @@ class Context:
     def advdiff_advance(self, c0, n_steps: int, method="bicgstab", rtol=1e-12, maxit=10000, precond="amg",
                         raise_on_fail=True, device=False):
         """``n_steps`` implicit Euler steps of the assembled advection-diffusion system (pfv_advdiff_advance) with
-        the preconditioner ``precond`` ("amg" or "jacobi").  Returns (c, info); ``device``: ``c0`` is the address of
-        Nc doubles on the device, advanced in place (c is None)."""
+        the preconditioner ``precond`` ("amg", "jacobi" or "sweep").  Returns (c, info); ``device``: ``c0`` is the
+        address of Nc doubles on the device, advanced in place (c is None)."""
         code = {"bicgstab": SOLVE_BICGSTAB, "gmres": SOLVE_GMRES}[method]
-        if precond not in ("amg", "jacobi"):
-            raise ValueError('precond must be "amg" or "jacobi"')
+        if precond not in ("amg", "jacobi", "sweep"):
+            raise ValueError('precond must be "amg", "jacobi" or "sweep"')
         self._select_precond(precond)
         if device:
             c, pc = None, C.cast(int(c0), _dp)

@@ -135,16 +135,21 @@ class AdvectionDiffusion:
 
     def solve(self, sd, data: dict, accumulation=None, c_old=None, source=None, method: str = "bicgstab",
               precond: str = "amg", rtol: float = 1e-12, maxit: int = 20000, x0=None, restart: int = 0):
-        """Solve ``(diag(accumulation) + A) c = accumulation * c_old + b + source``.  Returns (c, info)."""
+        """Solve ``(diag(accumulation) + A) c = accumulation * c_old + b + source``.  Returns (c, info).
+
+        ``precond="sweep"``: downstream-ordered Gauss-Seidel, one substitution in the flow order of ``darcy_flux``
+        (``context(sd).sweep_info()``).  For this system it is always a preconditioner of ``method``, never exact: the
+        diffusion couples every cell to its downstream neighbours too.  It pays in the advection-dominated regime."""
         self._assemble(sd, data, accumulation, c_old, source)
         return self.context(sd).solve(method=method, rtol=rtol, maxit=maxit, x0=x0, restart=restart, precond=precond)
 
     def advance(self, sd, data: dict, c0, n_steps: int, accumulation, source=None, method: str = "bicgstab",
                 precond: str = "amg", rtol: float = 1e-12, maxit: int = 20000, raise_on_fail: bool = True):
         """``n_steps`` implicit Euler steps from ``c0`` with ``accumulation`` = capacity x volume / dt per cell, all on
-        the device, preconditioned by ``precond`` ("amg": one hierarchy for all steps; "jacobi").  Returns (c_n, info);
+        the device, preconditioned by ``precond`` ("amg": one hierarchy for all steps; "jacobi"; "sweep": the
+        substitution in flow order, built once per flux -- a preconditioner here, see ``solve``).  Returns (c_n, info);
         info["steps_done"] counts the converged steps.  ``context(sd).stats()`` has ``advdiff_iterations`` and
-        ``advdiff_precond_fallbacks`` (steps the AMG-preconditioned solve left to Jacobi-GMRES)."""
+        ``advdiff_precond_fallbacks`` (steps the AMG- or sweep-preconditioned solve left to Jacobi-GMRES)."""
         self._assemble(sd, data, accumulation, None, source)
         return self.context(sd).advdiff_advance(c0, n_steps, method=method, rtol=rtol, maxit=maxit, precond=precond,
                                                 raise_on_fail=raise_on_fail)

@@ -2097,8 +2097,12 @@ static void blockpc_apply(pfv_ctx_impl& c, BlockPc& M, const CsrPattern& P, cons
 // ---- preconditioner handle used by the Krylov loops
 struct AmgNns;  // amg_nns.inc
 static void amg_nns_cycle(pfv_ctx_impl& c, AmgNns& H, size_t l, const double* b, double* x);
+struct Sweep;  // sweep.inc
+static void sweep_apply(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* val, const double* diag,
+                        const double* in, double* out);
 struct Precond {
   Amg* amg = nullptr;          // nullptr: Jacobi
+  const Sweep* sweep = nullptr;  // flow-ordered sweep (PFV_PRECOND_SWEEP; takes precedence; couples through P / val / diag)
   AmgNns* nns = nullptr;       // aggregation AMG with a near-null space (PFV_PRECOND_AMG_NNS)
   const double* diag = nullptr;
   BlockPc* blocks = nullptr;   // block lower-triangular preconditioner (takes precedence)
@@ -2106,7 +2110,9 @@ struct Precond {
   const double* val = nullptr;
 };
 static void precond_apply(pfv_ctx_impl& c, const Precond& M, int64_t n, const double* in, double* out) {
-  if (M.blocks) {
+  if (M.sweep) {
+    sweep_apply(c, *M.sweep, *M.P, M.val, M.diag, in, out);
+  } else if (M.blocks) {
     blockpc_apply(c, *M.blocks, *M.P, M.val, n, in, out);
   } else if (M.nns) {
     amg_nns_cycle(c, *M.nns, 0, in, out);

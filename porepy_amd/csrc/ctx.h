@@ -81,6 +81,7 @@ struct LinSys {
 struct Amg;      // amg.inc
 struct BlockPc;  // amg.inc
 struct AmgNns;   // amg_nns.inc
+struct Sweep;    // sweep.inc
 
 struct pfv_ctx_impl {
   MemPool pool;     // first member: destroyed last, after every buffer has been handed back
@@ -339,6 +340,10 @@ struct pfv_ctx_impl {
   Buf<double> adv_acc, adv_src, adv_c, adv_keep, adv_rhs, adv_diag, adv_bref;
   bool have_adv_acc = false, have_adv_src = false;
   int64_t advdiff_zero_diag = -1;    // first row of S with a zero or NaN diagonal (-1: none)
+
+  // ---- flow-ordered sweep (sweep.inc): levels of the flux graph of the transport / advection-diffusion system -----
+  std::unique_ptr<Sweep> sweep;      // the order and what it was built from (nullptr / !valid: none)
+  const double* transport_q = nullptr;  // [nf] the flux the values of the transport system were assembled with
 
   pfv_stats stats{};
 

@@ -21,6 +21,7 @@ static int rccl_exchange_halo(void* user, double* d_x, void* stream);  // rccl_h
 #include "ad_flux.inc"
 #include "upwind.inc"
 #include "advdiff.inc"
+#include "sweep.inc"
 
 namespace pfv {
 #ifndef PFV_EMULATE
@@ -289,6 +290,8 @@ pfv_status pfv_set_grid(pfv_ctx* h, int nd, int64_t nc, int64_t nf, int64_t nn, 
     h->transport_zero_diag = -1;
     h->have_advdiff = h->have_adv_bD = h->have_adv_acc = h->have_adv_src = false;
     h->advdiff_zero_diag = -1;
+    h->sweep.reset();
+    h->transport_q = nullptr;
   });
 }
 
@@ -829,6 +832,18 @@ static void upwind_drop_transport(pfv_ctx* h) {
   h->have_transport = false;
   h->filled[PFV_MAT_TRANSPORT_SYSTEM] = false;
   h->transport_zero_diag = -1;
+  if (h->sweep && h->sweep->for_system == PFV_MAT_TRANSPORT_SYSTEM) h->sweep->valid = false;
+}
+
+// An assembly of system `which` with the flux d_q: a flow order built for another system, or for a flux with other
+// edges, is stale.  Costs nothing unless a sweep solve has built an order on this handle.
+static void sweep_note_assembly(pfv_ctx* h, int which, const double* d_q) {
+  if (!h->sweep || !h->sweep->valid) return;
+  if (h->sweep->for_system != which || !pfv::sweep_same_edges(*h, *h->sweep, d_q)) h->sweep->valid = false;
+}
+
+static bool transport_is_active(const pfv_ctx* h) {
+  return h->have_transport && h->active.valid && h->active.val == h->val[PFV_MAT_TRANSPORT_SYSTEM].p;
 }
 
 pfv_status pfv_mpfa_face_flux(pfv_ctx* h, const double* p, const double* bc_values, const double* vector_source,
@@ -929,6 +944,8 @@ pfv_status pfv_upwind_assemble(pfv_ctx* h, const double* q, const double* bc_val
     pfv::upwind_assemble(*h, d_q, d_bc, h->have_acc_t ? h->acc_t.p : nullptr, d_cold,
                          h->have_src_t ? h->src_t.p : nullptr);
     h->stats.transport_assemble_ms = tm.stop(s);
+    h->transport_q = d_q;
+    sweep_note_assembly(h, PFV_MAT_TRANSPORT_SYSTEM, d_q);
     if (bound_rhs_out) {
       if (h->vectors_on_device) pfv::be_d2d(bound_rhs_out, h->bref_t.p, nc * sizeof(double), s);
       else be_d2h(bound_rhs_out, h->bref_t.p, nc * sizeof(double), s);
@@ -973,8 +990,9 @@ pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rto
   const bool caller_on_device = h->vectors_on_device;
   const int precond = h->precond;
   h->vectors_on_device = true;  // the state stays in c_t between the steps
-  h->precond = PFV_PRECOND_JACOBI;
-  int64_t iters = 0, retries = 0;
+  h->precond = precond == PFV_PRECOND_SWEEP ? PFV_PRECOND_SWEEP : PFV_PRECOND_JACOBI;
+  int64_t iters = 0, retries = 0, direct = 0, direct_fb = 0;
+  double order_ms = 0.0;
   const size_t nbytes = (size_t)h->nc * sizeof(double);
   for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
     // BiCGStab can break down (rho = (r_hat, r) = 0: the residual turns NaN) where the first residual sits in cells
@@ -988,12 +1006,17 @@ pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rto
     pfv_solve_info info{};
     st = pfv_solve(h, method, rtol, maxit, 0, h->c_t.p, h->c_t.p, &info);
     iters += info.iterations;
+    direct += h->stats.sweep_direct_steps;
+    direct_fb += h->stats.sweep_direct_fallbacks;
+    order_ms += h->stats.sweep_order_ms;
     if (st == PFV_ERR_NOT_CONVERGED && method == PFV_SOLVE_BICGSTAB && !(info.rel_residual == info.rel_residual)) {
       st = guarded(h, [&] { pfv::be_d2d(h->c_t.p, h->c_keep.p, nbytes, h->stream); });
       if (st != PFV_OK) break;
       ++retries;
       st = pfv_solve(h, PFV_SOLVE_GMRES, rtol, maxit, 0, h->c_t.p, h->c_t.p, &info);
       iters += info.iterations;
+      direct += h->stats.sweep_direct_steps;
+      direct_fb += h->stats.sweep_direct_fallbacks;
     }
     if (last) *last = info;
     if (st == PFV_OK && steps_done) ++*steps_done;
@@ -1006,6 +1029,9 @@ pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rto
     tm.reset();
     h->stats.transport_iterations = iters;
     h->stats.transport_gmres_retries = retries;
+    h->stats.sweep_direct_steps = direct;
+    h->stats.sweep_direct_fallbacks = direct_fb;
+    h->stats.sweep_order_ms = order_ms;
     const size_t nc = (size_t)h->nc;
     if (h->vectors_on_device) pfv::be_d2d(c, h->c_t.p, nc * sizeof(double), h->stream);
     else be_d2h(c, h->c_t.p, nc * sizeof(double), h->stream);
@@ -1092,6 +1118,7 @@ pfv_status pfv_advdiff_assemble(pfv_ctx* h, const double* q, double flux_scale, 
     pfv::advdiff_refresh(*h, d_q, flux_scale, h->adv_bc.p, h->have_adv_acc ? h->adv_acc.p : nullptr, d_cold,
                          h->have_adv_src ? h->adv_src.p : nullptr);
     h->stats.advdiff_assemble_ms = tm.stop(s);
+    sweep_note_assembly(h, PFV_MAT_ADVDIFF_SYSTEM, d_q);
     if (bound_rhs_out) {
       if (h->vectors_on_device) pfv::be_d2d(bound_rhs_out, h->adv_bref.p, nc * sizeof(double), s);
       else be_d2h(bound_rhs_out, h->adv_bref.p, nc * sizeof(double), s);
@@ -1125,8 +1152,8 @@ pfv_status pfv_advdiff_advance(pfv_ctx* h, int n_steps, int method, double rtol,
     require(n_steps >= 0 && c != nullptr, "bad argument");
     require(method == PFV_SOLVE_BICGSTAB || method == PFV_SOLVE_GMRES,
             "method must be PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES (the matrix is not symmetric)");
-    require(h->precond == PFV_PRECOND_JACOBI || h->precond == PFV_PRECOND_AMG,
-            "the advection-diffusion step takes PFV_PRECOND_JACOBI or PFV_PRECOND_AMG");
+    require(h->precond == PFV_PRECOND_JACOBI || h->precond == PFV_PRECOND_AMG || h->precond == PFV_PRECOND_SWEEP,
+            "the advection-diffusion step takes PFV_PRECOND_JACOBI, PFV_PRECOND_AMG or PFV_PRECOND_SWEEP");
     vec_in(h, h->adv_c.ensure((size_t)h->nc), c, (size_t)h->nc);
     tm = std::make_unique<pfv::Timer>();
     tm->start(h->stream);
@@ -1136,6 +1163,7 @@ pfv_status pfv_advdiff_advance(pfv_ctx* h, int n_steps, int method, double rtol,
   const int precond = h->precond;
   h->vectors_on_device = true;  // the state stays in adv_c between the steps
   int64_t iters = 0, retries = 0, fallbacks = 0;
+  double order_ms = 0.0;
   const size_t nbytes = (size_t)h->nc * sizeof(double);
   for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
     st = guarded(h, [&] {
@@ -1146,6 +1174,7 @@ pfv_status pfv_advdiff_advance(pfv_ctx* h, int n_steps, int method, double rtol,
     pfv_solve_info info{};
     st = pfv_solve(h, method, rtol, maxit, 0, h->adv_c.p, h->adv_c.p, &info);
     iters += info.iterations;
+    order_ms += h->stats.sweep_order_ms;
     // BiCGStab breakdown (NaN residual): again with GMRES from the kept state, as pfv_transport_advance does
     if (st == PFV_ERR_NOT_CONVERGED && method == PFV_SOLVE_BICGSTAB && !(info.rel_residual == info.rel_residual)) {
       st = guarded(h, [&] { pfv::be_d2d(h->adv_c.p, h->adv_keep.p, nbytes, h->stream); });
@@ -1154,8 +1183,8 @@ pfv_status pfv_advdiff_advance(pfv_ctx* h, int n_steps, int method, double rtol,
       st = pfv_solve(h, PFV_SOLVE_GMRES, rtol, maxit, 0, h->adv_c.p, h->adv_c.p, &info);
       iters += info.iterations;
     }
-    // the AMG-preconditioned solve did not get there: the step again with Jacobi-GMRES from the kept state
-    if (st == PFV_ERR_NOT_CONVERGED && precond == PFV_PRECOND_AMG) {
+    // the AMG- or sweep-preconditioned solve did not get there: the step again with Jacobi-GMRES from the kept state
+    if (st == PFV_ERR_NOT_CONVERGED && (precond == PFV_PRECOND_AMG || precond == PFV_PRECOND_SWEEP)) {
       st = guarded(h, [&] { pfv::be_d2d(h->adv_c.p, h->adv_keep.p, nbytes, h->stream); });
       if (st != PFV_OK) break;
       ++fallbacks;
@@ -1176,6 +1205,7 @@ pfv_status pfv_advdiff_advance(pfv_ctx* h, int n_steps, int method, double rtol,
     h->stats.advdiff_iterations = iters;
     h->stats.advdiff_gmres_retries = retries;
     h->stats.advdiff_precond_fallbacks = fallbacks;
+    if (precond == PFV_PRECOND_SWEEP) h->stats.sweep_order_ms = order_ms;
     const size_t nc = (size_t)h->nc;
     if (h->vectors_on_device) pfv::be_d2d(c, h->adv_c.p, nc * sizeof(double), h->stream);
     else be_d2h(c, h->adv_c.p, nc * sizeof(double), h->stream);
@@ -1866,6 +1896,8 @@ pfv_status pfv_set_system(pfv_ctx* h, int64_t n, const int32_t* indptr, const in
 
 pfv_status pfv_amg_setup(pfv_ctx* h, int64_t n_own) {
   return guarded(h, [&] {
+    if (h->precond == PFV_PRECOND_SWEEP)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "PFV_PRECOND_SWEEP has no AMG hierarchy and no sharded form");
     if (h->precond == PFV_PRECOND_AMG_NNS)
       throw pfv::Error(PFV_ERR_UNSUPPORTED, "PFV_PRECOND_AMG_NNS has no sharded form: pfv_set_preconditioner(PFV_PRECOND_AMG) "
                                             "or PFV_PRECOND_JACOBI for sharded solves");
@@ -1932,6 +1964,8 @@ pfv_status pfv_amg_setup_sharded(pfv_ctx* h, int64_t n_own, const pfv_shard_hook
                                  int n_peers, const int32_t* peers, const int64_t* send_ptr,
                                  const int32_t* send_idx, const int64_t* recv_ptr, const int32_t* recv_pos) {
   return guarded(h, [&] {
+    if (h->precond == PFV_PRECOND_SWEEP)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "PFV_PRECOND_SWEEP has no AMG hierarchy and no sharded form");
     if (h->precond == PFV_PRECOND_AMG_NNS)
       throw pfv::Error(PFV_ERR_UNSUPPORTED, "PFV_PRECOND_AMG_NNS has no sharded form: pfv_set_preconditioner(PFV_PRECOND_AMG) "
                                             "or PFV_PRECOND_JACOBI for sharded solves");
@@ -2010,7 +2044,7 @@ pfv_status pfv_amg_apply_device(pfv_ctx* h, const double* d_r, double* d_z) {
 pfv_status pfv_set_preconditioner(pfv_ctx* h, int kind) {
   return guarded(h, [&] {
     require(kind == PFV_PRECOND_JACOBI || kind == PFV_PRECOND_AMG || (kind == PFV_PRECOND_BLOCK && h->block_pc) ||
-                (kind == PFV_PRECOND_AMG_NNS && h->nns_k > 0),
+                (kind == PFV_PRECOND_AMG_NNS && h->nns_k > 0) || kind == PFV_PRECOND_SWEEP,
             "unknown preconditioner (PFV_PRECOND_BLOCK: pfv_set_block_preconditioner first; PFV_PRECOND_AMG_NNS: "
             "pfv_set_near_null_space first)");
     h->precond = kind;
@@ -2254,6 +2288,24 @@ pfv_status pfv_solve(pfv_ctx* h, int method, double rtol, int maxit, int restart
     require(method == PFV_SOLVE_CG || method == PFV_SOLVE_BICGSTAB || method == PFV_SOLVE_GMRES,
             "method must be PFV_SOLVE_CG, PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES");
     require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
+    const bool sweep_transport = h->precond == PFV_PRECOND_SWEEP && transport_is_active(h);
+    const bool sweep_advdiff = h->precond == PFV_PRECOND_SWEEP && !sweep_transport && advdiff_is_active(h);
+    if (h->precond == PFV_PRECOND_SWEEP && !sweep_transport && !sweep_advdiff)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "PFV_PRECOND_SWEEP applies to the transport system (pfv_upwind_assemble) and to "
+                                            "the advection-diffusion system (pfv_advdiff_assemble) of the handle only: the "
+                                            "active system is neither");
+    h->stats.sweep_levels = h->stats.sweep_core_cells = h->stats.sweep_launches = 0;
+    h->stats.sweep_direct_steps = h->stats.sweep_direct_fallbacks = 0;
+    h->stats.sweep_order_ms = 0.0;
+    if (h->precond == PFV_PRECOND_SWEEP) {
+      // the flow order is a function of the flux alone: built by the first solve that needs it, before the system is judged
+      const int which = sweep_transport ? PFV_MAT_TRANSPORT_SYSTEM : PFV_MAT_ADVDIFF_SYSTEM;
+      if (!h->sweep) h->sweep = std::make_unique<pfv::Sweep>();
+      if (!h->sweep->valid || h->sweep->for_system != which) {
+        pfv::sweep_build_order(*h, *h->sweep, sweep_transport ? h->transport_q : h->adv_q.p, which);
+        h->stats.sweep_order_ms = h->sweep->order_ms;
+      }
+    }
     if (h->have_transport && h->active.val == h->val[PFV_MAT_TRANSPORT_SYSTEM].p && h->transport_zero_diag >= 0)
       throw pfv::Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(h->transport_zero_diag) +
                                                 " of the transport system (a cell without outflow and without an "
@@ -2326,12 +2378,32 @@ pfv_status pfv_solve(pfv_ctx* h, int method, double rtol, int maxit, int restart
       M.val = sys.val;
       M.diag = sys.diag;
       Mp = &M;
+    } else if (h->precond == PFV_PRECOND_SWEEP) {
+      pfv::Sweep& sw = *h->sweep;
+      pfv::sweep_set_numbering(*h, sw, permuted);
+      pfv::sweep_make_plan(sw);
+      h->stats.sweep_levels = sw.nlev;
+      h->stats.sweep_core_cells = sw.n_core;
+      h->stats.sweep_launches = (int64_t)sw.plan.size();
+      M.sweep = &sw;
+      M.P = sys.P;
+      M.val = sys.val;
+      M.diag = sys.diag;
+      Mp = &M;
     }
+    const bool sweep_direct = M.sweep && sweep_transport && M.sweep->n_core == 0;
     const long long launches_before_loop = pfv::launch_counter().load(std::memory_order_relaxed);
     h->stats.amg_setup_launches = (int64_t)(launches_before_loop - launches_before_setup);
+    if (sweep_direct) {
+      bool fell_back = false;
+      res = pfv::sweep_direct_solve(*h, sys, M, rtol, maxit, restart, dxs, fell_back);
+      h->stats.sweep_direct_steps = 1;
+      h->stats.sweep_direct_fallbacks = fell_back ? 1 : 0;
+    } else {
     res = method == PFV_SOLVE_GMRES
               ? pfv::gmres_solve(*h, sys, rtol, maxit, restart, dxs, x0 == nullptr, Mp)
               : pfv::krylov_solve(*h, sys, method, rtol, maxit, dxs, x0 == nullptr, Mp);
+    }
     if (M.amg && x0 == nullptr) h->amg->note_iterations(res.iterations, rtol, method, res.converged);
     h->stats.solve_launches = (int64_t)(pfv::launch_counter().load(std::memory_order_relaxed) - launches_before_loop);
     if (permuted) pfv::permute_vector(*h, (int64_t)n, h->active_bs, dxs, dx, false);
@@ -2360,6 +2432,8 @@ pfv_status pfv_solve_sharded(pfv_ctx* h, int method, double rtol, int maxit, int
     if (h->precond == PFV_PRECOND_AMG_NNS)
       throw pfv::Error(PFV_ERR_UNSUPPORTED, "PFV_PRECOND_AMG_NNS has no sharded form: pfv_set_preconditioner(PFV_PRECOND_AMG) "
                                             "or PFV_PRECOND_JACOBI for sharded solves");
+    if (h->precond == PFV_PRECOND_SWEEP)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "PFV_PRECOND_SWEEP has no AMG hierarchy and no sharded form");
     require(h->active.valid, "assemble first");
     require(hooks && hooks->exchange_halo && hooks->allreduce_sum, "both hooks are required");
     require(d_work && d_x_owned, "work space and x are required");
@@ -2470,6 +2544,21 @@ pfv_status pfv_solve_sharded(pfv_ctx* h, int method, double rtol, int maxit, int
     return PFV_ERR_NOT_CONVERGED;
   }
   return st;
+}
+
+pfv_status pfv_sweep_info(pfv_ctx* h, int64_t info[4], int32_t* level, int32_t* order) {
+  return guarded(h, [&] {
+    require(h->sweep && h->sweep->valid, "no flow order on the handle (a solve with PFV_PRECOND_SWEEP builds it)");
+    const pfv::Sweep& sw = *h->sweep;
+    if (info) {
+      info[0] = sw.nc;
+      info[1] = sw.nlev;
+      info[2] = sw.n_core;
+      info[3] = sw.core_level;
+    }
+    if (level) be_d2h(level, sw.level.p, sizeof(int32_t) * (size_t)sw.nc, h->stream);
+    if (order) be_d2h(order, sw.order.p, sizeof(int32_t) * (size_t)sw.nc, h->stream);
+  });
 }
 
 pfv_status pfv_get_stats(pfv_ctx* h, pfv_stats* out) {

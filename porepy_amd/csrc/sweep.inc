@@ -1,0 +1,358 @@
+// sweep.inc — the flow order of a face flux and the substitution along it (PFV_PRECOND_SWEEP).
+//
+//   order   An interior face with q != 0 (not NaN) is an edge upstream cell -> downstream cell, the upstream side as in
+//           upwind_discretize (q >= 0: the cell with cell_faces sign +1).  Forward peel: level 0 = cells without an
+//           incoming edge, level l + 1 = cells whose upstream cells all have level <= l (the longest upstream path).
+//           Backward peel of the rest: cells without an edge into the remaining set, pass by pass; they get the highest
+//           levels, the first pass the highest.  What both leave is the cyclic core: one level between the two.
+//           Both peels run on a frontier worklist with integer degree counters: a pass touches the faces of its
+//           frontier only, and the host reads one integer per pass (the new tail of the worklist).  The levels do not
+//           depend on the order in which the atomics land; the order is a stable radix sort of the cells by level.
+//   sweep   M = diagonal of S + the entries S[i,j] with level[j] < level[i].  Level by level, one thread per row:
+//           z[i] = (r[i] - sum_{level[j] < level[i]} S[i,j] z[j]) / S[i,i], the sum in stored order.  Levels follow each
+//           other by launch order on the handle's stream; a run of consecutive small levels is one launch of a single
+//           workgroup that separates them with __syncthreads().  No workgroup waits for another.
+//
+// No floating-point atomics; every sum has a fixed order.
+namespace pfv {
+
+struct Sweep {
+  bool valid = false;
+  int for_system = -1;           // PFV_MAT_TRANSPORT_SYSTEM or PFV_MAT_ADVDIFF_SYSTEM: whose flux the order was built from
+  int64_t nc = 0, n_core = 0;
+  int nlev = 0, core_level = -1;
+  Buf<int8_t> dir;               // [nf] +1 / -1: edge from the cell on that side of the face; 0: no edge
+  Buf<int32_t> level, order;     // caller's cell numbering
+  Buf<int32_t> level_s, order_s; // the solve's numbering (reorder.inc), when that differs
+  int numbering = -1;            // which numbering level_s / order_s hold (-1: none, 1: the renumbered one)
+  std::vector<int32_t> h_lptr;   // [nlev + 1] first position of every level in order
+  Buf<int32_t> lptr;             // the same on the device
+  struct Seg { int l0, l1; };    // levels [l0, l1) of one launch (l1 - l0 > 1: a single workgroup takes the run)
+  std::vector<Seg> plan;
+  int plan_key = -1;
+  double order_ms = 0.0;
+  const int32_t* lev(bool permuted) const { return permuted ? level_s.p : level.p; }
+  const int32_t* ord(bool permuted) const { return permuted ? order_s.p : order.p; }
+  bool permuted = false;         // numbering of the system the running solve works on
+};
+
+// the edge of every face for the flux q
+static void sweep_classify(pfv_ctx_impl& c, const double* q, int8_t* dir) {
+  const int64_t nf = c.nf;
+  const int32_t* side = c.upw_side;
+  parallel_for(c.stream, nf, PFV_LAMBDA(int64_t f) {
+    const double qf = q[f];
+    int8_t d = 0;
+    if (side[f] >= 0 && side[nf + f] >= 0 && qf == qf && qf != 0.0) d = qf > 0.0 ? 1 : -1;
+    dir[f] = d;
+  });
+}
+
+// does the flux q have the edges the order was built from?
+static bool sweep_same_edges(pfv_ctx_impl& c, const Sweep& sw, const double* q) {
+  stream_t s = c.stream;
+  const int64_t nf = c.nf;
+  const int32_t* side = c.upw_side;
+  const int8_t* dir = sw.dir;
+  Buf<int32_t> flag_;
+  int32_t* flag = flag_.ensure(1);
+  be_memset(flag, 0, sizeof(int32_t), s);
+  parallel_for(s, nf, PFV_LAMBDA(int64_t f) {
+    const double qf = q[f];
+    int8_t d = 0;
+    if (side[f] >= 0 && side[nf + f] >= 0 && qf == qf && qf != 0.0) d = qf > 0.0 ? 1 : -1;
+    if (d != dir[f]) atomic_max_i32(flag, 1);
+  });
+  return read_scalar<int32_t>(s, flag) == 0;
+}
+
+// stable sort of the cells by level (ascending index inside a level)
+static void sweep_sort(pfv_ctx_impl& c, int64_t nc, int nlev, const int32_t* lev, int32_t* order) {
+  stream_t s = c.stream;
+  Buf<uint32_t> kin_, kout_;
+  Buf<int32_t> vin_;
+  uint32_t* kin = kin_.ensure(nc);
+  int32_t* vin = vin_.ensure(nc);
+  parallel_for(s, nc, PFV_LAMBDA(int64_t i) {
+    kin[i] = (uint32_t)lev[i];
+    vin[i] = (int32_t)i;
+  });
+  int bits = 1;
+  while ((int64_t(1) << bits) < nlev) ++bits;
+  sort_pairs(s, c.scratch, kin, kout_.ensure(nc), vin, order, (size_t)nc, bits);
+  be_sync(s);  // (the key buffers are freed on return)
+}
+
+static void sweep_build_order(pfv_ctx_impl& c, Sweep& sw, const double* q, int for_system) {
+  stream_t s = c.stream;
+  Timer tm;
+  tm.start(s);
+  upwind_face_cells(c);
+  const int64_t nc = c.nc, nf = c.nf;
+  const int32_t* cf_ptr = c.cf_ptr;
+  const int32_t* cf_idx = c.cf_idx;
+  const int32_t* side = c.upw_side;
+  sw.valid = false;
+  sw.numbering = -1;
+  sw.plan_key = -1;
+  int8_t* dir = sw.dir.ensure(nf);
+  int32_t* lev = sw.level.ensure(nc);
+  Buf<int32_t> indeg_, outdeg_, wl_, blev_, tail_;
+  int32_t* indeg = indeg_.ensure(nc);
+  int32_t* outdeg = outdeg_.ensure(nc);
+  int32_t* wl = wl_.ensure(nc);      // every cell enters the worklist at most once: a pass is a range of it
+  int32_t* blev = blev_.ensure(nc);  // pass of the backward peel that removed the cell (-1: none)
+  int32_t* tail = tail_.ensure(1);
+  be_memset(indeg, 0, sizeof(int32_t) * (size_t)nc, s);
+  be_memset(lev, 0xff, sizeof(int32_t) * (size_t)nc, s);
+  be_memset(blev, 0xff, sizeof(int32_t) * (size_t)nc, s);
+  be_memset(tail, 0, sizeof(int32_t), s);
+  sweep_classify(c, q, dir);
+  parallel_for(s, nf, PFV_LAMBDA(int64_t f) {
+    const int d = dir[f];
+    if (d) atomic_add_i32(indeg + (d > 0 ? side[nf + f] : side[f]), 1);
+  });
+  // ---- forward peel
+  parallel_for(s, nc, PFV_LAMBDA(int64_t i) {
+    if (indeg[i] == 0) {
+      lev[i] = 0;
+      wl[atomic_fetch_add_i32(tail, 1)] = (int32_t)i;
+    }
+  });
+  std::vector<int32_t> fwd, bwd;  // cells per pass
+  int32_t begin = 0, end = read_scalar<int32_t>(s, tail);
+  while (end > begin) {
+    fwd.push_back(end - begin);
+    const int32_t next = (int32_t)fwd.size(), b0 = begin;
+    parallel_for(s, end - begin, PFV_LAMBDA(int64_t k) {
+      const int32_t cell = wl[b0 + k];
+      for (int e = cf_ptr[cell]; e < cf_ptr[cell + 1]; ++e) {
+        const int f = cf_idx[e];
+        const int d = dir[f];
+        if (!d) continue;
+        const int32_t up = d > 0 ? side[f] : side[nf + f];
+        if (up != cell) continue;
+        const int32_t dn = d > 0 ? side[nf + f] : side[f];
+        if (atomic_fetch_add_i32(indeg + dn, -1) == 1) {  // the last upstream cell of dn
+          lev[dn] = next;
+          wl[atomic_fetch_add_i32(tail, 1)] = dn;
+        }
+      }
+    });
+    begin = end;
+    end = read_scalar<int32_t>(s, tail);
+  }
+  const int nfwd = (int)fwd.size();
+  // ---- backward peel of the cells the forward peel left (lev < 0)
+  if (end < nc) {
+    parallel_for(s, nc, PFV_LAMBDA(int64_t i) {
+      if (lev[i] >= 0) return;
+      int m = 0;
+      for (int e = cf_ptr[i]; e < cf_ptr[i + 1]; ++e) {
+        const int f = cf_idx[e];
+        const int d = dir[f];
+        if (!d) continue;
+        const int32_t up = d > 0 ? side[f] : side[nf + f];
+        if (up != (int32_t)i) continue;
+        const int32_t dn = d > 0 ? side[nf + f] : side[f];
+        if (lev[dn] < 0) ++m;
+      }
+      outdeg[i] = m;
+      if (m == 0) {
+        blev[i] = 0;
+        wl[atomic_fetch_add_i32(tail, 1)] = (int32_t)i;
+      }
+    });
+    begin = end;
+    end = read_scalar<int32_t>(s, tail);
+    while (end > begin) {
+      bwd.push_back(end - begin);
+      const int32_t next = (int32_t)bwd.size(), b0 = begin;
+      parallel_for(s, end - begin, PFV_LAMBDA(int64_t k) {
+        const int32_t cell = wl[b0 + k];
+        for (int e = cf_ptr[cell]; e < cf_ptr[cell + 1]; ++e) {
+          const int f = cf_idx[e];
+          const int d = dir[f];
+          if (!d) continue;
+          const int32_t dn = d > 0 ? side[nf + f] : side[f];
+          if (dn != cell) continue;
+          const int32_t up = d > 0 ? side[f] : side[nf + f];
+          if (lev[up] >= 0) continue;  // (not in the remaining set)
+          if (atomic_fetch_add_i32(outdeg + up, -1) == 1) {  // the last edge of up into the remaining set
+            blev[up] = next;
+            wl[atomic_fetch_add_i32(tail, 1)] = up;
+          }
+        }
+      });
+      begin = end;
+      end = read_scalar<int32_t>(s, tail);
+    }
+  }
+  const int nbwd = (int)bwd.size();
+  sw.nc = nc;
+  sw.n_core = nc - end;
+  const int has_core = sw.n_core > 0 ? 1 : 0;
+  sw.core_level = has_core ? nfwd : -1;
+  sw.nlev = nfwd + has_core + nbwd;
+  if (has_core || nbwd) {
+    parallel_for(s, nc, PFV_LAMBDA(int64_t i) {
+      if (lev[i] >= 0) return;
+      lev[i] = blev[i] >= 0 ? nfwd + has_core + (nbwd - 1 - blev[i]) : nfwd;
+    });
+  }
+  sw.h_lptr.assign(1, 0);
+  for (int32_t m : fwd) sw.h_lptr.push_back(sw.h_lptr.back() + m);
+  if (has_core) sw.h_lptr.push_back(sw.h_lptr.back() + (int32_t)sw.n_core);
+  for (int k = nbwd - 1; k >= 0; --k) sw.h_lptr.push_back(sw.h_lptr.back() + bwd[(size_t)k]);
+  be_h2d(sw.lptr.ensure((size_t)sw.nlev + 1), sw.h_lptr.data(), sizeof(int32_t) * ((size_t)sw.nlev + 1), s);
+  sweep_sort(c, nc, sw.nlev, lev, sw.order.ensure(nc));
+  sw.for_system = for_system;
+  sw.valid = true;
+  sw.order_ms = tm.stop(s);
+}
+
+// level[] / order[] in the numbering the Krylov loop works in
+static void sweep_set_numbering(pfv_ctx_impl& c, Sweep& sw, bool permuted) {
+  sw.permuted = permuted;
+  if (!permuted || sw.numbering == 1) return;
+  const int64_t nc = sw.nc;
+  const int32_t* perm = c.cell_perm;
+  const int32_t* lev = sw.level;
+  int32_t* ls = sw.level_s.ensure(nc);
+  parallel_for(c.stream, nc, PFV_LAMBDA(int64_t r) { ls[r] = lev[perm[r]]; });
+  sweep_sort(c, nc, sw.nlev, ls, sw.order_s.ensure(nc));
+  sw.numbering = 1;
+}
+
+// which levels go into which launch.  PFV_SWEEP_MERGE=0: one launch per level; else runs of consecutive levels of at
+// most PFV_SWEEP_MERGE_ROWS rows (default 512) are handed to one workgroup each
+static void sweep_make_plan(Sweep& sw) {
+  const int merge = env_int("PFV_SWEEP_MERGE", 1) != 0 ? 1 : 0;
+  const int rows = std::max(1, std::min(env_int("PFV_SWEEP_MERGE_ROWS", 512), 1 << 20));
+  const int key = merge ? rows : 0;
+  if (sw.plan_key == key) return;
+  sw.plan.clear();
+  for (int l = 0; l < sw.nlev; ++l) {
+    const bool small = merge && sw.h_lptr[(size_t)l + 1] - sw.h_lptr[(size_t)l] <= rows;
+    const bool prev_small = merge && l > 0 && sw.h_lptr[(size_t)l] - sw.h_lptr[(size_t)l - 1] <= rows;
+    if (small && prev_small) sw.plan.back().l1 = l + 1;
+    else sw.plan.push_back({l, l + 1});
+  }
+  sw.plan_key = key;
+}
+
+// one row of the substitution (shared by both launch forms: they give the same bits)
+PFV_FN void sweep_row(int32_t i, const int32_t* ip, const int32_t* ix, const double* val, const double* diag,
+                      const int32_t* lev, const double* r, double* z) {
+  const int32_t li = lev[i];
+  double sum = 0.0;
+  for (int e = ip[i]; e < ip[i + 1]; ++e) {
+    const int32_t j = ix[e];
+    if (lev[j] < li) sum += val[e] * z[j];
+  }
+  z[i] = (r[i] - sum) / diag[i];
+}
+
+static void sweep_apply(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* val, const double* diag,
+                        const double* in, double* out) {
+  stream_t s = c.stream;
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* lev = sw.lev(sw.permuted);
+  const int32_t* ord = sw.ord(sw.permuted);
+  const int32_t* lp = sw.lptr;
+  for (const Sweep::Seg& g : sw.plan) {
+    if (g.l1 - g.l0 == 1) {
+      const int32_t a = sw.h_lptr[(size_t)g.l0], m = sw.h_lptr[(size_t)g.l1] - a;
+      parallel_for(s, m, PFV_LAMBDA(int64_t k) { sweep_row(ord[a + k], ip, ix, val, diag, lev, in, out); });
+    } else {
+      const int l0 = g.l0, l1 = g.l1;
+      block_for<256>(s, 1, 0, PFV_LAMBDA(const WaveCtx& w) {
+        for (int l = l0; l < l1; ++l) {
+          const int32_t a = lp[l], m = lp[l + 1] - a;
+          PFV_LANES(k, m) sweep_row(ord[a + k], ip, ix, val, diag, lev, in, out);
+          w.sync();  // (the next level reads what this one wrote: same workgroup, same CU)
+        }
+      });
+    }
+  }
+}
+
+// out[0] = (b, b), out[1] = (b - t, b - t): fixed partition, fixed reduction order
+static void sweep_residual_norms(pfv_ctx_impl& c, int64_t n, const double* b, const double* t, double* out) {
+  stream_t s = c.stream;
+  const int nb = (int)std::min<int64_t>(kGmresBlocks, (n + 2047) / 2048);
+  double* partial = c.red.ensure(2 * (size_t)kGmresBlocks + 64);
+  block_for<256>(s, nb, 2 * 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& wc) {
+    double* sh = reinterpret_cast<double*>(wc.lds);
+    const int64_t blk = wc.item;
+    const int64_t lo = n * blk / nb, hi = n * (blk + 1) / nb;
+    double a0 = 0.0, a1 = 0.0;
+    for (int64_t i = lo + wc.lane; i < hi; i += wc.width) {
+      const double bi = b[i], ri = bi - t[i];
+      a0 += bi * bi;
+      a1 += ri * ri;
+    }
+    sh[wc.lane] = a0;
+    sh[wc.width + wc.lane] = a1;
+    wc.sync();
+    for (int o = wc.width >> 1; o > 0; o >>= 1) {
+      if (wc.lane < o) {
+        sh[wc.lane] += sh[wc.lane + o];
+        sh[wc.width + wc.lane] += sh[wc.width + wc.lane + o];
+      }
+      wc.sync();
+    }
+    if (wc.lane0()) {
+      partial[blk] = sh[0];
+      partial[nb + blk] = sh[wc.width];
+    }
+    wc.sync();
+  });
+  block_for<256>(s, 2, 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& wc) {
+    double* sh = reinterpret_cast<double*>(wc.lds);
+    const int64_t k = wc.item;
+    double a = 0.0;
+    for (int i = wc.lane; i < nb; i += wc.width) a += partial[k * nb + i];
+    sh[wc.lane] = a;
+    wc.sync();
+    for (int o = wc.width >> 1; o > 0; o >>= 1) {
+      if (wc.lane < o) sh[wc.lane] += sh[wc.lane + o];
+      wc.sync();
+    }
+    if (wc.lane0()) out[k] = sh[0];
+    wc.sync();
+  });
+}
+
+// The direct solve of the transport system of an acyclic flux: x = M^-1 b with M = S, then the true residual.  Should
+// the check fail (a flux array in the assembly that disagrees with the discretization's, NaN entries), GMRES
+// preconditioned by the sweep goes on from that x.
+static SolveResult sweep_direct_solve(pfv_ctx_impl& c, const LinSys& sys, const Precond& M, double rtol, int maxit,
+                                      int restart, double* d_x, bool& fell_back) {
+  stream_t s = c.stream;
+  const int64_t n = sys.n;
+  SolveResult res;
+  fell_back = false;
+  precond_apply(c, M, n, sys.rhs, d_x);
+  double* t = c.kry[6].ensure(n);
+  double* nrm = c.kry[7].ensure(2);
+  sys_spmv(c, sys, d_x, t);
+  sweep_residual_norms(c, n, sys.rhs, t, nrm);
+  double h[2];
+  be_d2h(h, nrm, sizeof(h), s);
+  res.iterations = 1;
+  if (!(h[0] > 0.0)) {  // b = 0 -> x = 0 (what the sweep has left)
+    res.converged = h[0] == 0.0;
+    return res;
+  }
+  res.relres = std::sqrt(h[1] / h[0]);
+  res.converged = h[1] <= rtol * rtol * h[0];
+  if (res.converged) return res;
+  fell_back = true;
+  SolveResult g = gmres_solve(c, sys, rtol, maxit, restart, d_x, false, &M);
+  g.iterations += 1;
+  return g;
+}
+
+}  // namespace pfv

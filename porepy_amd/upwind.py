@@ -155,19 +155,28 @@ class Upwind:
 
         The matrix of an acyclic flow field is triangular up to a permutation; BiCGStab (the default) breaks down on
         it when the right-hand side sits in cells nothing flows back into -- injection into a field at rest, in any
-        dimension.  ``method="gmres"`` solves those; ``advance`` switches by itself."""
+        dimension.  ``method="gmres"`` solves those; ``advance`` switches by itself.
+
+        ``precond="sweep"``: one substitution in flow order (``context(sd).sweep_info()``).  When the flux graph is
+        acyclic it is exact -- the solve is one sweep and one residual check, ``info["iterations"] == 1``, whatever
+        ``method`` says.  Where the flux has cycles (``stats()["sweep_core_cells"] > 0``) the cells of the cyclic core
+        are treated by Jacobi against their upstream values and the sweep preconditions ``method``."""
         self._assemble(sd, data, accumulation, c_old, source)
         return self.context(sd).solve(method=method, rtol=rtol, maxit=maxit, x0=x0, restart=restart, precond=precond)
 
     def advance(self, sd, data: dict, c0, n_steps: int, accumulation, source=None, method: str = "bicgstab",
-                rtol: float = 1e-12, maxit: int = 20000, raise_on_fail: bool = True):
+                rtol: float = 1e-12, maxit: int = 20000, raise_on_fail: bool = True, precond: str = "jacobi"):
         """``n_steps`` implicit Euler steps from ``c0`` with ``accumulation`` = porosity x volume / dt per cell, all
         on the device.  Returns (c_n, info); info["steps_done"] counts the converged steps.  A step whose BiCGStab solve
         breaks down (see ``solve``) is solved again with GMRES from the kept state; ``context(sd).stats()
-        ["transport_gmres_retries"]`` counts them."""
+        ["transport_gmres_retries"]`` counts them.
+
+        ``precond="sweep"`` (default "jacobi"): every step is one substitution in flow order plus a residual check when
+        the flux graph is acyclic (``stats()["sweep_direct_steps"]`` counts them); with a cyclic core the sweep
+        preconditions ``method`` (see ``solve``).  The order is built once per flux."""
         self._assemble(sd, data, accumulation, None, source)
         return self.context(sd).transport_advance(c0, n_steps, method=method, rtol=rtol, maxit=maxit,
-                                                  raise_on_fail=raise_on_fail)
+                                                  raise_on_fail=raise_on_fail, precond=precond)
 
 
 def as_porepy_upwind(device: int = 0, library=None):

@@ -6,7 +6,8 @@
       both as wall clock around synchronised calls from the same host arrays, median after warm-up (the composition
       spans many library calls, so one pair of device events cannot bracket it); for (a) also the HIP-event time of
       its kernels alone (pfv_stats.advdiff_assemble_ms)
-  (c) ms and iterations per implicit Euler step of ``advance`` with AMG and with Jacobi at cell Peclet 0.05 and 5
+  (c) ms and iterations per implicit Euler step of ``advance`` with AMG, with Jacobi and with the flow-ordered sweep at
+      cell Peclet 0.05 and 5
   and the stream triad rate of the device (pfv_time_kernel) next to the refresh's algorithmic bytes.
 
 Prints a small report.  A measurement, not a test: no thresholds.
@@ -113,13 +114,14 @@ def main():
                   f"{100 * bytes_alg / t_a / 1e6 / rate:.0f} % of the measured stream triad rate {rate:.0f} GB/s")
             ad._assemble(g, data, acc, c0)
         # (c) the step
-        for precond in ("amg", "jacobi"):
+        for precond in ("amg", "jacobi", "sweep"):
             ad.advance(g, data, c0, 1, acc, precond=precond, rtol=1e-10, raise_on_fail=False)  # warm-up (AMG setup)
             _, info = ad.advance(g, data, c0, a.steps, acc, precond=precond, rtol=1e-10, raise_on_fail=False)
             st = ctx.stats()
             print(f"(c) Peclet {pe:g}, {precond:6s}: {st['advdiff_advance_ms'] / max(info['steps_done'], 1):8.3f} ms/step, "
                   f"{st['advdiff_iterations'] / max(info['steps_done'], 1):6.1f} iterations/step, "
-                  f"{info['steps_done']}/{a.steps} steps, {st['advdiff_precond_fallbacks']} fallbacks")
+                  f"{info['steps_done']}/{a.steps} steps, {st['advdiff_precond_fallbacks']} fallbacks"
+                  + (f", {st['sweep_levels']} levels, {st['sweep_launches']} launches per sweep" if precond == "sweep" else ""))
 
 
 if __name__ == "__main__":

@@ -6,7 +6,11 @@ the same chain on the host with scipy, measured in the same run:
 Device times are HIP-event times from pfv_stats; the host times are wall clock.  Prints one JSON line.  A measurement,
 not a test: no thresholds.
 
-    python tools/bench_transport.py [--n-side 69] [--steps 20] [--no-host]
+    python tools/bench_transport.py [--n-side 69] [--steps 20] [--no-host] [--precond sweep]
+
+--precond sweep: after the Jacobi-BiCGStab steps, the same steps from the same state with the flow-ordered sweep
+(PFV_PRECOND_SWEEP) -- order-build ms, levels, core cells, launches per sweep, ms per step -- and again with one launch
+per level (PFV_SWEEP_MERGE=0); both figures of the comparison come from this one run on the same inputs.
 """
 from __future__ import annotations
 
@@ -30,6 +34,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--precond", choices=["jacobi", "sweep"], default="jacobi",
+                    help="sweep: also time the steps with the flow-ordered sweep, next to the Jacobi-BiCGStab ones")
     ap.add_argument("--emulation", action="store_true", help="run on the host-emulation build (plumbing check)")
     a = ap.parse_args()
     lib = None
@@ -78,6 +84,21 @@ def main():
     st = ctx.stats()
     out["advance"] = {"steps_done": ainfo["steps_done"], "ms_per_step": st["transport_advance_ms"] / max(a.steps, 1),
                       "iterations_per_step": st["transport_iterations"] / max(a.steps, 1)}
+    if a.precond == "sweep":
+        for key, merge in (("advance_sweep", "1"), ("advance_sweep_one_launch_per_level", "0")):
+            os.environ["PFV_SWEEP_MERGE"] = merge
+            cs, sinfo = ctx.transport_advance(c0, a.steps, rtol=1e-10, raise_on_fail=False, precond="sweep")
+            first = ctx.stats()  # (the first call builds the order)
+            cs, sinfo = ctx.transport_advance(c0, a.steps, rtol=1e-10, raise_on_fail=False, precond="sweep")
+            ss = ctx.stats()
+            out[key] = {"steps_done": sinfo["steps_done"], "ms_per_step": ss["transport_advance_ms"] / max(a.steps, 1),
+                        "ms_per_step_first_call": first["transport_advance_ms"] / max(a.steps, 1),
+                        "order_build_ms": first["sweep_order_ms"], "levels": ss["sweep_levels"],
+                        "core_cells": ss["sweep_core_cells"], "launches_per_sweep": ss["sweep_launches"],
+                        "direct_steps": ss["sweep_direct_steps"], "direct_fallbacks": ss["sweep_direct_fallbacks"],
+                        "rel_residual_last_step": sinfo["rel_residual"],
+                        "max_diff_to_jacobi_bicgstab": float(np.abs(cs - c).max())}
+        del os.environ["PFV_SWEEP_MERGE"]
     # bytes each kernel has to move at least ("Upwind advection"): the fraction of a stream rate follows
     nnz_flux = ctx.matrix_info(_lib.MAT_FLUX)[2]
     nnz_bound = ctx.matrix_info(_lib.MAT_BOUND_FLUX)[2]

@@ -731,40 +731,12 @@ pfv_status pfv_csr_set_system(pfv_ctx* h, const pfv_csr* A, const double* rhs, i
     int32_t* ix = P.indices.ensure((size_t)std::max<int64_t>(nnz, 1));
     double* v = h->val[PFV_MAT_USER_SYSTEM].ensure((size_t)std::max<int64_t>(nnz, 1));
     double* b = h->rhs_u.ensure((size_t)n);
-    double* dg = h->diag_u.ensure((size_t)n);
     pfv::be_d2d(ip, A->P.indptr.p, sizeof(int32_t) * (size_t)(n + 1), s);
     pfv::be_d2d(ix, A->P.indices.p, sizeof(int32_t) * (size_t)nnz, s);
     pfv::be_d2d(v, A->val.p, sizeof(double) * (size_t)nnz, s);
     if (rhs_on_device) pfv::be_d2d(b, rhs, sizeof(double) * (size_t)n, s);
     else be_h2d(b, rhs, sizeof(double) * (size_t)n, s);
-    int32_t* st = h->status.ensure(16);
-    pfv::be_memset(st, 0, sizeof(int32_t) * 4, s);
-    pfv::parallel_for(s, n, PFV_LAMBDA(int64_t i) {
-      double d = 0.0;
-      for (int e = ip[i]; e < ip[i + 1]; ++e)
-        if (ix[e] == i) d += v[e];
-      dg[i] = d;
-      if (!(d != 0.0) || !(d == d)) pfv::atomic_max_i32(st + 0, (int32_t)(i < 0x7fffffff ? i + 1 : 0x7fffffff));
-    });
-    const int32_t bad = pfv::read_scalar<int32_t>(s, st);
-    if (bad)
-      throw pfv::Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(bad - 1) +
-                                                ": the Jacobi-preconditioned solver does not apply");
-    h->filled[PFV_MAT_USER_SYSTEM] = true;
-    h->active.P = &P;
-    h->active.val = v;
-    h->active.diag = dg;
-    h->active.rhs = b;
-    h->active.n = n;
-    h->active_bs = 1;
-    if (h->amg) h->amg->valid = false;
-    h->nns_stale = true;  // (the near-null-space hierarchy too)
-    if (h->amg_block) h->amg_block->valid = false;
-    if (h->block_pc) h->block_pc->for_val = nullptr;  // (the user-system buffer is reused: same pointer, new matrix)
-    h->perm_for_val = nullptr;
-    h->win_for = h->win_rows_for = nullptr;
-    h->active_is_grid = false;
-    h->active.valid = true;
+    user_system_ready(h);
   });
 }
 

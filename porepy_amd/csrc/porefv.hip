@@ -221,6 +221,64 @@ static void vec_in(pfv_ctx* h, double* dst, const double* src, size_t n) {
   else be_h2d(dst, src, n * sizeof(double), h->stream);
 }
 
+// ... and the mirror for what the calls hand back (does not synchronise)
+static void vec_out(pfv_ctx* h, double* dst, const double* src, size_t n) {
+  if (h->vectors_on_device) pfv::be_d2d(dst, src, n * sizeof(double), h->stream);
+  else be_d2h(dst, src, n * sizeof(double), h->stream);
+}
+
+// ---- the active system and the solver caches keyed on it ("The active system and its caches") ---------
+// A call that makes a system the active one calls values_changed (when it wrote the values) and activate, and touches
+// none of the fields behind them itself.
+
+// is system `which` of the handle (a PFV_MAT_* selector with values of its own) the active one?
+static bool active_is(const pfv_ctx* h, int which) { return h->active.valid && h->active.val == h->val[which].p; }
+
+static void activate(pfv_ctx* h, const pfv::CsrPattern& P, double* val, double* diag, double* rhs, int64_t n, int bs,
+                     bool is_grid) {
+  h->active.P = &P;
+  h->active.val = val;
+  h->active.diag = diag;
+  h->active.rhs = rhs;
+  h->active.n = n;
+  h->active_bs = bs;
+  h->active_is_grid = is_grid;
+  h->active.valid = true;
+}
+
+// what becomes of the SpMV windows (win_sys, win_rows: functions of a pattern, keyed on its index array) when the
+// values of a system change
+enum class Windows {
+  keep,     // the pattern under the values is the one the windows were keyed on: a refresh of values in place
+  consume,  // div @ flux assembled for a new discretization: a window the discretize call built for this very pattern
+            // (win_*_prebuilt) survives once, any other is dropped
+  drop,     // the pattern was rebuilt or replaced in buffers that keep their address: no window survives
+};
+// `drop` also clears the two win_*_prebuilt flags.  They are set by pfv_mpfa_discretize alone, together with the pointer
+// they vouch for, and read by `consume` alone; with the pointer gone, consuming a set flag and consuming a cleared one
+// both end at (flag cleared, pointer null) -- and a pointer that a solve of another system sets in between is not
+// pat_A's, so the next solve of the flow system builds its window either way.
+
+// The values of a system were written into buffers whose address the caches below are keyed on: drop all five.
+// copy_only: solver_system has just renumbered the active system -- what was built on the loop's copy goes, what was
+// built on the active system itself (amg_block) and the copy's own key stay.
+static void values_changed(pfv_ctx* h, Windows w, bool copy_only = false) {
+  if (h->amg) h->amg->valid = false;  // keyed on amg_for_val
+  h->nns_stale = true;                // amg_nns, keyed on amg_nns_for_val
+  if (h->block_pc) h->block_pc->for_val = nullptr;
+  if (!copy_only) {
+    if (h->amg_block) h->amg_block->valid = false;
+    h->perm_for_val = nullptr;  // the renumbered copy
+  }
+  if (w == Windows::consume) {
+    if (!h->win_sys_prebuilt) h->win_for = nullptr;
+    if (!h->win_rows_prebuilt) h->win_rows_for = nullptr;
+  } else if (w == Windows::drop) {
+    h->win_for = h->win_rows_for = nullptr;
+  }
+  if (w != Windows::keep) h->win_sys_prebuilt = h->win_rows_prebuilt = false;
+}
+
 pfv_status pfv_set_vectors_on_device(pfv_ctx* h, int on) {
   return guarded(h, [&] { h->vectors_on_device = on != 0; });
 }
@@ -741,29 +799,13 @@ pfv_status pfv_mpfa_assemble(pfv_ctx* h, const double* bc_values, const double* 
     if (!h->have_system) {
       pfv::assemble_system(*h);
       h->have_advdiff = h->have_adv_bD = false;  // (advdiff.inc: built on the previous div @ flux)
-      if (h->amg) h->amg->valid = false;
-      h->nns_stale = true;  // (the near-null-space hierarchy too)
-      if (h->block_pc) h->block_pc->for_val = nullptr;
-      if (h->amg_block) h->amg_block->valid = false;
-      h->perm_for_val = nullptr;
-      // windows built for this very pattern by the discretize call are kept
-      if (h->win_rows_prebuilt) h->win_rows_prebuilt = false;
-      else h->win_rows_for = nullptr;
-      if (h->win_sys_prebuilt) h->win_sys_prebuilt = false;
-      else h->win_for = nullptr;
+      values_changed(h, Windows::consume);
     }
     pfv::assemble_rhs(*h, d_bc, d_vs, d_src);
     h->stats.assemble_ms = tm.stop(s);
     h->have_system = true;
     h->have_flow_rhs = true;
-    h->active.P = &h->pat_A;
-    h->active.val = h->val[PFV_MAT_SYSTEM].p;
-    h->active.diag = h->diag.p;
-    h->active.rhs = h->rhs.p;
-    h->active.n = h->nc;
-    h->active_bs = 1;
-    h->active_is_grid = true;
-    h->active.valid = true;
+    activate(h, h->pat_A, h->val[PFV_MAT_SYSTEM].p, h->diag.p, h->rhs.p, h->nc, 1, true);
   });
 }
 
@@ -795,27 +837,11 @@ pfv_status pfv_mpfa_ad_flux_system(pfv_ctx* h, const double* p, const double* dk
     pfv::ad_flux_system(*h, d_p, d_dk, d_bc, d_vs, d_src, flux_out ? d_q : nullptr,
                         (flags & PFV_AD_WANT_FLUX_JACOBIAN) != 0);
     h->stats.assemble_ms = tm.stop(s);
-    if (flux_out) {
-      if (h->vectors_on_device) pfv::be_d2d(flux_out, d_q, nf * sizeof(double), s);
-      else be_d2h(flux_out, d_q, nf * sizeof(double), s);
-    }
+    if (flux_out) vec_out(h, flux_out, d_q, nf);
     pfv::be_sync(s);
     h->have_system = false;  // PFV_MAT_SYSTEM now holds J, not div flux: pfv_mpfa_assemble rebuilds it
-    if (h->amg) h->amg->valid = false;
-    h->nns_stale = true;  // (the near-null-space hierarchy too)
-      if (h->block_pc) h->block_pc->for_val = nullptr;
-    if (h->amg_block) h->amg_block->valid = false;
-    h->perm_for_val = nullptr;
-    h->win_for = h->win_rows_for = nullptr;
-    h->win_sys_prebuilt = h->win_rows_prebuilt = false;
-    h->active.P = &h->pat_A;
-    h->active.val = h->val[PFV_MAT_SYSTEM].p;
-    h->active.diag = h->diag.p;
-    h->active.rhs = h->rhs.p;
-    h->active.n = h->nc;
-    h->active_bs = 1;
-    h->active_is_grid = true;
-    h->active.valid = true;
+    values_changed(h, Windows::drop);
+    activate(h, h->pat_A, h->val[PFV_MAT_SYSTEM].p, h->diag.p, h->rhs.p, h->nc, 1, true);
   });
 }
 
@@ -828,7 +854,7 @@ static void upwind_supported(pfv_ctx* h) {
 
 // the transport system no longer belongs to the discretization on the handle: it must not stay the active system
 static void upwind_drop_transport(pfv_ctx* h) {
-  if (h->active.valid && h->active.val == h->val[PFV_MAT_TRANSPORT_SYSTEM].p && h->have_transport) h->active.valid = false;
+  if (h->have_transport && active_is(h, PFV_MAT_TRANSPORT_SYSTEM)) h->active.valid = false;
   h->have_transport = false;
   h->filled[PFV_MAT_TRANSPORT_SYSTEM] = false;
   h->transport_zero_diag = -1;
@@ -843,7 +869,7 @@ static void sweep_note_assembly(pfv_ctx* h, int which, const double* d_q) {
 }
 
 static bool transport_is_active(const pfv_ctx* h) {
-  return h->have_transport && h->active.valid && h->active.val == h->val[PFV_MAT_TRANSPORT_SYSTEM].p;
+  return h->have_transport && active_is(h, PFV_MAT_TRANSPORT_SYSTEM);
 }
 
 pfv_status pfv_mpfa_face_flux(pfv_ctx* h, const double* p, const double* bc_values, const double* vector_source,
@@ -870,10 +896,7 @@ pfv_status pfv_mpfa_face_flux(pfv_ctx* h, const double* p, const double* bc_valu
     pfv::upwind_face_flux(*h, d_p, d_bc, d_vs);
     h->stats.face_flux_ms = tm.stop(s);
     h->have_q_res = true;
-    if (q_out) {
-      if (h->vectors_on_device) pfv::be_d2d(q_out, h->q_res.p, nf * sizeof(double), s);
-      else be_d2h(q_out, h->q_res.p, nf * sizeof(double), s);
-    }
+    if (q_out) vec_out(h, q_out, h->q_res.p, nf);
     pfv::be_sync(s);  // (the staging buffer is freed on return)
   });
 }
@@ -946,77 +969,83 @@ pfv_status pfv_upwind_assemble(pfv_ctx* h, const double* q, const double* bc_val
     h->stats.transport_assemble_ms = tm.stop(s);
     h->transport_q = d_q;
     sweep_note_assembly(h, PFV_MAT_TRANSPORT_SYSTEM, d_q);
-    if (bound_rhs_out) {
-      if (h->vectors_on_device) pfv::be_d2d(bound_rhs_out, h->bref_t.p, nc * sizeof(double), s);
-      else be_d2h(bound_rhs_out, h->bref_t.p, nc * sizeof(double), s);
-    }
+    if (bound_rhs_out) vec_out(h, bound_rhs_out, h->bref_t.p, nc);
     pfv::be_sync(s);
     h->have_transport = true;
-    // the values under the solver's caches changed (they are keyed on the value pointer)
-    if (h->amg) h->amg->valid = false;
-    h->nns_stale = true;
-    if (h->block_pc) h->block_pc->for_val = nullptr;
-    if (h->amg_block) h->amg_block->valid = false;
-    h->perm_for_val = nullptr;
-    h->win_for = h->win_rows_for = nullptr;
-    h->win_sys_prebuilt = h->win_rows_prebuilt = false;
-    h->active.P = &h->pat_T;
-    h->active.val = h->val[PFV_MAT_TRANSPORT_SYSTEM].p;
-    h->active.diag = h->diag_t.p;
-    h->active.rhs = h->rhs_t.p;
-    h->active.n = h->nc;
-    h->active_bs = 1;
-    h->active_is_grid = true;
-    h->active.valid = true;
+    values_changed(h, Windows::drop);
+    activate(h, h->pat_T, h->val[PFV_MAT_TRANSPORT_SYSTEM].p, h->diag_t.p, h->rhs_t.p, h->nc, 1, true);
   });
 }
 
-pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rtol, int maxit, double* c,
-                                 int32_t* steps_done, pfv_solve_info* last) {
+// ---- the step loop of pfv_transport_advance and pfv_advdiff_advance --------------------------------------------------
+struct StepLoop {  // what differs between the two
+  pfv::Buf<double> pfv::pfv_ctx_impl::*state;  // the state between the steps
+  pfv::Buf<double> pfv::pfv_ctx_impl::*keep;   // the state before the step, for a second attempt
+  void (*step_rhs)(pfv::pfv_ctx_impl&, const double*);
+  bool jacobi_unless_sweep;  // the transport matrix is one-sided: any other choice on the handle is replaced by Jacobi
+  bool jacobi_fallback;      // a step the AMG- or sweep-preconditioned solve gives up on: again with Jacobi-GMRES
+};
+struct StepTotals {
+  bool ran = false;  // the checks passed: the totals below are to be written to the statistics
+  int64_t iterations = 0, gmres_retries = 0, precond_fallbacks = 0, direct = 0, direct_fallbacks = 0;
+  double order_ms = 0.0, ms = 0.0;
+};
+
+// `checks` throws for what the call does not take.  Then n_steps times: form the right-hand side, solve from the state;
+// a step that ends in NaN under BiCGStab is solved again with GMRES from the kept state.  BiCGStab can break down
+// (rho = (r_hat, r) = 0: the residual turns NaN) where the first residual sits in cells nothing flows back into --
+// injection into a field at rest, the matrix of an acyclic flow being triangular.  The error of a failed step is what
+// pfv_last_error reports, whatever the epilogue does.
+static pfv_status advance_steps(pfv_ctx* h, const StepLoop& L, const std::function<void()>& checks, int n_steps,
+                                int method, double rtol, int maxit, double* c, int32_t* steps_done,
+                                pfv_solve_info* last, StepTotals& tot) {
   if (steps_done) *steps_done = 0;
   std::unique_ptr<pfv::Timer> tm;
   pfv_status st = guarded(h, [&] {
-    upwind_supported(h);
-    require(h->have_transport && h->active.valid && h->active.val == h->val[PFV_MAT_TRANSPORT_SYSTEM].p,
-            "pfv_upwind_assemble first (the transport system must be the active one)");
-    require(n_steps >= 0 && c != nullptr, "bad argument");
-    require(method == PFV_SOLVE_BICGSTAB || method == PFV_SOLVE_GMRES,
-            "method must be PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES (the transport matrix is not symmetric)");
-    vec_in(h, h->c_t.ensure((size_t)h->nc), c, (size_t)h->nc);
+    checks();
+    vec_in(h, (h->*L.state).ensure((size_t)h->nc), c, (size_t)h->nc);
     tm = std::make_unique<pfv::Timer>();
     tm->start(h->stream);
   });
   if (st != PFV_OK) return st;
+  tot.ran = true;
+  pfv::Buf<double>&state = h->*L.state, &keep = h->*L.keep;
   const bool caller_on_device = h->vectors_on_device;
   const int precond = h->precond;
-  h->vectors_on_device = true;  // the state stays in c_t between the steps
-  h->precond = precond == PFV_PRECOND_SWEEP ? PFV_PRECOND_SWEEP : PFV_PRECOND_JACOBI;
-  int64_t iters = 0, retries = 0, direct = 0, direct_fb = 0;
-  double order_ms = 0.0;
+  h->vectors_on_device = true;  // the state stays on the device between the steps
+  if (L.jacobi_unless_sweep && precond != PFV_PRECOND_SWEEP) h->precond = PFV_PRECOND_JACOBI;
   const size_t nbytes = (size_t)h->nc * sizeof(double);
+  const bool keep_state = method == PFV_SOLVE_BICGSTAB || L.jacobi_fallback;
+  auto restore_state = [&] { return guarded(h, [&] { pfv::be_d2d(state.p, keep.p, nbytes, h->stream); }); };
+  auto solve = [&](int m, pfv_solve_info& info) {
+    const pfv_status r = pfv_solve(h, m, rtol, maxit, 0, state.p, state.p, &info);
+    tot.iterations += info.iterations;
+    return r;
+  };
   for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
-    // BiCGStab can break down (rho = (r_hat, r) = 0: the residual turns NaN) where the first residual sits in cells
-    // nothing flows back into -- injection into a field at rest, the matrix of an acyclic flow being triangular.  The
-    // state is kept, and such a step is solved again with GMRES from it; transport_gmres_retries counts them.
     st = guarded(h, [&] {
-      pfv::upwind_step_rhs(*h, h->c_t.p);
-      if (method == PFV_SOLVE_BICGSTAB) pfv::be_d2d(h->c_keep.ensure((size_t)h->nc), h->c_t.p, nbytes, h->stream);
+      L.step_rhs(*h, state.p);
+      if (keep_state) pfv::be_d2d(keep.ensure((size_t)h->nc), state.p, nbytes, h->stream);
     });
     if (st != PFV_OK) break;
     pfv_solve_info info{};
-    st = pfv_solve(h, method, rtol, maxit, 0, h->c_t.p, h->c_t.p, &info);
-    iters += info.iterations;
-    direct += h->stats.sweep_direct_steps;
-    direct_fb += h->stats.sweep_direct_fallbacks;
-    order_ms += h->stats.sweep_order_ms;
+    st = solve(method, info);
+    tot.direct += h->stats.sweep_direct_steps;
+    tot.direct_fallbacks += h->stats.sweep_direct_fallbacks;
+    tot.order_ms += h->stats.sweep_order_ms;
     if (st == PFV_ERR_NOT_CONVERGED && method == PFV_SOLVE_BICGSTAB && !(info.rel_residual == info.rel_residual)) {
-      st = guarded(h, [&] { pfv::be_d2d(h->c_t.p, h->c_keep.p, nbytes, h->stream); });
-      if (st != PFV_OK) break;
-      ++retries;
-      st = pfv_solve(h, PFV_SOLVE_GMRES, rtol, maxit, 0, h->c_t.p, h->c_t.p, &info);
-      iters += info.iterations;
-      direct += h->stats.sweep_direct_steps;
-      direct_fb += h->stats.sweep_direct_fallbacks;
+      if ((st = restore_state()) != PFV_OK) break;
+      ++tot.gmres_retries;
+      st = solve(PFV_SOLVE_GMRES, info);
+      tot.direct += h->stats.sweep_direct_steps;
+      tot.direct_fallbacks += h->stats.sweep_direct_fallbacks;
+    }
+    if (st == PFV_ERR_NOT_CONVERGED && L.jacobi_fallback && (precond == PFV_PRECOND_AMG || precond == PFV_PRECOND_SWEEP)) {
+      if ((st = restore_state()) != PFV_OK) break;
+      ++tot.precond_fallbacks;
+      h->precond = PFV_PRECOND_JACOBI;
+      st = solve(PFV_SOLVE_GMRES, info);
+      h->precond = precond;
     }
     if (last) *last = info;
     if (st == PFV_OK && steps_done) ++*steps_done;
@@ -1025,16 +1054,9 @@ pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rto
   h->precond = precond;
   const std::string err = h->err;
   const pfv_status st2 = guarded(h, [&] {
-    h->stats.transport_advance_ms = tm->stop(h->stream);
+    tot.ms = tm->stop(h->stream);
     tm.reset();
-    h->stats.transport_iterations = iters;
-    h->stats.transport_gmres_retries = retries;
-    h->stats.sweep_direct_steps = direct;
-    h->stats.sweep_direct_fallbacks = direct_fb;
-    h->stats.sweep_order_ms = order_ms;
-    const size_t nc = (size_t)h->nc;
-    if (h->vectors_on_device) pfv::be_d2d(c, h->c_t.p, nc * sizeof(double), h->stream);
-    else be_d2h(c, h->c_t.p, nc * sizeof(double), h->stream);
+    vec_out(h, c, state.p, (size_t)h->nc);
     pfv::be_sync(h->stream);
   });
   if (st != PFV_OK) {
@@ -1042,6 +1064,28 @@ pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rto
     return st;
   }
   return st2;
+}
+
+pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rtol, int maxit, double* c,
+                                 int32_t* steps_done, pfv_solve_info* last) {
+  static const StepLoop loop{&pfv_ctx::c_t, &pfv_ctx::c_keep, pfv::upwind_step_rhs, true, false};
+  StepTotals tot;
+  const pfv_status st = advance_steps(h, loop, [&] {
+    upwind_supported(h);
+    require(transport_is_active(h), "pfv_upwind_assemble first (the transport system must be the active one)");
+    require(n_steps >= 0 && c != nullptr, "bad argument");
+    require(method == PFV_SOLVE_BICGSTAB || method == PFV_SOLVE_GMRES,
+            "method must be PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES (the transport matrix is not symmetric)");
+  }, n_steps, method, rtol, maxit, c, steps_done, last, tot);
+  if (tot.ran) {
+    h->stats.transport_advance_ms = tot.ms;
+    h->stats.transport_iterations = tot.iterations;
+    h->stats.transport_gmres_retries = tot.gmres_retries;
+    h->stats.sweep_direct_steps = tot.direct;
+    h->stats.sweep_direct_fallbacks = tot.direct_fallbacks;
+    h->stats.sweep_order_ms = tot.order_ms;
+  }
+  return st;
 }
 
 // ---- advection-diffusion on one handle (advdiff.inc) -----------------------------------------------------------
@@ -1053,18 +1097,13 @@ static void advdiff_supported(pfv_ctx* h) {
 }
 
 static bool advdiff_is_active(const pfv_ctx* h) {
-  return h->have_advdiff && h->have_system && h->have_adv_bD && h->active.valid &&
-         h->active.val == h->val[PFV_MAT_ADVDIFF_SYSTEM].p;
+  return h->have_advdiff && h->have_system && h->have_adv_bD && active_is(h, PFV_MAT_ADVDIFF_SYSTEM);
 }
 
 pfv_status pfv_resident_flux(pfv_ctx* h, double** d_q, double* q_out) {
   return guarded(h, [&] {
     require(h->have_grid && h->have_q_res, "no resident face flux on the handle (pfv_mpfa_face_flux)");
-    const size_t bytes = (size_t)h->nf * sizeof(double);
-    if (q_out) {
-      if (h->vectors_on_device) pfv::be_d2d(q_out, h->q_res.p, bytes, h->stream);
-      else be_d2h(q_out, h->q_res.p, bytes, h->stream);
-    }
+    if (q_out) vec_out(h, q_out, h->q_res.p, (size_t)h->nf);
     pfv::be_sync(h->stream);  // (a reader on another handle's stream must find it complete)
     if (d_q) *d_q = h->q_res.p;
   });
@@ -1081,7 +1120,7 @@ pfv_status pfv_advdiff_assemble(pfv_ctx* h, const double* q, double flux_scale, 
     require(q || h->have_q_res, "no face flux given and no resident face flux on the handle (pfv_mpfa_face_flux)");
     auto s = h->stream;
     const size_t nf = (size_t)h->nf, nc = (size_t)h->nc;
-    if (h->active.valid && h->active.val == h->val[PFV_MAT_ADVDIFF_SYSTEM].p) h->active.valid = false;
+    if (active_is(h, PFV_MAT_ADVDIFF_SYSTEM)) h->active.valid = false;
     h->have_advdiff = false;
     h->filled[PFV_MAT_ADVDIFF_SYSTEM] = false;
     h->advdiff_zero_diag = -1;
@@ -1101,10 +1140,7 @@ pfv_status pfv_advdiff_assemble(pfv_ctx* h, const double* q, double flux_scale, 
     if (!h->have_system) {  // div @ flux_D: once per discretization, by the flow assembly
       pfv::assemble_system(*h);
       h->have_adv_bD = false;
-      if (h->win_rows_prebuilt) h->win_rows_prebuilt = false;
-      else h->win_rows_for = nullptr;
-      if (h->win_sys_prebuilt) h->win_sys_prebuilt = false;
-      else h->win_for = nullptr;
+      values_changed(h, Windows::consume);  // (PFV_MAT_SYSTEM's)
       h->have_system = true;      // PFV_MAT_SYSTEM and its diagonal hold div @ flux ...
       h->have_flow_rhs = false;   // ... but no flow right-hand side was formed with them
     }
@@ -1119,34 +1155,19 @@ pfv_status pfv_advdiff_assemble(pfv_ctx* h, const double* q, double flux_scale, 
                          h->have_adv_src ? h->adv_src.p : nullptr);
     h->stats.advdiff_assemble_ms = tm.stop(s);
     sweep_note_assembly(h, PFV_MAT_ADVDIFF_SYSTEM, d_q);
-    if (bound_rhs_out) {
-      if (h->vectors_on_device) pfv::be_d2d(bound_rhs_out, h->adv_bref.p, nc * sizeof(double), s);
-      else be_d2h(bound_rhs_out, h->adv_bref.p, nc * sizeof(double), s);
-    }
+    if (bound_rhs_out) vec_out(h, bound_rhs_out, h->adv_bref.p, nc);
     pfv::be_sync(s);
     h->have_advdiff = true;
-    // the values under the solver's caches changed (they are keyed on the value pointer); the aggregate maps stay
-    if (h->amg) h->amg->valid = false;
-    h->nns_stale = true;
-    if (h->block_pc) h->block_pc->for_val = nullptr;
-    if (h->amg_block) h->amg_block->valid = false;
-    h->perm_for_val = nullptr;
-    h->active.P = &h->pat_A;
-    h->active.val = h->val[PFV_MAT_ADVDIFF_SYSTEM].p;
-    h->active.diag = h->adv_diag.p;
-    h->active.rhs = h->adv_rhs.p;
-    h->active.n = h->nc;
-    h->active_bs = 1;
-    h->active_is_grid = true;
-    h->active.valid = true;
+    values_changed(h, Windows::keep);  // (S shares pat_A with div @ flux; the aggregate maps stay too)
+    activate(h, h->pat_A, h->val[PFV_MAT_ADVDIFF_SYSTEM].p, h->adv_diag.p, h->adv_rhs.p, h->nc, 1, true);
   });
 }
 
 pfv_status pfv_advdiff_advance(pfv_ctx* h, int n_steps, int method, double rtol, int maxit, double* c,
                                int32_t* steps_done, pfv_solve_info* last) {
-  if (steps_done) *steps_done = 0;
-  std::unique_ptr<pfv::Timer> tm;
-  pfv_status st = guarded(h, [&] {
+  static const StepLoop loop{&pfv_ctx::adv_c, &pfv_ctx::adv_keep, pfv::advdiff_step_rhs, false, true};
+  StepTotals tot;
+  const pfv_status st = advance_steps(h, loop, [&] {
     advdiff_supported(h);
     require(advdiff_is_active(h), "pfv_advdiff_assemble first (the advection-diffusion system must be the active one)");
     require(n_steps >= 0 && c != nullptr, "bad argument");
@@ -1154,68 +1175,15 @@ pfv_status pfv_advdiff_advance(pfv_ctx* h, int n_steps, int method, double rtol,
             "method must be PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES (the matrix is not symmetric)");
     require(h->precond == PFV_PRECOND_JACOBI || h->precond == PFV_PRECOND_AMG || h->precond == PFV_PRECOND_SWEEP,
             "the advection-diffusion step takes PFV_PRECOND_JACOBI, PFV_PRECOND_AMG or PFV_PRECOND_SWEEP");
-    vec_in(h, h->adv_c.ensure((size_t)h->nc), c, (size_t)h->nc);
-    tm = std::make_unique<pfv::Timer>();
-    tm->start(h->stream);
-  });
-  if (st != PFV_OK) return st;
-  const bool caller_on_device = h->vectors_on_device;
-  const int precond = h->precond;
-  h->vectors_on_device = true;  // the state stays in adv_c between the steps
-  int64_t iters = 0, retries = 0, fallbacks = 0;
-  double order_ms = 0.0;
-  const size_t nbytes = (size_t)h->nc * sizeof(double);
-  for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
-    st = guarded(h, [&] {
-      pfv::advdiff_step_rhs(*h, h->adv_c.p);
-      pfv::be_d2d(h->adv_keep.ensure((size_t)h->nc), h->adv_c.p, nbytes, h->stream);
-    });
-    if (st != PFV_OK) break;
-    pfv_solve_info info{};
-    st = pfv_solve(h, method, rtol, maxit, 0, h->adv_c.p, h->adv_c.p, &info);
-    iters += info.iterations;
-    order_ms += h->stats.sweep_order_ms;
-    // BiCGStab breakdown (NaN residual): again with GMRES from the kept state, as pfv_transport_advance does
-    if (st == PFV_ERR_NOT_CONVERGED && method == PFV_SOLVE_BICGSTAB && !(info.rel_residual == info.rel_residual)) {
-      st = guarded(h, [&] { pfv::be_d2d(h->adv_c.p, h->adv_keep.p, nbytes, h->stream); });
-      if (st != PFV_OK) break;
-      ++retries;
-      st = pfv_solve(h, PFV_SOLVE_GMRES, rtol, maxit, 0, h->adv_c.p, h->adv_c.p, &info);
-      iters += info.iterations;
-    }
-    // the AMG- or sweep-preconditioned solve did not get there: the step again with Jacobi-GMRES from the kept state
-    if (st == PFV_ERR_NOT_CONVERGED && (precond == PFV_PRECOND_AMG || precond == PFV_PRECOND_SWEEP)) {
-      st = guarded(h, [&] { pfv::be_d2d(h->adv_c.p, h->adv_keep.p, nbytes, h->stream); });
-      if (st != PFV_OK) break;
-      ++fallbacks;
-      h->precond = PFV_PRECOND_JACOBI;
-      st = pfv_solve(h, PFV_SOLVE_GMRES, rtol, maxit, 0, h->adv_c.p, h->adv_c.p, &info);
-      h->precond = precond;
-      iters += info.iterations;
-    }
-    if (last) *last = info;
-    if (st == PFV_OK && steps_done) ++*steps_done;
+  }, n_steps, method, rtol, maxit, c, steps_done, last, tot);
+  if (tot.ran) {
+    h->stats.advdiff_advance_ms = tot.ms;
+    h->stats.advdiff_iterations = tot.iterations;
+    h->stats.advdiff_gmres_retries = tot.gmres_retries;
+    h->stats.advdiff_precond_fallbacks = tot.precond_fallbacks;
+    if (h->precond == PFV_PRECOND_SWEEP) h->stats.sweep_order_ms = tot.order_ms;
   }
-  h->vectors_on_device = caller_on_device;
-  h->precond = precond;
-  const std::string err = h->err;
-  const pfv_status st2 = guarded(h, [&] {
-    h->stats.advdiff_advance_ms = tm->stop(h->stream);
-    tm.reset();
-    h->stats.advdiff_iterations = iters;
-    h->stats.advdiff_gmres_retries = retries;
-    h->stats.advdiff_precond_fallbacks = fallbacks;
-    if (precond == PFV_PRECOND_SWEEP) h->stats.sweep_order_ms = order_ms;
-    const size_t nc = (size_t)h->nc;
-    if (h->vectors_on_device) pfv::be_d2d(c, h->adv_c.p, nc * sizeof(double), h->stream);
-    else be_d2h(c, h->adv_c.p, nc * sizeof(double), h->stream);
-    pfv::be_sync(h->stream);
-  });
-  if (st != PFV_OK) {
-    h->err = err;
-    return st;
-  }
-  return st2;
+  return st;
 }
 
 pfv_status pfv_advdiff_face_flux(pfv_ctx* h, const double* c, double* out) {
@@ -1231,8 +1199,7 @@ pfv_status pfv_advdiff_face_flux(pfv_ctx* h, const double* c, double* out) {
     double* d_out = d_c + nc;
     vec_in(h, d_c, c, nc);
     pfv::advdiff_face_flux(*h, d_c, d_out);
-    if (h->vectors_on_device) pfv::be_d2d(out, d_out, nf * sizeof(double), s);
-    else be_d2h(out, d_out, nf * sizeof(double), s);
+    vec_out(h, out, d_out, nf);
     pfv::be_sync(s);  // (the staging buffer is freed on return)
   });
 }
@@ -1643,24 +1610,12 @@ pfv_status pfv_mpsa_assemble(pfv_ctx* h, const double* bc_values, const double* 
     tm.start(s);
     if (!h->have_mech_system) {
       pfv::mpsa_assemble_system(*h);
-      if (h->amg) h->amg->valid = false;
-      h->nns_stale = true;  // (the near-null-space hierarchy too)
-      if (h->block_pc) h->block_pc->for_val = nullptr;
-      if (h->amg_block) h->amg_block->valid = false;
-      h->perm_for_val = nullptr;
-      h->win_for = h->win_rows_for = nullptr;
+      values_changed(h, Windows::drop);
     }
     pfv::mpsa_assemble_rhs(*h, in, d_src);
     h->stats.assemble_ms = tm.stop(s);
     h->have_mech_system = true;
-    h->active.P = &h->pat_Am;
-    h->active.val = h->val[PFV_MAT_MECH_SYSTEM].p;
-    h->active.diag = h->diag_m.p;
-    h->active.rhs = h->rhs_m.p;
-    h->active.n = h->nc * h->nd;
-    h->active_bs = h->nd;
-    h->active_is_grid = true;
-    h->active.valid = true;
+    activate(h, h->pat_Am, h->val[PFV_MAT_MECH_SYSTEM].p, h->diag_m.p, h->rhs_m.p, h->nc * h->nd, h->nd, true);
   });
 }
 
@@ -1833,6 +1788,41 @@ pfv_status pfv_sync(pfv_ctx* h) {
   return guarded(h, [&] { pfv::be_sync(h->stream); });
 }
 
+// The tail of pfv_set_system and pfv_csr_set_system: pat_user, val[PFV_MAT_USER_SYSTEM] and rhs_u hold the system.
+// Extracts the diagonal, refuses a column out of range or a zero diagonal, and makes the system the active one.
+static void user_system_ready(pfv_ctx* h) {
+  auto s = h->stream;
+  pfv::CsrPattern& P = h->pat_user;
+  const int64_t n = P.nrows;
+  const int32_t* ip = P.indptr.p;
+  const int32_t* ix = P.indices.p;
+  double* v = h->val[PFV_MAT_USER_SYSTEM].p;
+  double* dg = h->diag_u.ensure(n);
+  int32_t* st = h->status.ensure(16);
+  pfv::be_memset(st, 0, sizeof(int32_t) * 4, s);
+  pfv::parallel_for(s, n, PFV_LAMBDA(int64_t i) {
+    double d = 0.0;
+    bool bad = false;
+    for (int e = ip[i]; e < ip[i + 1]; ++e) {
+      const int cidx = ix[e];
+      if (cidx < 0 || cidx >= n) bad = true;
+      else if (cidx == i) d += v[e];
+    }
+    dg[i] = d;
+    if (bad) pfv::atomic_max_i32(st + 1, 1);
+    if (!(d != 0.0) || !(d == d)) pfv::atomic_max_i32(st + 0, (int32_t)(i < 0x7fffffff ? i + 1 : 0x7fffffff));
+  });
+  int32_t sth[2];
+  be_d2h(sth, st, sizeof(sth), s);
+  require(!sth[1], "column index out of range");
+  if (sth[0])
+    throw pfv::Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(sth[0] - 1) +
+                                              ": the Jacobi-preconditioned solver does not apply");
+  h->filled[PFV_MAT_USER_SYSTEM] = true;
+  values_changed(h, Windows::drop);  // (the user-system buffers are reused: same pointers, new matrix)
+  activate(h, P, v, dg, h->rhs_u.p, n, 1, false);
+}
+
 pfv_status pfv_set_system(pfv_ctx* h, int64_t n, const int32_t* indptr, const int32_t* indices,
                           const double* data, const double* rhs) {
   return guarded(h, [&] {
@@ -1848,49 +1838,14 @@ pfv_status pfv_set_system(pfv_ctx* h, int64_t n, const int32_t* indptr, const in
     int32_t* ix = P.indices.ensure(std::max<int64_t>(nnz, 1));
     double* v = h->val[PFV_MAT_USER_SYSTEM].ensure(std::max<int64_t>(nnz, 1));
     double* b = h->rhs_u.ensure(n);
-    double* dg = h->diag_u.ensure(n);
     be_h2d(ip, indptr, sizeof(int32_t) * (size_t)(n + 1), s);
     be_h2d(ix, indices, sizeof(int32_t) * (size_t)nnz, s);
     be_h2d(v, data, sizeof(double) * (size_t)nnz, s);
     be_h2d(b, rhs, sizeof(double) * (size_t)n, s);
-    int32_t* st = h->status.ensure(16);
-    pfv::be_memset(st, 0, sizeof(int32_t) * 4, s);
-    pfv::parallel_for(s, n, PFV_LAMBDA(int64_t i) {
-      double d = 0.0;
-      bool bad = false;
-      for (int e = ip[i]; e < ip[i + 1]; ++e) {
-        const int cidx = ix[e];
-        if (cidx < 0 || cidx >= n) bad = true;
-        else if (cidx == i) d += v[e];
-      }
-      dg[i] = d;
-      if (bad) pfv::atomic_max_i32(st + 1, 1);
-      if (!(d != 0.0) || !(d == d)) pfv::atomic_max_i32(st + 0, (int32_t)(i < 0x7fffffff ? i + 1 : 0x7fffffff));
-    });
-    int32_t sth[2];
-    be_d2h(sth, st, sizeof(sth), s);
-    require(!sth[1], "column index out of range");
-    if (sth[0])
-      throw pfv::Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(sth[0] - 1) +
-                                                ": the Jacobi-preconditioned solver does not apply");
     int mr = 0;
     for (int64_t i = 0; i < n; ++i) mr = std::max(mr, indptr[i + 1] - indptr[i]);
     P.max_row = mr;
-    h->filled[PFV_MAT_USER_SYSTEM] = true;
-    h->active.P = &P;
-    h->active.val = v;
-    h->active.diag = dg;
-    h->active.rhs = b;
-    h->active.n = n;
-    h->active_bs = 1;
-    if (h->amg) h->amg->valid = false;
-    h->nns_stale = true;  // (the near-null-space hierarchy too)
-      if (h->block_pc) h->block_pc->for_val = nullptr;
-    if (h->amg_block) h->amg_block->valid = false;
-    h->perm_for_val = nullptr;
-    h->win_for = h->win_rows_for = nullptr;
-    h->active_is_grid = false;
-    h->active.valid = true;
+    user_system_ready(h);
   });
 }
 
@@ -2254,10 +2209,7 @@ static pfv::LinSys solver_system(pfv_ctx* h, bool& permuted) {
     if (h->perm_for_val != sys.val) {
       pfv::permute_matrix(*h, sys, bs);
       h->perm_for_val = sys.val;
-      h->win_for = h->win_rows_for = nullptr;
-      if (h->amg) h->amg->valid = false;
-      h->nns_stale = true;  // (the near-null-space hierarchy too)
-      if (h->block_pc) h->block_pc->for_val = nullptr;  // (the copy's buffers are shared by the flow and mechanics systems)
+      values_changed(h, Windows::drop, true);  // (the copy's buffers are shared by all grid systems)
     }
     pfv::permute_vector(*h, sys.n, bs, sys.rhs, h->rhs_perm.ensure(sys.n), true);
     sys.P = &h->pat_perm;
@@ -2306,11 +2258,11 @@ pfv_status pfv_solve(pfv_ctx* h, int method, double rtol, int maxit, int restart
         h->stats.sweep_order_ms = h->sweep->order_ms;
       }
     }
-    if (h->have_transport && h->active.val == h->val[PFV_MAT_TRANSPORT_SYSTEM].p && h->transport_zero_diag >= 0)
+    if (transport_is_active(h) && h->transport_zero_diag >= 0)
       throw pfv::Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(h->transport_zero_diag) +
                                                 " of the transport system (a cell without outflow and without an "
                                                 "accumulation term): the Jacobi-preconditioned solver does not apply");
-    if (h->have_advdiff && h->active.val == h->val[PFV_MAT_ADVDIFF_SYSTEM].p && h->advdiff_zero_diag >= 0)
+    if (h->have_advdiff && active_is(h, PFV_MAT_ADVDIFF_SYSTEM) && h->advdiff_zero_diag >= 0)
       throw pfv::Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(h->advdiff_zero_diag) +
                                                 " of the advection-diffusion system: the solver does not apply");
     auto s = h->stream;
@@ -2408,7 +2360,7 @@ pfv_status pfv_solve(pfv_ctx* h, int method, double rtol, int maxit, int restart
     h->stats.solve_launches = (int64_t)(pfv::launch_counter().load(std::memory_order_relaxed) - launches_before_loop);
     if (permuted) pfv::permute_vector(*h, (int64_t)n, h->active_bs, dxs, dx, false);
     h->stats.solve_ms = tm.stop(s);
-    if (h->vectors_on_device) pfv::be_d2d(x, dx, n * sizeof(double), s); else be_d2h(x, dx, n * sizeof(double), s);
+    vec_out(h, x, dx, n);
   });
   if (info) {
     info->iterations = res.iterations;
@@ -2587,8 +2539,7 @@ pfv_status pfv_time_kernel(pfv_ctx* h, int kernel, int reps, double* avg_ms) {
       double* y = h->kry[8].ensure(n);
       pfv::be_d2d(x, h->rhs.p, n * sizeof(double), s);
       // what the Krylov loop launches (renumbered system, windowed kernel when the pattern allows it)
-      require(h->active.valid && h->active.P == &h->pat_A && h->active.val == h->val[PFV_MAT_SYSTEM].p,
-              "the flow system must be the active one");
+      require(active_is(h, PFV_MAT_SYSTEM) && h->active.P == &h->pat_A, "the flow system must be the active one");
       bool permuted = false;
       const pfv::LinSys sys = solver_system(h, permuted);
       pfv::sys_spmv(*h, sys, x, y);

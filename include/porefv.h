@@ -180,6 +180,10 @@ typedef struct {
                                      loop); after pfv_transport_advance: the number of such steps */
   int64_t sweep_direct_fallbacks; /* ... direct solves whose residual check failed and that went on with sweep-preconditioned
                                      GMRES from the swept x (counted the same way) */
+  int64_t transport_multi_components; /* last pfv_transport_advance_multi: n_comp */
+  int64_t transport_multi_direct_steps; /* ... steps taken entirely by one sweep and one residual check of all components */
+  int64_t transport_multi_fallback_components; /* ... component-steps solved by that component's own pfv_upwind_assemble +
+                                                  pfv_transport_advance (another preconditioner, a cyclic core, a failed check) */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -568,6 +572,25 @@ pfv_status pfv_upwind_assemble(pfv_ctx* h, const double* q, const double* bc_val
  * (pfv_stats.sweep_direct_steps), and the order is built by the first step. */
 pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rtol, int maxit, double* c,
                                  int32_t* steps_done, pfv_solve_info* last);
+/* n_steps implicit Euler steps of n_comp (1 .. 64, else PFV_ERR_ARGUMENT) quantities on one flux: component a solves
+ * (diag(accumulation[a]) + A) c[a] = accumulation[a] o c[a] - b_ref(bc_values[a]) + source[a] with A = div diag(q) U of
+ * the one-component discretization on the handle (pfv_upwind_discretize with num_components = 1).  All arrays are
+ * component-major: bc_values [n_comp][Nf], accumulation, source (may be NULL) and c (in and out) [n_comp][Nc]; q (Nf)
+ * NULL = the flux of the discretization.  On the device the vectors are cell-major and interleaved, v[i * n_comp + a];
+ * the transposition happens there.  The call does not need pfv_upwind_assemble and leaves no transport system behind:
+ * afterwards pfv_solve asks for an assembly, as after pfv_upwind_set_bc; the flow order stays.
+ *   With PFV_PRECOND_SWEEP selected and an acyclic flux, every step is one right-hand side, one sweep that carries
+ * all components (the matrix and the levels are read once, csrc/sweep.inc: sweep_apply_multi), one residual check of
+ * all of them and one host read; last[a].iterations = 1.  A component whose check fails is stepped from the state at
+ * the start of the step by pfv_upwind_assemble + pfv_transport_advance on its own arrays, the others keep their
+ * result.  With any other preconditioner, or a cyclic core, every component is stepped that way.
+ *   A zero or NaN diagonal A[i,i] + accumulation[a][i]: PFV_ERR_UNSUPPORTED naming the first such row and its first
+ * such component.  c holds the state after the last step completed by all components, steps_done that number of
+ * steps; last (n_comp entries, may be NULL) the info of every component's last solve.  pfv_stats:
+ * transport_multi_*, sweep_levels / sweep_launches / sweep_order_ms as after pfv_transport_advance. */
+pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, const double* bc_values,
+                                       const double* accumulation, const double* source, int n_steps, int method,
+                                       double rtol, int maxit, double* c, int32_t* steps_done, pfv_solve_info* last);
 
 /* ---- Advection-diffusion step on the device (csrc/advdiff.inc) ---------------------------------------------------
  * One handle carries the transport keyword: its diffusion discretization (pfv_mpfa_discretize or pfv_tpfa_discretize

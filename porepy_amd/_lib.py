@@ -49,7 +49,7 @@ EXPORTS = [
     "pfv_mpfa_set_permeability", "pfv_set_near_null_space", "pfv_amg_nns_level", "pfv_amg_level",
     "pfv_mpfa_face_flux", "pfv_upwind_set_bc", "pfv_upwind_discretize", "pfv_upwind_assemble", "pfv_transport_advance",
     "pfv_advdiff_assemble", "pfv_advdiff_advance", "pfv_advdiff_face_flux", "pfv_resident_flux",
-    "pfv_sweep_info",
+    "pfv_sweep_info", "pfv_transport_advance_multi",
 ]
 
 
@@ -81,7 +81,9 @@ class Stats(C.Structure):
                 ("advdiff_gmres_retries", C.c_int64),
                 ("sweep_levels", C.c_int64), ("sweep_core_cells", C.c_int64), ("sweep_launches", C.c_int64),
                 ("sweep_order_ms", C.c_double), ("sweep_direct_steps", C.c_int64),
-                ("sweep_direct_fallbacks", C.c_int64)]
+                ("sweep_direct_fallbacks", C.c_int64),
+                ("transport_multi_components", C.c_int64), ("transport_multi_direct_steps", C.c_int64),
+                ("transport_multi_fallback_components", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -296,6 +298,9 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_transport_advance.argtypes = [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(C.c_int32),
                                           C.POINTER(SolveInfo)]
     lib.pfv_transport_advance.restype = C.c_int
+    lib.pfv_transport_advance_multi.argtypes = [_h, _dp, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                _dp, C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
+    lib.pfv_transport_advance_multi.restype = C.c_int
     lib.pfv_advdiff_assemble.argtypes = [_h, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pfv_advdiff_assemble.restype = C.c_int
     lib.pfv_advdiff_advance.argtypes = [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(C.c_int32),
@@ -1362,6 +1367,48 @@ class Context:
                 self._dev(False)
         out = {"steps_done": done.value, "iterations": info.iterations, "converged": bool(info.converged),
                "rel_residual": info.rel_residual, "solve_ms": info.solve_ms}
+        if st != 0 and (raise_on_fail or st != 6):
+            self._check(st)
+        return c, out
+
+    def transport_advance_multi(self, c0, n_steps: int, accumulation, bc_values, q=None, source=None,
+                                method="bicgstab", rtol=1e-12, maxit=10000, raise_on_fail=True, precond="jacobi"):
+        """``n_steps`` implicit Euler steps of k quantities on the flux of the one-component upwind discretization on
+        this handle (pfv_transport_advance_multi).  ``c0``, ``accumulation`` and ``source`` (may be None): k x Nc,
+        ``bc_values``: k x Nf, ``q``: Nf or None (the flux of the discretization).  Returns (c, info) with c of shape
+        k x Nc and per-component lists ``iterations``, ``rel_residual``, ``converged`` in info.  ``precond="sweep"``
+        with an acyclic flux: one sweep per step carries all components."""
+        code = {"bicgstab": SOLVE_BICGSTAB, "gmres": SOLVE_GMRES}[method]
+        if precond not in ("jacobi", "sweep"):
+            raise ValueError('precond must be "jacobi" or "sweep"')
+        c = np.array(c0, dtype=np.float64, copy=True, order="C")
+        if c.ndim != 2 or c.shape[1] != self.nc:
+            raise ValueError(f"c0 must have shape (k, {self.nc}), not {c.shape}")
+        k = c.shape[0]
+        if not 1 <= k <= 64:
+            raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (c0 has shape {c.shape})")
+        arrays = []
+        for name, a, n, needed in (("accumulation", accumulation, self.nc, True), ("bc_values", bc_values, self.nf, True),
+                                   ("source", source, self.nc, False)):
+            if a is None:
+                if needed:
+                    raise ValueError(f"{name} is required")
+                arrays.append(None)
+                continue
+            a = _f64(a)
+            if a.shape != (k, n):
+                raise ValueError(f"{name} must have shape ({k}, {n}), not {a.shape}")
+            arrays.append(a)
+        acc, bv, src = arrays
+        kq, pq = self._vec(q, self.nf, "the flux array", False)
+        self._select_precond(precond)
+        done, infos = C.c_int32(0), (SolveInfo * k)()
+        st = self.lib.pfv_transport_advance_multi(self._h, pq, k, _ptr(bv, _dp), _ptr(acc, _dp), _ptr(src, _dp),
+                                                  int(n_steps), code, float(rtol), int(maxit), _ptr(c, _dp),
+                                                  C.byref(done), infos)
+        out = {"steps_done": done.value, "iterations": [i.iterations for i in infos],
+               "converged": [bool(i.converged) for i in infos], "rel_residual": [i.rel_residual for i in infos],
+               "solve_ms": [i.solve_ms for i in infos]}
         if st != 0 and (raise_on_fail or st != 6):
             self._check(st)
         return c, out

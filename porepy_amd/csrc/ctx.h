@@ -329,6 +329,10 @@ struct pfv_ctx_impl {
   Buf<double> rhs_t, diag_t, bref_t, acc_t, src_t, c_t, c_keep, q_t, bc_t;
   bool have_acc_t = false, have_src_t = false;
   int64_t transport_zero_diag = -1;  // first row of the transport system with a zero diagonal (-1: none)
+  // k components on one flux (pfv_transport_advance_multi): the caller's arrays as they came, component-major [k][n] ...
+  Buf<double> mc_q, mc_bc, mc_acc, mc_src, mc_c;
+  // ... and the vectors of the step, cell-major interleaved v[i * k + a]
+  Buf<double> mc_acc_i, mc_src_i, mc_bref_i, mc_x, mc_z, mc_r, mc_nrm, mc_col;
 
   // ---- advection-diffusion (advdiff.inc): S = diag(acc) + div flux_D + w div diag(q) U on pat_A -------------------
   bool have_advdiff = false;         // val[PFV_MAT_ADVDIFF_SYSTEM], adv_diag, adv_rhs hold a system of the discretization

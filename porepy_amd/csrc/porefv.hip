@@ -853,12 +853,13 @@ static void upwind_supported(pfv_ctx* h) {
 }
 
 // the transport system no longer belongs to the discretization on the handle: it must not stay the active system
-static void upwind_drop_transport(pfv_ctx* h) {
+// (keep_order: the discretization and its flux stay, only the assembled values go -- pfv_transport_advance_multi)
+static void upwind_drop_transport(pfv_ctx* h, bool keep_order = false) {
   if (h->have_transport && active_is(h, PFV_MAT_TRANSPORT_SYSTEM)) h->active.valid = false;
   h->have_transport = false;
   h->filled[PFV_MAT_TRANSPORT_SYSTEM] = false;
   h->transport_zero_diag = -1;
-  if (h->sweep && h->sweep->for_system == PFV_MAT_TRANSPORT_SYSTEM) h->sweep->valid = false;
+  if (!keep_order && h->sweep && h->sweep->for_system == PFV_MAT_TRANSPORT_SYSTEM) h->sweep->valid = false;
 }
 
 // An assembly of system `which` with the flux d_q: a flow order built for another system, or for a flux with other
@@ -1086,6 +1087,226 @@ pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rto
     h->stats.sweep_order_ms = tot.order_ms;
   }
   return st;
+}
+
+// ---- k components on one flux -----------------------------------------------------------------------------------------
+// Fast path (PFV_PRECOND_SWEEP, acyclic flux): per step one right-hand side, one sweep and one residual check for all
+// components, in the caller's numbering on pat_T, one host read of 2k numbers.  Everything else -- another
+// preconditioner, a cyclic core, a component whose check fails -- is pfv_upwind_assemble + pfv_transport_advance on
+// that component's arrays, which lie on the device component by component as the caller passed them.
+pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, const double* bc_values,
+                                       const double* accumulation, const double* source, int n_steps, int method,
+                                       double rtol, int maxit, double* c, int32_t* steps_done, pfv_solve_info* last) {
+  if (steps_done) *steps_done = 0;
+  const int k = n_comp;
+  std::unique_ptr<pfv::Timer> tm;
+  bool fast = false, touched = false;
+  double order_ms = 0.0;
+  const double* d_q = nullptr;
+  size_t nc = 0, nf = 0;
+  pfv_status st = guarded(h, [&] {
+    upwind_supported(h);
+    require(h->have_upwind, "pfv_upwind_discretize first");
+    require(h->upw_ncomp == 1, "the components share one discretization: pfv_upwind_discretize with num_components = 1");
+    require(n_comp >= 1 && n_comp <= 64, "n_comp must lie in 1 .. 64");
+    require(bc_values && accumulation && c, "bc_values, accumulation and c are required");
+    require(n_steps >= 0, "bad argument");
+    require(method == PFV_SOLVE_BICGSTAB || method == PFV_SOLVE_GMRES,
+            "method must be PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES (the transport matrix is not symmetric)");
+    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
+    nc = (size_t)h->nc;
+    nf = (size_t)h->nf;
+    if ((int64_t)nc * k >= (int64_t(1) << 31) || (int64_t)nf * k >= (int64_t(1) << 31))
+      throw Error(PFV_ERR_UNSUPPORTED, "n_comp x cells (faces) beyond int32 indices");
+    if (q) vec_in(h, h->mc_q.ensure(nf), q, nf);
+    vec_in(h, h->mc_bc.ensure(k * nf), bc_values, k * nf);
+    vec_in(h, h->mc_acc.ensure(k * nc), accumulation, k * nc);
+    if (source) vec_in(h, h->mc_src.ensure(k * nc), source, k * nc);
+    vec_in(h, h->mc_c.ensure(k * nc), c, k * nc);
+    d_q = q ? h->mc_q.p : h->upw_q.p;
+    tm = std::make_unique<pfv::Timer>();
+    tm->start(h->stream);
+    // the values every component shares, without accumulation: once per call
+    upwind_drop_transport(h, true);
+    touched = true;
+    pfv::upwind_assemble(*h, d_q, h->mc_bc.p, nullptr, nullptr, nullptr);
+    values_changed(h, Windows::drop);
+    pfv::multi_interleave(*h, (int64_t)nc, k, h->mc_acc.p, h->mc_acc_i.ensure(k * nc));
+    if (source) pfv::multi_interleave(*h, (int64_t)nc, k, h->mc_src.p, h->mc_src_i.ensure(k * nc));
+    pfv::multi_interleave(*h, (int64_t)nc, k, h->mc_c.p, h->mc_x.ensure(k * nc));
+    h->mc_z.ensure(k * nc);
+    h->mc_r.ensure(k * nc);
+    h->mc_col.ensure(nc);
+    h->mc_nrm.ensure(2 * (size_t)k);
+    const int64_t zd = pfv::upwind_zero_diag_multi(*h, k, h->diag_t.p, h->mc_acc_i.p);
+    if (zd >= 0)
+      throw Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(zd / k) + ", component " +
+                                           std::to_string(zd % k) + " of the transport system (a cell without outflow "
+                                           "and without an accumulation term): the solvers do not apply");
+    pfv::upwind_bref_multi(*h, k, d_q, h->mc_bc.p, h->mc_bref_i.ensure(k * nc));
+    if (h->precond == PFV_PRECOND_SWEEP) {
+      // the order of the flux, built on first use and kept while assemblies bring the same edges (sweep_note_assembly)
+      if (!h->sweep) h->sweep = std::make_unique<pfv::Sweep>();
+      pfv::Sweep& sw = *h->sweep;
+      if (sw.valid && (sw.for_system != PFV_MAT_TRANSPORT_SYSTEM || !pfv::sweep_same_edges(*h, sw, d_q))) sw.valid = false;
+      if (!sw.valid) {
+        pfv::sweep_build_order(*h, sw, d_q, PFV_MAT_TRANSPORT_SYSTEM);
+        order_ms += sw.order_ms;
+      }
+      fast = sw.n_core == 0;
+    }
+  });
+  if (st != PFV_OK) {
+    if (touched) upwind_drop_transport(h, true);  // (the values of no component's system: not to be solved with)
+    return st;
+  }
+
+  const bool caller_on_device = h->vectors_on_device;
+  const double* src_i = source ? h->mc_src_i.p : nullptr;
+  int64_t direct_steps = 0, fallback = 0, iterations = 0, retries = 0;
+  std::vector<pfv_solve_info> info((size_t)k);
+  // `steps` steps of component a alone, from and to `col`, as pfv_upwind_assemble + pfv_transport_advance do them
+  auto component_steps = [&](int a, int steps, int32_t& done) {
+    h->vectors_on_device = true;
+    pfv_status r = pfv_upwind_assemble(h, q ? h->mc_q.p : nullptr, h->mc_bc.p + (size_t)a * nf,
+                                       h->mc_acc.p + (size_t)a * nc, nullptr,
+                                       source ? h->mc_src.p + (size_t)a * nc : nullptr, nullptr);
+    done = 0;
+    if (r == PFV_OK) {
+      r = pfv_transport_advance(h, steps, method, rtol, maxit, h->mc_col.p, &done, &info[(size_t)a]);
+      iterations += h->stats.transport_iterations;
+      retries += h->stats.transport_gmres_retries;
+      order_ms += h->stats.sweep_order_ms;
+    }
+    h->vectors_on_device = caller_on_device;
+    return r;
+  };
+  int32_t completed = 0;
+  std::string err;
+  if (fast) {
+    bool shared_values = true;  // PFV_MAT_TRANSPORT_SYSTEM holds A without accumulation
+    std::vector<double> nrm(2 * (size_t)k);
+    for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
+      st = guarded(h, [&] {
+        if (!shared_values) {
+          upwind_drop_transport(h, true);
+          pfv::upwind_assemble(*h, d_q, h->mc_bc.p, nullptr, nullptr, nullptr);
+          values_changed(h, Windows::drop);
+          shared_values = true;
+        }
+        pfv::Sweep& sw = *h->sweep;
+        if (!sw.valid) {
+          pfv::sweep_build_order(*h, sw, d_q, PFV_MAT_TRANSPORT_SYSTEM);
+          order_ms += sw.order_ms;
+        }
+        pfv::sweep_set_numbering(*h, sw, false);  // (a component's own solve in between works in the renumbered system)
+        pfv::sweep_make_plan(sw);
+        const double* val = h->val[PFV_MAT_TRANSPORT_SYSTEM].p;
+        pfv::upwind_step_rhs_multi(*h, k, h->mc_acc_i.p, src_i, h->mc_bref_i.p, h->mc_x.p, h->mc_r.p);
+        pfv::sweep_apply_multi(*h, sw, h->pat_T, val, h->diag_t.p, h->mc_acc_i.p, k, h->mc_r.p, h->mc_z.p);
+        pfv::sweep_residual_norms_multi(*h, h->pat_T, val, h->mc_acc_i.p, k, h->mc_r.p, h->mc_z.p, h->mc_nrm.p);
+        be_d2h(nrm.data(), h->mc_nrm.p, sizeof(double) * 2 * (size_t)k, h->stream);
+      });
+      if (st != PFV_OK) break;
+      int failed = 0;
+      for (int a = 0; a < k && st == PFV_OK; ++a) {
+        const double bb = nrm[(size_t)a], rr = nrm[(size_t)k + a];
+        pfv_solve_info& ia = info[(size_t)a];
+        ia = pfv_solve_info{};
+        ia.iterations = 1;
+        if (!(bb > 0.0)) {  // r_a = 0 -> the sweep has left 0
+          ia.converged = bb == 0.0 ? 1 : 0;
+        } else {
+          ia.rel_residual = std::sqrt(rr / bb);
+          ia.converged = rr <= rtol * rtol * bb ? 1 : 0;
+        }
+        if (ia.converged) {
+          ++iterations;
+          continue;
+        }
+        // this component alone, from the state at the start of the step
+        ++failed;
+        ++fallback;
+        shared_values = false;
+        st = guarded(h, [&] { pfv::multi_get_column(*h, (int64_t)nc, k, a, h->mc_x.p, h->mc_col.p); });
+        int32_t done = 0;
+        if (st == PFV_OK) st = component_steps(a, 1, done);
+        if (st == PFV_OK) st = guarded(h, [&] { pfv::multi_set_column(*h, (int64_t)nc, k, a, h->mc_col.p, h->mc_z.p); });
+      }
+      if (st != PFV_OK) break;
+      std::swap(h->mc_x.p, h->mc_z.p);
+      std::swap(h->mc_x.cap, h->mc_z.cap);
+      ++completed;
+      if (!failed) ++direct_steps;
+    }
+    if (st != PFV_OK) err = h->err;
+  } else {
+    // component by component; should one stop early, all are taken again from the start to the step it reached, so
+    // that c is one state of all components
+    int target = n_steps;
+    for (;;) {
+      int32_t least = target;
+      pfv_status first = PFV_OK;
+      for (int a = 0; a < k; ++a) {
+        pfv_status r = guarded(h, [&] { pfv::multi_get_column(*h, (int64_t)nc, k, a, h->mc_x.p, h->mc_col.p); });
+        int32_t done = 0;
+        if (r == PFV_OK) r = component_steps(a, target, done);
+        if (r == PFV_OK) r = guarded(h, [&] { pfv::multi_set_column(*h, (int64_t)nc, k, a, h->mc_col.p, h->mc_z.p); });
+        if (r != PFV_OK) {
+          if (first == PFV_OK && st == PFV_OK) {
+            first = r;
+            err = h->err;
+          }
+          least = std::min(least, done);
+          break;
+        }
+      }
+      if (first != PFV_OK) st = first;
+      if (least == target) break;
+      target = least;
+    }
+    completed = target;
+    fallback = (int64_t)k * target;
+    if (target > 0) {
+      std::swap(h->mc_x.p, h->mc_z.p);
+      std::swap(h->mc_x.cap, h->mc_z.cap);
+    }
+  }
+  double ms = 0.0;
+  const pfv_status st2 = guarded(h, [&] {
+    ms = tm->stop(h->stream);
+    tm.reset();
+    pfv::multi_deinterleave(*h, (int64_t)nc, k, h->mc_x.p, h->mc_c.p);
+    vec_out(h, c, h->mc_c.p, k * nc);
+    pfv::be_sync(h->stream);
+    upwind_drop_transport(h, true);
+  });
+  if (steps_done) *steps_done = completed;
+  if (last) {
+    for (int a = 0; a < k; ++a) {
+      last[a] = info[(size_t)a];
+      if (fast && last[a].solve_ms == 0.0 && completed > 0) last[a].solve_ms = ms / completed;
+    }
+  }
+  h->stats.transport_advance_ms = ms;
+  h->stats.transport_iterations = iterations;
+  h->stats.transport_gmres_retries = retries;
+  h->stats.transport_multi_components = k;
+  h->stats.transport_multi_direct_steps = direct_steps;
+  h->stats.transport_multi_fallback_components = fallback;
+  h->stats.sweep_direct_steps = direct_steps;
+  if (h->precond == PFV_PRECOND_SWEEP && h->sweep && h->sweep->valid) {
+    pfv::sweep_make_plan(*h->sweep);
+    h->stats.sweep_levels = h->sweep->nlev;
+    h->stats.sweep_core_cells = h->sweep->n_core;
+    h->stats.sweep_launches = (int64_t)h->sweep->plan.size();
+    h->stats.sweep_order_ms = order_ms;
+  }
+  if (st != PFV_OK) {
+    h->err = err;
+    return st;
+  }
+  return st2;
 }
 
 // ---- advection-diffusion on one handle (advdiff.inc) -----------------------------------------------------------

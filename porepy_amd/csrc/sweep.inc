@@ -325,6 +325,117 @@ static void sweep_residual_norms(pfv_ctx_impl& c, int64_t n, const double* b, co
   });
 }
 
+// ---- k vectors per sweep (pfv_transport_advance_multi).  The k systems share the pattern, the off-diagonal values and
+// the level test; they differ in the diagonal A[i,i] + acc[i,a] and the right-hand side.  Vectors are interleaved,
+// v[i * k + a].  One work item per (row, component) of a level: the k items of a row load val[e], ix[e] and lev[j] from
+// the same address and z[j, 0..k) as one contiguous run, and a level has k times the work items of the single sweep.
+// The order and the launch plan are those of sweep_apply; the sum runs in stored order, as in sweep_row.
+PFV_FN void sweep_row_multi(int32_t i, int a, int k, const int32_t* ip, const int32_t* ix, const double* val,
+                            const double* diag, const double* acc, const int32_t* lev, const double* r, double* z) {
+  const int32_t li = lev[i];
+  double sum = 0.0;
+  for (int e = ip[i]; e < ip[i + 1]; ++e) {
+    const int32_t j = ix[e];
+    if (lev[j] < li) sum += val[e] * z[(int64_t)j * k + a];
+  }
+  const int64_t p = (int64_t)i * k + a;
+  z[p] = (r[p] - sum) / (diag[i] + acc[p]);
+}
+
+static void sweep_apply_multi(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* val,
+                              const double* diag, const double* acc, int k, const double* in, double* out) {
+  stream_t s = c.stream;
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* lev = sw.lev(sw.permuted);
+  const int32_t* ord = sw.ord(sw.permuted);
+  const int32_t* lp = sw.lptr;
+  for (const Sweep::Seg& g : sw.plan) {
+    if (g.l1 - g.l0 == 1) {
+      const int32_t a0 = sw.h_lptr[(size_t)g.l0], m = sw.h_lptr[(size_t)g.l1] - a0;
+      parallel_for(s, (int64_t)m * k, PFV_LAMBDA(int64_t t) {
+        sweep_row_multi(ord[a0 + t / k], (int)(t % k), k, ip, ix, val, diag, acc, lev, in, out);
+      });
+    } else {
+      const int l0 = g.l0, l1 = g.l1;
+      block_for<256>(s, 1, 0, PFV_LAMBDA(const WaveCtx& w) {
+        for (int l = l0; l < l1; ++l) {
+          const int32_t a0 = lp[l], m = lp[l + 1] - a0;
+          PFV_LANES(t, m * k) sweep_row_multi(ord[a0 + t / k], t % k, k, ip, ix, val, diag, acc, lev, in, out);
+          w.sync();  // (the next level reads what this one wrote: same workgroup, same CU)
+        }
+      });
+    }
+  }
+}
+
+// The residual check of all k components in one pass: t[i,a] = sum_e A[i,e] x[j,a] + acc[i,a] x[i,a] in stored order,
+// out[a] = (r_a, r_a), out[k + a] = (r_a - t_a, r_a - t_a).  Fixed partition, fixed reduction order: a workgroup takes a
+// range of rows, slot g * k + a of it the rows lo + g, lo + g + G, ... of component a (G = 256 / k), and the G sums of a
+// component are folded pairwise; then one workgroup per number adds the workgroups' partial sums as
+// sweep_residual_norms does.
+static void sweep_residual_norms_multi(pfv_ctx_impl& c, const CsrPattern& P, const double* val, const double* acc,
+                                       int k, const double* r, const double* x, double* out) {
+  stream_t s = c.stream;
+  const int64_t n = P.nrows;
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int nb = (int)std::min<int64_t>(kGmresBlocks, (n * k + 2047) / 2048);
+  const int G = 256 / k, slots = G * k;
+  int fold = 1;
+  while (fold < G) fold <<= 1;
+  double* partial = c.red.ensure(2 * (size_t)k * kGmresBlocks + 64);
+  block_for<256>(s, nb, 2 * 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& w) {
+    double* sh = reinterpret_cast<double*>(w.lds);
+    const int64_t blk = w.item;
+    const int64_t lo = n * blk / nb, hi = n * (blk + 1) / nb;
+    PFV_LANES(slot, slots) {
+      const int a = slot % k, g = slot / k;
+      double a0 = 0.0, a1 = 0.0;
+      for (int64_t i = lo + g; i < hi; i += G) {
+        double t = 0.0;
+        for (int e = ip[i]; e < ip[i + 1]; ++e) t += val[e] * x[(int64_t)ix[e] * k + a];
+        const int64_t p = i * k + a;
+        t += acc[p] * x[p];
+        const double ri = r[p], d = ri - t;
+        a0 += ri * ri;
+        a1 += d * d;
+      }
+      sh[slot] = a0;
+      sh[256 + slot] = a1;
+    }
+    w.sync();
+    for (int o = fold >> 1; o > 0; o >>= 1) {
+      PFV_LANES(slot, slots) {
+        if (slot / k < o && slot / k + o < G) {
+          sh[slot] += sh[slot + o * k];
+          sh[256 + slot] += sh[256 + slot + o * k];
+        }
+      }
+      w.sync();
+    }
+    PFV_LANES(a, k) {
+      partial[(int64_t)a * nb + blk] = sh[a];
+      partial[(int64_t)(k + a) * nb + blk] = sh[256 + a];
+    }
+    w.sync();
+  });
+  block_for<256>(s, 2 * k, 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& wc) {
+    double* sh = reinterpret_cast<double*>(wc.lds);
+    const int64_t m = wc.item;
+    double a = 0.0;
+    for (int i = wc.lane; i < nb; i += wc.width) a += partial[m * nb + i];
+    sh[wc.lane] = a;
+    wc.sync();
+    for (int o = wc.width >> 1; o > 0; o >>= 1) {
+      if (wc.lane < o) sh[wc.lane] += sh[wc.lane + o];
+      wc.sync();
+    }
+    if (wc.lane0()) out[m] = sh[0];
+    wc.sync();
+  });
+}
+
 // The direct solve of the transport system of an acyclic flux: x = M^-1 b with M = S, then the true residual.  Should
 // the check fail (a flux array in the assembly that disagrees with the discretization's, NaN entries), GMRES
 // preconditioned by the sweep goes on from that x.

@@ -297,4 +297,73 @@ static void upwind_step_rhs(pfv_ctx_impl& c, const double* d_c) {
   });
 }
 
+// ---- (e) k components on one flux (pfv_transport_advance_multi).  Every multi-component vector on the device is
+// cell-major and interleaved, v[i * k + a]: the k values a row needs from an upstream cell are one contiguous run.
+// The caller's arrays are component-major [k][n]; they are transposed here, on the device, on the way in and out.
+static void multi_interleave(pfv_ctx_impl& c, int64_t n, int k, const double* by_comp, double* by_cell) {
+  parallel_for(c.stream, n * k, PFV_LAMBDA(int64_t t) { by_cell[t] = by_comp[(t % k) * n + t / k]; });
+}
+
+static void multi_deinterleave(pfv_ctx_impl& c, int64_t n, int k, const double* by_cell, double* by_comp) {
+  parallel_for(c.stream, n * k, PFV_LAMBDA(int64_t t) { by_comp[t] = by_cell[(t % n) * k + t / n]; });
+}
+
+// column a of an interleaved vector <-> a plain vector of n values
+static void multi_get_column(pfv_ctx_impl& c, int64_t n, int k, int a, const double* by_cell, double* col) {
+  parallel_for(c.stream, n, PFV_LAMBDA(int64_t i) { col[i] = by_cell[i * k + a]; });
+}
+
+static void multi_set_column(pfv_ctx_impl& c, int64_t n, int k, int a, const double* col, double* by_cell) {
+  parallel_for(c.stream, n, PFV_LAMBDA(int64_t i) { by_cell[i * k + a] = col[i]; });
+}
+
+// b_ref of every component from its boundary values bc[a][f], by the rule and in the order of upwind_assemble
+static void upwind_bref_multi(pfv_ctx_impl& c, int k, const double* d_q, const double* bc, double* bref) {
+  const int64_t nc = c.nc, nf = c.nf;
+  const int32_t* cf_ptr = c.cf_ptr;
+  const int32_t* cf_idx = c.cf_idx;
+  const int8_t* cf_sgn = c.cf_sgn;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* cnt = c.upw_cnt;
+  parallel_for(c.stream, nc * k, PFV_LAMBDA(int64_t t) {
+    const int64_t cell = t / k, a = t % k;
+    double b = 0.0;
+    for (int e = cf_ptr[cell]; e < cf_ptr[cell + 1]; ++e) {
+      const int f = cf_idx[e];
+      const unsigned cl = cls[f];
+      if (cl & (UPW_NEU | UPW_DIRIN)) {
+        double m = 0.0;
+        if (cl & UPW_NEU) m = (double)(cnt[f] - cnt[nf + f]);
+        if (cl & UPW_DIRIN) m += 1.0 * d_q[f];
+        b += (double)cf_sgn[e] * (m * bc[a * nf + f]);
+      }
+    }
+    bref[t] = b;
+  });
+}
+
+// first (row, component), as row * k + component, whose diagonal A[i,i] + acc[i,a] is zero or NaN; -1: none
+static int64_t upwind_zero_diag_multi(pfv_ctx_impl& c, int k, const double* diag, const double* acc) {
+  stream_t s = c.stream;
+  int32_t* st = c.status.ensure(16);
+  be_memset(st, 0x7f, sizeof(int32_t), s);
+  parallel_for(s, c.nc * k, PFV_LAMBDA(int64_t t) {
+    const double d = diag[t / k] + acc[t];
+    if (!(d != 0.0) || !(d == d)) atomic_min_i32(st, (int32_t)t);
+  });
+  const int32_t zd = read_scalar<int32_t>(s, st);
+  return zd == 0x7f7f7f7f ? -1 : (int64_t)zd;
+}
+
+// right-hand side of one implicit Euler step of all components: the expression of upwind_step_rhs
+static void upwind_step_rhs_multi(pfv_ctx_impl& c, int k, const double* acc, const double* src, const double* bref,
+                                  const double* x, double* rhs) {
+  parallel_for(c.stream, c.nc * k, PFV_LAMBDA(int64_t t) {
+    double r = acc[t] * x[t];
+    r -= bref[t];
+    if (src) r += src[t];
+    rhs[t] = r;
+  });
+}
+
 }  // namespace pfv

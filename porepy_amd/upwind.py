@@ -178,6 +178,51 @@ class Upwind:
         return self.context(sd).transport_advance(c0, n_steps, method=method, rtol=rtol, maxit=maxit,
                                                   raise_on_fail=raise_on_fail, precond=precond)
 
+    def advance_components(self, sd, data: dict, c0, n_steps: int, accumulation, bc_values=None, source=None,
+                           method: str = "bicgstab", rtol: float = 1e-12, maxit: int = 20000,
+                           raise_on_fail: bool = True, precond: str = "jacobi"):
+        """``n_steps`` implicit Euler steps of k quantities carried by the one flux of the (one-component)
+        discretization: solutes with different retardation, a tracer and a temperature.  ``c0``: (k, Nc).
+        ``accumulation``: (Nc,) shared or (k, Nc).  ``bc_values``: None (the keyword's for every component), (Nf,) or
+        (k, Nf).  ``source``: None, (Nc,) or (k, Nc).  Returns (c, info): c of shape (k, Nc), info["steps_done"] the
+        steps completed by all components and the per-component lists "iterations", "rel_residual", "converged".
+
+        ``precond="sweep"`` on an acyclic flux: every step is ONE substitution in flow order that carries all k
+        components -- the matrix, the levels and the launches are those of a single component
+        (``stats()["transport_multi_direct_steps"]``).  Any other case -- ``precond="jacobi"``, a cyclic core, a
+        component whose residual check fails (``stats()["transport_multi_fallback_components"]``) -- steps the component
+        as ``advance`` would.  Afterwards the handle holds no assembled transport system."""
+        pd = data[PARAMETERS][self.keyword]
+        c0 = np.asarray(c0, dtype=np.float64)
+        nc, nf = sd.num_cells, sd.num_faces
+        if c0.ndim != 2 or c0.shape[1] != nc:
+            raise ValueError(f"c0 must have shape (k, {nc}), not {c0.shape}")
+        k = c0.shape[0]
+        if not 1 <= k <= 64:
+            raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (c0 has shape {c0.shape})")
+
+        def per_component(name, a, n):
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape == (n,):
+                return np.broadcast_to(a, (k, n))
+            if a.shape != (k, n):
+                raise ValueError(f"{name} must have shape ({n},) or ({k}, {n}), not {a.shape}")
+            return a
+
+        if accumulation is None:
+            raise ValueError("accumulation is required")
+        acc = per_component("accumulation", accumulation, nc)
+        bv = per_component("bc_values", pd["bc_values"] if bc_values is None else bc_values, nf)
+        src = None if source is None else per_component("source", source, nc)
+        try:
+            return self.context(sd).transport_advance_multi(c0, n_steps, acc, bv, q=self._flux(sd, pd), source=src,
+                                                            method=method, rtol=rtol, maxit=maxit,
+                                                            raise_on_fail=raise_on_fail, precond=precond)
+        except _lib.PorefvError as e:
+            if e.status == 4:
+                raise ValueError(e.message) from None
+            raise
+
 
 def as_porepy_upwind(device: int = 0, library=None):
     """Subclass of the reference's ``pp.Upwind`` whose discretization and assembly run on the device; rebind with

@@ -6,11 +6,16 @@ the same chain on the host with scipy, measured in the same run:
 Device times are HIP-event times from pfv_stats; the host times are wall clock.  Prints one JSON line.  A measurement,
 not a test: no thresholds.
 
-    python tools/bench_transport.py [--n-side 69] [--steps 20] [--no-host] [--precond sweep]
+    python tools/bench_transport.py [--n-side 69] [--steps 20] [--no-host] [--precond sweep] [--components 8]
 
 --precond sweep: after the Jacobi-BiCGStab steps, the same steps from the same state with the flow-ordered sweep
 (PFV_PRECOND_SWEEP) -- order-build ms, levels, core cells, launches per sweep, ms per step -- and again with one launch
 per level (PFV_SWEEP_MERGE=0); both figures of the comparison come from this one run on the same inputs.
+
+--components K (with --precond sweep; a comma-separated list runs several K): K quantities with retardation 1 + a / 2
+and their own inflow values, first as K single assemble + advance(precond="sweep") runs, then as ONE
+transport_advance_multi from the same state on the same handle: ms per step of both (HIP events, best and median of
+--reps), levels and launches per sweep, and the largest difference between the two results.
 """
 from __future__ import annotations
 
@@ -36,6 +41,8 @@ def main():
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--precond", choices=["jacobi", "sweep"], default="jacobi",
                     help="sweep: also time the steps with the flow-ordered sweep, next to the Jacobi-BiCGStab ones")
+    ap.add_argument("--components", default="",
+                    help="K or K1,K2,...: K single sweep runs against one multi-component run (needs --precond sweep)")
     ap.add_argument("--emulation", action="store_true", help="run on the host-emulation build (plumbing check)")
     a = ap.parse_args()
     lib = None
@@ -99,6 +106,38 @@ def main():
                         "rel_residual_last_step": sinfo["rel_residual"],
                         "max_diff_to_jacobi_bicgstab": float(np.abs(cs - c).max())}
         del os.environ["PFV_SWEEP_MERGE"]
+        out["components"] = []
+        for kc in [int(v) for v in a.components.split(",") if v]:
+            acc_k = np.array([(1.0 + 0.5 * j) * acc for j in range(kc)])
+            bv_k = np.array([tbv * (j + 1) / kc for j in range(kc)])
+            c0_k = rng.random((kc, nc))
+            single_ms, multi_ms = [], []
+            for _ in range(a.reps + 1):  # (the first repeat warms up and is dropped)
+                ms, cs_k = 0.0, np.empty_like(c0_k)
+                for j in range(kc):
+                    ctx.upwind_assemble(bv_k[j], None, accumulation=acc_k[j])
+                    ms += ctx.stats()["transport_assemble_ms"]
+                    cs_k[j], sinfo = ctx.transport_advance(c0_k[j], a.steps, rtol=1e-10, raise_on_fail=False, precond="sweep")
+                    ms += ctx.stats()["transport_advance_ms"]
+                single_stats = ctx.stats()
+                single_ms.append(ms / max(a.steps, 1))
+                cm_k, minfo = ctx.transport_advance_multi(c0_k, a.steps, acc_k, bv_k, rtol=1e-10, raise_on_fail=False,
+                                                          precond="sweep")
+                ms_ = ctx.stats()
+                multi_ms.append(ms_["transport_advance_ms"] / max(a.steps, 1))
+            single_ms, multi_ms = single_ms[1:], multi_ms[1:]
+            out["components"].append({
+                "k": kc, "steps_done": minfo["steps_done"],
+                "single_runs_ms_per_step": (min(single_ms), float(np.median(single_ms))),
+                "multi_ms_per_step": (min(multi_ms), float(np.median(multi_ms))),
+                "levels": ms_["sweep_levels"], "launches_per_sweep": ms_["sweep_launches"],
+                "launches_per_sweep_single": single_stats["sweep_launches"],
+                "direct_steps": ms_["transport_multi_direct_steps"],
+                "fallback_components": ms_["transport_multi_fallback_components"],
+                "max_rel_residual_last_step": max(minfo["rel_residual"]),
+                "max_diff_multi_to_single": float(np.abs(cm_k - cs_k).max())})
+        if a.components:
+            ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the multi-component call leaves no system behind)
     # bytes each kernel has to move at least ("Upwind advection"): the fraction of a stream rate follows
     nnz_flux = ctx.matrix_info(_lib.MAT_FLUX)[2]
     nnz_bound = ctx.matrix_info(_lib.MAT_BOUND_FLUX)[2]

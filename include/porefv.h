@@ -84,6 +84,14 @@ enum { PFV_PRECOND_JACOBI = 0, PFV_PRECOND_AMG = 1, PFV_PRECOND_BLOCK = 2,
        PFV_PRECOND_SWEEP = 4    /* one substitution in flow order (csrc/sweep.inc): transport and advection-diffusion
                                    systems only; exact for the transport system of an acyclic flux (see pfv_sweep_info) */ };
 
+/* flux functions f(s) of pfv_transport_advance_nl (csrc/fluxfn.h), nondecreasing on [0, 1] */
+enum {
+  PFV_FLUXFN_LINEAR = 0, /* f(s) = s, no parameters: the linear transport step */
+  PFV_FLUXFN_COREY = 1,  /* 6 parameters s_wr, s_nr, n_w, n_n, mu_w, mu_n: s_e = clamp((s - s_wr) / (1 - s_wr - s_nr), 0, 1),
+                            f = l_w / (l_w + l_n) with l_w = s_e^n_w / mu_w, l_n = (1 - s_e)^n_n / mu_n */
+  PFV_FLUXFN_TABLE = 2   /* m = 2 .. 1024 finite, nondecreasing values on uniform knots over [0, 1], piecewise linear */
+};
+
 /* flags for pfv_mpfa_discretize */
 enum {
   PFV_DISCR_REBUILD_TOPOLOGY = 1, /* redo sub-cell topology + CSR symbolic phase even if
@@ -184,6 +192,9 @@ typedef struct {
   int64_t transport_multi_direct_steps; /* ... steps taken entirely by one sweep and one residual check of all components */
   int64_t transport_multi_fallback_components; /* ... component-steps solved by that component's own pfv_upwind_assemble +
                                                   pfv_transport_advance (another preconditioner, a cyclic core, a failed check) */
+  double transport_nl_ms;         /* last pfv_transport_advance_nl, all steps (HIP events) */
+  int64_t transport_nl_steps;     /* ... accepted steps */
+  int64_t transport_nl_core_iterations; /* ... nonlinear Jacobi iterations of the cyclic core, summed over the steps */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -591,6 +602,34 @@ pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rto
 pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, const double* bc_values,
                                        const double* accumulation, const double* source, int n_steps, int method,
                                        double rtol, int maxit, double* c, int32_t* steps_done, pfv_solve_info* last);
+/* n_steps implicit upwind steps of a saturation s that moves with q f(s) (csrc/sweep.inc: sweep_apply_nl).  Per cell
+ *     acc_i (s_i - s_old_i) + (A_ii + sink_i) f(s_i) + sum_{j != i} A_ij f(s_j) + b_ref_i = source_i
+ * with A = div diag(q) U of the one-component discretization on the handle (pfv_upwind_discretize with
+ * num_components = 1; no pfv_upwind_assemble is needed) and b_ref = div (rhs_neu bc + rhs_dir diag(q) f(bc)): a Dirichlet
+ * inflow value is a saturation, a Neumann value a flux of the transported phase, values on outflow faces are not read.
+ * In flow order every cell is one scalar monotone root-finding given its upstream cells: no Jacobian, no Krylov loop.
+ * The cells of a cyclic core are iterated by nonlinear Jacobi until ||F_core|| <= rtol ||rhs|| / 2 or maxit iterations;
+ * a step is accepted when ||F(s)|| <= rtol ||rhs|| over all rows, rhs = acc o s_old - b_ref + source.
+ *   fluxfn_kind / fluxfn_params / n_params: a PFV_FLUXFN_* and its parameters (host memory).  q (Nf): NULL = the flux
+ * of the discretization.  accumulation (Nc) must be positive; source and sink (Nc, sink >= 0: a production rate that
+ * removes fluid at the cell's own f(s_i)) may be NULL.  s (Nc) holds the state in [0, 1] on entry and the state after
+ * the last accepted step on return, steps_done that number of steps.  last (may be NULL): iterations = 1 for an acyclic
+ * flux, else the core iterations of the last step; rel_residual the measured ||F|| / ||rhs||.
+ *   PFV_ERR_ARGUMENT (the text names the first offender): no discretization or num_components != 1; an unknown kind,
+ * a wrong n_params, Corey parameters with a negative residual saturation, s_wr + s_nr >= 1, an exponent or viscosity
+ * <= 0; a table that decreases or is not finite; accumulation <= 0 or NaN; a negative sink; s or a Dirichlet inflow
+ * value outside [0, 1]; a boundary face with inflow that is neither Dirichlet nor Neumann; a step whose solution
+ * leaves [0, 1] (the text holds the step and the lowest such cell; s is the state before that step).
+ * PFV_ERR_NOT_CONVERGED: the core iteration or the acceptance check of a step failed; s is the state before it.
+ * PFV_ERR_UNSUPPORTED: periodic grids, conditions per sub-face, the sharded solve.
+ *   The flow order is built if the handle has none for this flux, whatever preconditioner is selected, and stays under
+ * the rules of pfv_transport_advance; the selected preconditioner and the flow system are left alone; no transport
+ * system is left behind (pfv_solve asks for an assembly).  pfv_stats: transport_nl_*, sweep_levels / sweep_core_cells /
+ * sweep_launches / sweep_order_ms. */
+pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
+                                    int n_params, const double* bc_values, const double* accumulation,
+                                    const double* source, const double* sink, int n_steps, double rtol, int maxit,
+                                    double* s, int32_t* steps_done, pfv_solve_info* last);
 
 /* ---- Advection-diffusion step on the device (csrc/advdiff.inc) ---------------------------------------------------
  * One handle carries the transport keyword: its diffusion discretization (pfv_mpfa_discretize or pfv_tpfa_discretize

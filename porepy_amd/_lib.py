@@ -25,6 +25,7 @@ MAT_ADVDIFF_SYSTEM = 18
 BC_DIR, BC_NEU, BC_ROB, BC_INTERNAL = 1, 2, 4, 8
 SOLVE_CG, SOLVE_BICGSTAB, SOLVE_GMRES = 0, 1, 2
 PRECOND_JACOBI, PRECOND_AMG, PRECOND_BLOCK, PRECOND_AMG_NNS, PRECOND_SWEEP = 0, 1, 2, 3, 4
+FLUXFN_LINEAR, FLUXFN_COREY, FLUXFN_TABLE = 0, 1, 2
 DISCR_REBUILD_TOPOLOGY, DISCR_SKIP_VECTOR_SOURCE = 1, 2
 
 STATUS_NAMES = {
@@ -49,7 +50,7 @@ EXPORTS = [
     "pfv_mpfa_set_permeability", "pfv_set_near_null_space", "pfv_amg_nns_level", "pfv_amg_level",
     "pfv_mpfa_face_flux", "pfv_upwind_set_bc", "pfv_upwind_discretize", "pfv_upwind_assemble", "pfv_transport_advance",
     "pfv_advdiff_assemble", "pfv_advdiff_advance", "pfv_advdiff_face_flux", "pfv_resident_flux",
-    "pfv_sweep_info", "pfv_transport_advance_multi",
+    "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl",
 ]
 
 
@@ -83,7 +84,9 @@ class Stats(C.Structure):
                 ("sweep_order_ms", C.c_double), ("sweep_direct_steps", C.c_int64),
                 ("sweep_direct_fallbacks", C.c_int64),
                 ("transport_multi_components", C.c_int64), ("transport_multi_direct_steps", C.c_int64),
-                ("transport_multi_fallback_components", C.c_int64)]
+                ("transport_multi_fallback_components", C.c_int64),
+                ("transport_nl_ms", C.c_double), ("transport_nl_steps", C.c_int64),
+                ("transport_nl_core_iterations", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -301,6 +304,9 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_transport_advance_multi.argtypes = [_h, _dp, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_int,
                                                 _dp, C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
     lib.pfv_transport_advance_multi.restype = C.c_int
+    lib.pfv_transport_advance_nl.argtypes = [_h, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_double,
+                                             C.c_int, _dp, C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
+    lib.pfv_transport_advance_nl.restype = C.c_int
     lib.pfv_advdiff_assemble.argtypes = [_h, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pfv_advdiff_assemble.restype = C.c_int
     lib.pfv_advdiff_advance.argtypes = [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(C.c_int32),
@@ -1412,6 +1418,39 @@ class Context:
         if st != 0 and (raise_on_fail or st != 6):
             self._check(st)
         return c, out
+
+    def transport_advance_nl(self, s0, n_steps: int, accumulation, bc_values, fluxfn_kind: int, fluxfn_params=(),
+                             q=None, source=None, sink=None, rtol=1e-12, maxit=500, raise_on_fail=True):
+        """``n_steps`` implicit upwind steps of a saturation that moves with ``q f(s)`` on the flux of the
+        one-component upwind discretization on this handle (pfv_transport_advance_nl): in flow order every cell is one
+        scalar root-finding.  ``fluxfn_kind``: FLUXFN_LINEAR, FLUXFN_COREY (six parameters) or FLUXFN_TABLE (its
+        values).  Returns (s, info) with ``steps_done``, ``iterations`` (1, or the core iterations of the last step),
+        ``rel_residual`` and ``converged``.  An error raised for a refused step carries ``state`` (the saturation before
+        that step) and ``info``."""
+        s = np.array(s0, dtype=np.float64, copy=True).ravel()
+        if s.shape != (self.nc,):
+            raise ValueError("s0 must have one entry per cell")
+        par = np.ascontiguousarray(fluxfn_params, dtype=np.float64).ravel()
+        kq, pq = self._vec(q, self.nf, "the flux array", False)
+        kb, pb = self._vec(bc_values, self.nf, "bc_values", False)
+        ka, pa_ = self._vec(accumulation, self.nc, "accumulation", False)
+        ks, ps = self._vec(source, self.nc, "source", False)
+        kk, pk = self._vec(sink, self.nc, "sink", False)
+        if pb is None or pa_ is None:
+            raise ValueError("bc_values and accumulation are required")
+        done, info = C.c_int32(0), SolveInfo()
+        st = self.lib.pfv_transport_advance_nl(self._h, pq, int(fluxfn_kind), _ptr(par, _dp) if par.size else None,
+                                               int(par.size), pb, pa_, ps, pk, int(n_steps), float(rtol), int(maxit),
+                                               _ptr(s, _dp), C.byref(done), C.byref(info))
+        out = {"steps_done": done.value, "iterations": info.iterations, "converged": bool(info.converged),
+               "rel_residual": info.rel_residual, "solve_ms": info.solve_ms}
+        if st != 0 and (raise_on_fail or st != 6):
+            try:
+                self._check(st)
+            except PorefvError as e:  # (the state before the refused step and what was done until then)
+                e.state, e.info = s, out
+                raise
+        return s, out
 
     # ---- advection-diffusion on one handle (include/porefv.h: pfv_advdiff_*) ----
     def resident_flux_ptr(self) -> int:

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "ctx.h"
+#include "fluxfn.h"
 namespace pfv {
 static int rccl_exchange_halo(void* user, double* d_x, void* stream);  // rccl_hooks.inc
 }
@@ -1300,6 +1301,198 @@ pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, 
     h->stats.sweep_levels = h->sweep->nlev;
     h->stats.sweep_core_cells = h->sweep->n_core;
     h->stats.sweep_launches = (int64_t)h->sweep->plan.size();
+    h->stats.sweep_order_ms = order_ms;
+  }
+  if (st != PFV_OK) {
+    h->err = err;
+    return st;
+  }
+  return st2;
+}
+
+// ---- the saturation step: q f(s) in flow order (sweep.inc: sweep_row_nl) -----------------------------------------------
+// Per step: rhs, the forward levels, the core level iterated by nonlinear Jacobi (a host read every kNlCoreCheck-th
+// iteration), the backward levels, F(s) over all rows and ONE host read of its norms and the status words.  The state
+// of the step's start stays in its own buffer until the step is accepted.
+pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
+                                    int n_params, const double* bc_values, const double* accumulation,
+                                    const double* source, const double* sink, int n_steps, double rtol, int maxit,
+                                    double* s, int32_t* steps_done, pfv_solve_info* last) {
+  if (steps_done) *steps_done = 0;
+  std::unique_ptr<pfv::Timer> tm;
+  bool touched = false;
+  double order_ms = 0.0;
+  const double* d_q = nullptr;
+  size_t nc = 0, nf = 0;
+  pfv::FluxFn F;
+  pfv_status st = guarded(h, [&] {
+    upwind_supported(h);
+    if (h->subface_bc) throw Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
+    require(h->have_upwind, "pfv_upwind_discretize first");
+    require(h->upw_ncomp == 1, "the saturation step needs pfv_upwind_discretize with num_components = 1");
+    const std::string bad = pfv::fluxfn_check(fluxfn_kind, fluxfn_params, n_params);
+    if (!bad.empty()) throw Error(PFV_ERR_ARGUMENT, bad);
+    require(bc_values && accumulation && s, "bc_values, accumulation and s are required");
+    require(n_steps >= 0, "bad argument");
+    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
+    nc = (size_t)h->nc;
+    nf = (size_t)h->nf;
+    if (q) vec_in(h, h->nl_q.ensure(nf), q, nf);
+    vec_in(h, h->nl_bc.ensure(nf), bc_values, nf);
+    vec_in(h, h->nl_acc.ensure(nc), accumulation, nc);
+    if (source) vec_in(h, h->nl_src.ensure(nc), source, nc);
+    if (sink) vec_in(h, h->nl_sink.ensure(nc), sink, nc);
+    vec_in(h, h->nl_s.ensure(nc), s, nc);
+    d_q = q ? h->nl_q.p : h->upw_q.p;
+    pfv::upwind_face_cells(*h);
+    int32_t off[5];
+    pfv::sweep_nl_check_inputs(*h, d_q, h->nl_bc.p, h->nl_acc.p, sink ? h->nl_sink.p : nullptr, h->nl_s.p, off);
+    static const char* what[5] = {"accumulation must be positive: cell ", "negative sink in cell ",
+                                  "s outside [0, 1] in cell ", "Dirichlet inflow value outside [0, 1] on face ",
+                                  "negative axis 1 index: -1 (neither Dirichlet nor Neumann, with inflow: no upstream "
+                                  "cell) face "};
+    for (int k = 0; k < 5; ++k)
+      if (off[k] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, what[k] + std::to_string(off[k]));
+    if (fluxfn_kind == PFV_FLUXFN_TABLE)
+      be_h2d(h->nl_table.ensure((size_t)n_params), fluxfn_params, sizeof(double) * (size_t)n_params, h->stream);
+    F = pfv::fluxfn_make(fluxfn_kind, fluxfn_params, n_params, h->nl_table.p);
+    tm = std::make_unique<pfv::Timer>();
+    tm->start(h->stream);
+    // A = div diag(q) U without accumulation (its diagonal: the outflow of the cell), once per call
+    upwind_drop_transport(h, true);
+    touched = true;
+    pfv::upwind_assemble(*h, d_q, h->nl_bc.p, nullptr, nullptr, nullptr);
+    values_changed(h, Windows::drop);
+    pfv::upwind_bref_nl(*h, F, d_q, h->nl_bc.p, h->nl_bref.ensure(nc));
+    for (pfv::Buf<double>* b : {&h->nl_s2, &h->nl_phi, &h->nl_phi2, &h->nl_rhs, &h->nl_t}) b->ensure(nc);
+    h->nl_out.ensure(8);
+    // the order of the flux, built on first use and kept while assemblies bring the same edges (sweep_note_assembly)
+    if (!h->sweep) h->sweep = std::make_unique<pfv::Sweep>();
+    pfv::Sweep& sw = *h->sweep;
+    if (sw.valid && (sw.for_system != PFV_MAT_TRANSPORT_SYSTEM || !pfv::sweep_same_edges(*h, sw, d_q))) sw.valid = false;
+    if (!sw.valid) {
+      pfv::sweep_build_order(*h, sw, d_q, PFV_MAT_TRANSPORT_SYSTEM);
+      order_ms += sw.order_ms;
+    }
+    pfv::sweep_set_numbering(*h, sw, false);
+    pfv::sweep_make_plan(sw);
+    if (sw.n_core > 0) {
+      h->nl_cb.ensure((size_t)sw.n_core);
+      h->nl_ct.ensure((size_t)sw.n_core);
+    }
+  });
+  if (st != PFV_OK) {
+    if (touched) upwind_drop_transport(h, true);  // (A without accumulation: not a system to be solved with)
+    return st;
+  }
+
+  const double* d_src = source ? h->nl_src.p : nullptr;
+  const double* d_sink = sink ? h->nl_sink.p : nullptr;
+  int32_t completed = 0;
+  int64_t core_total = 0, launches = 0;
+  pfv_solve_info info{};
+  std::string err;
+  for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
+    pfv_status verdict = PFV_OK;
+    st = guarded(h, [&] {
+      pfv::pfv_ctx_impl& c = *h;
+      const pfv::Sweep& sw = *c.sweep;
+      const double* val = c.val[PFV_MAT_TRANSPORT_SYSTEM].p;
+      const double* diag = c.diag_t.p;
+      const double *acc = c.nl_acc.p, *rhs = c.nl_rhs.p, *s_old = c.nl_s.p;
+      double *s_new = c.nl_s2.p, *phi = c.nl_phi.p, *out = c.nl_out.p;
+      int32_t* status = reinterpret_cast<int32_t*>(out + 4);  // [0] the levels outside the core, [1] the core
+      const bool has_core = sw.n_core > 0;
+      const int core = has_core ? sw.core_level : sw.nlev;
+      pfv::upwind_step_rhs_multi(c, 1, acc, d_src, c.nl_bref.p, s_old, c.nl_rhs.p);
+      pfv::be_memset(out, 0, 4 * sizeof(double), c.stream);
+      pfv::be_memset(status, 0x7f, 2 * sizeof(int32_t), c.stream);
+      launches = pfv::sweep_apply_nl(c, sw, 0, core, c.pat_T, val, diag, d_sink, acc, rhs, F, s_old, s_new, phi, status);
+      double hst[5];
+      auto flagged = [&](bool core_too, int32_t& cell) {
+        int32_t w[2];
+        std::memcpy(w, hst + 4, sizeof(w));
+        cell = core_too ? std::min(w[0], w[1]) : w[0];
+        return cell != 0x7f7f7f7f;
+      };
+      int core_it = 0;
+      if (has_core) {
+        bool settled = false;
+        pfv::sweep_residual_norms(c, c.nc, rhs, rhs, out);  // out[0] = (rhs, rhs)
+        pfv::sweep_nl_core_init(c, sw, F, s_old, s_new, phi);
+        while (core_it < maxit && !settled) {
+          pfv::sweep_nl_core_keep(c, sw, phi, c.nl_phi2.p, status + 1);
+          pfv::sweep_levels_nl(c, sw, core, core + 1, c.pat_T, val, diag, d_sink, acc, rhs, F, s_new, c.nl_phi2.p, s_new,
+                               phi, status + 1);
+          ++core_it;
+          if (core_it % pfv::kNlCoreCheck != 0 && core_it != maxit) continue;
+          pfv::sweep_nl_core_image(c, sw, c.pat_T, val, d_sink, acc, rhs, s_new, phi, c.nl_cb.p, c.nl_ct.p);
+          pfv::sweep_residual_norms(c, sw.n_core, c.nl_cb.p, c.nl_ct.p, out + 2);  // out[3] = (F_core, F_core)
+          be_d2h(hst, out, sizeof(hst), c.stream);
+          settled = hst[3] <= 0.25 * rtol * rtol * hst[0];
+        }
+        core_total += core_it;
+        launches += 2;
+        if (!settled) {  // (what the backward levels would compute from this core is not judged)
+          info = pfv_solve_info{};
+          info.iterations = core_it;
+          info.rel_residual = hst[0] > 0.0 ? std::sqrt(hst[3] / hst[0]) : 0.0;
+          int32_t cell;  // (the core's word belongs to an iterate that has not settled: the other levels' alone)
+          if (flagged(false, cell))
+            throw Error(PFV_ERR_ARGUMENT, "step " + std::to_string(step) + " leaves [0, 1]: no root in cell " +
+                                              std::to_string(cell));
+          verdict = PFV_ERR_NOT_CONVERGED;
+          c.err = "step " + std::to_string(step) + ": the cyclic core of " + std::to_string(sw.n_core) +
+                  " cells did not settle in " + std::to_string(core_it) + " iterations";
+          return;
+        }
+        launches += pfv::sweep_apply_nl(c, sw, core + 1, sw.nlev, c.pat_T, val, diag, d_sink, acc, rhs, F, s_old, s_new, phi,
+                                        status);
+      }
+      pfv::sweep_nl_image(c, c.pat_T, val, d_sink, acc, s_new, phi, c.nl_t.p);
+      pfv::sweep_residual_norms(c, c.nc, rhs, c.nl_t.p, out);
+      be_d2h(hst, out, sizeof(hst), c.stream);
+      info = pfv_solve_info{};
+      info.iterations = has_core ? core_it : 1;
+      info.rel_residual = hst[0] > 0.0 ? std::sqrt(hst[1] / hst[0]) : 0.0;
+      int32_t cell;
+      if (flagged(true, cell))
+        throw Error(PFV_ERR_ARGUMENT, "step " + std::to_string(step) + " leaves [0, 1]: no root in cell " +
+                                          std::to_string(cell));
+      info.converged = hst[1] <= rtol * rtol * hst[0] ? 1 : 0;
+      if (!info.converged) {
+        verdict = PFV_ERR_NOT_CONVERGED;
+        c.err = "step " + std::to_string(step) + ": relative residual " + std::to_string(info.rel_residual) +
+                " after the sweep (a flux that contradicts the discretization's?)";
+        return;
+      }
+      std::swap(c.nl_s.p, c.nl_s2.p);
+      std::swap(c.nl_s.cap, c.nl_s2.cap);
+      ++completed;
+    });
+    if (st == PFV_OK) st = verdict;
+  }
+  if (st != PFV_OK) err = h->err;
+  double ms = 0.0;
+  const pfv_status st2 = guarded(h, [&] {
+    ms = tm->stop(h->stream);
+    tm.reset();
+    vec_out(h, s, h->nl_s.p, nc);
+    pfv::be_sync(h->stream);
+    upwind_drop_transport(h, true);
+  });
+  if (steps_done) *steps_done = completed;
+  if (last) {
+    *last = info;
+    if (completed > 0) last->solve_ms = ms / completed;
+  }
+  h->stats.transport_nl_ms = ms;
+  h->stats.transport_nl_steps = completed;
+  h->stats.transport_nl_core_iterations = core_total;
+  if (h->sweep && h->sweep->valid) {
+    h->stats.sweep_levels = h->sweep->nlev;
+    h->stats.sweep_core_cells = h->sweep->n_core;
+    h->stats.sweep_launches = n_steps > 0 ? launches : (int64_t)h->sweep->plan.size();
     h->stats.sweep_order_ms = order_ms;
   }
   if (st != PFV_OK) {

@@ -436,6 +436,235 @@ static void sweep_residual_norms_multi(pfv_ctx_impl& c, const CsrPattern& P, con
   });
 }
 
+// ---- the saturation step (pfv_transport_advance_nl): the quantity moves with q f(s), f nondecreasing (fluxfn.h).
+// Per row  acc_i s_i + o_i f(s_i) = R_i,  o_i = A_ii + sink_i,  R_i = rhs_i - sum_{lev[j] < lev[i]} A_ij phi_j  with
+// rhs = acc o s_old - b_ref + src and phi = f(s) carried beside s: a row reads the phi of its upstream cells and writes
+// its own s and phi, so no row evaluates f for a neighbour.  g(x) = acc x + o f(x) - R is strictly increasing (acc > 0).
+//   root   Newton from the start value clipped into the bracket [0, 1]; an iterate that leaves the bracket, or a |g|
+//          that did not halve, is replaced by the midpoint.  Stop: |g| <= 2^-50 (|R| + acc + |o|) -- twice what evaluating
+//          g in doubles resolves --, or a bracket of 2^-52, or kNlEvals evaluations.  Lanes of a wavefront need different
+//          numbers of evaluations; they wait for the slowest.
+//   leave  g(0) or g(1) beyond that tolerance on the wrong side: no root in [0, 1].  The row takes the end of the
+//          interval and records its index with an integer atomic minimum.
+//   core   rows of the core level (phi_prev != nullptr) take their in-core neighbours from phi_prev, the previous
+//          iterate: nonlinear Jacobi, independent of the scheduling.
+constexpr int kNlEvals = 64;
+constexpr double kNlGTol = 8.881784197001252e-16;  // 2^-50
+constexpr int kNlCoreCheck = 8;                    // the core's stop test is evaluated every 8th iteration
+
+PFV_FN void sweep_row_nl(int32_t i, const int32_t* ip, const int32_t* ix, const double* val, const double* diag,
+                         const double* sink, const double* acc, const double* rhs, const int32_t* lev, const FluxFn& F,
+                         const double* s_start, const double* phi_prev, double* s, double* phi, int32_t* status) {
+  const int32_t li = lev[i];
+  double sum = 0.0;
+  for (int e = ip[i]; e < ip[i + 1]; ++e) {
+    const int32_t j = ix[e];
+    const int32_t lj = lev[j];
+    if (lj < li) sum += val[e] * phi[j];
+    else if (phi_prev && lj == li && j != i) sum += val[e] * phi_prev[j];
+  }
+  const double R = rhs[i] - sum, a = acc[i], o = diag[i] + (sink ? sink[i] : 0.0);
+  const double tol = kNlGTol * (fabs(R) + a + fabs(o));
+  double df;
+  double x = 0.0, f = fluxfn_eval(F, x, &df);
+  if (o * f - R > tol) {  // g(0) > 0
+    atomic_min_i32(status, i);
+    s[i] = x;
+    phi[i] = f;
+    return;
+  }
+  x = 1.0;
+  f = fluxfn_eval(F, x, &df);
+  if (a + o * f - R < -tol) {  // g(1) < 0
+    atomic_min_i32(status, i);
+    s[i] = x;
+    phi[i] = f;
+    return;
+  }
+  double lo = 0.0, hi = 1.0, g_prev = 1.79769313486231570e308;
+  x = s_start[i];
+  x = x < lo ? lo : (x > hi ? hi : x);
+  for (int it = 0;; ++it) {
+    f = fluxfn_eval(F, x, &df);
+    const double g = a * x + o * f - R;
+    if (fabs(g) <= tol || it == kNlEvals - 1) break;
+    if (g > 0.0) hi = x;
+    else lo = x;
+    if (hi - lo <= 2.220446049250313e-16) break;
+    double xn = x - g / (a + o * df);
+    if (!(xn > lo && xn < hi) || fabs(g) > 0.5 * g_prev) xn = 0.5 * (lo + hi);
+    g_prev = fabs(g);
+    x = xn;
+  }
+  s[i] = x;
+  phi[i] = f;
+}
+
+// levels [l0, l1) of the order, by the rule of the launch plan: one level is one launch, a run is one workgroup
+static void sweep_levels_nl(pfv_ctx_impl& c, const Sweep& sw, int l0, int l1, const CsrPattern& P, const double* val,
+                            const double* diag, const double* sink, const double* acc, const double* rhs,
+                            const FluxFn& F, const double* s_start, const double* phi_prev, double* s, double* phi,
+                            int32_t* status) {
+  stream_t st = c.stream;
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* lev = sw.lev(false);
+  const int32_t* ord = sw.ord(false);
+  const int32_t* lp = sw.lptr;
+  if (l1 - l0 == 1) {
+    const int32_t a0 = sw.h_lptr[(size_t)l0], m = sw.h_lptr[(size_t)l1] - a0;
+    parallel_for(st, m, PFV_LAMBDA(int64_t k) {
+      sweep_row_nl(ord[a0 + k], ip, ix, val, diag, sink, acc, rhs, lev, F, s_start, phi_prev, s, phi, status);
+    });
+  } else if (l1 > l0) {
+    block_for<256>(st, 1, 0, PFV_LAMBDA(const WaveCtx& w) {
+      for (int l = l0; l < l1; ++l) {
+        const int32_t a0 = lp[l], m = lp[l + 1] - a0;
+        PFV_LANES(k, m) sweep_row_nl(ord[a0 + k], ip, ix, val, diag, sink, acc, rhs, lev, F, s_start, phi_prev, s, phi, status);
+        w.sync();  // (the next level reads what this one wrote: same workgroup, same CU)
+      }
+    });
+  }
+}
+
+// The segments of the launch plan with levels in [from, to): the plan of sweep_apply, a run cut where the core level
+// (which is iterated on its own) falls into it.  Returns the launches.
+static int sweep_apply_nl(pfv_ctx_impl& c, const Sweep& sw, int from, int to, const CsrPattern& P, const double* val,
+                          const double* diag, const double* sink, const double* acc, const double* rhs,
+                          const FluxFn& F, const double* s_start, double* s, double* phi, int32_t* status) {
+  int launches = 0;
+  for (const Sweep::Seg& g : sw.plan) {
+    const int l0 = std::max(g.l0, from), l1 = std::min(g.l1, to);
+    if (l0 >= l1) continue;
+    sweep_levels_nl(c, sw, l0, l1, P, val, diag, sink, acc, rhs, F, s_start, nullptr, s, phi, status);
+    ++launches;
+  }
+  return launches;
+}
+
+// t[i] = acc_i s_i + sum_e A_ie phi_j + sink_i phi_i in stored order: F(s) = rhs - t.  With lev: the entries up to the
+// row's own level alone (the core's stop test runs before the levels behind it have a phi; their entries are the stored
+// zeros of the downstream side)
+PFV_FN double sweep_nl_row_image(int32_t i, const int32_t* ip, const int32_t* ix, const double* val, const double* sink,
+                                 const double* acc, const double* s, const double* phi, const int32_t* lev) {
+  double t = 0.0;
+  for (int e = ip[i]; e < ip[i + 1]; ++e) {
+    const int32_t j = ix[e];
+    if (!lev || lev[j] <= lev[i]) t += val[e] * phi[j];
+  }
+  if (sink) t += sink[i] * phi[i];
+  return t + acc[i] * s[i];
+}
+
+static void sweep_nl_image(pfv_ctx_impl& c, const CsrPattern& P, const double* val, const double* sink,
+                           const double* acc, const double* s, const double* phi, double* t) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  parallel_for(c.stream, P.nrows, PFV_LAMBDA(int64_t i) {
+    t[i] = sweep_nl_row_image((int32_t)i, ip, ix, val, sink, acc, s, phi, nullptr);
+  });
+}
+
+// The core rows, compacted: cb[k] = rhs of the k-th core row, ct[k] = its image.  A row that sits at an end of [0, 1]
+// with the residual pointing outwards (it took that end because it has no root inside) counts as solved: the
+// iteration then settles, and the step is refused by the status word, not by maxit.
+static void sweep_nl_core_image(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* val,
+                                const double* sink, const double* acc, const double* rhs, const double* s,
+                                const double* phi, double* cb, double* ct) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* ord = sw.ord(false);
+  const int32_t* lev = sw.lev(false);
+  const int32_t a0 = sw.h_lptr[(size_t)sw.core_level];
+  parallel_for(c.stream, sw.n_core, PFV_LAMBDA(int64_t k) {
+    const int32_t i = ord[a0 + k];
+    const double b = rhs[i];
+    double t = sweep_nl_row_image(i, ip, ix, val, sink, acc, s, phi, lev);
+    if ((s[i] == 0.0 && t > b) || (s[i] == 1.0 && t < b)) t = b;
+    cb[k] = b;
+    ct[k] = t;
+  });
+}
+
+// before the first core iteration: the core rows start from the state of the step's start
+static void sweep_nl_core_init(pfv_ctx_impl& c, const Sweep& sw, const FluxFn& F, const double* s_old, double* s,
+                               double* phi) {
+  const int32_t* ord = sw.ord(false);
+  const int32_t a0 = sw.h_lptr[(size_t)sw.core_level];
+  parallel_for(c.stream, sw.n_core, PFV_LAMBDA(int64_t k) {
+    const int32_t i = ord[a0 + k];
+    double df;
+    s[i] = s_old[i];
+    phi[i] = fluxfn_eval(F, s_old[i], &df);
+  });
+}
+
+// before every core iteration: phi_prev <- phi on the core rows; the core's status word starts afresh
+static void sweep_nl_core_keep(pfv_ctx_impl& c, const Sweep& sw, const double* phi, double* phi_prev,
+                               int32_t* core_status) {
+  const int32_t* ord = sw.ord(false);
+  const int32_t a0 = sw.h_lptr[(size_t)sw.core_level];
+  parallel_for(c.stream, sw.n_core, PFV_LAMBDA(int64_t k) {
+    const int32_t i = ord[a0 + k];
+    phi_prev[i] = phi[i];
+    if (k == 0) *core_status = 0x7f7f7f7f;
+  });
+}
+
+// b_ref = div (rhs_neu bc + rhs_dir diag(q) f(bc)) by the rule and in the order of upwind_assemble
+static void upwind_bref_nl(pfv_ctx_impl& c, const FluxFn& F, const double* d_q, const double* bc, double* bref) {
+  const int64_t nf = c.nf;
+  const int32_t* cf_ptr = c.cf_ptr;
+  const int32_t* cf_idx = c.cf_idx;
+  const int8_t* cf_sgn = c.cf_sgn;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* cnt = c.upw_cnt;
+  parallel_for(c.stream, c.nc, PFV_LAMBDA(int64_t cell) {
+    double b = 0.0;
+    for (int e = cf_ptr[cell]; e < cf_ptr[cell + 1]; ++e) {
+      const int f = cf_idx[e];
+      const unsigned cl = cls[f];
+      if (cl & (UPW_NEU | UPW_DIRIN)) {
+        double v = 0.0, df;  // the entry of rhs_neu bc + rhs_dir diag(q) f(bc) in row f
+        if (cl & UPW_NEU) v = (double)(cnt[f] - cnt[nf + f]) * bc[f];
+        if (cl & UPW_DIRIN) v += d_q[f] * fluxfn_eval(F, bc[f], &df);
+        b += (double)cf_sgn[e] * v;
+      }
+    }
+    bref[cell] = b;
+  });
+}
+
+// What the call refuses in its arrays, each with the lowest index: st[0] accumulation <= 0 or NaN, st[1] sink < 0,
+// st[2] s outside [0, 1], st[3] a Dirichlet inflow value outside [0, 1], st[4] a boundary face with inflow under q that
+// is neither Dirichlet nor Neumann.  (0x7f7f7f7f: none.)
+static void sweep_nl_check_inputs(pfv_ctx_impl& c, const double* d_q, const double* bc, const double* acc,
+                                  const double* sink, const double* s, int32_t out[5]) {
+  stream_t st_ = c.stream;
+  const int64_t nc = c.nc, nf = c.nf;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* side = c.upw_side;
+  const int32_t* cnt = c.upw_cnt;
+  const uint8_t* flag = c.have_upw_bc ? c.upw_bc.p : nullptr;
+  int32_t* st = c.status.ensure(16);
+  be_memset(st, 0x7f, sizeof(int32_t) * 5, st_);
+  parallel_for(st_, std::max(nc, nf), PFV_LAMBDA(int64_t t) {
+    if (t < nc) {
+      if (!(acc[t] > 0.0)) atomic_min_i32(st, (int32_t)t);
+      if (sink && !(sink[t] >= 0.0)) atomic_min_i32(st + 1, (int32_t)t);
+      if (!(s[t] >= 0.0 && s[t] <= 1.0)) atomic_min_i32(st + 2, (int32_t)t);
+    }
+    if (t < nf) {
+      if ((cls[t] & UPW_DIRIN) && !(bc[t] >= 0.0 && bc[t] <= 1.0)) atomic_min_i32(st + 3, (int32_t)t);
+      if (cnt[t] + cnt[nf + t] == 1 && flag && !(flag[t] & (PFV_BC_DIR | PFV_BC_NEU))) {
+        const int32_t u = d_q[t] >= 0.0 ? side[t] : side[nf + t];
+        if (u < 0) atomic_min_i32(st + 4, (int32_t)t);
+      }
+    }
+  });
+  be_d2h(out, st, sizeof(int32_t) * 5, st_);
+}
+
 // The direct solve of the transport system of an acyclic flux: x = M^-1 b with M = S, then the true residual.  Should
 // the check fail (a flux array in the assembly that disagrees with the discretization's, NaN entries), GMRES
 // preconditioned by the sweep goes on from that x.

@@ -33,6 +33,52 @@ def flow_darcy_flux(ctx, pd: dict, p, vector_source=None, resident: bool = False
     return ResidentFlux(ctx) if resident else q
 
 
+class CoreyFractionalFlow:
+    """Fractional flow of the wetting phase with Corey relative permeabilities: ``s_e = clip((s - s_wr) /
+    (1 - s_wr - s_nr), 0, 1)``, ``f = l_w / (l_w + l_n)`` with ``l_w = s_e**n_w / mu_w``, ``l_n = (1 - s_e)**n_n / mu_n``.
+    Calling it evaluates the curve with numpy -- the curve ``Upwind.advance_saturation`` steps with on the device."""
+
+    kind = _lib.FLUXFN_COREY
+
+    def __init__(self, s_wr=0.0, s_nr=0.0, n_w=2.0, n_n=2.0, mu_w=1.0, mu_n=1.0):
+        self.s_wr, self.s_nr, self.n_w, self.n_n = float(s_wr), float(s_nr), float(n_w), float(n_n)
+        self.mu_w, self.mu_n = float(mu_w), float(mu_n)
+
+    @property
+    def params(self) -> np.ndarray:
+        return np.array([self.s_wr, self.s_nr, self.n_w, self.n_n, self.mu_w, self.mu_n])
+
+    def __call__(self, s):
+        se = np.clip((np.asarray(s, dtype=np.float64) - self.s_wr) / (1.0 - self.s_wr - self.s_nr), 0.0, 1.0)
+        lw, ln = se ** self.n_w / self.mu_w, (1.0 - se) ** self.n_n / self.mu_n
+        return lw / (lw + ln)
+
+    def __repr__(self):
+        return (f"CoreyFractionalFlow(s_wr={self.s_wr}, s_nr={self.s_nr}, n_w={self.n_w}, n_n={self.n_n}, "
+                f"mu_w={self.mu_w}, mu_n={self.mu_n})")
+
+
+class TabulatedFractionalFlow:
+    """Piecewise-linear flux function through ``values`` (2 .. 1024 of them, finite, nondecreasing) on uniform knots
+    over [0, 1].  Calling it evaluates the curve with numpy."""
+
+    kind = _lib.FLUXFN_TABLE
+
+    def __init__(self, values):
+        self.values = np.array(values, dtype=np.float64).ravel()
+
+    @property
+    def params(self) -> np.ndarray:
+        return self.values
+
+    def __call__(self, s):
+        s = np.clip(np.asarray(s, dtype=np.float64), 0.0, 1.0)
+        return np.interp(s, np.linspace(0.0, 1.0, self.values.size), self.values)
+
+    def __repr__(self):
+        return f"TabulatedFractionalFlow(<{self.values.size} values>)"
+
+
 class Upwind:
     """Upwind discretization of ``keyword`` on the device.  ``flow``: an ``Mpfa`` / ``Tpfa`` object whose device
     handle of a grid is shared, so that the flux it left resident can be taken without a copy."""
@@ -222,6 +268,44 @@ class Upwind:
             if e.status == 4:
                 raise ValueError(e.message) from None
             raise
+
+    def advance_saturation(self, sd, data: dict, s0, n_steps: int, accumulation, flux_function, source=None, sink=None,
+                           rtol: float = 1e-12, maxit: int = 500, raise_on_fail: bool = True):
+        """``n_steps`` implicit upwind steps of a saturation that moves with ``q f(s)`` -- the transport step of
+        immiscible two-phase flow without gravity and capillary pressure:
+        ``acc (s - s_old) + (A_ii + sink) f(s_i) + sum_j A_ij f(s_j) + b_ref = source``.  ``flux_function``: ``"linear"``,
+        a ``CoreyFractionalFlow`` or a ``TabulatedFractionalFlow``.  A Dirichlet inflow value of the keyword's
+        ``bc_values`` is a saturation, a Neumann value a flux of the transported phase.  ``accumulation`` (Nc, positive)
+        = porosity x volume / dt; ``sink`` (Nc, >= 0) a production rate that takes fluid at the cell's own ``f(s)``.
+
+        In flow order the step is one scalar monotone root-finding per cell, exact given its upstream cells: no
+        Jacobian, no Krylov loop, no damping.  The cells of a cyclic core (``stats()["sweep_core_cells"]``) are iterated
+        by nonlinear Jacobi, at most ``maxit`` times per step.  Returns (s, info): info["steps_done"] counts the accepted
+        steps, "iterations" is 1 (or the core iterations of the last step), "rel_residual" the measured
+        ``||F(s)|| / ||rhs||``.  A step that would leave [0, 1] raises ``ValueError`` naming the step and the cell; the
+        error carries ``state``, the saturation before that step, and ``info``."""
+        pd = data[PARAMETERS][self.keyword]
+        if isinstance(flux_function, str):
+            if flux_function != "linear":
+                raise ValueError('flux_function must be "linear", a CoreyFractionalFlow or a TabulatedFractionalFlow')
+            kind, params = _lib.FLUXFN_LINEAR, ()
+        elif isinstance(flux_function, (CoreyFractionalFlow, TabulatedFractionalFlow)):
+            kind, params = flux_function.kind, flux_function.params
+        else:
+            raise ValueError('flux_function must be "linear", a CoreyFractionalFlow or a TabulatedFractionalFlow')
+        if accumulation is None:
+            raise ValueError("accumulation is required")
+        try:
+            s, info = self.context(sd).transport_advance_nl(
+                s0, n_steps, accumulation, np.asarray(pd["bc_values"], dtype=float), kind, params, q=self._flux(sd, pd),
+                source=source, sink=sink, rtol=rtol, maxit=maxit, raise_on_fail=raise_on_fail)
+        except _lib.PorefvError as e:
+            if e.status == 4:
+                err = ValueError(e.message)
+                err.state, err.info = getattr(e, "state", None), getattr(e, "info", None)
+                raise err from None
+            raise
+        return s, info
 
 
 def as_porepy_upwind(device: int = 0, library=None):

@@ -7,6 +7,7 @@ Device times are HIP-event times from pfv_stats; the host times are wall clock. 
 not a test: no thresholds.
 
     python tools/bench_transport.py [--n-side 69] [--steps 20] [--no-host] [--precond sweep] [--components 8]
+                                    [--saturation]
 
 --precond sweep: after the Jacobi-BiCGStab steps, the same steps from the same state with the flow-ordered sweep
 (PFV_PRECOND_SWEEP) -- order-build ms, levels, core cells, launches per sweep, ms per step -- and again with one launch
@@ -16,6 +17,11 @@ per level (PFV_SWEEP_MERGE=0); both figures of the comparison come from this one
 and their own inflow values, first as K single assemble + advance(precond="sweep") runs, then as ONE
 transport_advance_multi from the same state on the same handle: ms per step of both (HIP events, best and median of
 --reps), levels and launches per sweep, and the largest difference between the two results.
+
+--saturation: on the same flux and from the same state, the linear sweep steps (advance with precond="sweep") and then
+the same number of saturation steps with a Corey curve (transport_advance_nl: exponents 2 / 2, viscosities 1 / 5,
+residual saturations 0.1 / 0.15): ms per step of both from pfv_stats (best and median of --reps, the first repeat
+dropped), levels, launches, core cells and core iterations.
 """
 from __future__ import annotations
 
@@ -43,6 +49,8 @@ def main():
                     help="sweep: also time the steps with the flow-ordered sweep, next to the Jacobi-BiCGStab ones")
     ap.add_argument("--components", default="",
                     help="K or K1,K2,...: K single sweep runs against one multi-component run (needs --precond sweep)")
+    ap.add_argument("--saturation", action="store_true",
+                    help="linear sweep steps against Corey saturation steps on the same flux and state")
     ap.add_argument("--emulation", action="store_true", help="run on the host-emulation build (plumbing check)")
     a = ap.parse_args()
     lib = None
@@ -138,6 +146,31 @@ def main():
                 "max_diff_multi_to_single": float(np.abs(cm_k - cs_k).max())})
         if a.components:
             ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the multi-component call leaves no system behind)
+    if a.saturation:
+        s0 = np.full(nc, 0.1)
+        corey = pa.CoreyFractionalFlow(s_wr=0.1, s_nr=0.15, n_w=2.0, n_n=2.0, mu_w=1.0, mu_n=5.0)
+        lin_ms, nl_ms, sat = [], [], {}
+        for _ in range(a.reps + 1):  # (the first repeat builds the order and warms up: dropped)
+            cl, linfo = ctx.transport_advance(s0, a.steps, rtol=1e-10, raise_on_fail=False, precond="sweep")
+            ls = ctx.stats()
+            lin_ms.append(ls["transport_advance_ms"] / max(a.steps, 1))
+        try:
+            for _ in range(a.reps + 1):
+                sn, ninfo = ctx.transport_advance_nl(s0, a.steps, acc, tbv, corey.kind, corey.params, rtol=1e-10,
+                                                     raise_on_fail=False)
+                ns = ctx.stats()
+                nl_ms.append(ns["transport_nl_ms"] / max(a.steps, 1))
+            sat = {"steps_done": ninfo["steps_done"], "corey_ms_per_step": (min(nl_ms[1:]), float(np.median(nl_ms[1:]))),
+                   "levels": ns["sweep_levels"], "core_cells": ns["sweep_core_cells"],
+                   "launches_per_step": ns["sweep_launches"], "core_iterations": ns["transport_nl_core_iterations"],
+                   "rel_residual_last_step": ninfo["rel_residual"], "s_min": float(sn.min()), "s_max": float(sn.max())}
+        except pa.PorefvError as e:
+            sat = {"error": e.message, "core_cells": ctx.stats()["sweep_core_cells"], "levels": ctx.stats()["sweep_levels"]}
+        sat.update({"linear_sweep_ms_per_step": (min(lin_ms[1:]), float(np.median(lin_ms[1:]))),
+                    "linear_steps_done": linfo["steps_done"], "linear_direct_steps": ls["sweep_direct_steps"],
+                    "linear_launches_per_sweep": ls["sweep_launches"], "linear_core_cells": ls["sweep_core_cells"]})
+        out["saturation"] = sat
+        ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the saturation call leaves no system behind)
     # bytes each kernel has to move at least ("Upwind advection"): the fraction of a stream rate follows
     nnz_flux = ctx.matrix_info(_lib.MAT_FLUX)[2]
     nnz_bound = ctx.matrix_info(_lib.MAT_BOUND_FLUX)[2]

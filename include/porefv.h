@@ -192,9 +192,10 @@ typedef struct {
   int64_t transport_multi_direct_steps; /* ... steps taken entirely by one sweep and one residual check of all components */
   int64_t transport_multi_fallback_components; /* ... component-steps solved by that component's own pfv_upwind_assemble +
                                                   pfv_transport_advance (another preconditioner, a cyclic core, a failed check) */
-  double transport_nl_ms;         /* last pfv_transport_advance_nl, all steps (HIP events) */
+  double transport_nl_ms;         /* last pfv_transport_advance_nl or pfv_transport_advance_nl_multi, all steps (HIP events) */
   int64_t transport_nl_steps;     /* ... accepted steps */
   int64_t transport_nl_core_iterations; /* ... nonlinear Jacobi iterations of the cyclic core, summed over the steps */
+  int64_t transport_nl_components; /* ... k of pfv_transport_advance_nl_multi, 0 after pfv_transport_advance_nl */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -630,6 +631,37 @@ pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind
                                     int n_params, const double* bc_values, const double* accumulation,
                                     const double* source, const double* sink, int n_steps, double rtol, int maxit,
                                     double* s, int32_t* steps_done, pfv_solve_info* last);
+/* The same steps with k (1 .. 64, else PFV_ERR_ARGUMENT) components carried by the transported phase: salinity, a
+ * polymer, a tracer that marks injected water, the water's heat content.  c_a is the amount of component a per unit
+ * volume of the phase.  After s_i and phi_i = f(s_i) of the step are known, component a solves, with o_i = A_ii + sink_i,
+ *     (acc_i s_i + ads_ai) c_ai + o_i phi_i c_ai + sum_{j != i} A_ij phi_j c_aj
+ *         = (acc_i s_old_i + ads_ai) c_old_ai - b_ref_ai + src_ai
+ *     b_ref_a = div (rhs_neu cbc_a + rhs_dir diag(q) (f(bc) o cbc_a)):
+ * on a Dirichlet inflow face c_bc_values[a] is the concentration in the entering phase (the saturation there is still
+ * bc_values through f), on a Neumann face the component's flux; values on outflow faces are not read.  c_source[a] is a
+ * mass rate of the component; the sink removes it at sink_i phi_i c_ai; sorption[a] >= 0 is a linear sorption capacity
+ * that does not scale with s (the retardation of pfv_transport_advance_multi).  In flow order the row is one division
+ * once s_i is known, in the launches of the saturation (csrc/sweep.inc: sweep_row_nlc): pfv_stats.sweep_launches is that
+ * of pfv_transport_advance_nl, and s is, bit for bit, what that call computes from the same arguments.  A row whose
+ * diagonal acc_i s_i + ads_ai + o_i phi_i is zero (a dry cell without sorption) keeps c_old_ai.  The cells of a cyclic
+ * core iterate s and c jointly; the core has settled when ||F_core|| <= rtol ||rhs|| / 2 holds for the saturation and
+ * for every component with its own rhs_a.
+ *   c_bc_values [k][Nf], sorption and c_source ([k][Nc], each may be NULL) and c ([k][Nc], in and out) are
+ * component-major; on the device the vectors are cell-major and interleaved, v[i * k + a].  (k + 1) max(Nc, Nf) must stay
+ * below 2^31 (PFV_ERR_UNSUPPORTED).  A step is accepted only if the saturation and every component satisfy
+ * ||F|| <= rtol ||rhs||, 0 <= 0 included (a component that is absent everywhere is valid); one host read per step brings
+ * all 2 (k + 1) norms and the status words.  A refused step returns s and c of the step's start, steps_done and
+ * PFV_ERR_NOT_CONVERGED; a step that leaves [0, 1] PFV_ERR_ARGUMENT as above.  There is no per-component fallback: the
+ * matrix of a component changes with s in every step, so no assembled linear system exists to fall back to.
+ *   PFV_ERR_ARGUMENT beyond those of pfv_transport_advance_nl: a negative or NaN sorption, a non-finite c, a non-finite
+ * c_bc_values on a Dirichlet inflow or Neumann face (the text names the lowest cell or face and its lowest component).
+ * last (k + 1 entries, may be NULL): the saturation first, then the components.  The handle rules are those of
+ * pfv_transport_advance_nl; pfv_stats: transport_nl_* (transport_nl_components = k) and the sweep_* fields. */
+pfv_status pfv_transport_advance_nl_multi(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
+                                          int n_params, const double* bc_values, const double* accumulation,
+                                          const double* source, const double* sink, int k, const double* c_bc_values,
+                                          const double* sorption, const double* c_source, int n_steps, double rtol,
+                                          int maxit, double* s, double* c, int32_t* steps_done, pfv_solve_info* last);
 
 /* ---- Advection-diffusion step on the device (csrc/advdiff.inc) ---------------------------------------------------
  * One handle carries the transport keyword: its diffusion discretization (pfv_mpfa_discretize or pfv_tpfa_discretize

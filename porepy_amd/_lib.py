@@ -50,7 +50,7 @@ EXPORTS = [
     "pfv_mpfa_set_permeability", "pfv_set_near_null_space", "pfv_amg_nns_level", "pfv_amg_level",
     "pfv_mpfa_face_flux", "pfv_upwind_set_bc", "pfv_upwind_discretize", "pfv_upwind_assemble", "pfv_transport_advance",
     "pfv_advdiff_assemble", "pfv_advdiff_advance", "pfv_advdiff_face_flux", "pfv_resident_flux",
-    "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl",
+    "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl", "pfv_transport_advance_nl_multi",
 ]
 
 
@@ -86,7 +86,7 @@ class Stats(C.Structure):
                 ("transport_multi_components", C.c_int64), ("transport_multi_direct_steps", C.c_int64),
                 ("transport_multi_fallback_components", C.c_int64),
                 ("transport_nl_ms", C.c_double), ("transport_nl_steps", C.c_int64),
-                ("transport_nl_core_iterations", C.c_int64)]
+                ("transport_nl_core_iterations", C.c_int64), ("transport_nl_components", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -307,6 +307,10 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_transport_advance_nl.argtypes = [_h, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_double,
                                              C.c_int, _dp, C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
     lib.pfv_transport_advance_nl.restype = C.c_int
+    lib.pfv_transport_advance_nl_multi.argtypes = [_h, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp,
+                                                   _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, C.POINTER(C.c_int32),
+                                                   C.POINTER(SolveInfo)]
+    lib.pfv_transport_advance_nl_multi.restype = C.c_int
     lib.pfv_advdiff_assemble.argtypes = [_h, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pfv_advdiff_assemble.restype = C.c_int
     lib.pfv_advdiff_advance.argtypes = [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(C.c_int32),
@@ -1451,6 +1455,62 @@ class Context:
                 e.state, e.info = s, out
                 raise
         return s, out
+
+    def transport_advance_nl_multi(self, s0, c0, n_steps: int, accumulation, bc_values, c_bc_values, fluxfn_kind: int,
+                                   fluxfn_params=(), q=None, sorption=None, source=None, sink=None, c_source=None,
+                                   rtol=1e-12, maxit=500, raise_on_fail=True):
+        """The steps of ``transport_advance_nl`` with k components carried by the transported phase
+        (pfv_transport_advance_nl_multi): once a cell's saturation is known, each of its components is one division, in
+        the same launches.  ``c0``: k x Nc, the amount per unit volume of the phase; ``c_bc_values``: k x Nf, on a
+        Dirichlet inflow face the concentration in the entering phase, on a Neumann face the component's flux;
+        ``sorption`` (>= 0) and ``c_source`` (a mass rate), each k x Nc or None.  Returns (s, c, info): info as
+        ``transport_advance_nl`` reports it for the saturation, with the per-component lists ``c_rel_residual`` and
+        ``c_converged``.  An error raised for a refused step carries ``state = (s, c)`` before that step and ``info``."""
+        s = np.array(s0, dtype=np.float64, copy=True).ravel()
+        if s.shape != (self.nc,):
+            raise ValueError("s0 must have one entry per cell")
+        c = np.array(c0, dtype=np.float64, copy=True, order="C")
+        if c.ndim != 2 or c.shape[1] != self.nc:
+            raise ValueError(f"c0 must have shape (k, {self.nc}), not {c.shape}")
+        k = c.shape[0]
+        if not 1 <= k <= 64:
+            raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (c0 has shape {c.shape})")
+        arrays = []
+        for name, a, n, needed in (("c_bc_values", c_bc_values, self.nf, True), ("sorption", sorption, self.nc, False),
+                                   ("c_source", c_source, self.nc, False)):
+            if a is None:
+                if needed:
+                    raise ValueError(f"{name} is required")
+                arrays.append(None)
+                continue
+            a = _f64(a)
+            if a.shape != (k, n):
+                raise ValueError(f"{name} must have shape ({k}, {n}), not {a.shape}")
+            arrays.append(a)
+        cbv, ads, csrc = arrays
+        par = np.ascontiguousarray(fluxfn_params, dtype=np.float64).ravel()
+        kq, pq = self._vec(q, self.nf, "the flux array", False)
+        kb, pb = self._vec(bc_values, self.nf, "bc_values", False)
+        ka, pa_ = self._vec(accumulation, self.nc, "accumulation", False)
+        ks, ps = self._vec(source, self.nc, "source", False)
+        kk, pk = self._vec(sink, self.nc, "sink", False)
+        if pb is None or pa_ is None:
+            raise ValueError("bc_values and accumulation are required")
+        done, infos = C.c_int32(0), (SolveInfo * (k + 1))()
+        st = self.lib.pfv_transport_advance_nl_multi(
+            self._h, pq, int(fluxfn_kind), _ptr(par, _dp) if par.size else None, int(par.size), pb, pa_, ps, pk, k,
+            _ptr(cbv, _dp), _ptr(ads, _dp), _ptr(csrc, _dp), int(n_steps), float(rtol), int(maxit), _ptr(s, _dp),
+            _ptr(c, _dp), C.byref(done), infos)
+        out = {"steps_done": done.value, "iterations": infos[0].iterations, "converged": bool(infos[0].converged),
+               "rel_residual": infos[0].rel_residual, "solve_ms": infos[0].solve_ms,
+               "c_rel_residual": [i.rel_residual for i in infos[1:]], "c_converged": [bool(i.converged) for i in infos[1:]]}
+        if st != 0 and (raise_on_fail or st != 6):
+            try:
+                self._check(st)
+            except PorefvError as e:  # (the state before the refused step and what was done until then)
+                e.state, e.info = (s, c), out
+                raise
+        return s, c, out
 
     # ---- advection-diffusion on one handle (include/porefv.h: pfv_advdiff_*) ----
     def resident_flux_ptr(self) -> int:

@@ -334,9 +334,15 @@ struct pfv_ctx_impl {
   // ... and the vectors of the step, cell-major interleaved v[i * k + a]
   Buf<double> mc_acc_i, mc_src_i, mc_bref_i, mc_x, mc_z, mc_r, mc_nrm, mc_col;
   // the saturation step (pfv_transport_advance_nl): the caller's arrays, the two states, phi = f(s) and its copy for the
-  // core, rhs, A(phi), the core rows' compacted (rhs, A(phi)), the flux table; nl_out: 4 norms, then 2 status words
+  // core, rhs, A(phi), the core rows' compacted (rhs, A(phi)), the flux table; nl_out: 4 norms, 2 status words, then
+  // the components' 4 k norms
   Buf<double> nl_q, nl_bc, nl_acc, nl_src, nl_sink, nl_s, nl_s2, nl_phi, nl_phi2, nl_bref, nl_rhs, nl_t, nl_cb, nl_ct;
   Buf<double> nl_table, nl_out;
+  // its k components (pfv_transport_advance_nl_multi): the caller's arrays as they came, component-major [k][n] ...
+  Buf<double> nlc_cbc, nlc_ads_in, nlc_src_in, nlc_c_in;
+  // ... and the vectors of the step, cell-major interleaved v[i * k + a]: sorption, source, b_ref, the two states,
+  // psi = phi o c and its copy for the core, rhs, the image, the core rows' compacted (rhs, image)
+  Buf<double> nlc_ads, nlc_src, nlc_bref, nlc_x, nlc_z, nlc_psi, nlc_psi2, nlc_rhs, nlc_t, nlc_cb, nlc_ct;
 
   // ---- advection-diffusion (advdiff.inc): S = diag(acc) + div flux_D + w div diag(q) U on pat_A -------------------
   bool have_advdiff = false;         // val[PFV_MAT_ADVDIFF_SYSTEM], adv_diag, adv_rhs hold a system of the discretization

@@ -1314,10 +1314,15 @@ pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, 
 // Per step: rhs, the forward levels, the core level iterated by nonlinear Jacobi (a host read every kNlCoreCheck-th
 // iteration), the backward levels, F(s) over all rows and ONE host read of its norms and the status words.  The state
 // of the step's start stays in its own buffer until the step is accepted.
-pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
-                                    int n_params, const double* bc_values, const double* accumulation,
-                                    const double* source, const double* sink, int n_steps, double rtol, int maxit,
-                                    double* s, int32_t* steps_done, pfv_solve_info* last) {
+//   With k > 0 components carried by the phase (pfv_transport_advance_nl_multi; k == 0: pfv_transport_advance_nl) the
+// same launches take them (sweep_row_nlc), the core iterates them jointly and the one host read brings their norms too.
+// nl_out: [0, 4) the saturation's norms (all rows, core rows), [4] the two status words, [5, 5 + 2k) the components'
+// (rhs_a, rhs_a) and (F_a, F_a) over all rows, [5 + 2k, 5 + 4k) the same over the core rows.
+static pfv_status advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params, int n_params,
+                             const double* bc_values, const double* accumulation, const double* source,
+                             const double* sink, int k, const double* c_bc_values, const double* sorption,
+                             const double* c_source, int n_steps, double rtol, int maxit, double* s, double* cc,
+                             int32_t* steps_done, pfv_solve_info* last) {
   if (steps_done) *steps_done = 0;
   std::unique_ptr<pfv::Timer> tm;
   bool touched = false;
@@ -1333,26 +1338,42 @@ pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind
     const std::string bad = pfv::fluxfn_check(fluxfn_kind, fluxfn_params, n_params);
     if (!bad.empty()) throw Error(PFV_ERR_ARGUMENT, bad);
     require(bc_values && accumulation && s, "bc_values, accumulation and s are required");
+    require(k == 0 || (c_bc_values && cc), "c_bc_values and c are required");
     require(n_steps >= 0, "bad argument");
     require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
     nc = (size_t)h->nc;
     nf = (size_t)h->nf;
+    if (k > 0 && (int64_t)(k + 1) * (int64_t)std::max(nc, nf) >= (int64_t(1) << 31))
+      throw Error(PFV_ERR_UNSUPPORTED, "(k + 1) x cells (faces) beyond int32 indices");
     if (q) vec_in(h, h->nl_q.ensure(nf), q, nf);
     vec_in(h, h->nl_bc.ensure(nf), bc_values, nf);
     vec_in(h, h->nl_acc.ensure(nc), accumulation, nc);
     if (source) vec_in(h, h->nl_src.ensure(nc), source, nc);
     if (sink) vec_in(h, h->nl_sink.ensure(nc), sink, nc);
     vec_in(h, h->nl_s.ensure(nc), s, nc);
+    if (k > 0) {  // component-major, as they came
+      vec_in(h, h->nlc_cbc.ensure(k * nf), c_bc_values, k * nf);
+      if (sorption) vec_in(h, h->nlc_ads_in.ensure(k * nc), sorption, k * nc);
+      if (c_source) vec_in(h, h->nlc_src_in.ensure(k * nc), c_source, k * nc);
+      vec_in(h, h->nlc_c_in.ensure(k * nc), cc, k * nc);
+    }
     d_q = q ? h->nl_q.p : h->upw_q.p;
     pfv::upwind_face_cells(*h);
-    int32_t off[5];
-    pfv::sweep_nl_check_inputs(*h, d_q, h->nl_bc.p, h->nl_acc.p, sink ? h->nl_sink.p : nullptr, h->nl_s.p, off);
+    int32_t off[pfv::kNlChecks];
+    pfv::sweep_nl_check_inputs(*h, d_q, h->nl_bc.p, h->nl_acc.p, sink ? h->nl_sink.p : nullptr, h->nl_s.p, k,
+                               sorption ? h->nlc_ads_in.p : nullptr, h->nlc_c_in.p, h->nlc_cbc.p, off);
     static const char* what[5] = {"accumulation must be positive: cell ", "negative sink in cell ",
                                   "s outside [0, 1] in cell ", "Dirichlet inflow value outside [0, 1] on face ",
                                   "negative axis 1 index: -1 (neither Dirichlet nor Neumann, with inflow: no upstream "
                                   "cell) face "};
-    for (int k = 0; k < 5; ++k)
-      if (off[k] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, what[k] + std::to_string(off[k]));
+    for (int m = 0; m < 5; ++m)
+      if (off[m] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, what[m] + std::to_string(off[m]));
+    static const char* whatc[3] = {"sorption must not be negative: cell ", "c is not finite in cell ",
+                                   "c_bc_values is not finite on face "};
+    for (int m = 0; m < 3; ++m)
+      if (off[5 + m] != 0x7f7f7f7f)
+        throw Error(PFV_ERR_ARGUMENT, whatc[m] + std::to_string(off[5 + m] / k) + ", component " +
+                                          std::to_string(off[5 + m] % k));
     if (fluxfn_kind == PFV_FLUXFN_TABLE)
       be_h2d(h->nl_table.ensure((size_t)n_params), fluxfn_params, sizeof(double) * (size_t)n_params, h->stream);
     F = pfv::fluxfn_make(fluxfn_kind, fluxfn_params, n_params, h->nl_table.p);
@@ -1365,7 +1386,14 @@ pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind
     values_changed(h, Windows::drop);
     pfv::upwind_bref_nl(*h, F, d_q, h->nl_bc.p, h->nl_bref.ensure(nc));
     for (pfv::Buf<double>* b : {&h->nl_s2, &h->nl_phi, &h->nl_phi2, &h->nl_rhs, &h->nl_t}) b->ensure(nc);
-    h->nl_out.ensure(8);
+    h->nl_out.ensure(8 + 4 * (size_t)k);
+    if (k > 0) {  // the vectors of the step, cell-major interleaved
+      if (sorption) pfv::multi_interleave(*h, (int64_t)nc, k, h->nlc_ads_in.p, h->nlc_ads.ensure(k * nc));
+      if (c_source) pfv::multi_interleave(*h, (int64_t)nc, k, h->nlc_src_in.p, h->nlc_src.ensure(k * nc));
+      pfv::multi_interleave(*h, (int64_t)nc, k, h->nlc_c_in.p, h->nlc_x.ensure(k * nc));
+      pfv::upwind_bref_nlc(*h, F, k, d_q, h->nl_bc.p, h->nlc_cbc.p, h->nlc_bref.ensure(k * nc));
+      for (pfv::Buf<double>* b : {&h->nlc_z, &h->nlc_psi, &h->nlc_psi2, &h->nlc_rhs, &h->nlc_t}) b->ensure(k * nc);
+    }
     // the order of the flux, built on first use and kept while assemblies bring the same edges (sweep_note_assembly)
     if (!h->sweep) h->sweep = std::make_unique<pfv::Sweep>();
     pfv::Sweep& sw = *h->sweep;
@@ -1379,6 +1407,10 @@ pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind
     if (sw.n_core > 0) {
       h->nl_cb.ensure((size_t)sw.n_core);
       h->nl_ct.ensure((size_t)sw.n_core);
+      if (k > 0) {
+        h->nlc_cb.ensure(k * (size_t)sw.n_core);
+        h->nlc_ct.ensure(k * (size_t)sw.n_core);
+      }
     }
   });
   if (st != PFV_OK) {
@@ -1391,6 +1423,8 @@ pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind
   int32_t completed = 0;
   int64_t core_total = 0, launches = 0;
   pfv_solve_info info{};
+  std::vector<pfv_solve_info> cinfo((size_t)k);
+  std::vector<double> hst(5 + 4 * (size_t)k);
   std::string err;
   for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
     pfv_status verdict = PFV_OK;
@@ -1404,14 +1438,30 @@ pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind
       int32_t* status = reinterpret_cast<int32_t*>(out + 4);  // [0] the levels outside the core, [1] the core
       const bool has_core = sw.n_core > 0;
       const int core = has_core ? sw.core_level : sw.nlev;
+      pfv::NlComp C;  // the levels outside the core; Cc: the core level, with psi of the previous iterate
+      if (k > 0) {
+        C.k = k;
+        C.ads = sorption ? c.nlc_ads.p : nullptr;
+        C.rhs = c.nlc_rhs.p;
+        C.c_start = c.nlc_x.p;
+        C.c = c.nlc_z.p;
+        C.psi = c.nlc_psi.p;
+      }
+      pfv::NlComp Cc = C;
+      Cc.psi_prev = k > 0 ? c.nlc_psi2.p : nullptr;
+      double* cout = out + 5;
       pfv::upwind_step_rhs_multi(c, 1, acc, d_src, c.nl_bref.p, s_old, c.nl_rhs.p);
+      if (k > 0)
+        pfv::upwind_step_rhs_nlc(c, k, acc, s_old, C.ads, c_source ? c.nlc_src.p : nullptr, c.nlc_bref.p, c.nlc_x.p,
+                                 c.nlc_rhs.p);
       pfv::be_memset(out, 0, 4 * sizeof(double), c.stream);
       pfv::be_memset(status, 0x7f, 2 * sizeof(int32_t), c.stream);
-      launches = pfv::sweep_apply_nl(c, sw, 0, core, c.pat_T, val, diag, d_sink, acc, rhs, F, s_old, s_new, phi, status);
-      double hst[5];
+      if (k > 0) pfv::be_memset(cout, 0, 4 * (size_t)k * sizeof(double), c.stream);
+      launches = pfv::sweep_apply_nl(c, sw, 0, core, c.pat_T, val, diag, d_sink, acc, rhs, F, s_old, s_new, phi, status, C);
+      const size_t hst_bytes = sizeof(double) * hst.size();
       auto flagged = [&](bool core_too, int32_t& cell) {
         int32_t w[2];
-        std::memcpy(w, hst + 4, sizeof(w));
+        std::memcpy(w, hst.data() + 4, sizeof(w));
         cell = core_too ? std::min(w[0], w[1]) : w[0];
         return cell != 0x7f7f7f7f;
       };
@@ -1420,16 +1470,31 @@ pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind
         bool settled = false;
         pfv::sweep_residual_norms(c, c.nc, rhs, rhs, out);  // out[0] = (rhs, rhs)
         pfv::sweep_nl_core_init(c, sw, F, s_old, s_new, phi);
+        if (k > 0) {
+          pfv::sweep_norms_interleaved(c, c.nc, k, C.rhs, C.rhs, cout);  // cout[a] = (rhs_a, rhs_a)
+          pfv::sweep_nlc_core_init(c, sw, phi, C);
+        }
         while (core_it < maxit && !settled) {
-          pfv::sweep_nl_core_keep(c, sw, phi, c.nl_phi2.p, status + 1);
+          // (once the saturation has passed its own test it stays, with its status word: the components alone go on)
+          if (!Cc.frozen) pfv::sweep_nl_core_keep(c, sw, phi, c.nl_phi2.p, status + 1);
+          if (k > 0) pfv::sweep_nlc_core_keep(c, sw, k, C.psi, c.nlc_psi2.p);
           pfv::sweep_levels_nl(c, sw, core, core + 1, c.pat_T, val, diag, d_sink, acc, rhs, F, s_new, c.nl_phi2.p, s_new,
-                               phi, status + 1);
+                               phi, status + 1, Cc);
           ++core_it;
           if (core_it % pfv::kNlCoreCheck != 0 && core_it != maxit) continue;
-          pfv::sweep_nl_core_image(c, sw, c.pat_T, val, d_sink, acc, rhs, s_new, phi, c.nl_cb.p, c.nl_ct.p);
-          pfv::sweep_residual_norms(c, sw.n_core, c.nl_cb.p, c.nl_ct.p, out + 2);  // out[3] = (F_core, F_core)
-          be_d2h(hst, out, sizeof(hst), c.stream);
+          if (!Cc.frozen) {
+            pfv::sweep_nl_core_image(c, sw, c.pat_T, val, d_sink, acc, rhs, s_new, phi, c.nl_cb.p, c.nl_ct.p);
+            pfv::sweep_residual_norms(c, sw.n_core, c.nl_cb.p, c.nl_ct.p, out + 2);  // out[3] = (F_core, F_core)
+          }
+          if (k > 0) {
+            pfv::sweep_nlc_core_image(c, sw, c.pat_T, val, d_sink, acc, s_new, C, c.nlc_cb.p, c.nlc_ct.p);
+            pfv::sweep_norms_interleaved(c, sw.n_core, k, c.nlc_cb.p, c.nlc_ct.p, cout + 2 * k);
+          }
+          be_d2h(hst.data(), out, hst_bytes, c.stream);
           settled = hst[3] <= 0.25 * rtol * rtol * hst[0];
+          Cc.frozen = settled;
+          for (int a = 0; a < k; ++a)  // (F_core_a, F_core_a) against (rhs_a, rhs_a)
+            settled = settled && hst[5 + 3 * (size_t)k + a] <= 0.25 * rtol * rtol * hst[5 + (size_t)a];
         }
         core_total += core_it;
         launches += 2;
@@ -1437,6 +1502,12 @@ pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind
           info = pfv_solve_info{};
           info.iterations = core_it;
           info.rel_residual = hst[0] > 0.0 ? std::sqrt(hst[3] / hst[0]) : 0.0;
+          for (int a = 0; a < k; ++a) {
+            const double bb = hst[5 + (size_t)a], rr = hst[5 + 3 * (size_t)k + a];
+            cinfo[(size_t)a] = pfv_solve_info{};
+            cinfo[(size_t)a].iterations = core_it;
+            cinfo[(size_t)a].rel_residual = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
+          }
           int32_t cell;  // (the core's word belongs to an iterate that has not settled: the other levels' alone)
           if (flagged(false, cell))
             throw Error(PFV_ERR_ARGUMENT, "step " + std::to_string(step) + " leaves [0, 1]: no root in cell " +
@@ -1447,11 +1518,13 @@ pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind
           return;
         }
         launches += pfv::sweep_apply_nl(c, sw, core + 1, sw.nlev, c.pat_T, val, diag, d_sink, acc, rhs, F, s_old, s_new, phi,
-                                        status);
+                                        status, C);
       }
-      pfv::sweep_nl_image(c, c.pat_T, val, d_sink, acc, s_new, phi, c.nl_t.p);
+      if (k > 0) pfv::sweep_nlc_image(c, c.pat_T, val, d_sink, acc, s_new, phi, c.nl_t.p, C, c.nlc_t.p);
+      else pfv::sweep_nl_image(c, c.pat_T, val, d_sink, acc, s_new, phi, c.nl_t.p);
       pfv::sweep_residual_norms(c, c.nc, rhs, c.nl_t.p, out);
-      be_d2h(hst, out, sizeof(hst), c.stream);
+      if (k > 0) pfv::sweep_norms_interleaved(c, c.nc, k, C.rhs, c.nlc_t.p, cout);
+      be_d2h(hst.data(), out, hst_bytes, c.stream);
       info = pfv_solve_info{};
       info.iterations = has_core ? core_it : 1;
       info.rel_residual = hst[0] > 0.0 ? std::sqrt(hst[1] / hst[0]) : 0.0;
@@ -1460,14 +1533,30 @@ pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind
         throw Error(PFV_ERR_ARGUMENT, "step " + std::to_string(step) + " leaves [0, 1]: no root in cell " +
                                           std::to_string(cell));
       info.converged = hst[1] <= rtol * rtol * hst[0] ? 1 : 0;
-      if (!info.converged) {
+      int bad = info.converged ? -1 : k;  // the first component whose check fails; k: the saturation
+      for (int a = k - 1; a >= 0; --a) {
+        const double bb = hst[5 + (size_t)a], rr = hst[5 + (size_t)k + a];
+        pfv_solve_info& ia = cinfo[(size_t)a];
+        ia = pfv_solve_info{};
+        ia.iterations = info.iterations;
+        ia.rel_residual = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
+        ia.converged = rr <= rtol * rtol * bb ? 1 : 0;  // (0 <= 0: a component that is absent everywhere is valid)
+        if (!ia.converged && info.converged) bad = a;
+      }
+      if (bad >= 0) {
         verdict = PFV_ERR_NOT_CONVERGED;
-        c.err = "step " + std::to_string(step) + ": relative residual " + std::to_string(info.rel_residual) +
+        const double rel = bad == k ? info.rel_residual : cinfo[(size_t)bad].rel_residual;
+        c.err = "step " + std::to_string(step) + ": relative residual " + std::to_string(rel) +
+                (bad == k ? std::string() : " of component " + std::to_string(bad)) +
                 " after the sweep (a flux that contradicts the discretization's?)";
         return;
       }
       std::swap(c.nl_s.p, c.nl_s2.p);
       std::swap(c.nl_s.cap, c.nl_s2.cap);
+      if (k > 0) {
+        std::swap(c.nlc_x.p, c.nlc_z.p);
+        std::swap(c.nlc_x.cap, c.nlc_z.cap);
+      }
       ++completed;
     });
     if (st == PFV_OK) st = verdict;
@@ -1478,6 +1567,10 @@ pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind
     ms = tm->stop(h->stream);
     tm.reset();
     vec_out(h, s, h->nl_s.p, nc);
+    if (k > 0) {
+      pfv::multi_deinterleave(*h, (int64_t)nc, k, h->nlc_x.p, h->nlc_c_in.p);
+      vec_out(h, cc, h->nlc_c_in.p, k * nc);
+    }
     pfv::be_sync(h->stream);
     upwind_drop_transport(h, true);
   });
@@ -1485,10 +1578,15 @@ pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind
   if (last) {
     *last = info;
     if (completed > 0) last->solve_ms = ms / completed;
+    for (int a = 0; a < k; ++a) {
+      last[1 + a] = cinfo[(size_t)a];
+      last[1 + a].solve_ms = last->solve_ms;
+    }
   }
   h->stats.transport_nl_ms = ms;
   h->stats.transport_nl_steps = completed;
   h->stats.transport_nl_core_iterations = core_total;
+  h->stats.transport_nl_components = k;
   if (h->sweep && h->sweep->valid) {
     h->stats.sweep_levels = h->sweep->nlev;
     h->stats.sweep_core_cells = h->sweep->n_core;
@@ -1500,6 +1598,27 @@ pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind
     return st;
   }
   return st2;
+}
+
+pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
+                                    int n_params, const double* bc_values, const double* accumulation,
+                                    const double* source, const double* sink, int n_steps, double rtol, int maxit,
+                                    double* s, int32_t* steps_done, pfv_solve_info* last) {
+  return advance_nl(h, q, fluxfn_kind, fluxfn_params, n_params, bc_values, accumulation, source, sink, 0, nullptr,
+                    nullptr, nullptr, n_steps, rtol, maxit, s, nullptr, steps_done, last);
+}
+
+pfv_status pfv_transport_advance_nl_multi(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
+                                          int n_params, const double* bc_values, const double* accumulation,
+                                          const double* source, const double* sink, int k, const double* c_bc_values,
+                                          const double* sorption, const double* c_source, int n_steps, double rtol,
+                                          int maxit, double* s, double* c, int32_t* steps_done, pfv_solve_info* last) {
+  if (k < 1 || k > 64) {
+    if (steps_done) *steps_done = 0;
+    return guarded(h, [&] { require(false, "k must lie in 1 .. 64"); });
+  }
+  return advance_nl(h, q, fluxfn_kind, fluxfn_params, n_params, bc_values, accumulation, source, sink, k, c_bc_values,
+                    sorption, c_source, n_steps, rtol, maxit, s, c, steps_done, last);
 }
 
 // ---- advection-diffusion on one handle (advdiff.inc) -----------------------------------------------------------

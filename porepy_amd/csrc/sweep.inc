@@ -500,18 +500,124 @@ PFV_FN void sweep_row_nl(int32_t i, const int32_t* ip, const int32_t* ix, const 
   phi[i] = f;
 }
 
-// levels [l0, l1) of the order, by the rule of the launch plan: one level is one launch, a run is one workgroup
+// ---- k components carried by the transported phase (pfv_transport_advance_nl_multi).  Once s_i and phi_i = f(s_i) of a
+// row are known, component a of the row is one division:
+//     d = acc_i s_i + ads_ai + o_i phi_i,   c_ai = (rhs_ai - sum_{lev[j] < lev[i]} A_ij psi_aj) / d,   psi_ai = phi_i c_ai
+// with psi = phi o c carried for the cells downstream as phi is.  Vectors are interleaved as in sweep_row_multi,
+// v[i * k + a]: the k values of an upstream cell are one run of 8 k bytes.  The thread that found the root of the row
+// takes its components, four accumulators at a time, the sums in stored order; the last chunk takes k mod 4.  d == 0 (a
+// dry cell without sorption) keeps the value of the step's start; the acceptance check judges that row.  Core rows take psi_prev of their in-core neighbours, as phi_prev.
+// `frozen` (core iterations after the saturation's own stop test has passed): s and phi of the row stay as they are and
+// the components alone go on, so that the saturation stops where pfv_transport_advance_nl stops, bit for bit.
+constexpr int kNlcGroup = 8;  // entries of a row whose loads are issued together (a tetrahedron's row has 5, a hexahedron's 7)
+struct NlComp {
+  int k = 0;                       // 0: the saturation alone
+  const double* ads = nullptr;     // [n k] sorption capacity (may be nullptr)
+  const double* rhs = nullptr;     // [n k]
+  const double* c_start = nullptr; // [n k] the state of the step's start
+  const double* psi_prev = nullptr;
+  bool frozen = false;
+  double* c = nullptr;
+  double* psi = nullptr;
+};
+
+PFV_FN double sweep_nlc_divide(const NlComp& C, int64_t p, double as, double op, double u) {
+  const double d = as + (C.ads ? C.ads[p] : 0.0) + op;
+  return d != 0.0 ? (C.rhs[p] - u) / d : C.c_start[p];
+}
+
+PFV_FN void sweep_row_nlc(int32_t i, const int32_t* ip, const int32_t* ix, const double* val, const double* diag,
+                          const double* sink, const double* acc, const double* rhs, const int32_t* lev, const FluxFn& F,
+                          const double* s_start, const double* phi_prev, double* s, double* phi, int32_t* status,
+                          const NlComp& C) {
+  if (!C.frozen) sweep_row_nl(i, ip, ix, val, diag, sink, acc, rhs, lev, F, s_start, phi_prev, s, phi, status);
+  const int k = C.k;
+  const int32_t li = lev[i];
+  const double ph = phi[i];
+  const double as = acc[i] * s[i], op = (diag[i] + (sink ? sink[i] : 0.0)) * ph;
+  const int64_t p = (int64_t)i * k;
+  const int e_end = ip[i + 1];
+  for (int a0 = 0; a0 < k; a0 += 4) {
+    // Components a0 .. a0 + 3.  In the last chunk an accumulator beyond k takes component a0 again (offset 0): it sums
+    // the same products in the same order and writes the same bits to the same place, so nothing below branches on k.
+    // The entries are taken kNlcGroup at a time: the group's indices, then its levels, then its values are loaded
+    // together, so a row of up to kNlcGroup entries pays three round trips to memory and not three per entry -- the
+    // level is bound by that latency.  A slot past the row's end repeats the last entry, and a slot that is not
+    // upstream reads the row's own rhs instead of psi (an address that is valid and that no thread writes here); both
+    // enter the sums as + 0, in stored order.
+    const int m = k - a0;
+    const int o1 = m > 1 ? 1 : 0, o2 = m > 2 ? 2 : 0, o3 = m > 3 ? 3 : 0;
+    const double* own = C.rhs + p + a0;
+    double u0 = 0.0, u1 = 0.0, u2 = 0.0, u3 = 0.0;
+    for (int e0 = ip[i]; e0 < e_end; e0 += kNlcGroup) {
+      int32_t j[kNlcGroup];
+      double v[kNlcGroup];
+      const double* up[kNlcGroup];
+#pragma unroll
+      for (int t = 0; t < kNlcGroup; ++t) {
+        const int e = e0 + t < e_end ? e0 + t : e_end - 1;
+        j[t] = ix[e];
+        v[t] = val[e];
+      }
+#pragma unroll
+      for (int t = 0; t < kNlcGroup; ++t) {
+        const int32_t lj = lev[j[t]];
+        const double* src = lj < li ? C.psi : (C.psi_prev && lj == li && j[t] != i ? C.psi_prev : nullptr);
+        up[t] = src && e0 + t < e_end ? src + (int64_t)j[t] * k + a0 : nullptr;
+      }
+#pragma unroll
+      for (int t = 0; t < kNlcGroup; ++t) {
+        const double* r = up[t] ? up[t] : own;
+        const double w0 = r[0], w1 = r[o1], w2 = r[o2], w3 = r[o3];
+        const double vt = up[t] ? v[t] : 0.0;
+        u0 += vt * (up[t] ? w0 : 0.0);
+        u1 += vt * (up[t] ? w1 : 0.0);
+        u2 += vt * (up[t] ? w2 : 0.0);
+        u3 += vt * (up[t] ? w3 : 0.0);
+      }
+    }
+    const int64_t p0 = p + a0, p1 = p0 + o1, p2 = p0 + o2, p3 = p0 + o3;
+    const double x0 = sweep_nlc_divide(C, p0, as, op, u0), x1 = sweep_nlc_divide(C, p1, as, op, u1);
+    const double x2 = sweep_nlc_divide(C, p2, as, op, u2), x3 = sweep_nlc_divide(C, p3, as, op, u3);
+    C.c[p0] = x0;  // (the loads of all four before the first store: a store could alias them for the compiler)
+    C.c[p1] = x1;
+    C.c[p2] = x2;
+    C.c[p3] = x3;
+    C.psi[p0] = ph * x0;
+    C.psi[p1] = ph * x1;
+    C.psi[p2] = ph * x2;
+    C.psi[p3] = ph * x3;
+  }
+}
+
+// levels [l0, l1) of the order, by the rule of the launch plan: one level is one launch, a run is one workgroup;
+// with components (C.k > 0) both forms inline sweep_row_nlc, else sweep_row_nl
 static void sweep_levels_nl(pfv_ctx_impl& c, const Sweep& sw, int l0, int l1, const CsrPattern& P, const double* val,
                             const double* diag, const double* sink, const double* acc, const double* rhs,
                             const FluxFn& F, const double* s_start, const double* phi_prev, double* s, double* phi,
-                            int32_t* status) {
+                            int32_t* status, const NlComp& C) {
   stream_t st = c.stream;
   const int32_t* ip = P.indptr;
   const int32_t* ix = P.indices;
   const int32_t* lev = sw.lev(false);
   const int32_t* ord = sw.ord(false);
   const int32_t* lp = sw.lptr;
-  if (l1 - l0 == 1) {
+  if (C.k > 0) {
+    if (l1 - l0 == 1) {
+      const int32_t a0 = sw.h_lptr[(size_t)l0], m = sw.h_lptr[(size_t)l1] - a0;
+      parallel_for(st, m, PFV_LAMBDA(int64_t k) {
+        sweep_row_nlc(ord[a0 + k], ip, ix, val, diag, sink, acc, rhs, lev, F, s_start, phi_prev, s, phi, status, C);
+      });
+    } else if (l1 > l0) {
+      block_for<256>(st, 1, 0, PFV_LAMBDA(const WaveCtx& w) {
+        for (int l = l0; l < l1; ++l) {
+          const int32_t a0 = lp[l], m = lp[l + 1] - a0;
+          PFV_LANES(k, m) sweep_row_nlc(ord[a0 + k], ip, ix, val, diag, sink, acc, rhs, lev, F, s_start, phi_prev, s, phi, status, C);
+          w.sync();  // (the next level reads what this one wrote: same workgroup, same CU)
+        }
+      });
+    }
+  } else if (l1 - l0 == 1) {
     const int32_t a0 = sw.h_lptr[(size_t)l0], m = sw.h_lptr[(size_t)l1] - a0;
     parallel_for(st, m, PFV_LAMBDA(int64_t k) {
       sweep_row_nl(ord[a0 + k], ip, ix, val, diag, sink, acc, rhs, lev, F, s_start, phi_prev, s, phi, status);
@@ -531,12 +637,13 @@ static void sweep_levels_nl(pfv_ctx_impl& c, const Sweep& sw, int l0, int l1, co
 // (which is iterated on its own) falls into it.  Returns the launches.
 static int sweep_apply_nl(pfv_ctx_impl& c, const Sweep& sw, int from, int to, const CsrPattern& P, const double* val,
                           const double* diag, const double* sink, const double* acc, const double* rhs,
-                          const FluxFn& F, const double* s_start, double* s, double* phi, int32_t* status) {
+                          const FluxFn& F, const double* s_start, double* s, double* phi, int32_t* status,
+                          const NlComp& C) {
   int launches = 0;
   for (const Sweep::Seg& g : sw.plan) {
     const int l0 = std::max(g.l0, from), l1 = std::min(g.l1, to);
     if (l0 >= l1) continue;
-    sweep_levels_nl(c, sw, l0, l1, P, val, diag, sink, acc, rhs, F, s_start, nullptr, s, phi, status);
+    sweep_levels_nl(c, sw, l0, l1, P, val, diag, sink, acc, rhs, F, s_start, nullptr, s, phi, status, C);
     ++launches;
   }
   return launches;
@@ -565,6 +672,94 @@ static void sweep_nl_image(pfv_ctx_impl& c, const CsrPattern& P, const double* v
   });
 }
 
+// The components' images beside it: tc[i, a] = (acc_i s_i + ads_ai) c_ai + sum_e A_ie psi_aj + sink_i psi_ai, in stored
+// order; lev as in sweep_nl_row_image.
+PFV_FN double sweep_nlc_row_image(int32_t i, int a, int k, const int32_t* ip, const int32_t* ix, const double* val,
+                                  const double* sink, const double* acc, const double* ads, const double* s,
+                                  const double* c, const double* psi, const int32_t* lev) {
+  double t = 0.0;
+  for (int e = ip[i]; e < ip[i + 1]; ++e) {
+    const int32_t j = ix[e];
+    if (!lev || lev[j] <= lev[i]) t += val[e] * psi[(int64_t)j * k + a];
+  }
+  const int64_t p = (int64_t)i * k + a;
+  if (sink) t += sink[i] * psi[p];
+  return t + (acc[i] * s[i] + (ads ? ads[p] : 0.0)) * c[p];
+}
+
+// one kernel for the saturation's image and the k components': work item (row, a), a == k the saturation
+static void sweep_nlc_image(pfv_ctx_impl& c, const CsrPattern& P, const double* val, const double* sink,
+                            const double* acc, const double* s, const double* phi, double* t, const NlComp& C,
+                            double* tc) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int k = C.k;
+  parallel_for(c.stream, P.nrows * (k + 1), PFV_LAMBDA(int64_t w) {
+    const int32_t i = (int32_t)(w / (k + 1));
+    const int a = (int)(w % (k + 1));
+    if (a == k) t[i] = sweep_nl_row_image(i, ip, ix, val, sink, acc, s, phi, nullptr);
+    else tc[(int64_t)i * k + a] = sweep_nlc_row_image(i, a, k, ip, ix, val, sink, acc, C.ads, s, C.c, C.psi, nullptr);
+  });
+}
+
+// out[a] = (r_a, r_a), out[k + a] = (r_a - t_a, r_a - t_a) of interleaved vectors of n rows, with the partition and the
+// reduction order of sweep_residual_norms_multi: a workgroup takes a range of rows, slot g * k + a of it the rows
+// lo + g, lo + g + G, ... of component a (G = 256 / k), the G sums of a component are folded pairwise, and one
+// workgroup per number adds the workgroups' partial sums.
+static void sweep_norms_interleaved(pfv_ctx_impl& c, int64_t n, int k, const double* r, const double* t, double* out) {
+  stream_t s = c.stream;
+  const int nb = (int)std::min<int64_t>(kGmresBlocks, (n * k + 2047) / 2048);
+  const int G = 256 / k, slots = G * k;
+  int fold = 1;
+  while (fold < G) fold <<= 1;
+  double* partial = c.red.ensure(2 * (size_t)k * kGmresBlocks + 64);
+  block_for<256>(s, nb, 2 * 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& w) {
+    double* sh = reinterpret_cast<double*>(w.lds);
+    const int64_t blk = w.item;
+    const int64_t lo = n * blk / nb, hi = n * (blk + 1) / nb;
+    PFV_LANES(slot, slots) {
+      const int a = slot % k, g = slot / k;
+      double a0 = 0.0, a1 = 0.0;
+      for (int64_t i = lo + g; i < hi; i += G) {
+        const double ri = r[i * k + a], d = ri - t[i * k + a];
+        a0 += ri * ri;
+        a1 += d * d;
+      }
+      sh[slot] = a0;
+      sh[256 + slot] = a1;
+    }
+    w.sync();
+    for (int o = fold >> 1; o > 0; o >>= 1) {
+      PFV_LANES(slot, slots) {
+        if (slot / k < o && slot / k + o < G) {
+          sh[slot] += sh[slot + o * k];
+          sh[256 + slot] += sh[256 + slot + o * k];
+        }
+      }
+      w.sync();
+    }
+    PFV_LANES(a, k) {
+      partial[(int64_t)a * nb + blk] = sh[a];
+      partial[(int64_t)(k + a) * nb + blk] = sh[256 + a];
+    }
+    w.sync();
+  });
+  block_for<256>(s, 2 * k, 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& wc) {
+    double* sh = reinterpret_cast<double*>(wc.lds);
+    const int64_t m = wc.item;
+    double a = 0.0;
+    for (int i = wc.lane; i < nb; i += wc.width) a += partial[m * nb + i];
+    sh[wc.lane] = a;
+    wc.sync();
+    for (int o = wc.width >> 1; o > 0; o >>= 1) {
+      if (wc.lane < o) sh[wc.lane] += sh[wc.lane + o];
+      wc.sync();
+    }
+    if (wc.lane0()) out[m] = sh[0];
+    wc.sync();
+  });
+}
+
 // The core rows, compacted: cb[k] = rhs of the k-th core row, ct[k] = its image.  A row that sits at an end of [0, 1]
 // with the residual pointing outwards (it took that end because it has no root inside) counts as solved: the
 // iteration then settles, and the step is refused by the status word, not by maxit.
@@ -586,6 +781,24 @@ static void sweep_nl_core_image(pfv_ctx_impl& c, const Sweep& sw, const CsrPatte
   });
 }
 
+// the same for the components, interleaved: ccb[m k + a], cct[m k + a] of the m-th core row
+static void sweep_nlc_core_image(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* val,
+                                 const double* sink, const double* acc, const double* s, const NlComp& C, double* ccb,
+                                 double* cct) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* ord = sw.ord(false);
+  const int32_t* lev = sw.lev(false);
+  const int32_t a0 = sw.h_lptr[(size_t)sw.core_level];
+  const int k = C.k;
+  parallel_for(c.stream, sw.n_core * k, PFV_LAMBDA(int64_t w) {
+    const int32_t i = ord[a0 + w / k];
+    const int a = (int)(w % k);
+    ccb[w] = C.rhs[(int64_t)i * k + a];
+    cct[w] = sweep_nlc_row_image(i, a, k, ip, ix, val, sink, acc, C.ads, s, C.c, C.psi, lev);
+  });
+}
+
 // before the first core iteration: the core rows start from the state of the step's start
 static void sweep_nl_core_init(pfv_ctx_impl& c, const Sweep& sw, const FluxFn& F, const double* s_old, double* s,
                                double* phi) {
@@ -596,6 +809,29 @@ static void sweep_nl_core_init(pfv_ctx_impl& c, const Sweep& sw, const FluxFn& F
     double df;
     s[i] = s_old[i];
     phi[i] = fluxfn_eval(F, s_old[i], &df);
+  });
+}
+
+// ... and so do their components: c <- c_start, psi <- phi c_start (after sweep_nl_core_init)
+static void sweep_nlc_core_init(pfv_ctx_impl& c, const Sweep& sw, const double* phi, const NlComp& C) {
+  const int32_t* ord = sw.ord(false);
+  const int32_t a0 = sw.h_lptr[(size_t)sw.core_level];
+  const int k = C.k;
+  parallel_for(c.stream, sw.n_core * k, PFV_LAMBDA(int64_t w) {
+    const int32_t i = ord[a0 + w / k];
+    const int64_t p = (int64_t)i * k + w % k;
+    C.c[p] = C.c_start[p];
+    C.psi[p] = phi[i] * C.c_start[p];
+  });
+}
+
+// before every core iteration: psi_prev <- psi on the core rows
+static void sweep_nlc_core_keep(pfv_ctx_impl& c, const Sweep& sw, int k, const double* psi, double* psi_prev) {
+  const int32_t* ord = sw.ord(false);
+  const int32_t a0 = sw.h_lptr[(size_t)sw.core_level];
+  parallel_for(c.stream, sw.n_core * k, PFV_LAMBDA(int64_t w) {
+    const int64_t p = (int64_t)ord[a0 + w / k] * k + w % k;
+    psi_prev[p] = psi[p];
   });
 }
 
@@ -635,11 +871,56 @@ static void upwind_bref_nl(pfv_ctx_impl& c, const FluxFn& F, const double* d_q, 
   });
 }
 
+// b_ref of component a = div (rhs_neu cbc_a + rhs_dir diag(q) (f(bc) o cbc_a)), by the same rule and in the same face
+// order: on a Dirichlet inflow face cbc is the concentration in the entering phase, on a Neumann face the component's
+// flux.  cbc is component-major [k][nf] as the caller passed it, bref interleaved.
+static void upwind_bref_nlc(pfv_ctx_impl& c, const FluxFn& F, int k, const double* d_q, const double* bc,
+                            const double* cbc, double* bref) {
+  const int64_t nf = c.nf;
+  const int32_t* cf_ptr = c.cf_ptr;
+  const int32_t* cf_idx = c.cf_idx;
+  const int8_t* cf_sgn = c.cf_sgn;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* cnt = c.upw_cnt;
+  parallel_for(c.stream, c.nc * k, PFV_LAMBDA(int64_t t) {
+    const int64_t cell = t / k, a = t % k;
+    double b = 0.0;
+    for (int e = cf_ptr[cell]; e < cf_ptr[cell + 1]; ++e) {
+      const int f = cf_idx[e];
+      const unsigned cl = cls[f];
+      if (cl & (UPW_NEU | UPW_DIRIN)) {
+        const double cb = cbc[a * nf + f];
+        double v = 0.0, df;
+        if (cl & UPW_NEU) v = (double)(cnt[f] - cnt[nf + f]) * cb;
+        if (cl & UPW_DIRIN) v += d_q[f] * (fluxfn_eval(F, bc[f], &df) * cb);
+        b += (double)cf_sgn[e] * v;
+      }
+    }
+    bref[t] = b;
+  });
+}
+
+// right-hand side of the components' step: rhs_a = (acc o s_old + ads_a) o c_old_a - b_ref_a + src_a (interleaved)
+static void upwind_step_rhs_nlc(pfv_ctx_impl& c, int k, const double* acc, const double* s_old, const double* ads,
+                                const double* src, const double* bref, const double* x, double* rhs) {
+  parallel_for(c.stream, c.nc * k, PFV_LAMBDA(int64_t t) {
+    const int64_t i = t / k;
+    double r = (acc[i] * s_old[i] + (ads ? ads[t] : 0.0)) * x[t];
+    r -= bref[t];
+    if (src) r += src[t];
+    rhs[t] = r;
+  });
+}
+
 // What the call refuses in its arrays, each with the lowest index: st[0] accumulation <= 0 or NaN, st[1] sink < 0,
 // st[2] s outside [0, 1], st[3] a Dirichlet inflow value outside [0, 1], st[4] a boundary face with inflow under q that
-// is neither Dirichlet nor Neumann.  (0x7f7f7f7f: none.)
+// is neither Dirichlet nor Neumann.  With k > 0 components (component-major arrays as the caller passed them; an
+// offender is reported as index * k + component, so the lowest cell or face comes first): st[5] a negative or NaN
+// sorption, st[6] a non-finite c, st[7] a non-finite c_bc on a face that is read.  (0x7f7f7f7f: none.)
+constexpr int kNlChecks = 8;
 static void sweep_nl_check_inputs(pfv_ctx_impl& c, const double* d_q, const double* bc, const double* acc,
-                                  const double* sink, const double* s, int32_t out[5]) {
+                                  const double* sink, const double* s, int k, const double* ads, const double* cc,
+                                  const double* cbc, int32_t out[kNlChecks]) {
   stream_t st_ = c.stream;
   const int64_t nc = c.nc, nf = c.nf;
   const uint8_t* cls = c.upw_cls;
@@ -647,22 +928,30 @@ static void sweep_nl_check_inputs(pfv_ctx_impl& c, const double* d_q, const doub
   const int32_t* cnt = c.upw_cnt;
   const uint8_t* flag = c.have_upw_bc ? c.upw_bc.p : nullptr;
   int32_t* st = c.status.ensure(16);
-  be_memset(st, 0x7f, sizeof(int32_t) * 5, st_);
+  be_memset(st, 0x7f, sizeof(int32_t) * kNlChecks, st_);
   parallel_for(st_, std::max(nc, nf), PFV_LAMBDA(int64_t t) {
+    const double big = 1.79769313486231570e308;
     if (t < nc) {
       if (!(acc[t] > 0.0)) atomic_min_i32(st, (int32_t)t);
       if (sink && !(sink[t] >= 0.0)) atomic_min_i32(st + 1, (int32_t)t);
       if (!(s[t] >= 0.0 && s[t] <= 1.0)) atomic_min_i32(st + 2, (int32_t)t);
+      for (int a = 0; a < k; ++a) {
+        if (ads && !(ads[a * nc + t] >= 0.0)) atomic_min_i32(st + 5, (int32_t)(t * k + a));
+        if (!(fabs(cc[a * nc + t]) <= big)) atomic_min_i32(st + 6, (int32_t)(t * k + a));
+      }
     }
     if (t < nf) {
       if ((cls[t] & UPW_DIRIN) && !(bc[t] >= 0.0 && bc[t] <= 1.0)) atomic_min_i32(st + 3, (int32_t)t);
+      if (cls[t] & (UPW_NEU | UPW_DIRIN))
+        for (int a = 0; a < k; ++a)
+          if (!(fabs(cbc[a * nf + t]) <= big)) atomic_min_i32(st + 7, (int32_t)(t * k + a));
       if (cnt[t] + cnt[nf + t] == 1 && flag && !(flag[t] & (PFV_BC_DIR | PFV_BC_NEU))) {
         const int32_t u = d_q[t] >= 0.0 ? side[t] : side[nf + t];
         if (u < 0) atomic_min_i32(st + 4, (int32_t)t);
       }
     }
   });
-  be_d2h(out, st, sizeof(int32_t) * 5, st_);
+  be_d2h(out, st, sizeof(int32_t) * kNlChecks, st_);
 }
 
 // The direct solve of the transport system of an acyclic flux: x = M^-1 b with M = S, then the true residual.  Should

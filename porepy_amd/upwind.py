@@ -285,14 +285,7 @@ class Upwind:
         ``||F(s)|| / ||rhs||``.  A step that would leave [0, 1] raises ``ValueError`` naming the step and the cell; the
         error carries ``state``, the saturation before that step, and ``info``."""
         pd = data[PARAMETERS][self.keyword]
-        if isinstance(flux_function, str):
-            if flux_function != "linear":
-                raise ValueError('flux_function must be "linear", a CoreyFractionalFlow or a TabulatedFractionalFlow')
-            kind, params = _lib.FLUXFN_LINEAR, ()
-        elif isinstance(flux_function, (CoreyFractionalFlow, TabulatedFractionalFlow)):
-            kind, params = flux_function.kind, flux_function.params
-        else:
-            raise ValueError('flux_function must be "linear", a CoreyFractionalFlow or a TabulatedFractionalFlow')
+        kind, params = _flux_function(flux_function)
         if accumulation is None:
             raise ValueError("accumulation is required")
         try:
@@ -306,6 +299,68 @@ class Upwind:
                 raise err from None
             raise
         return s, info
+
+    def advance_saturation_components(self, sd, data: dict, s0, c0, n_steps: int, accumulation, flux_function,
+                                      c_bc_values=None, sorption=None, source=None, sink=None, c_source=None,
+                                      rtol: float = 1e-12, maxit: int = 500, raise_on_fail: bool = True):
+        """``advance_saturation`` with k components carried by the transported phase -- salinity, a polymer, a tracer
+        that marks injected water, the water's heat content.  ``c0``: (k, Nc), the amount per unit volume of the phase.
+        With ``phi = f(s)`` of the step, component a solves
+        ``(acc s + sorption_a) c_a + (A + diag(sink)) (phi c_a) = (acc s_old + sorption_a) c_old_a - b_ref_a + c_source_a``.
+        ``c_bc_values``: None (zeros), (Nf,) or (k, Nf) -- on a Dirichlet inflow face the concentration in the entering
+        phase (the saturation there is still the keyword's ``bc_values``), on a Neumann face the component's flux.
+        ``sorption`` (>= 0, a capacity that does not scale with ``s``) and ``c_source`` (a mass rate): None, (Nc,) or
+        (k, Nc).  The sink takes the component at ``sink f(s) c``.
+
+        In flow order a component is one division per cell once the cell's saturation is known: the components ride in
+        the launches of the saturation (``stats()["sweep_launches"]`` is that of ``advance_saturation``), and ``s`` is
+        bit for bit what ``advance_saturation`` returns.  The cells of a cyclic core iterate ``s`` and ``c`` jointly.
+        Returns (s, c, info); a step is accepted only if the saturation and every component pass the residual check
+        (``info["c_rel_residual"]``), there is no per-component fallback.  Errors as ``advance_saturation``; the
+        ``ValueError`` of a refused step carries ``state = (s, c)`` before that step, and ``info``."""
+        pd = data[PARAMETERS][self.keyword]
+        kind, params = _flux_function(flux_function)
+        if accumulation is None:
+            raise ValueError("accumulation is required")
+        c0 = np.asarray(c0, dtype=np.float64)
+        nc, nf = sd.num_cells, sd.num_faces
+        if c0.ndim != 2 or c0.shape[1] != nc:
+            raise ValueError(f"c0 must have shape (k, {nc}), not {c0.shape}")
+        k = c0.shape[0]
+        if not 1 <= k <= 64:
+            raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (c0 has shape {c0.shape})")
+
+        def per_component(name, a, n):
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape == (n,):
+                return np.broadcast_to(a, (k, n))
+            if a.shape != (k, n):
+                raise ValueError(f"{name} must have shape ({n},) or ({k}, {n}), not {a.shape}")
+            return a
+
+        cbv = np.zeros((k, nf)) if c_bc_values is None else per_component("c_bc_values", c_bc_values, nf)
+        ads = None if sorption is None else per_component("sorption", sorption, nc)
+        csrc = None if c_source is None else per_component("c_source", c_source, nc)
+        try:
+            return self.context(sd).transport_advance_nl_multi(
+                s0, c0, n_steps, accumulation, np.asarray(pd["bc_values"], dtype=float), cbv, kind, params,
+                q=self._flux(sd, pd), sorption=ads, source=source, sink=sink, c_source=csrc, rtol=rtol, maxit=maxit,
+                raise_on_fail=raise_on_fail)
+        except _lib.PorefvError as e:
+            if e.status == 4:
+                err = ValueError(e.message)
+                err.state, err.info = getattr(e, "state", None), getattr(e, "info", None)
+                raise err from None
+            raise
+
+
+def _flux_function(flux_function):
+    """(kind, parameters) of the C ABI for what ``advance_saturation`` takes as ``flux_function``"""
+    if isinstance(flux_function, str) and flux_function == "linear":
+        return _lib.FLUXFN_LINEAR, ()
+    if isinstance(flux_function, (CoreyFractionalFlow, TabulatedFractionalFlow)):
+        return flux_function.kind, flux_function.params
+    raise ValueError('flux_function must be "linear", a CoreyFractionalFlow or a TabulatedFractionalFlow')
 
 
 def as_porepy_upwind(device: int = 0, library=None):

@@ -7,7 +7,7 @@ Device times are HIP-event times from pfv_stats; the host times are wall clock. 
 not a test: no thresholds.
 
     python tools/bench_transport.py [--n-side 69] [--steps 20] [--no-host] [--precond sweep] [--components 8]
-                                    [--saturation]
+                                    [--saturation [--components 4]]
 
 --precond sweep: after the Jacobi-BiCGStab steps, the same steps from the same state with the flow-ordered sweep
 (PFV_PRECOND_SWEEP) -- order-build ms, levels, core cells, launches per sweep, ms per step -- and again with one launch
@@ -22,6 +22,11 @@ transport_advance_multi from the same state on the same handle: ms per step of b
 the same number of saturation steps with a Corey curve (transport_advance_nl: exponents 2 / 2, viscosities 1 / 5,
 residual saturations 0.1 / 0.15): ms per step of both from pfv_stats (best and median of --reps, the first repeat
 dropped), levels, launches, core cells and core iterations.
+
+--saturation --components K (a list runs several K): in addition, alternating in one loop from the same state, the
+Corey step alone, the Corey step with K phase-carried components (transport_advance_nl_multi: own inflow concentrations,
+sorption on component 0) and, for orientation, the K-component linear step (transport_advance_multi with
+precond="sweep"): ms per step of the three (best and median of --reps, the first repeat dropped), levels, launches.
 """
 from __future__ import annotations
 
@@ -48,7 +53,8 @@ def main():
     ap.add_argument("--precond", choices=["jacobi", "sweep"], default="jacobi",
                     help="sweep: also time the steps with the flow-ordered sweep, next to the Jacobi-BiCGStab ones")
     ap.add_argument("--components", default="",
-                    help="K or K1,K2,...: K single sweep runs against one multi-component run (needs --precond sweep)")
+                    help="K or K1,K2,...: K single sweep runs against one multi-component run (with --precond sweep); "
+                         "the Corey step alone against the Corey step with K components (with --saturation)")
     ap.add_argument("--saturation", action="store_true",
                     help="linear sweep steps against Corey saturation steps on the same flux and state")
     ap.add_argument("--emulation", action="store_true", help="run on the host-emulation build (plumbing check)")
@@ -169,6 +175,43 @@ def main():
         sat.update({"linear_sweep_ms_per_step": (min(lin_ms[1:]), float(np.median(lin_ms[1:]))),
                     "linear_steps_done": linfo["steps_done"], "linear_direct_steps": ls["sweep_direct_steps"],
                     "linear_launches_per_sweep": ls["sweep_launches"], "linear_core_cells": ls["sweep_core_cells"]})
+        sat["components"] = []
+        for kc in [int(v) for v in a.components.split(",") if v]:
+            cbv_k = np.array([tbv * (j + 1) / kc for j in range(kc)])
+            acc_k = np.array([(1.0 + 0.5 * j) * acc for j in range(kc)])
+            ads_k = np.zeros((kc, nc))
+            ads_k[0] = 0.5 * acc
+            c0_k = rng.random((kc, nc))
+            alone_ms, with_ms, multi_ms = [], [], []
+            entry = {"k": kc}
+            try:
+                for _ in range(a.reps + 1):  # (the first repeat warms up: dropped)
+                    sa, ainfo_ = ctx.transport_advance_nl(s0, a.steps, acc, tbv, corey.kind, corey.params, rtol=1e-10,
+                                                          raise_on_fail=False)
+                    alone = ctx.stats()
+                    alone_ms.append(alone["transport_nl_ms"] / max(a.steps, 1))
+                    sc, cc, cinfo = ctx.transport_advance_nl_multi(s0, c0_k, a.steps, acc, tbv, cbv_k, corey.kind,
+                                                                   corey.params, sorption=ads_k, rtol=1e-10,
+                                                                   raise_on_fail=False)
+                    both = ctx.stats()
+                    with_ms.append(both["transport_nl_ms"] / max(a.steps, 1))
+                    cm, minfo = ctx.transport_advance_multi(c0_k, a.steps, acc_k, cbv_k, rtol=1e-10, raise_on_fail=False,
+                                                            precond="sweep")
+                    multi = ctx.stats()
+                    multi_ms.append(multi["transport_advance_ms"] / max(a.steps, 1))
+                entry.update({
+                    "steps_done": cinfo["steps_done"], "corey_alone_ms_per_step": (min(alone_ms[1:]), float(np.median(alone_ms[1:]))),
+                    "corey_with_components_ms_per_step": (min(with_ms[1:]), float(np.median(with_ms[1:]))),
+                    "linear_components_ms_per_step": (min(multi_ms[1:]), float(np.median(multi_ms[1:]))),
+                    "levels": both["sweep_levels"], "launches_per_step": both["sweep_launches"],
+                    "launches_per_step_alone": alone["sweep_launches"], "launches_per_sweep_linear": multi["sweep_launches"],
+                    "linear_direct_steps": multi["transport_multi_direct_steps"], "core_cells": both["sweep_core_cells"],
+                    "rel_residual_last_step": cinfo["rel_residual"], "max_c_rel_residual_last_step": max(cinfo["c_rel_residual"]),
+                    "saturation_bits_equal": bool(sc.tobytes() == sa.tobytes()),
+                    "c_min": float(cc.min()), "c_max": float(cc.max())})
+            except pa.PorefvError as e:
+                entry["error"] = e.message
+            sat["components"].append(entry)
         out["saturation"] = sat
         ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the saturation call leaves no system behind)
     # bytes each kernel has to move at least ("Upwind advection"): the fraction of a stream rate follows

@@ -196,6 +196,10 @@ typedef struct {
   int64_t transport_nl_steps;     /* ... accepted steps */
   int64_t transport_nl_core_iterations; /* ... nonlinear Jacobi iterations of the cyclic core, summed over the steps */
   int64_t transport_nl_components; /* ... k of pfv_transport_advance_nl_multi, 0 after pfv_transport_advance_nl */
+  double transport_react_ms;      /* last pfv_transport_advance_react, all steps (HIP events) */
+  int64_t transport_react_steps;  /* ... accepted steps */
+  int64_t transport_react_core_iterations; /* ... block Jacobi iterations of the cyclic core, summed over the steps */
+  int64_t transport_react_components; /* ... its k */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -662,6 +666,48 @@ pfv_status pfv_transport_advance_nl_multi(pfv_ctx* h, const double* q, int fluxf
                                           const double* source, const double* sink, int k, const double* c_bc_values,
                                           const double* sorption, const double* c_source, int n_steps, double rtol,
                                           int maxit, double* s, double* c, int32_t* steps_done, pfv_solve_info* last);
+
+/* n_steps implicit Euler steps of k (1 .. 8, else PFV_ERR_ARGUMENT) COUPLED components on one flux: a decay chain,
+ * reversible first-order kinetics, kinetic sorption or mobile-immobile exchange, biodegradation with a yield.  Per cell i
+ * and component a
+ *     acc_ia (c_ia - c_old_ia) + w_a [sum_j A_ij c_ja + b_ref_ia] + rho_i sum_b K_ab c_ib = src_ia
+ *     b_ref_a = div (rhs_neu + rhs_dir diag(q)) bc_values[a]                         (as pfv_transport_advance_multi)
+ * with A = div diag(q) U of the one-component discretization on the handle (pfv_upwind_discretize with
+ * num_components = 1; no pfv_upwind_assemble is needed).  rate = K (k x k, row-major, host memory) is the rate matrix of
+ * dc/dt = -K c, shared by all cells; rate_weight = rho (Nc, NULL = 1, >= 0) the weight of the reaction term per cell
+ * (pore volume x dt, a reactive zone, a temperature factor); mobility = w (k, host memory, NULL = 1, >= 0): w_a = 0 is an
+ * immobile component (a sorbed phase, matrix porosity, biomass) that sees no flux and no boundary -- its bc_values[a] are
+ * not read --, w_a = 1 what pfv_transport_advance_multi does.
+ *   Admissible K, else PFV_ERR_ARGUMENT: K_aa >= 0; K_ab <= 0 for a != b; every column sum
+ * sum_a K_ab >= -k 2^-52 sum_a |K_ab| (no mass created, up to the rounding of a sum of k terms).  With accumulation > 0
+ * every row block B_i = diag(acc_ia + w_a A_ii) + rho_i K then is a strictly column-diagonally-dominant M-matrix: it is
+ * eliminated WITHOUT pivoting, non-negative data give non-negative concentrations, and block Jacobi converges on a
+ * cyclic core.  Decay chains, A <-> B, mobile <-> immobile pairs and yields <= 1 are covered; there is no pivoted path.
+ *   In flow order a cell is one k x k solve in registers once its upstream cells are known (csrc/sweep.inc:
+ * sweep_row_react<k>), in the launches of one component: pfv_stats.sweep_launches is that of pfv_transport_advance
+ * with PFV_PRECOND_SWEEP on the same flux.  The cells of a cyclic core are iterated by block Jacobi until every component
+ * has ||F_core,a|| <= rtol ||g_a|| / 2, or maxit iterations.  A step is accepted when every component has
+ * ||F_a|| <= rtol ||g_a|| (0 <= 0 counts) with F_a the residual of its equations and the scale
+ * g_a = rhs_a - rho sum_{b != a} K_ab c_b, rhs_a = acc_a o c_old_a - w_a b_ref_a + src_a: a daughter that starts from
+ * nothing has rhs_a = 0 and lives on what its parent produces.  One host read per step brings the 2 k norms.
+ *   bc_values [k][Nf], accumulation, source (may be NULL) and c (in and out) [k][Nc] are component-major and follow
+ * pfv_set_vectors_on_device, as rate_weight and q (Nf, NULL = the flux of the discretization) do; on the device the
+ * vectors are cell-major and interleaved, v[i * k + a].  c holds the state after the last accepted step; a refused
+ * step returns the state of that step's start, steps_done and PFV_ERR_NOT_CONVERGED.  last (k entries, may be NULL):
+ * iterations = 1 for an acyclic flux, else the core iterations of the last step; rel_residual the measured
+ * ||F_a|| / ||g_a||.
+ *   PFV_ERR_ARGUMENT (the text names the first offender, the lowest cell or face and its lowest component): no
+ * discretization or num_components != 1; k outside 1 .. 8; a K that breaks the conditions above or is not finite; a
+ * negative or non-finite mobility; a negative or NaN rate_weight; accumulation <= 0 or NaN; a non-finite c; a
+ * non-finite bc_values[a] on a Dirichlet inflow or Neumann face of a component with w_a > 0; a boundary face with inflow
+ * that is neither Dirichlet nor Neumann.  PFV_ERR_UNSUPPORTED: periodic grids, conditions per sub-face, the sharded
+ * solve, (k + 1) max(Nc, Nf) >= 2^31.  The handle rules are those of pfv_transport_advance_nl: the flow order is built
+ * if the handle has none for this flux, whatever preconditioner is selected; the selection and the flow system are left
+ * alone; no transport system is left behind.  pfv_stats: transport_react_* and the sweep_* fields. */
+pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const double* bc_values,
+                                       const double* accumulation, const double* source, const double* mobility,
+                                       const double* rate, const double* rate_weight, int n_steps, double rtol,
+                                       int maxit, double* c, int32_t* steps_done, pfv_solve_info* last);
 
 /* ---- Advection-diffusion step on the device (csrc/advdiff.inc) ---------------------------------------------------
  * One handle carries the transport keyword: its diffusion discretization (pfv_mpfa_discretize or pfv_tpfa_discretize

@@ -51,6 +51,7 @@ EXPORTS = [
     "pfv_mpfa_face_flux", "pfv_upwind_set_bc", "pfv_upwind_discretize", "pfv_upwind_assemble", "pfv_transport_advance",
     "pfv_advdiff_assemble", "pfv_advdiff_advance", "pfv_advdiff_face_flux", "pfv_resident_flux",
     "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl", "pfv_transport_advance_nl_multi",
+    "pfv_transport_advance_react",
 ]
 
 
@@ -86,7 +87,9 @@ class Stats(C.Structure):
                 ("transport_multi_components", C.c_int64), ("transport_multi_direct_steps", C.c_int64),
                 ("transport_multi_fallback_components", C.c_int64),
                 ("transport_nl_ms", C.c_double), ("transport_nl_steps", C.c_int64),
-                ("transport_nl_core_iterations", C.c_int64), ("transport_nl_components", C.c_int64)]
+                ("transport_nl_core_iterations", C.c_int64), ("transport_nl_components", C.c_int64),
+                ("transport_react_ms", C.c_double), ("transport_react_steps", C.c_int64),
+                ("transport_react_core_iterations", C.c_int64), ("transport_react_components", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -311,6 +314,9 @@ def _bind(lib: C.CDLL) -> C.CDLL:
                                                    _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, C.POINTER(C.c_int32),
                                                    C.POINTER(SolveInfo)]
     lib.pfv_transport_advance_nl_multi.restype = C.c_int
+    lib.pfv_transport_advance_react.argtypes = [_h, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double,
+                                                C.c_int, _dp, C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
+    lib.pfv_transport_advance_react.restype = C.c_int
     lib.pfv_advdiff_assemble.argtypes = [_h, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pfv_advdiff_assemble.restype = C.c_int
     lib.pfv_advdiff_advance.argtypes = [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(C.c_int32),
@@ -1511,6 +1517,57 @@ class Context:
                 e.state, e.info = (s, c), out
                 raise
         return s, c, out
+
+    def transport_advance_react(self, c0, n_steps: int, accumulation, bc_values, rate, rate_weight=None, mobility=None,
+                                q=None, source=None, rtol=1e-12, maxit=500, raise_on_fail=True):
+        """``n_steps`` implicit Euler steps of k coupled components on the flux of the one-component upwind
+        discretization on this handle (pfv_transport_advance_react): in flow order every cell is one k x k solve.
+        ``c0``, ``accumulation`` and ``source`` (may be None): k x Nc; ``bc_values``: k x Nf; ``rate``: the k x k rate
+        matrix K of dc/dt = -K c (K_aa >= 0, K_ab <= 0, no negative column sum); ``rate_weight``: Nc or None (1);
+        ``mobility``: k values >= 0 or None (1), 0 = an immobile component.  Returns (c, info) with ``steps_done``,
+        ``converged`` and the per-component lists ``iterations`` and ``rel_residual``.  An error raised for a refused
+        step carries ``state`` (c before that step) and ``info``."""
+        c = np.array(c0, dtype=np.float64, copy=True, order="C")
+        if c.ndim != 2 or c.shape[1] != self.nc:
+            raise ValueError(f"c0 must have shape (k, {self.nc}), not {c.shape}")
+        k = c.shape[0]
+        if not 1 <= k <= 8:
+            raise ValueError(f"the number of coupled components must lie in 1 .. 8, not {k} (c0 has shape {c.shape})")
+        arrays = []
+        for name, a, n, needed in (("accumulation", accumulation, self.nc, True), ("bc_values", bc_values, self.nf, True),
+                                   ("source", source, self.nc, False)):
+            if a is None:
+                if needed:
+                    raise ValueError(f"{name} is required")
+                arrays.append(None)
+                continue
+            a = _f64(a)
+            if a.shape != (k, n):
+                raise ValueError(f"{name} must have shape ({k}, {n}), not {a.shape}")
+            arrays.append(a)
+        acc, bv, src = arrays
+        K = _f64(rate)
+        if K.shape != (k, k):
+            raise ValueError(f"rate_matrix must have shape ({k}, {k}), not {K.shape}")
+        w = None if mobility is None else _f64(mobility)
+        if w is not None and w.shape != (k,):
+            raise ValueError(f"mobility must have shape ({k},), not {w.shape}")
+        kq, pq = self._vec(q, self.nf, "the flux array", False)
+        kr, pr = self._vec(rate_weight, self.nc, "rate_weight", False)
+        done, infos = C.c_int32(0), (SolveInfo * k)()
+        st = self.lib.pfv_transport_advance_react(self._h, pq, k, _ptr(bv, _dp), _ptr(acc, _dp), _ptr(src, _dp),
+                                                  _ptr(w, _dp), _ptr(K, _dp), pr, int(n_steps), float(rtol), int(maxit),
+                                                  _ptr(c, _dp), C.byref(done), infos)
+        out = {"steps_done": done.value, "converged": all(bool(i.converged) for i in infos),
+               "iterations": [i.iterations for i in infos], "rel_residual": [i.rel_residual for i in infos],
+               "solve_ms": [i.solve_ms for i in infos]}
+        if st != 0 and (raise_on_fail or st != 6):
+            try:
+                self._check(st)
+            except PorefvError as e:  # (the state before the refused step and what was done until then)
+                e.state, e.info = c, out
+                raise
+        return c, out
 
     # ---- advection-diffusion on one handle (include/porefv.h: pfv_advdiff_*) ----
     def resident_flux_ptr(self) -> int:

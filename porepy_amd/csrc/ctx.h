@@ -343,6 +343,12 @@ struct pfv_ctx_impl {
   // ... and the vectors of the step, cell-major interleaved v[i * k + a]: sorption, source, b_ref, the two states,
   // psi = phi o c and its copy for the core, rhs, the image, the core rows' compacted (rhs, image)
   Buf<double> nlc_ads, nlc_src, nlc_bref, nlc_x, nlc_z, nlc_psi, nlc_psi2, nlc_rhs, nlc_t, nlc_cb, nlc_ct;
+  // k coupled components (pfv_transport_advance_react): the caller's arrays as they came, component-major [k][n] ...
+  Buf<double> rc_q, rc_bc, rc_acc_in, rc_src_in, rc_c_in, rc_rho;
+  // ... the vectors of the step, cell-major interleaved v[i * k + a]: accumulation, source, w o b_ref, the two states,
+  // the copy of the state for the core, rhs, the scale g and F = rhs - image; rc_par: ReactPar (w, K) for the kernels
+  // that index it at run time; rc_out: 2 k norms, then the status word
+  Buf<double> rc_acc, rc_src, rc_bref, rc_x, rc_z, rc_prev, rc_rhs, rc_g, rc_F, rc_par, rc_out;
 
   // ---- advection-diffusion (advdiff.inc): S = diag(acc) + div flux_D + w div diag(q) U on pat_A -------------------
   bool have_advdiff = false;         // val[PFV_MAT_ADVDIFF_SYSTEM], adv_diag, adv_rhs hold a system of the discretization

@@ -8,6 +8,7 @@
 
 #include "ctx.h"
 #include "fluxfn.h"
+#include "react.h"
 namespace pfv {
 static int rccl_exchange_halo(void* user, double* d_x, void* stream);  // rccl_hooks.inc
 }
@@ -1619,6 +1620,209 @@ pfv_status pfv_transport_advance_nl_multi(pfv_ctx* h, const double* q, int fluxf
   }
   return advance_nl(h, q, fluxfn_kind, fluxfn_params, n_params, bc_values, accumulation, source, sink, k, c_bc_values,
                     sorption, c_source, n_steps, rtol, maxit, s, c, steps_done, last);
+}
+
+// ---- k coupled components: one k x k solve per cell in flow order (sweep.inc: sweep_row_react) -------------------------
+// Per step: rhs, the forward levels, the core level iterated by block Jacobi (a host read every kNlCoreCheck-th
+// iteration), the backward levels, then g and F = rhs - image over all rows and ONE host read of their 2k norms and the
+// status word.  The state of the step's start stays in its own buffer until the step is accepted.
+pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const double* bc_values,
+                                       const double* accumulation, const double* source, const double* mobility,
+                                       const double* rate, const double* rate_weight, int n_steps, double rtol,
+                                       int maxit, double* c, int32_t* steps_done, pfv_solve_info* last) {
+  if (steps_done) *steps_done = 0;
+  std::unique_ptr<pfv::Timer> tm;
+  bool touched = false;
+  double order_ms = 0.0;
+  const double* d_q = nullptr;
+  size_t nc = 0, nf = 0;
+  pfv::ReactPar par;
+  pfv_status st = guarded(h, [&] {
+    upwind_supported(h);
+    if (h->subface_bc) throw Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
+    require(h->have_upwind, "pfv_upwind_discretize first");
+    require(h->upw_ncomp == 1, "the components share one discretization: pfv_upwind_discretize with num_components = 1");
+    const std::string bad = pfv::react_check(k, rate, mobility);
+    if (!bad.empty()) throw Error(PFV_ERR_ARGUMENT, bad);
+    require(bc_values && accumulation && c, "bc_values, accumulation and c are required");
+    require(n_steps >= 0, "bad argument");
+    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
+    nc = (size_t)h->nc;
+    nf = (size_t)h->nf;
+    if ((int64_t)(k + 1) * (int64_t)std::max(nc, nf) >= (int64_t(1) << 31))
+      throw Error(PFV_ERR_UNSUPPORTED, "(k + 1) x cells (faces) beyond int32 indices");
+    par = pfv::react_make(k, rate, mobility);
+    be_h2d(h->rc_par.ensure(sizeof(par) / sizeof(double)), &par, sizeof(par), h->stream);
+    if (q) vec_in(h, h->rc_q.ensure(nf), q, nf);
+    vec_in(h, h->rc_bc.ensure(k * nf), bc_values, k * nf);  // component-major, as they came
+    vec_in(h, h->rc_acc_in.ensure(k * nc), accumulation, k * nc);
+    if (source) vec_in(h, h->rc_src_in.ensure(k * nc), source, k * nc);
+    if (rate_weight) vec_in(h, h->rc_rho.ensure(nc), rate_weight, nc);
+    vec_in(h, h->rc_c_in.ensure(k * nc), c, k * nc);
+    d_q = q ? h->rc_q.p : h->upw_q.p;
+    pfv::upwind_face_cells(*h);
+    int32_t off[pfv::kReactChecks];
+    pfv::sweep_react_check_inputs(*h, d_q, k, h->rc_bc.p, h->rc_acc_in.p, rate_weight ? h->rc_rho.p : nullptr,
+                                  h->rc_c_in.p, h->rc_par.p, off);
+    auto comp = [&](int32_t v) { return std::to_string(v / k) + ", component " + std::to_string(v % k); };
+    if (off[0] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, "accumulation must be positive: cell " + comp(off[0]));
+    if (off[1] != 0x7f7f7f7f)
+      throw Error(PFV_ERR_ARGUMENT, "rate_weight must not be negative: cell " + std::to_string(off[1]));
+    if (off[2] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, "c is not finite in cell " + comp(off[2]));
+    if (off[3] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, "bc_values is not finite on face " + comp(off[3]));
+    if (off[4] != 0x7f7f7f7f)
+      throw Error(PFV_ERR_ARGUMENT, "negative axis 1 index: -1 (neither Dirichlet nor Neumann, with inflow: no upstream "
+                                    "cell) face " + std::to_string(off[4]));
+    tm = std::make_unique<pfv::Timer>();
+    tm->start(h->stream);
+    // A = div diag(q) U without accumulation (its diagonal: the outflow of the cell), once per call.  (The boundary
+    // term that upwind_assemble forms beside it is not used: b_ref of every component comes from upwind_bref_react.)
+    upwind_drop_transport(h, true);
+    touched = true;
+    pfv::upwind_assemble(*h, d_q, h->rc_bc.p, nullptr, nullptr, nullptr);
+    values_changed(h, Windows::drop);
+    pfv::multi_interleave(*h, (int64_t)nc, k, h->rc_acc_in.p, h->rc_acc.ensure(k * nc));
+    if (source) pfv::multi_interleave(*h, (int64_t)nc, k, h->rc_src_in.p, h->rc_src.ensure(k * nc));
+    pfv::multi_interleave(*h, (int64_t)nc, k, h->rc_c_in.p, h->rc_x.ensure(k * nc));
+    pfv::upwind_bref_react(*h, k, d_q, h->rc_bc.p, h->rc_par.p, h->rc_bref.ensure(k * nc));
+    for (pfv::Buf<double>* b : {&h->rc_z, &h->rc_prev, &h->rc_rhs, &h->rc_g, &h->rc_F}) b->ensure(k * nc);
+    h->rc_out.ensure(2 * (size_t)k + 1);
+    // the order of the flux, built on first use and kept while assemblies bring the same edges (sweep_note_assembly)
+    if (!h->sweep) h->sweep = std::make_unique<pfv::Sweep>();
+    pfv::Sweep& sw = *h->sweep;
+    if (sw.valid && (sw.for_system != PFV_MAT_TRANSPORT_SYSTEM || !pfv::sweep_same_edges(*h, sw, d_q))) sw.valid = false;
+    if (!sw.valid) {
+      pfv::sweep_build_order(*h, sw, d_q, PFV_MAT_TRANSPORT_SYSTEM);
+      order_ms += sw.order_ms;
+    }
+    pfv::sweep_set_numbering(*h, sw, false);
+    pfv::sweep_make_plan(sw);
+  });
+  if (st != PFV_OK) {
+    if (touched) upwind_drop_transport(h, true);  // (A without accumulation: not a system to be solved with)
+    return st;
+  }
+
+  int32_t completed = 0;
+  int64_t core_total = 0, launches = 0;
+  std::vector<pfv_solve_info> info((size_t)k);
+  std::vector<double> hst(2 * (size_t)k + 1);
+  std::string err;
+  for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
+    pfv_status verdict = PFV_OK;
+    st = guarded(h, [&] {
+      pfv::pfv_ctx_impl& cx = *h;
+      const pfv::Sweep& sw = *cx.sweep;
+      const double* val = cx.val[PFV_MAT_TRANSPORT_SYSTEM].p;
+      const double* rho = rate_weight ? cx.rc_rho.p : nullptr;
+      double* out = cx.rc_out.p;
+      int32_t* status = reinterpret_cast<int32_t*>(out + 2 * k);
+      const bool has_core = sw.n_core > 0;
+      const int core = has_core ? sw.core_level : sw.nlev;
+      pfv::ReactRow A{cx.pat_T.indptr, cx.pat_T.indices, sw.lev(false), val, cx.diag_t.p, cx.rc_acc.p, rho,
+                      cx.rc_rhs.p, nullptr, cx.rc_z.p, status};
+      pfv::ReactRow Ac = A;  // the core level, with the state of the previous iterate
+      Ac.c_prev = cx.rc_prev.p;
+      const size_t hst_bytes = sizeof(double) * hst.size();
+      auto component_info = [&](int it) {  // from hst: (g_a, g_a), (F_a, F_a)
+        for (int a = 0; a < k; ++a) {
+          const double gg = hst[(size_t)a], ff = hst[(size_t)k + a];
+          info[(size_t)a] = pfv_solve_info{};
+          info[(size_t)a].iterations = it;
+          info[(size_t)a].rel_residual = gg > 0.0 ? std::sqrt(ff / gg) : 0.0;
+        }
+      };
+      pfv::upwind_step_rhs_multi(cx, k, cx.rc_acc.p, source ? cx.rc_src.p : nullptr, cx.rc_bref.p, cx.rc_x.p, cx.rc_rhs.p);
+      pfv::be_memset(status, 0x7f, sizeof(double), cx.stream);
+      launches = pfv::sweep_apply_react(cx, sw, 0, core, k, A, par);
+      int core_it = 0;
+      if (has_core) {
+        bool settled = false;
+        pfv::sweep_nlc_core_keep(cx, sw, k, cx.rc_x.p, cx.rc_z.p);  // the core rows start from the state of the step's start
+        while (core_it < maxit && !settled) {
+          pfv::sweep_nlc_core_keep(cx, sw, k, cx.rc_z.p, cx.rc_prev.p);
+          pfv::sweep_levels_react(cx, sw, core, core + 1, k, Ac, par);
+          ++core_it;
+          if (core_it % pfv::kNlCoreCheck != 0 && core_it != maxit) continue;
+          pfv::sweep_react_image(cx, cx.pat_T, val, k, cx.rc_acc.p, rho, cx.rc_rhs.p, cx.rc_par.p, cx.rc_z.p, A.lev, core,
+                                 cx.rc_g.p, cx.rc_F.p);
+          pfv::sweep_react_norms(cx, cx.nc, k, cx.rc_g.p, cx.rc_F.p, out);
+          be_d2h(hst.data(), out, hst_bytes, cx.stream);
+          settled = true;
+          for (int a = 0; a < k; ++a) settled = settled && hst[(size_t)k + a] <= 0.25 * rtol * rtol * hst[(size_t)a];
+        }
+        core_total += core_it;
+        launches += 2;
+        if (!settled) {  // (what the backward levels would compute from this core is not judged)
+          component_info(core_it);
+          verdict = PFV_ERR_NOT_CONVERGED;
+          cx.err = "step " + std::to_string(step) + ": the cyclic core of " + std::to_string(sw.n_core) +
+                   " cells did not settle in " + std::to_string(core_it) + " iterations";
+          return;
+        }
+        launches += pfv::sweep_apply_react(cx, sw, core + 1, sw.nlev, k, A, par);
+      }
+      pfv::sweep_react_image(cx, cx.pat_T, val, k, cx.rc_acc.p, rho, cx.rc_rhs.p, cx.rc_par.p, cx.rc_z.p, A.lev, -1,
+                             cx.rc_g.p, cx.rc_F.p);
+      pfv::sweep_react_norms(cx, cx.nc, k, cx.rc_g.p, cx.rc_F.p, out);
+      be_d2h(hst.data(), out, hst_bytes, cx.stream);
+      component_info(has_core ? core_it : 1);
+      int32_t cell;
+      std::memcpy(&cell, hst.data() + 2 * k, sizeof(cell));
+      if (cell != 0x7f7f7f7f) {
+        verdict = PFV_ERR_NOT_CONVERGED;
+        cx.err = "step " + std::to_string(step) + ": the block of cell " + std::to_string(cell) +
+                 " has a pivot that is not positive and finite";
+        return;
+      }
+      int bad = -1;  // the first component whose check fails
+      for (int a = k - 1; a >= 0; --a) {
+        info[(size_t)a].converged = hst[(size_t)k + a] <= rtol * rtol * hst[(size_t)a] ? 1 : 0;  // (0 <= 0 counts)
+        if (!info[(size_t)a].converged) bad = a;
+      }
+      if (bad >= 0) {
+        verdict = PFV_ERR_NOT_CONVERGED;
+        cx.err = "step " + std::to_string(step) + ": relative residual " + std::to_string(info[(size_t)bad].rel_residual) +
+                 " of component " + std::to_string(bad) + " after the sweep (a flux that contradicts the discretization's?)";
+        return;
+      }
+      std::swap(cx.rc_x.p, cx.rc_z.p);
+      std::swap(cx.rc_x.cap, cx.rc_z.cap);
+      ++completed;
+    });
+    if (st == PFV_OK) st = verdict;
+  }
+  if (st != PFV_OK) err = h->err;
+  double ms = 0.0;
+  const pfv_status st2 = guarded(h, [&] {
+    ms = tm->stop(h->stream);
+    tm.reset();
+    pfv::multi_deinterleave(*h, (int64_t)nc, k, h->rc_x.p, h->rc_c_in.p);
+    vec_out(h, c, h->rc_c_in.p, k * nc);
+    pfv::be_sync(h->stream);
+    upwind_drop_transport(h, true);
+  });
+  if (steps_done) *steps_done = completed;
+  if (last)
+    for (int a = 0; a < k; ++a) {
+      last[a] = info[(size_t)a];
+      if (completed > 0) last[a].solve_ms = ms / completed;
+    }
+  h->stats.transport_react_ms = ms;
+  h->stats.transport_react_steps = completed;
+  h->stats.transport_react_core_iterations = core_total;
+  h->stats.transport_react_components = k;
+  if (h->sweep && h->sweep->valid) {
+    h->stats.sweep_levels = h->sweep->nlev;
+    h->stats.sweep_core_cells = h->sweep->n_core;
+    h->stats.sweep_launches = n_steps > 0 ? launches : (int64_t)h->sweep->plan.size();
+    h->stats.sweep_order_ms = order_ms;
+  }
+  if (st != PFV_OK) {
+    h->err = err;
+    return st;
+  }
+  return st2;
 }
 
 // ---- advection-diffusion on one handle (advdiff.inc) -----------------------------------------------------------

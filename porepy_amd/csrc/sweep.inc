@@ -954,6 +954,322 @@ static void sweep_nl_check_inputs(pfv_ctx_impl& c, const double* d_q, const doub
   be_d2h(out, st, sizeof(int32_t) * kNlChecks, st_);
 }
 
+// ---- k coupled components (pfv_transport_advance_react): per cell and component
+//     acc_ia (c_ia - c_old_ia) + w_a (sum_j A_ij c_ja + b_ref_ia) + rho_i sum_b K_ab c_ib = src_ia
+// with the rate matrix K of dc/dt = -K c, the mobilities w >= 0 (react.h) and the weight rho >= 0 of the reaction term.
+// Once the upstream cells of a row are known its k unknowns are one k x k system
+//     B_i c_i = R_i,   B_i = diag(acc_ia + w_a A_ii) + rho_i K,   R_ia = rhs_ia - w_a sum_{lev[j] < lev[i]} A_ij c_ja
+// with rhs_a = acc_a o c_old_a - w_a b_ref_a + src_a.  B_i is a strictly column-diagonally-dominant M-matrix (react.h):
+// it is eliminated without pivoting.  One thread per row; k is a template parameter, so that B, R and the sums are
+// registers under compile-time indices and every loop over them is unrolled (a per-thread array under a run-time
+// index goes to scratch memory).  The sums run in stored order and the entries are taken kNlcGroup at a time, by the
+// rules of sweep_row_nlc: a slot past the row's end repeats the last entry, a slot that is not upstream reads the
+// row's own rhs and enters as + 0.  With K = 0 and w = 1 the row is (rhs - sum) / (A_ii + acc), the bits of
+// sweep_row_multi: w_a sum, + rho 0 and the elimination of a diagonal block are exact.
+//   core   rows of the core level (c_prev != nullptr) take their in-core neighbours from c_prev, the previous
+//          iterate: block Jacobi, independent of the scheduling.
+//   status the lowest row with a pivot that is not positive and finite (it cannot happen with finite admissible data)
+struct ReactRow {
+  const int32_t *ip, *ix, *lev;
+  const double *val, *diag, *acc, *rho, *rhs;  // rho may be nullptr (1)
+  const double* c_prev;
+  double* c;
+  int32_t* status;
+};
+
+template <int K>
+PFV_FN void sweep_row_react(int32_t i, const ReactRow& A, const ReactPar& P) {
+  const int32_t li = A.lev[i];
+  const int64_t p = (int64_t)i * K;
+  const int e_end = A.ip[i + 1];
+  const double* own = A.rhs + p;
+  double u[K];
+#pragma unroll
+  for (int a = 0; a < K; ++a) u[a] = 0.0;
+  for (int e0 = A.ip[i]; e0 < e_end; e0 += kNlcGroup) {
+    int32_t j[kNlcGroup];
+    double v[kNlcGroup];
+    const double* up[kNlcGroup];
+#pragma unroll
+    for (int t = 0; t < kNlcGroup; ++t) {
+      const int e = e0 + t < e_end ? e0 + t : e_end - 1;
+      j[t] = A.ix[e];
+      v[t] = A.val[e];
+    }
+#pragma unroll
+    for (int t = 0; t < kNlcGroup; ++t) {
+      const int32_t lj = A.lev[j[t]];
+      const double* src = lj < li ? A.c : (A.c_prev && lj == li && j[t] != i ? A.c_prev : nullptr);
+      up[t] = src && e0 + t < e_end ? src + (int64_t)j[t] * K : nullptr;
+    }
+#pragma unroll
+    for (int t = 0; t < kNlcGroup; ++t) {
+      const double* r = up[t] ? up[t] : own;
+      const double vt = up[t] ? v[t] : 0.0;
+      double x[K];
+#pragma unroll
+      for (int a = 0; a < K; ++a) x[a] = r[a];
+#pragma unroll
+      for (int a = 0; a < K; ++a) u[a] += vt * (up[t] ? x[a] : 0.0);
+    }
+  }
+  const double rw = A.rho ? A.rho[i] : 1.0, d = A.diag[i];
+  double B[K][K], R[K];
+#pragma unroll
+  for (int a = 0; a < K; ++a) {
+    R[a] = A.rhs[p + a] - P.w[a] * u[a];
+#pragma unroll
+    for (int b = 0; b < K; ++b) B[a][b] = rw * P.K[a * K + b];
+    B[a][a] += A.acc[p + a] + P.w[a] * d;
+  }
+  // elimination without pivoting: the factors by one reciprocal per pivot, the solution by a true division
+  bool bad = false;
+#pragma unroll
+  for (int a = 0; a < K; ++a) {
+    const double piv = B[a][a];
+    bad = bad || !(piv > 0.0 && piv <= 1.79769313486231570e308);
+    if (a + 1 < K) {
+      const double inv = 1.0 / piv;
+#pragma unroll
+      for (int b = a + 1; b < K; ++b) {
+        const double f = B[b][a] * inv;
+#pragma unroll
+        for (int m = a + 1; m < K; ++m) B[b][m] -= f * B[a][m];
+        R[b] -= f * R[a];
+      }
+    }
+  }
+  double x[K];
+#pragma unroll
+  for (int a = K - 1; a >= 0; --a) {
+    double s = R[a];
+#pragma unroll
+    for (int b = a + 1; b < K; ++b) s -= B[a][b] * x[b];
+    x[a] = s / B[a][a];
+  }
+#pragma unroll
+  for (int a = 0; a < K; ++a) A.c[p + a] = x[a];
+  if (bad) atomic_min_i32(A.status, i);
+}
+
+// levels [l0, l1) of the order, by the rule of the launch plan: one level is one launch, a run is one workgroup; both
+// forms inline sweep_row_react<K>
+template <int K>
+static void sweep_levels_react_k(pfv_ctx_impl& c, const Sweep& sw, int l0, int l1, const ReactRow& A_,
+                                 const ReactPar& P_) {
+  stream_t st = c.stream;
+  const ReactRow A = A_;
+  const ReactPar P = P_;
+  const int32_t* ord = sw.ord(false);
+  const int32_t* lp = sw.lptr;
+  if (l1 - l0 == 1) {
+    const int32_t a0 = sw.h_lptr[(size_t)l0], m = sw.h_lptr[(size_t)l1] - a0;
+    parallel_for(st, m, PFV_LAMBDA(int64_t t) { sweep_row_react<K>(ord[a0 + t], A, P); });
+  } else if (l1 > l0) {
+    block_for<256>(st, 1, 0, PFV_LAMBDA(const WaveCtx& w) {
+      for (int l = l0; l < l1; ++l) {
+        const int32_t a0 = lp[l], m = lp[l + 1] - a0;
+        PFV_LANES(t, m) sweep_row_react<K>(ord[a0 + t], A, P);
+        w.sync();  // (the next level reads what this one wrote: same workgroup, same CU)
+      }
+    });
+  }
+}
+
+static void sweep_levels_react(pfv_ctx_impl& c, const Sweep& sw, int l0, int l1, int k, const ReactRow& A,
+                               const ReactPar& P) {
+  switch (k) {
+    case 1: sweep_levels_react_k<1>(c, sw, l0, l1, A, P); break;
+    case 2: sweep_levels_react_k<2>(c, sw, l0, l1, A, P); break;
+    case 3: sweep_levels_react_k<3>(c, sw, l0, l1, A, P); break;
+    case 4: sweep_levels_react_k<4>(c, sw, l0, l1, A, P); break;
+    case 5: sweep_levels_react_k<5>(c, sw, l0, l1, A, P); break;
+    case 6: sweep_levels_react_k<6>(c, sw, l0, l1, A, P); break;
+    case 7: sweep_levels_react_k<7>(c, sw, l0, l1, A, P); break;
+    case 8: sweep_levels_react_k<8>(c, sw, l0, l1, A, P); break;
+    default: throw Error(PFV_ERR_ARGUMENT, "k must lie in 1 .. 8");
+  }
+}
+
+// The segments of the launch plan with levels in [from, to), as sweep_apply_nl cuts them.  Returns the launches.
+static int sweep_apply_react(pfv_ctx_impl& c, const Sweep& sw, int from, int to, int k, const ReactRow& A,
+                             const ReactPar& P) {
+  int launches = 0;
+  for (const Sweep::Seg& g : sw.plan) {
+    const int l0 = std::max(g.l0, from), l1 = std::min(g.l1, to);
+    if (l0 >= l1) continue;
+    sweep_levels_react(c, sw, l0, l1, k, A, P);
+    ++launches;
+  }
+  return launches;
+}
+
+// After the sweep, per (row, a) in stored order: the image t_a = acc_a c_a + w_a (A c_a) + rho (K c)_a, of which
+// F[i, a] = rhs_a - t_a is kept, and the scale g[i, a] = rhs_a - rho sum_{b != a} K_ab c_b: what component a is solved
+// against once its partners are known (a daughter that starts from nothing has rhs_a = 0 and lives on the second term).
+// par: ReactPar on the device (w, then K), read under run-time indices.  upto >= 0 (the core's stop test, before the
+// levels behind the core have a c): rows behind level upto give g = F = 0, rows before it F = 0, and a row's entries
+// beyond its own level (the stored zeros of the downstream side) are skipped.
+static void sweep_react_image(pfv_ctx_impl& c, const CsrPattern& P, const double* val, int k, const double* acc,
+                              const double* rho, const double* rhs, const double* par, const double* x,
+                              const int32_t* lev, int upto, double* g, double* F) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const double* w = par;
+  const double* Km = par + kReactMax;
+  parallel_for(c.stream, P.nrows * k, PFV_LAMBDA(int64_t t) {
+    const int32_t i = (int32_t)(t / k);
+    const int a = (int)(t % k);
+    const int32_t li = lev[i];
+    if (upto >= 0 && li > upto) {
+      g[t] = 0.0;
+      F[t] = 0.0;
+      return;
+    }
+    double s = 0.0;
+    for (int e = ip[i]; e < ip[i + 1]; ++e) {
+      const int32_t j = ix[e];
+      if (upto < 0 || lev[j] <= li) s += val[e] * x[(int64_t)j * k + a];
+    }
+    const int64_t p = (int64_t)i * k;
+    double kc = 0.0, off = 0.0;
+    for (int b = 0; b < k; ++b) {
+      const double m = Km[a * k + b] * x[p + b];
+      kc += m;
+      if (b != a) off += m;
+    }
+    const double rw = rho ? rho[i] : 1.0, r = rhs[t];
+    g[t] = r - rw * off;
+    F[t] = upto >= 0 && li < upto ? 0.0 : r - (acc[t] * x[t] + w[a] * s + rw * kc);
+  });
+}
+
+// out[a] = (g_a, g_a), out[k + a] = (F_a, F_a) of interleaved vectors of n rows, with the partition and the reduction
+// order of sweep_norms_interleaved
+static void sweep_react_norms(pfv_ctx_impl& c, int64_t n, int k, const double* g, const double* F, double* out) {
+  stream_t s = c.stream;
+  const int nb = (int)std::min<int64_t>(kGmresBlocks, (n * k + 2047) / 2048);
+  const int G = 256 / k, slots = G * k;
+  int fold = 1;
+  while (fold < G) fold <<= 1;
+  double* partial = c.red.ensure(2 * (size_t)k * kGmresBlocks + 64);
+  block_for<256>(s, nb, 2 * 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& w) {
+    double* sh = reinterpret_cast<double*>(w.lds);
+    const int64_t blk = w.item;
+    const int64_t lo = n * blk / nb, hi = n * (blk + 1) / nb;
+    PFV_LANES(slot, slots) {
+      const int a = slot % k, q = slot / k;
+      double a0 = 0.0, a1 = 0.0;
+      for (int64_t i = lo + q; i < hi; i += G) {
+        const double gi = g[i * k + a], fi = F[i * k + a];
+        a0 += gi * gi;
+        a1 += fi * fi;
+      }
+      sh[slot] = a0;
+      sh[256 + slot] = a1;
+    }
+    w.sync();
+    for (int o = fold >> 1; o > 0; o >>= 1) {
+      PFV_LANES(slot, slots) {
+        if (slot / k < o && slot / k + o < G) {
+          sh[slot] += sh[slot + o * k];
+          sh[256 + slot] += sh[256 + slot + o * k];
+        }
+      }
+      w.sync();
+    }
+    PFV_LANES(a, k) {
+      partial[(int64_t)a * nb + blk] = sh[a];
+      partial[(int64_t)(k + a) * nb + blk] = sh[256 + a];
+    }
+    w.sync();
+  });
+  block_for<256>(s, 2 * k, 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& wc) {
+    double* sh = reinterpret_cast<double*>(wc.lds);
+    const int64_t m = wc.item;
+    double a = 0.0;
+    for (int i = wc.lane; i < nb; i += wc.width) a += partial[m * nb + i];
+    sh[wc.lane] = a;
+    wc.sync();
+    for (int o = wc.width >> 1; o > 0; o >>= 1) {
+      if (wc.lane < o) sh[wc.lane] += sh[wc.lane + o];
+      wc.sync();
+    }
+    if (wc.lane0()) out[m] = sh[0];
+    wc.sync();
+  });
+}
+
+// What the call refuses in its arrays, each with the lowest index (component-major arrays as the caller passed them;
+// an offender with a component is reported as index * k + component, so the lowest cell or face comes first):
+// st[0] accumulation <= 0 or NaN, st[1] a negative or NaN rate_weight, st[2] a non-finite c, st[3] a non-finite
+// bc_values on a Dirichlet inflow or Neumann face of a component with w_a > 0, st[4] a boundary face with inflow under
+// q that is neither Dirichlet nor Neumann.  (0x7f7f7f7f: none.)  par: ReactPar on the device.
+constexpr int kReactChecks = 5;
+static void sweep_react_check_inputs(pfv_ctx_impl& c, const double* d_q, int k, const double* bc, const double* acc,
+                                     const double* rho, const double* cc, const double* par,
+                                     int32_t out[kReactChecks]) {
+  stream_t st_ = c.stream;
+  const int64_t nc = c.nc, nf = c.nf;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* side = c.upw_side;
+  const int32_t* cnt = c.upw_cnt;
+  const uint8_t* flag = c.have_upw_bc ? c.upw_bc.p : nullptr;
+  int32_t* st = c.status.ensure(16);
+  be_memset(st, 0x7f, sizeof(int32_t) * kReactChecks, st_);
+  parallel_for(st_, std::max(nc, nf), PFV_LAMBDA(int64_t t) {
+    const double big = 1.79769313486231570e308;
+    if (t < nc) {
+      if (rho && !(rho[t] >= 0.0)) atomic_min_i32(st + 1, (int32_t)t);
+      for (int a = 0; a < k; ++a) {
+        if (!(acc[a * nc + t] > 0.0)) atomic_min_i32(st, (int32_t)(t * k + a));
+        if (!(fabs(cc[a * nc + t]) <= big)) atomic_min_i32(st + 2, (int32_t)(t * k + a));
+      }
+    }
+    if (t < nf) {
+      if (cls[t] & (UPW_NEU | UPW_DIRIN))
+        for (int a = 0; a < k; ++a)
+          if (par[a] > 0.0 && !(fabs(bc[a * nf + t]) <= big)) atomic_min_i32(st + 3, (int32_t)(t * k + a));
+      if (cnt[t] + cnt[nf + t] == 1 && flag && !(flag[t] & (PFV_BC_DIR | PFV_BC_NEU))) {
+        const int32_t u = d_q[t] >= 0.0 ? side[t] : side[nf + t];
+        if (u < 0) atomic_min_i32(st + 4, (int32_t)t);
+      }
+    }
+  });
+  be_d2h(out, st, sizeof(int32_t) * kReactChecks, st_);
+}
+
+// b_ref of every component, times its mobility: w_a div (rhs_neu + rhs_dir diag(q)) bc[a] by the rule and in the order
+// of upwind_bref_multi (w_a = 1: its bits).  An immobile component (w_a = 0) gets 0 and its bc values are not read.
+static void upwind_bref_react(pfv_ctx_impl& c, int k, const double* d_q, const double* bc, const double* par,
+                              double* bref) {
+  const int64_t nc = c.nc, nf = c.nf;
+  const int32_t* cf_ptr = c.cf_ptr;
+  const int32_t* cf_idx = c.cf_idx;
+  const int8_t* cf_sgn = c.cf_sgn;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* cnt = c.upw_cnt;
+  parallel_for(c.stream, nc * k, PFV_LAMBDA(int64_t t) {
+    const int64_t cell = t / k, a = t % k;
+    const double wa = par[a];
+    double b = 0.0;
+    if (wa > 0.0) {
+      for (int e = cf_ptr[cell]; e < cf_ptr[cell + 1]; ++e) {
+        const int f = cf_idx[e];
+        const unsigned cl = cls[f];
+        if (cl & (UPW_NEU | UPW_DIRIN)) {
+          double m = 0.0;
+          if (cl & UPW_NEU) m = (double)(cnt[f] - cnt[nf + f]);
+          if (cl & UPW_DIRIN) m += 1.0 * d_q[f];
+          b += (double)cf_sgn[e] * (m * bc[a * nf + f]);
+        }
+      }
+      b = wa * b;
+    }
+    bref[t] = b;
+  });
+}
+
 // The direct solve of the transport system of an acyclic flux: x = M^-1 b with M = S, then the true residual.  Should
 // the check fail (a flux array in the assembly that disagrees with the discretization's, NaN entries), GMRES
 // preconditioned by the sweep goes on from that x.

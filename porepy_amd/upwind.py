@@ -353,6 +353,60 @@ class Upwind:
                 raise err from None
             raise
 
+    def advance_reactive_components(self, sd, data: dict, c0, n_steps: int, accumulation, rate_matrix, rate_weight=None,
+                                    mobility=None, bc_values=None, source=None, rtol: float = 1e-12, maxit: int = 500,
+                                    raise_on_fail: bool = True):
+        """``n_steps`` implicit Euler steps of k (1 .. 8) COUPLED components on the one flux of the (one-component)
+        discretization -- a radionuclide decay chain, reversible first-order kinetics, kinetic sorption or
+        mobile-immobile exchange, biodegradation with a yield:
+        ``acc_a (c_a - c_old_a) + w_a (A c_a + b_ref_a) + rate_weight * (K c)_a = source_a``.
+        ``rate_matrix`` K (k, k) is the rate matrix of ``dc/dt = -K c``, shared by all cells; ``rate_weight`` (Nc, >= 0,
+        None = 1) weighs the reaction term per cell (pore volume x dt, a reactive zone); ``mobility`` w (k, >= 0,
+        None = 1): 0 is an immobile component that sees no flux and no boundary (its boundary values are not read).
+        ``c0``: (k, Nc); ``accumulation`` (positive), ``bc_values`` and ``source`` broadcast as in ``advance_components``.
+
+        K must have a non-negative diagonal, non-positive off-diagonal entries and no negative column sum (no mass
+        created; rounding of the sum is allowed for) -- ``ValueError`` otherwise.  Every cell's k x k block then is a
+        column-diagonally-dominant M-matrix, solved without pivoting; non-negative data stay non-negative.
+
+        In flow order a cell is one k x k solve once its upstream cells are known: the matrix, the levels and the
+        launches are those of one component.  The cells of a cyclic core are iterated by block Jacobi, at most ``maxit``
+        times per step.  Returns (c, info): info["steps_done"], "converged" and the per-component lists "iterations"
+        (1, or the core iterations of the last step) and "rel_residual".  The error of a refused step carries
+        ``state``, c before that step, and ``info``."""
+        pd = data[PARAMETERS][self.keyword]
+        c0 = np.asarray(c0, dtype=np.float64)
+        nc, nf = sd.num_cells, sd.num_faces
+        if c0.ndim != 2 or c0.shape[1] != nc:
+            raise ValueError(f"c0 must have shape (k, {nc}), not {c0.shape}")
+        k = c0.shape[0]
+        if not 1 <= k <= 8:
+            raise ValueError(f"the number of coupled components must lie in 1 .. 8, not {k} (c0 has shape {c0.shape})")
+
+        def per_component(name, a, n):
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape == (n,):
+                return np.broadcast_to(a, (k, n))
+            if a.shape != (k, n):
+                raise ValueError(f"{name} must have shape ({n},) or ({k}, {n}), not {a.shape}")
+            return a
+
+        if accumulation is None:
+            raise ValueError("accumulation is required")
+        acc = per_component("accumulation", accumulation, nc)
+        bv = per_component("bc_values", pd["bc_values"] if bc_values is None else bc_values, nf)
+        src = None if source is None else per_component("source", source, nc)
+        try:
+            return self.context(sd).transport_advance_react(c0, n_steps, acc, bv, rate_matrix, rate_weight=rate_weight,
+                                                            mobility=mobility, q=self._flux(sd, pd), source=src,
+                                                            rtol=rtol, maxit=maxit, raise_on_fail=raise_on_fail)
+        except _lib.PorefvError as e:
+            if e.status == 4:
+                err = ValueError(e.message)
+                err.state, err.info = getattr(e, "state", None), getattr(e, "info", None)
+                raise err from None
+            raise
+
 
 def _flux_function(flux_function):
     """(kind, parameters) of the C ABI for what ``advance_saturation`` takes as ``flux_function``"""

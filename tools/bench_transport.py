@@ -7,7 +7,7 @@ Device times are HIP-event times from pfv_stats; the host times are wall clock. 
 not a test: no thresholds.
 
     python tools/bench_transport.py [--n-side 69] [--steps 20] [--no-host] [--precond sweep] [--components 8]
-                                    [--saturation [--components 4]]
+                                    [--saturation [--components 4]] [--reactive]
 
 --precond sweep: after the Jacobi-BiCGStab steps, the same steps from the same state with the flow-ordered sweep
 (PFV_PRECOND_SWEEP) -- order-build ms, levels, core cells, launches per sweep, ms per step -- and again with one launch
@@ -27,6 +27,11 @@ dropped), levels, launches, core cells and core iterations.
 Corey step alone, the Corey step with K phase-carried components (transport_advance_nl_multi: own inflow concentrations,
 sorption on component 0) and, for orientation, the K-component linear step (transport_advance_multi with
 precond="sweep"): ms per step of the three (best and median of --reps, the first repeat dropped), levels, launches.
+
+--reactive: alternating in one loop from the same state, the k = 4 steps of the linear multi-component sweep
+(transport_advance_multi with precond="sweep") and the same number of reactive k = 4 steps (transport_advance_react):
+the chain 0 -> 1 -> 2 plus the exchange 0 <-> 3 with component 3 immobile, the reaction term weighted by the pore
+volume.  ms per step of both from pfv_stats (best and median of --reps, the first repeat dropped), levels, launches.
 """
 from __future__ import annotations
 
@@ -57,6 +62,8 @@ def main():
                          "the Corey step alone against the Corey step with K components (with --saturation)")
     ap.add_argument("--saturation", action="store_true",
                     help="linear sweep steps against Corey saturation steps on the same flux and state")
+    ap.add_argument("--reactive", action="store_true",
+                    help="the linear k = 4 sweep steps against k = 4 coupled (reactive) steps on the same flux and state")
     ap.add_argument("--emulation", action="store_true", help="run on the host-emulation build (plumbing check)")
     a = ap.parse_args()
     lib = None
@@ -214,6 +221,45 @@ def main():
             sat["components"].append(entry)
         out["saturation"] = sat
         ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the saturation call leaves no system behind)
+    if a.reactive:
+        kc = 4
+        acc_k = np.array([(1.0 + 0.5 * j) * acc for j in range(kc)])
+        bv_k = np.array([tbv * (j + 1) / kc for j in range(kc)])
+        c0_k = rng.random((kc, nc))
+        l0, l1, l2, kf, kb = 20.0, 10.0, 2.0, 30.0, 15.0  # rates per unit time; dt = 0.5 / n
+        Kr = np.zeros((kc, kc))
+        Kr[0, 0], Kr[1, 0], Kr[3, 0] = l0 + kf, -l0, -kf
+        Kr[1, 1], Kr[2, 1] = l1, -l1
+        Kr[2, 2] = l2
+        Kr[3, 3], Kr[0, 3] = kb, -kb
+        mobility = np.array([1.0, 1.0, 1.0, 0.0])
+        pore_volume = 0.2 * g.cell_volumes
+        lin_ms, react_ms = [], []
+        entry = {"k": kc}
+        try:
+            for _ in range(a.reps + 1):  # (the first repeat builds the order and warms up: dropped)
+                cm, minfo = ctx.transport_advance_multi(c0_k, a.steps, acc_k, bv_k, rtol=1e-10, raise_on_fail=False,
+                                                        precond="sweep")
+                multi = ctx.stats()
+                lin_ms.append(multi["transport_advance_ms"] / max(a.steps, 1))
+                cr, rinfo = ctx.transport_advance_react(c0_k, a.steps, acc_k, bv_k, Kr, rate_weight=pore_volume,
+                                                        mobility=mobility, rtol=1e-10, raise_on_fail=False)
+                react = ctx.stats()
+                react_ms.append(react["transport_react_ms"] / max(a.steps, 1))
+            entry.update({
+                "steps_done": rinfo["steps_done"], "linear_steps_done": minfo["steps_done"],
+                "linear_components_ms_per_step": (min(lin_ms[1:]), float(np.median(lin_ms[1:]))),
+                "reactive_ms_per_step": (min(react_ms[1:]), float(np.median(react_ms[1:]))),
+                "levels": react["sweep_levels"], "core_cells": react["sweep_core_cells"],
+                "launches_per_step": react["sweep_launches"], "launches_per_sweep_linear": multi["sweep_launches"],
+                "linear_direct_steps": multi["transport_multi_direct_steps"],
+                "core_iterations": react["transport_react_core_iterations"],
+                "max_rel_residual_last_step": max(rinfo["rel_residual"]),
+                "c_min": float(cr.min()), "c_max": float(cr.max())})
+        except pa.PorefvError as e:
+            entry["error"] = e.message
+        out["reactive"] = entry
+        ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the reactive call leaves no system behind)
     # bytes each kernel has to move at least ("Upwind advection"): the fraction of a stream rate follows
     nnz_flux = ctx.matrix_info(_lib.MAT_FLUX)[2]
     nnz_bound = ctx.matrix_info(_lib.MAT_BOUND_FLUX)[2]

@@ -690,15 +690,8 @@ static void amg_swap_pattern(CsrPattern& a, CsrPattern& b) {
   std::swap(a.ncols, b.ncols);
   std::swap(a.nnz, b.nnz);
   std::swap(a.max_row, b.max_row);
-  std::swap(a.indptr.p, b.indptr.p);
-  std::swap(a.indptr.cap, b.indptr.cap);
-  std::swap(a.indices.p, b.indices.p);
-  std::swap(a.indices.cap, b.indices.cap);
-}
-template <class T>
-static void amg_swap_buf(Buf<T>& a, Buf<T>& b) {
-  std::swap(a.p, b.p);
-  std::swap(a.cap, b.cap);
+  a.indptr.swap(b.indptr);
+  a.indices.swap(b.indices);
 }
 
 // checksum of a pattern's index arrays (topology.inc: launch_pattern_checksum), read back: tells whether saved
@@ -1494,8 +1487,8 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
     Ln.n = L.nc_cells * bs;
     // the last intermediate matrix becomes the new level (its old buffers go back to the slot)
     amg_swap_pattern(Ln.P_own, amg.wk.P[slot]);
-    amg_swap_buf(Ln.val_own, amg.wk.V[slot]);
-    amg_swap_buf(Ln.dinv, amg.wk.D[slot]);
+    Ln.val_own.swap(amg.wk.V[slot]);
+    Ln.dinv.swap(amg.wk.D[slot]);
     Ln.P = &Ln.P_own;
     Ln.val = Ln.val_own.p;
     Ln.win = nullptr;

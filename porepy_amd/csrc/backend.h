@@ -325,6 +325,10 @@ struct Buf {
     p = nullptr;
     cap = 0;
   }
+  void swap(Buf& o) {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+  }
   operator T*() const { return p; }
 };
 

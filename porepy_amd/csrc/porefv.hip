@@ -980,6 +980,62 @@ pfv_status pfv_upwind_assemble(pfv_ctx* h, const double* q, const double* bc_val
   });
 }
 
+// ---- what the step calls share ----------------------------------------------------------------------------------------
+// The flow order of the flux d_q on the transport system, in the caller's numbering and with its launch plan: built on
+// first use and kept while the flux brings the same edges; the time of a rebuild is added to order_ms.  same_flux: d_q is
+// the flux the order was last checked against in this call (an assembly in between can only have dropped it).
+static pfv::Sweep& transport_order(pfv_ctx* h, const double* d_q, double& order_ms, bool same_flux = false) {
+  if (!h->sweep) h->sweep = std::make_unique<pfv::Sweep>();
+  if (!same_flux) sweep_note_assembly(h, PFV_MAT_TRANSPORT_SYSTEM, d_q);
+  pfv::Sweep& sw = *h->sweep;
+  if (!sw.valid) {
+    pfv::sweep_build_order(*h, sw, d_q, PFV_MAT_TRANSPORT_SYSTEM);
+    order_ms += sw.order_ms;
+  }
+  pfv::sweep_set_numbering(*h, sw, false);
+  pfv::sweep_make_plan(sw);
+  return sw;
+}
+
+// The policy of the core loop: iterate() until the core has settled, at most maxit times.  The stop test runs every
+// kNlCoreCheck-th iteration and at maxit: stop_test() launches it, ONE host read brings `out` into hst, judge() says
+// whether the core has settled.
+struct CoreRun {
+  int iterations = 0;
+  bool settled = false;
+};
+static CoreRun core_iterate(pfv_ctx* h, int maxit, const double* out, std::vector<double>& hst,
+                            const std::function<void()>& iterate, const std::function<void()>& stop_test,
+                            const std::function<bool()>& judge) {
+  CoreRun run;
+  while (run.iterations < maxit && !run.settled) {
+    iterate();
+    ++run.iterations;
+    if (run.iterations % pfv::kNlCoreCheck != 0 && run.iterations != maxit) continue;
+    stop_test();
+    be_d2h(hst.data(), out, sizeof(double) * hst.size(), h->stream);
+    run.settled = judge();
+  }
+  return run;
+}
+
+// the sweep statistics of a step call; launches < 0: those of the launch plan
+static void sweep_step_stats(pfv_ctx* h, int64_t launches, double order_ms) {
+  if (!h->sweep || !h->sweep->valid) return;
+  pfv::sweep_make_plan(*h->sweep);
+  h->stats.sweep_levels = h->sweep->nlev;
+  h->stats.sweep_core_cells = h->sweep->n_core;
+  h->stats.sweep_launches = launches >= 0 ? launches : (int64_t)h->sweep->plan.size();
+  h->stats.sweep_order_ms = order_ms;
+}
+
+// The error of a failed step (status st, text err) is what the call reports, whatever the epilogue (st2) did.
+static pfv_status step_status(pfv_ctx* h, pfv_status st, const std::string& err, pfv_status st2) {
+  if (st == PFV_OK) return st2;
+  h->err = err;
+  return st;
+}
+
 // ---- the step loop of pfv_transport_advance and pfv_advdiff_advance --------------------------------------------------
 struct StepLoop {  // what differs between the two
   pfv::Buf<double> pfv::pfv_ctx_impl::*state;  // the state between the steps
@@ -1062,11 +1118,7 @@ static pfv_status advance_steps(pfv_ctx* h, const StepLoop& L, const std::functi
     vec_out(h, c, state.p, (size_t)h->nc);
     pfv::be_sync(h->stream);
   });
-  if (st != PFV_OK) {
-    h->err = err;
-    return st;
-  }
-  return st2;
+  return step_status(h, st, err, st2);
 }
 
 pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rtol, int maxit, double* c,
@@ -1147,15 +1199,7 @@ pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, 
                                            "and without an accumulation term): the solvers do not apply");
     pfv::upwind_bref_multi(*h, k, d_q, h->mc_bc.p, h->mc_bref_i.ensure(k * nc));
     if (h->precond == PFV_PRECOND_SWEEP) {
-      // the order of the flux, built on first use and kept while assemblies bring the same edges (sweep_note_assembly)
-      if (!h->sweep) h->sweep = std::make_unique<pfv::Sweep>();
-      pfv::Sweep& sw = *h->sweep;
-      if (sw.valid && (sw.for_system != PFV_MAT_TRANSPORT_SYSTEM || !pfv::sweep_same_edges(*h, sw, d_q))) sw.valid = false;
-      if (!sw.valid) {
-        pfv::sweep_build_order(*h, sw, d_q, PFV_MAT_TRANSPORT_SYSTEM);
-        order_ms += sw.order_ms;
-      }
-      fast = sw.n_core == 0;
+      fast = transport_order(h, d_q, order_ms).n_core == 0;
     }
   });
   if (st != PFV_OK) {
@@ -1196,13 +1240,8 @@ pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, 
           values_changed(h, Windows::drop);
           shared_values = true;
         }
-        pfv::Sweep& sw = *h->sweep;
-        if (!sw.valid) {
-          pfv::sweep_build_order(*h, sw, d_q, PFV_MAT_TRANSPORT_SYSTEM);
-          order_ms += sw.order_ms;
-        }
-        pfv::sweep_set_numbering(*h, sw, false);  // (a component's own solve in between works in the renumbered system)
-        pfv::sweep_make_plan(sw);
+        // (a component's own solve in between works in the renumbered system, and its assembly can drop the order)
+        const pfv::Sweep& sw = transport_order(h, d_q, order_ms, true);
         const double* val = h->val[PFV_MAT_TRANSPORT_SYSTEM].p;
         pfv::upwind_step_rhs_multi(*h, k, h->mc_acc_i.p, src_i, h->mc_bref_i.p, h->mc_x.p, h->mc_r.p);
         pfv::sweep_apply_multi(*h, sw, h->pat_T, val, h->diag_t.p, h->mc_acc_i.p, k, h->mc_r.p, h->mc_z.p);
@@ -1236,8 +1275,7 @@ pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, 
         if (st == PFV_OK) st = guarded(h, [&] { pfv::multi_set_column(*h, (int64_t)nc, k, a, h->mc_col.p, h->mc_z.p); });
       }
       if (st != PFV_OK) break;
-      std::swap(h->mc_x.p, h->mc_z.p);
-      std::swap(h->mc_x.cap, h->mc_z.cap);
+      h->mc_x.swap(h->mc_z);
       ++completed;
       if (!failed) ++direct_steps;
     }
@@ -1269,10 +1307,7 @@ pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, 
     }
     completed = target;
     fallback = (int64_t)k * target;
-    if (target > 0) {
-      std::swap(h->mc_x.p, h->mc_z.p);
-      std::swap(h->mc_x.cap, h->mc_z.cap);
-    }
+    if (target > 0) h->mc_x.swap(h->mc_z);
   }
   double ms = 0.0;
   const pfv_status st2 = guarded(h, [&] {
@@ -1297,18 +1332,8 @@ pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, 
   h->stats.transport_multi_direct_steps = direct_steps;
   h->stats.transport_multi_fallback_components = fallback;
   h->stats.sweep_direct_steps = direct_steps;
-  if (h->precond == PFV_PRECOND_SWEEP && h->sweep && h->sweep->valid) {
-    pfv::sweep_make_plan(*h->sweep);
-    h->stats.sweep_levels = h->sweep->nlev;
-    h->stats.sweep_core_cells = h->sweep->n_core;
-    h->stats.sweep_launches = (int64_t)h->sweep->plan.size();
-    h->stats.sweep_order_ms = order_ms;
-  }
-  if (st != PFV_OK) {
-    h->err = err;
-    return st;
-  }
-  return st2;
+  if (h->precond == PFV_PRECOND_SWEEP) sweep_step_stats(h, -1, order_ms);
+  return step_status(h, st, err, st2);
 }
 
 // ---- the saturation step: q f(s) in flow order (sweep.inc: sweep_row_nl) -----------------------------------------------
@@ -1365,8 +1390,7 @@ static pfv_status advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const
                                sorption ? h->nlc_ads_in.p : nullptr, h->nlc_c_in.p, h->nlc_cbc.p, off);
     static const char* what[5] = {"accumulation must be positive: cell ", "negative sink in cell ",
                                   "s outside [0, 1] in cell ", "Dirichlet inflow value outside [0, 1] on face ",
-                                  "negative axis 1 index: -1 (neither Dirichlet nor Neumann, with inflow: no upstream "
-                                  "cell) face "};
+                                  pfv::kUnmarkedInflowFace};
     for (int m = 0; m < 5; ++m)
       if (off[m] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, what[m] + std::to_string(off[m]));
     static const char* whatc[3] = {"sorption must not be negative: cell ", "c is not finite in cell ",
@@ -1395,16 +1419,7 @@ static pfv_status advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const
       pfv::upwind_bref_nlc(*h, F, k, d_q, h->nl_bc.p, h->nlc_cbc.p, h->nlc_bref.ensure(k * nc));
       for (pfv::Buf<double>* b : {&h->nlc_z, &h->nlc_psi, &h->nlc_psi2, &h->nlc_rhs, &h->nlc_t}) b->ensure(k * nc);
     }
-    // the order of the flux, built on first use and kept while assemblies bring the same edges (sweep_note_assembly)
-    if (!h->sweep) h->sweep = std::make_unique<pfv::Sweep>();
-    pfv::Sweep& sw = *h->sweep;
-    if (sw.valid && (sw.for_system != PFV_MAT_TRANSPORT_SYSTEM || !pfv::sweep_same_edges(*h, sw, d_q))) sw.valid = false;
-    if (!sw.valid) {
-      pfv::sweep_build_order(*h, sw, d_q, PFV_MAT_TRANSPORT_SYSTEM);
-      order_ms += sw.order_ms;
-    }
-    pfv::sweep_set_numbering(*h, sw, false);
-    pfv::sweep_make_plan(sw);
+    const pfv::Sweep& sw = transport_order(h, d_q, order_ms);
     if (sw.n_core > 0) {
       h->nl_cb.ensure((size_t)sw.n_core);
       h->nl_ct.ensure((size_t)sw.n_core);
@@ -1459,7 +1474,6 @@ static pfv_status advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const
       pfv::be_memset(status, 0x7f, 2 * sizeof(int32_t), c.stream);
       if (k > 0) pfv::be_memset(cout, 0, 4 * (size_t)k * sizeof(double), c.stream);
       launches = pfv::sweep_apply_nl(c, sw, 0, core, c.pat_T, val, diag, d_sink, acc, rhs, F, s_old, s_new, phi, status, C);
-      const size_t hst_bytes = sizeof(double) * hst.size();
       auto flagged = [&](bool core_too, int32_t& cell) {
         int32_t w[2];
         std::memcpy(w, hst.data() + 4, sizeof(w));
@@ -1468,21 +1482,19 @@ static pfv_status advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const
       };
       int core_it = 0;
       if (has_core) {
-        bool settled = false;
         pfv::sweep_residual_norms(c, c.nc, rhs, rhs, out);  // out[0] = (rhs, rhs)
         pfv::sweep_nl_core_init(c, sw, F, s_old, s_new, phi);
         if (k > 0) {
           pfv::sweep_norms_interleaved(c, c.nc, k, C.rhs, C.rhs, cout);  // cout[a] = (rhs_a, rhs_a)
           pfv::sweep_nlc_core_init(c, sw, phi, C);
         }
-        while (core_it < maxit && !settled) {
+        const CoreRun run = core_iterate(h, maxit, out, hst, [&] {
           // (once the saturation has passed its own test it stays, with its status word: the components alone go on)
           if (!Cc.frozen) pfv::sweep_nl_core_keep(c, sw, phi, c.nl_phi2.p, status + 1);
-          if (k > 0) pfv::sweep_nlc_core_keep(c, sw, k, C.psi, c.nlc_psi2.p);
+          if (k > 0) pfv::sweep_core_copy(c, sw, k, C.psi, c.nlc_psi2.p);
           pfv::sweep_levels_nl(c, sw, core, core + 1, c.pat_T, val, diag, d_sink, acc, rhs, F, s_new, c.nl_phi2.p, s_new,
                                phi, status + 1, Cc);
-          ++core_it;
-          if (core_it % pfv::kNlCoreCheck != 0 && core_it != maxit) continue;
+        }, [&] {
           if (!Cc.frozen) {
             pfv::sweep_nl_core_image(c, sw, c.pat_T, val, d_sink, acc, rhs, s_new, phi, c.nl_cb.p, c.nl_ct.p);
             pfv::sweep_residual_norms(c, sw.n_core, c.nl_cb.p, c.nl_ct.p, out + 2);  // out[3] = (F_core, F_core)
@@ -1491,15 +1503,17 @@ static pfv_status advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const
             pfv::sweep_nlc_core_image(c, sw, c.pat_T, val, d_sink, acc, s_new, C, c.nlc_cb.p, c.nlc_ct.p);
             pfv::sweep_norms_interleaved(c, sw.n_core, k, c.nlc_cb.p, c.nlc_ct.p, cout + 2 * k);
           }
-          be_d2h(hst.data(), out, hst_bytes, c.stream);
-          settled = hst[3] <= 0.25 * rtol * rtol * hst[0];
+        }, [&] {
+          bool settled = hst[3] <= 0.25 * rtol * rtol * hst[0];
           Cc.frozen = settled;
           for (int a = 0; a < k; ++a)  // (F_core_a, F_core_a) against (rhs_a, rhs_a)
             settled = settled && hst[5 + 3 * (size_t)k + a] <= 0.25 * rtol * rtol * hst[5 + (size_t)a];
-        }
+          return settled;
+        });
+        core_it = run.iterations;
         core_total += core_it;
         launches += 2;
-        if (!settled) {  // (what the backward levels would compute from this core is not judged)
+        if (!run.settled) {  // (what the backward levels would compute from this core is not judged)
           info = pfv_solve_info{};
           info.iterations = core_it;
           info.rel_residual = hst[0] > 0.0 ? std::sqrt(hst[3] / hst[0]) : 0.0;
@@ -1525,7 +1539,7 @@ static pfv_status advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const
       else pfv::sweep_nl_image(c, c.pat_T, val, d_sink, acc, s_new, phi, c.nl_t.p);
       pfv::sweep_residual_norms(c, c.nc, rhs, c.nl_t.p, out);
       if (k > 0) pfv::sweep_norms_interleaved(c, c.nc, k, C.rhs, c.nlc_t.p, cout);
-      be_d2h(hst.data(), out, hst_bytes, c.stream);
+      be_d2h(hst.data(), out, sizeof(double) * hst.size(), c.stream);
       info = pfv_solve_info{};
       info.iterations = has_core ? core_it : 1;
       info.rel_residual = hst[0] > 0.0 ? std::sqrt(hst[1] / hst[0]) : 0.0;
@@ -1552,12 +1566,8 @@ static pfv_status advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const
                 " after the sweep (a flux that contradicts the discretization's?)";
         return;
       }
-      std::swap(c.nl_s.p, c.nl_s2.p);
-      std::swap(c.nl_s.cap, c.nl_s2.cap);
-      if (k > 0) {
-        std::swap(c.nlc_x.p, c.nlc_z.p);
-        std::swap(c.nlc_x.cap, c.nlc_z.cap);
-      }
+      c.nl_s.swap(c.nl_s2);
+      if (k > 0) c.nlc_x.swap(c.nlc_z);
       ++completed;
     });
     if (st == PFV_OK) st = verdict;
@@ -1588,17 +1598,8 @@ static pfv_status advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const
   h->stats.transport_nl_steps = completed;
   h->stats.transport_nl_core_iterations = core_total;
   h->stats.transport_nl_components = k;
-  if (h->sweep && h->sweep->valid) {
-    h->stats.sweep_levels = h->sweep->nlev;
-    h->stats.sweep_core_cells = h->sweep->n_core;
-    h->stats.sweep_launches = n_steps > 0 ? launches : (int64_t)h->sweep->plan.size();
-    h->stats.sweep_order_ms = order_ms;
-  }
-  if (st != PFV_OK) {
-    h->err = err;
-    return st;
-  }
-  return st2;
+  sweep_step_stats(h, n_steps > 0 ? launches : -1, order_ms);
+  return step_status(h, st, err, st2);
 }
 
 pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
@@ -1670,9 +1671,7 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
       throw Error(PFV_ERR_ARGUMENT, "rate_weight must not be negative: cell " + std::to_string(off[1]));
     if (off[2] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, "c is not finite in cell " + comp(off[2]));
     if (off[3] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, "bc_values is not finite on face " + comp(off[3]));
-    if (off[4] != 0x7f7f7f7f)
-      throw Error(PFV_ERR_ARGUMENT, "negative axis 1 index: -1 (neither Dirichlet nor Neumann, with inflow: no upstream "
-                                    "cell) face " + std::to_string(off[4]));
+    if (off[4] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, pfv::kUnmarkedInflowFace + std::to_string(off[4]));
     tm = std::make_unique<pfv::Timer>();
     tm->start(h->stream);
     // A = div diag(q) U without accumulation (its diagonal: the outflow of the cell), once per call.  (The boundary
@@ -1687,16 +1686,7 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
     pfv::upwind_bref_react(*h, k, d_q, h->rc_bc.p, h->rc_par.p, h->rc_bref.ensure(k * nc));
     for (pfv::Buf<double>* b : {&h->rc_z, &h->rc_prev, &h->rc_rhs, &h->rc_g, &h->rc_F}) b->ensure(k * nc);
     h->rc_out.ensure(2 * (size_t)k + 1);
-    // the order of the flux, built on first use and kept while assemblies bring the same edges (sweep_note_assembly)
-    if (!h->sweep) h->sweep = std::make_unique<pfv::Sweep>();
-    pfv::Sweep& sw = *h->sweep;
-    if (sw.valid && (sw.for_system != PFV_MAT_TRANSPORT_SYSTEM || !pfv::sweep_same_edges(*h, sw, d_q))) sw.valid = false;
-    if (!sw.valid) {
-      pfv::sweep_build_order(*h, sw, d_q, PFV_MAT_TRANSPORT_SYSTEM);
-      order_ms += sw.order_ms;
-    }
-    pfv::sweep_set_numbering(*h, sw, false);
-    pfv::sweep_make_plan(sw);
+    transport_order(h, d_q, order_ms);
   });
   if (st != PFV_OK) {
     if (touched) upwind_drop_transport(h, true);  // (A without accumulation: not a system to be solved with)
@@ -1723,7 +1713,6 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
                       cx.rc_rhs.p, nullptr, cx.rc_z.p, status};
       pfv::ReactRow Ac = A;  // the core level, with the state of the previous iterate
       Ac.c_prev = cx.rc_prev.p;
-      const size_t hst_bytes = sizeof(double) * hst.size();
       auto component_info = [&](int it) {  // from hst: (g_a, g_a), (F_a, F_a)
         for (int a = 0; a < k; ++a) {
           const double gg = hst[(size_t)a], ff = hst[(size_t)k + a];
@@ -1737,23 +1726,23 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
       launches = pfv::sweep_apply_react(cx, sw, 0, core, k, A, par);
       int core_it = 0;
       if (has_core) {
-        bool settled = false;
-        pfv::sweep_nlc_core_keep(cx, sw, k, cx.rc_x.p, cx.rc_z.p);  // the core rows start from the state of the step's start
-        while (core_it < maxit && !settled) {
-          pfv::sweep_nlc_core_keep(cx, sw, k, cx.rc_z.p, cx.rc_prev.p);
+        pfv::sweep_core_copy(cx, sw, k, cx.rc_x.p, cx.rc_z.p);  // the core rows start from the state of the step's start
+        const CoreRun run = core_iterate(h, maxit, out, hst, [&] {
+          pfv::sweep_core_copy(cx, sw, k, cx.rc_z.p, cx.rc_prev.p);
           pfv::sweep_levels_react(cx, sw, core, core + 1, k, Ac, par);
-          ++core_it;
-          if (core_it % pfv::kNlCoreCheck != 0 && core_it != maxit) continue;
+        }, [&] {
           pfv::sweep_react_image(cx, cx.pat_T, val, k, cx.rc_acc.p, rho, cx.rc_rhs.p, cx.rc_par.p, cx.rc_z.p, A.lev, core,
                                  cx.rc_g.p, cx.rc_F.p);
           pfv::sweep_react_norms(cx, cx.nc, k, cx.rc_g.p, cx.rc_F.p, out);
-          be_d2h(hst.data(), out, hst_bytes, cx.stream);
-          settled = true;
+        }, [&] {
+          bool settled = true;
           for (int a = 0; a < k; ++a) settled = settled && hst[(size_t)k + a] <= 0.25 * rtol * rtol * hst[(size_t)a];
-        }
+          return settled;
+        });
+        core_it = run.iterations;
         core_total += core_it;
         launches += 2;
-        if (!settled) {  // (what the backward levels would compute from this core is not judged)
+        if (!run.settled) {  // (what the backward levels would compute from this core is not judged)
           component_info(core_it);
           verdict = PFV_ERR_NOT_CONVERGED;
           cx.err = "step " + std::to_string(step) + ": the cyclic core of " + std::to_string(sw.n_core) +
@@ -1765,7 +1754,7 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
       pfv::sweep_react_image(cx, cx.pat_T, val, k, cx.rc_acc.p, rho, cx.rc_rhs.p, cx.rc_par.p, cx.rc_z.p, A.lev, -1,
                              cx.rc_g.p, cx.rc_F.p);
       pfv::sweep_react_norms(cx, cx.nc, k, cx.rc_g.p, cx.rc_F.p, out);
-      be_d2h(hst.data(), out, hst_bytes, cx.stream);
+      be_d2h(hst.data(), out, sizeof(double) * hst.size(), cx.stream);
       component_info(has_core ? core_it : 1);
       int32_t cell;
       std::memcpy(&cell, hst.data() + 2 * k, sizeof(cell));
@@ -1786,8 +1775,7 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
                  " of component " + std::to_string(bad) + " after the sweep (a flux that contradicts the discretization's?)";
         return;
       }
-      std::swap(cx.rc_x.p, cx.rc_z.p);
-      std::swap(cx.rc_x.cap, cx.rc_z.cap);
+      cx.rc_x.swap(cx.rc_z);
       ++completed;
     });
     if (st == PFV_OK) st = verdict;
@@ -1812,17 +1800,8 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
   h->stats.transport_react_steps = completed;
   h->stats.transport_react_core_iterations = core_total;
   h->stats.transport_react_components = k;
-  if (h->sweep && h->sweep->valid) {
-    h->stats.sweep_levels = h->sweep->nlev;
-    h->stats.sweep_core_cells = h->sweep->n_core;
-    h->stats.sweep_launches = n_steps > 0 ? launches : (int64_t)h->sweep->plan.size();
-    h->stats.sweep_order_ms = order_ms;
-  }
-  if (st != PFV_OK) {
-    h->err = err;
-    return st;
-  }
-  return st2;
+  sweep_step_stats(h, n_steps > 0 ? launches : -1, order_ms);
+  return step_status(h, st, err, st2);
 }
 
 // ---- advection-diffusion on one handle (advdiff.inc) -----------------------------------------------------------

@@ -253,29 +253,63 @@ PFV_FN void sweep_row(int32_t i, const int32_t* ip, const int32_t* ix, const dou
   z[i] = (r[i] - sum) / diag[i];
 }
 
+// ---- the launch rule, once.  Levels [l0, l1) of the order in the chosen numbering, `items` work items per row:
+// body(row, a) for a in [0, items).  One level is one launch over its rows; a run of levels is one launch of a single
+// workgroup that takes them one after the other.  OnePerRow makes the count a compile-time 1 (no division in the
+// kernel); an int is the run-time count.  (Both forms name `ord` before `body`: the kernel's arguments then lie in the
+// order the row functions' register use was measured with -- DESIGN.md 18, 19.)
+struct OnePerRow {
+  PFV_FN constexpr operator int() const { return 1; }
+};
+template <class Items, class Body>
+static void sweep_levels(pfv_ctx_impl& c, const Sweep& sw, bool permuted, int l0, int l1, Items items, Body body) {
+  const int32_t* ord = sw.ord(permuted);
+  if (l1 - l0 == 1) {
+    const int32_t a0 = sw.h_lptr[(size_t)l0], m = sw.h_lptr[(size_t)l1] - a0;
+    parallel_for(c.stream, (int64_t)m * items, PFV_LAMBDA(int64_t t) {
+      const int k = items;
+      const int32_t i = ord[a0 + t / k];
+      body(i, (int)(t % k));
+    });
+  } else if (l1 > l0) {
+    const int32_t* lp = sw.lptr;
+    block_for<256>(c.stream, 1, 0, PFV_LAMBDA(const WaveCtx& w) {
+      const int k = items;
+      for (int l = l0; l < l1; ++l) {
+        const int32_t a0 = lp[l], m = lp[l + 1] - a0;
+        PFV_LANES(t, m * k) {
+          const int32_t i = ord[a0 + t / k];
+          body(i, t % k);
+        }
+        w.sync();  // (the next level reads what this one wrote: same workgroup, same CU)
+      }
+    });
+  }
+}
+
+// The segments of the launch plan cut to the levels [from, to) -- a run is cut where the core level, which is iterated
+// on its own, falls into it --, each handed to levels(l0, l1).  Returns the launches.
+template <class Levels>
+static int sweep_plan_range(const Sweep& sw, int from, int to, Levels levels) {
+  int launches = 0;
+  for (const Sweep::Seg& g : sw.plan) {
+    const int l0 = std::max(g.l0, from), l1 = std::min(g.l1, to);
+    if (l0 >= l1) continue;
+    levels(l0, l1);
+    ++launches;
+  }
+  return launches;
+}
+
 static void sweep_apply(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* val, const double* diag,
                         const double* in, double* out) {
-  stream_t s = c.stream;
   const int32_t* ip = P.indptr;
   const int32_t* ix = P.indices;
   const int32_t* lev = sw.lev(sw.permuted);
-  const int32_t* ord = sw.ord(sw.permuted);
-  const int32_t* lp = sw.lptr;
-  for (const Sweep::Seg& g : sw.plan) {
-    if (g.l1 - g.l0 == 1) {
-      const int32_t a = sw.h_lptr[(size_t)g.l0], m = sw.h_lptr[(size_t)g.l1] - a;
-      parallel_for(s, m, PFV_LAMBDA(int64_t k) { sweep_row(ord[a + k], ip, ix, val, diag, lev, in, out); });
-    } else {
-      const int l0 = g.l0, l1 = g.l1;
-      block_for<256>(s, 1, 0, PFV_LAMBDA(const WaveCtx& w) {
-        for (int l = l0; l < l1; ++l) {
-          const int32_t a = lp[l], m = lp[l + 1] - a;
-          PFV_LANES(k, m) sweep_row(ord[a + k], ip, ix, val, diag, lev, in, out);
-          w.sync();  // (the next level reads what this one wrote: same workgroup, same CU)
-        }
-      });
-    }
-  }
+  sweep_plan_range(sw, 0, sw.nlev, [&](int l0, int l1) {
+    sweep_levels(c, sw, sw.permuted, l0, l1, OnePerRow{},
+                 PFV_LAMBDA(int32_t i, int) { sweep_row(i, ip, ix, val, diag, lev, in, out); });
+  });
 }
 
 // out[0] = (b, b), out[1] = (b - t, b - t): fixed partition, fixed reduction order
@@ -344,42 +378,26 @@ PFV_FN void sweep_row_multi(int32_t i, int a, int k, const int32_t* ip, const in
 
 static void sweep_apply_multi(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* val,
                               const double* diag, const double* acc, int k, const double* in, double* out) {
-  stream_t s = c.stream;
   const int32_t* ip = P.indptr;
   const int32_t* ix = P.indices;
   const int32_t* lev = sw.lev(sw.permuted);
-  const int32_t* ord = sw.ord(sw.permuted);
-  const int32_t* lp = sw.lptr;
-  for (const Sweep::Seg& g : sw.plan) {
-    if (g.l1 - g.l0 == 1) {
-      const int32_t a0 = sw.h_lptr[(size_t)g.l0], m = sw.h_lptr[(size_t)g.l1] - a0;
-      parallel_for(s, (int64_t)m * k, PFV_LAMBDA(int64_t t) {
-        sweep_row_multi(ord[a0 + t / k], (int)(t % k), k, ip, ix, val, diag, acc, lev, in, out);
-      });
-    } else {
-      const int l0 = g.l0, l1 = g.l1;
-      block_for<256>(s, 1, 0, PFV_LAMBDA(const WaveCtx& w) {
-        for (int l = l0; l < l1; ++l) {
-          const int32_t a0 = lp[l], m = lp[l + 1] - a0;
-          PFV_LANES(t, m * k) sweep_row_multi(ord[a0 + t / k], t % k, k, ip, ix, val, diag, acc, lev, in, out);
-          w.sync();  // (the next level reads what this one wrote: same workgroup, same CU)
-        }
-      });
-    }
-  }
+  sweep_plan_range(sw, 0, sw.nlev, [&](int l0, int l1) {
+    sweep_levels(c, sw, sw.permuted, l0, l1, k,
+                 PFV_LAMBDA(int32_t i, int a) { sweep_row_multi(i, a, k, ip, ix, val, diag, acc, lev, in, out); });
+  });
 }
 
-// The residual check of all k components in one pass: t[i,a] = sum_e A[i,e] x[j,a] + acc[i,a] x[i,a] in stored order,
-// out[a] = (r_a, r_a), out[k + a] = (r_a - t_a, r_a - t_a).  Fixed partition, fixed reduction order: a workgroup takes a
+// ---- the norms of k interleaved vectors, once.  pair(i, a) gives the two numbers (u, v) of row i, component a;
+// out[a] = sum_i u^2, out[k + a] = sum_i v^2 over the n rows.  Fixed partition, fixed reduction order: a workgroup takes a
 // range of rows, slot g * k + a of it the rows lo + g, lo + g + G, ... of component a (G = 256 / k), and the G sums of a
 // component are folded pairwise; then one workgroup per number adds the workgroups' partial sums as
 // sweep_residual_norms does.
-static void sweep_residual_norms_multi(pfv_ctx_impl& c, const CsrPattern& P, const double* val, const double* acc,
-                                       int k, const double* r, const double* x, double* out) {
+struct NormPair {
+  double u, v;
+};
+template <class Pair>
+static void sweep_norms_pairs(pfv_ctx_impl& c, int64_t n, int k, double* out, Pair pair) {
   stream_t s = c.stream;
-  const int64_t n = P.nrows;
-  const int32_t* ip = P.indptr;
-  const int32_t* ix = P.indices;
   const int nb = (int)std::min<int64_t>(kGmresBlocks, (n * k + 2047) / 2048);
   const int G = 256 / k, slots = G * k;
   int fold = 1;
@@ -393,13 +411,9 @@ static void sweep_residual_norms_multi(pfv_ctx_impl& c, const CsrPattern& P, con
       const int a = slot % k, g = slot / k;
       double a0 = 0.0, a1 = 0.0;
       for (int64_t i = lo + g; i < hi; i += G) {
-        double t = 0.0;
-        for (int e = ip[i]; e < ip[i + 1]; ++e) t += val[e] * x[(int64_t)ix[e] * k + a];
-        const int64_t p = i * k + a;
-        t += acc[p] * x[p];
-        const double ri = r[p], d = ri - t;
-        a0 += ri * ri;
-        a1 += d * d;
+        const NormPair q = pair(i, a);
+        a0 += q.u * q.u;
+        a1 += q.v * q.v;
       }
       sh[slot] = a0;
       sh[256 + slot] = a1;
@@ -433,6 +447,30 @@ static void sweep_residual_norms_multi(pfv_ctx_impl& c, const CsrPattern& P, con
     }
     if (wc.lane0()) out[m] = sh[0];
     wc.sync();
+  });
+}
+
+// out[a] = (r_a, r_a), out[k + a] = (r_a - t_a, r_a - t_a) of interleaved vectors of n rows
+static void sweep_norms_interleaved(pfv_ctx_impl& c, int64_t n, int k, const double* r, const double* t, double* out) {
+  sweep_norms_pairs(c, n, k, out, PFV_LAMBDA(int64_t i, int a) {
+    const double ri = r[i * k + a];
+    return NormPair{ri, ri - t[i * k + a]};
+  });
+}
+
+// The residual check of all k components in one pass: t[i,a] = sum_e A[i,e] x[j,a] + acc[i,a] x[i,a] in stored order,
+// out[a] = (r_a, r_a), out[k + a] = (r_a - t_a, r_a - t_a).
+static void sweep_residual_norms_multi(pfv_ctx_impl& c, const CsrPattern& P, const double* val, const double* acc,
+                                       int k, const double* r, const double* x, double* out) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  sweep_norms_pairs(c, P.nrows, k, out, PFV_LAMBDA(int64_t i, int a) {
+    double t = 0.0;
+    for (int e = ip[i]; e < ip[i + 1]; ++e) t += val[e] * x[(int64_t)ix[e] * k + a];
+    const int64_t p = i * k + a;
+    t += acc[p] * x[p];
+    const double ri = r[p];
+    return NormPair{ri, ri - t};
   });
 }
 
@@ -590,63 +628,34 @@ PFV_FN void sweep_row_nlc(int32_t i, const int32_t* ip, const int32_t* ix, const
   }
 }
 
-// levels [l0, l1) of the order, by the rule of the launch plan: one level is one launch, a run is one workgroup;
-// with components (C.k > 0) both forms inline sweep_row_nlc, else sweep_row_nl
+// levels [l0, l1) of the order by the launch rule (sweep_levels): with components (C.k > 0) the rows are those of
+// sweep_row_nlc, else of sweep_row_nl
 static void sweep_levels_nl(pfv_ctx_impl& c, const Sweep& sw, int l0, int l1, const CsrPattern& P, const double* val,
                             const double* diag, const double* sink, const double* acc, const double* rhs,
                             const FluxFn& F, const double* s_start, const double* phi_prev, double* s, double* phi,
                             int32_t* status, const NlComp& C) {
-  stream_t st = c.stream;
   const int32_t* ip = P.indptr;
   const int32_t* ix = P.indices;
   const int32_t* lev = sw.lev(false);
-  const int32_t* ord = sw.ord(false);
-  const int32_t* lp = sw.lptr;
   if (C.k > 0) {
-    if (l1 - l0 == 1) {
-      const int32_t a0 = sw.h_lptr[(size_t)l0], m = sw.h_lptr[(size_t)l1] - a0;
-      parallel_for(st, m, PFV_LAMBDA(int64_t k) {
-        sweep_row_nlc(ord[a0 + k], ip, ix, val, diag, sink, acc, rhs, lev, F, s_start, phi_prev, s, phi, status, C);
-      });
-    } else if (l1 > l0) {
-      block_for<256>(st, 1, 0, PFV_LAMBDA(const WaveCtx& w) {
-        for (int l = l0; l < l1; ++l) {
-          const int32_t a0 = lp[l], m = lp[l + 1] - a0;
-          PFV_LANES(k, m) sweep_row_nlc(ord[a0 + k], ip, ix, val, diag, sink, acc, rhs, lev, F, s_start, phi_prev, s, phi, status, C);
-          w.sync();  // (the next level reads what this one wrote: same workgroup, same CU)
-        }
-      });
-    }
-  } else if (l1 - l0 == 1) {
-    const int32_t a0 = sw.h_lptr[(size_t)l0], m = sw.h_lptr[(size_t)l1] - a0;
-    parallel_for(st, m, PFV_LAMBDA(int64_t k) {
-      sweep_row_nl(ord[a0 + k], ip, ix, val, diag, sink, acc, rhs, lev, F, s_start, phi_prev, s, phi, status);
+    sweep_levels(c, sw, false, l0, l1, OnePerRow{}, PFV_LAMBDA(int32_t i, int) {
+      sweep_row_nlc(i, ip, ix, val, diag, sink, acc, rhs, lev, F, s_start, phi_prev, s, phi, status, C);
     });
-  } else if (l1 > l0) {
-    block_for<256>(st, 1, 0, PFV_LAMBDA(const WaveCtx& w) {
-      for (int l = l0; l < l1; ++l) {
-        const int32_t a0 = lp[l], m = lp[l + 1] - a0;
-        PFV_LANES(k, m) sweep_row_nl(ord[a0 + k], ip, ix, val, diag, sink, acc, rhs, lev, F, s_start, phi_prev, s, phi, status);
-        w.sync();  // (the next level reads what this one wrote: same workgroup, same CU)
-      }
+  } else {
+    sweep_levels(c, sw, false, l0, l1, OnePerRow{}, PFV_LAMBDA(int32_t i, int) {
+      sweep_row_nl(i, ip, ix, val, diag, sink, acc, rhs, lev, F, s_start, phi_prev, s, phi, status);
     });
   }
 }
 
-// The segments of the launch plan with levels in [from, to): the plan of sweep_apply, a run cut where the core level
-// (which is iterated on its own) falls into it.  Returns the launches.
+// the launch plan's levels in [from, to), outside the core (phi_prev = nullptr).  Returns the launches.
 static int sweep_apply_nl(pfv_ctx_impl& c, const Sweep& sw, int from, int to, const CsrPattern& P, const double* val,
                           const double* diag, const double* sink, const double* acc, const double* rhs,
                           const FluxFn& F, const double* s_start, double* s, double* phi, int32_t* status,
                           const NlComp& C) {
-  int launches = 0;
-  for (const Sweep::Seg& g : sw.plan) {
-    const int l0 = std::max(g.l0, from), l1 = std::min(g.l1, to);
-    if (l0 >= l1) continue;
+  return sweep_plan_range(sw, from, to, [&](int l0, int l1) {
     sweep_levels_nl(c, sw, l0, l1, P, val, diag, sink, acc, rhs, F, s_start, nullptr, s, phi, status, C);
-    ++launches;
-  }
-  return launches;
+  });
 }
 
 // t[i] = acc_i s_i + sum_e A_ie phi_j + sink_i phi_i in stored order: F(s) = rhs - t.  With lev: the entries up to the
@@ -702,65 +711,19 @@ static void sweep_nlc_image(pfv_ctx_impl& c, const CsrPattern& P, const double* 
   });
 }
 
-// out[a] = (r_a, r_a), out[k + a] = (r_a - t_a, r_a - t_a) of interleaved vectors of n rows, with the partition and the
-// reduction order of sweep_residual_norms_multi: a workgroup takes a range of rows, slot g * k + a of it the rows
-// lo + g, lo + g + G, ... of component a (G = 256 / k), the G sums of a component are folded pairwise, and one
-// workgroup per number adds the workgroups' partial sums.
-static void sweep_norms_interleaved(pfv_ctx_impl& c, int64_t n, int k, const double* r, const double* t, double* out) {
-  stream_t s = c.stream;
-  const int nb = (int)std::min<int64_t>(kGmresBlocks, (n * k + 2047) / 2048);
-  const int G = 256 / k, slots = G * k;
-  int fold = 1;
-  while (fold < G) fold <<= 1;
-  double* partial = c.red.ensure(2 * (size_t)k * kGmresBlocks + 64);
-  block_for<256>(s, nb, 2 * 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& w) {
-    double* sh = reinterpret_cast<double*>(w.lds);
-    const int64_t blk = w.item;
-    const int64_t lo = n * blk / nb, hi = n * (blk + 1) / nb;
-    PFV_LANES(slot, slots) {
-      const int a = slot % k, g = slot / k;
-      double a0 = 0.0, a1 = 0.0;
-      for (int64_t i = lo + g; i < hi; i += G) {
-        const double ri = r[i * k + a], d = ri - t[i * k + a];
-        a0 += ri * ri;
-        a1 += d * d;
-      }
-      sh[slot] = a0;
-      sh[256 + slot] = a1;
-    }
-    w.sync();
-    for (int o = fold >> 1; o > 0; o >>= 1) {
-      PFV_LANES(slot, slots) {
-        if (slot / k < o && slot / k + o < G) {
-          sh[slot] += sh[slot + o * k];
-          sh[256 + slot] += sh[256 + slot + o * k];
-        }
-      }
-      w.sync();
-    }
-    PFV_LANES(a, k) {
-      partial[(int64_t)a * nb + blk] = sh[a];
-      partial[(int64_t)(k + a) * nb + blk] = sh[256 + a];
-    }
-    w.sync();
-  });
-  block_for<256>(s, 2 * k, 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& wc) {
-    double* sh = reinterpret_cast<double*>(wc.lds);
-    const int64_t m = wc.item;
-    double a = 0.0;
-    for (int i = wc.lane; i < nb; i += wc.width) a += partial[m * nb + i];
-    sh[wc.lane] = a;
-    wc.sync();
-    for (int o = wc.width >> 1; o > 0; o >>= 1) {
-      if (wc.lane < o) sh[wc.lane] += sh[wc.lane + o];
-      wc.sync();
-    }
-    if (wc.lane0()) out[m] = sh[0];
-    wc.sync();
+// ---- the core rows.  For each (core row, component): body(row, a, w), w = m * items + a the position of component a
+// of the m-th core row among them (Items as in sweep_levels).
+template <class Items, class Body>
+static void sweep_core_rows(pfv_ctx_impl& c, const Sweep& sw, Items items, Body body) {
+  const int32_t* ord = sw.ord(false);
+  const int32_t a0 = sw.h_lptr[(size_t)sw.core_level];
+  parallel_for(c.stream, sw.n_core * items, PFV_LAMBDA(int64_t w) {
+    const int k = items;
+    body(ord[a0 + w / k], (int)(w % k), w);
   });
 }
 
-// The core rows, compacted: cb[k] = rhs of the k-th core row, ct[k] = its image.  A row that sits at an end of [0, 1]
+// The core rows, compacted: cb[m] = rhs of the m-th core row, ct[m] = its image.  A row that sits at an end of [0, 1]
 // with the residual pointing outwards (it took that end because it has no root inside) counts as solved: the
 // iteration then settles, and the step is refused by the status word, not by maxit.
 static void sweep_nl_core_image(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* val,
@@ -768,16 +731,13 @@ static void sweep_nl_core_image(pfv_ctx_impl& c, const Sweep& sw, const CsrPatte
                                 const double* phi, double* cb, double* ct) {
   const int32_t* ip = P.indptr;
   const int32_t* ix = P.indices;
-  const int32_t* ord = sw.ord(false);
   const int32_t* lev = sw.lev(false);
-  const int32_t a0 = sw.h_lptr[(size_t)sw.core_level];
-  parallel_for(c.stream, sw.n_core, PFV_LAMBDA(int64_t k) {
-    const int32_t i = ord[a0 + k];
+  sweep_core_rows(c, sw, OnePerRow{}, PFV_LAMBDA(int32_t i, int, int64_t m) {
     const double b = rhs[i];
     double t = sweep_nl_row_image(i, ip, ix, val, sink, acc, s, phi, lev);
     if ((s[i] == 0.0 && t > b) || (s[i] == 1.0 && t < b)) t = b;
-    cb[k] = b;
-    ct[k] = t;
+    cb[m] = b;
+    ct[m] = t;
   });
 }
 
@@ -787,13 +747,9 @@ static void sweep_nlc_core_image(pfv_ctx_impl& c, const Sweep& sw, const CsrPatt
                                  double* cct) {
   const int32_t* ip = P.indptr;
   const int32_t* ix = P.indices;
-  const int32_t* ord = sw.ord(false);
   const int32_t* lev = sw.lev(false);
-  const int32_t a0 = sw.h_lptr[(size_t)sw.core_level];
   const int k = C.k;
-  parallel_for(c.stream, sw.n_core * k, PFV_LAMBDA(int64_t w) {
-    const int32_t i = ord[a0 + w / k];
-    const int a = (int)(w % k);
+  sweep_core_rows(c, sw, k, PFV_LAMBDA(int32_t i, int a, int64_t w) {
     ccb[w] = C.rhs[(int64_t)i * k + a];
     cct[w] = sweep_nlc_row_image(i, a, k, ip, ix, val, sink, acc, C.ads, s, C.c, C.psi, lev);
   });
@@ -802,10 +758,7 @@ static void sweep_nlc_core_image(pfv_ctx_impl& c, const Sweep& sw, const CsrPatt
 // before the first core iteration: the core rows start from the state of the step's start
 static void sweep_nl_core_init(pfv_ctx_impl& c, const Sweep& sw, const FluxFn& F, const double* s_old, double* s,
                                double* phi) {
-  const int32_t* ord = sw.ord(false);
-  const int32_t a0 = sw.h_lptr[(size_t)sw.core_level];
-  parallel_for(c.stream, sw.n_core, PFV_LAMBDA(int64_t k) {
-    const int32_t i = ord[a0 + k];
+  sweep_core_rows(c, sw, OnePerRow{}, PFV_LAMBDA(int32_t i, int, int64_t) {
     double df;
     s[i] = s_old[i];
     phi[i] = fluxfn_eval(F, s_old[i], &df);
@@ -814,36 +767,29 @@ static void sweep_nl_core_init(pfv_ctx_impl& c, const Sweep& sw, const FluxFn& F
 
 // ... and so do their components: c <- c_start, psi <- phi c_start (after sweep_nl_core_init)
 static void sweep_nlc_core_init(pfv_ctx_impl& c, const Sweep& sw, const double* phi, const NlComp& C) {
-  const int32_t* ord = sw.ord(false);
-  const int32_t a0 = sw.h_lptr[(size_t)sw.core_level];
   const int k = C.k;
-  parallel_for(c.stream, sw.n_core * k, PFV_LAMBDA(int64_t w) {
-    const int32_t i = ord[a0 + w / k];
-    const int64_t p = (int64_t)i * k + w % k;
+  sweep_core_rows(c, sw, k, PFV_LAMBDA(int32_t i, int a, int64_t) {
+    const int64_t p = (int64_t)i * k + a;
     C.c[p] = C.c_start[p];
     C.psi[p] = phi[i] * C.c_start[p];
   });
 }
 
-// before every core iteration: psi_prev <- psi on the core rows
-static void sweep_nlc_core_keep(pfv_ctx_impl& c, const Sweep& sw, int k, const double* psi, double* psi_prev) {
-  const int32_t* ord = sw.ord(false);
-  const int32_t a0 = sw.h_lptr[(size_t)sw.core_level];
-  parallel_for(c.stream, sw.n_core * k, PFV_LAMBDA(int64_t w) {
-    const int64_t p = (int64_t)ord[a0 + w / k] * k + w % k;
-    psi_prev[p] = psi[p];
+// to <- from on the core rows of an interleaved vector (psi_prev <- psi before every core iteration of the saturation's
+// components; the reactive step's start state and its previous iterate)
+static void sweep_core_copy(pfv_ctx_impl& c, const Sweep& sw, int k, const double* from, double* to) {
+  sweep_core_rows(c, sw, k, PFV_LAMBDA(int32_t i, int a, int64_t) {
+    const int64_t p = (int64_t)i * k + a;
+    to[p] = from[p];
   });
 }
 
 // before every core iteration: phi_prev <- phi on the core rows; the core's status word starts afresh
 static void sweep_nl_core_keep(pfv_ctx_impl& c, const Sweep& sw, const double* phi, double* phi_prev,
                                int32_t* core_status) {
-  const int32_t* ord = sw.ord(false);
-  const int32_t a0 = sw.h_lptr[(size_t)sw.core_level];
-  parallel_for(c.stream, sw.n_core, PFV_LAMBDA(int64_t k) {
-    const int32_t i = ord[a0 + k];
+  sweep_core_rows(c, sw, OnePerRow{}, PFV_LAMBDA(int32_t i, int, int64_t m) {
     phi_prev[i] = phi[i];
-    if (k == 0) *core_status = 0x7f7f7f7f;
+    if (m == 0) *core_status = 0x7f7f7f7f;
   });
 }
 
@@ -912,6 +858,16 @@ static void upwind_step_rhs_nlc(pfv_ctx_impl& c, int k, const double* acc, const
   });
 }
 
+// A boundary face with inflow under q that carries neither a Dirichlet nor a Neumann condition: it has no upstream
+// cell.  Refused by the saturation and the reactive step alike, with one message.
+constexpr const char* kUnmarkedInflowFace =
+    "negative axis 1 index: -1 (neither Dirichlet nor Neumann, with inflow: no upstream cell) face ";
+PFV_FN bool upwind_unmarked_inflow(int64_t f, int64_t nf, const int32_t* cnt, const uint8_t* flag, const int32_t* side,
+                                   const double* d_q) {
+  if (!(cnt[f] + cnt[nf + f] == 1 && flag && !(flag[f] & (PFV_BC_DIR | PFV_BC_NEU)))) return false;
+  return (d_q[f] >= 0.0 ? side[f] : side[nf + f]) < 0;
+}
+
 // What the call refuses in its arrays, each with the lowest index: st[0] accumulation <= 0 or NaN, st[1] sink < 0,
 // st[2] s outside [0, 1], st[3] a Dirichlet inflow value outside [0, 1], st[4] a boundary face with inflow under q that
 // is neither Dirichlet nor Neumann.  With k > 0 components (component-major arrays as the caller passed them; an
@@ -945,10 +901,7 @@ static void sweep_nl_check_inputs(pfv_ctx_impl& c, const double* d_q, const doub
       if (cls[t] & (UPW_NEU | UPW_DIRIN))
         for (int a = 0; a < k; ++a)
           if (!(fabs(cbc[a * nf + t]) <= big)) atomic_min_i32(st + 7, (int32_t)(t * k + a));
-      if (cnt[t] + cnt[nf + t] == 1 && flag && !(flag[t] & (PFV_BC_DIR | PFV_BC_NEU))) {
-        const int32_t u = d_q[t] >= 0.0 ? side[t] : side[nf + t];
-        if (u < 0) atomic_min_i32(st + 4, (int32_t)t);
-      }
+      if (upwind_unmarked_inflow(t, nf, cnt, flag, side, d_q)) atomic_min_i32(st + 4, (int32_t)t);
     }
   });
   be_d2h(out, st, sizeof(int32_t) * kNlChecks, st_);
@@ -1052,28 +1005,13 @@ PFV_FN void sweep_row_react(int32_t i, const ReactRow& A, const ReactPar& P) {
   if (bad) atomic_min_i32(A.status, i);
 }
 
-// levels [l0, l1) of the order, by the rule of the launch plan: one level is one launch, a run is one workgroup; both
-// forms inline sweep_row_react<K>
+// levels [l0, l1) of the order by the launch rule (sweep_levels); the kernel holds ReactRow and ReactPar by value
 template <int K>
 static void sweep_levels_react_k(pfv_ctx_impl& c, const Sweep& sw, int l0, int l1, const ReactRow& A_,
                                  const ReactPar& P_) {
-  stream_t st = c.stream;
   const ReactRow A = A_;
   const ReactPar P = P_;
-  const int32_t* ord = sw.ord(false);
-  const int32_t* lp = sw.lptr;
-  if (l1 - l0 == 1) {
-    const int32_t a0 = sw.h_lptr[(size_t)l0], m = sw.h_lptr[(size_t)l1] - a0;
-    parallel_for(st, m, PFV_LAMBDA(int64_t t) { sweep_row_react<K>(ord[a0 + t], A, P); });
-  } else if (l1 > l0) {
-    block_for<256>(st, 1, 0, PFV_LAMBDA(const WaveCtx& w) {
-      for (int l = l0; l < l1; ++l) {
-        const int32_t a0 = lp[l], m = lp[l + 1] - a0;
-        PFV_LANES(t, m) sweep_row_react<K>(ord[a0 + t], A, P);
-        w.sync();  // (the next level reads what this one wrote: same workgroup, same CU)
-      }
-    });
-  }
+  sweep_levels(c, sw, false, l0, l1, OnePerRow{}, PFV_LAMBDA(int32_t i, int) { sweep_row_react<K>(i, A, P); });
 }
 
 static void sweep_levels_react(pfv_ctx_impl& c, const Sweep& sw, int l0, int l1, int k, const ReactRow& A,
@@ -1091,17 +1029,10 @@ static void sweep_levels_react(pfv_ctx_impl& c, const Sweep& sw, int l0, int l1,
   }
 }
 
-// The segments of the launch plan with levels in [from, to), as sweep_apply_nl cuts them.  Returns the launches.
+// the launch plan's levels in [from, to).  Returns the launches.
 static int sweep_apply_react(pfv_ctx_impl& c, const Sweep& sw, int from, int to, int k, const ReactRow& A,
                              const ReactPar& P) {
-  int launches = 0;
-  for (const Sweep::Seg& g : sw.plan) {
-    const int l0 = std::max(g.l0, from), l1 = std::min(g.l1, to);
-    if (l0 >= l1) continue;
-    sweep_levels_react(c, sw, l0, l1, k, A, P);
-    ++launches;
-  }
-  return launches;
+  return sweep_plan_range(sw, from, to, [&](int l0, int l1) { sweep_levels_react(c, sw, l0, l1, k, A, P); });
 }
 
 // After the sweep, per (row, a) in stored order: the image t_a = acc_a c_a + w_a (A c_a) + rho (K c)_a, of which
@@ -1144,60 +1075,9 @@ static void sweep_react_image(pfv_ctx_impl& c, const CsrPattern& P, const double
   });
 }
 
-// out[a] = (g_a, g_a), out[k + a] = (F_a, F_a) of interleaved vectors of n rows, with the partition and the reduction
-// order of sweep_norms_interleaved
+// out[a] = (g_a, g_a), out[k + a] = (F_a, F_a) of interleaved vectors of n rows
 static void sweep_react_norms(pfv_ctx_impl& c, int64_t n, int k, const double* g, const double* F, double* out) {
-  stream_t s = c.stream;
-  const int nb = (int)std::min<int64_t>(kGmresBlocks, (n * k + 2047) / 2048);
-  const int G = 256 / k, slots = G * k;
-  int fold = 1;
-  while (fold < G) fold <<= 1;
-  double* partial = c.red.ensure(2 * (size_t)k * kGmresBlocks + 64);
-  block_for<256>(s, nb, 2 * 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& w) {
-    double* sh = reinterpret_cast<double*>(w.lds);
-    const int64_t blk = w.item;
-    const int64_t lo = n * blk / nb, hi = n * (blk + 1) / nb;
-    PFV_LANES(slot, slots) {
-      const int a = slot % k, q = slot / k;
-      double a0 = 0.0, a1 = 0.0;
-      for (int64_t i = lo + q; i < hi; i += G) {
-        const double gi = g[i * k + a], fi = F[i * k + a];
-        a0 += gi * gi;
-        a1 += fi * fi;
-      }
-      sh[slot] = a0;
-      sh[256 + slot] = a1;
-    }
-    w.sync();
-    for (int o = fold >> 1; o > 0; o >>= 1) {
-      PFV_LANES(slot, slots) {
-        if (slot / k < o && slot / k + o < G) {
-          sh[slot] += sh[slot + o * k];
-          sh[256 + slot] += sh[256 + slot + o * k];
-        }
-      }
-      w.sync();
-    }
-    PFV_LANES(a, k) {
-      partial[(int64_t)a * nb + blk] = sh[a];
-      partial[(int64_t)(k + a) * nb + blk] = sh[256 + a];
-    }
-    w.sync();
-  });
-  block_for<256>(s, 2 * k, 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& wc) {
-    double* sh = reinterpret_cast<double*>(wc.lds);
-    const int64_t m = wc.item;
-    double a = 0.0;
-    for (int i = wc.lane; i < nb; i += wc.width) a += partial[m * nb + i];
-    sh[wc.lane] = a;
-    wc.sync();
-    for (int o = wc.width >> 1; o > 0; o >>= 1) {
-      if (wc.lane < o) sh[wc.lane] += sh[wc.lane + o];
-      wc.sync();
-    }
-    if (wc.lane0()) out[m] = sh[0];
-    wc.sync();
-  });
+  sweep_norms_pairs(c, n, k, out, PFV_LAMBDA(int64_t i, int a) { return NormPair{g[i * k + a], F[i * k + a]}; });
 }
 
 // What the call refuses in its arrays, each with the lowest index (component-major arrays as the caller passed them;
@@ -1230,10 +1110,7 @@ static void sweep_react_check_inputs(pfv_ctx_impl& c, const double* d_q, int k, 
       if (cls[t] & (UPW_NEU | UPW_DIRIN))
         for (int a = 0; a < k; ++a)
           if (par[a] > 0.0 && !(fabs(bc[a * nf + t]) <= big)) atomic_min_i32(st + 3, (int32_t)(t * k + a));
-      if (cnt[t] + cnt[nf + t] == 1 && flag && !(flag[t] & (PFV_BC_DIR | PFV_BC_NEU))) {
-        const int32_t u = d_q[t] >= 0.0 ? side[t] : side[nf + t];
-        if (u < 0) atomic_min_i32(st + 4, (int32_t)t);
-      }
+      if (upwind_unmarked_inflow(t, nf, cnt, flag, side, d_q)) atomic_min_i32(st + 4, (int32_t)t);
     }
   });
   be_d2h(out, st, sizeof(int32_t) * kReactChecks, st_);

@@ -250,10 +250,13 @@ def launch_forms(lib, n=4, k=4, rows=24):
 
 # ---- 8. cyclic core ------------------------------------------------------------------------------------------------------
 def core_case(lib, which):
+    """which: the core, or "<core>-k<k>" for the network of k components (k = 3: 256 is no multiple of k, the norms'
+    partition has G = 85 rows per slot and an odd fold)"""
+    which, _, kk = which.partition("-k")
     g, q = cyclic_field(12) if which == "cyclic12" else rotation(8)
     n_core = 45 if which == "cyclic12" else 64
-    nc, k = g.num_cells, 4
-    K, w = chain_with_partner()
+    nc, k = g.num_cells, int(kk or 4)
+    K, w = network(k)
     rng = np.random.default_rng(5)
     acc0 = cfl_accumulation(g, q, 2.0)
     acc = np.array([(1.0 + 0.5 * a) * acc0 for a in range(k)])

@@ -36,6 +36,7 @@ BOUNDS = {                 # largest error of the emulation build -> bound
     "linear": 1e-14,       # against advance_components(precond="sweep"): 7.78e-16
     "cyclic12": 1e-11,     # the cyclic cores, k = 2: 1.44e-13
     "rotation8": 1e-11,    # 8.43e-13
+    "cyclic12-k64": 1e-10,  # not from a run: the project's bound for a cyclic core stopped at rtol = 1e-12 (err_s below)
     "refused": 1e-10,      # the state handed back by the refused step (a core case): 2.03e-12
 }
 
@@ -255,13 +256,12 @@ def reduces_to_linear_components(lib, k=3, s_const=0.6):
 
 
 # ---- 5. the saturation is that of advance_saturation, to the bit ------------------------------------------------------------
-def _core_setup(which):
+def _core_setup(which, k=2):
     g, q, cfl, s0, n_core = core_problem(which)
     bv, acc = inflow_values(g), cfl_accumulation(g, q, cfl)
     rng = np.random.default_rng(5)
-    k = 2
     cbv = np.zeros((k, g.num_faces))
-    cbv[:, g.get_all_boundary_faces()] = np.array([0.5, 1.5])[:, None]
+    cbv[:, g.get_all_boundary_faces()] = (0.5 + np.arange(k))[:, None]
     c0 = 0.2 + rng.random((k, g.num_cells))
     ads = np.zeros((k, g.num_cells))
     ads[0] = 0.3 * acc
@@ -327,7 +327,9 @@ def launch_forms(lib, k=3, rows=24):
 
 # ---- 7. a cyclic core iterates s and c jointly -------------------------------------------------------------------------------
 def core_case(lib, which):
-    g, q, bv, acc, s0, n_core, cbv, c0, ads = _core_setup(which)
+    """which: the core, or "<core>-k<k>" for k components (k = 64: one slot per component in the core rows' norms)"""
+    core, _, kk = which.partition("-k")
+    g, q, bv, acc, s0, n_core, cbv, c0, ads = _core_setup(core, int(kk or 2))
     ff = corey()
     traj = newton_steps(g, q, bv, acc, s0, ff, 3)
     ref = component_steps(g, q, bv, cbv, acc, ff, traj, c0, ads)[-1]

@@ -47,7 +47,7 @@ def test_launch_forms(lib):
     C.launch_forms(lib)
 
 
-@pytest.mark.parametrize("which", ["cyclic12", "rotation8"])
+@pytest.mark.parametrize("which", ["cyclic12", "rotation8", "cyclic12-k64"])
 def test_core_iterates_jointly(lib, which):
     C.core_case(lib, which)
 

@@ -46,7 +46,7 @@ def test_launch_forms_and_determinism(lib):
     C.launch_forms(lib)
 
 
-@pytest.mark.parametrize("which", ["cyclic12", "rotation8"])
+@pytest.mark.parametrize("which", ["cyclic12", "rotation8", "cyclic12-k3"])
 def test_cyclic_core(lib, which):
     C.core_case(lib, which)
 

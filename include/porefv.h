@@ -200,6 +200,9 @@ typedef struct {
   int64_t transport_react_steps;  /* ... accepted steps */
   int64_t transport_react_core_iterations; /* ... block Jacobi iterations of the cyclic core, summed over the steps */
   int64_t transport_react_components; /* ... its k */
+  double transport_adjoint_ms;    /* last pfv_transport_adjoint_multi, all steps (HIP events) */
+  int64_t transport_adjoint_steps; /* ... accepted adjoint steps */
+  int64_t transport_adjoint_core_iterations; /* ... Jacobi iterations of the cyclic core, summed over the steps */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -708,6 +711,46 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
                                        const double* accumulation, const double* source, const double* mobility,
                                        const double* rate, const double* rate_weight, int n_steps, double rtol,
                                        int maxit, double* c, int32_t* steps_done, pfv_solve_info* last);
+
+/* The adjoint of pfv_transport_advance_multi: every gradient of J = sum_{n=1..N} sum_a <g_a^n, c_a^n> through n_steps = N
+ * forward steps (diag(acc_a) + A(q)) c_a^n = acc_a o c_a^{n-1} - b_ref(q, bv_a) + src_a, for the cost of about one more
+ * run.  For n = N .. 1 the call solves S_a^T lambda_a^n = g_a^n + acc_a o lambda_a^{n+1} (lambda^{N+1} = 0) for all
+ * n_comp components by ONE transposed substitution in reverse flow order (csrc/sweep.inc: sweep_row_multi_t): the
+ * levels, the launch plan and the load chain per row are those of the forward sweep.  The cells of a cyclic core are
+ * iterated by Jacobi on their transposed rows until ||residual_core,a|| <= rtol ||rhs_a|| / 2 for every component, or
+ * maxit iterations.  A step is accepted when ||rhs_a - S_a^T lambda_a|| <= rtol ||rhs_a|| holds for every component
+ * (0 <= 0 counts); one host read per step brings the 2 n_comp norms.  There is no per-component fallback.
+ *   loads [N][n_comp][n_obs]: loads[n - 1] = g^n = dJ/dc^n on the observation cells obs_cells (n_obs int32 cell indices
+ * in HOST memory, no repeats; NULL: every cell in order, n_obs must be Nc).  states (may be NULL): c^0 .. c^N as
+ * [N + 1][n_comp][Nc]; one slab is staged per step.  q (Nf, NULL = the flux of the discretization), bc_values
+ * [n_comp][Nf], accumulation [n_comp][Nc], loads and states follow pfv_set_vectors_on_device, as the gradients do.
+ *   Gradients, each may be NULL (not wanted), all accumulated on the device without floating-point atomics:
+ *     grad_c0 [n_comp][Nc]           acc_a o lambda_a^1
+ *     grad_source [n_comp][Nc]       sum_n lambda_a^n
+ *     grad_bc_values [n_comp][Nf]    -sum_n B^T lambda_a^n, B = div (rhs_neu + rhs_dir diag(q)): non-zero on Neumann faces
+ *                                    and on Dirichlet inflow faces only
+ *     grad_accumulation [n_comp][Nc] sum_n lambda_a^n o (c_a^{n-1} - c_a^n)                          (needs states)
+ *     grad_flux [Nf]                 -sum_n sum_a (lambda_a^n[p] - lambda_a^n[m]) cup_a^n[f]         (needs states)
+ * with p / m the cells of cell_faces sign +1 / -1 at f (a missing cell contributes nothing) and cup the value the upwind
+ * rule takes at f: the upstream cell's c^n on interior and outflow faces, bc_values on a Dirichlet inflow face; 0 on a
+ * Neumann face, whose flux is data.  grad_flux is the derivative at a FIXED upstream side: it is the derivative of J
+ * wherever no q_f is exactly zero, and a one-sided one there.
+ *   Requirements as pfv_transport_advance_multi: a one-component discretization on the handle, n_comp in 1 .. 64,
+ * n_comp x Nc and n_comp x Nf below 2^31 (PFV_ERR_UNSUPPORTED); a zero or NaN diagonal A[i,i] + accumulation[a][i] is
+ * PFV_ERR_UNSUPPORTED naming the row and the component.  PFV_ERR_ARGUMENT (the text names the offender): an obs_cells
+ * entry out of range or repeated; grad_accumulation or grad_flux without states; a non-finite value in loads.
+ *   steps_done: the adjoint steps completed.  A refused step returns PFV_ERR_NOT_CONVERGED and writes no gradient.
+ * last (n_comp entries, may be NULL): iterations = 1 for an acyclic flux, else the core iterations of the last step;
+ * rel_residual the measured ||rhs_a - S_a^T lambda_a|| / ||rhs_a||.  The flow order is built if the handle has none
+ * for this flux, whatever preconditioner is selected, and stays; the selection and the flow system are left alone; no
+ * transport system is left behind (pfv_solve asks for an assembly).  pfv_stats: transport_adjoint_* and the sweep_*
+ * fields (sweep_launches: those of one transposed sweep -- the forward sweep's on an acyclic flux). */
+pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, const double* bc_values,
+                                       const double* accumulation, int n_steps, int64_t n_obs, const int32_t* obs_cells,
+                                       const double* loads, const double* states, double rtol, int maxit,
+                                       double* grad_c0, double* grad_source, double* grad_bc_values,
+                                       double* grad_accumulation, double* grad_flux, int32_t* steps_done,
+                                       pfv_solve_info* last);
 
 /* ---- Advection-diffusion step on the device (csrc/advdiff.inc) ---------------------------------------------------
  * One handle carries the transport keyword: its diffusion discretization (pfv_mpfa_discretize or pfv_tpfa_discretize

@@ -349,6 +349,16 @@ struct pfv_ctx_impl {
   // the copy of the state for the core, rhs, the scale g and F = rhs - image; rc_par: ReactPar (w, K) for the kernels
   // that index it at run time; rc_out: 2 k norms, then the status word
   Buf<double> rc_acc, rc_src, rc_bref, rc_x, rc_z, rc_prev, rc_rhs, rc_g, rc_F, rc_par, rc_out;
+  // the adjoint of the k-component step (pfv_transport_adjoint_multi; q, bc and accumulation in mc_q, mc_bc, mc_acc,
+  // mc_acc_i).  tpos_T: position of the transposed partner of every entry of pat_T -- a property of that pattern, valid
+  // while have_tpos_T (dropped wherever pat_T is rebuilt); valT_T: the transposed values of the call's assembly
+  bool have_tpos_T = false;
+  Buf<int32_t> tpos_T, aj_slot, aj_obs;
+  Buf<double> valT_T;
+  // ... the loads [N][k][n_obs] and one slab of states as they came; then interleaved: the two slabs c^n / c^{n+1},
+  // lambda^n / lambda^{n+1}, the core's previous iterate, rhs; the accumulators of grad_source and grad_accumulation
+  // (interleaved), of grad_bc_values (component-major [k][nf]) and of grad_flux [nf]
+  Buf<double> aj_loads, aj_state_in, aj_sA, aj_sB, aj_lam, aj_lam2, aj_prev, aj_r, aj_gsrc, aj_gacc, aj_gbc, aj_gq;
 
   // ---- advection-diffusion (advdiff.inc): S = diag(acc) + div flux_D + w div diag(q) U on pat_A -------------------
   bool have_advdiff = false;         // val[PFV_MAT_ADVDIFF_SYSTEM], adv_diag, adv_rhs hold a system of the discretization

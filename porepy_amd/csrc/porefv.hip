@@ -346,6 +346,7 @@ pfv_status pfv_set_grid(pfv_ctx* h, int nd, int64_t nc, int64_t nf, int64_t nn, 
     h->active.valid = false;
     for (bool& f : h->filled) f = false;
     h->have_q_res = h->have_upw_bc = h->have_upwind = h->have_transport = h->have_pat_T = h->have_upw_cells = false;
+    h->have_tpos_T = false;
     h->have_acc_t = h->have_src_t = false;
     h->transport_zero_diag = -1;
     h->have_advdiff = h->have_adv_bD = h->have_adv_acc = h->have_adv_src = false;
@@ -1800,6 +1801,247 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
   h->stats.transport_react_steps = completed;
   h->stats.transport_react_core_iterations = core_total;
   h->stats.transport_react_components = k;
+  sweep_step_stats(h, n_steps > 0 ? launches : -1, order_ms);
+  return step_status(h, st, err, st2);
+}
+
+// ---- the adjoint of the k-component step: one transposed sweep in reverse flow order per step (sweep.inc) -------------
+// Per step n = N .. 1: one slab of states (when given), the right-hand side g^n + acc o lambda^{n+1} fused with what
+// lambda^{n+1} adds to grad_source and grad_accumulation, the backward-peel levels from last to first, the core level
+// iterated by Jacobi on its transposed rows (a host read every kNlCoreCheck-th iteration), the forward-peel levels, the
+// residual norms of all components and ONE host read, then the two face kernels (grad_bc_values, grad_flux).  After
+// the last step the right-hand-side kernel runs once more without loads: it leaves acc o lambda^1 = grad_c0.
+pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, const double* bc_values,
+                                       const double* accumulation, int n_steps, int64_t n_obs, const int32_t* obs_cells,
+                                       const double* loads, const double* states, double rtol, int maxit,
+                                       double* grad_c0, double* grad_source, double* grad_bc_values,
+                                       double* grad_accumulation, double* grad_flux, int32_t* steps_done,
+                                       pfv_solve_info* last) {
+  if (steps_done) *steps_done = 0;
+  const int k = n_comp;
+  std::unique_ptr<pfv::Timer> tm;
+  bool touched = false;
+  double order_ms = 0.0;
+  const double* d_q = nullptr;
+  size_t nc = 0, nf = 0;
+  pfv_status st = guarded(h, [&] {
+    upwind_supported(h);
+    require(h->have_upwind, "pfv_upwind_discretize first");
+    require(h->upw_ncomp == 1, "the components share one discretization: pfv_upwind_discretize with num_components = 1");
+    require(n_comp >= 1 && n_comp <= 64, "n_comp must lie in 1 .. 64");
+    require(bc_values && accumulation, "bc_values and accumulation are required");
+    require(n_steps >= 0, "bad argument");
+    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
+    require(loads != nullptr || n_steps == 0, "loads is required");
+    require(states || !grad_accumulation, "grad_accumulation needs states (c^0 .. c^N)");
+    require(states || !grad_flux, "grad_flux needs states (c^0 .. c^N)");
+    nc = (size_t)h->nc;
+    nf = (size_t)h->nf;
+    if ((int64_t)nc * k >= (int64_t(1) << 31) || (int64_t)nf * k >= (int64_t(1) << 31))
+      throw Error(PFV_ERR_UNSUPPORTED, "n_comp x cells (faces) beyond int32 indices");
+    if (obs_cells) {
+      require(n_obs >= 0 && n_obs <= (int64_t)nc, "n_obs must lie in 0 .. the number of cells");
+      std::vector<char> seen(nc, 0);
+      for (int64_t m = 0; m < n_obs; ++m) {
+        const int32_t cell = obs_cells[m];
+        if (cell < 0 || (size_t)cell >= nc)
+          throw Error(PFV_ERR_ARGUMENT, "obs_cells[" + std::to_string(m) + "] = " + std::to_string(cell) +
+                                            " is out of range (0 .. " + std::to_string(nc - 1) + ")");
+        if (seen[(size_t)cell])
+          throw Error(PFV_ERR_ARGUMENT, "obs_cells[" + std::to_string(m) + "] = " + std::to_string(cell) + " is repeated");
+        seen[(size_t)cell] = 1;
+      }
+    } else {
+      require(n_obs == (int64_t)nc, "obs_cells == NULL means every cell: n_obs must be the number of cells");
+    }
+    const size_t nl = (size_t)n_steps * k * (size_t)n_obs;
+    if (nl) {
+      vec_in(h, h->aj_loads.ensure(nl), loads, nl);
+      const int64_t bad = nl < (size_t(1) << 31) ? pfv::adjoint_first_nonfinite(*h, (int64_t)nl, h->aj_loads.p) : -1;
+      if (bad >= 0) {
+        const int64_t per = (int64_t)k * n_obs;
+        throw Error(PFV_ERR_ARGUMENT, "loads is not finite at step " + std::to_string(bad / per + 1) + ", component " +
+                                          std::to_string(bad % per / n_obs) + ", observation " +
+                                          std::to_string(bad % n_obs));
+      }
+    }
+    if (q) vec_in(h, h->mc_q.ensure(nf), q, nf);
+    vec_in(h, h->mc_bc.ensure(k * nf), bc_values, k * nf);
+    vec_in(h, h->mc_acc.ensure(k * nc), accumulation, k * nc);
+    d_q = q ? h->mc_q.p : h->upw_q.p;
+    tm = std::make_unique<pfv::Timer>();
+    tm->start(h->stream);
+    // A = div diag(q) U without accumulation, once per call; its transposed values beside it
+    upwind_drop_transport(h, true);
+    touched = true;
+    pfv::upwind_assemble(*h, d_q, h->mc_bc.p, nullptr, nullptr, nullptr);
+    values_changed(h, Windows::drop);
+    pfv::multi_interleave(*h, (int64_t)nc, k, h->mc_acc.p, h->mc_acc_i.ensure(k * nc));
+    const int64_t zd = pfv::upwind_zero_diag_multi(*h, k, h->diag_t.p, h->mc_acc_i.p);
+    if (zd >= 0)
+      throw Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(zd / k) + ", component " +
+                                           std::to_string(zd % k) + " of the transport system (a cell without outflow "
+                                           "and without an accumulation term): the solvers do not apply");
+    const size_t nnz = (size_t)std::max<int64_t>(h->pat_T.nnz, 1);
+    if (!h->have_tpos_T) {
+      pfv::sweep_transpose_positions(*h, h->pat_T, h->tpos_T.ensure(nnz));
+      h->have_tpos_T = true;
+    }
+    pfv::sweep_transpose_values(*h, h->pat_T.nnz, h->tpos_T.p, h->val[PFV_MAT_TRANSPORT_SYSTEM].p, h->valT_T.ensure(nnz));
+    if (obs_cells && n_obs > 0) {
+      be_h2d(h->aj_obs.ensure((size_t)n_obs), obs_cells, sizeof(int32_t) * (size_t)n_obs, h->stream);
+      pfv::be_memset(h->aj_slot.ensure(nc), 0xff, sizeof(int32_t) * nc, h->stream);
+      pfv::adjoint_obs_slots(*h, n_obs, h->aj_obs.p, h->aj_slot.p);
+    } else if (obs_cells) {
+      pfv::be_memset(h->aj_slot.ensure(nc), 0xff, sizeof(int32_t) * nc, h->stream);
+    }
+    for (pfv::Buf<double>* b : {&h->aj_lam, &h->aj_lam2, &h->aj_prev, &h->aj_r}) b->ensure(k * nc);
+    if (states) {
+      h->aj_sA.ensure(k * nc);
+      h->aj_sB.ensure(k * nc);
+      if (!h->vectors_on_device) h->aj_state_in.ensure(k * nc);
+    }
+    if (grad_source) pfv::be_memset(h->aj_gsrc.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
+    if (grad_accumulation) pfv::be_memset(h->aj_gacc.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
+    if (grad_bc_values) pfv::be_memset(h->aj_gbc.ensure(k * nf), 0, sizeof(double) * k * nf, h->stream);
+    if (grad_flux) pfv::be_memset(h->aj_gq.ensure(nf), 0, sizeof(double) * nf, h->stream);
+    h->mc_nrm.ensure(2 * (size_t)k);
+    h->mc_c.ensure(k * nc);
+    transport_order(h, d_q, order_ms);
+  });
+  if (st != PFV_OK) {
+    if (touched) upwind_drop_transport(h, true);  // (A without accumulation: not a system to be solved with)
+    return st;
+  }
+
+  const int32_t* slot = obs_cells ? h->aj_slot.p : nullptr;
+  // slab n of the states, interleaved into `to`
+  auto stage_slab = [&](int n, double* to) {
+    const double* src = states + (size_t)n * k * nc;
+    if (!h->vectors_on_device) {
+      be_h2d(h->aj_state_in.p, src, sizeof(double) * k * nc, h->stream);
+      src = h->aj_state_in.p;
+    }
+    pfv::multi_interleave(*h, (int64_t)nc, k, src, to);
+  };
+  int32_t completed = 0;
+  int64_t core_total = 0, launches = 0;
+  std::vector<pfv_solve_info> info((size_t)k);
+  std::vector<double> hst(2 * (size_t)k);
+  std::string err;
+  bool have_lam = false;  // aj_lam holds lambda^{n+1}
+  for (int n = n_steps; n >= 1 && st == PFV_OK; --n) {
+    pfv_status verdict = PFV_OK;
+    st = guarded(h, [&] {
+      pfv::pfv_ctx_impl& cx = *h;
+      const pfv::Sweep& sw = *cx.sweep;
+      const double* valT = cx.valT_T.p;
+      const double* acc = cx.mc_acc_i.p;
+      double* out = cx.mc_nrm.p;
+      const bool has_core = sw.n_core > 0;
+      const int core = has_core ? sw.core_level : -1;
+      if (states) stage_slab(n, cx.aj_sB.p);  // c^n; aj_sA holds c^{n+1}
+      pfv::adjoint_step_rhs(cx, k, acc, have_lam ? cx.aj_lam.p : nullptr, slot,
+                            cx.aj_loads.p + (size_t)(n - 1) * k * (size_t)n_obs, n_obs, cx.aj_sB.p, cx.aj_sA.p,
+                            grad_source ? cx.aj_gsrc.p : nullptr, grad_accumulation ? cx.aj_gacc.p : nullptr, cx.aj_r.p);
+      double* z = cx.aj_lam2.p;
+      launches = pfv::sweep_apply_multi_t(cx, sw, core + 1, sw.nlev, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, z);
+      int core_it = 0;
+      auto component_info = [&](int it) {  // from hst: (r_a, r_a), (residual_a, residual_a)
+        for (int a = 0; a < k; ++a) {
+          const double bb = hst[(size_t)a], rr = hst[(size_t)k + a];
+          info[(size_t)a] = pfv_solve_info{};
+          info[(size_t)a].iterations = it;
+          info[(size_t)a].rel_residual = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
+        }
+      };
+      if (has_core) {
+        pfv::sweep_core_zero(cx, sw, k, z);
+        const CoreRun run = core_iterate(h, maxit, out, hst, [&] {
+          pfv::sweep_core_copy(cx, sw, k, z, cx.aj_prev.p);
+          pfv::sweep_core_multi_t(cx, sw, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, cx.aj_prev.p, z);
+        }, [&] {
+          pfv::sweep_core_norms_multi_t(cx, sw, cx.pat_T, valT, acc, k, cx.aj_r.p, z, out);
+        }, [&] {
+          bool settled = true;
+          for (int a = 0; a < k; ++a) settled = settled && hst[(size_t)k + a] <= 0.25 * rtol * rtol * hst[(size_t)a];
+          return settled;
+        });
+        core_it = run.iterations;
+        core_total += core_it;
+        launches += 2;
+        if (!run.settled) {  // (what the forward-peel levels would compute from this core is not judged)
+          component_info(core_it);
+          verdict = PFV_ERR_NOT_CONVERGED;
+          cx.err = "adjoint step " + std::to_string(n) + ": the cyclic core of " + std::to_string(sw.n_core) +
+                   " cells did not settle in " + std::to_string(core_it) + " iterations";
+          return;
+        }
+        launches += pfv::sweep_apply_multi_t(cx, sw, 0, core, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, z);
+      }
+      pfv::sweep_residual_norms_multi(cx, cx.pat_T, valT, acc, k, cx.aj_r.p, z, out);  // (valT: the image under S^T)
+      be_d2h(hst.data(), out, sizeof(double) * hst.size(), cx.stream);
+      component_info(has_core ? core_it : 1);
+      int bad = -1;  // the first component whose check fails
+      for (int a = k - 1; a >= 0; --a) {
+        info[(size_t)a].converged = hst[(size_t)k + a] <= rtol * rtol * hst[(size_t)a] ? 1 : 0;  // (0 <= 0 counts)
+        if (!info[(size_t)a].converged) bad = a;
+      }
+      if (bad >= 0) {
+        verdict = PFV_ERR_NOT_CONVERGED;
+        cx.err = "adjoint step " + std::to_string(n) + ": relative residual " +
+                 std::to_string(info[(size_t)bad].rel_residual) + " of component " + std::to_string(bad) +
+                 " after the transposed sweep (a flux that contradicts the discretization's?)";
+        return;
+      }
+      if (grad_bc_values) pfv::adjoint_grad_bc(cx, k, d_q, z, cx.aj_gbc.p);
+      if (grad_flux) pfv::adjoint_grad_flux(cx, k, cx.mc_bc.p, z, cx.aj_sB.p, cx.aj_gq.p);
+      cx.aj_lam.swap(cx.aj_lam2);
+      cx.aj_sA.swap(cx.aj_sB);
+      have_lam = true;
+      ++completed;
+    });
+    if (st == PFV_OK) st = verdict;
+  }
+  if (st != PFV_OK) err = h->err;
+  double ms = 0.0;
+  const pfv_status st2 = guarded(h, [&] {
+    pfv::pfv_ctx_impl& cx = *h;
+    if (st == PFV_OK) {
+      // lambda^1 into the cell gradients; the right-hand side it leaves is acc o lambda^1
+      if (have_lam && grad_accumulation) stage_slab(0, cx.aj_sB.p);  // c^0
+      if (have_lam)
+        pfv::adjoint_step_rhs(cx, k, cx.mc_acc_i.p, cx.aj_lam.p, nullptr, nullptr, 0, cx.aj_sB.p, cx.aj_sA.p,
+                              grad_source ? cx.aj_gsrc.p : nullptr, grad_accumulation ? cx.aj_gacc.p : nullptr,
+                              cx.aj_r.p);
+      else
+        pfv::be_memset(cx.aj_r.p, 0, sizeof(double) * k * nc, cx.stream);
+    }
+    ms = tm->stop(cx.stream);
+    tm.reset();
+    if (st == PFV_OK) {
+      auto cells_out = [&](double* to, const double* from) {
+        pfv::multi_deinterleave(cx, (int64_t)nc, k, from, cx.mc_c.p);
+        vec_out(h, to, cx.mc_c.p, k * nc);
+      };
+      if (grad_c0) cells_out(grad_c0, cx.aj_r.p);
+      if (grad_source) cells_out(grad_source, cx.aj_gsrc.p);
+      if (grad_accumulation) cells_out(grad_accumulation, cx.aj_gacc.p);
+      if (grad_bc_values) vec_out(h, grad_bc_values, cx.aj_gbc.p, k * nf);
+      if (grad_flux) vec_out(h, grad_flux, cx.aj_gq.p, nf);
+    }
+    pfv::be_sync(cx.stream);
+    upwind_drop_transport(h, true);
+  });
+  if (steps_done) *steps_done = completed;
+  if (last)
+    for (int a = 0; a < k; ++a) {
+      last[a] = info[(size_t)a];
+      if (completed > 0) last[a].solve_ms = ms / completed;
+    }
+  h->stats.transport_adjoint_ms = ms;
+  h->stats.transport_adjoint_steps = completed;
+  h->stats.transport_adjoint_core_iterations = core_total;
   sweep_step_stats(h, n_steps > 0 ? launches : -1, order_ms);
   return step_status(h, st, err, st2);
 }

@@ -261,8 +261,17 @@ PFV_FN void sweep_row(int32_t i, const int32_t* ip, const int32_t* ix, const dou
 struct OnePerRow {
   PFV_FN constexpr operator int() const { return 1; }
 };
-template <class Items, class Body>
-static void sweep_levels(pfv_ctx_impl& c, const Sweep& sw, bool permuted, int l0, int l1, Items items, Body body) {
+// The direction the levels are taken in: Ascending is the substitution with S, Descending the one with its transpose
+// (sweep_row_multi_t).  A compile-time tag: the loop over the levels of a run folds to one direction per instantiation.
+struct Ascending {
+  static constexpr bool reverse = false;
+};
+struct Descending {
+  static constexpr bool reverse = true;
+};
+template <class Items, class Body, class Dir = Ascending>
+static void sweep_levels(pfv_ctx_impl& c, const Sweep& sw, bool permuted, int l0, int l1, Items items, Body body,
+                         Dir = Dir{}) {
   const int32_t* ord = sw.ord(permuted);
   if (l1 - l0 == 1) {
     const int32_t a0 = sw.h_lptr[(size_t)l0], m = sw.h_lptr[(size_t)l1] - a0;
@@ -275,7 +284,7 @@ static void sweep_levels(pfv_ctx_impl& c, const Sweep& sw, bool permuted, int l0
     const int32_t* lp = sw.lptr;
     block_for<256>(c.stream, 1, 0, PFV_LAMBDA(const WaveCtx& w) {
       const int k = items;
-      for (int l = l0; l < l1; ++l) {
+      for (int l = Dir::reverse ? l1 - 1 : l0; Dir::reverse ? l >= l0 : l < l1; l += Dir::reverse ? -1 : 1) {
         const int32_t a0 = lp[l], m = lp[l + 1] - a0;
         PFV_LANES(t, m * k) {
           const int32_t i = ord[a0 + t / k];
@@ -288,11 +297,14 @@ static void sweep_levels(pfv_ctx_impl& c, const Sweep& sw, bool permuted, int l0
 }
 
 // The segments of the launch plan cut to the levels [from, to) -- a run is cut where the core level, which is iterated
-// on its own, falls into it --, each handed to levels(l0, l1).  Returns the launches.
-template <class Levels>
-static int sweep_plan_range(const Sweep& sw, int from, int to, Levels levels) {
+// on its own, falls into it --, each handed to levels(l0, l1); Descending: the segments from last to first.  Returns
+// the launches.
+template <class Levels, class Dir = Ascending>
+static int sweep_plan_range(const Sweep& sw, int from, int to, Levels levels, Dir = Dir{}) {
   int launches = 0;
-  for (const Sweep::Seg& g : sw.plan) {
+  const size_t ns = sw.plan.size();
+  for (size_t n = 0; n < ns; ++n) {
+    const Sweep::Seg& g = sw.plan[Dir::reverse ? ns - 1 - n : n];
     const int l0 = std::max(g.l0, from), l1 = std::min(g.l1, to);
     if (l0 >= l1) continue;
     levels(l0, l1);
@@ -1144,6 +1156,214 @@ static void upwind_bref_react(pfv_ctx_impl& c, int k, const double* d_q, const d
       b = wa * b;
     }
     bref[t] = b;
+  });
+}
+
+// ---- the adjoint of the k-component step (pfv_transport_adjoint_multi): S_a^T lambda_a = r_a.  S_a = diag(acc_a) + A is
+// triangular in flow order, S_a^T in reverse flow order: one substitution over the same levels from last to first.
+//   tpos    the pattern of A (a cell and its face neighbours) is structurally symmetric: tpos[e] is the position of
+//           (j, i) for the entry e = (i, j).  A property of the pattern, kept with it.
+//   valT    valT[e] = val[tpos[e]], once per assembly: row i of valT is column i of A on the pattern of row i, so the
+//           transposed row has the load chain of sweep_row_multi -- no search in a level, no atomics.
+// first entry without a partner in tpos' status word (0x7f7f7f7f: none)
+static void sweep_transpose_positions(pfv_ctx_impl& c, const CsrPattern& P, int32_t* tpos) {
+  stream_t s = c.stream;
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  int32_t* st = c.status.ensure(16);
+  be_memset(st, 0x7f, sizeof(int32_t), s);
+  parallel_for(s, P.nrows, PFV_LAMBDA(int64_t i) {
+    for (int e = ip[i]; e < ip[i + 1]; ++e) {
+      const int32_t j = ix[e];
+      const int b0 = ip[j], len = ip[j + 1] - b0;
+      const int pos = lower_bound_idx<int32_t>(ix + b0, len, (int32_t)i);
+      const bool found = pos < len && ix[b0 + pos] == (int32_t)i;
+      tpos[e] = found ? b0 + pos : e;  // (an address inside the values in any case)
+      if (!found) atomic_min_i32(st, e);
+    }
+  });
+  const int32_t bad = read_scalar<int32_t>(s, st);
+  if (bad != 0x7f7f7f7f)
+    throw Error(PFV_ERR_UNSUPPORTED, "the pattern of the transport system is not structurally symmetric (entry " +
+                                         std::to_string(bad) + " has no transposed partner)");
+}
+
+static void sweep_transpose_values(pfv_ctx_impl& c, int64_t nnz, const int32_t* tpos, const double* val, double* valT) {
+  parallel_for(c.stream, nnz, PFV_LAMBDA(int64_t e) { valT[e] = val[tpos[e]]; });
+}
+
+// one (row, component) of the transposed substitution: the cells downstream of i have the higher levels
+PFV_FN void sweep_row_multi_t(int32_t i, int a, int k, const int32_t* ip, const int32_t* ix, const double* valT,
+                              const double* diag, const double* acc, const int32_t* lev, const double* r, double* z) {
+  const int32_t li = lev[i];
+  double sum = 0.0;
+  for (int e = ip[i]; e < ip[i + 1]; ++e) {
+    const int32_t j = ix[e];
+    if (lev[j] > li) sum += valT[e] * z[(int64_t)j * k + a];
+  }
+  const int64_t p = (int64_t)i * k + a;
+  z[p] = (r[p] - sum) / (diag[i] + acc[p]);
+}
+
+// ... of the core level: the in-core neighbours from z_prev, the previous iterate (Jacobi, independent of the scheduling)
+PFV_FN void sweep_row_multi_t_core(int32_t i, int a, int k, const int32_t* ip, const int32_t* ix, const double* valT,
+                                   const double* diag, const double* acc, const int32_t* lev, const double* r,
+                                   const double* z_prev, double* z) {
+  const int32_t li = lev[i];
+  double sum = 0.0;
+  for (int e = ip[i]; e < ip[i + 1]; ++e) {
+    const int32_t j = ix[e];
+    const int32_t lj = lev[j];
+    if (lj > li) sum += valT[e] * z[(int64_t)j * k + a];
+    else if (lj == li && j != i) sum += valT[e] * z_prev[(int64_t)j * k + a];
+  }
+  const int64_t p = (int64_t)i * k + a;
+  z[p] = (r[p] - sum) / (diag[i] + acc[p]);
+}
+
+// the launch plan's levels in [from, to), from last to first.  Returns the launches.
+static int sweep_apply_multi_t(pfv_ctx_impl& c, const Sweep& sw, int from, int to, const CsrPattern& P,
+                               const double* valT, const double* diag, const double* acc, int k, const double* in,
+                               double* out) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* lev = sw.lev(false);
+  return sweep_plan_range(sw, from, to, [&](int l0, int l1) {
+    sweep_levels(c, sw, false, l0, l1, k,
+                 PFV_LAMBDA(int32_t i, int a) { sweep_row_multi_t(i, a, k, ip, ix, valT, diag, acc, lev, in, out); },
+                 Descending{});
+  }, Descending{});
+}
+
+// one Jacobi iteration of the core level on its transposed rows
+static void sweep_core_multi_t(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* valT,
+                               const double* diag, const double* acc, int k, const double* in, const double* prev,
+                               double* out) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* lev = sw.lev(false);
+  sweep_core_rows(c, sw, k, PFV_LAMBDA(int32_t i, int a, int64_t) {
+    sweep_row_multi_t_core(i, a, k, ip, ix, valT, diag, acc, lev, in, prev, out);
+  });
+}
+
+// to <- 0 on the core rows of an interleaved vector (the start of the core's iteration)
+static void sweep_core_zero(pfv_ctx_impl& c, const Sweep& sw, int k, double* to) {
+  sweep_core_rows(c, sw, k, PFV_LAMBDA(int32_t i, int a, int64_t) { to[(int64_t)i * k + a] = 0.0; });
+}
+
+// The core's stop test: out[a] = (r_a, r_a) over all rows, out[k + a] = the squared residual of the core rows, the
+// image taken from the entries of the row's own level and above (the levels below have no value yet; their entries
+// are the stored zeros of the upstream side).
+static void sweep_core_norms_multi_t(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* valT,
+                                     const double* acc, int k, const double* r, const double* x, double* out) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* lev = sw.lev(false);
+  const int32_t core = sw.core_level;
+  sweep_norms_pairs(c, P.nrows, k, out, PFV_LAMBDA(int64_t i, int a) {
+    const int64_t p = i * k + a;
+    const double ri = r[p];
+    if (lev[i] != core) return NormPair{ri, 0.0};
+    double t = 0.0;
+    for (int e = ip[i]; e < ip[i + 1]; ++e) {
+      const int32_t j = ix[e];
+      if (lev[j] >= core) t += valT[e] * x[(int64_t)j * k + a];
+    }
+    t += acc[p] * x[p];
+    return NormPair{ri, ri - t};
+  });
+}
+
+// The right-hand side of adjoint step n, r = g^n + acc o lambda^{n+1}, fused with what lambda^{n+1} adds to the
+// gradients that live on the cells: grad_source += lambda^{n+1}, grad_accumulation += lambda^{n+1} o (c^n - c^{n+1}).
+// lam == nullptr (the first step): r = g^n.  loads == nullptr (after the last step): r = acc o lambda^1 = grad_c0.
+// loads is [k][n_obs]; slot[i] is the position of cell i among the observation cells (-1: not observed; slot ==
+// nullptr: every cell, in order).  Interleaved vectors; c_n, c_np1 only with gacc.
+static void adjoint_step_rhs(pfv_ctx_impl& c, int k, const double* acc, const double* lam, const int32_t* slot,
+                             const double* loads, int64_t n_obs, const double* c_n, const double* c_np1, double* gsrc,
+                             double* gacc, double* r) {
+  parallel_for(c.stream, c.nc * k, PFV_LAMBDA(int64_t t) {
+    const int64_t i = t / k, a = t % k;
+    double g = 0.0;
+    if (loads) {
+      const int64_t m = slot ? (int64_t)slot[i] : i;
+      if (m >= 0) g = loads[a * n_obs + m];
+    }
+    double v = g;
+    if (lam) {
+      const double l = lam[t];
+      v = g + acc[t] * l;
+      if (gsrc) gsrc[t] += l;
+      if (gacc) gacc[t] += l * (c_n[t] - c_np1[t]);
+    }
+    r[t] = v;
+  });
+}
+
+// slot[obs[m]] = m (slot preset to -1)
+static void adjoint_obs_slots(pfv_ctx_impl& c, int64_t n_obs, const int32_t* obs, int32_t* slot) {
+  parallel_for(c.stream, n_obs, PFV_LAMBDA(int64_t m) { slot[obs[m]] = (int32_t)m; });
+}
+
+// first non-finite entry of v[0 .. n), -1: none
+static int64_t adjoint_first_nonfinite(pfv_ctx_impl& c, int64_t n, const double* v) {
+  stream_t s = c.stream;
+  int32_t* st = c.status.ensure(16);
+  be_memset(st, 0x7f, sizeof(int32_t), s);
+  parallel_for(s, n, PFV_LAMBDA(int64_t t) {
+    if (!(fabs(v[t]) <= 1.79769313486231570e308)) atomic_min_i32(st, (int32_t)t);
+  });
+  const int32_t bad = read_scalar<int32_t>(s, st);
+  return bad == 0x7f7f7f7f ? -1 : (int64_t)bad;
+}
+
+// grad_bc_values[a][f] -= sum_i B[i, f] lambda[i, a], B = div (rhs_neu + rhs_dir diag(q)): the transpose of
+// upwind_bref_multi.  One work item per (face, component); a face reads the cells on its two sides (a boundary face
+// has one).  gbc is component-major [k][nf], lam interleaved.
+static void adjoint_grad_bc(pfv_ctx_impl& c, int k, const double* d_q, const double* lam, double* gbc) {
+  const int64_t nf = c.nf;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* cnt = c.upw_cnt;
+  const int32_t* side = c.upw_side;
+  parallel_for(c.stream, nf * k, PFV_LAMBDA(int64_t t) {
+    const int64_t f = t / k, a = t % k;
+    const unsigned cl = cls[f];
+    if (!(cl & (UPW_NEU | UPW_DIRIN))) return;
+    double m = 0.0;
+    if (cl & UPW_NEU) m = (double)(cnt[f] - cnt[nf + f]);
+    if (cl & UPW_DIRIN) m += 1.0 * d_q[f];
+    const int32_t cp = side[f], cm = side[nf + f];
+    double s = 0.0;
+    if (cp >= 0) s += m * lam[(int64_t)cp * k + a];
+    if (cm >= 0) s -= m * lam[(int64_t)cm * k + a];
+    gbc[a * nf + f] -= s;
+  });
+}
+
+// grad_flux[f] -= sum_a (lambda[p, a] - lambda[m, a]) cup[a, f] with p / m the cells on the +1 / -1 side of f and cup the
+// value the upwind rule takes at f: the upstream cell's c^n (interior and outflow faces), the boundary value (Dirichlet
+// inflow); a Neumann face gives 0.  One work item per face, the components summed in order.  bc is component-major.
+static void adjoint_grad_flux(pfv_ctx_impl& c, int k, const double* bc, const double* lam, const double* c_n,
+                              double* gq) {
+  const int64_t nf = c.nf;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* up = c.upw_up;
+  const int32_t* side = c.upw_side;
+  parallel_for(c.stream, nf, PFV_LAMBDA(int64_t f) {
+    const unsigned cl = cls[f];
+    if (!(cl & (UPW_KEPT | UPW_DIRIN))) return;
+    const int32_t cp = side[f], cm = side[nf + f];
+    const int32_t u = up[f];
+    double s = 0.0;
+    for (int a = 0; a < k; ++a) {
+      double d = 0.0;
+      if (cp >= 0) d = lam[(int64_t)cp * k + a];
+      if (cm >= 0) d -= lam[(int64_t)cm * k + a];
+      const double cup = (cl & UPW_KEPT) ? c_n[(int64_t)u * k + a] : bc[a * nf + f];
+      s += d * cup;
+    }
+    gq[f] -= s;
   });
 }
 

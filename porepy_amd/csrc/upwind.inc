@@ -60,6 +60,7 @@ static void upwind_system_pattern(pfv_ctx_impl& c) {
   int32_t* ln = len.ensure(nc + 1);
   ptr64.ensure(nc + 1);
   CsrPattern& PT = c.pat_T;
+  c.have_tpos_T = false;  // (the transposed positions belong to the pattern that is replaced here)
   // Rows come out ascending by selection -- the smallest column above the last one written, over the cell and the
   // <= 2 cells of each of its faces -- so that no per-thread list (scratch memory) is needed: a cell has few faces.
   for (int pass = 0; pass < 2; ++pass) {

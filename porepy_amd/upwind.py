@@ -269,6 +269,64 @@ class Upwind:
                 raise ValueError(e.message) from None
             raise
 
+    def adjoint_components(self, sd, data: dict, n_steps: int, accumulation, loads, obs_cells=None, states=None,
+                           bc_values=None, want=("c0", "source", "bc_values"), rtol: float = 1e-12, maxit: int = 500,
+                           raise_on_fail: bool = True):
+        """The adjoint of ``advance_components``: the gradients of
+        ``J = sum_{n=1..N} sum_a <loads[n-1, a], c_a^n[obs_cells]>`` through ``n_steps`` = N forward steps, for the
+        cost of about one more run -- what a calibration of porosity, retardation, inflow concentrations, sources or
+        the flux itself against breakthrough curves needs.  Per step, backwards in time, all k components are ONE
+        transposed substitution in reverse flow order (``S_a^T lambda_a^n = g_a^n + acc_a o lambda_a^{n+1}``): the
+        levels and the launches are those of the forward sweep.
+
+        ``accumulation``: (Nc,) or (k, Nc) with k taken from ``loads``; ``loads``: (N, k, n_obs), dJ/dc^n on the
+        observation cells; ``obs_cells``: n_obs cell indices without repeats, None = every cell; ``bc_values``: None
+        (the keyword's), (Nf,) or (k, Nf); ``states``: (N + 1, k, Nc), c^0 .. c^N of the forward run, or None.
+        ``want`` names the gradients:
+
+        - ``"c0"`` (k, Nc): ``acc_a o lambda_a^1``;  ``"source"`` (k, Nc): ``sum_n lambda_a^n``;
+        - ``"bc_values"`` (k, Nf): non-zero on Neumann faces and on Dirichlet inflow faces only;
+        - ``"accumulation"`` (k, Nc): ``sum_n lambda_a^n o (c_a^{n-1} - c_a^n)`` -- needs ``states``;
+        - ``"flux"`` (Nf,): ``-sum_n sum_a (lambda_a^n[p] - lambda_a^n[m]) cup_a^n`` with p / m the cells of
+          ``cell_faces`` sign +1 / -1 and ``cup`` the upwind value at the face -- needs ``states``.  It is the
+          derivative at a FIXED upstream side: valid wherever no ``q_f`` is exactly zero (a face whose flux changes sign
+          has a kink there), zero on Neumann faces, whose flux is data.  The chain on to permeability goes through
+          ``Mpfa.ad_flux_system`` and is the caller's to compose.
+
+        The cells of a cyclic core are iterated by Jacobi on their transposed rows, at most ``maxit`` times per step.
+        Returns (grads, info): a dict by the names in ``want``, and info["steps_done"], "converged" and the
+        per-component lists "iterations" (1, or the core iterations of the last step) and "rel_residual".  Afterwards
+        the handle holds no assembled transport system; the flow order stays."""
+        pd = data[PARAMETERS][self.keyword]
+        nc, nf = sd.num_cells, sd.num_faces
+        loads = np.asarray(loads, dtype=np.float64)
+        if loads.ndim != 3 or loads.shape[0] != int(n_steps):
+            raise ValueError(f"loads must have shape ({int(n_steps)}, k, n_obs), not {loads.shape}")
+        k = loads.shape[1]
+        if not 1 <= k <= 64:
+            raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (loads has shape {loads.shape})")
+
+        def per_component(name, a, n):
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape == (n,):
+                return np.broadcast_to(a, (k, n))
+            if a.shape != (k, n):
+                raise ValueError(f"{name} must have shape ({n},) or ({k}, {n}), not {a.shape}")
+            return a
+
+        if accumulation is None:
+            raise ValueError("accumulation is required")
+        acc = per_component("accumulation", accumulation, nc)
+        bv = per_component("bc_values", pd["bc_values"] if bc_values is None else bc_values, nf)
+        try:
+            return self.context(sd).transport_adjoint_multi(n_steps, acc, bv, loads, obs_cells=obs_cells, states=states,
+                                                            q=self._flux(sd, pd), want=want, rtol=rtol, maxit=maxit,
+                                                            raise_on_fail=raise_on_fail)
+        except _lib.PorefvError as e:
+            if e.status == 4:
+                raise ValueError(e.message) from None
+            raise
+
     def advance_saturation(self, sd, data: dict, s0, n_steps: int, accumulation, flux_function, source=None, sink=None,
                            rtol: float = 1e-12, maxit: int = 500, raise_on_fail: bool = True):
         """``n_steps`` implicit upwind steps of a saturation that moves with ``q f(s)`` -- the transport step of

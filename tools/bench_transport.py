@@ -7,7 +7,7 @@ Device times are HIP-event times from pfv_stats; the host times are wall clock. 
 not a test: no thresholds.
 
     python tools/bench_transport.py [--n-side 69] [--steps 20] [--no-host] [--precond sweep] [--components 8]
-                                    [--saturation [--components 4]] [--reactive]
+                                    [--saturation [--components 4]] [--reactive] [--adjoint]
 
 --precond sweep: after the Jacobi-BiCGStab steps, the same steps from the same state with the flow-ordered sweep
 (PFV_PRECOND_SWEEP) -- order-build ms, levels, core cells, launches per sweep, ms per step -- and again with one launch
@@ -32,6 +32,12 @@ precond="sweep"): ms per step of the three (best and median of --reps, the first
 (transport_advance_multi with precond="sweep") and the same number of reactive k = 4 steps (transport_advance_react):
 the chain 0 -> 1 -> 2 plus the exchange 0 <-> 3 with component 3 immobile, the reaction term weighted by the pore
 volume.  ms per step of both from pfv_stats (best and median of --reps, the first repeat dropped), levels, launches.
+
+--adjoint: in the same process and on the same flux, alternating in one loop, the forward k = 4 sweep step
+(transport_advance_multi with precond="sweep") and the adjoint k = 4 step (transport_adjoint_multi) on 16 observation
+cells -- once with the three gradients that need no states (c0, source, bc_values) and once with all five, which stages
+one slab of states per step: ms per step of the three from pfv_stats (best and median of --reps, the first repeat
+dropped), the launches of the sweep and the other kernels per step for both directions.
 """
 from __future__ import annotations
 
@@ -64,6 +70,8 @@ def main():
                     help="linear sweep steps against Corey saturation steps on the same flux and state")
     ap.add_argument("--reactive", action="store_true",
                     help="the linear k = 4 sweep steps against k = 4 coupled (reactive) steps on the same flux and state")
+    ap.add_argument("--adjoint", action="store_true",
+                    help="the forward k = 4 sweep step against the adjoint k = 4 step on the same flux")
     ap.add_argument("--emulation", action="store_true", help="run on the host-emulation build (plumbing check)")
     a = ap.parse_args()
     lib = None
@@ -260,6 +268,51 @@ def main():
             entry["error"] = e.message
         out["reactive"] = entry
         ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the reactive call leaves no system behind)
+    if a.adjoint:
+        kc, n_obs = 4, 16
+        acc_k = np.array([(1.0 + 0.5 * j) * acc for j in range(kc)])
+        bv_k = np.array([tbv * (j + 1) / kc for j in range(kc)])
+        states = np.empty((a.steps + 1, kc, nc))
+        states[0] = rng.random((kc, nc))
+        obs = np.sort(rng.permutation(nc)[:n_obs])
+        loads = rng.standard_normal((a.steps, kc, n_obs))
+        entry = {"k": kc, "observation_cells": n_obs}
+        try:
+            for s_ in range(a.steps):  # the states of the forward run, one step at a time
+                states[s_ + 1], minfo = ctx.transport_advance_multi(states[s_], 1, acc_k, bv_k, rtol=1e-10, precond="sweep")
+            fwd_ms, adj3_ms, adj5_ms = [], [], []
+            for _ in range(a.reps + 1):  # (the first repeat warms up: dropped)
+                cm, minfo = ctx.transport_advance_multi(states[0], a.steps, acc_k, bv_k, rtol=1e-10, raise_on_fail=False,
+                                                        precond="sweep")
+                multi = ctx.stats()
+                fwd_ms.append(multi["transport_advance_ms"] / max(a.steps, 1))
+                g3, i3 = ctx.transport_adjoint_multi(a.steps, acc_k, bv_k, loads, obs_cells=obs, rtol=1e-10,
+                                                     raise_on_fail=False)
+                adj3_ms.append(ctx.stats()["transport_adjoint_ms"] / max(a.steps, 1))
+                g5, i5 = ctx.transport_adjoint_multi(a.steps, acc_k, bv_k, loads, obs_cells=obs, states=states,
+                                                     want=ctx.ADJOINT_GRADIENTS, rtol=1e-10, raise_on_fail=False)
+                adj = ctx.stats()
+                adj5_ms.append(adj["transport_adjoint_ms"] / max(a.steps, 1))
+            J = float(np.sum(loads * states[1:][:, :, obs]))
+            lin = float(np.sum(g5["c0"] * states[0]) + np.sum(g5["bc_values"] * bv_k))
+            entry.update({
+                "steps_done": i5["steps_done"], "forward_steps_done": minfo["steps_done"],
+                "forward_ms_per_step": (min(fwd_ms[1:]), float(np.median(fwd_ms[1:]))),
+                "adjoint_ms_per_step_c0_source_bc": (min(adj3_ms[1:]), float(np.median(adj3_ms[1:]))),
+                "adjoint_ms_per_step_all_five": (min(adj5_ms[1:]), float(np.median(adj5_ms[1:]))),
+                "levels": adj["sweep_levels"], "core_cells": adj["sweep_core_cells"],
+                # per step: the sweep, then forward rhs + 2 norms kernels; adjoint rhs + 2 norms kernels (+ one
+                # interleave of the slab, grad_bc_values and grad_flux with all five)
+                "forward_launches_per_step": {"sweep": multi["sweep_launches"], "other": 3},
+                "adjoint_launches_per_step": {"sweep": adj["sweep_launches"], "other_c0_source_bc": 4, "other_all_five": 6},
+                "core_iterations": adj["transport_adjoint_core_iterations"],
+                "max_rel_residual_last_step": max(i5["rel_residual"]),
+                "identity_J_minus_products_relative": abs(J - lin) / max(abs(J), 1e-300),
+                "c0_bits_equal_between_the_two_adjoint_calls": bool(g3["c0"].tobytes() == g5["c0"].tobytes())})
+        except pa.PorefvError as e:
+            entry["error"] = e.message
+        out["adjoint"] = entry
+        ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the adjoint call leaves no system behind)
     # bytes each kernel has to move at least ("Upwind advection"): the fraction of a stream rate follows
     nnz_flux = ctx.matrix_info(_lib.MAT_FLUX)[2]
     nnz_bound = ctx.matrix_info(_lib.MAT_BOUND_FLUX)[2]

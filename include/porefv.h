@@ -203,6 +203,11 @@ typedef struct {
   double transport_adjoint_ms;    /* last pfv_transport_adjoint_multi, all steps (HIP events) */
   int64_t transport_adjoint_steps; /* ... accepted adjoint steps */
   int64_t transport_adjoint_core_iterations; /* ... Jacobi iterations of the cyclic core, summed over the steps */
+  int64_t amg_ap_nnz;             /* entries of AP = A_s P of the last AMG setup: the matrix the post-smoothing step of the
+                                     cycle's finest level reads in place of a second sweep over the level's operator
+                                     (PFV_AMG_POST_AP, default on; its build is part of amg_setup_ms).  0: that level takes the
+                                     prolongation and the smoothing product as two launches (block systems, sharded solves,
+                                     PFV_AMG_FP32=0, a finest level small enough for the fused restriction) */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);

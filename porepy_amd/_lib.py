@@ -91,7 +91,7 @@ class Stats(C.Structure):
                 ("transport_react_ms", C.c_double), ("transport_react_steps", C.c_int64),
                 ("transport_react_core_iterations", C.c_int64), ("transport_react_components", C.c_int64),
                 ("transport_adjoint_ms", C.c_double), ("transport_adjoint_steps", C.c_int64),
-                ("transport_adjoint_core_iterations", C.c_int64)]
+                ("transport_adjoint_core_iterations", C.c_int64), ("amg_ap_nnz", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

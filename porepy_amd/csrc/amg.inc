@@ -92,6 +92,7 @@ struct AmgSwitches {
   // how the work is launched: PFV_AMG_GALERKIN_BATCHED, _FILTER_UNROLL, _DENSE_LDS
   bool galerkin_batched = true, filter_unroll = true, dense_lds = true;
   int64_t gather_rows = kAmgGatherRowsDefault;  // PFV_AMG_GATHER_ROWS, >= 1
+  bool post_ap = true;               // PFV_AMG_POST_AP: finest post-smoothing through A_s P (amg_build_ap / amg_post_ap)
 };
 
 static AmgSwitches amg_read_switches(int bs) {
@@ -138,6 +139,7 @@ static AmgSwitches amg_read_switches(int bs) {
   w.filter_unroll = on("PFV_AMG_FILTER_UNROLL", 1);
   w.dense_lds = on("PFV_AMG_DENSE_LDS", 1);
   w.gather_rows = std::max<int64_t>(1, env_int("PFV_AMG_GATHER_ROWS", (int)kAmgGatherRowsDefault));
+  w.post_ap = on("PFV_AMG_POST_AP", 1);
   return w;
 }
 
@@ -306,6 +308,12 @@ struct Amg {
                            // and first smoothing step in one product, its correction folded into the parent's prolongation
   bool fp32 = true;    // cycle products read single-precision matrix values (vectors stay double)
   double setup_ms = 0.0, op_complexity = 0.0;
+  // AP = A_s P of level 0 (amg_build_ap): compact CSR, n rows x coarse cells of level 0, values double, columns ascending
+  bool ap_ok = false;
+  int64_t ap_nnz = 0;
+  Buf<int32_t> ap_ptr, ap_col, ap_len;
+  Buf<int64_t> ap_pos;
+  Buf<double> ap_val;
   const CsrPattern* sysP = nullptr;  // the matrix the last setup was given (before the filter; pfv_amg_level reads it)
   const double* sysV = nullptr;
 };
@@ -1392,6 +1400,239 @@ static int amg_coarsen_level(pfv_ctx_impl& c, Amg& amg, size_t l, bool reuse) {
   return slot;
 }
 
+// AP = A_s P of level 0, for the post-smoothing step of the cycle (amg_post_ap): with x0 the pre-smoothed iterate and
+// t = A_s x0 still in memory, A_s (x0 + alpha P xs) = t + alpha (A_s P) xs -- the second sweep over A_s becomes a sweep
+// over AP, whose row r holds one entry per distinct aggregate among the columns of row r of A_s.
+// Values: the single-precision values the cycle's products read, summed per aggregate in double in entry order (a sum
+// of a few dozen floats is exact in double), so the operator differs from the two-launch form by the order of double
+// additions only.  Deterministic: keys ranked, every run summed in entry order, columns ascending.
+// Two kernels and a scan, no host read: rows are formed in the slots [fp[r], fp[r + 1]) of the Galerkin scratch (a row
+// of AP is never longer than its row of A_s; the scratch has that size since the first product of this level), their
+// lengths are scanned, and the rows are packed -- the slots use a third of their lines' bytes, and the post-smoothing
+// kernel, which runs twice per Krylov iteration, would fetch them all.
+// Scalar, non-distributed hierarchies with a single-precision copy whose level 0 takes the two-launch restriction.
+// A failed allocation leaves the cycle on its two-launch form.
+constexpr int kApKeys = 128;  // entries of a row ranked in LDS (longer rows: one lane inserts them one by one)
+constexpr int kApChunk = 8;   // ... entries per unrolled trip of the ranking loops
+static void amg_build_ap(pfv_ctx_impl& c, Amg& amg) {
+  stream_t s = c.stream;
+  amg.ap_ok = false;
+  amg.ap_nnz = 0;
+  AmgLevel& L = *amg.lev[0];
+  if (!amg.sw.post_ap || amg.bs != 1 || amg.dist || amg.no_filter || amg.finest_cells_parent > 0 || !L.v32 ||
+      L.nc_cells <= 0 || L.n != L.m || (L.n <= amg.fuse_rows && !(L.win && L.win->ok)))
+    return;
+  const int64_t n = L.n, fnnz = L.P->nnz;
+  int32_t *sx, *al, *cp, *cx;
+  int64_t* pos;
+  double *sv, *cv;
+  try {
+    sx = amg.wk.tcol.ensure(std::max<int64_t>(fnnz, 1));
+    sv = amg.wk.tval.ensure(std::max<int64_t>(fnnz, 1));
+    al = amg.ap_len.ensure(n + 1);
+    pos = amg.ap_pos.ensure(n + 1);
+    cp = amg.ap_ptr.ensure(n + 1);
+    cx = amg.ap_col.ensure(std::max<int64_t>(fnnz, 1));
+    cv = amg.ap_val.ensure(std::max<int64_t>(fnnz, 1));
+  } catch (const Error&) {
+#ifndef PFV_EMULATE
+    (void)hipGetLastError();  // (the failed allocation is not an error of the launches that follow)
+#endif
+    amg.ap_col.release();
+    amg.ap_val.release();
+    return;
+  }
+  const int32_t* fp = L.P->indptr;
+  const int32_t* ix = L.P->indices;
+  const float* v32 = L.v32;
+  const int32_t* agg = L.agg;
+  wave_for<16>(s, n, (kApKeys + kApChunk) * (2 * sizeof(int32_t) + sizeof(float)) + 16, PFV_LAMBDA(const WaveCtx& w) {
+    const int64_t r = w.item;
+    const int p0 = fp[r], len = fp[r + 1] - p0;
+    if (len > kApKeys) {
+      if (w.lane0()) {  // sorted insertion, sums in entry order
+        int cnt = 0;
+        for (int e = 0; e < len; ++e) {
+          const int32_t k = agg[ix[p0 + e]];
+          const double v = (double)v32[p0 + e];
+          int q = 0;
+          while (q < cnt && sx[p0 + q] < k) ++q;
+          if (q < cnt && sx[p0 + q] == k) {
+            sv[p0 + q] += v;
+          } else {
+            for (int m = cnt; m > q; --m) {
+              sx[p0 + m] = sx[p0 + m - 1];
+              sv[p0 + m] = sv[p0 + m - 1];
+            }
+            sx[p0 + q] = k;
+            sv[p0 + q] = 0.0 + v;
+            ++cnt;
+          }
+        }
+        al[r] = cnt;
+      }
+      return;
+    }
+    // (the loops over the row run in chunks of kApChunk without early exits: the LDS reads of a chunk are in flight
+    // together -- entry by entry with a break, every read waited for the one before it.  What the kernel is bound by is
+    // the instructions of the len x len comparisons, so the ranking loop tests as little as it can: an entry that is
+    // not the first of its aggregate carries bit 31, which takes it out of "first entries with a smaller key" by the
+    // unsigned comparison alone, and kApChunk sentinels of all ones behind the row need no test of the bounds.)
+    uint32_t* kh = reinterpret_cast<uint32_t*>(w.lds);  // [kApKeys + kApChunk] aggregate of every entry | bit 31
+    int32_t* dupf = reinterpret_cast<int32_t*>(kh + kApKeys + kApChunk);  // [kApKeys] 1: an earlier entry has this aggregate
+    float* vs = reinterpret_cast<float*>(dupf + kApKeys + kApChunk);      // [kApKeys + kApChunk]
+    PFV_LANES(e, len) {
+      kh[e] = (uint32_t)agg[ix[p0 + e]];
+      vs[e] = v32[p0 + e];
+    }
+    PFV_LANES(u, kApChunk) kh[len + u] = 0xffffffffu;
+    w.lsync();
+    PFV_LANES(e, len) {
+      const uint32_t k = kh[e];
+      int dup = 0;
+      for (int q0 = 0; q0 < e; q0 += kApChunk) {
+#pragma unroll
+        for (int u = 0; u < kApChunk; ++u) dup |= (q0 + u < e && kh[q0 + u] == k) ? 1 : 0;
+      }
+      dupf[e] = dup;
+    }
+    w.lsync();
+    PFV_LANES(e, len) kh[e] |= dupf[e] ? 0x80000000u : 0u;
+    w.lsync();
+    PFV_LANES(e, len) {
+      const uint32_t ke = kh[e];
+      const uint32_t k = ke & 0x7fffffffu;
+      int rank = 0, cnt = 0;
+      double sum = 0.0;
+      for (int q0 = 0; q0 < len; q0 += kApChunk) {
+#pragma unroll
+        for (int u = 0; u < kApChunk; ++u) {
+          const uint32_t kq = kh[q0 + u];
+          const float vq = vs[q0 + u];
+          rank += kq < k ? 1 : 0;
+          cnt += (int)((kq >> 31) ^ 1u);
+          // (for a first entry no earlier one has its key: the whole row in entry order is its run in entry order)
+          if ((kq & 0x7fffffffu) == k) sum += (double)vq;
+        }
+      }
+      if (ke == k) {
+        sx[p0 + rank] = (int32_t)k;
+        sv[p0 + rank] = sum;
+      }
+      if (e == 0) al[r] = cnt;
+    }
+    if (len == 0 && w.lane0()) al[r] = 0;
+    w.lsync();
+  });
+  exclusive_scan<int32_t, int64_t>(s, c.scratch, al, pos, (size_t)n);
+  wave_for<8>(s, n, 16, PFV_LAMBDA(const WaveCtx& w) {
+    const int64_t r = w.item;
+    const int p0 = fp[r];
+    const int64_t o = pos[r];
+    PFV_LANES(q, al[r]) {
+      cx[o + q] = sx[p0 + q];
+      cv[o + q] = sv[p0 + q];
+    }
+    if (w.lane0()) {
+      cp[r] = (int32_t)o;
+      if (r + 1 == n) cp[n] = (int32_t)pos[n];
+    }
+  });
+  amg.ap_ok = true;
+}
+
+// y = tt + omega D^-1 (b - (t + alpha AP xs)) with tt = x0 + alpha P xs, xs = xc (+ xc2), x0 = x on entry and t = A_s x0:
+// the post-smoothing step of level 0 in one launch, in place (a row reads only its own x0[r]).  xs is a vector of the
+// first coarse level (2 MB at 2 M cells: the gather stays in L2, no window).
+#ifndef PFV_EMULATE
+// A workgroup takes 256 rows.  Their entries are one contiguous stretch of AP (~2 000 at 7-8 per row), so they are
+// streamed by a thread per ENTRY -- every lane of every load busy -- and the products go to LDS; then a thread per ROW
+// adds its stretch of products in entry order and finishes the row, its six scalars read by full wavefronts.  (Eight
+// lanes per row, as the short-row products do it, issued 13 memory instructions per 8 rows with an eighth of the lanes
+// active in half of them, and ran 145 us on 160 MB: bound by the issue of loads, not by bytes.)  Rows of any length:
+// the stretch goes through LDS in chunks of CH products.
+template <int CH>
+__global__ void __launch_bounds__(256) k_amg_post_ap(int64_t nrows, const int32_t* __restrict__ ap,
+                                                     const int32_t* __restrict__ ax, const double* __restrict__ av,
+                                                     const int32_t* __restrict__ agg, const double* __restrict__ xc,
+                                                     const double* __restrict__ xc2, const double* __restrict__ t,
+                                                     const double* __restrict__ b, const double* __restrict__ dinv,
+                                                     double omega, double alpha, double* x) {
+  __shared__ double prod[CH];
+  const int64_t row0 = (int64_t)blockIdx.x * 256;
+  const int64_t row1 = row0 + 256 < nrows ? row0 + 256 : nrows;
+  const int64_t row = row0 + threadIdx.x;
+  const bool live = row < nrows;
+  const int a0 = ap[row0], e0 = ap[row1];
+  int a = 0, e = 0;
+  double x0 = 0.0, tr = 0.0, br = 0.0, dr = 0.0, xr = 0.0;
+  if (live) {
+    a = ap[row];
+    e = ap[row + 1];
+    const int k = agg[row];
+    x0 = x[row];
+    tr = t[row];
+    br = b[row];
+    dr = dinv[row];
+    xr = xc[k];
+    if (xc2) xr += xc2[k];
+  }
+  double sum = 0.0;
+  for (int c0 = a0; c0 < e0; c0 += CH) {
+    constexpr int U = CH / 256;
+    int k[U];
+    double v[U], xs[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int p = c0 + u * 256 + (int)threadIdx.x;
+      const bool ok = p < e0;
+      k[u] = ok ? ax[p] : -1;
+      v[u] = ok ? av[p] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      xs[u] = k[u] >= 0 ? xc[k[u]] : 0.0;
+      if (xc2 && k[u] >= 0) xs[u] += xc2[k[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) prod[u * 256 + threadIdx.x] = v[u] * xs[u];
+    __syncthreads();
+    const int lo = a > c0 ? a : c0, hi = e < c0 + CH ? e : c0 + CH;
+    for (int p = lo; p < hi; ++p) sum += prod[p - c0];  // entry order
+    __syncthreads();
+  }
+  if (live) {
+    const double tt = x0 + alpha * xr;
+    x[row] = tt + omega * dr * (br - (tr + alpha * sum));
+  }
+}
+#endif
+static void amg_post_ap(pfv_ctx_impl& c, const Amg& amg, const AmgLevel& L, const double* b, const double* t,
+                        const double* xc, const double* xc2, double* x) {
+  stream_t s = c.stream;
+  const int64_t n = L.n;
+  const int32_t* ap = amg.ap_ptr;
+  const int32_t* ax = amg.ap_col;
+  const double* av = amg.ap_val;
+  const int32_t* agg = L.agg;
+  const double* dinv = L.dinv;
+  const double omega = L.omega, alpha = amg.alpha;
+#ifdef PFV_EMULATE
+  parallel_for(s, n, PFV_LAMBDA(int64_t r) {
+    double sum = 0.0;
+    for (int p = ap[r]; p < ap[r + 1]; ++p) sum += av[p] * (xc2 ? xc[ax[p]] + xc2[ax[p]] : xc[ax[p]]);
+    const int k = agg[r];
+    const double tt = x[r] + alpha * (xc2 ? xc[k] + xc2[k] : xc[k]);
+    x[r] = tt + omega * dinv[r] * (b[r] - (t[r] + alpha * sum));
+  });
+#else
+  const unsigned blocks = (unsigned)((n + 255) / 256);
+  PFV_LAUNCH(HIP_KERNEL_NAME(k_amg_post_ap<2048>), dim3(blocks), dim3(256), 0, s, n, ap, ax, av, agg, xc, xc2, t, b, dinv,
+             omega, alpha, x);
+  PFV_HIP_CHECK(hipGetLastError());
+#endif
+}
+
 // The closing work: the coarsest level (explicit inverse when small enough; coupled hierarchy: the gathered level and
 // the replicated hierarchy below it), the damping, the row safeguard, and what the kept maps belong to.
 static void amg_setup_finish(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, double nnz_sum, unsigned long long csum,
@@ -1443,7 +1684,8 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
   tm.start(s);
   AmgDist* D = amg.dist.get();  // coupled hierarchy of a sharded solve (amg_dist.inc): A = owned rows x (owned + halo)
   amg.bs = bs;
-  amg.valid = amg.dense_ok = false;
+  amg.valid = amg.dense_ok = amg.ap_ok = false;
+  amg.ap_nnz = 0;
   amg.sysP = &A;
   amg.sysV = val;
   if (A.nrows % bs) throw Error(PFV_ERR_ARGUMENT, "AMG: system size is not a multiple of the block size");
@@ -1483,6 +1725,7 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
     if (D ? (l >= 1 && l == D->kgather) : (L.n <= w.coarse_target || (int)l + 1 >= kAmgMaxLevels)) break;
     const int slot = amg_coarsen_level(c, amg, l, reuse);
     if (slot < 0) break;  // coarsening stalled: this level is the coarsest
+    if (l == 0) amg_build_ap(c, amg);
     AmgLevel& Ln = amg_level(amg, l + 1);
     Ln.n = L.nc_cells * bs;
     // the last intermediate matrix becomes the new level (its old buffers go back to the slot)
@@ -1505,6 +1748,9 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
   }
   amg.nlev = l + 1;
   amg_setup_finish(c, amg, A, nnz_sum, csum, level0_sum);
+  // (entries of AP: a read for the statistics only, where the setup waits for its own end anyway)
+  if (amg.ap_ok) amg.ap_nnz = read_scalar<int64_t>(s, amg.ap_pos.p + amg.lev[0]->n);
+  c.stats.amg_ap_nnz = amg.ap_nnz;
   amg.setup_ms = tm.stop(s);
 }
 
@@ -1952,6 +2198,12 @@ static double* amg_cycle(pfv_ctx_impl& c, Amg& amg, size_t l, const double* b, d
     F.alpha = alpha;
     amg_spmv_fused<4>(c, L, x, out, b, F);
     return out;
+  }
+  if (l == 0 && amg.ap_ok && !small) {
+    // level 0 with AP: t = A_s x0 of the restriction is still in L.t (the coarse visits work in the vectors of their own
+    // levels; nothing above has written it), x still holds x0 -- prolongation and post-smoothing in one launch
+    amg_post_ap(c, amg, L, b, t, xc, xc2, x);
+    return x;
   }
   {
     const int32_t* agg = L.agg;

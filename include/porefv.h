@@ -208,6 +208,9 @@ typedef struct {
                                      (PFV_AMG_POST_AP, default on; its build is part of amg_setup_ms).  0: that level takes the
                                      prolongation and the smoothing product as two launches (block systems, sharded solves,
                                      PFV_AMG_FP32=0, a finest level small enough for the fused restriction) */
+  double transport_react_adjoint_ms; /* last pfv_transport_adjoint_react, all steps (HIP events) */
+  int64_t transport_react_adjoint_steps; /* ... accepted adjoint steps */
+  int64_t transport_react_adjoint_core_iterations; /* ... block Jacobi iterations of the cyclic core, summed over the steps */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -756,6 +759,54 @@ pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, 
                                        double* grad_c0, double* grad_source, double* grad_bc_values,
                                        double* grad_accumulation, double* grad_flux, int32_t* steps_done,
                                        pfv_solve_info* last);
+
+/* The adjoint of pfv_transport_advance_react: every gradient of J = sum_{n=1..N} sum_a <g_a^n, c_a^n> through n_steps = N
+ * forward steps acc_a o (c_a^n - c_a^{n-1}) + w_a (A(q) c_a^n + b_ref_a) + rho o sum_b K_ab c_b^n = src_a.  The step is
+ * linear in c, so the adjoint is exact: for n = N .. 1 all k components solve ONE system
+ * M^T lambda^n = g^n + acc o lambda^{n+1} (lambda^{N+1} = 0).  In reverse flow order cell i is one k x k solve
+ *     B_i^T lambda_i = R_i,  B_i = diag(acc_ia + w_a A_ii) + rho_i K,  R_ia = r_ia - w_a sum_{lev[j] > lev[i]} valT[e] lambda_ja
+ * (csrc/sweep.inc: sweep_row_react<k, Descending>, the forward row with the transposed values and K^T): the levels and
+ * the launch plan are those of the forward sweep.  B_i^T is a strictly row-diagonally-dominant M-matrix; it is
+ * eliminated WITHOUT pivoting (growth factor <= 2), there is no pivoted path.  The cells of a cyclic core are iterated
+ * by block Jacobi from zero until every component has ||F_core,a|| <= rtol ||g~_a|| / 2, or maxit iterations.  A step is
+ * accepted when every component has ||F_a|| <= rtol ||g~_a|| (0 <= 0 counts), F_a = r_a - (M^T lambda)_a and the scale
+ * g~_a = r_a - rho sum_{b != a} K_ba lambda_b (a parent that is observed only through its daughter has r_a = 0).  One host
+ * read per step brings the 2 k norms and the status word.
+ *   k, bc_values, accumulation, mobility, rate, rate_weight and q are those of pfv_transport_advance_react, with its
+ * rules and texts (rate is checked as the caller passes it, not its transpose; bc_values[a] of an immobile component
+ * is not read and may be NaN); loads, obs_cells, states and the first five gradients are those of
+ * pfv_transport_adjoint_multi.  rate and mobility are HOST memory, and so is grad_rate (k^2 doubles); every other
+ * array follows pfv_set_vectors_on_device.  states are NOT checked for finiteness.
+ *   Gradients, each may be NULL (not wanted), all accumulated on the device without floating-point atomics:
+ *     grad_c0 [k][Nc]            acc_a o lambda_a^1
+ *     grad_source [k][Nc]        sum_n lambda_a^n
+ *     grad_bc_values [k][Nf]     -w_a sum_n B^T lambda_a^n; all zero for w_a = 0
+ *     grad_accumulation [k][Nc]  sum_n lambda_a^n o (c_a^{n-1} - c_a^n)                               (needs states)
+ *     grad_flux [Nf]             -sum_n sum_a w_a (lambda_a^n[p] - lambda_a^n[m]) cup_a^n[f], at a fixed upstream side;
+ *                                components with w_a = 0 are skipped                                   (needs states)
+ *     grad_rate [k][k]           -sum_n sum_i rho_i lambda_ia^n c_ib^n: the plain partial derivative with respect to
+ *                                EVERY entry of K, structural zeros included; the chain to the caller's rate
+ *                                parameters is the caller's                                            (needs states)
+ *     grad_rate_weight [Nc]      -sum_n sum_a lambda_ia^n sum_b K_ab c_ib^n                            (needs states)
+ * The k^2 sums of grad_rate run over a fixed partition of the cells that depends on Nc and k alone and are added in
+ * step order: the result does not depend on the launch form of the sweep or on a repeat of the call.  The gradient
+ * with respect to the mobility is not offered (it needs the boundary values of immobile components).
+ *   PFV_ERR_ARGUMENT (the text names the offender): what pfv_transport_advance_react refuses in its arguments; an
+ * obs_cells entry out of range or repeated; a non-finite value in loads; grad_accumulation, grad_flux, grad_rate or
+ * grad_rate_weight without states.  PFV_ERR_UNSUPPORTED as pfv_transport_advance_react.
+ *   steps_done: the adjoint steps completed.  A refused step returns PFV_ERR_NOT_CONVERGED and writes no gradient.
+ * last (k entries, may be NULL): iterations = 1 for an acyclic flux, else the core iterations of the last step;
+ * rel_residual the measured ||F_a|| / ||g~_a||.  Handle rules as pfv_transport_adjoint_multi: the flow order is built
+ * if needed and stays, the transposed positions stay with the pattern, the selection and the flow system are left
+ * alone, no transport system is left behind.  pfv_stats: transport_react_adjoint_* and the sweep_* fields
+ * (sweep_launches: the forward sweep's on an acyclic flux). */
+pfv_status pfv_transport_adjoint_react(pfv_ctx* h, const double* q, int k, const double* bc_values,
+                                       const double* accumulation, const double* mobility, const double* rate,
+                                       const double* rate_weight, int n_steps, int64_t n_obs, const int32_t* obs_cells,
+                                       const double* loads, const double* states, double rtol, int maxit,
+                                       double* grad_c0, double* grad_source, double* grad_bc_values,
+                                       double* grad_accumulation, double* grad_flux, double* grad_rate,
+                                       double* grad_rate_weight, int32_t* steps_done, pfv_solve_info* last);
 
 /* ---- Advection-diffusion step on the device (csrc/advdiff.inc) ---------------------------------------------------
  * One handle carries the transport keyword: its diffusion discretization (pfv_mpfa_discretize or pfv_tpfa_discretize

@@ -51,7 +51,7 @@ EXPORTS = [
     "pfv_mpfa_face_flux", "pfv_upwind_set_bc", "pfv_upwind_discretize", "pfv_upwind_assemble", "pfv_transport_advance",
     "pfv_advdiff_assemble", "pfv_advdiff_advance", "pfv_advdiff_face_flux", "pfv_resident_flux",
     "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl", "pfv_transport_advance_nl_multi",
-    "pfv_transport_advance_react", "pfv_transport_adjoint_multi",
+    "pfv_transport_advance_react", "pfv_transport_adjoint_multi", "pfv_transport_adjoint_react",
 ]
 
 
@@ -91,7 +91,9 @@ class Stats(C.Structure):
                 ("transport_react_ms", C.c_double), ("transport_react_steps", C.c_int64),
                 ("transport_react_core_iterations", C.c_int64), ("transport_react_components", C.c_int64),
                 ("transport_adjoint_ms", C.c_double), ("transport_adjoint_steps", C.c_int64),
-                ("transport_adjoint_core_iterations", C.c_int64), ("amg_ap_nnz", C.c_int64)]
+                ("transport_adjoint_core_iterations", C.c_int64), ("amg_ap_nnz", C.c_int64),
+                ("transport_react_adjoint_ms", C.c_double), ("transport_react_adjoint_steps", C.c_int64),
+                ("transport_react_adjoint_core_iterations", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -323,6 +325,10 @@ def _bind(lib: C.CDLL) -> C.CDLL:
                                                 C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32),
                                                 C.POINTER(SolveInfo)]
     lib.pfv_transport_adjoint_multi.restype = C.c_int
+    lib.pfv_transport_adjoint_react.argtypes = [_h, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int64, _ip, _dp,
+                                                _dp, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
+    lib.pfv_transport_adjoint_react.restype = C.c_int
     lib.pfv_advdiff_assemble.argtypes = [_h, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pfv_advdiff_assemble.restype = C.c_int
     lib.pfv_advdiff_advance.argtypes = [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(C.c_int32),
@@ -1634,6 +1640,84 @@ class Context:
             float(rtol), int(maxit), _ptr(grads.get("c0"), _dp), _ptr(grads.get("source"), _dp),
             _ptr(grads.get("bc_values"), _dp), _ptr(grads.get("accumulation"), _dp), _ptr(grads.get("flux"), _dp),
             C.byref(done), infos)
+        out = {"steps_done": done.value, "converged": all(bool(i.converged) for i in infos),
+               "iterations": [i.iterations for i in infos], "rel_residual": [i.rel_residual for i in infos],
+               "solve_ms": [i.solve_ms for i in infos]}
+        if st != 0 and (raise_on_fail or st != 6):
+            try:
+                self._check(st)
+            except PorefvError as e:
+                e.info = out
+                raise
+        return grads, out
+
+    REACT_ADJOINT_GRADIENTS = ADJOINT_GRADIENTS + ("rate_matrix", "rate_weight")
+
+    def transport_adjoint_react(self, n_steps: int, accumulation, bc_values, rate, loads, rate_weight=None, mobility=None,
+                                obs_cells=None, states=None, q=None, want=("c0", "source", "bc_values"), rtol=1e-12,
+                                maxit=500, raise_on_fail=True):
+        """The adjoint of ``transport_advance_react`` (pfv_transport_adjoint_react): the gradients of
+        ``J = sum_n sum_a <loads[n-1, a], c_a^n[obs_cells]>`` through ``n_steps`` reactive steps, by one transposed
+        k x k sweep in reverse flow order per step.  ``accumulation``, ``bc_values``, ``rate``, ``rate_weight``,
+        ``mobility`` and ``q`` as in ``transport_advance_react``; ``loads``, ``obs_cells`` and ``states`` as in
+        ``transport_adjoint_multi``.  ``want``: names out of ``REACT_ADJOINT_GRADIENTS``; "accumulation", "flux",
+        "rate_matrix" and "rate_weight" need ``states`` (which are not checked for finiteness).  grads["rate_matrix"]
+        (k, k) is the plain partial derivative with respect to every entry of K, structural zeros included: the chain
+        to rate parameters is the caller's.  grads["rate_weight"]: (Nc,).  Returns (grads, info) as
+        ``transport_adjoint_multi``; a refused step leaves the gradients zero."""
+        acc = _f64(accumulation)
+        if acc.ndim != 2 or acc.shape[1] != self.nc:
+            raise ValueError(f"accumulation must have shape (k, {self.nc}), not {acc.shape}")
+        k = acc.shape[0]
+        if not 1 <= k <= 8:
+            raise ValueError(f"the number of coupled components must lie in 1 .. 8, not {k} "
+                             f"(accumulation has shape {acc.shape})")
+        bv = _f64(bc_values)
+        if bv.shape != (k, self.nf):
+            raise ValueError(f"bc_values must have shape ({k}, {self.nf}), not {bv.shape}")
+        K = _f64(rate)
+        if K.shape != (k, k):
+            raise ValueError(f"rate_matrix must have shape ({k}, {k}), not {K.shape}")
+        w = None if mobility is None else _f64(mobility)
+        if w is not None and w.shape != (k,):
+            raise ValueError(f"mobility must have shape ({k},), not {w.shape}")
+        n_steps = int(n_steps)
+        if n_steps < 0:
+            raise ValueError("n_steps must not be negative")
+        obs = None
+        if obs_cells is not None:
+            obs = np.ascontiguousarray(obs_cells)
+            if obs.ndim != 1 or not np.issubdtype(obs.dtype, np.integer):
+                raise ValueError("obs_cells must be a one-dimensional array of cell indices")
+            big = obs[(obs < -2 ** 31) | (obs >= 2 ** 31)]
+            if big.size:
+                raise ValueError(f"obs_cells: {int(big[0])} is out of range (0 .. {self.nc - 1})")
+            obs = obs.astype(np.int32)
+        n_obs = self.nc if obs is None else obs.size
+        ld = _f64(loads)
+        if ld.shape != (n_steps, k, n_obs):
+            raise ValueError(f"loads must have shape ({n_steps}, {k}, {n_obs}), not {ld.shape}")
+        stt = None
+        if states is not None:
+            stt = _f64(states)
+            if stt.shape != (n_steps + 1, k, self.nc):
+                raise ValueError(f"states must have shape ({n_steps + 1}, {k}, {self.nc}), not {stt.shape}")
+        want = tuple(want)
+        for name in want:
+            if name not in self.REACT_ADJOINT_GRADIENTS:
+                raise ValueError(f"want: unknown gradient {name!r} (known: {', '.join(self.REACT_ADJOINT_GRADIENTS)})")
+            if name in ("accumulation", "flux", "rate_matrix", "rate_weight") and stt is None:
+                raise ValueError(f'the gradient "{name}" needs states (c^0 .. c^N)')
+        kq, pq = self._vec(q, self.nf, "the flux array", False)
+        kr, pr = self._vec(rate_weight, self.nc, "rate_weight", False)
+        shapes = {"c0": (k, self.nc), "source": (k, self.nc), "bc_values": (k, self.nf), "accumulation": (k, self.nc),
+                  "flux": (self.nf,), "rate_matrix": (k, k), "rate_weight": (self.nc,)}
+        grads = {name: np.zeros(shapes[name]) for name in self.REACT_ADJOINT_GRADIENTS if name in want}
+        done, infos = C.c_int32(0), (SolveInfo * k)()
+        st = self.lib.pfv_transport_adjoint_react(
+            self._h, pq, k, _ptr(bv, _dp), _ptr(acc, _dp), _ptr(w, _dp), _ptr(K, _dp), pr, n_steps, n_obs,
+            _ptr(obs, _ip), _ptr(ld, _dp), _ptr(stt, _dp), float(rtol), int(maxit),
+            *[_ptr(grads.get(name), _dp) for name in self.REACT_ADJOINT_GRADIENTS], C.byref(done), infos)
         out = {"steps_done": done.value, "converged": all(bool(i.converged) for i in infos),
                "iterations": [i.iterations for i in infos], "rel_residual": [i.rel_residual for i in infos],
                "solve_ms": [i.solve_ms for i in infos]}

@@ -359,6 +359,10 @@ struct pfv_ctx_impl {
   // lambda^n / lambda^{n+1}, the core's previous iterate, rhs; the accumulators of grad_source and grad_accumulation
   // (interleaved), of grad_bc_values (component-major [k][nf]) and of grad_flux [nf]
   Buf<double> aj_loads, aj_state_in, aj_sA, aj_sB, aj_lam, aj_lam2, aj_prev, aj_r, aj_gsrc, aj_gacc, aj_gbc, aj_gq;
+  // the adjoint of the reactive step (pfv_transport_adjoint_react) takes its inputs and the acceptance test's vectors
+  // from the rc_ buffers and the rest from the aj_ ones.  rc_parT: ReactPar with K^T; the accumulators of grad_rate
+  // (k^2, row-major) and of grad_rate_weight [nc]
+  Buf<double> rc_parT, aj_gK, aj_grho;
 
   // ---- advection-diffusion (advdiff.inc): S = diag(acc) + div flux_D + w div diag(q) U on pat_A -------------------
   bool have_advdiff = false;         // val[PFV_MAT_ADVDIFF_SYSTEM], adv_diag, adv_rhs hold a system of the discretization

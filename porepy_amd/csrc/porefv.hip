@@ -1805,12 +1805,189 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
   return step_status(h, st, err, st2);
 }
 
-// ---- the adjoint of the k-component step: one transposed sweep in reverse flow order per step (sweep.inc) -------------
+// ---- the observation of an adjoint call, shared by pfv_transport_adjoint_multi and pfv_transport_adjoint_react --------
+// obs_cells (host) are checked, the loads [N][k][n_obs] go to aj_loads and are checked for finiteness
+static void adjoint_take_loads(pfv_ctx* h, int k, int n_steps, int64_t n_obs, const int32_t* obs_cells,
+                               const double* loads) {
+  const size_t nc = (size_t)h->nc;
+  if (obs_cells) {
+    require(n_obs >= 0 && n_obs <= (int64_t)nc, "n_obs must lie in 0 .. the number of cells");
+    std::vector<char> seen(nc, 0);
+    for (int64_t m = 0; m < n_obs; ++m) {
+      const int32_t cell = obs_cells[m];
+      if (cell < 0 || (size_t)cell >= nc)
+        throw Error(PFV_ERR_ARGUMENT, "obs_cells[" + std::to_string(m) + "] = " + std::to_string(cell) +
+                                          " is out of range (0 .. " + std::to_string(nc - 1) + ")");
+      if (seen[(size_t)cell])
+        throw Error(PFV_ERR_ARGUMENT, "obs_cells[" + std::to_string(m) + "] = " + std::to_string(cell) + " is repeated");
+      seen[(size_t)cell] = 1;
+    }
+  } else {
+    require(n_obs == (int64_t)nc, "obs_cells == NULL means every cell: n_obs must be the number of cells");
+  }
+  const size_t nl = (size_t)n_steps * k * (size_t)n_obs;
+  if (nl) {
+    vec_in(h, h->aj_loads.ensure(nl), loads, nl);
+    const int64_t bad = nl < (size_t(1) << 31) ? pfv::adjoint_first_nonfinite(*h, (int64_t)nl, h->aj_loads.p) : -1;
+    if (bad >= 0) {
+      const int64_t per = (int64_t)k * n_obs;
+      throw Error(PFV_ERR_ARGUMENT, "loads is not finite at step " + std::to_string(bad / per + 1) + ", component " +
+                                        std::to_string(bad % per / n_obs) + ", observation " +
+                                        std::to_string(bad % n_obs));
+    }
+  }
+}
+
+// aj_slot: the position of every cell among the observation cells (after adjoint_take_loads; nothing for obs_cells == NULL)
+static void adjoint_take_slots(pfv_ctx* h, int64_t n_obs, const int32_t* obs_cells) {
+  const size_t nc = (size_t)h->nc;
+  if (obs_cells && n_obs > 0) {
+    be_h2d(h->aj_obs.ensure((size_t)n_obs), obs_cells, sizeof(int32_t) * (size_t)n_obs, h->stream);
+    pfv::be_memset(h->aj_slot.ensure(nc), 0xff, sizeof(int32_t) * nc, h->stream);
+    pfv::adjoint_obs_slots(*h, n_obs, h->aj_obs.p, h->aj_slot.p);
+  } else if (obs_cells) {
+    pfv::be_memset(h->aj_slot.ensure(nc), 0xff, sizeof(int32_t) * nc, h->stream);
+  }
+}
+
+// ---- the step frame of the two adjoint calls (after their set-up, with the timer running) -------------------------------
 // Per step n = N .. 1: one slab of states (when given), the right-hand side g^n + acc o lambda^{n+1} fused with what
-// lambda^{n+1} adds to grad_source and grad_accumulation, the backward-peel levels from last to first, the core level
+// lambda^{n+1} adds to grad_source and grad_accumulation (adjoint_step_rhs), the call's own solve -- sweep, core,
+// acceptance --, its gradients of the accepted step, the swap of the two lambda and the two slab buffers.  After the
+// last step the right-hand-side kernel runs once more without loads: it leaves acc o lambda^1 = grad_c0.  Then the three
+// cell gradients go out, the call's other outputs, and the transport system is dropped.
+struct AdjointCall {  // what the two calls share, by the callers' names
+  int k, n_steps;
+  int64_t n_obs;
+  const int32_t* obs_cells;
+  const double* states;
+  const double* acc;  // the accumulation on the device, interleaved
+  double *grad_c0, *grad_source, *grad_accumulation;
+  int32_t* steps_done;
+  pfv_solve_info* last;
+};
+struct AdjointRun {
+  int32_t completed = 0;
+  int64_t core_total = 0, launches = 0;
+  double ms = 0.0;
+  std::vector<pfv_solve_info> info;
+};
+
+// info from hst: (scale_a, scale_a), (residual_a, residual_a)
+static void adjoint_component_info(std::vector<pfv_solve_info>& info, const std::vector<double>& hst, int k, int it) {
+  for (int a = 0; a < k; ++a) {
+    const double bb = hst[(size_t)a], rr = hst[(size_t)k + a];
+    info[(size_t)a] = pfv_solve_info{};
+    info[(size_t)a].iterations = it;
+    info[(size_t)a].rel_residual = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
+  }
+}
+
+// ||residual_a|| <= tol ||scale_a|| for every component (0 <= 0 counts)
+static bool adjoint_norms_pass(const std::vector<double>& hst, int k, double tol) {
+  bool pass = true;
+  for (int a = 0; a < k; ++a) pass = pass && hst[(size_t)k + a] <= tol * tol * hst[(size_t)a];
+  return pass;
+}
+
+// the acceptance of step n from the norms in hst (after adjoint_component_info)
+static pfv_status adjoint_accept(pfv_ctx* h, std::vector<pfv_solve_info>& info, const std::vector<double>& hst, int k,
+                                 double rtol, int n) {
+  int bad = -1;  // the first component whose check fails
+  for (int a = k - 1; a >= 0; --a) {
+    info[(size_t)a].converged = hst[(size_t)k + a] <= rtol * rtol * hst[(size_t)a] ? 1 : 0;  // (0 <= 0 counts)
+    if (!info[(size_t)a].converged) bad = a;
+  }
+  if (bad < 0) return PFV_OK;
+  h->err = "adjoint step " + std::to_string(n) + ": relative residual " + std::to_string(info[(size_t)bad].rel_residual) +
+           " of component " + std::to_string(bad) +
+           " after the transposed sweep (a flux that contradicts the discretization's?)";
+  return PFV_ERR_NOT_CONVERGED;
+}
+
+// solve(n, z) -> PFV_OK or the verdict of a refused step (its text in h->err): lambda^n into z from the right-hand side
+// aj_r; it fills run.info and counts run.launches / run.core_total.  step_grads(z): what the accepted step adds to the
+// call's other gradients (c^n in aj_sB).  rest_out(): the outputs beyond the three cell gradients.
+static pfv_status adjoint_steps(pfv_ctx* h, std::unique_ptr<pfv::Timer>& tm, const AdjointCall& A, AdjointRun& run,
+                                const std::function<pfv_status(int, double*)>& solve,
+                                const std::function<void(double*)>& step_grads, const std::function<void()>& rest_out) {
+  const int k = A.k;
+  const size_t nc = (size_t)h->nc;
+  const int32_t* slot = A.obs_cells ? h->aj_slot.p : nullptr;
+  // slab n of the states, interleaved into `to`
+  auto stage_slab = [&](int n, double* to) {
+    const double* src = A.states + (size_t)n * k * nc;
+    if (!h->vectors_on_device) {
+      be_h2d(h->aj_state_in.p, src, sizeof(double) * k * nc, h->stream);
+      src = h->aj_state_in.p;
+    }
+    pfv::multi_interleave(*h, (int64_t)nc, k, src, to);
+  };
+  run.info.assign((size_t)k, pfv_solve_info{});
+  pfv_status st = PFV_OK;
+  std::string err;
+  bool have_lam = false;  // aj_lam holds lambda^{n+1}
+  for (int n = A.n_steps; n >= 1 && st == PFV_OK; --n) {
+    pfv_status verdict = PFV_OK;
+    st = guarded(h, [&] {
+      pfv::pfv_ctx_impl& cx = *h;
+      if (A.states) stage_slab(n, cx.aj_sB.p);  // c^n; aj_sA holds c^{n+1}
+      pfv::adjoint_step_rhs(cx, k, A.acc, have_lam ? cx.aj_lam.p : nullptr, slot,
+                            cx.aj_loads.p + (size_t)(n - 1) * k * (size_t)A.n_obs, A.n_obs, cx.aj_sB.p, cx.aj_sA.p,
+                            A.grad_source ? cx.aj_gsrc.p : nullptr, A.grad_accumulation ? cx.aj_gacc.p : nullptr,
+                            cx.aj_r.p);
+      double* z = cx.aj_lam2.p;
+      verdict = solve(n, z);
+      if (verdict != PFV_OK) return;
+      step_grads(z);
+      cx.aj_lam.swap(cx.aj_lam2);
+      cx.aj_sA.swap(cx.aj_sB);
+      have_lam = true;
+      ++run.completed;
+    });
+    if (st == PFV_OK) st = verdict;
+  }
+  if (st != PFV_OK) err = h->err;
+  const pfv_status st2 = guarded(h, [&] {
+    pfv::pfv_ctx_impl& cx = *h;
+    if (st == PFV_OK) {
+      // lambda^1 into the cell gradients; the right-hand side it leaves is acc o lambda^1
+      if (have_lam && A.grad_accumulation) stage_slab(0, cx.aj_sB.p);  // c^0
+      if (have_lam)
+        pfv::adjoint_step_rhs(cx, k, A.acc, cx.aj_lam.p, nullptr, nullptr, 0, cx.aj_sB.p, cx.aj_sA.p,
+                              A.grad_source ? cx.aj_gsrc.p : nullptr, A.grad_accumulation ? cx.aj_gacc.p : nullptr,
+                              cx.aj_r.p);
+      else
+        pfv::be_memset(cx.aj_r.p, 0, sizeof(double) * k * nc, cx.stream);
+    }
+    run.ms = tm->stop(cx.stream);
+    tm.reset();
+    if (st == PFV_OK) {
+      auto cells_out = [&](double* to, const double* from) {
+        pfv::multi_deinterleave(cx, (int64_t)nc, k, from, cx.mc_c.p);
+        vec_out(h, to, cx.mc_c.p, k * nc);
+      };
+      if (A.grad_c0) cells_out(A.grad_c0, cx.aj_r.p);
+      if (A.grad_source) cells_out(A.grad_source, cx.aj_gsrc.p);
+      if (A.grad_accumulation) cells_out(A.grad_accumulation, cx.aj_gacc.p);
+      rest_out();
+    }
+    pfv::be_sync(cx.stream);
+    upwind_drop_transport(h, true);
+  });
+  if (A.steps_done) *A.steps_done = run.completed;
+  if (A.last)
+    for (int a = 0; a < k; ++a) {
+      A.last[a] = run.info[(size_t)a];
+      if (run.completed > 0) A.last[a].solve_ms = run.ms / run.completed;
+    }
+  return step_status(h, st, err, st2);
+}
+
+// ---- the adjoint of the k-component step: one transposed sweep in reverse flow order per step (sweep.inc) -------------
+// In the frame of adjoint_steps, the solve of a step: the backward-peel levels from last to first, the core level
 // iterated by Jacobi on its transposed rows (a host read every kNlCoreCheck-th iteration), the forward-peel levels, the
-// residual norms of all components and ONE host read, then the two face kernels (grad_bc_values, grad_flux).  After
-// the last step the right-hand-side kernel runs once more without loads: it leaves acc o lambda^1 = grad_c0.
+// residual norms of all components and ONE host read; then the two face kernels (grad_bc_values, grad_flux).
 pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, const double* bc_values,
                                        const double* accumulation, int n_steps, int64_t n_obs, const int32_t* obs_cells,
                                        const double* loads, const double* states, double rtol, int maxit,
@@ -1839,32 +2016,7 @@ pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, 
     nf = (size_t)h->nf;
     if ((int64_t)nc * k >= (int64_t(1) << 31) || (int64_t)nf * k >= (int64_t(1) << 31))
       throw Error(PFV_ERR_UNSUPPORTED, "n_comp x cells (faces) beyond int32 indices");
-    if (obs_cells) {
-      require(n_obs >= 0 && n_obs <= (int64_t)nc, "n_obs must lie in 0 .. the number of cells");
-      std::vector<char> seen(nc, 0);
-      for (int64_t m = 0; m < n_obs; ++m) {
-        const int32_t cell = obs_cells[m];
-        if (cell < 0 || (size_t)cell >= nc)
-          throw Error(PFV_ERR_ARGUMENT, "obs_cells[" + std::to_string(m) + "] = " + std::to_string(cell) +
-                                            " is out of range (0 .. " + std::to_string(nc - 1) + ")");
-        if (seen[(size_t)cell])
-          throw Error(PFV_ERR_ARGUMENT, "obs_cells[" + std::to_string(m) + "] = " + std::to_string(cell) + " is repeated");
-        seen[(size_t)cell] = 1;
-      }
-    } else {
-      require(n_obs == (int64_t)nc, "obs_cells == NULL means every cell: n_obs must be the number of cells");
-    }
-    const size_t nl = (size_t)n_steps * k * (size_t)n_obs;
-    if (nl) {
-      vec_in(h, h->aj_loads.ensure(nl), loads, nl);
-      const int64_t bad = nl < (size_t(1) << 31) ? pfv::adjoint_first_nonfinite(*h, (int64_t)nl, h->aj_loads.p) : -1;
-      if (bad >= 0) {
-        const int64_t per = (int64_t)k * n_obs;
-        throw Error(PFV_ERR_ARGUMENT, "loads is not finite at step " + std::to_string(bad / per + 1) + ", component " +
-                                          std::to_string(bad % per / n_obs) + ", observation " +
-                                          std::to_string(bad % n_obs));
-      }
-    }
+    adjoint_take_loads(h, k, n_steps, n_obs, obs_cells, loads);
     if (q) vec_in(h, h->mc_q.ensure(nf), q, nf);
     vec_in(h, h->mc_bc.ensure(k * nf), bc_values, k * nf);
     vec_in(h, h->mc_acc.ensure(k * nc), accumulation, k * nc);
@@ -1888,13 +2040,7 @@ pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, 
       h->have_tpos_T = true;
     }
     pfv::sweep_transpose_values(*h, h->pat_T.nnz, h->tpos_T.p, h->val[PFV_MAT_TRANSPORT_SYSTEM].p, h->valT_T.ensure(nnz));
-    if (obs_cells && n_obs > 0) {
-      be_h2d(h->aj_obs.ensure((size_t)n_obs), obs_cells, sizeof(int32_t) * (size_t)n_obs, h->stream);
-      pfv::be_memset(h->aj_slot.ensure(nc), 0xff, sizeof(int32_t) * nc, h->stream);
-      pfv::adjoint_obs_slots(*h, n_obs, h->aj_obs.p, h->aj_slot.p);
-    } else if (obs_cells) {
-      pfv::be_memset(h->aj_slot.ensure(nc), 0xff, sizeof(int32_t) * nc, h->stream);
-    }
+    adjoint_take_slots(h, n_obs, obs_cells);
     for (pfv::Buf<double>* b : {&h->aj_lam, &h->aj_lam2, &h->aj_prev, &h->aj_r}) b->ensure(k * nc);
     if (states) {
       h->aj_sA.ensure(k * nc);
@@ -1914,136 +2060,227 @@ pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, 
     return st;
   }
 
-  const int32_t* slot = obs_cells ? h->aj_slot.p : nullptr;
-  // slab n of the states, interleaved into `to`
-  auto stage_slab = [&](int n, double* to) {
-    const double* src = states + (size_t)n * k * nc;
-    if (!h->vectors_on_device) {
-      be_h2d(h->aj_state_in.p, src, sizeof(double) * k * nc, h->stream);
-      src = h->aj_state_in.p;
-    }
-    pfv::multi_interleave(*h, (int64_t)nc, k, src, to);
-  };
-  int32_t completed = 0;
-  int64_t core_total = 0, launches = 0;
-  std::vector<pfv_solve_info> info((size_t)k);
+  AdjointRun run;
   std::vector<double> hst(2 * (size_t)k);
-  std::string err;
-  bool have_lam = false;  // aj_lam holds lambda^{n+1}
-  for (int n = n_steps; n >= 1 && st == PFV_OK; --n) {
-    pfv_status verdict = PFV_OK;
-    st = guarded(h, [&] {
-      pfv::pfv_ctx_impl& cx = *h;
-      const pfv::Sweep& sw = *cx.sweep;
-      const double* valT = cx.valT_T.p;
-      const double* acc = cx.mc_acc_i.p;
-      double* out = cx.mc_nrm.p;
-      const bool has_core = sw.n_core > 0;
-      const int core = has_core ? sw.core_level : -1;
-      if (states) stage_slab(n, cx.aj_sB.p);  // c^n; aj_sA holds c^{n+1}
-      pfv::adjoint_step_rhs(cx, k, acc, have_lam ? cx.aj_lam.p : nullptr, slot,
-                            cx.aj_loads.p + (size_t)(n - 1) * k * (size_t)n_obs, n_obs, cx.aj_sB.p, cx.aj_sA.p,
-                            grad_source ? cx.aj_gsrc.p : nullptr, grad_accumulation ? cx.aj_gacc.p : nullptr, cx.aj_r.p);
-      double* z = cx.aj_lam2.p;
-      launches = pfv::sweep_apply_multi_t(cx, sw, core + 1, sw.nlev, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, z);
-      int core_it = 0;
-      auto component_info = [&](int it) {  // from hst: (r_a, r_a), (residual_a, residual_a)
-        for (int a = 0; a < k; ++a) {
-          const double bb = hst[(size_t)a], rr = hst[(size_t)k + a];
-          info[(size_t)a] = pfv_solve_info{};
-          info[(size_t)a].iterations = it;
-          info[(size_t)a].rel_residual = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
-        }
-      };
-      if (has_core) {
-        pfv::sweep_core_zero(cx, sw, k, z);
-        const CoreRun run = core_iterate(h, maxit, out, hst, [&] {
-          pfv::sweep_core_copy(cx, sw, k, z, cx.aj_prev.p);
-          pfv::sweep_core_multi_t(cx, sw, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, cx.aj_prev.p, z);
-        }, [&] {
-          pfv::sweep_core_norms_multi_t(cx, sw, cx.pat_T, valT, acc, k, cx.aj_r.p, z, out);
-        }, [&] {
-          bool settled = true;
-          for (int a = 0; a < k; ++a) settled = settled && hst[(size_t)k + a] <= 0.25 * rtol * rtol * hst[(size_t)a];
-          return settled;
-        });
-        core_it = run.iterations;
-        core_total += core_it;
-        launches += 2;
-        if (!run.settled) {  // (what the forward-peel levels would compute from this core is not judged)
-          component_info(core_it);
-          verdict = PFV_ERR_NOT_CONVERGED;
-          cx.err = "adjoint step " + std::to_string(n) + ": the cyclic core of " + std::to_string(sw.n_core) +
-                   " cells did not settle in " + std::to_string(core_it) + " iterations";
-          return;
-        }
-        launches += pfv::sweep_apply_multi_t(cx, sw, 0, core, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, z);
-      }
-      pfv::sweep_residual_norms_multi(cx, cx.pat_T, valT, acc, k, cx.aj_r.p, z, out);  // (valT: the image under S^T)
-      be_d2h(hst.data(), out, sizeof(double) * hst.size(), cx.stream);
-      component_info(has_core ? core_it : 1);
-      int bad = -1;  // the first component whose check fails
-      for (int a = k - 1; a >= 0; --a) {
-        info[(size_t)a].converged = hst[(size_t)k + a] <= rtol * rtol * hst[(size_t)a] ? 1 : 0;  // (0 <= 0 counts)
-        if (!info[(size_t)a].converged) bad = a;
-      }
-      if (bad >= 0) {
-        verdict = PFV_ERR_NOT_CONVERGED;
-        cx.err = "adjoint step " + std::to_string(n) + ": relative residual " +
-                 std::to_string(info[(size_t)bad].rel_residual) + " of component " + std::to_string(bad) +
-                 " after the transposed sweep (a flux that contradicts the discretization's?)";
-        return;
-      }
-      if (grad_bc_values) pfv::adjoint_grad_bc(cx, k, d_q, z, cx.aj_gbc.p);
-      if (grad_flux) pfv::adjoint_grad_flux(cx, k, cx.mc_bc.p, z, cx.aj_sB.p, cx.aj_gq.p);
-      cx.aj_lam.swap(cx.aj_lam2);
-      cx.aj_sA.swap(cx.aj_sB);
-      have_lam = true;
-      ++completed;
-    });
-    if (st == PFV_OK) st = verdict;
-  }
-  if (st != PFV_OK) err = h->err;
-  double ms = 0.0;
-  const pfv_status st2 = guarded(h, [&] {
+  const AdjointCall call{k, n_steps, n_obs, obs_cells, states, h->mc_acc_i.p, grad_c0, grad_source, grad_accumulation,
+                         steps_done, last};
+  st = adjoint_steps(h, tm, call, run, [&](int n, double* z) -> pfv_status {
     pfv::pfv_ctx_impl& cx = *h;
-    if (st == PFV_OK) {
-      // lambda^1 into the cell gradients; the right-hand side it leaves is acc o lambda^1
-      if (have_lam && grad_accumulation) stage_slab(0, cx.aj_sB.p);  // c^0
-      if (have_lam)
-        pfv::adjoint_step_rhs(cx, k, cx.mc_acc_i.p, cx.aj_lam.p, nullptr, nullptr, 0, cx.aj_sB.p, cx.aj_sA.p,
-                              grad_source ? cx.aj_gsrc.p : nullptr, grad_accumulation ? cx.aj_gacc.p : nullptr,
-                              cx.aj_r.p);
-      else
-        pfv::be_memset(cx.aj_r.p, 0, sizeof(double) * k * nc, cx.stream);
+    const pfv::Sweep& sw = *cx.sweep;
+    const double* valT = cx.valT_T.p;
+    const double* acc = cx.mc_acc_i.p;
+    double* out = cx.mc_nrm.p;
+    const bool has_core = sw.n_core > 0;
+    const int core = has_core ? sw.core_level : -1;
+    run.launches = pfv::sweep_apply_multi_t(cx, sw, core + 1, sw.nlev, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, z);
+    int core_it = 0;
+    if (has_core) {
+      pfv::sweep_core_zero(cx, sw, k, z);
+      const CoreRun cr = core_iterate(h, maxit, out, hst, [&] {
+        pfv::sweep_core_copy(cx, sw, k, z, cx.aj_prev.p);
+        pfv::sweep_core_multi_t(cx, sw, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, cx.aj_prev.p, z);
+      }, [&] {
+        pfv::sweep_core_norms_multi_t(cx, sw, cx.pat_T, valT, acc, k, cx.aj_r.p, z, out);
+      }, [&] { return adjoint_norms_pass(hst, k, 0.5 * rtol); });
+      core_it = cr.iterations;
+      run.core_total += core_it;
+      run.launches += 2;
+      if (!cr.settled) {  // (what the forward-peel levels would compute from this core is not judged)
+        adjoint_component_info(run.info, hst, k, core_it);
+        cx.err = "adjoint step " + std::to_string(n) + ": the cyclic core of " + std::to_string(sw.n_core) +
+                 " cells did not settle in " + std::to_string(core_it) + " iterations";
+        return PFV_ERR_NOT_CONVERGED;
+      }
+      run.launches += pfv::sweep_apply_multi_t(cx, sw, 0, core, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, z);
     }
-    ms = tm->stop(cx.stream);
-    tm.reset();
-    if (st == PFV_OK) {
-      auto cells_out = [&](double* to, const double* from) {
-        pfv::multi_deinterleave(cx, (int64_t)nc, k, from, cx.mc_c.p);
-        vec_out(h, to, cx.mc_c.p, k * nc);
-      };
-      if (grad_c0) cells_out(grad_c0, cx.aj_r.p);
-      if (grad_source) cells_out(grad_source, cx.aj_gsrc.p);
-      if (grad_accumulation) cells_out(grad_accumulation, cx.aj_gacc.p);
-      if (grad_bc_values) vec_out(h, grad_bc_values, cx.aj_gbc.p, k * nf);
-      if (grad_flux) vec_out(h, grad_flux, cx.aj_gq.p, nf);
-    }
-    pfv::be_sync(cx.stream);
-    upwind_drop_transport(h, true);
+    pfv::sweep_residual_norms_multi(cx, cx.pat_T, valT, acc, k, cx.aj_r.p, z, out);  // (valT: the image under S^T)
+    be_d2h(hst.data(), out, sizeof(double) * hst.size(), cx.stream);
+    adjoint_component_info(run.info, hst, k, has_core ? core_it : 1);
+    return adjoint_accept(h, run.info, hst, k, rtol, n);
+  }, [&](double* z) {
+    if (grad_bc_values) pfv::adjoint_grad_bc(*h, k, d_q, z, h->aj_gbc.p);
+    if (grad_flux) pfv::adjoint_grad_flux(*h, k, h->mc_bc.p, z, h->aj_sB.p, h->aj_gq.p);
+  }, [&] {
+    if (grad_bc_values) vec_out(h, grad_bc_values, h->aj_gbc.p, k * nf);
+    if (grad_flux) vec_out(h, grad_flux, h->aj_gq.p, nf);
   });
-  if (steps_done) *steps_done = completed;
-  if (last)
-    for (int a = 0; a < k; ++a) {
-      last[a] = info[(size_t)a];
-      if (completed > 0) last[a].solve_ms = ms / completed;
+  h->stats.transport_adjoint_ms = run.ms;
+  h->stats.transport_adjoint_steps = run.completed;
+  h->stats.transport_adjoint_core_iterations = run.core_total;
+  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, order_ms);
+  return st;
+}
+
+// ---- the adjoint of the reactive step: one transposed k x k sweep in reverse flow order per step (sweep.inc) ----------
+// The frame is that of pfv_transport_adjoint_multi with the row, the acceptance test and the core of
+// pfv_transport_advance_react in the transposed system M^T lambda^n = g^n + acc o lambda^{n+1}: the rows read valT and a
+// ReactPar that holds K^T (sweep_row_react<K, Descending>), the image and the scale g~_a = r_a - rho sum_{b != a} K_ba
+// lambda_b come from sweep_react_image on the same two.  After an accepted step the face kernels take the mobility and
+// the two rate gradients are added in step order (adjoint_grad_rate, adjoint_grad_rate_weight).
+pfv_status pfv_transport_adjoint_react(pfv_ctx* h, const double* q, int k, const double* bc_values,
+                                       const double* accumulation, const double* mobility, const double* rate,
+                                       const double* rate_weight, int n_steps, int64_t n_obs, const int32_t* obs_cells,
+                                       const double* loads, const double* states, double rtol, int maxit,
+                                       double* grad_c0, double* grad_source, double* grad_bc_values,
+                                       double* grad_accumulation, double* grad_flux, double* grad_rate,
+                                       double* grad_rate_weight, int32_t* steps_done, pfv_solve_info* last) {
+  if (steps_done) *steps_done = 0;
+  std::unique_ptr<pfv::Timer> tm;
+  bool touched = false;
+  double order_ms = 0.0;
+  const double* d_q = nullptr;
+  size_t nc = 0, nf = 0;
+  pfv::ReactPar par, parT;
+  pfv_status st = guarded(h, [&] {
+    upwind_supported(h);
+    if (h->subface_bc) throw Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
+    require(h->have_upwind, "pfv_upwind_discretize first");
+    require(h->upw_ncomp == 1, "the components share one discretization: pfv_upwind_discretize with num_components = 1");
+    const std::string bad = pfv::react_check(k, rate, mobility);  // (the caller's K, not its transpose)
+    if (!bad.empty()) throw Error(PFV_ERR_ARGUMENT, bad);
+    require(bc_values && accumulation, "bc_values and accumulation are required");
+    require(n_steps >= 0, "bad argument");
+    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
+    require(loads != nullptr || n_steps == 0, "loads is required");
+    require(states || !grad_accumulation, "grad_accumulation needs states (c^0 .. c^N)");
+    require(states || !grad_flux, "grad_flux needs states (c^0 .. c^N)");
+    require(states || !grad_rate, "grad_rate needs states (c^0 .. c^N)");
+    require(states || !grad_rate_weight, "grad_rate_weight needs states (c^0 .. c^N)");
+    nc = (size_t)h->nc;
+    nf = (size_t)h->nf;
+    if ((int64_t)(k + 1) * (int64_t)std::max(nc, nf) >= (int64_t(1) << 31))
+      throw Error(PFV_ERR_UNSUPPORTED, "(k + 1) x cells (faces) beyond int32 indices");
+    par = pfv::react_make(k, rate, mobility);
+    parT = par;
+    for (int a = 0; a < k; ++a)
+      for (int b = 0; b < k; ++b) parT.K[a * k + b] = par.K[b * k + a];
+    be_h2d(h->rc_par.ensure(sizeof(par) / sizeof(double)), &par, sizeof(par), h->stream);
+    be_h2d(h->rc_parT.ensure(sizeof(parT) / sizeof(double)), &parT, sizeof(parT), h->stream);
+    adjoint_take_loads(h, k, n_steps, n_obs, obs_cells, loads);
+    if (q) vec_in(h, h->rc_q.ensure(nf), q, nf);
+    vec_in(h, h->rc_bc.ensure(k * nf), bc_values, k * nf);  // component-major, as they came
+    vec_in(h, h->rc_acc_in.ensure(k * nc), accumulation, k * nc);
+    if (rate_weight) vec_in(h, h->rc_rho.ensure(nc), rate_weight, nc);
+    d_q = q ? h->rc_q.p : h->upw_q.p;
+    pfv::upwind_face_cells(*h);
+    int32_t off[pfv::kReactChecks];  // (the call has no state to check: the accumulation stands in, off[2] says nothing)
+    pfv::sweep_react_check_inputs(*h, d_q, k, h->rc_bc.p, h->rc_acc_in.p, rate_weight ? h->rc_rho.p : nullptr,
+                                  h->rc_acc_in.p, h->rc_par.p, off);
+    auto comp = [&](int32_t v) { return std::to_string(v / k) + ", component " + std::to_string(v % k); };
+    if (off[0] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, "accumulation must be positive: cell " + comp(off[0]));
+    if (off[1] != 0x7f7f7f7f)
+      throw Error(PFV_ERR_ARGUMENT, "rate_weight must not be negative: cell " + std::to_string(off[1]));
+    if (off[3] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, "bc_values is not finite on face " + comp(off[3]));
+    if (off[4] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, pfv::kUnmarkedInflowFace + std::to_string(off[4]));
+    tm = std::make_unique<pfv::Timer>();
+    tm->start(h->stream);
+    // A = div diag(q) U without accumulation, once per call; its transposed values beside it
+    upwind_drop_transport(h, true);
+    touched = true;
+    pfv::upwind_assemble(*h, d_q, h->rc_bc.p, nullptr, nullptr, nullptr);
+    values_changed(h, Windows::drop);
+    pfv::multi_interleave(*h, (int64_t)nc, k, h->rc_acc_in.p, h->rc_acc.ensure(k * nc));
+    const size_t nnz = (size_t)std::max<int64_t>(h->pat_T.nnz, 1);
+    if (!h->have_tpos_T) {
+      pfv::sweep_transpose_positions(*h, h->pat_T, h->tpos_T.ensure(nnz));
+      h->have_tpos_T = true;
     }
-  h->stats.transport_adjoint_ms = ms;
-  h->stats.transport_adjoint_steps = completed;
-  h->stats.transport_adjoint_core_iterations = core_total;
-  sweep_step_stats(h, n_steps > 0 ? launches : -1, order_ms);
-  return step_status(h, st, err, st2);
+    pfv::sweep_transpose_values(*h, h->pat_T.nnz, h->tpos_T.p, h->val[PFV_MAT_TRANSPORT_SYSTEM].p, h->valT_T.ensure(nnz));
+    adjoint_take_slots(h, n_obs, obs_cells);
+    for (pfv::Buf<double>* b : {&h->aj_lam, &h->aj_lam2, &h->aj_r, &h->rc_prev, &h->rc_g, &h->rc_F, &h->mc_c})
+      b->ensure(k * nc);
+    if (states) {
+      h->aj_sA.ensure(k * nc);
+      h->aj_sB.ensure(k * nc);
+      if (!h->vectors_on_device) h->aj_state_in.ensure(k * nc);
+    }
+    if (grad_source) pfv::be_memset(h->aj_gsrc.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
+    if (grad_accumulation) pfv::be_memset(h->aj_gacc.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
+    if (grad_bc_values) pfv::be_memset(h->aj_gbc.ensure(k * nf), 0, sizeof(double) * k * nf, h->stream);
+    if (grad_flux) pfv::be_memset(h->aj_gq.ensure(nf), 0, sizeof(double) * nf, h->stream);
+    if (grad_rate) pfv::be_memset(h->aj_gK.ensure((size_t)k * k), 0, sizeof(double) * k * k, h->stream);
+    if (grad_rate_weight) pfv::be_memset(h->aj_grho.ensure(nc), 0, sizeof(double) * nc, h->stream);
+    h->rc_out.ensure(2 * (size_t)k + 1);
+    transport_order(h, d_q, order_ms);
+  });
+  if (st != PFV_OK) {
+    if (touched) upwind_drop_transport(h, true);  // (A without accumulation: not a system to be solved with)
+    return st;
+  }
+
+  AdjointRun run;
+  std::vector<double> hst(2 * (size_t)k + 1);
+  const double* rho = rate_weight ? h->rc_rho.p : nullptr;
+  const AdjointCall call{k, n_steps, n_obs, obs_cells, states, h->rc_acc.p, grad_c0, grad_source, grad_accumulation,
+                         steps_done, last};
+  st = adjoint_steps(h, tm, call, run, [&](int n, double* z) -> pfv_status {
+    pfv::pfv_ctx_impl& cx = *h;
+    const pfv::Sweep& sw = *cx.sweep;
+    const double* valT = cx.valT_T.p;
+    const double* acc = cx.rc_acc.p;
+    double* out = cx.rc_out.p;
+    int32_t* status = reinterpret_cast<int32_t*>(out + 2 * k);
+    const bool has_core = sw.n_core > 0;
+    const int core = has_core ? sw.core_level : -1;
+    pfv::ReactRow A{cx.pat_T.indptr, cx.pat_T.indices, sw.lev(false), valT, cx.diag_t.p, acc, rho,
+                    cx.aj_r.p, nullptr, z, status};
+    pfv::ReactRow Ac = A;  // the core level, with the previous iterate
+    Ac.c_prev = cx.rc_prev.p;
+    pfv::be_memset(status, 0x7f, sizeof(double), cx.stream);
+    run.launches = pfv::sweep_apply_react(cx, sw, core + 1, sw.nlev, k, A, parT, pfv::Descending{});
+    int core_it = 0;
+    if (has_core) {
+      pfv::sweep_core_zero(cx, sw, k, z);
+      const CoreRun cr = core_iterate(h, maxit, out, hst, [&] {
+        pfv::sweep_core_copy(cx, sw, k, z, cx.rc_prev.p);
+        pfv::sweep_levels_react(cx, sw, core, core + 1, k, Ac, parT, pfv::Descending{});
+      }, [&] {
+        pfv::sweep_react_image(cx, cx.pat_T, valT, k, acc, rho, cx.aj_r.p, cx.rc_parT.p, z, A.lev, core, cx.rc_g.p,
+                               cx.rc_F.p, true);
+        pfv::sweep_react_norms(cx, cx.nc, k, cx.rc_g.p, cx.rc_F.p, out);
+      }, [&] { return adjoint_norms_pass(hst, k, 0.5 * rtol); });
+      core_it = cr.iterations;
+      run.core_total += core_it;
+      run.launches += 2;
+      if (!cr.settled) {  // (what the forward-peel levels would compute from this core is not judged)
+        adjoint_component_info(run.info, hst, k, core_it);
+        cx.err = "adjoint step " + std::to_string(n) + ": the cyclic core of " + std::to_string(sw.n_core) +
+                 " cells did not settle in " + std::to_string(core_it) + " iterations";
+        return PFV_ERR_NOT_CONVERGED;
+      }
+      run.launches += pfv::sweep_apply_react(cx, sw, 0, core, k, A, parT, pfv::Descending{});
+    }
+    pfv::sweep_react_image(cx, cx.pat_T, valT, k, acc, rho, cx.aj_r.p, cx.rc_parT.p, z, A.lev, -1, cx.rc_g.p, cx.rc_F.p,
+                           true);
+    pfv::sweep_react_norms(cx, cx.nc, k, cx.rc_g.p, cx.rc_F.p, out);
+    be_d2h(hst.data(), out, sizeof(double) * hst.size(), cx.stream);
+    adjoint_component_info(run.info, hst, k, has_core ? core_it : 1);  // from hst: (g~_a, g~_a), (F_a, F_a)
+    int32_t cell;
+    std::memcpy(&cell, hst.data() + 2 * k, sizeof(cell));
+    if (cell != 0x7f7f7f7f) {
+      cx.err = "adjoint step " + std::to_string(n) + ": the block of cell " + std::to_string(cell) +
+               " has a pivot that is not positive and finite";
+      return PFV_ERR_NOT_CONVERGED;
+    }
+    return adjoint_accept(h, run.info, hst, k, rtol, n);
+  }, [&](double* z) {
+    pfv::pfv_ctx_impl& cx = *h;
+    if (grad_bc_values) pfv::adjoint_grad_bc(cx, k, d_q, z, cx.aj_gbc.p, cx.rc_par.p);
+    if (grad_flux) pfv::adjoint_grad_flux(cx, k, cx.rc_bc.p, z, cx.aj_sB.p, cx.aj_gq.p, cx.rc_par.p);
+    if (grad_rate) pfv::adjoint_grad_rate(cx, k, rho, z, cx.aj_sB.p, cx.aj_gK.p);
+    if (grad_rate_weight)
+      pfv::adjoint_grad_rate_weight(cx, k, cx.rc_par.p + pfv::kReactMax, z, cx.aj_sB.p, cx.aj_grho.p);
+  }, [&] {
+    if (grad_bc_values) vec_out(h, grad_bc_values, h->aj_gbc.p, k * nf);
+    if (grad_flux) vec_out(h, grad_flux, h->aj_gq.p, nf);
+    if (grad_rate_weight) vec_out(h, grad_rate_weight, h->aj_grho.p, nc);
+    if (grad_rate) be_d2h(grad_rate, h->aj_gK.p, sizeof(double) * k * k, h->stream);  // (host memory, as rate is)
+  });
+  h->stats.transport_react_adjoint_ms = run.ms;
+  h->stats.transport_react_adjoint_steps = run.completed;
+  h->stats.transport_react_adjoint_core_iterations = run.core_total;
+  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, order_ms);
+  return st;
 }
 
 // ---- advection-diffusion on one handle (advdiff.inc) -----------------------------------------------------------

@@ -934,6 +934,13 @@ static void sweep_nl_check_inputs(pfv_ctx_impl& c, const double* d_q, const doub
 //   core   rows of the core level (c_prev != nullptr) take their in-core neighbours from c_prev, the previous
 //          iterate: block Jacobi, independent of the scheduling.
 //   status the lowest row with a pivot that is not positive and finite (it cannot happen with finite admissible data)
+//   Dir    Ascending: the step itself, upstream = lev[j] < lev[i].  Descending: the row of the transposed system
+//          M^T lambda = r of pfv_transport_adjoint_react -- val is valT (sweep_transpose_values), the cells that are
+//          known are those with lev[j] > lev[i], and the caller hands a ReactPar that holds K^T, so that the block is
+//          B_i^T and the elimination below is shared.  B_i^T is a strictly ROW-diagonally-dominant M-matrix: row
+//          dominance is inherited by every Schur complement, so each pivot stays at least its row's excess, the growth
+//          factor of the unpivoted elimination is at most 2 (Wilkinson), and there is still no pivoted path.  With
+//          K = 0 and w = 1 the row gives the bits of sweep_row_multi_t.
 struct ReactRow {
   const int32_t *ip, *ix, *lev;
   const double *val, *diag, *acc, *rho, *rhs;  // rho may be nullptr (1)
@@ -942,7 +949,7 @@ struct ReactRow {
   int32_t* status;
 };
 
-template <int K>
+template <int K, class Dir = Ascending>
 PFV_FN void sweep_row_react(int32_t i, const ReactRow& A, const ReactPar& P) {
   const int32_t li = A.lev[i];
   const int64_t p = (int64_t)i * K;
@@ -964,7 +971,8 @@ PFV_FN void sweep_row_react(int32_t i, const ReactRow& A, const ReactPar& P) {
 #pragma unroll
     for (int t = 0; t < kNlcGroup; ++t) {
       const int32_t lj = A.lev[j[t]];
-      const double* src = lj < li ? A.c : (A.c_prev && lj == li && j[t] != i ? A.c_prev : nullptr);
+      const bool known = Dir::reverse ? lj > li : lj < li;
+      const double* src = known ? A.c : (A.c_prev && lj == li && j[t] != i ? A.c_prev : nullptr);
       up[t] = src && e0 + t < e_end ? src + (int64_t)j[t] * K : nullptr;
     }
 #pragma unroll
@@ -1017,34 +1025,39 @@ PFV_FN void sweep_row_react(int32_t i, const ReactRow& A, const ReactPar& P) {
   if (bad) atomic_min_i32(A.status, i);
 }
 
-// levels [l0, l1) of the order by the launch rule (sweep_levels); the kernel holds ReactRow and ReactPar by value
-template <int K>
+// levels [l0, l1) of the order by the launch rule (sweep_levels); the kernel holds ReactRow and ReactPar by value.
+// Dir as in sweep_levels: Descending takes a run of levels from last to first with the transposed row.
+template <int K, class Dir>
 static void sweep_levels_react_k(pfv_ctx_impl& c, const Sweep& sw, int l0, int l1, const ReactRow& A_,
                                  const ReactPar& P_) {
   const ReactRow A = A_;
   const ReactPar P = P_;
-  sweep_levels(c, sw, false, l0, l1, OnePerRow{}, PFV_LAMBDA(int32_t i, int) { sweep_row_react<K>(i, A, P); });
+  sweep_levels(c, sw, false, l0, l1, OnePerRow{}, PFV_LAMBDA(int32_t i, int) { sweep_row_react<K, Dir>(i, A, P); },
+               Dir{});
 }
 
+template <class Dir = Ascending>
 static void sweep_levels_react(pfv_ctx_impl& c, const Sweep& sw, int l0, int l1, int k, const ReactRow& A,
-                               const ReactPar& P) {
+                               const ReactPar& P, Dir = Dir{}) {
   switch (k) {
-    case 1: sweep_levels_react_k<1>(c, sw, l0, l1, A, P); break;
-    case 2: sweep_levels_react_k<2>(c, sw, l0, l1, A, P); break;
-    case 3: sweep_levels_react_k<3>(c, sw, l0, l1, A, P); break;
-    case 4: sweep_levels_react_k<4>(c, sw, l0, l1, A, P); break;
-    case 5: sweep_levels_react_k<5>(c, sw, l0, l1, A, P); break;
-    case 6: sweep_levels_react_k<6>(c, sw, l0, l1, A, P); break;
-    case 7: sweep_levels_react_k<7>(c, sw, l0, l1, A, P); break;
-    case 8: sweep_levels_react_k<8>(c, sw, l0, l1, A, P); break;
+    case 1: sweep_levels_react_k<1, Dir>(c, sw, l0, l1, A, P); break;
+    case 2: sweep_levels_react_k<2, Dir>(c, sw, l0, l1, A, P); break;
+    case 3: sweep_levels_react_k<3, Dir>(c, sw, l0, l1, A, P); break;
+    case 4: sweep_levels_react_k<4, Dir>(c, sw, l0, l1, A, P); break;
+    case 5: sweep_levels_react_k<5, Dir>(c, sw, l0, l1, A, P); break;
+    case 6: sweep_levels_react_k<6, Dir>(c, sw, l0, l1, A, P); break;
+    case 7: sweep_levels_react_k<7, Dir>(c, sw, l0, l1, A, P); break;
+    case 8: sweep_levels_react_k<8, Dir>(c, sw, l0, l1, A, P); break;
     default: throw Error(PFV_ERR_ARGUMENT, "k must lie in 1 .. 8");
   }
 }
 
-// the launch plan's levels in [from, to).  Returns the launches.
+// the launch plan's levels in [from, to) (Descending: from last to first).  Returns the launches.
+template <class Dir = Ascending>
 static int sweep_apply_react(pfv_ctx_impl& c, const Sweep& sw, int from, int to, int k, const ReactRow& A,
-                             const ReactPar& P) {
-  return sweep_plan_range(sw, from, to, [&](int l0, int l1) { sweep_levels_react(c, sw, l0, l1, k, A, P); });
+                             const ReactPar& P, Dir = Dir{}) {
+  return sweep_plan_range(sw, from, to, [&](int l0, int l1) { sweep_levels_react(c, sw, l0, l1, k, A, P, Dir{}); },
+                          Dir{});
 }
 
 // After the sweep, per (row, a) in stored order: the image t_a = acc_a c_a + w_a (A c_a) + rho (K c)_a, of which
@@ -1052,10 +1065,12 @@ static int sweep_apply_react(pfv_ctx_impl& c, const Sweep& sw, int from, int to,
 // against once its partners are known (a daughter that starts from nothing has rhs_a = 0 and lives on the second term).
 // par: ReactPar on the device (w, then K), read under run-time indices.  upto >= 0 (the core's stop test, before the
 // levels behind the core have a c): rows behind level upto give g = F = 0, rows before it F = 0, and a row's entries
-// beyond its own level (the stored zeros of the downstream side) are skipped.
+// beyond its own level (the stored zeros of the downstream side) are skipped.  descending (the transposed system: val
+// is valT, par holds K^T, the levels are taken from last to first): "behind", "before" and "beyond" change sides -- the
+// entries of the lower levels are the ones that do not exist yet.
 static void sweep_react_image(pfv_ctx_impl& c, const CsrPattern& P, const double* val, int k, const double* acc,
                               const double* rho, const double* rhs, const double* par, const double* x,
-                              const int32_t* lev, int upto, double* g, double* F) {
+                              const int32_t* lev, int upto, double* g, double* F, bool descending = false) {
   const int32_t* ip = P.indptr;
   const int32_t* ix = P.indices;
   const double* w = par;
@@ -1064,7 +1079,7 @@ static void sweep_react_image(pfv_ctx_impl& c, const CsrPattern& P, const double
     const int32_t i = (int32_t)(t / k);
     const int a = (int)(t % k);
     const int32_t li = lev[i];
-    if (upto >= 0 && li > upto) {
+    if (upto >= 0 && (descending ? li < upto : li > upto)) {
       g[t] = 0.0;
       F[t] = 0.0;
       return;
@@ -1072,7 +1087,7 @@ static void sweep_react_image(pfv_ctx_impl& c, const CsrPattern& P, const double
     double s = 0.0;
     for (int e = ip[i]; e < ip[i + 1]; ++e) {
       const int32_t j = ix[e];
-      if (upto < 0 || lev[j] <= li) s += val[e] * x[(int64_t)j * k + a];
+      if (upto < 0 || (descending ? lev[j] >= li : lev[j] <= li)) s += val[e] * x[(int64_t)j * k + a];
     }
     const int64_t p = (int64_t)i * k;
     double kc = 0.0, off = 0.0;
@@ -1083,7 +1098,8 @@ static void sweep_react_image(pfv_ctx_impl& c, const CsrPattern& P, const double
     }
     const double rw = rho ? rho[i] : 1.0, r = rhs[t];
     g[t] = r - rw * off;
-    F[t] = upto >= 0 && li < upto ? 0.0 : r - (acc[t] * x[t] + w[a] * s + rw * kc);
+    const bool done = upto >= 0 && (descending ? li > upto : li < upto);
+    F[t] = done ? 0.0 : r - (acc[t] * x[t] + w[a] * s + rw * kc);
   });
 }
 
@@ -1320,8 +1336,10 @@ static int64_t adjoint_first_nonfinite(pfv_ctx_impl& c, int64_t n, const double*
 
 // grad_bc_values[a][f] -= sum_i B[i, f] lambda[i, a], B = div (rhs_neu + rhs_dir diag(q)): the transpose of
 // upwind_bref_multi.  One work item per (face, component); a face reads the cells on its two sides (a boundary face
-// has one).  gbc is component-major [k][nf], lam interleaved.
-static void adjoint_grad_bc(pfv_ctx_impl& c, int k, const double* d_q, const double* lam, double* gbc) {
+// has one).  gbc is component-major [k][nf], lam interleaved.  par (may be nullptr: every mobility 1): ReactPar on the
+// device -- the term is scaled by w_a, and an immobile component (w_a = 0) keeps its zeros.
+static void adjoint_grad_bc(pfv_ctx_impl& c, int k, const double* d_q, const double* lam, double* gbc,
+                            const double* par = nullptr) {
   const int64_t nf = c.nf;
   const uint8_t* cls = c.upw_cls;
   const int32_t* cnt = c.upw_cnt;
@@ -1330,6 +1348,8 @@ static void adjoint_grad_bc(pfv_ctx_impl& c, int k, const double* d_q, const dou
     const int64_t f = t / k, a = t % k;
     const unsigned cl = cls[f];
     if (!(cl & (UPW_NEU | UPW_DIRIN))) return;
+    const double wa = par ? par[a] : 1.0;
+    if (!(wa > 0.0)) return;
     double m = 0.0;
     if (cl & UPW_NEU) m = (double)(cnt[f] - cnt[nf + f]);
     if (cl & UPW_DIRIN) m += 1.0 * d_q[f];
@@ -1337,15 +1357,17 @@ static void adjoint_grad_bc(pfv_ctx_impl& c, int k, const double* d_q, const dou
     double s = 0.0;
     if (cp >= 0) s += m * lam[(int64_t)cp * k + a];
     if (cm >= 0) s -= m * lam[(int64_t)cm * k + a];
-    gbc[a * nf + f] -= s;
+    gbc[a * nf + f] -= wa * s;  // (w_a = 1: the bits of the unscaled term)
   });
 }
 
 // grad_flux[f] -= sum_a (lambda[p, a] - lambda[m, a]) cup[a, f] with p / m the cells on the +1 / -1 side of f and cup the
 // value the upwind rule takes at f: the upstream cell's c^n (interior and outflow faces), the boundary value (Dirichlet
 // inflow); a Neumann face gives 0.  One work item per face, the components summed in order.  bc is component-major.
+// par (may be nullptr: every mobility 1): ReactPar on the device -- component a enters with w_a, and an immobile one
+// (w_a = 0) is skipped, not multiplied: its boundary values are not read (they may be NaN).
 static void adjoint_grad_flux(pfv_ctx_impl& c, int k, const double* bc, const double* lam, const double* c_n,
-                              double* gq) {
+                              double* gq, const double* par = nullptr) {
   const int64_t nf = c.nf;
   const uint8_t* cls = c.upw_cls;
   const int32_t* up = c.upw_up;
@@ -1357,13 +1379,84 @@ static void adjoint_grad_flux(pfv_ctx_impl& c, int k, const double* bc, const do
     const int32_t u = up[f];
     double s = 0.0;
     for (int a = 0; a < k; ++a) {
+      const double wa = par ? par[a] : 1.0;
+      if (!(wa > 0.0)) continue;
       double d = 0.0;
       if (cp >= 0) d = lam[(int64_t)cp * k + a];
       if (cm >= 0) d -= lam[(int64_t)cm * k + a];
       const double cup = (cl & UPW_KEPT) ? c_n[(int64_t)u * k + a] : bc[a * nf + f];
-      s += d * cup;
+      s += (wa * d) * cup;  // (w_a = 1: the bits of d * cup)
     }
     gq[f] -= s;
+  });
+}
+
+// ---- the gradients of pfv_transport_adjoint_react with respect to the reaction term rho_i sum_b K_ab c_ib, after an
+// accepted step (lam = lambda^n, c_n = c^n, both interleaved):
+//     grad_rate_weight[i] -= sum_a lambda_ia sum_b K_ab c_ib      one work item per row, the sums in index order
+//     grad_rate[a][b]     -= sum_i rho_i lambda_ia c_ib           k^2 sums over all rows
+// The k^2 sums take a fixed partition that depends on the number of rows and k alone, in the manner of
+// sweep_norms_pairs: a workgroup takes a range of rows, slot g * k^2 + (a k + b) of it the rows lo + g, lo + g + G, ...
+// of the pair (a, b) (G = 256 / k^2), the G sums of a pair are folded pairwise in LDS, and one workgroup per pair adds
+// the workgroups' partial sums and subtracts the result from the pair's accumulator: the steps add in step order.  No
+// floating-point atomics, no per-thread array.  Km: the caller's K on the device (not the transposed one).
+static void adjoint_grad_rate_weight(pfv_ctx_impl& c, int k, const double* Km, const double* lam, const double* c_n,
+                                     double* grho) {
+  parallel_for(c.stream, c.nc, PFV_LAMBDA(int64_t i) {
+    const int64_t p = i * k;
+    double s = 0.0;
+    for (int a = 0; a < k; ++a) {
+      double kc = 0.0;
+      for (int b = 0; b < k; ++b) kc += Km[a * k + b] * c_n[p + b];
+      s += lam[p + a] * kc;
+    }
+    grho[i] -= s;
+  });
+}
+
+static void adjoint_grad_rate(pfv_ctx_impl& c, int k, const double* rho, const double* lam, const double* c_n,
+                              double* gK) {
+  stream_t s = c.stream;
+  const int64_t n = c.nc;
+  const int P = k * k, G = 256 / P, slots = G * P;
+  const int nb = (int)std::min<int64_t>(kGmresBlocks, (n * P + 2047) / 2048);
+  int fold = 1;
+  while (fold < G) fold <<= 1;
+  double* partial = c.red.ensure((size_t)kReactMax * kReactMax * kGmresBlocks + 64);
+  block_for<256>(s, nb, 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& w) {
+    double* sh = reinterpret_cast<double*>(w.lds);
+    const int64_t blk = w.item;
+    const int64_t lo = n * blk / nb, hi = n * (blk + 1) / nb;
+    PFV_LANES(slot, slots) {
+      const int pair = slot % P, g = slot / P;
+      const int a = pair / k, b = pair % k;
+      double sum = 0.0;
+      for (int64_t i = lo + g; i < hi; i += G) sum += ((rho ? rho[i] : 1.0) * lam[i * k + a]) * c_n[i * k + b];
+      sh[slot] = sum;
+    }
+    w.sync();
+    for (int o = fold >> 1; o > 0; o >>= 1) {
+      PFV_LANES(slot, slots) {
+        if (slot / P < o && slot / P + o < G) sh[slot] += sh[slot + o * P];
+      }
+      w.sync();
+    }
+    PFV_LANES(pair, P) { partial[(int64_t)pair * nb + blk] = sh[pair]; }
+    w.sync();
+  });
+  block_for<256>(s, P, 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& wc) {
+    double* sh = reinterpret_cast<double*>(wc.lds);
+    const int64_t m = wc.item;
+    double a = 0.0;
+    for (int i = wc.lane; i < nb; i += wc.width) a += partial[m * nb + i];
+    sh[wc.lane] = a;
+    wc.sync();
+    for (int o = wc.width >> 1; o > 0; o >>= 1) {
+      if (wc.lane < o) sh[wc.lane] += sh[wc.lane + o];
+      wc.sync();
+    }
+    if (wc.lane0()) gK[m] -= sh[0];
+    wc.sync();
   });
 }
 

@@ -466,6 +466,67 @@ class Upwind:
             raise
 
 
+    def adjoint_reactive_components(self, sd, data: dict, n_steps: int, accumulation, rate_matrix, loads,
+                                    rate_weight=None, mobility=None, obs_cells=None, states=None, bc_values=None,
+                                    want=("c0", "source", "bc_values"), rtol: float = 1e-12, maxit: int = 500,
+                                    raise_on_fail: bool = True):
+        """The adjoint of ``advance_reactive_components``: the gradients of
+        ``J = sum_{n=1..N} sum_a <loads[n-1, a], c_a^n[obs_cells]>`` through ``n_steps`` = N reactive steps, for the
+        cost of about one more run -- what a calibration of decay constants, exchange rates, the extent of a reactive
+        zone or inflow concentrations against breakthrough curves needs.  The step is linear in c, so the adjoint is
+        exact.  Per step, backwards in time, all k components are ONE transposed sweep in reverse flow order in which
+        every cell is one k x k solve with the transposed block (``M^T lambda^n = g^n + acc o lambda^{n+1}``): the levels
+        and the launches are those of the forward sweep.
+
+        ``accumulation``, ``rate_matrix``, ``rate_weight``, ``mobility`` and ``bc_values`` as in
+        ``advance_reactive_components`` (k is taken from ``loads``; the boundary values of an immobile component are
+        not read); ``loads``, ``obs_cells`` and ``states`` as in ``adjoint_components``.  ``want`` names the gradients:
+
+        - ``"c0"``, ``"source"``, ``"accumulation"`` (k, Nc) and ``"flux"`` (Nf,) as in ``adjoint_components``, the
+          flux term of component a weighted by its mobility ``w_a`` (an immobile component is skipped);
+        - ``"bc_values"`` (k, Nf): ``-w_a sum_n B^T lambda_a^n``, all zero for an immobile component;
+        - ``"rate_matrix"`` (k, k): ``-sum_n sum_i rate_weight_i lambda_ia^n c_ib^n``.  It is the plain partial
+          derivative with respect to EVERY entry of K, structural zeros included, without regard to the sign and
+          column-sum conditions: chain it to your own rate parameters (a decay constant l of the chain a -> b enters as
+          ``K_aa = l, K_ba = -l``, so ``dJ/dl = g[a, a] - g[b, a]``);
+        - ``"rate_weight"`` (Nc,): ``-sum_n sum_a lambda_ia^n (K c_i^n)_a``.
+
+        ``"accumulation"``, ``"flux"``, ``"rate_matrix"`` and ``"rate_weight"`` need ``states``, which are not checked
+        for finiteness.  The gradient with respect to the mobility is not offered.  The cells of a cyclic core are
+        iterated by block Jacobi, at most ``maxit`` times per step.  Returns (grads, info) as ``adjoint_components``.
+        Afterwards the handle holds no assembled transport system; the flow order stays."""
+        pd = data[PARAMETERS][self.keyword]
+        nc, nf = sd.num_cells, sd.num_faces
+        loads = np.asarray(loads, dtype=np.float64)
+        if loads.ndim != 3 or loads.shape[0] != int(n_steps):
+            raise ValueError(f"loads must have shape ({int(n_steps)}, k, n_obs), not {loads.shape}")
+        k = loads.shape[1]
+        if not 1 <= k <= 8:
+            raise ValueError(f"the number of coupled components must lie in 1 .. 8, not {k} (loads has shape {loads.shape})")
+
+        def per_component(name, a, n):
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape == (n,):
+                return np.broadcast_to(a, (k, n))
+            if a.shape != (k, n):
+                raise ValueError(f"{name} must have shape ({n},) or ({k}, {n}), not {a.shape}")
+            return a
+
+        if accumulation is None:
+            raise ValueError("accumulation is required")
+        acc = per_component("accumulation", accumulation, nc)
+        bv = per_component("bc_values", pd["bc_values"] if bc_values is None else bc_values, nf)
+        try:
+            return self.context(sd).transport_adjoint_react(n_steps, acc, bv, rate_matrix, loads, rate_weight=rate_weight,
+                                                            mobility=mobility, obs_cells=obs_cells, states=states,
+                                                            q=self._flux(sd, pd), want=want, rtol=rtol, maxit=maxit,
+                                                            raise_on_fail=raise_on_fail)
+        except _lib.PorefvError as e:
+            if e.status == 4:
+                raise ValueError(e.message) from None
+            raise
+
+
 def _flux_function(flux_function):
     """(kind, parameters) of the C ABI for what ``advance_saturation`` takes as ``flux_function``"""
     if isinstance(flux_function, str) and flux_function == "linear":

@@ -1,0 +1,66 @@
+"""CPU suite for the adjoint of the reactive transport step (pfv_transport_adjoint_react, csrc/sweep.inc:
+sweep_row_react<K, Descending>) on the host-emulation build of the same kernels; tests/test_gpu_react_adjoint.py runs
+the same cases on the HIP library."""
+import pytest
+
+from tests import _parity as P
+from tests import _react_adjoint_cases as C
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return P.emulation_library()
+
+
+def test_judge_formulas_against_complex_step(lib):
+    C.formulas_against_complex_step(lib)
+
+
+@pytest.mark.parametrize("n,k", [(3, 3), (3, 4), (3, 8), (4, 1), (4, 3), (4, 4), (4, 8)])
+def test_exact_against_the_judge(lib, n, k):
+    C.exact(lib, n, k)
+
+
+def test_reduces_to_the_uncoupled_adjoint(lib):
+    C.reduces_to_uncoupled(lib)
+
+
+def test_immobile_partner(lib):
+    C.immobile_partner(lib)
+
+
+def test_adjoint_identity_with_own_forward(lib):
+    C.identity_with_own_forward(lib)
+
+
+def test_line_closed_form(lib):
+    C.line_closed_form(lib)
+
+
+def test_launch_forms_and_determinism(lib):
+    C.launch_forms_and_determinism(lib)
+
+
+@pytest.mark.parametrize("name", ["cyclic12", "rotation8"])
+def test_cyclic_core(lib, name):
+    C.cyclic_core(lib, name)
+
+
+def test_observation_forms(lib):
+    C.observation_forms(lib)
+
+
+def test_refusals(lib):
+    C.refusals(lib)
+
+
+def test_handle(lib):
+    C.handle(lib)
+
+
+def test_flow_system_is_untouched(lib):
+    C.flow_system_is_untouched(lib)
+
+
+def test_device_vectors(lib):
+    C.device_vectors(lib)

@@ -8,6 +8,7 @@ not a test: no thresholds.
 
     python tools/bench_transport.py [--n-side 69] [--steps 20] [--no-host] [--precond sweep] [--components 8]
                                     [--saturation [--components 4]] [--reactive] [--adjoint]
+                                    [--reactive --adjoint]
 
 --precond sweep: after the Jacobi-BiCGStab steps, the same steps from the same state with the flow-ordered sweep
 (PFV_PRECOND_SWEEP) -- order-build ms, levels, core cells, launches per sweep, ms per step -- and again with one launch
@@ -38,6 +39,12 @@ volume.  ms per step of both from pfv_stats (best and median of --reps, the firs
 cells -- once with the three gradients that need no states (c0, source, bc_values) and once with all five, which stages
 one slab of states per step: ms per step of the three from pfv_stats (best and median of --reps, the first repeat
 dropped), the launches of the sweep and the other kernels per step for both directions.
+
+--reactive --adjoint (together; the two blocks above are then NOT run, and the JSON has the key "reactive_adjoint" in
+place of "reactive" and "adjoint"): alternating in one loop, the forward reactive
+k = 4 step of --reactive's network (transport_advance_react), its adjoint (transport_adjoint_react) on 16 observation
+cells without states (c0, source, bc_values) and the adjoint with all seven gradients: ms per step of the three from
+pfv_stats (best and median of --reps, the first repeat dropped), levels and launches.
 """
 from __future__ import annotations
 
@@ -229,7 +236,58 @@ def main():
             sat["components"].append(entry)
         out["saturation"] = sat
         ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the saturation call leaves no system behind)
-    if a.reactive:
+    if a.reactive and a.adjoint:
+        kc, n_obs = 4, 16
+        acc_k = np.array([(1.0 + 0.5 * j) * acc for j in range(kc)])
+        bv_k = np.array([tbv * (j + 1) / kc for j in range(kc)])
+        l0, l1, l2, kf, kb = 20.0, 10.0, 2.0, 30.0, 15.0  # the network and the weight of --reactive
+        Kr = np.zeros((kc, kc))
+        Kr[0, 0], Kr[1, 0], Kr[3, 0] = l0 + kf, -l0, -kf
+        Kr[1, 1], Kr[2, 1] = l1, -l1
+        Kr[2, 2] = l2
+        Kr[3, 3], Kr[0, 3] = kb, -kb
+        mobility = np.array([1.0, 1.0, 1.0, 0.0])
+        pore_volume = 0.2 * g.cell_volumes
+        react = dict(rate_weight=pore_volume, mobility=mobility, rtol=1e-10)
+        states = np.empty((a.steps + 1, kc, nc))
+        states[0] = rng.random((kc, nc))
+        obs = np.sort(rng.permutation(nc)[:n_obs])
+        loads = rng.standard_normal((a.steps, kc, n_obs))
+        entry = {"k": kc, "observation_cells": n_obs}
+        try:
+            for s_ in range(a.steps):  # the states of the forward run, one step at a time
+                states[s_ + 1], rinfo = ctx.transport_advance_react(states[s_], 1, acc_k, bv_k, Kr, **react)
+            fwd_ms, adj3_ms, adj7_ms = [], [], []
+            for _ in range(a.reps + 1):  # (the first repeat warms up: dropped)
+                cr, rinfo = ctx.transport_advance_react(states[0], a.steps, acc_k, bv_k, Kr, raise_on_fail=False, **react)
+                fwd = ctx.stats()
+                fwd_ms.append(fwd["transport_react_ms"] / max(a.steps, 1))
+                g3, i3 = ctx.transport_adjoint_react(a.steps, acc_k, bv_k, Kr, loads, obs_cells=obs, raise_on_fail=False,
+                                                     **react)
+                adj3_ms.append(ctx.stats()["transport_react_adjoint_ms"] / max(a.steps, 1))
+                g7, i7 = ctx.transport_adjoint_react(a.steps, acc_k, bv_k, Kr, loads, obs_cells=obs, states=states,
+                                                     want=ctx.REACT_ADJOINT_GRADIENTS, raise_on_fail=False, **react)
+                adj = ctx.stats()
+                adj7_ms.append(adj["transport_react_adjoint_ms"] / max(a.steps, 1))
+            J = float(np.sum(loads * states[1:][:, :, obs]))
+            lin = float(np.sum(g7["c0"] * states[0]) + np.sum(g7["bc_values"] * bv_k))
+            entry.update({
+                "steps_done": i7["steps_done"], "forward_steps_done": rinfo["steps_done"],
+                "forward_reactive_ms_per_step": (min(fwd_ms[1:]), float(np.median(fwd_ms[1:]))),
+                "adjoint_ms_per_step_c0_source_bc": (min(adj3_ms[1:]), float(np.median(adj3_ms[1:]))),
+                "adjoint_ms_per_step_all_seven": (min(adj7_ms[1:]), float(np.median(adj7_ms[1:]))),
+                "levels": adj["sweep_levels"], "core_cells": adj["sweep_core_cells"],
+                "forward_launches_per_sweep": fwd["sweep_launches"], "adjoint_launches_per_sweep": adj["sweep_launches"],
+                "core_iterations": adj["transport_react_adjoint_core_iterations"],
+                "max_rel_residual_last_step": max(i7["rel_residual"]),
+                "identity_J_minus_products_relative": abs(J - lin) / max(abs(J), 1e-300),
+                "grad_rate_matrix": g7["rate_matrix"].tolist(),
+                "c0_bits_equal_between_the_two_adjoint_calls": bool(g3["c0"].tobytes() == g7["c0"].tobytes())})
+        except pa.PorefvError as e:
+            entry["error"] = e.message
+        out["reactive_adjoint"] = entry
+        ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the calls leave no system behind)
+    if a.reactive and not a.adjoint:
         kc = 4
         acc_k = np.array([(1.0 + 0.5 * j) * acc for j in range(kc)])
         bv_k = np.array([tbv * (j + 1) / kc for j in range(kc)])
@@ -268,7 +326,7 @@ def main():
             entry["error"] = e.message
         out["reactive"] = entry
         ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the reactive call leaves no system behind)
-    if a.adjoint:
+    if a.adjoint and not a.reactive:
         kc, n_obs = 4, 16
         acc_k = np.array([(1.0 + 0.5 * j) * acc for j in range(kc)])
         bv_k = np.array([tbv * (j + 1) / kc for j in range(kc)])

@@ -211,6 +211,10 @@ typedef struct {
   double transport_react_adjoint_ms; /* last pfv_transport_adjoint_react, all steps (HIP events) */
   int64_t transport_react_adjoint_steps; /* ... accepted adjoint steps */
   int64_t transport_react_adjoint_core_iterations; /* ... block Jacobi iterations of the cyclic core, summed over the steps */
+  int64_t amg_galerkin_ap;        /* 1: the last AMG setup formed the first coarse operator as P^T (A_s P), one Galerkin product
+                                     over AP (PFV_AMG_GALERKIN_AP, default on: scalar systems on kept aggregate maps whose AP is
+                                     built).  0: the pairwise passes formed it (first setup, changed pattern or matching
+                                     switches, block systems, sharded solves, PFV_AMG_FP32=0, PFV_AMG_POST_AP=0) */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);

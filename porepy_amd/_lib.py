@@ -93,7 +93,7 @@ class Stats(C.Structure):
                 ("transport_adjoint_ms", C.c_double), ("transport_adjoint_steps", C.c_int64),
                 ("transport_adjoint_core_iterations", C.c_int64), ("amg_ap_nnz", C.c_int64),
                 ("transport_react_adjoint_ms", C.c_double), ("transport_react_adjoint_steps", C.c_int64),
-                ("transport_react_adjoint_core_iterations", C.c_int64)]
+                ("transport_react_adjoint_core_iterations", C.c_int64), ("amg_galerkin_ap", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

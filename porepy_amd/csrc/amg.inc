@@ -93,6 +93,7 @@ struct AmgSwitches {
   bool galerkin_batched = true, filter_unroll = true, dense_lds = true;
   int64_t gather_rows = kAmgGatherRowsDefault;  // PFV_AMG_GATHER_ROWS, >= 1
   bool post_ap = true;               // PFV_AMG_POST_AP: finest post-smoothing through A_s P (amg_build_ap / amg_post_ap)
+  bool galerkin_ap = true;           // PFV_AMG_GALERKIN_AP: kept maps: the first coarse operator as P^T (A_s P) (amg_coarsen_level)
 };
 
 static AmgSwitches amg_read_switches(int bs) {
@@ -140,6 +141,7 @@ static AmgSwitches amg_read_switches(int bs) {
   w.dense_lds = on("PFV_AMG_DENSE_LDS", 1);
   w.gather_rows = std::max<int64_t>(1, env_int("PFV_AMG_GATHER_ROWS", (int)kAmgGatherRowsDefault));
   w.post_ap = on("PFV_AMG_POST_AP", 1);
+  w.galerkin_ap = on("PFV_AMG_GALERKIN_AP", 1);
   return w;
 }
 
@@ -266,6 +268,8 @@ struct Amg {
   unsigned long long gal_for_sum = 0;
   bool gal_use = false;
   size_t gal_k = 0;
+  int gal_route = 0;  // how the setup that recorded gal_sizes formed level 1 (0: passes, 1: from AP): the record is a sequence
+                      // in call order, and the two routes make different calls (amg_gal_route)
   unsigned long long filt_win_sum = 0;  // checksum of the filtered pattern filt_win was built for (0: unknown)
   // what the saved aggregate maps belong to: size, block size, setup parameters, checksum of the
   // pattern and the context's symbolic epoch (a re-built discretization never reuses)
@@ -314,6 +318,11 @@ struct Amg {
   Buf<int32_t> ap_ptr, ap_col, ap_len;
   Buf<int64_t> ap_pos;
   Buf<double> ap_val;
+  // the same rows with the sums of the double values of A_s, where the first coarse operator is formed from them
+  // (amg_coarsen_level; entry order and packing of ap_val)
+  bool ap64_ok = false;
+  Buf<double> ap_val64, ap_row64;  // (ap_row64: the sums in the rows' slots before packing, beside wk.tval)
+  bool galerkin_ap = false;  // the last setup formed level 1 as P^T (A_s P)
   const CsrPattern* sysP = nullptr;  // the matrix the last setup was given (before the filter; pfv_amg_level reads it)
   const double* sysV = nullptr;
 };
@@ -358,6 +367,15 @@ static void amg_gal_record(Amg* amg, int64_t ncr, int64_t annz, int maxcap, int6
   if (amg->gal_k < amg->gal_sizes.size()) amg->gal_sizes.resize(amg->gal_k);
   amg->gal_sizes.push_back(Amg::GalSizes{ncr, annz, nnz, maxcap});
   amg->gal_k = amg->gal_sizes.size();
+}
+// Before the first product of a setup: a record made on the other route does not describe this setup's calls.
+static void amg_gal_route(Amg& amg, int route) {
+  if (amg.gal_route != route) {
+    amg.gal_use = false;
+    amg.gal_sizes.clear();
+    amg.gal_k = 0;
+  }
+  amg.gal_route = route;
 }
 
 // ---- graph access: cell i, k-th neighbour block (full bs x bs blocks, see header comment)
@@ -501,13 +519,15 @@ static void amg_members(pfv_ctx_impl& c, AmgWork& wk, const int32_t* agg, int64_
 struct Amg;
 static bool amg_gal_cached(Amg* amg, int64_t ncr, int64_t annz, int* maxcap, int64_t* nnz);
 static void amg_gal_record(Amg* amg, int64_t ncr, int64_t annz, int maxcap, int64_t nnz);
-static void amg_galerkin(pfv_ctx_impl& c, const AmgSwitches& sw, AmgWork& wk, const CsrPattern& A, const double* val,
-                         int bs, const int32_t* agg, const int32_t* mptr, const int32_t* mem, int64_t nagg, CsrPattern& Ac,
-                         Buf<double>& valc, Buf<double>& dinvc, Amg* sizes = nullptr) {
+// The fine matrix comes as its arrays: (ip, ix, val) with `annz` an upper bound of its entries that is known on the host
+// (the exact count where the caller has it; the product from AP only knows the bound, amg_coarsen_level).  agg == nullptr:
+// the columns are coarse unknowns already.
+static void amg_galerkin_csr(pfv_ctx_impl& c, const AmgSwitches& sw, AmgWork& wk, const int32_t* ip, const int32_t* ix,
+                             int64_t annz, const double* val, int bs, const int32_t* agg, const int32_t* mptr,
+                             const int32_t* mem, int64_t nagg, CsrPattern& Ac, Buf<double>& valc, Buf<double>& dinvc,
+                             Amg* sizes = nullptr) {
   stream_t s = c.stream;
   const int64_t ncr = nagg * bs;  // coarse rows
-  const int32_t* ip = A.indptr;
-  const int32_t* ix = A.indices;
   int32_t* cap = wk.cap.ensure(ncr + 1);
   int32_t* cnt = wk.cnt.ensure(ncr + 1);
   int64_t* tptr = wk.tptr.ensure(ncr + 1);
@@ -528,9 +548,9 @@ static void amg_galerkin(pfv_ctx_impl& c, const AmgSwitches& sw, AmgWork& wk, co
   exclusive_scan<int32_t, int64_t>(s, c.scratch, cap, tptr, (size_t)ncr);
   int maxcap_c = 0;
   int64_t nnz_c = 0;
-  const bool known = amg_gal_cached(sizes, ncr, A.nnz, &maxcap_c, &nnz_c);
+  const bool known = amg_gal_cached(sizes, ncr, annz, &maxcap_c, &nnz_c);
   const int maxcap = known ? maxcap_c : read_scalar<int32_t>(s, st + 8);
-  const int64_t ttot = A.nnz;  // every fine row feeds exactly one coarse row (= tptr[ncr], no need to read it)
+  const int64_t ttot = annz;  // every fine row feeds exactly one coarse row (>= tptr[ncr], no need to read it)
   if (maxcap > 4096) throw Error(PFV_ERR_UNSUPPORTED, "AMG: more than 4096 entries feed one coarse row");
   int32_t* tcol = wk.tcol.ensure(std::max<int64_t>(ttot, 1));
   double* tval = wk.tval.ensure(std::max<int64_t>(ttot, 1));
@@ -593,7 +613,7 @@ static void amg_galerkin(pfv_ctx_impl& c, const AmgSwitches& sw, AmgWork& wk, co
         kcs[k] = 0;
         if (cidx[k] >= 0) {
           const int cj = cidx[k] / bs;
-          kcs[k] = agg[cj] * bs + (cidx[k] - cj * bs);
+          kcs[k] = agg ? agg[cj] * bs + (cidx[k] - cj * bs) : cidx[k];
         }
       }
 #pragma unroll
@@ -611,7 +631,7 @@ static void amg_galerkin(pfv_ctx_impl& c, const AmgSwitches& sw, AmgWork& wk, co
         PFV_LANES(t, len) {
           const int cidx = ix[p0 + t];
           const int cj = cidx / bs;
-          const unsigned long long kc = (unsigned long long)(unsigned)(agg[cj] * bs + (cidx - cj * bs));
+          const unsigned long long kc = (unsigned long long)(unsigned)(agg ? agg[cj] * bs + (cidx - cj * bs) : cidx);
           key[m + t] = (kc << 32) | (unsigned)(m + t);
           v0[m + t] = val[p0 + t];
         }
@@ -663,7 +683,7 @@ static void amg_galerkin(pfv_ctx_impl& c, const AmgSwitches& sw, AmgWork& wk, co
   });
   exclusive_scan<int32_t, int64_t>(s, c.scratch, cnt, cptr, (size_t)ncr);
   const int64_t nnz = known ? nnz_c : read_scalar<int64_t>(s, cptr + ncr);
-  if (!known) amg_gal_record(sizes, ncr, A.nnz, maxcap, nnz);
+  if (!known) amg_gal_record(sizes, ncr, annz, maxcap, nnz);
   if (nnz >= (int64_t(1) << 31)) throw Error(PFV_ERR_UNSUPPORTED, "AMG: coarse matrix with more than 2^31 entries");
   Ac.nrows = Ac.ncols = ncr;
   Ac.nnz = nnz;
@@ -680,6 +700,11 @@ static void amg_galerkin(pfv_ctx_impl& c, const AmgSwitches& sw, AmgWork& wk, co
     }
   });
   Ac.max_row = maxcap;  // upper bound (saves a host read; nothing sizes itself by it)
+}
+static void amg_galerkin(pfv_ctx_impl& c, const AmgSwitches& sw, AmgWork& wk, const CsrPattern& A, const double* val,
+                         int bs, const int32_t* agg, const int32_t* mptr, const int32_t* mem, int64_t nagg, CsrPattern& Ac,
+                         Buf<double>& valc, Buf<double>& dinvc, Amg* sizes = nullptr) {
+  amg_galerkin_csr(c, sw, wk, A.indptr, A.indices, A.nnz, val, bs, agg, mptr, mem, nagg, Ac, valc, dinvc, sizes);
 }
 
 static void amg_diag_inverse(pfv_ctx_impl& c, const CsrPattern& P, const double* val, double* dinv) {
@@ -1054,6 +1079,7 @@ static void amg_filter(pfv_ctx_impl& c, const AmgSwitches& sw, const CsrPattern&
 }
 
 static void amg_estimate_omegas(pfv_ctx_impl& c, Amg& amg);
+static void amg_build_ap(pfv_ctx_impl& c, Amg& amg, bool want64);
 static void amg_spmv(pfv_ctx_impl& c, const Amg& amg, const AmgLevel& L, const double* x, double* y,
                      const double* smooth_b);
 static double* amg_cycle(pfv_ctx_impl& c, Amg& amg, size_t l, const double* b, double* x, bool x_is_presmoothed = false,
@@ -1358,6 +1384,28 @@ static int amg_coarsen_level(pfv_ctx_impl& c, Amg& amg, size_t l, bool reuse) {
   // (the member lists of a kept map are kept with it: a sort of cur_cells pairs per pass otherwise -- with the
   // composed map and the level's own member lists below 1.3 ms of kernels and ~200 launches of a setup on kept maps)
   const bool members_reuse = reuse && L.members_kept && w.members_reuse;
+  // Level 0 on kept maps and member lists: nothing reads the intermediate matrices of the passes (the matching that
+  // would is skipped), and the last product is P^T A_s P = P^T (A_s P) with P the composed map -- and AP = A_s P is
+  // built for the cycle anyway (amg_build_ap), its columns coarse unknowns already, sorted and summed per aggregate.
+  // So level 1 is ONE product over AP (its double-precision sums, ap_val64) with the member lists of the composed map,
+  // instead of three over A_s and its pair matrices: a coarse row gathers ~72 entries instead of ~166 at 2 M
+  // tetrahedra.  Same pattern as the pass route; values differ by the order of the additions.  The entries of AP are
+  // known on the device only: the scratch of the product is sized by nnz(A_s).
+  if (l == 0 && !D && members_reuse && L.pmap_count > 0 && w.galerkin_ap && curP == L.P && curV == L.val &&
+      !(L.pmap_n[L.pmap_count - 1] > 0.85 * cells)) {
+    const int64_t nc = L.pmap_n[L.pmap_count - 1];
+    L.nc_cells = nc;
+    amg_build_ap(c, amg, true);
+    if (amg.ap_ok && amg.ap64_ok) {
+      amg_gal_route(amg, 1);
+      amg_galerkin_csr(c, w, wk, amg.ap_ptr, amg.ap_col, L.P->nnz, amg.ap_val64, bs, nullptr, L.mptr, L.mem, nc, wk.P[0],
+                       wk.V[0], wk.D[0], &amg);
+      amg.galerkin_ap = true;
+      return 0;
+    }
+    L.nc_cells = 0;  // (AP not built, or without its double sums: the passes)
+  }
+  if (l == 0 && !D) amg_gal_route(amg, 0);
   for (int pass = 0; pass < (reuse ? L.pmap_count : passes_here); ++pass) {
     int64_t nagg;
     if (reuse) {
@@ -1414,9 +1462,14 @@ static int amg_coarsen_level(pfv_ctx_impl& c, Amg& amg, size_t l, bool reuse) {
 // A failed allocation leaves the cycle on its two-launch form.
 constexpr int kApKeys = 128;  // entries of a row ranked in LDS (longer rows: one lane inserts them one by one)
 constexpr int kApChunk = 8;   // ... entries per unrolled trip of the ranking loops
-static void amg_build_ap(pfv_ctx_impl& c, Amg& amg) {
+// want64: also ap_val64, the sums of the DOUBLE values of A_s over the same runs in the same entry order, ranked and
+// packed by the same two kernels -- the input of the Galerkin product that forms level 1 from AP (amg_coarsen_level).
+// Its rows are formed in a buffer of their own (the value slots of the passes change hands with the levels' matrices:
+// one of them grown to nnz(A_s) here would be allocated anew by every setup).  When the storage cannot be had, AP is
+// built for the cycle alone (ap64_ok stays false: the passes form level 1).
+static void amg_build_ap(pfv_ctx_impl& c, Amg& amg, bool want64) {
   stream_t s = c.stream;
-  amg.ap_ok = false;
+  amg.ap_ok = amg.ap64_ok = false;
   amg.ap_nnz = 0;
   AmgLevel& L = *amg.lev[0];
   if (!amg.sw.post_ap || amg.bs != 1 || amg.dist || amg.no_filter || amg.finest_cells_parent > 0 || !L.v32 ||
@@ -1425,7 +1478,7 @@ static void amg_build_ap(pfv_ctx_impl& c, Amg& amg) {
   const int64_t n = L.n, fnnz = L.P->nnz;
   int32_t *sx, *al, *cp, *cx;
   int64_t* pos;
-  double *sv, *cv;
+  double *sv, *cv, *sv64 = nullptr, *cv64 = nullptr;
   try {
     sx = amg.wk.tcol.ensure(std::max<int64_t>(fnnz, 1));
     sv = amg.wk.tval.ensure(std::max<int64_t>(fnnz, 1));
@@ -1440,13 +1493,30 @@ static void amg_build_ap(pfv_ctx_impl& c, Amg& amg) {
 #endif
     amg.ap_col.release();
     amg.ap_val.release();
+    amg.ap_val64.release();
+    amg.ap_row64.release();
     return;
+  }
+  if (want64) {
+    try {
+      sv64 = amg.ap_row64.ensure(std::max<int64_t>(fnnz, 1));
+      cv64 = amg.ap_val64.ensure(std::max<int64_t>(fnnz, 1));
+    } catch (const Error&) {
+#ifndef PFV_EMULATE
+      (void)hipGetLastError();
+#endif
+      amg.ap_val64.release();
+      amg.ap_row64.release();
+      want64 = false;
+    }
   }
   const int32_t* fp = L.P->indptr;
   const int32_t* ix = L.P->indices;
   const float* v32 = L.v32;
+  const double* v64 = L.val;
   const int32_t* agg = L.agg;
-  wave_for<16>(s, n, (kApKeys + kApChunk) * (2 * sizeof(int32_t) + sizeof(float)) + 16, PFV_LAMBDA(const WaveCtx& w) {
+  auto rank_rows = PFV_LAMBDA(const WaveCtx& w, auto with64) {
+    constexpr bool W64 = decltype(with64)::value;
     const int64_t r = w.item;
     const int p0 = fp[r], len = fp[r + 1] - p0;
     if (len > kApKeys) {
@@ -1455,17 +1525,21 @@ static void amg_build_ap(pfv_ctx_impl& c, Amg& amg) {
         for (int e = 0; e < len; ++e) {
           const int32_t k = agg[ix[p0 + e]];
           const double v = (double)v32[p0 + e];
+          const double vd = W64 ? v64[p0 + e] : 0.0;
           int q = 0;
           while (q < cnt && sx[p0 + q] < k) ++q;
           if (q < cnt && sx[p0 + q] == k) {
             sv[p0 + q] += v;
+            if constexpr (W64) sv64[p0 + q] += vd;
           } else {
             for (int m = cnt; m > q; --m) {
               sx[p0 + m] = sx[p0 + m - 1];
               sv[p0 + m] = sv[p0 + m - 1];
+              if constexpr (W64) sv64[p0 + m] = sv64[p0 + m - 1];
             }
             sx[p0 + q] = k;
             sv[p0 + q] = 0.0 + v;
+            if constexpr (W64) sv64[p0 + q] = 0.0 + vd;
             ++cnt;
           }
         }
@@ -1473,19 +1547,27 @@ static void amg_build_ap(pfv_ctx_impl& c, Amg& amg) {
       }
       return;
     }
-    // (the loops over the row run in chunks of kApChunk without early exits: the LDS reads of a chunk are in flight
-    // together -- entry by entry with a break, every read waited for the one before it.  What the kernel is bound by is
-    // the instructions of the len x len comparisons, so the ranking loop tests as little as it can: an entry that is
-    // not the first of its aggregate carries bit 31, which takes it out of "first entries with a smaller key" by the
-    // unsigned comparison alone, and kApChunk sentinels of all ones behind the row need no test of the bounds.)
-    uint32_t* kh = reinterpret_cast<uint32_t*>(w.lds);  // [kApKeys + kApChunk] aggregate of every entry | bit 31
-    int32_t* dupf = reinterpret_cast<int32_t*>(kh + kApKeys + kApChunk);  // [kApKeys] 1: an earlier entry has this aggregate
-    float* vs = reinterpret_cast<float*>(dupf + kApKeys + kApChunk);      // [kApKeys + kApChunk]
+    // What the kernel is bound by is the instructions of its comparisons, so it makes as few as it can.  Only the FIRST
+    // entry of every aggregate is ranked and summed (~8 of the 18 entries of a row on tetrahedra): a first pass marks
+    // them in a bit mask (entry e against the entries before it), they are compacted by the population counts of the
+    // mask, and the ranking loop runs over the compacted list -- one trip of the lane group where the whole row took two.
+    // (The loops over the row run in chunks of kApChunk without early exits: the LDS reads of a chunk are in flight
+    // together -- entry by entry with a break, every read waited for the one before it.  An entry that is not the
+    // first of its aggregate carries bit 31, which takes it out of "first entries with a smaller key" by the unsigned
+    // comparison alone, and kApChunk sentinels of all ones behind the row need no test of the bounds.)
+    unsigned long long* mask = reinterpret_cast<unsigned long long*>(w.lds);  // [2] bit e: entry e is the first of its aggregate
+    uint32_t* kh = reinterpret_cast<uint32_t*>(mask + 2);                 // [kApKeys + kApChunk] aggregate of every entry | bit 31
+    int32_t* fst = reinterpret_cast<int32_t*>(kh + kApKeys + kApChunk);   // [kApKeys] the first entries, in entry order
+    float* vs = reinterpret_cast<float*>(fst + kApKeys + kApChunk);       // [kApKeys + kApChunk]
+    double* vd = reinterpret_cast<double*>(vs + kApKeys + kApChunk);      // [kApKeys + kApChunk] (with64 only)
+    static_assert(kApKeys <= 128, "the mask of first entries has two words");
     PFV_LANES(e, len) {
       kh[e] = (uint32_t)agg[ix[p0 + e]];
       vs[e] = v32[p0 + e];
+      if constexpr (W64) vd[e] = v64[p0 + e];
     }
     PFV_LANES(u, kApChunk) kh[len + u] = 0xffffffffu;
+    PFV_LANES(i, 2) mask[i] = 0ull;
     w.lsync();
     PFV_LANES(e, len) {
       const uint32_t k = kh[e];
@@ -1494,36 +1576,50 @@ static void amg_build_ap(pfv_ctx_impl& c, Amg& amg) {
 #pragma unroll
         for (int u = 0; u < kApChunk; ++u) dup |= (q0 + u < e && kh[q0 + u] == k) ? 1 : 0;
       }
-      dupf[e] = dup;
+      if (!dup) atomic_or_u64(mask + (e >> 6), 1ull << (e & 63));
     }
     w.lsync();
-    PFV_LANES(e, len) kh[e] |= dupf[e] ? 0x80000000u : 0u;
-    w.lsync();
+    const unsigned long long m0 = mask[0], m1 = mask[1];
+    const int nf = popcount64(m0) + popcount64(m1);
     PFV_LANES(e, len) {
-      const uint32_t ke = kh[e];
-      const uint32_t k = ke & 0x7fffffffu;
-      int rank = 0, cnt = 0;
-      double sum = 0.0;
+      const unsigned long long word = e < 64 ? m0 : m1;
+      const unsigned long long bit = 1ull << (e & 63);
+      if (word & bit) fst[popcount64(word & (bit - 1ull)) + (e < 64 ? 0 : popcount64(m0))] = e;
+      else kh[e] |= 0x80000000u;
+    }
+    w.lsync();
+    PFV_LANES(j, nf) {
+      const uint32_t k = kh[fst[j]];
+      int rank = 0;
+      double sum = 0.0, sum64 = 0.0;
       for (int q0 = 0; q0 < len; q0 += kApChunk) {
 #pragma unroll
         for (int u = 0; u < kApChunk; ++u) {
           const uint32_t kq = kh[q0 + u];
           const float vq = vs[q0 + u];
           rank += kq < k ? 1 : 0;
-          cnt += (int)((kq >> 31) ^ 1u);
           // (for a first entry no earlier one has its key: the whole row in entry order is its run in entry order)
           if ((kq & 0x7fffffffu) == k) sum += (double)vq;
+          if constexpr (W64) {
+            const double dq = vd[q0 + u];
+            if ((kq & 0x7fffffffu) == k) sum64 += dq;
+          }
         }
       }
-      if (ke == k) {
-        sx[p0 + rank] = (int32_t)k;
-        sv[p0 + rank] = sum;
-      }
-      if (e == 0) al[r] = cnt;
+      sx[p0 + rank] = (int32_t)k;
+      sv[p0 + rank] = sum;
+      if constexpr (W64) sv64[p0 + rank] = sum64;
     }
-    if (len == 0 && w.lane0()) al[r] = 0;
+    if (w.lane0()) al[r] = nf;
     w.lsync();
-  });
+  };
+  const size_t lds32 = (kApKeys + kApChunk) * (2 * sizeof(int32_t) + sizeof(float)) + 16;
+  if (want64) {
+    wave_for<16>(s, n, lds32 + (kApKeys + kApChunk) * sizeof(double),
+                 PFV_LAMBDA(const WaveCtx& w) { rank_rows(w, std::true_type{}); });
+  } else {
+    wave_for<16>(s, n, lds32, PFV_LAMBDA(const WaveCtx& w) { rank_rows(w, std::false_type{}); });
+  }
   exclusive_scan<int32_t, int64_t>(s, c.scratch, al, pos, (size_t)n);
   wave_for<8>(s, n, 16, PFV_LAMBDA(const WaveCtx& w) {
     const int64_t r = w.item;
@@ -1532,6 +1628,7 @@ static void amg_build_ap(pfv_ctx_impl& c, Amg& amg) {
     PFV_LANES(q, al[r]) {
       cx[o + q] = sx[p0 + q];
       cv[o + q] = sv[p0 + q];
+      if (cv64) cv64[o + q] = sv64[p0 + q];
     }
     if (w.lane0()) {
       cp[r] = (int32_t)o;
@@ -1539,6 +1636,7 @@ static void amg_build_ap(pfv_ctx_impl& c, Amg& amg) {
     }
   });
   amg.ap_ok = true;
+  amg.ap64_ok = want64;
 }
 
 // y = tt + omega D^-1 (b - (t + alpha AP xs)) with tt = x0 + alpha P xs, xs = xc (+ xc2), x0 = x on entry and t = A_s x0:
@@ -1684,7 +1782,7 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
   tm.start(s);
   AmgDist* D = amg.dist.get();  // coupled hierarchy of a sharded solve (amg_dist.inc): A = owned rows x (owned + halo)
   amg.bs = bs;
-  amg.valid = amg.dense_ok = amg.ap_ok = false;
+  amg.valid = amg.dense_ok = amg.ap_ok = amg.ap64_ok = amg.galerkin_ap = false;
   amg.ap_nnz = 0;
   amg.sysP = &A;
   amg.sysV = val;
@@ -1725,7 +1823,7 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
     if (D ? (l >= 1 && l == D->kgather) : (L.n <= w.coarse_target || (int)l + 1 >= kAmgMaxLevels)) break;
     const int slot = amg_coarsen_level(c, amg, l, reuse);
     if (slot < 0) break;  // coarsening stalled: this level is the coarsest
-    if (l == 0) amg_build_ap(c, amg);
+    if (l == 0 && !amg.ap_ok) amg_build_ap(c, amg, false);  // (kept maps: built before the product that reads it)
     AmgLevel& Ln = amg_level(amg, l + 1);
     Ln.n = L.nc_cells * bs;
     // the last intermediate matrix becomes the new level (its old buffers go back to the slot)
@@ -1751,6 +1849,7 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
   // (entries of AP: a read for the statistics only, where the setup waits for its own end anyway)
   if (amg.ap_ok) amg.ap_nnz = read_scalar<int64_t>(s, amg.ap_pos.p + amg.lev[0]->n);
   c.stats.amg_ap_nnz = amg.ap_nnz;
+  c.stats.amg_galerkin_ap = amg.galerkin_ap ? 1 : 0;
   amg.setup_ms = tm.stop(s);
 }
 

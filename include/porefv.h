@@ -215,6 +215,9 @@ typedef struct {
                                      over AP (PFV_AMG_GALERKIN_AP, default on: scalar systems on kept aggregate maps whose AP is
                                      built).  0: the pairwise passes formed it (first setup, changed pattern or matching
                                      switches, block systems, sharded solves, PFV_AMG_FP32=0, PFV_AMG_POST_AP=0) */
+  double transport_nl_adjoint_ms; /* last pfv_transport_adjoint_nl, all steps (HIP events) */
+  int64_t transport_nl_adjoint_steps; /* ... accepted adjoint steps */
+  int64_t transport_nl_adjoint_core_iterations; /* ... Jacobi iterations of the cyclic core, summed over the steps */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -811,6 +814,58 @@ pfv_status pfv_transport_adjoint_react(pfv_ctx* h, const double* q, int k, const
                                        double* grad_c0, double* grad_source, double* grad_bc_values,
                                        double* grad_accumulation, double* grad_flux, double* grad_rate,
                                        double* grad_rate_weight, int32_t* steps_done, pfv_solve_info* last);
+
+/* The adjoint of pfv_transport_advance_nl: every gradient of J = sum_{n=1..N} <g^n, s^n[obs_cells]> through n_steps = N
+ * saturation steps acc o (s^n - s^{n-1}) + M f(s^n) + b_ref(q, f(bv)) = source, M = A(q) + diag(sink).  The step is
+ * linearised about the forward states: with d^n = f'(s^n) (one-sided, as the step's own Newton uses it) and
+ * lambda^{N+1} = 0 the call solves, for n = N .. 1,
+ *     (diag(acc) + diag(d^n) M^T) lambda^n = g^n + acc o lambda^{n+1}.
+ * In reverse flow order cell i is one division once the cells downstream of it are known (csrc/sweep.inc: sweep_row_nl_t),
+ *     lambda_i = (r_i - d_i sum_{lev[j] > lev[i]} valT[e] lambda_j) / (acc_i + d_i (A_ii + sink_i)):
+ * the levels, the launch plan and the launch count are those of the forward sweep, and there is no root-finding.  d^n
+ * and f(s^n) come from one streaming pass over the step's slab of states.  The Jacobian is strictly column-diagonally
+ * dominant (acc > 0), so the cells of a cyclic core converge under Jacobi on their transposed rows, from zero, until
+ * ||residual_core|| <= rtol ||rhs|| / 2 or maxit iterations.  A step is accepted when ||r - J^T lambda|| <= rtol ||r||
+ * (0 <= 0 counts); one host read per step.  A cell at or beyond a residual saturation (d_i = 0) is acc_i lambda_i = r_i.
+ *   fluxfn_kind / fluxfn_params / n_params, q, bc_values, accumulation and sink are those of pfv_transport_advance_nl,
+ * with its rules and texts (the source does not enter).  loads [N][n_obs] and obs_cells are those of
+ * pfv_transport_adjoint_multi with one component.  states [N + 1][Nc], s^0 .. s^N, is REQUIRED (PFV_ERR_ARGUMENT when
+ * NULL with n_steps > 0); one slab is staged per step; it is NOT checked for range or finiteness.  fluxfn_params and
+ * grad_fluxfn are HOST memory; every other array follows pfv_set_vectors_on_device.
+ *   Gradients, each may be NULL (not wanted), all accumulated on the device without floating-point atomics, every sum
+ * in a fixed order; p / m are the cells of cell_faces sign +1 / -1 at a face (a missing cell contributes nothing):
+ *     grad_s0 [Nc]            acc o lambda^1
+ *     grad_source [Nc]        sum_n lambda^n
+ *     grad_bc_values [Nf]     Neumann face: -sum_n (rhs_neu^T div^T lambda^n)_f; Dirichlet inflow face:
+ *                             -sum_n (lambda^n[p] - lambda^n[m]) q_f f'(bv_f); 0 on every other face
+ *     grad_accumulation [Nc]  sum_n lambda^n o (s^{n-1} - s^n)
+ *     grad_sink [Nc]          -sum_n lambda^n o f(s^n); with sink == NULL the derivative at sink = 0
+ *     grad_flux [Nf]          -sum_n (lambda^n[p] - lambda^n[m]) phiup_f^n, phiup = f of the upstream cell's s^n on interior
+ *                             and outflow faces, f(bv_f) on a Dirichlet inflow face, 0 on a Neumann face
+ *     grad_fluxfn [6]         PFV_FLUXFN_COREY only (else PFV_ERR_ARGUMENT), in the order of its parameters:
+ *                             -sum_n [ sum_i (M^T lambda^n)_i df/dtheta(s_i^n)
+ *                                      + sum_{Dirichlet inflow f} (lambda^n[p] - lambda^n[m]) q_f df/dtheta(bv_f) ],
+ *                             df/dtheta analytic (csrc/fluxfn.h: fluxfn_eval_params), 0 where s_e lies outside (0, 1)
+ * All are derivatives on a FIXED branch: of the table's interval, of the side of a residual saturation, of the upstream
+ * side of every face.  They are the derivatives of J wherever no state sits on a table knot or a residual saturation
+ * and no q_f is exactly zero, and one-sided ones there.  The six sums of grad_fluxfn run over a fixed partition that
+ * depends on Nc and Nf alone and are added in step order: the result does not depend on the launch form or a repeat.
+ *   PFV_ERR_ARGUMENT (the text names the offender): what pfv_transport_advance_nl refuses in the flux function,
+ * accumulation, sink, bc_values and the inflow faces; an obs_cells entry out of range or repeated; a non-finite value
+ * in loads; missing states; grad_fluxfn with another kind.  PFV_ERR_UNSUPPORTED as pfv_transport_advance_nl.
+ *   steps_done: the adjoint steps completed.  A refused step returns PFV_ERR_NOT_CONVERGED and writes no gradient.
+ * last (one entry, may be NULL): iterations = 1 for an acyclic flux, else the core iterations of the last step;
+ * rel_residual the measured ||r - J^T lambda|| / ||r||.  Handle rules as pfv_transport_adjoint_multi: the flow order is
+ * built if needed and stays, the transposed positions stay with the pattern, the selection and the flow system are left
+ * alone, no transport system is left behind.  pfv_stats: transport_nl_adjoint_* and the sweep_* fields (sweep_launches:
+ * the forward sweep's on an acyclic flux). */
+pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
+                                    int n_params, const double* bc_values, const double* accumulation,
+                                    const double* sink, int n_steps, int64_t n_obs, const int32_t* obs_cells,
+                                    const double* loads, const double* states, double rtol, int maxit, double* grad_s0,
+                                    double* grad_source, double* grad_bc_values, double* grad_accumulation,
+                                    double* grad_sink, double* grad_flux, double* grad_fluxfn, int32_t* steps_done,
+                                    pfv_solve_info* last);
 
 /* ---- Advection-diffusion step on the device (csrc/advdiff.inc) ---------------------------------------------------
  * One handle carries the transport keyword: its diffusion discretization (pfv_mpfa_discretize or pfv_tpfa_discretize

@@ -52,6 +52,7 @@ EXPORTS = [
     "pfv_advdiff_assemble", "pfv_advdiff_advance", "pfv_advdiff_face_flux", "pfv_resident_flux",
     "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl", "pfv_transport_advance_nl_multi",
     "pfv_transport_advance_react", "pfv_transport_adjoint_multi", "pfv_transport_adjoint_react",
+    "pfv_transport_adjoint_nl",
 ]
 
 
@@ -93,7 +94,9 @@ class Stats(C.Structure):
                 ("transport_adjoint_ms", C.c_double), ("transport_adjoint_steps", C.c_int64),
                 ("transport_adjoint_core_iterations", C.c_int64), ("amg_ap_nnz", C.c_int64),
                 ("transport_react_adjoint_ms", C.c_double), ("transport_react_adjoint_steps", C.c_int64),
-                ("transport_react_adjoint_core_iterations", C.c_int64), ("amg_galerkin_ap", C.c_int64)]
+                ("transport_react_adjoint_core_iterations", C.c_int64), ("amg_galerkin_ap", C.c_int64),
+                ("transport_nl_adjoint_ms", C.c_double), ("transport_nl_adjoint_steps", C.c_int64),
+                ("transport_nl_adjoint_core_iterations", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -329,6 +332,10 @@ def _bind(lib: C.CDLL) -> C.CDLL:
                                                 _dp, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                                 C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
     lib.pfv_transport_adjoint_react.restype = C.c_int
+    lib.pfv_transport_adjoint_nl.argtypes = [_h, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int64, _ip, _dp,
+                                             _dp, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                             C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
+    lib.pfv_transport_adjoint_nl.restype = C.c_int
     lib.pfv_advdiff_assemble.argtypes = [_h, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pfv_advdiff_assemble.restype = C.c_int
     lib.pfv_advdiff_advance.argtypes = [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(C.c_int32),
@@ -1721,6 +1728,75 @@ class Context:
         out = {"steps_done": done.value, "converged": all(bool(i.converged) for i in infos),
                "iterations": [i.iterations for i in infos], "rel_residual": [i.rel_residual for i in infos],
                "solve_ms": [i.solve_ms for i in infos]}
+        if st != 0 and (raise_on_fail or st != 6):
+            try:
+                self._check(st)
+            except PorefvError as e:
+                e.info = out
+                raise
+        return grads, out
+
+    NL_ADJOINT_GRADIENTS = ("s0", "source", "bc_values", "accumulation", "sink", "flux", "flux_function")
+
+    def transport_adjoint_nl(self, n_steps: int, accumulation, bc_values, fluxfn_kind: int, fluxfn_params, loads, states,
+                             sink=None, obs_cells=None, q=None, want=("s0", "source", "bc_values"), rtol=1e-12,
+                             maxit=500, raise_on_fail=True):
+        """The adjoint of ``transport_advance_nl`` (pfv_transport_adjoint_nl): the gradients of
+        ``J = sum_n <loads[n-1], s^n[obs_cells]>`` through ``n_steps`` saturation steps, by one transposed sweep on the
+        slopes ``f'(s^n)`` in reverse flow order per step.  ``accumulation``: Nc, ``bc_values``: Nf, ``loads``:
+        N x n_obs, ``obs_cells``: n_obs cell indices or None (every cell), ``states``: (N + 1) x Nc (s^0 .. s^N,
+        required, not checked for range or finiteness), ``sink``: Nc or None, ``q``: Nf or None (the flux of the
+        discretization).  ``want``: names out of ``NL_ADJOINT_GRADIENTS``; "flux_function" (the six Corey parameters,
+        in their order) needs FLUXFN_COREY.  Returns (grads, info): grads[name] of shape Nc ("s0", "source",
+        "accumulation", "sink"), Nf ("bc_values", "flux") or 6 ("flux_function"); info with ``steps_done``,
+        ``converged``, ``iterations`` and ``rel_residual``.  A refused step leaves the gradients zero."""
+        n_steps = int(n_steps)
+        if n_steps < 0:
+            raise ValueError("n_steps must not be negative")
+        acc = _f64(accumulation)
+        if acc.shape != (self.nc,):
+            raise ValueError(f"accumulation must have shape ({self.nc},), not {acc.shape}")
+        bv = _f64(bc_values)
+        if bv.shape != (self.nf,):
+            raise ValueError(f"bc_values must have shape ({self.nf},), not {bv.shape}")
+        par = np.ascontiguousarray(fluxfn_params, dtype=np.float64).ravel()
+        obs = None
+        if obs_cells is not None:
+            obs = np.ascontiguousarray(obs_cells)
+            if obs.ndim != 1 or not np.issubdtype(obs.dtype, np.integer):
+                raise ValueError("obs_cells must be a one-dimensional array of cell indices")
+            big = obs[(obs < -2 ** 31) | (obs >= 2 ** 31)]
+            if big.size:
+                raise ValueError(f"obs_cells: {int(big[0])} is out of range (0 .. {self.nc - 1})")
+            obs = obs.astype(np.int32)
+        n_obs = self.nc if obs is None else obs.size
+        ld = _f64(loads)
+        if ld.shape != (n_steps, n_obs):
+            raise ValueError(f"loads must have shape ({n_steps}, {n_obs}), not {ld.shape}")
+        if states is None:
+            raise ValueError("states (s^0 .. s^N) is required: the step is linearised about them")
+        stt = _f64(states)
+        if stt.shape != (n_steps + 1, self.nc):
+            raise ValueError(f"states must have shape ({n_steps + 1}, {self.nc}), not {stt.shape}")
+        want = tuple(want)
+        for name in want:
+            if name not in self.NL_ADJOINT_GRADIENTS:
+                raise ValueError(f"want: unknown gradient {name!r} (known: {', '.join(self.NL_ADJOINT_GRADIENTS)})")
+            if name == "flux_function" and int(fluxfn_kind) != FLUXFN_COREY:
+                raise ValueError('the gradient "flux_function" is that of the six Corey parameters: it needs a '
+                                 'CoreyFractionalFlow')
+        kq, pq = self._vec(q, self.nf, "the flux array", False)
+        kk, pk = self._vec(sink, self.nc, "sink", False)
+        shapes = {"s0": (self.nc,), "source": (self.nc,), "bc_values": (self.nf,), "accumulation": (self.nc,),
+                  "sink": (self.nc,), "flux": (self.nf,), "flux_function": (6,)}
+        grads = {name: np.zeros(shapes[name]) for name in self.NL_ADJOINT_GRADIENTS if name in want}
+        done, info = C.c_int32(0), SolveInfo()
+        st = self.lib.pfv_transport_adjoint_nl(
+            self._h, pq, int(fluxfn_kind), _ptr(par, _dp) if par.size else None, int(par.size), _ptr(bv, _dp),
+            _ptr(acc, _dp), pk, n_steps, n_obs, _ptr(obs, _ip), _ptr(ld, _dp), _ptr(stt, _dp), float(rtol), int(maxit),
+            *[_ptr(grads.get(name), _dp) for name in self.NL_ADJOINT_GRADIENTS], C.byref(done), C.byref(info))
+        out = {"steps_done": done.value, "iterations": info.iterations, "converged": bool(info.converged),
+               "rel_residual": info.rel_residual, "solve_ms": info.solve_ms}
         if st != 0 and (raise_on_fail or st != 6):
             try:
                 self._check(st)

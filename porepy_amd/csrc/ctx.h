@@ -363,6 +363,10 @@ struct pfv_ctx_impl {
   // from the rc_ buffers and the rest from the aj_ ones.  rc_parT: ReactPar with K^T; the accumulators of grad_rate
   // (k^2, row-major) and of grad_rate_weight [nc]
   Buf<double> rc_parT, aj_gK, aj_grho;
+  // the adjoint of the saturation step (pfv_transport_adjoint_nl) takes its inputs from the nl_ buffers and the rest from
+  // the aj_ ones (k = 1).  aj_d / aj_phi: f'(s^n) and f(s^n) of the step's slab; the accumulators of grad_sink [nc] and
+  // of grad_fluxfn (the six Corey parameters)
+  Buf<double> aj_d, aj_phi, aj_gsink, aj_gF;
 
   // ---- advection-diffusion (advdiff.inc): S = diag(acc) + div flux_D + w div diag(q) U on pat_A -------------------
   bool have_advdiff = false;         // val[PFV_MAT_ADVDIFF_SYSTEM], adv_diag, adv_rhs hold a system of the discretization

@@ -100,4 +100,27 @@ PFV_FN double fluxfn_eval(const FluxFn& F, double s, double* df) {
   return s;
 }
 
+// The derivatives of f(s) with respect to the six Corey parameters, out[0 .. 6) in the order s_wr, s_nr, n_w, n_n, mu_w,
+// mu_n (pfv_transport_adjoint_nl: grad_fluxfn).  With lw = se^n_w / mu_w, ln = (1 - se)^n_n / mu_n, tot = lw + ln:
+// df/dlw = ln / tot^2, df/dln = -lw / tot^2; the exponents enter through lw log se and ln log(1 - se), the viscosities
+// through -lw / mu_w and -ln / mu_n, the residual saturations through se with df/dse = f' / inv_span.  All six are 0
+// where se lies outside (0, 1), as f' of fluxfn_eval is: the clamp holds f there, and no log 0 is evaluated.  Another
+// kind has no such parameters: zeros.
+PFV_FN void fluxfn_eval_params(const FluxFn& F, double s, double out[6]) {
+  for (int k = 0; k < 6; ++k) out[k] = 0.0;
+  if (F.kind != PFV_FLUXFN_COREY) return;
+  const double se = (s - F.s_wr) * F.inv_span;
+  if (!(se > 0.0 && se < 1.0)) return;
+  const double lw = pow(se, F.n_w) * F.inv_mu_w, ln = pow(1.0 - se, F.n_n) * F.inv_mu_n;
+  const double tot = lw + ln, inv2 = 1.0 / (tot * tot);
+  const double f_lw = ln * inv2, f_ln = -lw * inv2;
+  const double f_se = (F.n_w * lw / se * ln + lw * F.n_n * ln / (1.0 - se)) * inv2;
+  out[0] = f_se * ((se - 1.0) * F.inv_span);
+  out[1] = f_se * (se * F.inv_span);
+  out[2] = f_lw * (lw * log(se));
+  out[3] = f_ln * (ln * log(1.0 - se));
+  out[4] = -f_lw * (lw * F.inv_mu_w);
+  out[5] = -f_ln * (ln * F.inv_mu_n);
+}
+
 }  // namespace pfv

@@ -2283,6 +2283,150 @@ pfv_status pfv_transport_adjoint_react(pfv_ctx* h, const double* q, int k, const
   return st;
 }
 
+// ---- the adjoint of the saturation step: one transposed sweep on the step's slopes per step (sweep.inc) ---------------
+// In the frame of adjoint_steps with k = 1.  The solve of step n: d = f'(s^n) and phi = f(s^n) from the slab the frame
+// has staged (one streaming pass), then the frame of pfv_transport_adjoint_multi on the rows of J^T = diag(acc) +
+// diag(d) M^T (sweep_row_nl_t): the backward-peel levels from last to first, the core level iterated by Jacobi, the
+// forward-peel levels, the residual norms and ONE host read.  After an accepted step the two face kernels, the sink's
+// cell kernel and the six Corey sums, which are added in step order.
+pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
+                                    int n_params, const double* bc_values, const double* accumulation,
+                                    const double* sink, int n_steps, int64_t n_obs, const int32_t* obs_cells,
+                                    const double* loads, const double* states, double rtol, int maxit, double* grad_s0,
+                                    double* grad_source, double* grad_bc_values, double* grad_accumulation,
+                                    double* grad_sink, double* grad_flux, double* grad_fluxfn, int32_t* steps_done,
+                                    pfv_solve_info* last) {
+  if (steps_done) *steps_done = 0;
+  std::unique_ptr<pfv::Timer> tm;
+  bool touched = false;
+  double order_ms = 0.0;
+  const double* d_q = nullptr;
+  size_t nc = 0, nf = 0;
+  pfv::FluxFn F;
+  pfv_status st = guarded(h, [&] {
+    upwind_supported(h);
+    if (h->subface_bc) throw Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
+    require(h->have_upwind, "pfv_upwind_discretize first");
+    require(h->upw_ncomp == 1, "the saturation step needs pfv_upwind_discretize with num_components = 1");
+    const std::string bad = pfv::fluxfn_check(fluxfn_kind, fluxfn_params, n_params);
+    if (!bad.empty()) throw Error(PFV_ERR_ARGUMENT, bad);
+    require(!grad_fluxfn || fluxfn_kind == PFV_FLUXFN_COREY,
+            "grad_fluxfn is the gradient with respect to the six Corey parameters: PFV_FLUXFN_COREY only");
+    require(bc_values && accumulation, "bc_values and accumulation are required");
+    require(n_steps >= 0, "bad argument");
+    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
+    require(loads != nullptr || n_steps == 0, "loads is required");
+    require(states != nullptr || n_steps == 0, "states (s^0 .. s^N) is required: the step is linearised about them");
+    nc = (size_t)h->nc;
+    nf = (size_t)h->nf;
+    adjoint_take_loads(h, 1, n_steps, n_obs, obs_cells, loads);
+    if (q) vec_in(h, h->nl_q.ensure(nf), q, nf);
+    vec_in(h, h->nl_bc.ensure(nf), bc_values, nf);
+    vec_in(h, h->nl_acc.ensure(nc), accumulation, nc);
+    if (sink) vec_in(h, h->nl_sink.ensure(nc), sink, nc);
+    d_q = q ? h->nl_q.p : h->upw_q.p;
+    pfv::upwind_face_cells(*h);
+    int32_t off[pfv::kNlChecks];  // (the states are not checked: the accumulation stands in, off[2] says nothing)
+    pfv::sweep_nl_check_inputs(*h, d_q, h->nl_bc.p, h->nl_acc.p, sink ? h->nl_sink.p : nullptr, h->nl_acc.p, 0, nullptr,
+                               nullptr, nullptr, off);
+    static const char* what[5] = {"accumulation must be positive: cell ", "negative sink in cell ", nullptr,
+                                  "Dirichlet inflow value outside [0, 1] on face ", pfv::kUnmarkedInflowFace};
+    for (int m = 0; m < 5; ++m)
+      if (what[m] && off[m] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, what[m] + std::to_string(off[m]));
+    if (fluxfn_kind == PFV_FLUXFN_TABLE)
+      be_h2d(h->nl_table.ensure((size_t)n_params), fluxfn_params, sizeof(double) * (size_t)n_params, h->stream);
+    F = pfv::fluxfn_make(fluxfn_kind, fluxfn_params, n_params, h->nl_table.p);
+    tm = std::make_unique<pfv::Timer>();
+    tm->start(h->stream);
+    // A = div diag(q) U without accumulation, once per call; its transposed values beside it
+    upwind_drop_transport(h, true);
+    touched = true;
+    pfv::upwind_assemble(*h, d_q, h->nl_bc.p, nullptr, nullptr, nullptr);
+    values_changed(h, Windows::drop);
+    const size_t nnz = (size_t)std::max<int64_t>(h->pat_T.nnz, 1);
+    if (!h->have_tpos_T) {
+      pfv::sweep_transpose_positions(*h, h->pat_T, h->tpos_T.ensure(nnz));
+      h->have_tpos_T = true;
+    }
+    pfv::sweep_transpose_values(*h, h->pat_T.nnz, h->tpos_T.p, h->val[PFV_MAT_TRANSPORT_SYSTEM].p, h->valT_T.ensure(nnz));
+    adjoint_take_slots(h, n_obs, obs_cells);
+    for (pfv::Buf<double>* b : {&h->aj_lam, &h->aj_lam2, &h->aj_prev, &h->aj_r, &h->aj_sA, &h->aj_sB, &h->aj_d, &h->aj_phi,
+                                &h->mc_c})
+      b->ensure(nc);
+    if (!h->vectors_on_device) h->aj_state_in.ensure(nc);
+    if (grad_source) pfv::be_memset(h->aj_gsrc.ensure(nc), 0, sizeof(double) * nc, h->stream);
+    if (grad_accumulation) pfv::be_memset(h->aj_gacc.ensure(nc), 0, sizeof(double) * nc, h->stream);
+    if (grad_sink) pfv::be_memset(h->aj_gsink.ensure(nc), 0, sizeof(double) * nc, h->stream);
+    if (grad_bc_values) pfv::be_memset(h->aj_gbc.ensure(nf), 0, sizeof(double) * nf, h->stream);
+    if (grad_flux) pfv::be_memset(h->aj_gq.ensure(nf), 0, sizeof(double) * nf, h->stream);
+    if (grad_fluxfn) pfv::be_memset(h->aj_gF.ensure(6), 0, sizeof(double) * 6, h->stream);
+    h->mc_nrm.ensure(2);
+    transport_order(h, d_q, order_ms);
+  });
+  if (st != PFV_OK) {
+    if (touched) upwind_drop_transport(h, true);  // (A without accumulation: not a system to be solved with)
+    return st;
+  }
+
+  AdjointRun run;
+  std::vector<double> hst(2);
+  const double* d_sink = sink ? h->nl_sink.p : nullptr;
+  const AdjointCall call{1, n_steps, n_obs, obs_cells, states, h->nl_acc.p, grad_s0, grad_source, grad_accumulation,
+                         steps_done, last};
+  st = adjoint_steps(h, tm, call, run, [&](int n, double* z) -> pfv_status {
+    pfv::pfv_ctx_impl& cx = *h;
+    const pfv::Sweep& sw = *cx.sweep;
+    const double* valT = cx.valT_T.p;
+    const double *acc = cx.nl_acc.p, *d = cx.aj_d.p, *diag = cx.diag_t.p;
+    double* out = cx.mc_nrm.p;
+    const bool has_core = sw.n_core > 0;
+    const int core = has_core ? sw.core_level : -1;
+    pfv::adjoint_nl_slopes(cx, F, cx.aj_sB.p, cx.aj_d.p, cx.aj_phi.p);  // of s^n
+    run.launches = pfv::sweep_apply_nl_t(cx, sw, core + 1, sw.nlev, cx.pat_T, valT, diag, d_sink, acc, d, cx.aj_r.p, z);
+    int core_it = 0;
+    if (has_core) {
+      pfv::sweep_core_zero(cx, sw, 1, z);
+      const CoreRun cr = core_iterate(h, maxit, out, hst, [&] {
+        pfv::sweep_core_copy(cx, sw, 1, z, cx.aj_prev.p);
+        pfv::sweep_core_nl_t(cx, sw, cx.pat_T, valT, diag, d_sink, acc, d, cx.aj_r.p, cx.aj_prev.p, z);
+      }, [&] {
+        pfv::sweep_norms_nl_t(cx, sw, cx.pat_T, valT, d_sink, acc, d, cx.aj_r.p, z, true, out);
+      }, [&] { return adjoint_norms_pass(hst, 1, 0.5 * rtol); });
+      core_it = cr.iterations;
+      run.core_total += core_it;
+      run.launches += 2;
+      if (!cr.settled) {  // (what the forward-peel levels would compute from this core is not judged)
+        adjoint_component_info(run.info, hst, 1, core_it);
+        cx.err = "adjoint step " + std::to_string(n) + ": the cyclic core of " + std::to_string(sw.n_core) +
+                 " cells did not settle in " + std::to_string(core_it) + " iterations";
+        return PFV_ERR_NOT_CONVERGED;
+      }
+      run.launches += pfv::sweep_apply_nl_t(cx, sw, 0, core, cx.pat_T, valT, diag, d_sink, acc, d, cx.aj_r.p, z);
+    }
+    pfv::sweep_norms_nl_t(cx, sw, cx.pat_T, valT, d_sink, acc, d, cx.aj_r.p, z, false, out);
+    be_d2h(hst.data(), out, sizeof(double) * hst.size(), cx.stream);
+    adjoint_component_info(run.info, hst, 1, has_core ? core_it : 1);
+    return adjoint_accept(h, run.info, hst, 1, rtol, n);
+  }, [&](double* z) {
+    pfv::pfv_ctx_impl& cx = *h;
+    if (grad_sink) pfv::adjoint_nl_grad_sink(cx, z, cx.aj_phi.p, cx.aj_gsink.p);
+    if (grad_bc_values) pfv::adjoint_nl_grad_bc(cx, F, d_q, cx.nl_bc.p, z, cx.aj_gbc.p);
+    if (grad_flux) pfv::adjoint_nl_grad_flux(cx, F, cx.nl_bc.p, z, cx.aj_phi.p, cx.aj_gq.p);
+    if (grad_fluxfn)
+      pfv::adjoint_nl_grad_fluxfn(cx, F, cx.pat_T, cx.valT_T.p, d_sink, d_q, cx.nl_bc.p, z, cx.aj_sB.p, cx.aj_gF.p);
+  }, [&] {
+    if (grad_bc_values) vec_out(h, grad_bc_values, h->aj_gbc.p, nf);
+    if (grad_flux) vec_out(h, grad_flux, h->aj_gq.p, nf);
+    if (grad_sink) vec_out(h, grad_sink, h->aj_gsink.p, nc);
+    if (grad_fluxfn) be_d2h(grad_fluxfn, h->aj_gF.p, sizeof(double) * 6, h->stream);  // (host memory, as the parameters are)
+  });
+  h->stats.transport_nl_adjoint_ms = run.ms;
+  h->stats.transport_nl_adjoint_steps = run.completed;
+  h->stats.transport_nl_adjoint_core_iterations = run.core_total;
+  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, order_ms);
+  return st;
+}
+
 // ---- advection-diffusion on one handle (advdiff.inc) -----------------------------------------------------------
 static void advdiff_supported(pfv_ctx* h) {
   require(h->have_grid, "pfv_set_grid first");

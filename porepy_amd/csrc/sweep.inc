@@ -1460,6 +1460,249 @@ static void adjoint_grad_rate(pfv_ctx_impl& c, int k, const double* rho, const d
   });
 }
 
+// ---- the adjoint of the saturation step (pfv_transport_adjoint_nl).  The step acc o (s - s_old) + M f(s) + b_ref = src,
+// M = A + diag(sink), has the Jacobian J = diag(acc) + M diag(d) with d = f'(s^n), so that
+//     J^T lambda = (diag(acc) + diag(d) M^T) lambda = r
+// and row i, once the cells downstream of it are known, is one division:
+//     lambda_i = (r_i - d_i sum_{lev[j] > lev[i]} valT[e] lambda_j) / (acc_i + d_i (A_ii + sink_i)).
+// No root-finding and no pow in a level: d and phi = f(s^n) come from ONE streaming pass over the step's slab of states
+// (adjoint_nl_slopes).  J is strictly column-diagonally dominant (acc > 0, M an M-matrix by columns), so Jacobi on the
+// transposed rows of a cyclic core converges; a row with d_i = 0 (a cell at or beyond a residual saturation) is
+// acc_i lambda_i = r_i.  The levels, the launch plan and the load chain of a row are those of sweep_row_multi_t.
+static void adjoint_nl_slopes(pfv_ctx_impl& c, const FluxFn& F, const double* s, double* d, double* phi) {
+  parallel_for(c.stream, c.nc, PFV_LAMBDA(int64_t i) {
+    double df;
+    phi[i] = fluxfn_eval(F, s[i], &df);
+    d[i] = df;
+  });
+}
+
+PFV_FN void sweep_row_nl_t(int32_t i, const int32_t* ip, const int32_t* ix, const double* valT, const double* diag,
+                           const double* sink, const double* acc, const double* d, const int32_t* lev, const double* r,
+                           double* z) {
+  const int32_t li = lev[i];
+  double sum = 0.0;
+  for (int e = ip[i]; e < ip[i + 1]; ++e) {
+    const int32_t j = ix[e];
+    if (lev[j] > li) sum += valT[e] * z[j];
+  }
+  const double di = d[i];
+  z[i] = (r[i] - di * sum) / (acc[i] + di * (diag[i] + (sink ? sink[i] : 0.0)));
+}
+
+// ... of the core level: the in-core neighbours from z_prev, the previous iterate (Jacobi, independent of the scheduling)
+PFV_FN void sweep_row_nl_t_core(int32_t i, const int32_t* ip, const int32_t* ix, const double* valT, const double* diag,
+                                const double* sink, const double* acc, const double* d, const int32_t* lev,
+                                const double* r, const double* z_prev, double* z) {
+  const int32_t li = lev[i];
+  double sum = 0.0;
+  for (int e = ip[i]; e < ip[i + 1]; ++e) {
+    const int32_t j = ix[e];
+    const int32_t lj = lev[j];
+    if (lj > li) sum += valT[e] * z[j];
+    else if (lj == li && j != i) sum += valT[e] * z_prev[j];
+  }
+  const double di = d[i];
+  z[i] = (r[i] - di * sum) / (acc[i] + di * (diag[i] + (sink ? sink[i] : 0.0)));
+}
+
+// the launch plan's levels in [from, to), from last to first.  Returns the launches.
+static int sweep_apply_nl_t(pfv_ctx_impl& c, const Sweep& sw, int from, int to, const CsrPattern& P, const double* valT,
+                            const double* diag, const double* sink, const double* acc, const double* d,
+                            const double* in, double* out) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* lev = sw.lev(false);
+  return sweep_plan_range(sw, from, to, [&](int l0, int l1) {
+    sweep_levels(c, sw, false, l0, l1, OnePerRow{},
+                 PFV_LAMBDA(int32_t i, int) { sweep_row_nl_t(i, ip, ix, valT, diag, sink, acc, d, lev, in, out); },
+                 Descending{});
+  }, Descending{});
+}
+
+// one Jacobi iteration of the core level on its transposed rows
+static void sweep_core_nl_t(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* valT,
+                            const double* diag, const double* sink, const double* acc, const double* d,
+                            const double* in, const double* prev, double* out) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* lev = sw.lev(false);
+  sweep_core_rows(c, sw, OnePerRow{}, PFV_LAMBDA(int32_t i, int, int64_t) {
+    sweep_row_nl_t_core(i, ip, ix, valT, diag, sink, acc, d, lev, in, prev, out);
+  });
+}
+
+// (M^T x)_i = sum_e valT[e] x_j + sink_i x_i in stored order; from >= 0: the entries of the levels from `from` on alone
+PFV_FN double sweep_nl_t_row_image(int64_t i, const int32_t* ip, const int32_t* ix, const double* valT,
+                                   const double* sink, const double* x, const int32_t* lev, int32_t from) {
+  double t = 0.0;
+  for (int e = ip[i]; e < ip[i + 1]; ++e) {
+    const int32_t j = ix[e];
+    if (from < 0 || lev[j] >= from) t += valT[e] * x[j];
+  }
+  if (sink) t += sink[i] * x[i];
+  return t;
+}
+
+// The acceptance check: out[0] = (r, r), out[1] = (r - J^T x, r - J^T x) over all rows.  core_only (the core's stop test):
+// out[1] is the squared residual of the core rows, the image taken from the entries of the row's own level and above
+// (the levels below have no value yet; their entries are the stored zeros of the upstream side).
+static void sweep_norms_nl_t(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* valT,
+                             const double* sink, const double* acc, const double* d, const double* r, const double* x,
+                             bool core_only, double* out) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* lev = sw.lev(false);
+  const int32_t core = core_only ? sw.core_level : -1;
+  sweep_norms_pairs(c, P.nrows, 1, out, PFV_LAMBDA(int64_t i, int) {
+    const double ri = r[i];
+    if (core >= 0 && lev[i] != core) return NormPair{ri, 0.0};
+    const double t = acc[i] * x[i] + d[i] * sweep_nl_t_row_image(i, ip, ix, valT, sink, x, lev, core);
+    return NormPair{ri, ri - t};
+  });
+}
+
+// grad_sink[i] -= lambda_i phi_i (the sink takes fluid at the cell's own f(s))
+static void adjoint_nl_grad_sink(pfv_ctx_impl& c, const double* lam, const double* phi, double* gsink) {
+  parallel_for(c.stream, c.nc, PFV_LAMBDA(int64_t i) { gsink[i] -= lam[i] * phi[i]; });
+}
+
+// grad_bc_values[f] -= m_f (lambda[p] - lambda[m]), m_f the derivative of the entry of rhs_neu bc + rhs_dir diag(q) f(bc)
+// in row f (upwind_bref_nl) with respect to bc_f: the Neumann count, q_f f'(bc_f) on a Dirichlet inflow face.  With
+// f(s) = s these are the bits of adjoint_grad_bc.
+static void adjoint_nl_grad_bc(pfv_ctx_impl& c, const FluxFn& F, const double* d_q, const double* bc, const double* lam,
+                               double* gbc) {
+  const int64_t nf = c.nf;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* cnt = c.upw_cnt;
+  const int32_t* side = c.upw_side;
+  parallel_for(c.stream, nf, PFV_LAMBDA(int64_t f) {
+    const unsigned cl = cls[f];
+    if (!(cl & (UPW_NEU | UPW_DIRIN))) return;
+    double m = 0.0;
+    if (cl & UPW_NEU) m = (double)(cnt[f] - cnt[nf + f]);
+    if (cl & UPW_DIRIN) {
+      double df;
+      fluxfn_eval(F, bc[f], &df);
+      m += df * d_q[f];
+    }
+    const int32_t cp = side[f], cm = side[nf + f];
+    double s = 0.0;
+    if (cp >= 0) s += m * lam[cp];
+    if (cm >= 0) s -= m * lam[cm];
+    gbc[f] -= s;
+  });
+}
+
+// grad_flux[f] -= (lambda[p] - lambda[m]) phiup_f with phiup the value the upwind rule moves through f: phi = f(s^n) of
+// the upstream cell (interior and outflow faces), f(bc_f) on a Dirichlet inflow face; a Neumann face gives 0.  The
+// upstream side is fixed, as in adjoint_grad_flux.
+static void adjoint_nl_grad_flux(pfv_ctx_impl& c, const FluxFn& F, const double* bc, const double* lam,
+                                 const double* phi, double* gq) {
+  const int64_t nf = c.nf;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* up = c.upw_up;
+  const int32_t* side = c.upw_side;
+  parallel_for(c.stream, nf, PFV_LAMBDA(int64_t f) {
+    const unsigned cl = cls[f];
+    if (!(cl & (UPW_KEPT | UPW_DIRIN))) return;
+    const int32_t cp = side[f], cm = side[nf + f];
+    double d = 0.0, df;
+    if (cp >= 0) d = lam[cp];
+    if (cm >= 0) d -= lam[cm];
+    const double pu = (cl & UPW_KEPT) ? phi[up[f]] : fluxfn_eval(F, bc[f], &df);
+    gq[f] -= d * pu;
+  });
+}
+
+// grad_fluxfn[m] -= sum_i (M^T lambda)_i df/dtheta_m(s_i) + sum_{Dirichlet inflow f} (lambda[p] - lambda[m]) q_f
+// df/dtheta_m(bc_f) for the six Corey parameters (fluxfn_eval_params).  The terms are the cells in index order, then the
+// faces: item t < nc is cell t -- its (M^T lambda) from the valT row in stored order --, item nc + f is face f.  The six
+// sums take a fixed partition that depends on the numbers of cells and faces alone: a workgroup takes a range of the
+// items, lane l of it the items lo + l, lo + l + 256, ... with its six sums in registers, the 256 lanes' sums are folded
+// pairwise in LDS, and one workgroup per parameter adds the workgroups' partial sums and subtracts the result from the
+// parameter's accumulator: the steps add in step order.  No floating-point atomics, no per-thread array under a
+// run-time index.
+static void adjoint_nl_grad_fluxfn(pfv_ctx_impl& c, const FluxFn& F, const CsrPattern& P, const double* valT,
+                                   const double* sink, const double* d_q, const double* bc, const double* lam,
+                                   const double* s_n, double* gF) {
+  stream_t s = c.stream;
+  const int64_t nc = c.nc, nf = c.nf, n = nc + nf;
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* side = c.upw_side;
+  const int nb = (int)std::min<int64_t>(kGmresBlocks, (n + 2047) / 2048);
+  double* partial = c.red.ensure(6 * (size_t)kGmresBlocks + 64);
+  block_for<256>(s, nb, 6 * 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& w) {
+    double* sh = reinterpret_cast<double*>(w.lds);
+    const int64_t blk = w.item;
+    const int64_t lo = n * blk / nb, hi = n * (blk + 1) / nb;
+    PFV_LANES(l, 256) {
+      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0, a5 = 0.0;
+      for (int64_t t = lo + l; t < hi; t += 256) {
+        double wt = 0.0, at = 0.0;  // the weight of the item and the saturation its derivatives are taken at
+        bool live = false;
+        if (t < nc) {
+          wt = sweep_nl_t_row_image(t, ip, ix, valT, sink, lam, nullptr, -1);
+          at = s_n[t];
+          live = true;
+        } else {
+          const int64_t f = t - nc;
+          if (cls[f] & UPW_DIRIN) {
+            const int32_t cp = side[f], cm = side[nf + f];
+            double dl = 0.0;
+            if (cp >= 0) dl = lam[cp];
+            if (cm >= 0) dl -= lam[cm];
+            wt = dl * d_q[f];
+            at = bc[f];
+            live = true;
+          }
+        }
+        if (live) {
+          double dp[6];
+          fluxfn_eval_params(F, at, dp);
+          a0 += wt * dp[0];
+          a1 += wt * dp[1];
+          a2 += wt * dp[2];
+          a3 += wt * dp[3];
+          a4 += wt * dp[4];
+          a5 += wt * dp[5];
+        }
+      }
+      sh[l] = a0;
+      sh[256 + l] = a1;
+      sh[512 + l] = a2;
+      sh[768 + l] = a3;
+      sh[1024 + l] = a4;
+      sh[1280 + l] = a5;
+    }
+    w.sync();
+    for (int o = 128; o > 0; o >>= 1) {
+      PFV_LANES(l, o) {
+        for (int m = 0; m < 6; ++m) sh[m * 256 + l] += sh[m * 256 + l + o];
+      }
+      w.sync();
+    }
+    PFV_LANES(m, 6) { partial[(int64_t)m * nb + blk] = sh[m * 256]; }
+    w.sync();
+  });
+  block_for<256>(s, 6, 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& wc) {
+    double* sh = reinterpret_cast<double*>(wc.lds);
+    const int64_t m = wc.item;
+    double a = 0.0;
+    for (int i = wc.lane; i < nb; i += wc.width) a += partial[m * nb + i];
+    sh[wc.lane] = a;
+    wc.sync();
+    for (int o = wc.width >> 1; o > 0; o >>= 1) {
+      if (wc.lane < o) sh[wc.lane] += sh[wc.lane + o];
+      wc.sync();
+    }
+    if (wc.lane0()) gF[m] -= sh[0];
+    wc.sync();
+  });
+}
+
 // The direct solve of the transport system of an acyclic flux: x = M^-1 b with M = S, then the true residual.  Should
 // the check fail (a flux array in the assembly that disagrees with the discretization's, NaN entries), GMRES
 // preconditioned by the sweep goes on from that x.

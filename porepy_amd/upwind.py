@@ -526,6 +526,56 @@ class Upwind:
                 raise ValueError(e.message) from None
             raise
 
+    def adjoint_saturation(self, sd, data: dict, n_steps: int, accumulation, flux_function, loads, states, sink=None,
+                           obs_cells=None, want=("s0", "source", "bc_values"), rtol: float = 1e-12, maxit: int = 500,
+                           raise_on_fail: bool = True):
+        """The adjoint of ``advance_saturation``: the gradients of ``J = sum_{n=1..N} <loads[n-1], s^n[obs_cells]>``
+        through ``n_steps`` = N saturation steps, for the cost of about one more run -- what a match of water-cut or
+        saturation observations by Corey exponents, the viscosity ratio, residual saturations, porosity, well rates or
+        the flux needs, without finite differences over whole runs.  The step is linearised about the forward states:
+        per step, backwards in time, ``(diag(acc) + diag(f'(s^n)) M^T) lambda^n = loads^n + acc o lambda^{n+1}`` is ONE
+        transposed sweep in reverse flow order, a division per cell; the levels and the launches are those of the
+        forward sweep.
+
+        ``accumulation``, ``flux_function`` and ``sink`` as in ``advance_saturation`` (the source does not enter);
+        ``loads``: (N, n_obs); ``obs_cells``: n_obs cell indices without repeats, or None (every cell, in order);
+        ``states``: (N + 1, Nc), s^0 .. s^N of the forward run -- required, and not checked for range or finiteness.
+        ``want`` names the gradients:
+
+        - ``"s0"``, ``"source"``, ``"accumulation"`` (Nc,): ``acc o lambda^1``, ``sum_n lambda^n``,
+          ``sum_n lambda^n o (s^{n-1} - s^n)``;
+        - ``"sink"`` (Nc,): ``-sum_n lambda^n o f(s^n)``; with ``sink=None`` the derivative at sink = 0;
+        - ``"bc_values"`` (Nf,): on a Neumann face the flux value's, on a Dirichlet inflow face the saturation's
+          (``-sum_n (lambda_p - lambda_m) q_f f'(bv_f)``), zero on every other face;
+        - ``"flux"`` (Nf,): ``-sum_n (lambda_p - lambda_m) f(s_upstream^n)`` (``f(bv_f)`` on a Dirichlet inflow face,
+          zero on a Neumann face);
+        - ``"flux_function"`` (6,): a ``CoreyFractionalFlow`` only (``ValueError`` otherwise), ordered as
+          ``CoreyFractionalFlow.params``: s_wr, s_nr, n_w, n_n, mu_w, mu_n.  Gradients with respect to the values of a
+          table are not offered.
+
+        Every gradient is the derivative on a FIXED branch: of the interval of a table, of the side of a residual
+        saturation, of the upstream side of every face.  J has kinks where a state sits on a table knot or on a
+        residual saturation and where a ``q_f`` is exactly zero: there the gradient is a one-sided derivative, elsewhere
+        the derivative.  The chain from ``"flux"`` to a permeability goes through ``Mpfa.ad_flux_system`` and is the
+        caller's.
+
+        The cells of a cyclic core are iterated by Jacobi on their transposed rows, at most ``maxit`` times per step.
+        Returns (grads, info): info["steps_done"], "converged", "iterations" (1, or the core iterations of the last
+        step) and "rel_residual" (the measured ``||r - J^T lambda|| / ||r||``).  A refused step leaves the gradients
+        zero.  Afterwards the handle holds no assembled transport system; the flow order stays."""
+        pd = data[PARAMETERS][self.keyword]
+        kind, params = _flux_function(flux_function)
+        if accumulation is None:
+            raise ValueError("accumulation is required")
+        try:
+            return self.context(sd).transport_adjoint_nl(
+                n_steps, accumulation, np.asarray(pd["bc_values"], dtype=float), kind, params, loads, states, sink=sink,
+                obs_cells=obs_cells, q=self._flux(sd, pd), want=want, rtol=rtol, maxit=maxit, raise_on_fail=raise_on_fail)
+        except _lib.PorefvError as e:
+            if e.status == 4:
+                raise ValueError(e.message) from None
+            raise
+
 
 def _flux_function(flux_function):
     """(kind, parameters) of the C ABI for what ``advance_saturation`` takes as ``flux_function``"""

@@ -8,7 +8,7 @@ not a test: no thresholds.
 
     python tools/bench_transport.py [--n-side 69] [--steps 20] [--no-host] [--precond sweep] [--components 8]
                                     [--saturation [--components 4]] [--reactive] [--adjoint]
-                                    [--reactive --adjoint]
+                                    [--reactive --adjoint] [--saturation --adjoint]
 
 --precond sweep: after the Jacobi-BiCGStab steps, the same steps from the same state with the flow-ordered sweep
 (PFV_PRECOND_SWEEP) -- order-build ms, levels, core cells, launches per sweep, ms per step -- and again with one launch
@@ -45,6 +45,13 @@ place of "reactive" and "adjoint"): alternating in one loop, the forward reactiv
 k = 4 step of --reactive's network (transport_advance_react), its adjoint (transport_adjoint_react) on 16 observation
 cells without states (c0, source, bc_values) and the adjoint with all seven gradients: ms per step of the three from
 pfv_stats (best and median of --reps, the first repeat dropped), levels and launches.
+
+--saturation --adjoint (together; the blocks of --saturation and of --adjoint are then NOT run, and the JSON has the key
+"saturation_adjoint" in their place): alternating in one loop, on the same flux, the forward Corey saturation step of
+--saturation's curve with a sink (transport_advance_nl) from a random state in [0.15, 0.65], its adjoint
+(transport_adjoint_nl) on 16 observation cells with the three gradients whose formulas need no states (s0, source,
+bc_values) and the adjoint with all seven; the states are those of the forward run, taken one step at a time.  ms per
+step of the three from pfv_stats (best and median of --reps, the first repeat dropped), levels and launches.
 """
 from __future__ import annotations
 
@@ -78,7 +85,8 @@ def main():
     ap.add_argument("--reactive", action="store_true",
                     help="the linear k = 4 sweep steps against k = 4 coupled (reactive) steps on the same flux and state")
     ap.add_argument("--adjoint", action="store_true",
-                    help="the forward k = 4 sweep step against the adjoint k = 4 step on the same flux")
+                    help="the forward k = 4 sweep step against the adjoint k = 4 step on the same flux; with --saturation: "
+                         "the forward Corey step against its adjoint")
     ap.add_argument("--emulation", action="store_true", help="run on the host-emulation build (plumbing check)")
     a = ap.parse_args()
     lib = None
@@ -174,7 +182,7 @@ def main():
                 "max_diff_multi_to_single": float(np.abs(cm_k - cs_k).max())})
         if a.components:
             ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the multi-component call leaves no system behind)
-    if a.saturation:
+    if a.saturation and not a.adjoint:
         s0 = np.full(nc, 0.1)
         corey = pa.CoreyFractionalFlow(s_wr=0.1, s_nr=0.15, n_w=2.0, n_n=2.0, mu_w=1.0, mu_n=5.0)
         lin_ms, nl_ms, sat = [], [], {}
@@ -236,6 +244,48 @@ def main():
             sat["components"].append(entry)
         out["saturation"] = sat
         ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the saturation call leaves no system behind)
+    if a.saturation and a.adjoint:
+        n_obs = 16
+        corey = pa.CoreyFractionalFlow(s_wr=0.1, s_nr=0.15, n_w=2.0, n_n=2.0, mu_w=1.0, mu_n=5.0)
+        sink = 0.05 * acc * rng.random(nc)
+        nl = dict(sink=sink, rtol=1e-10)
+        states = np.empty((a.steps + 1, nc))
+        states[0] = 0.15 + 0.5 * rng.random(nc)
+        obs = np.sort(rng.permutation(nc)[:n_obs])
+        loads = rng.standard_normal((a.steps, n_obs))
+        entry = {"observation_cells": n_obs}
+        try:
+            for s_ in range(a.steps):  # the states of the forward run, one step at a time
+                states[s_ + 1], ninfo = ctx.transport_advance_nl(states[s_], 1, acc, tbv, corey.kind, corey.params, **nl)
+            fwd_ms, adj3_ms, adj7_ms = [], [], []
+            for _ in range(a.reps + 1):  # (the first repeat warms up: dropped)
+                sn, ninfo = ctx.transport_advance_nl(states[0], a.steps, acc, tbv, corey.kind, corey.params,
+                                                     raise_on_fail=False, **nl)
+                fwd = ctx.stats()
+                fwd_ms.append(fwd["transport_nl_ms"] / max(a.steps, 1))
+                g3, i3 = ctx.transport_adjoint_nl(a.steps, acc, tbv, corey.kind, corey.params, loads, states, obs_cells=obs,
+                                                  raise_on_fail=False, **nl)
+                adj3_ms.append(ctx.stats()["transport_nl_adjoint_ms"] / max(a.steps, 1))
+                g7, i7 = ctx.transport_adjoint_nl(a.steps, acc, tbv, corey.kind, corey.params, loads, states, obs_cells=obs,
+                                                  want=ctx.NL_ADJOINT_GRADIENTS, raise_on_fail=False, **nl)
+                adj = ctx.stats()
+                adj7_ms.append(adj["transport_nl_adjoint_ms"] / max(a.steps, 1))
+            entry.update({
+                "steps_done": i7["steps_done"], "forward_steps_done": ninfo["steps_done"],
+                "forward_saturation_ms_per_step": (min(fwd_ms[1:]), float(np.median(fwd_ms[1:]))),
+                "adjoint_ms_per_step_s0_source_bc": (min(adj3_ms[1:]), float(np.median(adj3_ms[1:]))),
+                "adjoint_ms_per_step_all_seven": (min(adj7_ms[1:]), float(np.median(adj7_ms[1:]))),
+                "levels": adj["sweep_levels"], "core_cells": adj["sweep_core_cells"],
+                "forward_launches_per_sweep": fwd["sweep_launches"], "adjoint_launches_per_sweep": adj["sweep_launches"],
+                "core_iterations": adj["transport_nl_adjoint_core_iterations"],
+                "rel_residual_last_step": i7["rel_residual"], "forward_rel_residual_last_step": ninfo["rel_residual"],
+                "s_min": float(states.min()), "s_max": float(states.max()),
+                "grad_flux_function": g7["flux_function"].tolist(),
+                "s0_bits_equal_between_the_two_adjoint_calls": bool(g3["s0"].tobytes() == g7["s0"].tobytes())})
+        except pa.PorefvError as e:
+            entry["error"] = e.message
+        out["saturation_adjoint"] = entry
+        ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the calls leave no system behind)
     if a.reactive and a.adjoint:
         kc, n_obs = 4, 16
         acc_k = np.array([(1.0 + 0.5 * j) * acc for j in range(kc)])
@@ -326,7 +376,7 @@ def main():
             entry["error"] = e.message
         out["reactive"] = entry
         ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the reactive call leaves no system behind)
-    if a.adjoint and not a.reactive:
+    if a.adjoint and not a.reactive and not a.saturation:
         kc, n_obs = 4, 16
         acc_k = np.array([(1.0 + 0.5 * j) * acc for j in range(kc)])
         bv_k = np.array([tbv * (j + 1) / kc for j in range(kc)])

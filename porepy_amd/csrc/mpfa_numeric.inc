@@ -199,6 +199,9 @@ struct NodeArgs {
   int sub_bc;             // conditions per sub-face: bcflag / robin are indexed by sub-face id
   int refine;             // 0: refine where kappa asks for it; -1 never; k > 0: always k steps
   int32_t* redo;          // unpivoted elimination: nodes that fail its check, left to the pivoted body (count in st[2])
+  // ... and its acceptance, kNoPivotResidual times PFV_NODE_NP_TOLX (an integer, read per call like PFV_MPSA_NP_TOLX; default
+  // 1: the constant itself, bit for bit; 0: no region passes, every one of the unpivoted classes goes through the redo list)
+  double np_tol = kNoPivotResidual * (double)env_int("PFV_NODE_NP_TOLX", 1);
 };
 
 // L.bg: right-hand side of sub-face lf(j, k) per unit source component b in sub-cell j, stored sub-cell by sub-cell,
@@ -1232,7 +1235,7 @@ PFV_FN void node_body(const NodeArgs& a, const WaveCtx& w, int64_t first) {
       PFV_LANES(l, n) L.colk[l] = freivalds_v(l);
       w.lsync();
       node_residual_update(w, L, nh, n, ND, L.rowk, L.colk);  // colk = v - A (X v), A from its defining coefficients
-      const double tol = kNoPivotResidual * (kappa > 1.0 ? kappa : 1.0);
+      const double tol = a.np_tol * (kappa > 1.0 ? kappa : 1.0);
       bool off = false;
       PFV_LANES(l, n) off = off || !(fabs(L.colk[l]) <= tol);  // (NaN fails)
       const bool failed = degenerate || __ballot(off) != 0ull || !(kappa == kappa);

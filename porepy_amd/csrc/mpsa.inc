@@ -77,6 +77,15 @@ struct MpsaLdsT {
 };
 using MpsaLds = MpsaLdsT<double>;
 
+// Elements set aside for L.A.  The unpivoted elimination (mpsa_gj_reg_np) keeps its two exchange buffers of 256 doubles in
+// L.A while the matrix sits in registers: a system of n <= 22 unknowns (n * ld < 512: every node of a 2-D grid, the
+// boundary nodes of a 3-D one with at most 7 faces) is smaller than they are.  Sized by n * ld alone the buffers ran over
+// L.scale, L.rowk, L.colk and L.Om, the a-posteriori check read what they left there, never passed, and every such region
+// was computed a second time by the full body (right results, twice the work: all 2 116 regions of a 45 x 45 triangle
+// grid on the redo list).
+constexpr size_t kMpsaExchangeElems = 512;
+PFV_HD inline size_t mpsa_a_elems(size_t n, size_t ld) { return n * ld > kMpsaExchangeElems ? n * ld : kMpsaExchangeElems; }
+
 PFV_HD inline size_t mpsa_lds_bytes(int nsfmax, int degmax, int nbmax, int nd, bool biot = false, size_t tsize = 8) {
   const size_t n = (size_t)nd * nsfmax, ld = n | 1, n2 = (size_t)nd * nd, nh = (size_t)degmax * nd;
   const size_t ncu = (size_t)nd * degmax, ncb = (size_t)nd * nbmax;
@@ -88,7 +97,7 @@ PFV_HD inline size_t mpsa_lds_bytes(int nsfmax, int degmax, int nbmax, int nd, b
   size_t u = pi_or_ag + n2 * ncu /*PU*/ + n2 * n2 /*PLAG*/ + n2 * ncu /*Ptot*/ + n2 * (ncb + 1) /*Pb*/;
   const size_t ub = n * (size_t)degmax /*Lp*/ + n2 * (size_t)degmax /*Pp*/;
   if (biot && ub > u) u = ub;
-  size_t d = n * ld + 3 * n + nh * nd * n2 /*Om: nh*nd^3*/ + u + n2 * n /*PL*/ + nh * nd /*nvec*/ +
+  size_t d = mpsa_a_elems(n, ld) + 3 * n + nh * nd * n2 /*Om: nh*nd^3*/ + u + n2 * n /*PL*/ + nh * nd /*nvec*/ +
              degmax /*wj*/ + n /*beta*/ + (size_t)degmax * n2 /*Dinv*/ + 328 /*gjx*/ + (size_t)nsfmax * n2 /*basisL*/;
   size_t i = n + 4 + (size_t)nsfmax * 4;
   size_t b = n + 2 * nh;
@@ -104,7 +113,7 @@ PFV_FN void mpsa_carve(char* lds, int nsf, int deg, int nb, int nd, MpsaLdsT<T>&
   const size_t n = (size_t)nd * nsf, ld = n | 1, n2 = (size_t)nd * nd, nh = (size_t)deg * nd;
   const size_t ncu = (size_t)nd * deg, ncb = (size_t)nd * nb;
   Carver cv(lds);
-  L.A = cv.take<T>(n * ld);
+  L.A = cv.take<T>(mpsa_a_elems(n, ld));  // (at least the exchange buffers of mpsa_gj_reg_np)
   L.scale = cv.take<T>(n);
   L.rowk = cv.take<T>(n);
   L.colk = cv.take<T>(n);

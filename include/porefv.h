@@ -218,6 +218,9 @@ typedef struct {
   double transport_nl_adjoint_ms; /* last pfv_transport_adjoint_nl, all steps (HIP events) */
   int64_t transport_nl_adjoint_steps; /* ... accepted adjoint steps */
   int64_t transport_nl_adjoint_core_iterations; /* ... Jacobi iterations of the cyclic core, summed over the steps */
+  double transport_nlc_adjoint_ms; /* last pfv_transport_adjoint_nl_multi, all steps (HIP events) */
+  int64_t transport_nlc_adjoint_steps; /* ... accepted adjoint steps */
+  int64_t transport_nlc_adjoint_core_iterations; /* ... Jacobi iterations of the cyclic core, summed over the steps */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -866,6 +869,71 @@ pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind
                                     double* grad_source, double* grad_bc_values, double* grad_accumulation,
                                     double* grad_sink, double* grad_flux, double* grad_fluxfn, int32_t* steps_done,
                                     pfv_solve_info* last);
+
+/* The adjoint of pfv_transport_advance_nl_multi: the gradients of
+ *     J = sum_{n=1..N} [ <s_loads[n-1], s^n[obs_cells]> + sum_a <c_loads[n-1][a], c_a^n[obs_cells]> ]
+ * through n_steps = N steps of the saturation with k phase-carried components -- what a match of tracer, salinity or
+ * polymer breakthrough curves by Corey parameters, porosity, well rates or the flux needs.  With lambda the multiplier
+ * of the saturation's equation and mu_a that of component a's, M = A + diag(sink), phi^n = f(s^n), d^n = f'(s^n),
+ * e_a^n = acc o s^n + sorption_a and lambda^{N+1} = mu_a^{N+1} = 0 the call solves, for n = N .. 1,
+ *     (diag(e_a^n) + diag(phi^n) M^T) mu_a^n = c_loads_a^n + e_a^n o mu_a^{n+1}
+ *     (diag(acc) + diag(d^n) M^T) lambda^n  = s_loads^n + acc o lambda^{n+1}
+ *                                              - sum_a c_a^n o [acc o (mu_a^n - mu_a^{n+1}) + d^n o (M^T mu_a^n)].
+ * In reverse flow order cell i is k + 1 divisions once the cells downstream of it are known (csrc/sweep.inc:
+ * sweep_row_nlc_t): with o = A_ii + sink_i and u_a = sum_{lev[j] > lev[i]} valT[e] mu_aj,
+ *     mu_ai = (rmu_ai - phi_i u_a) / (acc_i s_i + sorption_ai + phi_i o),   (M^T mu_a)_i = u_a + o mu_ai,
+ * so the coupling term is known inside the row and lambda_i is the division of pfv_transport_adjoint_nl on the reduced
+ * right-hand side: ONE fused transposed sweep per step, with the levels, the launch plan and the launch count of the
+ * forward sweep.  The cells of a cyclic core iterate mu and lambda jointly by Jacobi on their transposed rows (the
+ * system is block triangular: the rate is that of its diagonal blocks), from zero, until every one of the k + 1
+ * residuals of the core is below rtol / 2 of its scale, at most maxit times.  A step is accepted when all k + 1
+ * residuals pass ||r - image|| <= rtol ||r|| (0 <= 0 counts); lambda's right-hand side in that check is recomputed from
+ * the image of the final mu.  One host read per step.
+ *   fluxfn_kind / fluxfn_params / n_params, q, bc_values, accumulation, sink, k, c_bc_values [k][Nf] and sorption
+ * [k][Nc] (may be NULL) are those of pfv_transport_advance_nl_multi, with its rules and texts (the sources do not
+ * enter).  s_loads [N][n_obs] and c_loads [N][k][n_obs] with obs_cells as in pfv_transport_adjoint_multi; either may be
+ * NULL (zeros), not both.  s_states [N + 1][Nc] and c_states [N + 1][k][Nc] are REQUIRED (PFV_ERR_ARGUMENT when NULL
+ * with n_steps > 0); one slab of each is staged per step; they are NOT checked for range or finiteness.  fluxfn_params
+ * and grad_fluxfn are HOST memory; every other array follows pfv_set_vectors_on_device.
+ *   Gradients, each may be NULL (not wanted), accumulated on the device in step order without floating-point atomics;
+ * p / m are the cells of cell_faces sign +1 / -1 at a face (a missing cell contributes nothing):
+ *     grad_s0 [Nc]              acc o lambda^1 + sum_a acc o c_a^0 o mu_a^1
+ *     grad_c0 [k][Nc]           (acc o s^0 + sorption_a) o mu_a^1
+ *     grad_source [Nc]          sum_n lambda^n
+ *     grad_c_source [k][Nc]     sum_n mu_a^n
+ *     grad_accumulation [Nc]    -sum_n [lambda^n o (s^n - s^{n-1}) + sum_a mu_a^n o (s^n o c_a^n - s^{n-1} o c_a^{n-1})]
+ *     grad_sorption [k][Nc]     -sum_n mu_a^n o (c_a^n - c_a^{n-1}); with sorption == NULL the derivative at zero
+ *     grad_sink [Nc]            -sum_n phi^n o (lambda^n + sum_a mu_a^n o c_a^n)
+ *     grad_bc_values [Nf]       the saturation's boundary value.  Neumann face: as pfv_transport_adjoint_nl, from lambda
+ *                               alone.  Dirichlet inflow face: -sum_n q_f f'(bv_f) [(lambda[p] - lambda[m]) +
+ *                               sum_a (mu_a[p] - mu_a[m]) cbv_af]
+ *     grad_c_bc_values [k][Nf]  Neumann face: -sum_n (rhs_neu^T div^T mu_a^n)_f.  Dirichlet inflow face:
+ *                               -sum_n (mu_a[p] - mu_a[m]) q_f f(bv_f).  0 on every other face
+ *     grad_flux [Nf]            -sum_n [(lambda[p] - lambda[m]) phiup_f + sum_a (mu_a[p] - mu_a[m]) phiup_f cup_af]: phiup as
+ *                               in pfv_transport_adjoint_nl, cup the upstream cell's c_a^n (interior and outflow faces),
+ *                               cbv_af on a Dirichlet inflow face; 0 on a Neumann face
+ *     grad_fluxfn [6]           PFV_FLUXFN_COREY only (else PFV_ERR_ARGUMENT): the sums of pfv_transport_adjoint_nl with the
+ *                               cell weight (M^T lambda)_i + sum_a c_ai (M^T mu_a)_i and the face weight
+ *                               q_f [(lambda[p] - lambda[m]) + sum_a (mu_a[p] - mu_a[m]) cbv_af]
+ * All are derivatives on a FIXED branch, as those of pfv_transport_adjoint_nl.
+ *   A dry row -- acc_i s_i^n + sorption_ai + phi_i o_i = 0, where the forward step keeps c and does not determine it -- is
+ * refused with PFV_ERR_ARGUMENT naming the step, the cell and the component (found in the streaming pass over the slab,
+ * read with the step's norms).  Rows with d_i = 0 are legal.  PFV_ERR_ARGUMENT otherwise as pfv_transport_advance_nl_multi
+ * and pfv_transport_adjoint_nl; PFV_ERR_UNSUPPORTED as pfv_transport_advance_nl_multi.
+ *   steps_done: the adjoint steps completed.  A refused step returns PFV_ERR_NOT_CONVERGED and writes no gradient.
+ * last (1 + k entries, may be NULL): the saturation's, then the components'; iterations = 1 for an acyclic flux, else
+ * the core iterations of the last step; rel_residual the measured ones.  Handle rules as pfv_transport_adjoint_nl.
+ * pfv_stats: transport_nlc_adjoint_* and the sweep_* fields (sweep_launches: the forward sweep's on an acyclic flux). */
+pfv_status pfv_transport_adjoint_nl_multi(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
+                                          int n_params, const double* bc_values, const double* accumulation,
+                                          const double* sink, int k, const double* c_bc_values, const double* sorption,
+                                          int n_steps, int64_t n_obs, const int32_t* obs_cells, const double* s_loads,
+                                          const double* c_loads, const double* s_states, const double* c_states,
+                                          double rtol, int maxit, double* grad_s0, double* grad_c0, double* grad_source,
+                                          double* grad_c_source, double* grad_accumulation, double* grad_sorption,
+                                          double* grad_sink, double* grad_bc_values, double* grad_c_bc_values,
+                                          double* grad_flux, double* grad_fluxfn, int32_t* steps_done,
+                                          pfv_solve_info* last);
 
 /* ---- Advection-diffusion step on the device (csrc/advdiff.inc) ---------------------------------------------------
  * One handle carries the transport keyword: its diffusion discretization (pfv_mpfa_discretize or pfv_tpfa_discretize

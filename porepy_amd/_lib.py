@@ -52,7 +52,7 @@ EXPORTS = [
     "pfv_advdiff_assemble", "pfv_advdiff_advance", "pfv_advdiff_face_flux", "pfv_resident_flux",
     "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl", "pfv_transport_advance_nl_multi",
     "pfv_transport_advance_react", "pfv_transport_adjoint_multi", "pfv_transport_adjoint_react",
-    "pfv_transport_adjoint_nl",
+    "pfv_transport_adjoint_nl", "pfv_transport_adjoint_nl_multi",
 ]
 
 
@@ -96,7 +96,9 @@ class Stats(C.Structure):
                 ("transport_react_adjoint_ms", C.c_double), ("transport_react_adjoint_steps", C.c_int64),
                 ("transport_react_adjoint_core_iterations", C.c_int64), ("amg_galerkin_ap", C.c_int64),
                 ("transport_nl_adjoint_ms", C.c_double), ("transport_nl_adjoint_steps", C.c_int64),
-                ("transport_nl_adjoint_core_iterations", C.c_int64)]
+                ("transport_nl_adjoint_core_iterations", C.c_int64),
+                ("transport_nlc_adjoint_ms", C.c_double), ("transport_nlc_adjoint_steps", C.c_int64),
+                ("transport_nlc_adjoint_core_iterations", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -336,6 +338,11 @@ def _bind(lib: C.CDLL) -> C.CDLL:
                                              _dp, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                              C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
     lib.pfv_transport_adjoint_nl.restype = C.c_int
+    lib.pfv_transport_adjoint_nl_multi.argtypes = [_h, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp,
+                                                   C.c_int, C.c_int64, _ip, _dp, _dp, _dp, _dp, C.c_double, C.c_int,
+                                                   _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                   C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
+    lib.pfv_transport_adjoint_nl_multi.restype = C.c_int
     lib.pfv_advdiff_assemble.argtypes = [_h, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pfv_advdiff_assemble.restype = C.c_int
     lib.pfv_advdiff_advance.argtypes = [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(C.c_int32),
@@ -1797,6 +1804,101 @@ class Context:
             *[_ptr(grads.get(name), _dp) for name in self.NL_ADJOINT_GRADIENTS], C.byref(done), C.byref(info))
         out = {"steps_done": done.value, "iterations": info.iterations, "converged": bool(info.converged),
                "rel_residual": info.rel_residual, "solve_ms": info.solve_ms}
+        if st != 0 and (raise_on_fail or st != 6):
+            try:
+                self._check(st)
+            except PorefvError as e:
+                e.info = out
+                raise
+        return grads, out
+
+    NLC_ADJOINT_GRADIENTS = ("s0", "c0", "source", "c_source", "accumulation", "sorption", "sink", "bc_values",
+                             "c_bc_values", "flux", "flux_function")
+
+    def transport_adjoint_nl_multi(self, n_steps: int, accumulation, bc_values, c_bc_values, fluxfn_kind: int,
+                                   fluxfn_params, s_states, c_states, s_loads=None, c_loads=None, sorption=None,
+                                   sink=None, obs_cells=None, q=None, want=("s0", "c0", "source", "c_source"),
+                                   rtol=1e-12, maxit=500, raise_on_fail=True):
+        """The adjoint of ``transport_advance_nl_multi`` (pfv_transport_adjoint_nl_multi): the gradients of
+        ``J = sum_n [<s_loads[n-1], s^n[obs_cells]> + sum_a <c_loads[n-1, a], c_a^n[obs_cells]>]`` through ``n_steps``
+        steps of the saturation with k phase-carried components, by one fused transposed sweep in reverse flow order
+        per step.  ``s_states``: (N + 1) x Nc and ``c_states``: (N + 1) x k x Nc (both required, not checked for range
+        or finiteness; k is taken from ``c_states``); ``s_loads``: N x n_obs, ``c_loads``: N x k x n_obs (at least one;
+        a missing one is zeros); ``c_bc_values``: k x Nf; ``sorption``: k x Nc or None; the rest as
+        ``transport_adjoint_nl``.  ``want``: names out of ``NLC_ADJOINT_GRADIENTS``; "flux_function" needs
+        FLUXFN_COREY.  Returns (grads, info): grads[name] of shape Nc ("s0", "source", "accumulation", "sink"), k x Nc
+        ("c0", "c_source", "sorption"), Nf ("bc_values", "flux"), k x Nf ("c_bc_values") or 6 ("flux_function"); info
+        with ``steps_done``, ``converged``, ``iterations``, ``rel_residual`` (the saturation's) and the per-component
+        list ``c_rel_residual``.  A refused step leaves the gradients zero."""
+        n_steps = int(n_steps)
+        if n_steps < 0:
+            raise ValueError("n_steps must not be negative")
+        if s_states is None or c_states is None:
+            raise ValueError("s_states (s^0 .. s^N) and c_states (c^0 .. c^N) are required: the step is linearised "
+                             "about them")
+        cst = _f64(c_states)
+        if cst.ndim != 3 or cst.shape[0] != n_steps + 1 or cst.shape[2] != self.nc:
+            raise ValueError(f"c_states must have shape ({n_steps + 1}, k, {self.nc}), not {cst.shape}")
+        k = cst.shape[1]
+        if not 1 <= k <= 64:
+            raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (c_states has shape {cst.shape})")
+        sst = _f64(s_states)
+        if sst.shape != (n_steps + 1, self.nc):
+            raise ValueError(f"s_states must have shape ({n_steps + 1}, {self.nc}), not {sst.shape}")
+        acc = _f64(accumulation)
+        if acc.shape != (self.nc,):
+            raise ValueError(f"accumulation must have shape ({self.nc},), not {acc.shape}")
+        bv = _f64(bc_values)
+        if bv.shape != (self.nf,):
+            raise ValueError(f"bc_values must have shape ({self.nf},), not {bv.shape}")
+        cbv = _f64(c_bc_values)
+        if cbv.shape != (k, self.nf):
+            raise ValueError(f"c_bc_values must have shape ({k}, {self.nf}), not {cbv.shape}")
+        ads = None if sorption is None else _f64(sorption)
+        if ads is not None and ads.shape != (k, self.nc):
+            raise ValueError(f"sorption must have shape ({k}, {self.nc}), not {ads.shape}")
+        par = np.ascontiguousarray(fluxfn_params, dtype=np.float64).ravel()
+        obs = None
+        if obs_cells is not None:
+            obs = np.ascontiguousarray(obs_cells)
+            if obs.ndim != 1 or not np.issubdtype(obs.dtype, np.integer):
+                raise ValueError("obs_cells must be a one-dimensional array of cell indices")
+            big = obs[(obs < -2 ** 31) | (obs >= 2 ** 31)]
+            if big.size:
+                raise ValueError(f"obs_cells: {int(big[0])} is out of range (0 .. {self.nc - 1})")
+            obs = obs.astype(np.int32)
+        n_obs = self.nc if obs is None else obs.size
+        if s_loads is None and c_loads is None:
+            raise ValueError("s_loads or c_loads is required (a missing one is zeros)")
+        sld = None if s_loads is None else _f64(s_loads)
+        if sld is not None and sld.shape != (n_steps, n_obs):
+            raise ValueError(f"s_loads must have shape ({n_steps}, {n_obs}), not {sld.shape}")
+        cld = None if c_loads is None else _f64(c_loads)
+        if cld is not None and cld.shape != (n_steps, k, n_obs):
+            raise ValueError(f"c_loads must have shape ({n_steps}, {k}, {n_obs}), not {cld.shape}")
+        want = tuple(want)
+        for name in want:
+            if name not in self.NLC_ADJOINT_GRADIENTS:
+                raise ValueError(f"want: unknown gradient {name!r} (known: {', '.join(self.NLC_ADJOINT_GRADIENTS)})")
+            if name == "flux_function" and int(fluxfn_kind) != FLUXFN_COREY:
+                raise ValueError('the gradient "flux_function" is that of the six Corey parameters: it needs a '
+                                 'CoreyFractionalFlow')
+        kq, pq = self._vec(q, self.nf, "the flux array", False)
+        kk, pk = self._vec(sink, self.nc, "sink", False)
+        nc, nf = self.nc, self.nf
+        shapes = {"s0": (nc,), "c0": (k, nc), "source": (nc,), "c_source": (k, nc), "accumulation": (nc,),
+                  "sorption": (k, nc), "sink": (nc,), "bc_values": (nf,), "c_bc_values": (k, nf), "flux": (nf,),
+                  "flux_function": (6,)}
+        grads = {name: np.zeros(shapes[name]) for name in self.NLC_ADJOINT_GRADIENTS if name in want}
+        done, infos = C.c_int32(0), (SolveInfo * (k + 1))()
+        st = self.lib.pfv_transport_adjoint_nl_multi(
+            self._h, pq, int(fluxfn_kind), _ptr(par, _dp) if par.size else None, int(par.size), _ptr(bv, _dp),
+            _ptr(acc, _dp), pk, k, _ptr(cbv, _dp), _ptr(ads, _dp), n_steps, n_obs, _ptr(obs, _ip), _ptr(sld, _dp),
+            _ptr(cld, _dp), _ptr(sst, _dp), _ptr(cst, _dp), float(rtol), int(maxit),
+            *[_ptr(grads.get(name), _dp) for name in self.NLC_ADJOINT_GRADIENTS], C.byref(done), infos)
+        out = {"steps_done": done.value, "iterations": infos[0].iterations,
+               "converged": all(bool(i.converged) for i in infos), "rel_residual": infos[0].rel_residual,
+               "c_rel_residual": [i.rel_residual for i in infos[1:]], "solve_ms": infos[0].solve_ms}
         if st != 0 and (raise_on_fail or st != 6):
             try:
                 self._check(st)

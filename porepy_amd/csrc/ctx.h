@@ -367,6 +367,11 @@ struct pfv_ctx_impl {
   // the aj_ ones (k = 1).  aj_d / aj_phi: f'(s^n) and f(s^n) of the step's slab; the accumulators of grad_sink [nc] and
   // of grad_fluxfn (the six Corey parameters)
   Buf<double> aj_d, aj_phi, aj_gsink, aj_gF;
+  // the adjoint of the step with phase-carried components (pfv_transport_adjoint_nl_multi): the saturation's side in the
+  // buffers above (its loads [N][n_obs] in aj_sloads), c_bc_values and the sorption in nlc_cbc / nlc_ads_in / nlc_ads.
+  // Interleaved: the two slabs c^n / c^{n+1}, mu^n / mu^{n+1}, the core's previous iterate, mu's right-hand side; the
+  // accumulators of grad_c_source and grad_sorption (interleaved) and of grad_c_bc_values (component-major [k][nf])
+  Buf<double> aj_sloads, aj_cA, aj_cB, aj_mu, aj_mu2, aj_muprev, aj_rmu, aj_gcsrc, aj_gads, aj_gcbc;
 
   // ---- advection-diffusion (advdiff.inc): S = diag(acc) + div flux_D + w div diag(q) U on pat_A -------------------
   bool have_advdiff = false;         // val[PFV_MAT_ADVDIFF_SYSTEM], adv_diag, adv_rhs hold a system of the discretization

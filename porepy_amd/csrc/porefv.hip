@@ -2427,6 +2427,296 @@ pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind
   return st;
 }
 
+// ---- the adjoint of the saturation step with phase-carried components: one fused transposed sweep per step ------------
+// Its own loop in the order of adjoint_steps (whose right-hand side g + acc o lambda+ has one kind of multiplier): per
+// step n = N .. 1 the slab (s^n, c^n), the slopes with the dry-row flag, the two right-hand sides fused with what the
+// multipliers of step n + 1 add to the cell gradients, the backward-peel levels from last to first (sweep_row_nlc_t),
+// the core level iterated by Jacobi on mu and lambda jointly, the forward-peel levels, the k + 1 pairs of norms and ONE
+// host read that brings the flag with them; then the gradients of the accepted step and the swap.  After the last step
+// slab 0 is staged and the right-hand-side kernel runs once more: it leaves grad_s0 and grad_c0.
+pfv_status pfv_transport_adjoint_nl_multi(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
+                                          int n_params, const double* bc_values, const double* accumulation,
+                                          const double* sink, int k, const double* c_bc_values, const double* sorption,
+                                          int n_steps, int64_t n_obs, const int32_t* obs_cells, const double* s_loads,
+                                          const double* c_loads, const double* s_states, const double* c_states,
+                                          double rtol, int maxit, double* grad_s0, double* grad_c0, double* grad_source,
+                                          double* grad_c_source, double* grad_accumulation, double* grad_sorption,
+                                          double* grad_sink, double* grad_bc_values, double* grad_c_bc_values,
+                                          double* grad_flux, double* grad_fluxfn, int32_t* steps_done,
+                                          pfv_solve_info* last) {
+  if (steps_done) *steps_done = 0;
+  if (k < 1 || k > 64) return guarded(h, [&] { require(false, "k must lie in 1 .. 64"); });
+  std::unique_ptr<pfv::Timer> tm;
+  bool touched = false;
+  double order_ms = 0.0;
+  const double* d_q = nullptr;
+  size_t nc = 0, nf = 0;
+  pfv::FluxFn F;
+  pfv_status st = guarded(h, [&] {
+    upwind_supported(h);
+    if (h->subface_bc) throw Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
+    require(h->have_upwind, "pfv_upwind_discretize first");
+    require(h->upw_ncomp == 1, "the saturation step needs pfv_upwind_discretize with num_components = 1");
+    const std::string bad = pfv::fluxfn_check(fluxfn_kind, fluxfn_params, n_params);
+    if (!bad.empty()) throw Error(PFV_ERR_ARGUMENT, bad);
+    require(!grad_fluxfn || fluxfn_kind == PFV_FLUXFN_COREY,
+            "grad_fluxfn is the gradient with respect to the six Corey parameters: PFV_FLUXFN_COREY only");
+    require(bc_values && accumulation, "bc_values and accumulation are required");
+    require(c_bc_values, "c_bc_values is required");
+    require(n_steps >= 0, "bad argument");
+    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
+    require(s_loads || c_loads || n_steps == 0, "s_loads or c_loads is required");
+    require((s_states && c_states) || n_steps == 0,
+            "s_states (s^0 .. s^N) and c_states (c^0 .. c^N) are required: the step is linearised about them");
+    nc = (size_t)h->nc;
+    nf = (size_t)h->nf;
+    if ((int64_t)(k + 1) * (int64_t)std::max(nc, nf) >= (int64_t(1) << 31))
+      throw Error(PFV_ERR_UNSUPPORTED, "(k + 1) x cells (faces) beyond int32 indices");
+    // the observation: the saturation's loads first (they move to their own buffer), then the components'
+    if (s_loads && n_steps > 0) {
+      adjoint_take_loads(h, 1, n_steps, n_obs, obs_cells, s_loads);
+      const size_t nl = (size_t)n_steps * (size_t)n_obs;
+      if (nl) pfv::be_d2d(h->aj_sloads.ensure(nl), h->aj_loads.p, sizeof(double) * nl, h->stream);
+    }
+    adjoint_take_loads(h, k, c_loads ? n_steps : 0, n_obs, obs_cells, c_loads);
+    if (q) vec_in(h, h->nl_q.ensure(nf), q, nf);
+    vec_in(h, h->nl_bc.ensure(nf), bc_values, nf);
+    vec_in(h, h->nl_acc.ensure(nc), accumulation, nc);
+    if (sink) vec_in(h, h->nl_sink.ensure(nc), sink, nc);
+    vec_in(h, h->nlc_cbc.ensure(k * nf), c_bc_values, k * nf);
+    if (sorption) vec_in(h, h->nlc_ads_in.ensure(k * nc), sorption, k * nc);
+    d_q = q ? h->nl_q.p : h->upw_q.p;
+    pfv::upwind_face_cells(*h);
+    // (the states are not checked: the accumulation stands in for s, zeros for c -- off[2] and off[6] say nothing)
+    pfv::be_memset(h->nlc_c_in.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
+    int32_t off[pfv::kNlChecks];
+    pfv::sweep_nl_check_inputs(*h, d_q, h->nl_bc.p, h->nl_acc.p, sink ? h->nl_sink.p : nullptr, h->nl_acc.p, k,
+                               sorption ? h->nlc_ads_in.p : nullptr, h->nlc_c_in.p, h->nlc_cbc.p, off);
+    static const char* what[5] = {"accumulation must be positive: cell ", "negative sink in cell ", nullptr,
+                                  "Dirichlet inflow value outside [0, 1] on face ", pfv::kUnmarkedInflowFace};
+    for (int m = 0; m < 5; ++m)
+      if (what[m] && off[m] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, what[m] + std::to_string(off[m]));
+    static const char* whatc[3] = {"sorption must not be negative: cell ", nullptr, "c_bc_values is not finite on face "};
+    for (int m = 0; m < 3; ++m)
+      if (whatc[m] && off[5 + m] != 0x7f7f7f7f)
+        throw Error(PFV_ERR_ARGUMENT, whatc[m] + std::to_string(off[5 + m] / k) + ", component " +
+                                          std::to_string(off[5 + m] % k));
+    if (fluxfn_kind == PFV_FLUXFN_TABLE)
+      be_h2d(h->nl_table.ensure((size_t)n_params), fluxfn_params, sizeof(double) * (size_t)n_params, h->stream);
+    F = pfv::fluxfn_make(fluxfn_kind, fluxfn_params, n_params, h->nl_table.p);
+    tm = std::make_unique<pfv::Timer>();
+    tm->start(h->stream);
+    // A = div diag(q) U without accumulation, once per call; its transposed values beside it
+    upwind_drop_transport(h, true);
+    touched = true;
+    pfv::upwind_assemble(*h, d_q, h->nl_bc.p, nullptr, nullptr, nullptr);
+    values_changed(h, Windows::drop);
+    const size_t nnz = (size_t)std::max<int64_t>(h->pat_T.nnz, 1);
+    if (!h->have_tpos_T) {
+      pfv::sweep_transpose_positions(*h, h->pat_T, h->tpos_T.ensure(nnz));
+      h->have_tpos_T = true;
+    }
+    pfv::sweep_transpose_values(*h, h->pat_T.nnz, h->tpos_T.p, h->val[PFV_MAT_TRANSPORT_SYSTEM].p, h->valT_T.ensure(nnz));
+    adjoint_take_slots(h, n_obs, obs_cells);
+    if (sorption) pfv::multi_interleave(*h, (int64_t)nc, k, h->nlc_ads_in.p, h->nlc_ads.ensure(k * nc));
+    for (pfv::Buf<double>* b : {&h->aj_lam, &h->aj_lam2, &h->aj_prev, &h->aj_r, &h->aj_sA, &h->aj_sB, &h->aj_d, &h->aj_phi})
+      b->ensure(nc);
+    for (pfv::Buf<double>* b : {&h->aj_mu, &h->aj_mu2, &h->aj_muprev, &h->aj_rmu, &h->aj_cA, &h->aj_cB, &h->aj_state_in,
+                                &h->mc_c})
+      b->ensure(k * nc);
+    pfv::be_memset(h->aj_mu.p, 0, sizeof(double) * k * nc, h->stream);  // mu^{N+1} = 0
+    if (grad_source) pfv::be_memset(h->aj_gsrc.ensure(nc), 0, sizeof(double) * nc, h->stream);
+    if (grad_accumulation) pfv::be_memset(h->aj_gacc.ensure(nc), 0, sizeof(double) * nc, h->stream);
+    if (grad_sink) pfv::be_memset(h->aj_gsink.ensure(nc), 0, sizeof(double) * nc, h->stream);
+    if (grad_c_source) pfv::be_memset(h->aj_gcsrc.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
+    if (grad_sorption) pfv::be_memset(h->aj_gads.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
+    if (grad_bc_values) pfv::be_memset(h->aj_gbc.ensure(nf), 0, sizeof(double) * nf, h->stream);
+    if (grad_c_bc_values) pfv::be_memset(h->aj_gcbc.ensure(k * nf), 0, sizeof(double) * k * nf, h->stream);
+    if (grad_flux) pfv::be_memset(h->aj_gq.ensure(nf), 0, sizeof(double) * nf, h->stream);
+    if (grad_fluxfn) pfv::be_memset(h->aj_gF.ensure(6), 0, sizeof(double) * 6, h->stream);
+    h->mc_nrm.ensure(2 * (size_t)(k + 1) + 1);  // the k + 1 pairs, then the word of the dry rows
+    transport_order(h, d_q, order_ms);
+  });
+  if (st != PFV_OK) {
+    if (touched) upwind_drop_transport(h, true);  // (A without accumulation: not a system to be solved with)
+    return st;
+  }
+
+  const int K = k + 1;  // the norms' pairs: components 0 .. k - 1, then the saturation
+  AdjointRun run;
+  run.info.assign((size_t)K, pfv_solve_info{});
+  std::vector<double> hst(2 * (size_t)K + 1);
+  const double* d_sink = sink ? h->nl_sink.p : nullptr;
+  const double* d_ads = sorption ? h->nlc_ads.p : nullptr;
+  const int32_t* slot = obs_cells ? h->aj_slot.p : nullptr;
+  // slab n of the states: s into `ts`, c interleaved into `tc`
+  auto stage_slab = [&](int n, double* ts, double* tc) {
+    vec_in(h, ts, s_states + (size_t)n * nc, nc);
+    vec_in(h, h->aj_state_in.p, c_states + (size_t)n * k * nc, k * nc);
+    pfv::multi_interleave(*h, (int64_t)nc, k, h->aj_state_in.p, tc);
+  };
+  std::string err;
+  bool have_next = false;  // aj_lam / aj_mu hold the multipliers of step n + 1
+  for (int n = n_steps; n >= 1 && st == PFV_OK; --n) {
+    pfv_status verdict = PFV_OK;
+    st = guarded(h, [&] {
+      pfv::pfv_ctx_impl& cx = *h;
+      const pfv::Sweep& sw = *cx.sweep;
+      const double* valT = cx.valT_T.p;
+      const double *acc = cx.nl_acc.p, *d = cx.aj_d.p, *phi = cx.aj_phi.p, *diag = cx.diag_t.p;
+      double* out = cx.mc_nrm.p;
+      int32_t* dry = reinterpret_cast<int32_t*>(out + 2 * K);
+      const bool has_core = sw.n_core > 0;
+      const int core = has_core ? sw.core_level : -1;
+      stage_slab(n, cx.aj_sB.p, cx.aj_cB.p);  // (s^n, c^n); aj_sA / aj_cA hold slab n + 1
+      const double *s_n = cx.aj_sB.p, *c_n = cx.aj_cB.p;
+      pfv::be_memset(dry, 0x7f, sizeof(double), cx.stream);
+      pfv::adjoint_nlc_slopes(cx, F, k, s_n, diag, d_sink, acc, d_ads, cx.aj_d.p, cx.aj_phi.p, dry);
+      pfv::adjoint_nlc_step_rhs(cx, k, acc, d_ads, s_n, c_n, cx.aj_sA.p, cx.aj_cA.p, have_next ? cx.aj_lam.p : nullptr,
+                                cx.aj_mu.p, slot, s_loads ? cx.aj_sloads.p + (size_t)(n - 1) * (size_t)n_obs : nullptr,
+                                c_loads ? cx.aj_loads.p + (size_t)(n - 1) * k * (size_t)n_obs : nullptr, n_obs, false,
+                                grad_source ? cx.aj_gsrc.p : nullptr, grad_c_source ? cx.aj_gcsrc.p : nullptr,
+                                grad_accumulation ? cx.aj_gacc.p : nullptr, grad_sorption ? cx.aj_gads.p : nullptr,
+                                cx.aj_r.p, cx.aj_rmu.p);
+      double* z = cx.aj_lam2.p;
+      pfv::NlCompT C;  // the levels outside the core; Cc: the core level, with the previous iterate
+      C.k = k;
+      C.ads = d_ads;
+      C.r = cx.aj_rmu.p;
+      C.mu_next = cx.aj_mu.p;
+      C.c = c_n;
+      C.mu = cx.aj_mu2.p;
+      pfv::NlCompT Cc = C;
+      Cc.mu_prev = cx.aj_muprev.p;
+      Cc.lam_prev = cx.aj_prev.p;
+      auto dry_row = [&]() -> bool {
+        int32_t w;
+        std::memcpy(&w, hst.data() + 2 * K, sizeof(w));
+        if (w == 0x7f7f7f7f) return false;
+        cx.err = "adjoint step " + std::to_string(n) + ": cell " + std::to_string(w / k) + ", component " +
+                 std::to_string(w % k) + " is dry (accumulation x s + sorption + f(s) x outflow is zero: the step does "
+                 "not determine the component there)";
+        return true;
+      };
+      run.launches = pfv::sweep_apply_nlc_t(cx, sw, core + 1, sw.nlev, cx.pat_T, valT, diag, d_sink, acc, d, phi, s_n,
+                                            cx.aj_r.p, z, C);
+      int core_it = 0;
+      if (has_core) {
+        pfv::sweep_core_zero(cx, sw, 1, z);
+        pfv::sweep_core_zero(cx, sw, k, C.mu);
+        const CoreRun cr = core_iterate(h, maxit, out, hst, [&] {
+          pfv::sweep_core_copy(cx, sw, 1, z, cx.aj_prev.p);
+          pfv::sweep_core_copy(cx, sw, k, C.mu, cx.aj_muprev.p);
+          pfv::sweep_core_nlc_t(cx, sw, cx.pat_T, valT, diag, d_sink, acc, d, phi, s_n, cx.aj_r.p, z, Cc);
+        }, [&] {
+          pfv::sweep_norms_nlc_t(cx, sw, cx.pat_T, valT, d_sink, acc, d, phi, s_n, cx.aj_r.p, z, C, true, out);
+        }, [&] {  // (a dry row never settles: it ends the iteration and is reported below)
+          int32_t w;
+          std::memcpy(&w, hst.data() + 2 * K, sizeof(w));
+          return w != 0x7f7f7f7f || adjoint_norms_pass(hst, K, 0.5 * rtol);
+        });
+        core_it = cr.iterations;
+        run.core_total += core_it;
+        run.launches += 2;
+        if (dry_row()) throw Error(PFV_ERR_ARGUMENT, cx.err);
+        if (!cr.settled) {  // (what the forward-peel levels would compute from this core is not judged)
+          adjoint_component_info(run.info, hst, K, core_it);
+          cx.err = "adjoint step " + std::to_string(n) + ": the cyclic core of " + std::to_string(sw.n_core) +
+                   " cells did not settle in " + std::to_string(core_it) + " iterations";
+          verdict = PFV_ERR_NOT_CONVERGED;
+          return;
+        }
+        run.launches += pfv::sweep_apply_nlc_t(cx, sw, 0, core, cx.pat_T, valT, diag, d_sink, acc, d, phi, s_n, cx.aj_r.p,
+                                               z, C);
+      }
+      pfv::sweep_norms_nlc_t(cx, sw, cx.pat_T, valT, d_sink, acc, d, phi, s_n, cx.aj_r.p, z, C, false, out);
+      be_d2h(hst.data(), out, sizeof(double) * hst.size(), cx.stream);
+      if (dry_row()) throw Error(PFV_ERR_ARGUMENT, cx.err);
+      adjoint_component_info(run.info, hst, K, has_core ? core_it : 1);
+      int bad = -1;  // the first check that fails; k: the saturation's (judged first)
+      for (int a = k - 1; a >= 0; --a) {
+        run.info[(size_t)a].converged = hst[(size_t)K + a] <= rtol * rtol * hst[(size_t)a] ? 1 : 0;  // (0 <= 0 counts)
+        if (!run.info[(size_t)a].converged) bad = a;
+      }
+      run.info[(size_t)k].converged = hst[(size_t)K + k] <= rtol * rtol * hst[(size_t)k] ? 1 : 0;
+      if (!run.info[(size_t)k].converged) bad = k;
+      if (bad >= 0) {
+        cx.err = "adjoint step " + std::to_string(n) + ": relative residual " +
+                 std::to_string(run.info[(size_t)bad].rel_residual) +
+                 (bad == k ? std::string() : " of component " + std::to_string(bad)) +
+                 " after the transposed sweep (a flux that contradicts the discretization's?)";
+        verdict = PFV_ERR_NOT_CONVERGED;
+        return;
+      }
+      const double* mu = C.mu;
+      if (grad_sink) pfv::adjoint_nlc_grad_sink(cx, k, z, mu, c_n, phi, cx.aj_gsink.p);
+      if (grad_bc_values) pfv::adjoint_nlc_grad_bc(cx, F, k, d_q, cx.nl_bc.p, cx.nlc_cbc.p, z, mu, cx.aj_gbc.p);
+      if (grad_c_bc_values) pfv::adjoint_nlc_grad_cbc(cx, F, k, d_q, cx.nl_bc.p, mu, cx.aj_gcbc.p);
+      if (grad_flux) pfv::adjoint_nlc_grad_flux(cx, F, k, cx.nl_bc.p, cx.nlc_cbc.p, z, mu, phi, c_n, cx.aj_gq.p);
+      if (grad_fluxfn)
+        pfv::adjoint_nlc_grad_fluxfn(cx, F, cx.pat_T, valT, d_sink, k, d_q, cx.nl_bc.p, cx.nlc_cbc.p, z, mu, s_n, c_n,
+                                     cx.aj_gF.p);
+      cx.aj_lam.swap(cx.aj_lam2);
+      cx.aj_mu.swap(cx.aj_mu2);
+      cx.aj_sA.swap(cx.aj_sB);
+      cx.aj_cA.swap(cx.aj_cB);
+      have_next = true;
+      ++run.completed;
+    });
+    if (st == PFV_OK) st = verdict;
+  }
+  if (st != PFV_OK) err = h->err;
+  const pfv_status st2 = guarded(h, [&] {
+    pfv::pfv_ctx_impl& cx = *h;
+    if (st == PFV_OK) {
+      // lambda^1 and mu^1 into the cell gradients on slab 0; the right-hand sides they leave are grad_s0 and grad_c0
+      if (have_next) {
+        stage_slab(0, cx.aj_sB.p, cx.aj_cB.p);
+        pfv::adjoint_nlc_step_rhs(cx, k, cx.nl_acc.p, d_ads, cx.aj_sB.p, cx.aj_cB.p, cx.aj_sA.p, cx.aj_cA.p, cx.aj_lam.p,
+                                  cx.aj_mu.p, nullptr, nullptr, nullptr, 0, true, grad_source ? cx.aj_gsrc.p : nullptr,
+                                  grad_c_source ? cx.aj_gcsrc.p : nullptr, grad_accumulation ? cx.aj_gacc.p : nullptr,
+                                  grad_sorption ? cx.aj_gads.p : nullptr, cx.aj_r.p, cx.aj_rmu.p);
+      } else {
+        pfv::be_memset(cx.aj_r.p, 0, sizeof(double) * nc, cx.stream);
+        pfv::be_memset(cx.aj_rmu.p, 0, sizeof(double) * k * nc, cx.stream);
+      }
+    }
+    run.ms = tm->stop(cx.stream);
+    tm.reset();
+    if (st == PFV_OK) {
+      auto cells_out = [&](double* to, const double* from) {
+        pfv::multi_deinterleave(cx, (int64_t)nc, k, from, cx.mc_c.p);
+        vec_out(h, to, cx.mc_c.p, k * nc);
+      };
+      if (grad_s0) vec_out(h, grad_s0, cx.aj_r.p, nc);
+      if (grad_c0) cells_out(grad_c0, cx.aj_rmu.p);
+      if (grad_source) vec_out(h, grad_source, cx.aj_gsrc.p, nc);
+      if (grad_c_source) cells_out(grad_c_source, cx.aj_gcsrc.p);
+      if (grad_accumulation) vec_out(h, grad_accumulation, cx.aj_gacc.p, nc);
+      if (grad_sorption) cells_out(grad_sorption, cx.aj_gads.p);
+      if (grad_sink) vec_out(h, grad_sink, cx.aj_gsink.p, nc);
+      if (grad_bc_values) vec_out(h, grad_bc_values, cx.aj_gbc.p, nf);
+      if (grad_c_bc_values) vec_out(h, grad_c_bc_values, cx.aj_gcbc.p, k * nf);
+      if (grad_flux) vec_out(h, grad_flux, cx.aj_gq.p, nf);
+      if (grad_fluxfn) be_d2h(grad_fluxfn, cx.aj_gF.p, sizeof(double) * 6, cx.stream);  // (host memory, as the parameters are)
+    }
+    pfv::be_sync(cx.stream);
+    upwind_drop_transport(h, true);
+  });
+  if (steps_done) *steps_done = run.completed;
+  if (last) {
+    last[0] = run.info[(size_t)k];
+    for (int a = 0; a < k; ++a) last[1 + a] = run.info[(size_t)a];
+    if (run.completed > 0)
+      for (int a = 0; a <= k; ++a) last[a].solve_ms = run.ms / run.completed;
+  }
+  h->stats.transport_nlc_adjoint_ms = run.ms;
+  h->stats.transport_nlc_adjoint_steps = run.completed;
+  h->stats.transport_nlc_adjoint_core_iterations = run.core_total;
+  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, order_ms);
+  return step_status(h, st, err, st2);
+}
+
 // ---- advection-diffusion on one handle (advdiff.inc) -----------------------------------------------------------
 static void advdiff_supported(pfv_ctx* h) {
   require(h->have_grid, "pfv_set_grid first");

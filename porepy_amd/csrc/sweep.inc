@@ -1623,15 +1623,15 @@ static void adjoint_nl_grad_flux(pfv_ctx_impl& c, const FluxFn& F, const double*
 // pairwise in LDS, and one workgroup per parameter adds the workgroups' partial sums and subtracts the result from the
 // parameter's accumulator: the steps add in step order.  No floating-point atomics, no per-thread array under a
 // run-time index.
-static void adjoint_nl_grad_fluxfn(pfv_ctx_impl& c, const FluxFn& F, const CsrPattern& P, const double* valT,
-                                   const double* sink, const double* d_q, const double* bc, const double* lam,
-                                   const double* s_n, double* gF) {
+// The scheme with the two weights as functors: cell_w(i) is the weight of cell i, face_w(f) that of the Dirichlet inflow
+// face f.  adjoint_nl_grad_fluxfn hands in the weights above; the step with phase-carried components adds the
+// components' terms to both (adjoint_nlc_grad_fluxfn).
+template <class CellW, class FaceW>
+static void adjoint_nl_grad_fluxfn_weighted(pfv_ctx_impl& c, const FluxFn& F, const double* bc, const double* s_n,
+                                            double* gF, CellW cell_w, FaceW face_w) {
   stream_t s = c.stream;
   const int64_t nc = c.nc, nf = c.nf, n = nc + nf;
-  const int32_t* ip = P.indptr;
-  const int32_t* ix = P.indices;
   const uint8_t* cls = c.upw_cls;
-  const int32_t* side = c.upw_side;
   const int nb = (int)std::min<int64_t>(kGmresBlocks, (n + 2047) / 2048);
   double* partial = c.red.ensure(6 * (size_t)kGmresBlocks + 64);
   block_for<256>(s, nb, 6 * 256 * sizeof(double), PFV_LAMBDA(const WaveCtx& w) {
@@ -1644,17 +1644,13 @@ static void adjoint_nl_grad_fluxfn(pfv_ctx_impl& c, const FluxFn& F, const CsrPa
         double wt = 0.0, at = 0.0;  // the weight of the item and the saturation its derivatives are taken at
         bool live = false;
         if (t < nc) {
-          wt = sweep_nl_t_row_image(t, ip, ix, valT, sink, lam, nullptr, -1);
+          wt = cell_w(t);
           at = s_n[t];
           live = true;
         } else {
           const int64_t f = t - nc;
           if (cls[f] & UPW_DIRIN) {
-            const int32_t cp = side[f], cm = side[nf + f];
-            double dl = 0.0;
-            if (cp >= 0) dl = lam[cp];
-            if (cm >= 0) dl -= lam[cm];
-            wt = dl * d_q[f];
+            wt = face_w(f);
             at = bc[f];
             live = true;
           }
@@ -1700,6 +1696,441 @@ static void adjoint_nl_grad_fluxfn(pfv_ctx_impl& c, const FluxFn& F, const CsrPa
     }
     if (wc.lane0()) gF[m] -= sh[0];
     wc.sync();
+  });
+}
+
+static void adjoint_nl_grad_fluxfn(pfv_ctx_impl& c, const FluxFn& F, const CsrPattern& P, const double* valT,
+                                   const double* sink, const double* d_q, const double* bc, const double* lam,
+                                   const double* s_n, double* gF) {
+  const int64_t nf = c.nf;
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* side = c.upw_side;
+  adjoint_nl_grad_fluxfn_weighted(c, F, bc, s_n, gF, PFV_LAMBDA(int64_t t) {
+    return sweep_nl_t_row_image(t, ip, ix, valT, sink, lam, nullptr, -1);
+  }, PFV_LAMBDA(int64_t f) {
+    const int32_t cp = side[f], cm = side[nf + f];
+    double dl = 0.0;
+    if (cp >= 0) dl = lam[cp];
+    if (cm >= 0) dl -= lam[cm];
+    return dl * d_q[f];
+  });
+}
+
+// ---- the adjoint of the saturation step with phase-carried components (pfv_transport_adjoint_nl_multi).  With the
+// multipliers lambda of the saturation's equation and mu_a of component a's, e_a = acc o s^n + ads_a, phi = f(s^n),
+// d = f'(s^n) and M = A + diag(sink), step n solves
+//     (diag(e_a) + diag(phi) M^T) mu_a = rmu_a                                                        (a = 0 .. k-1)
+//     (diag(acc) + diag(d) M^T) lambda = rl - sum_a c_a^n o [acc o (mu_a - mu_a^{n+1}) + d o (M^T mu_a)]
+// -- block triangular: the mu blocks, then lambda.  In reverse flow order row i is k + 1 divisions once the cells
+// downstream of it are known: with o = A_ii + sink_i and u_a = sum_{lev[j] > lev[i]} valT[e] mu_aj
+//     mu_ai = (rmu_ai - phi_i u_a) / (acc_i s_i + ads_ai + phi_i o),      (M^T mu_a)_i = u_a + o mu_ai
+// so the coupling term of lambda's right-hand side is known inside the row, and lambda_i is the division of
+// sweep_row_nl_t on rl_i minus that term.  One thread per row, the load chain of sweep_row_nlc: the components four
+// accumulators at a time with the entries in groups of kNlcGroup, the sums in stored order; a slot past the row's end
+// repeats the last entry, a slot that is not downstream reads the row's own right-hand side (an address that is valid
+// and that no thread writes here) and enters as + 0; in the last chunk an accumulator beyond k takes component a0 again
+// and its coupling term is selected away, so nothing branches on k; all loads of a chunk come before its first store.
+// The first chunk's groups carry lambda's downstream sum beside the four of mu (the indices, levels and values are
+// loaded once for both); the coupling sum is carried across the chunks; lambda's division comes last.
+//   core   rows of the core level take their in-core neighbours of both mu and lambda from the previous iterate:
+//          Jacobi on a block-triangular system, which converges at the rate of its diagonal blocks -- those of the
+//          forward components' step and of sweep_row_nl_t_core.
+struct NlCompT {
+  int k = 0;
+  const double* ads = nullptr;       // [n k] sorption capacity (may be nullptr)
+  const double* r = nullptr;         // [n k] the right-hand side of mu
+  const double* mu_next = nullptr;   // [n k] mu^{n+1} (zeros in the first step)
+  const double* c = nullptr;         // [n k] c^n
+  const double* mu_prev = nullptr;   // [n k] the core's previous iterate of mu ...
+  const double* lam_prev = nullptr;  // [n]   ... and of lambda
+  double* mu = nullptr;
+};
+struct NlcTSums {
+  double u0, u1, u2, u3, sl;
+};
+
+// the sums of the chunk a0 .. a0 + 3 over the row's entries; WithLam: lambda's sum beside them
+template <bool Core, bool WithLam>
+PFV_FN NlcTSums sweep_nlc_t_sums(int32_t i, int32_t li, int e_begin, int e_end, const int32_t* ix, const double* valT,
+                                 const int32_t* lev, int k, int a0, int o1, int o2, int o3, const double* mu,
+                                 const double* mu_prev, const double* own, const double* lam, const double* lam_prev,
+                                 const double* own_l) {
+  NlcTSums S{0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int e0 = e_begin; e0 < e_end; e0 += kNlcGroup) {
+    int32_t j[kNlcGroup];
+    double v[kNlcGroup];
+    const double* up[kNlcGroup];
+    const double* upl[kNlcGroup];
+#pragma unroll
+    for (int t = 0; t < kNlcGroup; ++t) {
+      const int e = e0 + t < e_end ? e0 + t : e_end - 1;
+      j[t] = ix[e];
+      v[t] = valT[e];
+    }
+#pragma unroll
+    for (int t = 0; t < kNlcGroup; ++t) {
+      const int32_t lj = lev[j[t]];
+      const bool down = lj > li, in_core = Core && lj == li && j[t] != i;
+      const bool live = (down || in_core) && e0 + t < e_end;
+      up[t] = live ? (down ? mu : mu_prev) + (int64_t)j[t] * k + a0 : nullptr;
+      if (WithLam) upl[t] = live ? (down ? lam : lam_prev) + j[t] : nullptr;
+    }
+#pragma unroll
+    for (int t = 0; t < kNlcGroup; ++t) {
+      const double* r = up[t] ? up[t] : own;
+      const double w0 = r[0], w1 = r[o1], w2 = r[o2], w3 = r[o3];
+      const double vt = up[t] ? v[t] : 0.0;
+      S.u0 += vt * (up[t] ? w0 : 0.0);
+      S.u1 += vt * (up[t] ? w1 : 0.0);
+      S.u2 += vt * (up[t] ? w2 : 0.0);
+      S.u3 += vt * (up[t] ? w3 : 0.0);
+      if (WithLam) {
+        const double wl = *(upl[t] ? upl[t] : own_l);
+        S.sl += vt * (upl[t] ? wl : 0.0);
+      }
+    }
+  }
+  return S;
+}
+
+// the four divisions of the chunk and its part of lambda's coupling term (m = k - a0 components are the chunk's own)
+PFV_FN double sweep_nlc_t_divide(const NlCompT& C, int64_t p0, int o1, int o2, int o3, int m, double as, double op,
+                                 double ph, double o, double ac, double di, const NlcTSums& S) {
+  const int64_t p1 = p0 + o1, p2 = p0 + o2, p3 = p0 + o3;
+  const double r0 = C.r[p0], r1 = C.r[p1], r2 = C.r[p2], r3 = C.r[p3];
+  const double g0 = C.ads ? C.ads[p0] : 0.0, g1 = C.ads ? C.ads[p1] : 0.0;
+  const double g2 = C.ads ? C.ads[p2] : 0.0, g3 = C.ads ? C.ads[p3] : 0.0;
+  const double n0 = C.mu_next[p0], n1 = C.mu_next[p1], n2 = C.mu_next[p2], n3 = C.mu_next[p3];
+  const double c0 = C.c[p0], c1 = C.c[p1], c2 = C.c[p2], c3 = C.c[p3];
+  const double x0 = (r0 - ph * S.u0) / (as + g0 + op), x1 = (r1 - ph * S.u1) / (as + g1 + op);
+  const double x2 = (r2 - ph * S.u2) / (as + g2 + op), x3 = (r3 - ph * S.u3) / (as + g3 + op);
+  C.mu[p0] = x0;  // (the loads of all four before the first store: a store could alias them for the compiler)
+  C.mu[p1] = x1;
+  C.mu[p2] = x2;
+  C.mu[p3] = x3;
+  const double t0 = c0 * (ac * (x0 - n0) + di * (S.u0 + o * x0)), t1 = c1 * (ac * (x1 - n1) + di * (S.u1 + o * x1));
+  const double t2 = c2 * (ac * (x2 - n2) + di * (S.u2 + o * x2)), t3 = c3 * (ac * (x3 - n3) + di * (S.u3 + o * x3));
+  double sum = t0;
+  sum += m > 1 ? t1 : 0.0;
+  sum += m > 2 ? t2 : 0.0;
+  sum += m > 3 ? t3 : 0.0;
+  return sum;
+}
+
+template <bool Core>
+PFV_FN void sweep_row_nlc_t_rule(int32_t i, const int32_t* ip, const int32_t* ix, const double* valT, const double* diag,
+                                 const double* sink, const double* acc, const double* d, const double* phi,
+                                 const double* s, const int32_t* lev, const double* rl, double* lam, const NlCompT& C) {
+  const int k = C.k;
+  const int32_t li = lev[i];
+  const double ph = phi[i], di = d[i], ac = acc[i], o = diag[i] + (sink ? sink[i] : 0.0);
+  const double as = ac * s[i], op = o * ph;
+  const int64_t p = (int64_t)i * k;
+  const int e_begin = ip[i], e_end = ip[i + 1];
+  const double ri = rl[i];
+  int o1 = k > 1 ? 1 : 0, o2 = k > 2 ? 2 : 0, o3 = k > 3 ? 3 : 0;
+  const NlcTSums S0 = sweep_nlc_t_sums<Core, true>(i, li, e_begin, e_end, ix, valT, lev, k, 0, o1, o2, o3, C.mu, C.mu_prev,
+                                                   C.r + p, lam, C.lam_prev, rl + i);
+  double cpl = sweep_nlc_t_divide(C, p, o1, o2, o3, k, as, op, ph, o, ac, di, S0);
+  for (int a0 = 4; a0 < k; a0 += 4) {
+    const int m = k - a0;
+    o1 = m > 1 ? 1 : 0, o2 = m > 2 ? 2 : 0, o3 = m > 3 ? 3 : 0;
+    const NlcTSums S = sweep_nlc_t_sums<Core, false>(i, li, e_begin, e_end, ix, valT, lev, k, a0, o1, o2, o3, C.mu,
+                                                     C.mu_prev, C.r + p + a0, nullptr, nullptr, nullptr);
+    cpl += sweep_nlc_t_divide(C, p + a0, o1, o2, o3, m, as, op, ph, o, ac, di, S);
+  }
+  lam[i] = ((ri - cpl) - di * S0.sl) / (ac + di * o);
+}
+
+PFV_FN void sweep_row_nlc_t(int32_t i, const int32_t* ip, const int32_t* ix, const double* valT, const double* diag,
+                            const double* sink, const double* acc, const double* d, const double* phi, const double* s,
+                            const int32_t* lev, const double* rl, double* lam, const NlCompT& C) {
+  sweep_row_nlc_t_rule<false>(i, ip, ix, valT, diag, sink, acc, d, phi, s, lev, rl, lam, C);
+}
+
+// ... of the core level: C.mu_prev and C.lam_prev hold the previous iterate
+PFV_FN void sweep_row_nlc_t_core(int32_t i, const int32_t* ip, const int32_t* ix, const double* valT, const double* diag,
+                                 const double* sink, const double* acc, const double* d, const double* phi,
+                                 const double* s, const int32_t* lev, const double* rl, double* lam, const NlCompT& C) {
+  sweep_row_nlc_t_rule<true>(i, ip, ix, valT, diag, sink, acc, d, phi, s, lev, rl, lam, C);
+}
+
+// the launch plan's levels in [from, to), from last to first.  Returns the launches.
+static int sweep_apply_nlc_t(pfv_ctx_impl& c, const Sweep& sw, int from, int to, const CsrPattern& P, const double* valT,
+                             const double* diag, const double* sink, const double* acc, const double* d,
+                             const double* phi, const double* s, const double* rl, double* lam, const NlCompT& C) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* lev = sw.lev(false);
+  return sweep_plan_range(sw, from, to, [&](int l0, int l1) {
+    sweep_levels(c, sw, false, l0, l1, OnePerRow{}, PFV_LAMBDA(int32_t i, int) {
+      sweep_row_nlc_t(i, ip, ix, valT, diag, sink, acc, d, phi, s, lev, rl, lam, C);
+    }, Descending{});
+  }, Descending{});
+}
+
+// one Jacobi iteration of the core level on its transposed rows
+static void sweep_core_nlc_t(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* valT,
+                             const double* diag, const double* sink, const double* acc, const double* d,
+                             const double* phi, const double* s, const double* rl, double* lam, const NlCompT& C) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* lev = sw.lev(false);
+  sweep_core_rows(c, sw, OnePerRow{}, PFV_LAMBDA(int32_t i, int, int64_t) {
+    sweep_row_nlc_t_core(i, ip, ix, valT, diag, sink, acc, d, phi, s, lev, rl, lam, C);
+  });
+}
+
+// The streaming pass over the step's slab: phi = f(s^n), d = f'(s^n), and the dry rows -- a divisor acc_i s_i + ads_ia +
+// phi_i (A_ii + sink_i) of a component that is zero (the forward step keeps c there and does not determine it): the
+// lowest i k + a in *dry, by the integer atomic minimum of sweep_nl_check_inputs (preset to 0x7f7f7f7f).
+static void adjoint_nlc_slopes(pfv_ctx_impl& c, const FluxFn& F, int k, const double* s, const double* diag,
+                               const double* sink, const double* acc, const double* ads, double* d, double* phi,
+                               int32_t* dry) {
+  parallel_for(c.stream, c.nc, PFV_LAMBDA(int64_t i) {
+    double df;
+    const double ph = fluxfn_eval(F, s[i], &df);
+    phi[i] = ph;
+    d[i] = df;
+    const double as = acc[i] * s[i], op = (diag[i] + (sink ? sink[i] : 0.0)) * ph;
+    for (int a = 0; a < k; ++a)
+      if (as + (ads ? ads[i * k + a] : 0.0) + op == 0.0) atomic_min_i32(dry, (int32_t)(i * k + a));
+  });
+}
+
+// The right-hand sides of adjoint step n, rmu_a = c_loads_a^n + (acc o s^n + ads_a) o mu_a^{n+1} and rl = s_loads^n +
+// acc o lambda^{n+1}, fused with what the multipliers of step n + 1 add to the gradients that live on the cells:
+//     grad_source += lambda^{n+1},   grad_c_source_a += mu_a^{n+1},   grad_sorption_a -= mu_a^{n+1} o (c_a^{n+1} - c_a^n),
+//     grad_accumulation -= lambda^{n+1} o (s^{n+1} - s^n) + sum_a mu_a^{n+1} o (s^{n+1} o c_a^{n+1} - s^n o c_a^n).
+// Work item (row, a); a == k is the saturation's.  lam == nullptr (the first step): the loads alone.  closing (after the
+// last step, no loads, slab 0 in s_n / c_n): rmu_a = (acc o s^0 + ads_a) o mu_a^1 = grad_c0 and rl = acc o lambda^1 +
+// sum_a acc o c_a^0 o mu_a^1 = grad_s0.  s_loads is [n_obs], c_loads [k][n_obs] (either may be nullptr: zeros); slot as
+// in adjoint_step_rhs.  Interleaved vectors.
+static void adjoint_nlc_step_rhs(pfv_ctx_impl& c, int k, const double* acc, const double* ads, const double* s_n,
+                                 const double* c_n, const double* s_np1, const double* c_np1, const double* lam,
+                                 const double* mu, const int32_t* slot, const double* s_loads, const double* c_loads,
+                                 int64_t n_obs, bool closing, double* gsrc, double* gcsrc, double* gacc, double* gads,
+                                 double* rl, double* rmu) {
+  parallel_for(c.stream, c.nc * (k + 1), PFV_LAMBDA(int64_t w) {
+    const int64_t i = w / (k + 1);
+    const int a = (int)(w % (k + 1));
+    const int64_t m = (s_loads || c_loads) ? (slot ? (int64_t)slot[i] : i) : -1;
+    if (a < k) {
+      const int64_t t = i * k + a;
+      const double g = c_loads && m >= 0 ? c_loads[a * n_obs + m] : 0.0;
+      double v = g;
+      if (lam) {
+        const double x = mu[t];
+        v = g + (acc[i] * s_n[i] + (ads ? ads[t] : 0.0)) * x;
+        if (gcsrc) gcsrc[t] += x;
+        if (gads) gads[t] -= x * (c_np1[t] - c_n[t]);
+      }
+      rmu[t] = v;
+    } else {
+      const double g = s_loads && m >= 0 ? s_loads[m] : 0.0;
+      double v = g;
+      if (lam) {
+        const double l = lam[i];
+        v = g + acc[i] * l;
+        if (gsrc) gsrc[i] += l;
+        if (gacc || closing) {
+          const double s0 = s_n[i], s1 = s_np1[i];
+          double da = 0.0, cm = 0.0;
+          for (int b = 0; b < k; ++b) {
+            const int64_t t = i * k + b;
+            const double x = mu[t];
+            da += x * (s1 * c_np1[t] - s0 * c_n[t]);
+            cm += c_n[t] * x;
+          }
+          if (gacc) gacc[i] -= l * (s1 - s0) + da;
+          if (closing) v += acc[i] * cm;
+        }
+      }
+      rl[i] = v;
+    }
+  });
+}
+
+// (M^T mu_a)_i = sum_e valT[e] mu_aj + sink_i mu_ai in stored order; from >= 0: the entries of the levels from `from` on alone
+PFV_FN double sweep_nlc_t_row_image(int64_t i, int a, int k, const int32_t* ip, const int32_t* ix, const double* valT,
+                                    const double* sink, const double* mu, const int32_t* lev, int32_t from) {
+  double t = 0.0;
+  for (int e = ip[i]; e < ip[i + 1]; ++e) {
+    const int32_t j = ix[e];
+    if (from < 0 || lev[j] >= from) t += valT[e] * mu[(int64_t)j * k + a];
+  }
+  if (sink) t += sink[i] * mu[i * k + a];
+  return t;
+}
+
+// the coupling term of lambda's right-hand side from the image of mu: sum_a c_ai [acc_i (mu_ai - mu+_ai) + d_i (M^T mu_a)_i]
+PFV_FN double sweep_nlc_t_coupling(int64_t i, int k, const int32_t* ip, const int32_t* ix, const double* valT,
+                                   const double* sink, const double* acc, const double* d, const NlCompT& C,
+                                   const int32_t* lev, int32_t from) {
+  double cpl = 0.0;
+  for (int b = 0; b < k; ++b) {
+    const int64_t p = i * k + b;
+    const double img = sweep_nlc_t_row_image(i, b, k, ip, ix, valT, sink, C.mu, lev, from);
+    cpl += C.c[p] * (acc[i] * (C.mu[p] - C.mu_next[p]) + d[i] * img);
+  }
+  return cpl;
+}
+
+// The acceptance check, k + 1 pairs in one kernel: out[a] = (rmu_a, rmu_a) and out[k + 1 + a] the squared residual of
+// mu_a's system; out[k] and out[2 k + 1] the same for lambda, whose right-hand side rl - coupling is RECOMPUTED from the
+// image of the final mu (not taken from what the row used: a wrong coupling in the row shows as a residual).
+// core_only (the core's stop test): the residuals of the core rows alone, the images taken from the entries of the
+// row's own level and above; lambda's scale takes the coupling on the rows from the core level on (the levels below
+// have no mu yet) and rl alone below.
+static void sweep_norms_nlc_t(pfv_ctx_impl& c, const Sweep& sw, const CsrPattern& P, const double* valT,
+                              const double* sink, const double* acc, const double* d, const double* phi,
+                              const double* s, const double* rl, const double* lam, const NlCompT& C, bool core_only,
+                              double* out) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* lev = sw.lev(false);
+  const int32_t core = core_only ? sw.core_level : -1;
+  const int k = C.k;
+  sweep_norms_pairs(c, P.nrows, k + 1, out, PFV_LAMBDA(int64_t i, int a) {
+    const bool judged = core < 0 || lev[i] == core;
+    if (a < k) {
+      const int64_t p = i * k + a;
+      const double ri = C.r[p];
+      if (!judged) return NormPair{ri, 0.0};
+      const double img = sweep_nlc_t_row_image(i, a, k, ip, ix, valT, sink, C.mu, lev, core);
+      const double t = (acc[i] * s[i] + (C.ads ? C.ads[p] : 0.0)) * C.mu[p] + phi[i] * img;
+      return NormPair{ri, ri - t};
+    }
+    if (core >= 0 && lev[i] < core) return NormPair{rl[i], 0.0};
+    const double ri = rl[i] - sweep_nlc_t_coupling(i, k, ip, ix, valT, sink, acc, d, C, lev, core);
+    if (!judged) return NormPair{ri, 0.0};
+    const double t = acc[i] * lam[i] + d[i] * sweep_nl_t_row_image(i, ip, ix, valT, sink, lam, lev, core);
+    return NormPair{ri, ri - t};
+  });
+}
+
+// grad_sink[i] -= phi_i (lambda_i + sum_a mu_ai c_ai): the sink takes the phase at f(s) and the components with it
+static void adjoint_nlc_grad_sink(pfv_ctx_impl& c, int k, const double* lam, const double* mu, const double* c_n,
+                                  const double* phi, double* gsink) {
+  parallel_for(c.stream, c.nc, PFV_LAMBDA(int64_t i) {
+    double sum = 0.0;
+    for (int a = 0; a < k; ++a) sum += mu[i * k + a] * c_n[i * k + a];
+    gsink[i] -= (lam[i] + sum) * phi[i];
+  });
+}
+
+// lambda[p] - lambda[m] of face f (a missing cell contributes nothing); stride k, offset a for an interleaved vector
+PFV_FN double adjoint_face_jump(int64_t f, int64_t nf, const int32_t* side, const double* x, int k, int a) {
+  const int32_t cp = side[f], cm = side[nf + f];
+  double dx = 0.0;
+  if (cp >= 0) dx = x[(int64_t)cp * k + a];
+  if (cm >= 0) dx -= x[(int64_t)cm * k + a];
+  return dx;
+}
+
+// grad_bc_values[f] (the saturation's boundary value): a Neumann face as adjoint_nl_grad_bc, from lambda alone; a
+// Dirichlet inflow face  -= q_f f'(bc_f) [(lambda[p] - lambda[m]) + sum_a (mu_a[p] - mu_a[m]) cbc_af].  cbc is
+// component-major [k][nf].
+static void adjoint_nlc_grad_bc(pfv_ctx_impl& c, const FluxFn& F, int k, const double* d_q, const double* bc,
+                                const double* cbc, const double* lam, const double* mu, double* gbc) {
+  const int64_t nf = c.nf;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* cnt = c.upw_cnt;
+  const int32_t* side = c.upw_side;
+  parallel_for(c.stream, nf, PFV_LAMBDA(int64_t f) {
+    const unsigned cl = cls[f];
+    if (!(cl & (UPW_NEU | UPW_DIRIN))) return;
+    double m = 0.0, md = 0.0;
+    if (cl & UPW_NEU) m = (double)(cnt[f] - cnt[nf + f]);
+    if (cl & UPW_DIRIN) {
+      double df;
+      fluxfn_eval(F, bc[f], &df);
+      md = df * d_q[f];
+      m += md;
+    }
+    const int32_t cp = side[f], cm = side[nf + f];
+    double s = 0.0;
+    if (cp >= 0) s += m * lam[cp];
+    if (cm >= 0) s -= m * lam[cm];
+    if (cl & UPW_DIRIN) {
+      double dm = 0.0;
+      for (int a = 0; a < k; ++a) dm += adjoint_face_jump(f, nf, side, mu, k, a) * cbc[a * nf + f];
+      s += md * dm;
+    }
+    gbc[f] -= s;
+  });
+}
+
+// grad_c_bc_values[a][f] -= m_f (mu_a[p] - mu_a[m]), m_f the derivative of the entry of rhs_neu cbc_a + rhs_dir diag(q)
+// (f(bc) o cbc_a) in row f (upwind_bref_nlc) with respect to cbc_af: the Neumann count, q_f f(bc_f) on a Dirichlet inflow
+// face.  One work item per (face, component); gcbc is component-major [k][nf].
+static void adjoint_nlc_grad_cbc(pfv_ctx_impl& c, const FluxFn& F, int k, const double* d_q, const double* bc,
+                                 const double* mu, double* gcbc) {
+  const int64_t nf = c.nf;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* cnt = c.upw_cnt;
+  const int32_t* side = c.upw_side;
+  parallel_for(c.stream, nf * k, PFV_LAMBDA(int64_t t) {
+    const int64_t f = t / k, a = t % k;
+    const unsigned cl = cls[f];
+    if (!(cl & (UPW_NEU | UPW_DIRIN))) return;
+    double m = 0.0, df;
+    if (cl & UPW_NEU) m = (double)(cnt[f] - cnt[nf + f]);
+    if (cl & UPW_DIRIN) m += d_q[f] * fluxfn_eval(F, bc[f], &df);
+    const int32_t cp = side[f], cm = side[nf + f];
+    double s = 0.0;
+    if (cp >= 0) s += m * mu[(int64_t)cp * k + a];
+    if (cm >= 0) s -= m * mu[(int64_t)cm * k + a];
+    gcbc[a * nf + f] -= s;
+  });
+}
+
+// grad_flux[f] -= (lambda[p] - lambda[m]) phiup_f + sum_a (mu_a[p] - mu_a[m]) phiup_f cup_af: phiup as in
+// adjoint_nl_grad_flux, cup the concentration the phase carries through f -- the upstream cell's c^n (interior and
+// outflow faces), cbc on a Dirichlet inflow face; a Neumann face gives 0.  The upstream side is fixed.
+static void adjoint_nlc_grad_flux(pfv_ctx_impl& c, const FluxFn& F, int k, const double* bc, const double* cbc,
+                                  const double* lam, const double* mu, const double* phi, const double* c_n,
+                                  double* gq) {
+  const int64_t nf = c.nf;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* up = c.upw_up;
+  const int32_t* side = c.upw_side;
+  parallel_for(c.stream, nf, PFV_LAMBDA(int64_t f) {
+    const unsigned cl = cls[f];
+    if (!(cl & (UPW_KEPT | UPW_DIRIN))) return;
+    const int32_t u = up[f];
+    double df;
+    const double pu = (cl & UPW_KEPT) ? phi[u] : fluxfn_eval(F, bc[f], &df);
+    double s = adjoint_face_jump(f, nf, side, lam, 1, 0) * pu;
+    for (int a = 0; a < k; ++a) {
+      const double cup = (cl & UPW_KEPT) ? c_n[(int64_t)u * k + a] : cbc[a * nf + f];
+      s += adjoint_face_jump(f, nf, side, mu, k, a) * (pu * cup);
+    }
+    gq[f] -= s;
+  });
+}
+
+// The six Corey sums by the scheme of adjoint_nl_grad_fluxfn with the components' terms in both weights: cell i weighs
+// (M^T lambda)_i + sum_a c_ai (M^T mu_a)_i, the Dirichlet inflow face f  q_f [(lambda[p] - lambda[m]) + sum_a (mu_a[p] -
+// mu_a[m]) cbc_af].
+static void adjoint_nlc_grad_fluxfn(pfv_ctx_impl& c, const FluxFn& F, const CsrPattern& P, const double* valT,
+                                    const double* sink, int k, const double* d_q, const double* bc, const double* cbc,
+                                    const double* lam, const double* mu, const double* s_n, const double* c_n,
+                                    double* gF) {
+  const int64_t nf = c.nf;
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  const int32_t* side = c.upw_side;
+  adjoint_nl_grad_fluxfn_weighted(c, F, bc, s_n, gF, PFV_LAMBDA(int64_t t) {
+    double wt = sweep_nl_t_row_image(t, ip, ix, valT, sink, lam, nullptr, -1);
+    for (int a = 0; a < k; ++a)
+      wt += c_n[t * k + a] * sweep_nlc_t_row_image(t, a, k, ip, ix, valT, sink, mu, nullptr, -1);
+    return wt;
+  }, PFV_LAMBDA(int64_t f) {
+    double dl = adjoint_face_jump(f, nf, side, lam, 1, 0);
+    for (int a = 0; a < k; ++a) dl += adjoint_face_jump(f, nf, side, mu, k, a) * cbc[a * nf + f];
+    return dl * d_q[f];
   });
 }
 

@@ -577,6 +577,90 @@ class Upwind:
             raise
 
 
+    def adjoint_saturation_components(self, sd, data: dict, n_steps: int, accumulation, flux_function, s_states,
+                                      c_states, s_loads=None, c_loads=None, c_bc_values=None, sorption=None, sink=None,
+                                      obs_cells=None, want=("s0", "c0", "source", "c_source"), rtol: float = 1e-12,
+                                      maxit: int = 500, raise_on_fail: bool = True):
+        """The adjoint of ``advance_saturation_components``: the gradients of
+        ``J = sum_{n=1..N} [<s_loads[n-1], s^n[obs_cells]> + sum_a <c_loads[n-1, a], c_a^n[obs_cells]>]`` through
+        ``n_steps`` = N steps of the saturation with its k phase-carried components, for the cost of about one more
+        run -- what a match of tracer, salinity or polymer breakthrough curves needs: there the concentrations depend
+        on the saturation run and through it on the Corey parameters, porosity, well rates and the flux.  With the
+        multipliers ``lambda`` (saturation) and ``mu_a`` (component a), ``e_a = acc s^n + sorption_a``, per step,
+        backwards in time,
+        ``(diag(e_a) + diag(f(s^n)) M^T) mu_a^n = c_loads_a^n + e_a o mu_a^{n+1}`` and
+        ``(diag(acc) + diag(f'(s^n)) M^T) lambda^n = s_loads^n + acc o lambda^{n+1} - sum_a c_a^n o [acc o (mu_a^n -
+        mu_a^{n+1}) + f'(s^n) o (M^T mu_a^n)]`` are ONE fused transposed sweep in reverse flow order, k + 1 divisions per
+        cell; the levels and the launches are those of the forward sweep.
+
+        ``accumulation``, ``flux_function``, ``c_bc_values``, ``sorption`` and ``sink`` as in
+        ``advance_saturation_components`` (the sources do not enter; ``c_bc_values`` and ``sorption`` broadcast the same
+        way).  ``s_states``: (N + 1, Nc) and ``c_states``: (N + 1, k, Nc), the forward run's s^0 .. s^N and c^0 .. c^N --
+        both required, not checked for range or finiteness; k (1 .. 64) is taken from ``c_states``.  ``s_loads``:
+        (N, n_obs), ``c_loads``: (N, k, n_obs); at least one is given, a missing one is zeros.  ``obs_cells``: n_obs
+        cell indices without repeats, or None (every cell, in order).  ``want`` names the gradients:
+
+        - ``"s0"`` (Nc,): ``acc o lambda^1 + sum_a acc o c_a^0 o mu_a^1``; ``"c0"`` (k, Nc): ``(acc s^0 + sorption_a) o mu_a^1``;
+        - ``"source"`` (Nc,): ``sum_n lambda^n``; ``"c_source"`` (k, Nc): ``sum_n mu_a^n``;
+        - ``"accumulation"`` (Nc,): ``-sum_n [lambda^n o (s^n - s^{n-1}) + sum_a mu_a^n o (s^n c_a^n - s^{n-1} c_a^{n-1})]``;
+        - ``"sorption"`` (k, Nc): ``-sum_n mu_a^n o (c_a^n - c_a^{n-1})``; with ``sorption=None`` the derivative at zero;
+        - ``"sink"`` (Nc,): ``-sum_n f(s^n) o (lambda^n + sum_a mu_a^n o c_a^n)``;
+        - ``"bc_values"`` (Nf,): the saturation's boundary value -- a Neumann face as ``adjoint_saturation``, a Dirichlet
+          inflow face ``-sum_n q_f f'(bv_f) [(lambda_p - lambda_m) + sum_a (mu_ap - mu_am) cbv_af]``;
+        - ``"c_bc_values"`` (k, Nf): on a Neumann face the component flux's, on a Dirichlet inflow face
+          ``-sum_n (mu_ap - mu_am) q_f f(bv_f)``, zero on every other face;
+        - ``"flux"`` (Nf,): ``-sum_n [(lambda_p - lambda_m) f_up + sum_a (mu_ap - mu_am) f_up c_up,a]`` with the upstream
+          cell's ``f(s^n)`` and ``c_a^n`` (``f(bv_f)`` and ``cbv_af`` on a Dirichlet inflow face, zero on a Neumann face);
+        - ``"flux_function"`` (6,): a ``CoreyFractionalFlow`` only (``ValueError`` otherwise), ordered as
+          ``CoreyFractionalFlow.params``.
+
+        Every gradient is the derivative on a FIXED branch, as in ``adjoint_saturation``.  A dry row -- a cell and
+        component with ``acc s^n + sorption_a + f(s^n) (outflow + sink) = 0``, where the forward step keeps ``c`` and
+        does not determine it -- raises ``ValueError`` naming the step, the cell and the component; cells on a flat part
+        of the curve (``f' = 0``) are fine.
+
+        The cells of a cyclic core iterate ``mu`` and ``lambda`` jointly by Jacobi on their transposed rows, at most
+        ``maxit`` times per step.  Returns (grads, info): info["steps_done"], "converged", "iterations" (1, or the core
+        iterations of the last step), "rel_residual" (the saturation's) and "c_rel_residual" (per component).  A refused
+        step leaves the gradients zero.  Afterwards the handle holds no assembled transport system; the flow order
+        stays."""
+        pd = data[PARAMETERS][self.keyword]
+        kind, params = _flux_function(flux_function)
+        if accumulation is None:
+            raise ValueError("accumulation is required")
+        if s_states is None or c_states is None:
+            raise ValueError("s_states (s^0 .. s^N) and c_states (c^0 .. c^N) are required: the step is linearised "
+                             "about them")
+        nc, nf = sd.num_cells, sd.num_faces
+        c_states = np.asarray(c_states, dtype=np.float64)
+        if c_states.ndim != 3 or c_states.shape[0] != int(n_steps) + 1 or c_states.shape[2] != nc:
+            raise ValueError(f"c_states must have shape ({int(n_steps) + 1}, k, {nc}), not {c_states.shape}")
+        k = c_states.shape[1]
+        if not 1 <= k <= 64:
+            raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (c_states has shape "
+                             f"{c_states.shape})")
+
+        def per_component(name, a, n):
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape == (n,):
+                return np.broadcast_to(a, (k, n))
+            if a.shape != (k, n):
+                raise ValueError(f"{name} must have shape ({n},) or ({k}, {n}), not {a.shape}")
+            return a
+
+        cbv = np.zeros((k, nf)) if c_bc_values is None else per_component("c_bc_values", c_bc_values, nf)
+        ads = None if sorption is None else per_component("sorption", sorption, nc)
+        try:
+            return self.context(sd).transport_adjoint_nl_multi(
+                n_steps, accumulation, np.asarray(pd["bc_values"], dtype=float), cbv, kind, params, s_states, c_states,
+                s_loads=s_loads, c_loads=c_loads, sorption=ads, sink=sink, obs_cells=obs_cells, q=self._flux(sd, pd),
+                want=want, rtol=rtol, maxit=maxit, raise_on_fail=raise_on_fail)
+        except _lib.PorefvError as e:
+            if e.status == 4:
+                raise ValueError(e.message) from None
+            raise
+
+
 def _flux_function(flux_function):
     """(kind, parameters) of the C ABI for what ``advance_saturation`` takes as ``flux_function``"""
     if isinstance(flux_function, str) and flux_function == "linear":

@@ -52,6 +52,13 @@ pfv_stats (best and median of --reps, the first repeat dropped), levels and laun
 (transport_adjoint_nl) on 16 observation cells with the three gradients whose formulas need no states (s0, source,
 bc_values) and the adjoint with all seven; the states are those of the forward run, taken one step at a time.  ms per
 step of the three from pfv_stats (best and median of --reps, the first repeat dropped), levels and launches.
+
+--saturation --adjoint --components K (a list runs several K; the JSON gains the key "satcomp_adjoint"): after the
+block above and by its protocol, on the same flux, curve and sink, alternating in one loop: the forward Corey step with K
+phase-carried components (transport_advance_nl_multi: own inflow concentrations, sorption on component 0), its adjoint
+(transport_adjoint_nl_multi) on the same 16 observation cells with loads of both kinds and the four default gradients
+(s0, c0, source, c_source), and the adjoint with all eleven.  ms per step of the three from pfv_stats (best, median and
+worst of --reps, the first repeat dropped), levels and launches of both directions.
 """
 from __future__ import annotations
 
@@ -286,6 +293,54 @@ def main():
             entry["error"] = e.message
         out["saturation_adjoint"] = entry
         ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the calls leave no system behind)
+        for kc in [int(v) for v in a.components.split(",") if v]:
+            # the same flux, curve, sink and protocol with kc phase-carried components: the forward step of
+            # --saturation --components (transport_advance_nl_multi) against its adjoint, alternating
+            cbv_k = np.array([tbv * (j + 1) / kc for j in range(kc)])
+            ads_k = np.zeros((kc, nc))
+            ads_k[0] = 0.3 * acc
+            s_st, c_st = np.empty((a.steps + 1, nc)), np.empty((a.steps + 1, kc, nc))
+            s_st[0], c_st[0] = states[0], 0.2 + rng.random((kc, nc))
+            s_loads, c_loads = rng.standard_normal((a.steps, n_obs)), rng.standard_normal((a.steps, kc, n_obs))
+            fw = dict(sorption=ads_k, sink=sink, rtol=1e-10)
+            entry = {"k": kc, "observation_cells": n_obs}
+            try:
+                for s_ in range(a.steps):  # the states of the forward run, one step at a time
+                    s_st[s_ + 1], c_st[s_ + 1], cinfo = ctx.transport_advance_nl_multi(
+                        s_st[s_], c_st[s_], 1, acc, tbv, cbv_k, corey.kind, corey.params, **fw)
+                aj = dict(s_loads=s_loads, c_loads=c_loads, sorption=ads_k, sink=sink, obs_cells=obs, rtol=1e-10,
+                          raise_on_fail=False)
+                fwd_ms, adj4_ms, adj11_ms = [], [], []
+                for _ in range(a.reps + 1):  # (the first repeat warms up: dropped)
+                    sc, cc, cinfo = ctx.transport_advance_nl_multi(s_st[0], c_st[0], a.steps, acc, tbv, cbv_k, corey.kind,
+                                                                   corey.params, raise_on_fail=False, **fw)
+                    fwd = ctx.stats()
+                    fwd_ms.append(fwd["transport_nl_ms"] / max(a.steps, 1))
+                    g4, i4 = ctx.transport_adjoint_nl_multi(a.steps, acc, tbv, cbv_k, corey.kind, corey.params, s_st, c_st,
+                                                            **aj)
+                    adj4_ms.append(ctx.stats()["transport_nlc_adjoint_ms"] / max(a.steps, 1))
+                    g11, i11 = ctx.transport_adjoint_nl_multi(a.steps, acc, tbv, cbv_k, corey.kind, corey.params, s_st,
+                                                              c_st, want=ctx.NLC_ADJOINT_GRADIENTS, **aj)
+                    adj = ctx.stats()
+                    adj11_ms.append(adj["transport_nlc_adjoint_ms"] / max(a.steps, 1))
+                entry.update({
+                    "steps_done": i11["steps_done"], "forward_steps_done": cinfo["steps_done"],
+                    "forward_ms_per_step": (min(fwd_ms[1:]), float(np.median(fwd_ms[1:])), max(fwd_ms[1:])),
+                    "adjoint_ms_per_step_s0_c0_source_c_source": (min(adj4_ms[1:]), float(np.median(adj4_ms[1:])),
+                                                                  max(adj4_ms[1:])),
+                    "adjoint_ms_per_step_all_eleven": (min(adj11_ms[1:]), float(np.median(adj11_ms[1:])), max(adj11_ms[1:])),
+                    "levels": adj["sweep_levels"], "core_cells": adj["sweep_core_cells"],
+                    "forward_launches_per_sweep": fwd["sweep_launches"], "adjoint_launches_per_sweep": adj["sweep_launches"],
+                    "core_iterations": adj["transport_nlc_adjoint_core_iterations"],
+                    "rel_residual_last_step": i11["rel_residual"],
+                    "max_c_rel_residual_last_step": max(i11["c_rel_residual"]),
+                    "forward_rel_residual_last_step": cinfo["rel_residual"],
+                    "grad_flux_function": g11["flux_function"].tolist(),
+                    "c0_bits_equal_between_the_two_adjoint_calls": bool(g4["c0"].tobytes() == g11["c0"].tobytes())})
+            except pa.PorefvError as e:
+                entry["error"] = e.message
+            out.setdefault("satcomp_adjoint", []).append(entry)
+            ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the calls leave no system behind)
     if a.reactive and a.adjoint:
         kc, n_obs = 4, 16
         acc_k = np.array([(1.0 + 0.5 * j) * acc for j in range(kc)])

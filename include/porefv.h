@@ -486,10 +486,13 @@ pfv_status pfv_amg_level(pfv_ctx* h, int level, int64_t* info, double* params, i
  * models/constitutive_laws.py:987-1000): the unknowns of the system given to pfv_set_system are grouped in
  * n_blocks contiguous blocks [block_ptr[k], block_ptr[k+1]) -- one per (variable, subdomain or interface) -- and
  * the preconditioner is the block lower-triangular part of A, every diagonal block solved by one cycle of its own
- * aggregation-AMG hierarchy (blocks of at most 1024 rows: exactly, by their dense inverse).  gauss_seidel = 0: block
- * Jacobi.  Every diagonal entry must be non-zero: systems whose equations are ordered differently from their
- * unknowns are row-permuted first (host side: porepy_amd.solvers.match_rows).  Selects PFV_PRECOND_BLOCK; the
- * blocks are (re)built by the next pfv_solve. */
+ * aggregation-AMG hierarchy (blocks of at most 1024 rows: exactly, by the dense inverse of the block as given -- the
+ * strength filter of the hierarchies, PFV_AMG_FILTER_PERMIL, does not touch them).  gauss_seidel = 0: block
+ * Jacobi.  The coupling term of block k sums every stored entry of its rows whose column lies left of the block,
+ * whatever the order of the columns inside a row (as pfv_set_system accepts them); rows stored with ascending columns
+ * give the same sums, entry for entry in the same order.  Every diagonal entry must be non-zero: systems whose
+ * equations are ordered differently from their unknowns are row-permuted first (host side:
+ * porepy_amd.solvers.match_rows).  Selects PFV_PRECOND_BLOCK; the blocks are (re)built by the next pfv_solve. */
 pfv_status pfv_set_block_preconditioner(pfv_ctx* h, int64_t n_blocks, const int64_t* block_ptr, int gauss_seidel);
 
 /* Jacobi-preconditioned Krylov solve of A x = b on the device (stand-in for

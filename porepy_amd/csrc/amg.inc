@@ -2332,6 +2332,7 @@ struct BlockPc {
     CsrPattern P;
     Buf<double> val, diag;
     std::unique_ptr<Amg> amg;
+    bool ascending = false;  // every row of the block stores its columns in ascending order (blockpc_extract)
   };
   std::vector<int64_t> ptr;   // block boundaries as given by the caller
   std::vector<std::unique_ptr<Blk>> blk;
@@ -2367,13 +2368,17 @@ static void blockpc_extract(pfv_ctx_impl& c, const CsrPattern& P, const double* 
   double* bv = B.val.ensure(std::max<int64_t>(nnz, 1));
   double* bd = B.diag.ensure(n);
   int32_t* st = c.status.ensure(16);
-  be_memset(st + 11, 0, sizeof(int32_t), s);
+  be_memset(st + 11, 0, 2 * sizeof(int32_t), s);
   parallel_for(s, n + 1, PFV_LAMBDA(int64_t r) { bip[r] = (int32_t)ps[r]; });
   parallel_for(s, n, PFV_LAMBDA(int64_t r) {
     int64_t o = ps[r];
     double d = 0.0;
+    int prev = -1;
+    bool descends = false;
     for (int e = ip[p0 + r]; e < ip[p0 + r + 1]; ++e) {
       const int cc = ix[e];
+      descends = descends || cc < prev;
+      prev = cc;
       if (cc >= p0 && cc < p1) {
         bix[o] = (int32_t)(cc - p0);
         bv[o] = val[e];
@@ -2383,8 +2388,12 @@ static void blockpc_extract(pfv_ctx_impl& c, const CsrPattern& P, const double* 
     }
     bd[r] = d;
     if (!(d != 0.0)) atomic_max_i32(st + 11, 1);
+    if (descends) atomic_max_i32(st + 12, 1);
   });
-  if (read_scalar<int32_t>(s, st + 11))
+  int32_t hst[2];
+  be_d2h(hst, st + 11, sizeof(hst), s);
+  B.ascending = hst[1] == 0;
+  if (hst[0])
     throw Error(PFV_ERR_ARGUMENT, "block preconditioner: a diagonal entry is zero (permute the rows first: "
                                   "porepy_amd.solvers.match_rows)");
   B.P.max_row = 0;
@@ -2404,6 +2413,9 @@ static void blockpc_setup(pfv_ctx_impl& c, BlockPc& M, const CsrPattern& P, cons
     if (!B.amg) B.amg = std::make_unique<Amg>();
     B.amg->valid = false;
     B.amg->coarse_target = kAmgDenseMax;  // blocks up to kAmgDenseMax rows: exact
+    // ... so their one level is the block itself, not its strength-filtered copy (whose inverse is not the block's;
+    // the filter pays on the levels of a cycle, and these blocks have none)
+    B.amg->no_filter = B.p1 - B.p0 <= kAmgDenseMax;
     amg_setup(c, *B.amg, B.P, B.val, 1, B.diag, nullptr);
   }
   M.for_val = val;
@@ -2421,12 +2433,17 @@ static void blockpc_apply(pfv_ctx_impl& c, BlockPc& M, const CsrPattern& P, cons
     const int64_t p0 = B.p0, nk = B.p1 - B.p0;
     const double* rhs = in + p0;
     if (M.gs && k > 0) {
-      // t_k = r_k - sum_{j < k} A_kj z_j: the entries of the block's rows left of the block (columns ascending)
+      // t_k = r_k - sum_{j < k} A_kj z_j: every entry of the block's rows left of the block, in storage order (rows with
+      // ascending columns stop at the first entry that is not; pfv_set_system does not ask for sorted rows)
+      const bool ascending = B.ascending;
       parallel_for(s, nk, PFV_LAMBDA(int64_t r) {
         double sum = 0.0;
         for (int e = ip[p0 + r]; e < ip[p0 + r + 1]; ++e) {
           const int cc = ix[e];
-          if (cc >= p0) break;
+          if (cc >= p0) {
+            if (ascending) break;
+            continue;
+          }
           sum += val[e] * out[cc];
         }
         t[p0 + r] = in[p0 + r] - sum;

@@ -576,10 +576,11 @@ def spd_from(pattern, seed):
     return shuffle_rows(S, rng)
 
 
-def big_spd():
+def big_spd(n=None):
     """n = 64 * 2049 + 5 rows of 3 entries (periodic second difference plus a random positive shift): 2050 row blocks
-    for the windowed product and 4099 row groups for k_spmv_dot, more than kRedBlocks partial sums either way"""
-    n = WIN_ROWS * (RED_BLOCKS + 1) + 5
+    for the windowed product and 4099 row groups for k_spmv_dot, more than kRedBlocks partial sums either way.  (Another
+    `n`: the same generator at that size, for tests/_krylov_cases.py.)"""
+    n = WIN_ROWS * (RED_BLOCKS + 1) + 5 if n is None else n
     rng = np.random.default_rng(600)
     w = rng.uniform(0.5, 1.5, n)  # coupling of i and i + 1 (mod n)
     i = np.arange(n)

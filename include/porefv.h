@@ -221,6 +221,13 @@ typedef struct {
   double transport_nlc_adjoint_ms; /* last pfv_transport_adjoint_nl_multi, all steps (HIP events) */
   int64_t transport_nlc_adjoint_steps; /* ... accepted adjoint steps */
   int64_t transport_nlc_adjoint_core_iterations; /* ... Jacobi iterations of the cyclic core, summed over the steps */
+  int64_t flow_adjoint_calls;      /* pfv_flow_adjoint calls on this handle that reached their solve */
+  int64_t flow_adjoint_iterations; /* Krylov iterations of the last one */
+  int64_t flow_adjoint_map_builds; /* times the column maps of flux / bound_flux were built (kept with the patterns) */
+  double flow_adjoint_map_ms;      /* last pfv_flow_adjoint: column maps and transposed positions (0: kept) */
+  double flow_adjoint_products_ms; /* ... the two transposed products T^T g_q and B^T z */
+  double flow_adjoint_solve_ms;    /* ... the transposed solve, preconditioner set-up included */
+  double flow_adjoint_gradient_ms; /* ... the face kernel and the cell kernel of grad_perm */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -937,6 +944,45 @@ pfv_status pfv_transport_adjoint_nl_multi(pfv_ctx* h, const double* q, int fluxf
                                           double* grad_sink, double* grad_bc_values, double* grad_c_bc_values,
                                           double* grad_flux, double* grad_fluxfn, int32_t* steps_done,
                                           pfv_solve_info* last);
+
+/* ---- Adjoint of the flow solve (csrc/flow_adjoint.inc): where the grad_flux of the transport adjoints goes on ------
+ * The linear flow problem of the discretization on the handle, div = cell_faces^T:
+ *     q = T p + B bc (+ V g),      A p = source - div (B bc + V g),      A = div T
+ * (T, B, V = PFV_MAT_FLUX, PFV_MAT_BOUND_FLUX, PFV_MAT_VECTOR_SOURCE).  For an objective J with g_q = dJ/dq = load_flux
+ * (Nf) and g_p = dJ/dp = load_pressure (Nc) at the forward solution -- at least one of the two, else PFV_ERR_ARGUMENT --
+ *     A^T mu = g_p + T^T g_q                       one transposed solve
+ *     z_f    = g_q[f] - sum_{e of f} sgn_e mu_c(e)
+ *     grad_source [Nc]          mu
+ *     grad_bc_values [Nf]       B^T z                                           (zero off the boundary)
+ *     grad_perm [(3,3,Nc)]      sum_{e=(c,f)} z_f w_f t_f^2 sgn_e d_r n_s / (t_e^2 |d|^2), layout of perm_33n, all nine
+ *                               entries independent (the derivative of pfv_tpfa_transmissibility_ad)
+ * w_f = d q_f / d t_f = filter_f (p_diff_f + g_diff_f) - dir_f sgn_f bc_f as pfv_mpfa_ad_flux_system defines it (filter 0
+ * on Neumann faces).  What grad_perm means depends on the discretization.  pfv_tpfa_discretize: the exact gradient of
+ * the discrete problem.  pfv_mpfa_discretize: grad_source, grad_bc_values and mu are exact; grad_perm is the two-point
+ * product rule of the reference's AdTpfaFlux -- the same approximation pfv_mpfa_ad_flux_system makes for its Jacobian
+ * --, NOT the derivative of the MPFA matrices.  The gradient with respect to the vector source is not formed.
+ *   p (Nc) is the forward solution: the caller's responsibility, not checked against the system.  bc_values (Nf) and
+ * vector_source (per cell as pfv_mpfa_assemble takes it, or NULL) as in the forward solve.  mu_out (Nc), grad_perm,
+ * grad_bc_values and grad_source may each be NULL.  All vectors follow pfv_set_vectors_on_device: a grad_flux left in
+ * device memory by a transport adjoint is consumed without a host visit.
+ *   The solve: A = div T is assembled afresh (an earlier pfv_mpfa_ad_flux_system may have left J in its value array), its
+ * transposed values are taken on its own pattern through transposed positions (the pattern of div T is structurally
+ * symmetric; a missing partner is PFV_ERR_UNSUPPORTED), and (A^T, g_p + T^T g_q) becomes the active system of one
+ * pfv_solve with the preconditioner selected on the handle; method, rtol, maxit, restart as in pfv_solve, info receives
+ * its info.  A solve that does not converge returns PFV_ERR_NOT_CONVERGED and writes no output.  T^T and B^T are
+ * gathers over column maps of the two patterns (entries sorted by (column, row)), built on first use and kept with
+ * the patterns; no floating-point atomics, two calls give the same bits.
+ *   After the call the handle holds NO active system (pfv_solve asks for an assembly, as after the transport calls);
+ * the discretization, the resident face flux, the upwind discretization and the flow order are untouched.
+ *   PFV_ERR_ARGUMENT: no flow discretization with per-face conditions on the handle; no load; a non-finite value in a
+ * load, in p or in bc_values on a boundary face (the text names the lowest index).  PFV_ERR_UNSUPPORTED (the text names
+ * the first offending face where there is one): Robin faces, faces flagged PFV_BC_INTERNAL, periodic grids, conditions
+ * per sub-face, partial discretizations with zeroed rows, the sharded solve, a flux pattern of 2^31 entries or more.
+ * pfv_stats: flow_adjoint_*. */
+pfv_status pfv_flow_adjoint(pfv_ctx* h, const double* p, const double* bc_values, const double* vector_source,
+                            const double* load_flux, const double* load_pressure, int method, double rtol, int maxit,
+                            int restart, double* mu_out, double* grad_perm, double* grad_bc_values,
+                            double* grad_source, pfv_solve_info* info);
 
 /* ---- Advection-diffusion step on the device (csrc/advdiff.inc) ---------------------------------------------------
  * One handle carries the transport keyword: its diffusion discretization (pfv_mpfa_discretize or pfv_tpfa_discretize

@@ -52,7 +52,7 @@ EXPORTS = [
     "pfv_advdiff_assemble", "pfv_advdiff_advance", "pfv_advdiff_face_flux", "pfv_resident_flux",
     "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl", "pfv_transport_advance_nl_multi",
     "pfv_transport_advance_react", "pfv_transport_adjoint_multi", "pfv_transport_adjoint_react",
-    "pfv_transport_adjoint_nl", "pfv_transport_adjoint_nl_multi",
+    "pfv_transport_adjoint_nl", "pfv_transport_adjoint_nl_multi", "pfv_flow_adjoint",
 ]
 
 
@@ -98,7 +98,11 @@ class Stats(C.Structure):
                 ("transport_nl_adjoint_ms", C.c_double), ("transport_nl_adjoint_steps", C.c_int64),
                 ("transport_nl_adjoint_core_iterations", C.c_int64),
                 ("transport_nlc_adjoint_ms", C.c_double), ("transport_nlc_adjoint_steps", C.c_int64),
-                ("transport_nlc_adjoint_core_iterations", C.c_int64)]
+                ("transport_nlc_adjoint_core_iterations", C.c_int64),
+                ("flow_adjoint_calls", C.c_int64), ("flow_adjoint_iterations", C.c_int64),
+                ("flow_adjoint_map_builds", C.c_int64), ("flow_adjoint_map_ms", C.c_double),
+                ("flow_adjoint_products_ms", C.c_double), ("flow_adjoint_solve_ms", C.c_double),
+                ("flow_adjoint_gradient_ms", C.c_double)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -343,6 +347,9 @@ def _bind(lib: C.CDLL) -> C.CDLL:
                                                    _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                                    C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
     lib.pfv_transport_adjoint_nl_multi.restype = C.c_int
+    lib.pfv_flow_adjoint.argtypes = [_h, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp,
+                                     _dp, C.POINTER(SolveInfo)]
+    lib.pfv_flow_adjoint.restype = C.c_int
     lib.pfv_advdiff_assemble.argtypes = [_h, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pfv_advdiff_assemble.restype = C.c_int
     lib.pfv_advdiff_advance.argtypes = [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(C.c_int32),
@@ -1899,6 +1906,59 @@ class Context:
         out = {"steps_done": done.value, "iterations": infos[0].iterations,
                "converged": all(bool(i.converged) for i in infos), "rel_residual": infos[0].rel_residual,
                "c_rel_residual": [i.rel_residual for i in infos[1:]], "solve_ms": infos[0].solve_ms}
+        if st != 0 and (raise_on_fail or st != 6):
+            try:
+                self._check(st)
+            except PorefvError as e:
+                e.info = out
+                raise
+        return grads, out
+
+    # ---- the adjoint of the flow solve (include/porefv.h: pfv_flow_adjoint) ----
+    FLOW_ADJOINT_GRADIENTS = ("permeability", "bc_values", "source", "multiplier")
+
+    def flow_adjoint(self, p, bc_values, vector_source=None, load_flux=None, load_pressure=None,
+                     want=("permeability", "bc_values", "source"), method="bicgstab", rtol=1e-12, maxit=20000, restart=0,
+                     precond="amg", raise_on_fail=True, device=False, out_ptrs=None):
+        """The adjoint of the flow solve of the discretization on this handle (pfv_flow_adjoint): ``load_flux`` = dJ/dq
+        (Nf) and ``load_pressure`` = dJ/dp (Nc), at least one of them, become the gradients named in ``want`` --
+        "permeability" (3, 3, Nc), "bc_values" (Nf), "source" (Nc) and "multiplier" (Nc, the solution of the transposed
+        system) -- at the cost of one transposed solve.  ``p`` is the forward solution, ``bc_values`` / ``vector_source``
+        as in ``assemble``.  For a TPFA discretization the permeability gradient is exact; for MPFA it is the two-point
+        product rule of ``ad_flux_system``, not the derivative of the MPFA matrices.  Returns (grads, info).  A solve that
+        does not converge leaves the gradients zero.  ``device``: every vector argument is the address of a device
+        buffer and the wanted outputs go to the addresses in ``out_ptrs`` (name -> address); grads is then empty."""
+        code = {"cg": SOLVE_CG, "bicgstab": SOLVE_BICGSTAB, "gmres": SOLVE_GMRES}[method]
+        want = tuple(want)
+        for name in want:
+            if name not in self.FLOW_ADJOINT_GRADIENTS:
+                raise ValueError(f"want: unknown gradient {name!r} (known: {', '.join(self.FLOW_ADJOINT_GRADIENTS)})")
+        nvs = None if vector_source is None or device else self.matrix_info(MAT_VECTOR_SOURCE)[1]
+        k1, pp_ = self._vec(p, self.nc, "p", device)
+        k2, pb = self._vec(bc_values, self.nf, "bc_values", device)
+        k3, pv = self._vec(vector_source, nvs, "vector_source", device)
+        k4, pq = self._vec(load_flux, self.nf, "load_flux", device)
+        k5, pl = self._vec(load_pressure, self.nc, "load_pressure", device)
+        shapes = {"permeability": (3, 3, self.nc), "bc_values": (self.nf,), "source": (self.nc,), "multiplier": (self.nc,)}
+        if device:
+            grads = {}
+            outs = {name: C.cast(int((out_ptrs or {})[name]), _dp) for name in want}
+        else:
+            grads = {name: np.zeros(shapes[name]) for name in self.FLOW_ADJOINT_GRADIENTS if name in want}
+            outs = {name: _ptr(a, _dp) for name, a in grads.items()}
+        self._select_precond(precond)
+        info = SolveInfo()
+        if device:
+            self._dev(True)
+        try:
+            st = self.lib.pfv_flow_adjoint(self._h, pp_, pb, pv, pq, pl, code, float(rtol), int(maxit), int(restart),
+                                           outs.get("multiplier"), outs.get("permeability"), outs.get("bc_values"),
+                                           outs.get("source"), C.byref(info))
+        finally:
+            if device:
+                self._dev(False)
+        out = {"iterations": info.iterations, "converged": bool(info.converged),
+               "rel_residual": info.rel_residual, "solve_ms": info.solve_ms}
         if st != 0 and (raise_on_fail or st != 6):
             try:
                 self._check(st)

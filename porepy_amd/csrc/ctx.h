@@ -67,6 +67,15 @@ struct WinCsr {
   bool ok = false;   // false: not built / some block exceeds the LDS budget -> plain CSR kernels
 };
 
+// Column map of a CSR pattern (flow_adjoint.inc): its entries sorted by (column, row) -- what a transposed product
+// gathers over.  A property of the pattern, kept beside it.
+struct ColMap {
+  Buf<int32_t> colptr;  // [ncols + 1]
+  Buf<int32_t> pos;     // [nnz] position of the entry in the CSR value array
+  Buf<int32_t> row;     // [nnz] its row
+  int64_t ncols = 0, nnz = 0;
+};
+
 // a square system the Krylov solver can work on (flow: A = div flux; mechanics: A = div_nd stress)
 struct LinSys {
   const CsrPattern* P = nullptr;
@@ -372,6 +381,18 @@ struct pfv_ctx_impl {
   // Interleaved: the two slabs c^n / c^{n+1}, mu^n / mu^{n+1}, the core's previous iterate, mu's right-hand side; the
   // accumulators of grad_c_source and grad_sorption (interleaved) and of grad_c_bc_values (component-major [k][nf])
   Buf<double> aj_sloads, aj_cA, aj_cB, aj_mu, aj_mu2, aj_muprev, aj_rmu, aj_gcsrc, aj_gads, aj_gcbc;
+
+  // ---- the adjoint of the flow solve (pfv_flow_adjoint, flow_adjoint.inc) ---------------------------------------------
+  // cmap_flux / cmap_bound: column maps of pat_flux / pat_bound, valid while have_cmap (dropped wherever those patterns
+  // are rebuilt: pfv_set_grid, the symbolic phase, pfv_tpfa_discretize); tpos_A: transposed positions of pat_A, valid
+  // while have_tpos_A (same rule).  fa_valT / fa_rhs: the values of A^T on pat_A and g_p + T^T g_q -- the active
+  // system while the call's solve runs; fa_in: the call's vectors as they came (p | bc | load_flux | load_pressure |
+  // vector_source); fa_mu: the multiplier
+  bool have_cmap = false, have_tpos_A = false;
+  ColMap cmap_flux, cmap_bound;
+  Buf<int32_t> tpos_A;
+  Buf<int32_t> fa_half;  // the call's half-face lists: first [nf] | last [nf] | cell of every cell_faces entry [ncf]
+  Buf<double> fa_valT, fa_rhs, fa_in, fa_mu;
 
   // ---- advection-diffusion (advdiff.inc): S = diag(acc) + div flux_D + w div diag(q) U on pat_A -------------------
   bool have_advdiff = false;         // val[PFV_MAT_ADVDIFF_SYSTEM], adv_diag, adv_rhs hold a system of the discretization

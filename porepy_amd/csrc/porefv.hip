@@ -24,6 +24,7 @@ static int rccl_exchange_halo(void* user, double* d_x, void* stream);  // rccl_h
 #include "upwind.inc"
 #include "advdiff.inc"
 #include "sweep.inc"
+#include "flow_adjoint.inc"
 
 namespace pfv {
 #ifndef PFV_EMULATE
@@ -347,6 +348,7 @@ pfv_status pfv_set_grid(pfv_ctx* h, int nd, int64_t nc, int64_t nf, int64_t nn, 
     for (bool& f : h->filled) f = false;
     h->have_q_res = h->have_upw_bc = h->have_upwind = h->have_transport = h->have_pat_T = h->have_upw_cells = false;
     h->have_tpos_T = false;
+    h->have_cmap = h->have_tpos_A = false;
     h->have_acc_t = h->have_src_t = false;
     h->transport_zero_diag = -1;
     h->have_advdiff = h->have_adv_bD = h->have_adv_acc = h->have_adv_src = false;
@@ -4002,6 +4004,161 @@ pfv_status pfv_solve(pfv_ctx* h, int method, double rtol, int maxit, int restart
     return PFV_ERR_NOT_CONVERGED;
   }
   return st;
+}
+
+// ---- the adjoint of the flow solve (flow_adjoint.inc).  Three parts: the checks, the maps, A^T and the right-hand side,
+// ending with (A^T, g_p + T^T g_q) as the active system; pfv_solve itself; the gradients from mu.
+pfv_status pfv_flow_adjoint(pfv_ctx* h, const double* p, const double* bc_values, const double* vector_source,
+                            const double* load_flux, const double* load_pressure, int method, double rtol, int maxit,
+                            int restart, double* mu_out, double* grad_perm, double* grad_bc_values,
+                            double* grad_source, pfv_solve_info* info) {
+  if (info) *info = pfv_solve_info{};
+  const int none = 0x7f7f7f7f;
+  double *d_p = nullptr, *d_bc = nullptr, *d_gq = nullptr, *d_gp = nullptr, *d_vs = nullptr, *d_mu = nullptr;
+  int32_t *first = nullptr, *last = nullptr, *ecell = nullptr;
+  int vd = 0;
+  double products_ms = 0.0;
+  pfv_status st = guarded(h, [&] {
+    require(h->have_grid && h->have_numeric && h->filled[PFV_MAT_FLUX] && h->filled[PFV_MAT_BOUND_FLUX],
+            "no flow discretization on the handle: pfv_mpfa_discretize or pfv_tpfa_discretize first");
+    require(p && bc_values, "p and bc_values are required");
+    require(load_flux || load_pressure, "no loads: give load_flux, load_pressure or both");
+    require(method == PFV_SOLVE_CG || method == PFV_SOLVE_BICGSTAB || method == PFV_SOLVE_GMRES,
+            "method must be PFV_SOLVE_CG, PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES");
+    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
+    if (h->shard) throw pfv::Error(PFV_ERR_UNSUPPORTED, "the flow adjoint has no sharded form");
+    if (h->periodic) throw pfv::Error(PFV_ERR_UNSUPPORTED, "the flow adjoint does not cover periodic grids");
+    if (h->subface_bc)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "the flow adjoint does not cover conditions per sub-face (flux has sub-face rows)");
+    if (!h->tpfa_mode && !h->rows_complete)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "the flow adjoint does not cover a partial discretization (the rows of the "
+                                            "other faces are zero)");
+    if (h->pat_flux.nnz >= (int64_t(1) << 31))
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "the flow adjoint needs a flux pattern below 2^31 entries");
+    require(!vector_source || h->filled[PFV_MAT_VECTOR_SOURCE], "vector_source matrix was skipped");
+    auto s = h->stream;
+    const size_t nf = (size_t)h->nf, nc = (size_t)h->nc, ncf = (size_t)h->ncf;
+    vd = (int)(h->pat_vs.ncols / h->nc);
+    const size_t nvs = vector_source ? (size_t)vd * nc : 0;
+    double* in = h->fa_in.ensure(2 * nc + 2 * nf + nvs);
+    d_p = in;
+    d_bc = in + nc;
+    d_gq = load_flux ? in + nc + nf : nullptr;
+    d_gp = load_pressure ? in + nc + 2 * nf : nullptr;
+    d_vs = vector_source ? in + 2 * nc + 2 * nf : nullptr;
+    vec_in(h, d_p, p, nc);
+    vec_in(h, d_bc, bc_values, nf);
+    if (d_gq) vec_in(h, d_gq, load_flux, nf);
+    if (d_gp) vec_in(h, d_gp, load_pressure, nc);
+    if (d_vs) vec_in(h, d_vs, vector_source, nvs);
+    int32_t* half = h->fa_half.ensure(2 * nf + ncf);
+    first = half;
+    last = half + nf;
+    ecell = half + 2 * nf;
+    pfv::flow_adjoint_half_faces(*h, first, last, ecell);
+    const pfv::FlowAdjointFindings fd = pfv::flow_adjoint_check(*h, first, last, d_p, d_bc, d_gq, d_gp);
+    if (fd.robin != none)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "face " + std::to_string(fd.robin) + " carries a Robin condition: the flow "
+                                            "adjoint covers Dirichlet and Neumann faces");
+    if (fd.internal != none)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "face " + std::to_string(fd.internal) + " is flagged PFV_BC_INTERNAL: the flow "
+                                            "adjoint does not cover internal boundaries");
+    if (fd.bad_gq != none)
+      throw pfv::Error(PFV_ERR_ARGUMENT, "load_flux[" + std::to_string(fd.bad_gq) + "] is not finite");
+    if (fd.bad_gp != none)
+      throw pfv::Error(PFV_ERR_ARGUMENT, "load_pressure[" + std::to_string(fd.bad_gp) + "] is not finite");
+    if (fd.bad_p != none) throw pfv::Error(PFV_ERR_ARGUMENT, "p[" + std::to_string(fd.bad_p) + "] is not finite");
+    if (fd.bad_bc != none)
+      throw pfv::Error(PFV_ERR_ARGUMENT, "bc_values[" + std::to_string(fd.bad_bc) + "] (a boundary face) is not finite");
+    // ---- what belongs to the patterns: column maps, transposed positions
+    pfv::Timer tm;
+    h->stats.flow_adjoint_map_ms = 0.0;
+    const size_t nnzA = (size_t)std::max<int64_t>(h->pat_A.nnz, 1);
+    if (!h->have_cmap || !h->have_tpos_A) {
+      tm.start(s);
+      if (!h->have_cmap) {
+        pfv::colmap_build(*h, h->pat_flux, h->cmap_flux);
+        pfv::colmap_build(*h, h->pat_bound, h->cmap_bound);
+        h->have_cmap = true;
+        ++h->stats.flow_adjoint_map_builds;
+      }
+      if (!h->have_tpos_A) {
+        pfv::sweep_transpose_positions(*h, h->pat_A, h->tpos_A.ensure(nnzA), "div flux");
+        h->have_tpos_A = true;
+      }
+      h->stats.flow_adjoint_map_ms = tm.stop(s);
+    }
+    // ---- A = div T afresh, A^T on its own pattern
+    h->active.valid = false;  // (whatever was active: the call ends without an active system)
+    if (!h->have_system) {
+      h->have_advdiff = h->have_adv_bD = false;  // (as pfv_mpfa_assemble: built on the previous div @ flux)
+      values_changed(h, Windows::consume);
+    } else {
+      values_changed(h, Windows::keep);
+    }
+    pfv::assemble_system(*h);
+    double* valT = h->fa_valT.ensure(nnzA);
+    pfv::sweep_transpose_values(*h, h->pat_A.nnz, h->tpos_A.p, h->val[PFV_MAT_SYSTEM].p, valT);
+    double* rhs = h->fa_rhs.ensure(nc);
+    d_mu = h->fa_mu.ensure(nc);
+    tm.start(s);
+    if (d_gq) {
+      pfv::spmv_transposed(*h, h->cmap_flux, h->val[PFV_MAT_FLUX].p, d_gq, rhs);
+      if (d_gp) {
+        const double* gp = d_gp;
+        pfv::parallel_for(s, (int64_t)nc, PFV_LAMBDA(int64_t i) { rhs[i] = gp[i] + rhs[i]; });
+      }
+    } else {
+      pfv::be_d2d(rhs, d_gp, sizeof(double) * nc, s);
+    }
+    products_ms = tm.stop(s);
+    activate(h, h->pat_A, valT, h->diag.p, rhs, h->nc, 1, true);
+  });
+  if (st != PFV_OK) return st;
+  // ---- the solve, through the owner of the active system; mu stays on the device
+  pfv_solve_info sinfo{};
+  const bool on_device = h->vectors_on_device;
+  h->vectors_on_device = true;
+  st = pfv_solve(h, method, rtol, maxit, restart, nullptr, d_mu, &sinfo);
+  h->vectors_on_device = on_device;
+  h->active.valid = false;
+  if (info) *info = sinfo;
+  ++h->stats.flow_adjoint_calls;
+  h->stats.flow_adjoint_iterations = sinfo.iterations;
+  h->stats.flow_adjoint_solve_ms = sinfo.solve_ms;
+  h->stats.flow_adjoint_products_ms = products_ms;
+  h->stats.flow_adjoint_gradient_ms = 0.0;
+  if (st != PFV_OK) return st;
+  return guarded(h, [&] {
+    auto s = h->stream;
+    const size_t nf = (size_t)h->nf, nc = (size_t)h->nc, ncf = (size_t)h->ncf;
+    pfv::Timer tm;
+    if (grad_perm || grad_bc_values) {
+      pfv::Buf<double> z_, zw_, inv_, gk_, gb_;
+      double* z = z_.ensure(nf);
+      double* zw = zw_.ensure(nf);
+      tm.start(s);
+      pfv::flow_adjoint_faces(*h, first, last, ecell, d_p, d_bc, d_vs, vd, d_gq, d_mu, z, zw);
+      double* gk = nullptr;
+      if (grad_perm) {
+        gk = gk_.ensure(9 * nc);
+        pfv::flow_adjoint_grad_perm(*h, first, last, zw, inv_.ensure(std::max<size_t>(ncf, 1)), gk);
+      }
+      h->stats.flow_adjoint_gradient_ms = tm.stop(s);
+      if (gk) vec_out(h, grad_perm, gk, 9 * nc);
+      if (grad_bc_values) {
+        double* gb = gb_.ensure(nf);
+        tm.start(s);
+        pfv::spmv_transposed(*h, h->cmap_bound, h->val[PFV_MAT_BOUND_FLUX].p, z, gb);
+        h->stats.flow_adjoint_products_ms += tm.stop(s);
+        vec_out(h, grad_bc_values, gb, nf);
+      }
+      pfv::be_sync(s);  // (the staging buffers are freed on return)
+    }
+    if (mu_out) vec_out(h, mu_out, d_mu, nc);
+    if (grad_source) vec_out(h, grad_source, d_mu, nc);
+    pfv::be_sync(s);
+  });
 }
 
 

@@ -1182,7 +1182,8 @@ static void upwind_bref_react(pfv_ctx_impl& c, int k, const double* d_q, const d
 //   valT    valT[e] = val[tpos[e]], once per assembly: row i of valT is column i of A on the pattern of row i, so the
 //           transposed row has the load chain of sweep_row_multi -- no search in a level, no atomics.
 // first entry without a partner in tpos' status word (0x7f7f7f7f: none)
-static void sweep_transpose_positions(pfv_ctx_impl& c, const CsrPattern& P, int32_t* tpos) {
+static void sweep_transpose_positions(pfv_ctx_impl& c, const CsrPattern& P, int32_t* tpos,
+                                      const char* what = "the transport system") {
   stream_t s = c.stream;
   const int32_t* ip = P.indptr;
   const int32_t* ix = P.indices;
@@ -1200,7 +1201,7 @@ static void sweep_transpose_positions(pfv_ctx_impl& c, const CsrPattern& P, int3
   });
   const int32_t bad = read_scalar<int32_t>(s, st);
   if (bad != 0x7f7f7f7f)
-    throw Error(PFV_ERR_UNSUPPORTED, "the pattern of the transport system is not structurally symmetric (entry " +
+    throw Error(PFV_ERR_UNSUPPORTED, std::string("the pattern of ") + what + " is not structurally symmetric (entry " +
                                          std::to_string(bad) + " has no transposed partner)");
 }
 

@@ -980,6 +980,7 @@ static void build_symbolic(pfv_ctx_impl& c) {
   // the patterns are replaced: values computed for the old ones must not be handed out against them
   for (int m = PFV_MAT_FLUX; m <= PFV_MAT_SYSTEM; ++m) c.filled[m] = false;
   c.have_symbolic = false;
+  c.have_cmap = c.have_tpos_A = false;  // (flow_adjoint.inc: properties of the patterns replaced here)
   be_memset(st + 7, 0, sizeof(int32_t), s);
   Buf<int32_t> stage_ix;  // staging areas of the one-pass row builds (face rows, then the rows of A)
   Buf<uint8_t> stage_cp;

@@ -30,6 +30,7 @@ static void tpfa_discretize(pfv_ctx_impl& c, int vd) {
   int32_t* st = c.status.ensure(16);
   be_memset(st, 0, sizeof(int32_t) * 8, s);
   const bool periodic = c.periodic;
+  c.have_cmap = c.have_tpos_A = false;  // (flow_adjoint.inc: properties of the patterns replaced here)
 
   // ---- transpose cell_faces: entries grouped by face
   Buf<uint32_t> kin, kout;

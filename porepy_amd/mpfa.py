@@ -26,6 +26,7 @@ from .grid import grid_to_raw
 from .partial import active_indices
 from .periodic import merge_periodic, merged_subface_order
 from .params import DISCRETIZATION_MATRICES, PARAMETERS, bc_flags
+from .tpfa import flow_adjoint_call
 
 _KEYS = (
     ("flux", _lib.MAT_FLUX),
@@ -884,6 +885,38 @@ class Mpfa:
         if ent is None or ent[0] is not sd:
             raise RuntimeError("ad_flux_system(sd, ...) first")
         return ent[1].solve(method=method, rtol=rtol, maxit=maxit, precond=precond)
+
+    def adjoint_flow(self, sd, data: dict, p, grad_flux=None, grad_pressure=None,
+                     want=("permeability", "bc_values", "source"), method: str = "bicgstab", rtol: float = 1e-12,
+                     maxit: int = 20000, restart: int = 0, precond: str = "amg"):
+        """The adjoint of the flow solve ``A p = source - div (bound_flux bc_values + vector_source g)``, ``q = flux p +
+        bound_flux bc_values (+ vector_source g)`` of the last ``discretize(sd, data)``, on the device
+        (pfv_flow_adjoint): ``grad_flux`` = dJ/dq (Nf; what the ``Upwind.adjoint_*`` calls return as ``"flux"``) and
+        ``grad_pressure`` = dJ/dp (Nc) of an objective J at the forward solution ``p`` become, for about one more flow
+        solve, the gradients named in ``want``:
+
+        - ``"source"`` (Nc): the multiplier mu, ``A^T mu = grad_pressure + flux^T grad_flux``;
+        - ``"bc_values"`` (Nf): ``bound_flux^T z`` with ``z = grad_flux - cell_faces mu``; zero off the boundary;
+        - ``"permeability"`` (3, 3, Nc), all nine entries independent: ``sum_f z_f w_f dt_f/dK_rs(c)`` with the two-point
+          transmissibility derivative of ``DifferentiableTpfa`` and ``w_f = dq_f/dt_f`` of ``ad_flux_system``;
+        - ``"multiplier"`` (Nc): mu itself.
+
+        ``"source"``, ``"bc_values"`` and mu are exact.  ``"permeability"`` is, for this MPFA discretization, the
+        two-point product rule of the reference's ``AdTpfaFlux`` -- the same approximation ``ad_flux_system`` makes for
+        its Jacobian --, NOT the derivative of the MPFA matrices; ``Tpfa.adjoint_flow`` gives the exact gradient of its
+        discrete problem.  Robin and internal-boundary faces, conditions per sub-face, partial discretizations: status 5.
+        Returns (grads, info); afterwards the handle holds no active system."""
+        if sd.dim < 2:
+            return self._tpfa().adjoint_flow(sd, data, p, grad_flux=grad_flux, grad_pressure=grad_pressure, want=want,
+                                             method=method, rtol=rtol, maxit=maxit, restart=restart, precond=precond)
+        pd = data[PARAMETERS][self.keyword]
+        ent = self._contexts.get(id(sd))
+        if ent is None or ent[0] is not sd or not ent[1].has_discretization:
+            raise RuntimeError("discretize(sd, data) must run on this object before adjoint_flow")
+        if self._plane.get(id(sd)) is not None or self._periodic.get(id(sd)) is not None:
+            raise NotImplementedError("tilted or periodic grids are not covered by the flow adjoint")
+        return flow_adjoint_call(ent[1], pd, p, self._vector_source(sd, pd), grad_flux, grad_pressure, want, method,
+                                 rtol, maxit, restart, precond)
 
     def darcy_flux(self, sd, data: dict, p, resident: bool = False):
         """Face flux ``flux @ p + bound_flux @ bc_values (+ vector_source @ g)`` of the discretization on the device

@@ -34,6 +34,21 @@ def empty_matrices(sd, vector_source_dim: int) -> dict:
     }
 
 
+def flow_adjoint_call(ctx, pd, p, vector_source, grad_flux, grad_pressure, want, method, rtol, maxit, restart, precond):
+    """``Context.flow_adjoint`` for the parameters ``pd`` of a flow keyword (shared by ``Mpfa`` and ``Tpfa``): status 4
+    (a bad argument: no load, a non-finite value) becomes ``ValueError``, as in ``Upwind``."""
+    if grad_flux is None and grad_pressure is None:
+        raise ValueError("adjoint_flow needs grad_flux, grad_pressure or both")
+    try:
+        return ctx.flow_adjoint(p, np.asarray(pd["bc_values"], dtype=float), vector_source, load_flux=grad_flux,
+                                load_pressure=grad_pressure, want=want, method=method, rtol=rtol, maxit=maxit,
+                                restart=restart, precond=precond)
+    except _lib.PorefvError as e:
+        if e.status == 4:
+            raise ValueError(e.message) from None
+        raise
+
+
 class Tpfa:
     """TPFA flux discretization for ``keyword`` on the device."""
 
@@ -117,6 +132,17 @@ class Tpfa:
         if self._periodic.get(id(sd)) is not None:
             raise _lib.PorefvError(5, "the device face flux does not cover periodic grids")
         return flow_darcy_flux(self._ctx(sd), pd, p, pd.get("vector_source", None), resident)
+
+    def adjoint_flow(self, sd, data: dict, p, grad_flux=None, grad_pressure=None,
+                     want=("permeability", "bc_values", "source"), method: str = "cg", rtol: float = 1e-12,
+                     maxit: int = 20000, restart: int = 0, precond: str = "amg"):
+        """The adjoint of the flow solve of this discretization on the device; see ``Mpfa.adjoint_flow``.  Here
+        ``"permeability"`` is the exact gradient of the discrete problem."""
+        if self._periodic.get(id(sd)) is not None:
+            raise NotImplementedError("tilted or periodic grids are not covered by the flow adjoint")
+        pd = data[PARAMETERS][self.keyword]
+        return flow_adjoint_call(self._ctx(sd), pd, p, pd.get("vector_source", None), grad_flux, grad_pressure, want,
+                                 method, rtol, maxit, restart, precond)
 
     def solve(self, sd, data: dict, source=None, method: str = "cg", rtol: float = 1e-12, maxit: int = 20000,
               x0=None, restart: int = 0, precond: str = "jacobi"):

@@ -290,8 +290,9 @@ class Upwind:
         - ``"flux"`` (Nf,): ``-sum_n sum_a (lambda_a^n[p] - lambda_a^n[m]) cup_a^n`` with p / m the cells of
           ``cell_faces`` sign +1 / -1 and ``cup`` the upwind value at the face -- needs ``states``.  It is the
           derivative at a FIXED upstream side: valid wherever no ``q_f`` is exactly zero (a face whose flux changes sign
-          has a kink there), zero on Neumann faces, whose flux is data.  The chain on to permeability goes through
-          ``Mpfa.ad_flux_system`` and is the caller's to compose.
+          has a kink there), zero on Neumann faces, whose flux is data.  The chain on to permeability, the flow
+          boundary values and the flow source is ``Mpfa.adjoint_flow`` / ``Tpfa.adjoint_flow`` with this array as
+          ``grad_flux``.
 
         The cells of a cyclic core are iterated by Jacobi on their transposed rows, at most ``maxit`` times per step.
         Returns (grads, info): a dict by the names in ``want``, and info["steps_done"], "converged" and the
@@ -556,8 +557,8 @@ class Upwind:
         Every gradient is the derivative on a FIXED branch: of the interval of a table, of the side of a residual
         saturation, of the upstream side of every face.  J has kinks where a state sits on a table knot or on a
         residual saturation and where a ``q_f`` is exactly zero: there the gradient is a one-sided derivative, elsewhere
-        the derivative.  The chain from ``"flux"`` to a permeability goes through ``Mpfa.ad_flux_system`` and is the
-        caller's.
+        the derivative.  The chain from ``"flux"`` to a permeability is ``Mpfa.adjoint_flow`` /
+        ``Tpfa.adjoint_flow`` with that array as ``grad_flux``.
 
         The cells of a cyclic core are iterated by Jacobi on their transposed rows, at most ``maxit`` times per step.
         Returns (grads, info): info["steps_done"], "converged", "iterations" (1, or the core iterations of the last

@@ -458,6 +458,13 @@ pfv_status pfv_set_near_null_space(pfv_ctx* h, int bs, int k, const double* B);
 pfv_status pfv_amg_nns_level(pfv_ctx* h, int level, int64_t* info, int32_t* agg, double* P, double* B, double* Bc,
                              int32_t* indptr, int32_t* indices, double* val);
 
+/* One cycle of that hierarchy on device vectors of its n_0 rows (tests): d_z = cycle(level 0, d_r), d_r != d_z.  The
+ * twin of pfv_amg_apply_device: it only runs the cycle the solve runs, on the hierarchy's own scratch vectors, and
+ * changes nothing a later solve depends on.  The vectors are in the numbering of the system the hierarchy was built
+ * for: the caller's for a user system, the numbering the solve worked in (the renumbering along the cell order, when
+ * pfv_solve applied it) for a grid system.  PFV_ERR_ARGUMENT without a valid hierarchy, as pfv_amg_nns_level. */
+pfv_status pfv_amg_nns_apply_device(pfv_ctx* h, const double* d_r, double* d_z);
+
 /* Introspection of the plain aggregation hierarchy (PFV_PRECOND_AMG) that was set up last on this handle, by
  * pfv_amg_setup or by a pfv_solve with PFV_PRECOND_AMG (tests).  It only copies data out: no kernel, launch or buffer
  * of the setup or the cycle depends on it.  Numbering: the hierarchy of pfv_amg_setup is built on the active system as

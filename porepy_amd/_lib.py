@@ -47,7 +47,7 @@ EXPORTS = [
     "pfv_rccl_unique_id", "pfv_rccl_comm_create", "pfv_rccl_set_halo_plan", "pfv_rccl_hooks", "pfv_rccl_stats",
     "pfv_rccl_last_error", "pfv_rccl_comm_destroy", "pfv_mpfa_ad_flux_system", "pfv_host_alloc", "pfv_host_free",
     "pfv_mpsa_set_subface_eta", "pfv_mpsa_set_reconstruction_eta", "pfv_mpsa_set_reconstruction_eta_subface", "pfv_get_stats_n", "pfv_set_block_preconditioner",
-    "pfv_mpfa_set_permeability", "pfv_set_near_null_space", "pfv_amg_nns_level", "pfv_amg_level",
+    "pfv_mpfa_set_permeability", "pfv_set_near_null_space", "pfv_amg_nns_level", "pfv_amg_nns_apply_device", "pfv_amg_level",
     "pfv_mpfa_face_flux", "pfv_upwind_set_bc", "pfv_upwind_discretize", "pfv_upwind_assemble", "pfv_transport_advance",
     "pfv_advdiff_assemble", "pfv_advdiff_advance", "pfv_advdiff_face_flux", "pfv_resident_flux",
     "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl", "pfv_transport_advance_nl_multi",
@@ -253,6 +253,8 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_set_near_null_space.restype = C.c_int
     lib.pfv_amg_nns_level.argtypes = [_h, C.c_int, _lp, _ip, _dp, _dp, _dp, _ip, _ip, _dp]
     lib.pfv_amg_nns_level.restype = C.c_int
+    lib.pfv_amg_nns_apply_device.argtypes = [_h, C.c_void_p, C.c_void_p]
+    lib.pfv_amg_nns_apply_device.restype = C.c_int
     lib.pfv_amg_level.argtypes = [_h, C.c_int, _lp, _dp, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _ip, _dp, _dp, _ip, _ip, _ip,
                                   _dp]
     lib.pfv_amg_level.restype = C.c_int
@@ -1143,6 +1145,11 @@ class Context:
                                                _ptr(Bc, _dp) if nagg else None, _ptr(ip, _ip), _ptr(ix, _ip), _ptr(v, _dp)))
         return {"n": n, "block_size": bs, "k": k, "aggregates": nagg, "levels": nlev, "agg": agg, "P": P, "B": B,
                 "Bc": Bc, "A": sps.csr_matrix((v, ix, ip), shape=(n, n))}
+
+    def amg_nns_apply_device(self, r_ptr: int, z_ptr: int):
+        """z = one cycle of the PFV_PRECOND_AMG_NNS hierarchy of the last solve on device vectors of its level-0 size
+        (pfv_amg_nns_apply_device), in the numbering of the system the hierarchy was built for."""
+        self._check(self.lib.pfv_amg_nns_apply_device(self._h, C.c_void_p(r_ptr), C.c_void_p(z_ptr)))
 
     AMG_PATH_BITS = {"restrict_residual": 1, "prolong_smooth": 2, "fused_product": 4, "visited_twice": 8,
                      "second_visit": 16, "second_visit_fused": 32, "dense": 64, "jacobi": 128}

@@ -3750,6 +3750,14 @@ pfv_status pfv_amg_nns_level(pfv_ctx* h, int level, int64_t* info, int32_t* agg,
   });
 }
 
+pfv_status pfv_amg_nns_apply_device(pfv_ctx* h, const double* d_r, double* d_z) {
+  return guarded(h, [&] {
+    require(h->amg_nns && h->amg_nns->valid, "no near-null-space hierarchy (solve with PFV_PRECOND_AMG_NNS first)");
+    require(d_r && d_z && d_r != d_z, "bad vectors");
+    pfv::amg_nns_cycle(*h, *h->amg_nns, 0, d_r, d_z);
+  });
+}
+
 pfv_status pfv_amg_level(pfv_ctx* h, int level, int64_t* info, double* params, int32_t* sys_indptr, int32_t* sys_indices,
                          double* sys_val, int32_t* a_indptr, int32_t* a_indices, double* a_val, int32_t* op_indptr,
                          int32_t* op_indices, double* op_val, double* dinv, int32_t* agg, int32_t* mptr, int32_t* mem,

@@ -3,6 +3,7 @@ build of the same kernels; tests/test_gpu_amg_nns.py runs the same cases on the 
 import pytest
 
 from tests import _amg_nns_cases as C
+from tests import _amg_nns_cycle_cases as Y
 from tests import _parity as P
 
 
@@ -65,3 +66,31 @@ def test_sharded_unsupported(lib):
 
 def test_bad_arguments(lib):
     C.bad_arguments(lib)
+
+
+# the cycle against the independent reference (tests/_amg_nns_cycle_cases.py)
+
+@pytest.mark.parametrize("name", list(Y.USER_CASES))
+def test_cycle_against_reference(lib, name):
+    Y.user_case(lib, name)
+
+
+@pytest.mark.parametrize("name", list(Y.MPSA_CASES))
+def test_cycle_against_reference_mpsa(lib, name):
+    Y.mpsa_case(lib, name)
+
+
+def test_too_wide_coarse_row_is_refused(lib):
+    Y.too_wide_is_refused(lib)
+
+
+def test_passes_stop_at_the_built_in_target(lib):
+    Y.passes_stop_at_the_constant(lib)
+
+
+def test_rigid_body_modes_far_from_the_origin(lib):
+    Y.far_from_the_origin(lib)
+
+
+def test_apply_is_read_only(lib):
+    Y.apply_is_read_only(lib)

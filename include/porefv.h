@@ -228,6 +228,14 @@ typedef struct {
   double flow_adjoint_products_ms; /* ... the two transposed products T^T g_q and B^T z */
   double flow_adjoint_solve_ms;    /* ... the transposed solve, preconditioner set-up included */
   double flow_adjoint_gradient_ms; /* ... the face kernel and the cell kernel of grad_perm */
+  double advdiff_adjoint_ms;       /* last pfv_advdiff_adjoint: everything after its checks, up to the copies out */
+  int64_t advdiff_adjoint_steps;   /* ... adjoint steps accepted */
+  int64_t advdiff_adjoint_iterations; /* ... Krylov iterations summed over its steps */
+  int64_t advdiff_adjoint_gmres_retries; /* ... steps whose BiCGStab solve broke down (NaN residual) and were solved
+                                     again with GMRES */
+  int64_t advdiff_adjoint_precond_fallbacks; /* ... steps whose AMG-preconditioned solve did not converge and were
+                                     solved again with Jacobi-GMRES */
+  double advdiff_adjoint_accumulate_ms; /* ... HIP-event time of the face pass and the cell pass, summed over the steps */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -1024,6 +1032,56 @@ pfv_status pfv_advdiff_advance(pfv_ctx* h, int n_steps, int method, double rtol,
  * pfv_advdiff_assemble: w q c_upstream (+ the Dirichlet-inflow / Neumann boundary parts) + flux_D c + bound_flux_D
  * bc_values.  Its divergence over a step equals source - accumulation o (c_new - c_old). */
 pfv_status pfv_advdiff_face_flux(pfv_ctx* h, const double* c, double* out);
+
+/* The adjoint of pfv_advdiff_advance (csrc/advdiff_adjoint.inc): every gradient of J = sum_{n=1..N} <g^n, c^n[obs_cells]>
+ * through n_steps = N forward steps
+ *     S c^n = acc o c^{n-1} - b_ref + b_D + src,      S = diag(acc) + div T_D + w div diag(q) U
+ * of the system of the last pfv_advdiff_assemble (its q, w, bc_values, accumulation), which must be the active one
+ * (else PFV_ERR_ARGUMENT).  For n = N .. 1 the call solves S^T lambda^n = g^n + acc o lambda^{n+1} (lambda^{N+1} = 0): the
+ * values of S^T are taken on the pattern of S through transposed positions and (S^T, diag, rhs) is made the active
+ * system ONCE; with PFV_PRECOND_AMG the hierarchy of S^T is set up by the first step and reused by all later ones.  Every
+ * step is one pfv_solve started from lambda^{n+1} with the fallbacks of pfv_advdiff_advance: a BiCGStab step that breaks
+ * down (NaN residual) is solved again with GMRES from the kept state, a step the AMG-preconditioned solve does not finish
+ * with Jacobi-GMRES.  Then ONE pass over the faces and ONE over the cells accumulate the sums below; no step adds a host
+ * read beyond those of its solve.
+ *   loads [N][n_obs]: loads[n - 1] = g^n = dJ/dc^n on the observation cells obs_cells (n_obs int32 cell indices in HOST
+ * memory, no repeats; NULL: every cell in order, n_obs must be Nc).  states (may be NULL): c^0 .. c^N as [N + 1][Nc]; one
+ * slab is staged per step when they are host memory.  loads, states and the gradients follow
+ * pfv_set_vectors_on_device; grad_flux_scale is one double in host memory.  method: PFV_SOLVE_BICGSTAB or
+ * PFV_SOLVE_GMRES.
+ *   With y^n_f = lambda^n[p] - lambda^n[m] (p / m the cells of cell_faces sign +1 / -1 at f, a missing cell contributes
+ * nothing) and Lambda = sum_n lambda^n, each gradient may be NULL (not wanted):
+ *     grad_c0 [Nc]               acc o lambda^1
+ *     grad_source [Nc]           Lambda
+ *     grad_bc_values [Nf]        -(B_D^T + (rhs_neu + rhs_dir diag(w q))^T) (cell_faces Lambda), zero off the boundary
+ *     grad_accumulation [Nc]     sum_n lambda^n o (c^{n-1} - c^n)                                   (needs states)
+ *     grad_flux [Nf]             -w sum_n y^n_f cup^n_f                                             (needs states)
+ *     grad_flux_scale [1]        (1/w) sum_f q_f grad_flux_f, a reduction of fixed shape            (needs states)
+ *     grad_conductivity [(3,3,Nc)]  sum_{e=(c,f)} zw_f dt_f/dK_rs(c), zw_f = -sum_n y^n_f w^n_f     (needs states)
+ *     multipliers_out [N][Nc]    lambda^1 .. lambda^N
+ * cup is the upwind value of pfv_transport_adjoint_multi: the upstream cell's c^n on interior and outflow faces,
+ * bc_values on a Dirichlet inflow face, 0 on a Neumann face; grad_flux is the derivative at a FIXED upstream side.
+ * w^n_f = filter_f (c^n difference) - dir_f sgn_f bc_f and dt_f/dK are those of pfv_flow_adjoint for p = c^n, mu =
+ * lambda^n, and grad_conductivity has the meaning grad_perm has there: for pfv_tpfa_discretize it is the exact gradient of
+ * the discrete problem; for pfv_mpfa_discretize it is the two-point product rule of the reference's AdTpfaFlux, NOT the
+ * derivative of the MPFA matrices.  All other gradients are exact for both schemes.  Nothing uses floating-point
+ * atomics: two calls give the same bits.
+ *   steps_done: the adjoint steps accepted.  A step that does not converge returns PFV_ERR_NOT_CONVERGED and writes NO
+ * gradient.  last (may be NULL): the info of the last solve.
+ *   After the call the handle holds NO active system and no advection-diffusion system (pfv_solve and
+ * pfv_advdiff_advance ask for pfv_advdiff_assemble); the diffusion discretization, div T_D, b_D, the resident flux, the
+ * flow order and the AMG aggregate maps are untouched.
+ *   PFV_ERR_ARGUMENT: no active advection-diffusion system; another method; an obs_cells entry out of range or
+ * repeated; a non-finite load (the text names the lowest index); grad_accumulation, grad_flux, grad_flux_scale or
+ * grad_conductivity without states.  PFV_ERR_UNSUPPORTED: what pfv_advdiff_assemble refuses; Robin faces and faces
+ * flagged PFV_BC_INTERNAL (the text names the first); a partial discretization with zeroed rows; PFV_PRECOND_SWEEP (the
+ * substitution in reverse flow order on S^T is a later pull request); a pattern of div flux or bound_flux of 2^31
+ * entries or more.  pfv_stats: advdiff_adjoint_*. */
+pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int32_t* obs_cells, const double* loads,
+                               const double* states, int method, double rtol, int maxit, double* grad_c0,
+                               double* grad_source, double* grad_bc_values, double* grad_accumulation,
+                               double* grad_flux, double* grad_flux_scale, double* grad_conductivity,
+                               double* multipliers_out, int32_t* steps_done, pfv_solve_info* last);
 /* The resident face flux (pfv_mpfa_face_flux) of this handle: d_q (may be NULL) receives its device address -- Nf
  * doubles, valid until the next pfv_mpfa_face_flux or pfv_set_grid on the handle --, q_out (Nf, may be NULL) a copy,
  * in host or device memory as selected by pfv_set_vectors_on_device.  PFV_ERR_ARGUMENT when there is none. */

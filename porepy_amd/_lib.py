@@ -52,7 +52,7 @@ EXPORTS = [
     "pfv_advdiff_assemble", "pfv_advdiff_advance", "pfv_advdiff_face_flux", "pfv_resident_flux",
     "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl", "pfv_transport_advance_nl_multi",
     "pfv_transport_advance_react", "pfv_transport_adjoint_multi", "pfv_transport_adjoint_react",
-    "pfv_transport_adjoint_nl", "pfv_transport_adjoint_nl_multi", "pfv_flow_adjoint",
+    "pfv_transport_adjoint_nl", "pfv_transport_adjoint_nl_multi", "pfv_flow_adjoint", "pfv_advdiff_adjoint",
 ]
 
 
@@ -102,7 +102,10 @@ class Stats(C.Structure):
                 ("flow_adjoint_calls", C.c_int64), ("flow_adjoint_iterations", C.c_int64),
                 ("flow_adjoint_map_builds", C.c_int64), ("flow_adjoint_map_ms", C.c_double),
                 ("flow_adjoint_products_ms", C.c_double), ("flow_adjoint_solve_ms", C.c_double),
-                ("flow_adjoint_gradient_ms", C.c_double)]
+                ("flow_adjoint_gradient_ms", C.c_double),
+                ("advdiff_adjoint_ms", C.c_double), ("advdiff_adjoint_steps", C.c_int64),
+                ("advdiff_adjoint_iterations", C.c_int64), ("advdiff_adjoint_gmres_retries", C.c_int64),
+                ("advdiff_adjoint_precond_fallbacks", C.c_int64), ("advdiff_adjoint_accumulate_ms", C.c_double)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -359,6 +362,9 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_advdiff_advance.restype = C.c_int
     lib.pfv_advdiff_face_flux.argtypes = [_h, _dp, _dp]
     lib.pfv_advdiff_face_flux.restype = C.c_int
+    lib.pfv_advdiff_adjoint.argtypes = [_h, C.c_int, C.c_int64, _ip, _dp, _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp,
+                                        _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
+    lib.pfv_advdiff_adjoint.restype = C.c_int
     lib.pfv_resident_flux.argtypes = [_h, C.POINTER(C.c_void_p), _dp]
     lib.pfv_sweep_info.argtypes = [_h, _lp, _ip, _ip]
     lib.pfv_sweep_info.restype = C.c_int
@@ -2060,6 +2066,90 @@ class Context:
             if device:
                 self._dev(False)
         return out
+
+    ADVDIFF_ADJOINT_GRADIENTS = ("c0", "source", "bc_values", "accumulation", "flux", "flux_scale", "conductivity",
+                                 "multipliers")
+
+    def advdiff_adjoint(self, n_steps: int, loads, states=None, obs_cells=None, want=("c0", "source", "bc_values"),
+                        method="bicgstab", rtol=1e-12, maxit=20000, precond="amg", raise_on_fail=True, device=False,
+                        out_ptrs=None):
+        """The adjoint of ``advdiff_advance`` on the system of the last ``advdiff_assemble`` (pfv_advdiff_adjoint): the
+        gradients of ``J = sum_n <loads[n-1], c^n[obs_cells]>`` through ``n_steps`` forward steps, one transposed Krylov
+        solve per step.  ``loads``: N x n_obs, ``obs_cells``: n_obs cell indices (host) or None (every cell),
+        ``states``: (N + 1) x Nc (c^0 .. c^N) or None.  ``want``: names out of ``ADVDIFF_ADJOINT_GRADIENTS`` -- "c0",
+        "source", "accumulation" (Nc), "bc_values", "flux" (Nf), "flux_scale" (a float), "conductivity" (3, 3, Nc; exact
+        for a TPFA diffusion, for MPFA the two-point product rule of ``ad_flux_system``, not the derivative of the MPFA
+        matrices) and "multipliers" (N x Nc); "accumulation", "flux", "flux_scale" and "conductivity" need ``states``.
+        Returns (grads, info).  A step that does not converge leaves the gradients zero.  ``device``: ``loads`` and
+        ``states`` are addresses of device buffers and the wanted outputs go to the addresses in ``out_ptrs`` (name ->
+        address; "flux_scale" is returned in grads all the same: it is host memory)."""
+        code = {"cg": SOLVE_CG, "bicgstab": SOLVE_BICGSTAB, "gmres": SOLVE_GMRES}[method]  # ("cg": refused by the call)
+        n_steps = int(n_steps)
+        if n_steps < 0:
+            raise ValueError("n_steps must not be negative")
+        obs = None
+        if obs_cells is not None:
+            obs = np.ascontiguousarray(obs_cells)
+            if obs.ndim != 1 or not np.issubdtype(obs.dtype, np.integer):
+                raise ValueError("obs_cells must be a one-dimensional array of cell indices")
+            big = obs[(obs < -2 ** 31) | (obs >= 2 ** 31)]
+            if big.size:
+                raise ValueError(f"obs_cells: {int(big[0])} is out of range (0 .. {self.nc - 1})")
+            obs = obs.astype(np.int32)
+        n_obs = self.nc if obs is None else obs.size
+        want = tuple(want)
+        for name in want:
+            if name not in self.ADVDIFF_ADJOINT_GRADIENTS:
+                raise ValueError(f"want: unknown gradient {name!r} (known: {', '.join(self.ADVDIFF_ADJOINT_GRADIENTS)})")
+            if name in ("accumulation", "flux", "flux_scale", "conductivity") and states is None:
+                raise ValueError(f'the gradient "{name}" needs states (c^0 .. c^N)')
+        if device:
+            pl = C.cast(int(loads), _dp)
+            ps = C.cast(int(states), _dp) if states is not None else None
+        else:
+            ld = _f64(loads)
+            if ld.shape != (n_steps, n_obs):
+                raise ValueError(f"loads must have shape ({n_steps}, {n_obs}), not {ld.shape}")
+            pl = _ptr(ld, _dp)
+            stt = None
+            if states is not None:
+                stt = _f64(states)
+                if stt.shape != (n_steps + 1, self.nc):
+                    raise ValueError(f"states must have shape ({n_steps + 1}, {self.nc}), not {stt.shape}")
+            ps = _ptr(stt, _dp)
+        shapes = {"c0": (self.nc,), "source": (self.nc,), "bc_values": (self.nf,), "accumulation": (self.nc,),
+                  "flux": (self.nf,), "conductivity": (3, 3, self.nc), "multipliers": (n_steps, self.nc)}
+        scale = np.zeros(1) if "flux_scale" in want else None
+        if device:
+            grads = {}
+            outs = {name: C.cast(int((out_ptrs or {})[name]), _dp) for name in want if name != "flux_scale"}
+        else:
+            grads = {name: np.zeros(shapes[name]) for name in self.ADVDIFF_ADJOINT_GRADIENTS
+                     if name in want and name != "flux_scale"}
+            outs = {name: _ptr(a, _dp) for name, a in grads.items()}
+        self._select_precond(precond)
+        done, info = C.c_int32(0), SolveInfo()
+        if device:
+            self._dev(True)
+        try:
+            st = self.lib.pfv_advdiff_adjoint(
+                self._h, n_steps, n_obs, _ptr(obs, _ip), pl, ps, code, float(rtol), int(maxit), outs.get("c0"),
+                outs.get("source"), outs.get("bc_values"), outs.get("accumulation"), outs.get("flux"), _ptr(scale, _dp),
+                outs.get("conductivity"), outs.get("multipliers"), C.byref(done), C.byref(info))
+        finally:
+            if device:
+                self._dev(False)
+        if scale is not None:
+            grads["flux_scale"] = float(scale[0])
+        out = {"steps_done": done.value, "iterations": info.iterations, "converged": bool(info.converged),
+               "rel_residual": info.rel_residual, "solve_ms": info.solve_ms}
+        if st != 0 and (raise_on_fail or st != 6):
+            try:
+                self._check(st)
+            except PorefvError as e:
+                e.info = out
+                raise
+        return grads, out
 
     def tpfa_transmissibility_ad(self, perm):
         """Two-point face transmissibilities and their derivatives with respect to the permeability entries

@@ -144,15 +144,85 @@ class AdvectionDiffusion:
         return self.context(sd).solve(method=method, rtol=rtol, maxit=maxit, x0=x0, restart=restart, precond=precond)
 
     def advance(self, sd, data: dict, c0, n_steps: int, accumulation, source=None, method: str = "bicgstab",
-                precond: str = "amg", rtol: float = 1e-12, maxit: int = 20000, raise_on_fail: bool = True):
+                precond: str = "amg", rtol: float = 1e-12, maxit: int = 20000, raise_on_fail: bool = True,
+                return_states: bool = False):
         """``n_steps`` implicit Euler steps from ``c0`` with ``accumulation`` = capacity x volume / dt per cell, all on
         the device, preconditioned by ``precond`` ("amg": one hierarchy for all steps; "jacobi"; "sweep": the
         substitution in flow order, built once per flux -- a preconditioner here, see ``solve``).  Returns (c_n, info);
         info["steps_done"] counts the converged steps.  ``context(sd).stats()`` has ``advdiff_iterations`` and
-        ``advdiff_precond_fallbacks`` (steps the AMG- or sweep-preconditioned solve left to Jacobi-GMRES)."""
+        ``advdiff_precond_fallbacks`` (steps the AMG- or sweep-preconditioned solve left to Jacobi-GMRES).
+
+        ``return_states``: returns (c_n, info, states) with states = c^0 .. c^N as (N + 1, Nc) -- what ``adjoint`` takes
+        --, produced by stepping one step at a time on the same assembly (the statistics are then those of the last
+        step; info["steps_done"] and info["iterations"] are summed; the slabs after a step that failed are NaN)."""
         self._assemble(sd, data, accumulation, None, source)
-        return self.context(sd).advdiff_advance(c0, n_steps, method=method, rtol=rtol, maxit=maxit, precond=precond,
-                                                raise_on_fail=raise_on_fail)
+        ctx = self.context(sd)
+        if not return_states:
+            return ctx.advdiff_advance(c0, n_steps, method=method, rtol=rtol, maxit=maxit, precond=precond,
+                                       raise_on_fail=raise_on_fail)
+        c = np.array(c0, dtype=np.float64, copy=True).ravel()
+        states = np.full((int(n_steps) + 1, ctx.nc), np.nan)
+        if c.shape != (ctx.nc,):
+            raise ValueError("c0 must have one entry per cell")
+        states[0] = c
+        total = {"steps_done": 0, "iterations": 0, "converged": True, "rel_residual": 0.0, "solve_ms": 0.0}
+        for n in range(int(n_steps)):
+            c, info = ctx.advdiff_advance(c, 1, method=method, rtol=rtol, maxit=maxit, precond=precond,
+                                          raise_on_fail=raise_on_fail)
+            total = dict(info, steps_done=total["steps_done"] + info["steps_done"],
+                         iterations=total["iterations"] + info["iterations"])
+            if info["steps_done"] != 1:
+                break
+            states[n + 1] = c
+        return c, total, states
+
+    def adjoint(self, sd, data: dict, n_steps: int, accumulation, loads, states, obs_cells=None, source=None,
+                want=("c0", "source", "bc_values"), method: str = "bicgstab", precond: str = "amg",
+                rtol: float = 1e-12, maxit: int = 20000, raise_on_fail: bool = True):
+        """The adjoint of ``advance``: the gradients of ``J = sum_{n=1..N} <loads[n-1], c^n[obs_cells]>`` through
+        ``n_steps`` = N steps ``S c^n = acc o c^{n-1} - b_ref + b_D + source`` (csrc/advdiff_adjoint.inc).  The system is
+        assembled exactly as ``advance`` assembles it; then, backwards in time, ``S^T lambda^n = g^n + acc o lambda^{n+1}``
+        is one transposed Krylov solve per step, preconditioned by ``precond`` ("amg": one hierarchy of S^T for all steps;
+        "jacobi"), with the fallbacks of ``advance``.
+
+        ``loads``: (N, n_obs); ``obs_cells``: n_obs cell indices without repeats, or None (every cell in order);
+        ``states``: c^0 .. c^N as (N + 1, Nc) -- ``advance(..., return_states=True)`` -- or None.  With
+        ``y^n_f = lambda^n[p] - lambda^n[m]`` (p / m the cells of ``cell_faces`` sign +1 / -1 at face f; a missing cell
+        contributes nothing) and ``Lambda = sum_n lambda^n``, ``want`` names
+
+        ================  ========  ======================================================================
+        "c0"              Nc        ``acc o lambda^1``
+        "source"          Nc        ``Lambda``
+        "accumulation"    Nc        ``sum_n lambda^n o (c^{n-1} - c^n)``                       (needs states)
+        "bc_values"       Nf        ``-(B_D^T + (rhs_neu + rhs_dir diag(w q))^T)(cell_faces Lambda)``; zero off the
+                                    boundary
+        "flux"            Nf        ``-w sum_n y^n_f cup^n_f``, cup the upwind value: upstream ``c^n`` on interior
+                                    and outflow faces, ``bc_values`` on a Dirichlet inflow face, 0 on a Neumann face;
+                                    the derivative at a fixed upstream side                   (needs states)
+        "flux_scale"      float     ``(1/w) sum_f q_f grad_flux_f``                            (needs states)
+        "conductivity"    3,3,Nc    ``sum_e zw_f dt_f/dK_rs(c)``, ``zw_f = -sum_n y^n_f w^n_f`` with the face weight
+                                    ``w^n_f`` and the two-point ``dt_f/dK`` of ``adjoint_flow``  (needs states)
+        "multipliers"     N,Nc      every ``lambda^n``
+        ================  ========  ======================================================================
+
+        "conductivity" has the meaning ``grad_perm`` has in ``adjoint_flow``: it is exact for a TPFA diffusion; for MPFA
+        it is the two-point product rule of ``AdTpfaFlux``, NOT the derivative of the MPFA matrices.  All other gradients
+        are exact for both schemes.  ``grads["flux"]`` is what ``Mpfa.adjoint_flow(..., grad_flux=grads["flux"])`` /
+        ``Tpfa.adjoint_flow`` of the flow problem that produced ``darcy_flux`` takes: the chain ends at the permeability
+        of the flow.
+
+        Returns (grads, info); info["steps_done"] counts the accepted steps; a step that does not converge leaves the
+        gradients zero.  Afterwards the handle holds no assembled system.  ``context(sd).stats()`` has
+        ``advdiff_adjoint_*``."""
+        self._assemble(sd, data, accumulation, None, source)
+        try:
+            return self.context(sd).advdiff_adjoint(n_steps, loads, states=states, obs_cells=obs_cells, want=want,
+                                                    method=method, rtol=rtol, maxit=maxit, precond=precond,
+                                                    raise_on_fail=raise_on_fail)
+        except _lib.PorefvError as e:
+            if e.status == 4:
+                raise ValueError(e.message) from None
+            raise
 
     def total_flux(self, sd, data: dict, c) -> np.ndarray:
         """Total face flux of the transported quantity for the state ``c``, with the flux and boundary values of the

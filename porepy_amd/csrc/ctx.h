@@ -404,6 +404,11 @@ struct pfv_ctx_impl {
   Buf<double> adv_acc, adv_src, adv_c, adv_keep, adv_rhs, adv_diag, adv_bref;
   bool have_adv_acc = false, have_adv_src = false;
   int64_t advdiff_zero_diag = -1;    // first row of S with a zero or NaN diagonal (-1: none)
+  // the adjoint of the step (pfv_advdiff_adjoint, advdiff_adjoint.inc): ada_lam / ada_keep the multiplier between the
+  // steps and before a step; ada_rhs the right-hand side -- with fa_valT the active system while the call runs; ada_sA /
+  // ada_sB two slabs of states staged from the host; the accumulators Lambda [nc], grad_accumulation [nc], sum y cup
+  // [nf], zw [nf]; ada_mult the multipliers [N][nc]; ada_work: Y [nf] | gb [nf] | partial sums | total
+  Buf<double> ada_lam, ada_keep, ada_rhs, ada_sA, ada_sB, ada_Lam, ada_gacc, ada_sq, ada_zw, ada_mult, ada_work;
 
   // ---- flow-ordered sweep (sweep.inc): levels of the flux graph of the transport / advection-diffusion system -----
   std::unique_ptr<Sweep> sweep;      // the order and what it was built from (nullptr / !valid: none)

@@ -25,6 +25,7 @@ static int rccl_exchange_halo(void* user, double* d_x, void* stream);  // rccl_h
 #include "advdiff.inc"
 #include "sweep.inc"
 #include "flow_adjoint.inc"
+#include "advdiff_adjoint.inc"
 
 namespace pfv {
 #ifndef PFV_EMULATE
@@ -1047,6 +1048,10 @@ struct StepLoop {  // what differs between the two
   bool jacobi_unless_sweep;  // the transport matrix is one-sided: any other choice on the handle is replaced by Jacobi
   bool jacobi_fallback;      // a step the AMG- or sweep-preconditioned solve gives up on: again with Jacobi-GMRES
 };
+struct StepHooks {  // what the adjoint loop (pfv_advdiff_adjoint) adds; the forward calls pass none
+  std::function<void(int)> rhs;    // instead of StepLoop::step_rhs: the right-hand side of step `step` from the state
+  std::function<void(int)> after;  // after an accepted step, the state holding its solution
+};
 struct StepTotals {
   bool ran = false;  // the checks passed: the totals below are to be written to the statistics
   int64_t iterations = 0, gmres_retries = 0, precond_fallbacks = 0, direct = 0, direct_fallbacks = 0;
@@ -1060,12 +1065,13 @@ struct StepTotals {
 // pfv_last_error reports, whatever the epilogue does.
 static pfv_status advance_steps(pfv_ctx* h, const StepLoop& L, const std::function<void()>& checks, int n_steps,
                                 int method, double rtol, int maxit, double* c, int32_t* steps_done,
-                                pfv_solve_info* last, StepTotals& tot) {
+                                pfv_solve_info* last, StepTotals& tot, const StepHooks* hooks = nullptr) {
   if (steps_done) *steps_done = 0;
   std::unique_ptr<pfv::Timer> tm;
   pfv_status st = guarded(h, [&] {
     checks();
-    vec_in(h, (h->*L.state).ensure((size_t)h->nc), c, (size_t)h->nc);
+    if (c) vec_in(h, (h->*L.state).ensure((size_t)h->nc), c, (size_t)h->nc);
+    else pfv::be_memset((h->*L.state).ensure((size_t)h->nc), 0, sizeof(double) * (size_t)h->nc, h->stream);  // (hooks)
     tm = std::make_unique<pfv::Timer>();
     tm->start(h->stream);
   });
@@ -1086,7 +1092,8 @@ static pfv_status advance_steps(pfv_ctx* h, const StepLoop& L, const std::functi
   };
   for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
     st = guarded(h, [&] {
-      L.step_rhs(*h, state.p);
+      if (hooks && hooks->rhs) hooks->rhs(step);
+      else L.step_rhs(*h, state.p);
       if (keep_state) pfv::be_d2d(keep.ensure((size_t)h->nc), state.p, nbytes, h->stream);
     });
     if (st != PFV_OK) break;
@@ -1110,6 +1117,7 @@ static pfv_status advance_steps(pfv_ctx* h, const StepLoop& L, const std::functi
       h->precond = precond;
     }
     if (last) *last = info;
+    if (st == PFV_OK && hooks && hooks->after) st = guarded(h, [&] { hooks->after(step); });
     if (st == PFV_OK && steps_done) ++*steps_done;
   }
   h->vectors_on_device = caller_on_device;
@@ -1118,7 +1126,7 @@ static pfv_status advance_steps(pfv_ctx* h, const StepLoop& L, const std::functi
   const pfv_status st2 = guarded(h, [&] {
     tot.ms = tm->stop(h->stream);
     tm.reset();
-    vec_out(h, c, state.p, (size_t)h->nc);
+    if (c) vec_out(h, c, state.p, (size_t)h->nc);
     pfv::be_sync(h->stream);
   });
   return step_status(h, st, err, st2);
@@ -2833,6 +2841,205 @@ pfv_status pfv_advdiff_face_flux(pfv_ctx* h, const double* c, double* out) {
     vec_out(h, out, d_out, nf);
     pfv::be_sync(s);  // (the staging buffer is freed on return)
   });
+}
+
+// ---- the adjoint of the advection-diffusion step (advdiff_adjoint.inc) ---------------------------------------------
+// The checks and the set-up run as the `checks` of advance_steps and end with (pat_A, S^T, diag, ada_rhs) as the active
+// system; the loop is advance_steps itself -- the state is lambda, step `step` is n = N - step --, with the right-hand
+// side and the two accumulation passes as its hooks; the products that need the sums over the steps follow the loop.
+pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int32_t* obs_cells, const double* loads,
+                               const double* states, int method, double rtol, int maxit, double* grad_c0,
+                               double* grad_source, double* grad_bc_values, double* grad_accumulation,
+                               double* grad_flux, double* grad_flux_scale, double* grad_conductivity,
+                               double* multipliers_out, int32_t* steps_done, pfv_solve_info* last) {
+  static const StepLoop loop{&pfv_ctx::ada_lam, &pfv_ctx::ada_keep, nullptr, false, true};
+  const int none = 0x7f7f7f7f;
+  const int N = n_steps;
+  const bool want_sq = grad_flux || grad_flux_scale, want_zw = grad_conductivity != nullptr;
+  const bool want_Lam = grad_source || grad_bc_values;
+  const bool face_pass = want_sq || want_zw, cell_pass = want_Lam || grad_accumulation || multipliers_out;
+  bool activated = false, on_dev = false;
+  size_t nc = 0, nf = 0;
+  int32_t *first = nullptr, *last_hf = nullptr, *ecell = nullptr;
+  const int32_t* slot = nullptr;
+  const double *acc = nullptr, *cn = nullptr, *cprev = nullptr;
+  std::unique_ptr<pfv::Timer> whole;
+  std::vector<std::unique_ptr<pfv::Timer>> pass_tm;
+  double pass_ms = 0.0;
+  int32_t done = 0;
+  StepTotals tot;
+  StepHooks hooks;
+  hooks.rhs = [&](int step) {
+    const int n = N - step;
+    pfv::pfv_ctx_impl& cx = *h;
+    if (states && (face_pass || grad_accumulation)) {  // c^n and c^{n-1}: in place on the device, else one slab per step
+      if (on_dev) {
+        cn = states + (size_t)n * nc;
+        cprev = states + (size_t)(n - 1) * nc;
+      } else if (grad_accumulation) {  // ada_sA holds c^n (staged by the step before, or ahead of the loop)
+        be_h2d(cx.ada_sB.p, states + (size_t)(n - 1) * nc, sizeof(double) * nc, cx.stream);
+        cn = cx.ada_sA.p;
+        cprev = cx.ada_sB.p;
+      } else {
+        be_h2d(cx.ada_sA.p, states + (size_t)n * nc, sizeof(double) * nc, cx.stream);
+        cn = cx.ada_sA.p;
+      }
+    }
+    pfv::advdiff_adjoint_rhs(cx, slot, cx.aj_loads.p + (size_t)(n - 1) * (size_t)n_obs, acc, cx.ada_lam.p, cx.ada_rhs.p);
+  };
+  hooks.after = [&](int step) {
+    const int n = N - step;
+    pfv::pfv_ctx_impl& cx = *h;
+    pass_tm.emplace_back(std::make_unique<pfv::Timer>());
+    pfv::Timer& tm = *pass_tm.back();
+    tm.start(cx.stream);
+    if (face_pass)
+      pfv::advdiff_adjoint_faces(cx, first, last_hf, ecell, cx.adv_q.p, cx.adv_bc.p, cx.ada_lam.p, cn,
+                                 want_sq ? cx.ada_sq.p : nullptr, want_zw ? cx.ada_zw.p : nullptr);
+    if (cell_pass)
+      pfv::advdiff_adjoint_cells(cx, cx.ada_lam.p, cprev, cn, want_Lam ? cx.ada_Lam.p : nullptr,
+                                 grad_accumulation ? cx.ada_gacc.p : nullptr,
+                                 multipliers_out ? cx.ada_mult.p + (size_t)(n - 1) * nc : nullptr);
+#ifdef PFV_EMULATE
+    pass_ms += tm.stop(cx.stream);
+#else
+    tm.mark(cx.stream);  // (read after the loop: the step adds no host read)
+#endif
+    if (states && !on_dev && grad_accumulation) cx.ada_sA.swap(cx.ada_sB);
+    ++done;
+  };
+  pfv_status st = advance_steps(h, loop, [&] {
+    advdiff_supported(h);
+    require(advdiff_is_active(h), "pfv_advdiff_assemble first (the advection-diffusion system must be the active one)");
+    require(n_steps >= 0, "n_steps must not be negative");
+    require(method == PFV_SOLVE_BICGSTAB || method == PFV_SOLVE_GMRES,
+            "method must be PFV_SOLVE_BICGSTAB or PFV_SOLVE_GMRES (the matrix is not symmetric)");
+    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
+    if (h->precond == PFV_PRECOND_SWEEP)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "PFV_PRECOND_SWEEP is not covered by the advection-diffusion adjoint: the "
+                                            "substitution in reverse flow order on S^T is a later pull request; select "
+                                            "PFV_PRECOND_AMG or PFV_PRECOND_JACOBI");
+    require(h->precond == PFV_PRECOND_JACOBI || h->precond == PFV_PRECOND_AMG,
+            "the advection-diffusion adjoint takes PFV_PRECOND_JACOBI or PFV_PRECOND_AMG");
+    require(states || !grad_accumulation, "grad_accumulation needs states (c^0 .. c^N)");
+    require(states || !grad_flux, "grad_flux needs states (c^0 .. c^N)");
+    require(states || !grad_flux_scale, "grad_flux_scale needs states (c^0 .. c^N)");
+    require(states || !grad_conductivity, "grad_conductivity needs states (c^0 .. c^N)");
+    require(loads || n_steps == 0 || n_obs == 0, "loads is required");
+    if (!h->tpfa_mode && !h->rows_complete)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "the advection-diffusion adjoint does not cover a partial discretization "
+                                            "(the rows of the other faces are zero)");
+    if (h->pat_A.nnz >= (int64_t(1) << 31) || h->pat_bound.nnz >= (int64_t(1) << 31))
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "the advection-diffusion adjoint needs patterns of div flux and bound_flux "
+                                            "below 2^31 entries");
+    auto s = h->stream;
+    nc = (size_t)h->nc;
+    nf = (size_t)h->nf;
+    const size_t ncf = (size_t)h->ncf;
+    on_dev = h->vectors_on_device;
+    int32_t robin = none, internal = none;
+    pfv::advdiff_adjoint_check_faces(*h, robin, internal);
+    if (robin != none)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "face " + std::to_string(robin) + " carries a Robin condition: the "
+                                            "advection-diffusion adjoint covers Dirichlet and Neumann faces");
+    if (internal != none)
+      throw pfv::Error(PFV_ERR_UNSUPPORTED, "face " + std::to_string(internal) + " is flagged PFV_BC_INTERNAL: the "
+                                            "advection-diffusion adjoint does not cover internal boundaries");
+    adjoint_take_loads(h, 1, n_steps, n_obs, obs_cells, loads);
+    adjoint_take_slots(h, n_obs, obs_cells);
+    slot = obs_cells ? h->aj_slot.p : nullptr;
+    acc = h->have_adv_acc ? h->adv_acc.p : nullptr;
+    whole = std::make_unique<pfv::Timer>();
+    whole->start(s);
+    // ---- what belongs to the patterns and the grid: the half-face lists, the column maps, the transposed positions
+    int32_t* half = h->fa_half.ensure(2 * nf + ncf);
+    first = half;
+    last_hf = half + nf;
+    ecell = half + 2 * nf;
+    pfv::flow_adjoint_half_faces(*h, first, last_hf, ecell);
+    pfv::upwind_face_cells(*h);
+    const size_t nnzA = (size_t)std::max<int64_t>(h->pat_A.nnz, 1);
+    if (grad_bc_values && !h->have_cmap) {
+      pfv::colmap_build(*h, h->pat_flux, h->cmap_flux);
+      pfv::colmap_build(*h, h->pat_bound, h->cmap_bound);
+      h->have_cmap = true;
+      ++h->stats.flow_adjoint_map_builds;
+    }
+    if (!h->have_tpos_A) {
+      pfv::sweep_transpose_positions(*h, h->pat_A, h->tpos_A.ensure(nnzA), "div flux");
+      h->have_tpos_A = true;
+    }
+    // ---- the accumulators and the slabs
+    auto zeros = [&](pfv::Buf<double>& b, size_t n) { pfv::be_memset(b.ensure(std::max<size_t>(n, 1)), 0, sizeof(double) * n, s); };
+    h->ada_rhs.ensure(nc);
+    if (want_Lam) zeros(h->ada_Lam, nc);
+    if (grad_accumulation) zeros(h->ada_gacc, nc);
+    if (want_sq) zeros(h->ada_sq, nf);
+    if (want_zw) zeros(h->ada_zw, nf);
+    if (multipliers_out) zeros(h->ada_mult, (size_t)N * nc);
+    if (states && !on_dev && (face_pass || grad_accumulation)) {
+      h->ada_sA.ensure(nc);
+      h->ada_sB.ensure(nc);
+      if (grad_accumulation && N > 0) be_h2d(h->ada_sA.p, states + (size_t)N * nc, sizeof(double) * nc, s);  // c^N
+    }
+    // ---- S^T on the pattern of S: the active system of all steps (with AMG: one hierarchy, set up by the first)
+    double* valT = h->fa_valT.ensure(nnzA);
+    pfv::sweep_transpose_values(*h, h->pat_A.nnz, h->tpos_A.p, h->val[PFV_MAT_ADVDIFF_SYSTEM].p, valT);
+    h->active.valid = false;
+    h->have_advdiff = false;  // (the call ends without an active system: pfv_advdiff_assemble is asked for)
+    activated = true;
+    values_changed(h, Windows::keep);
+    activate(h, h->pat_A, valT, h->adv_diag.p, h->ada_rhs.p, h->nc, 1, true);
+  }, n_steps, method, rtol, maxit, nullptr, nullptr, last, tot, &hooks);
+  if (steps_done) *steps_done = done;
+  if (!tot.ran) return st;
+  const std::string err = h->err;
+  const pfv_status st2 = guarded(h, [&] {
+    pfv::pfv_ctx_impl& cx = *h;
+    auto s = cx.stream;
+    if (activated) cx.active.valid = false;
+#ifndef PFV_EMULATE
+    for (auto& t : pass_tm) pass_ms += t->elapsed_after_sync();
+#endif
+    pass_tm.clear();
+    if (st == PFV_OK) {
+      const size_t ncf = (size_t)cx.ncf;
+      pfv::Buf<double> inv_, gk_;
+      double* work = cx.ada_work.ensure(2 * nf + pfv::kAdaParts + 1);
+      double *Y = work, *gb = work + nf, *parts = work + 2 * nf, *total = parts + pfv::kAdaParts;
+      if (grad_bc_values) {
+        pfv::advdiff_adjoint_face_sum(cx, first, last_hf, ecell, cx.ada_Lam.p, Y);
+        pfv::spmv_transposed(cx, cx.cmap_bound, cx.val[PFV_MAT_BOUND_FLUX].p, Y, gb);
+        pfv::advdiff_adjoint_grad_bc(cx, cx.adv_q.p, cx.adv_w, Y, gb);
+      }
+      double* gk = nullptr;
+      if (grad_conductivity) {
+        gk = gk_.ensure(9 * nc);
+        pfv::flow_adjoint_grad_perm(cx, first, last_hf, cx.ada_zw.p, inv_.ensure(std::max<size_t>(ncf, 1)), gk);
+      }
+      if (want_sq) pfv::advdiff_adjoint_flux_out(cx, cx.adv_q.p, cx.adv_w, cx.ada_sq.p, parts, total);
+      if (grad_c0) pfv::advdiff_adjoint_grad_c0(cx, acc, cx.ada_lam.p, cx.ada_rhs.p);
+      h->stats.advdiff_adjoint_ms = whole->stop(s);
+      if (grad_c0) vec_out(h, grad_c0, cx.ada_rhs.p, nc);
+      if (grad_source) vec_out(h, grad_source, cx.ada_Lam.p, nc);
+      if (grad_bc_values) vec_out(h, grad_bc_values, gb, nf);
+      if (grad_accumulation) vec_out(h, grad_accumulation, cx.ada_gacc.p, nc);
+      if (grad_flux) vec_out(h, grad_flux, cx.ada_sq.p, nf);
+      if (grad_flux_scale) be_d2h(grad_flux_scale, total, sizeof(double), s);  // (host memory, as the scale itself is)
+      if (gk) vec_out(h, grad_conductivity, gk, 9 * nc);
+      if (multipliers_out) vec_out(h, multipliers_out, cx.ada_mult.p, (size_t)N * nc);
+    } else {
+      h->stats.advdiff_adjoint_ms = whole->stop(s);
+    }
+    pfv::be_sync(s);  // (the staging buffers are freed on return)
+    whole.reset();
+  });
+  h->stats.advdiff_adjoint_steps = done;
+  h->stats.advdiff_adjoint_iterations = tot.iterations;
+  h->stats.advdiff_adjoint_gmres_retries = tot.gmres_retries;
+  h->stats.advdiff_adjoint_precond_fallbacks = tot.precond_fallbacks;
+  h->stats.advdiff_adjoint_accumulate_ms = pass_ms;
+  return step_status(h, st, err, st2);
 }
 
 pfv_status pfv_mpsa_set_params(pfv_ctx* h, const double* stiffness_99n, const double* cell_volumes,

@@ -236,6 +236,10 @@ typedef struct {
   int64_t advdiff_adjoint_precond_fallbacks; /* ... steps whose AMG-preconditioned solve did not converge and were
                                      solved again with Jacobi-GMRES */
   double advdiff_adjoint_accumulate_ms; /* ... HIP-event time of the face pass and the cell pass, summed over the steps */
+  int64_t flow_adjoint_exact_calls; /* pfv_flow_adjoint_exact calls on this handle that ran the interaction-region pass */
+  int64_t flow_adjoint_exact_map_builds; /* times the cell -> sub-cell map was built (kept with the sub-cell topology) */
+  double flow_adjoint_exact_map_ms; /* last pfv_flow_adjoint / pfv_flow_adjoint_exact: that map (0: kept or not needed) */
+  double flow_adjoint_exact_ms;     /* ... the interaction-region kernel and the cell sum of grad_perm_exact (0: none) */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -975,7 +979,9 @@ pfv_status pfv_transport_adjoint_nl_multi(pfv_ctx* h, const double* q, int fluxf
  * on Neumann faces).  What grad_perm means depends on the discretization.  pfv_tpfa_discretize: the exact gradient of
  * the discrete problem.  pfv_mpfa_discretize: grad_source, grad_bc_values and mu are exact; grad_perm is the two-point
  * product rule of the reference's AdTpfaFlux -- the same approximation pfv_mpfa_ad_flux_system makes for its Jacobian
- * --, NOT the derivative of the MPFA matrices.  The gradient with respect to the vector source is not formed.
+ * --, NOT the derivative of the MPFA matrices: that derivative is the grad_perm_exact of pfv_flow_adjoint_exact below
+ * (on a K-orthogonal grid the two agree; on tetrahedra with a full tensor they do not, and the entries K_rs, r != s,
+ * have no meaningful two-point derivative).  The gradient with respect to the vector source is not formed.
  *   p (Nc) is the forward solution: the caller's responsibility, not checked against the system.  bc_values (Nf) and
  * vector_source (per cell as pfv_mpfa_assemble takes it, or NULL) as in the forward solve.  mu_out (Nc), grad_perm,
  * grad_bc_values and grad_source may each be NULL.  All vectors follow pfv_set_vectors_on_device: a grad_flux left in
@@ -998,6 +1004,27 @@ pfv_status pfv_flow_adjoint(pfv_ctx* h, const double* p, const double* bc_values
                             const double* load_flux, const double* load_pressure, int method, double rtol, int maxit,
                             int restart, double* mu_out, double* grad_perm, double* grad_bc_values,
                             double* grad_source, pfv_solve_info* info);
+
+/* The same call -- the same checks and refusals, the same solve, the same bits in every output of pfv_flow_adjoint --
+ * with one more output from the same mu (csrc/mpfa_adjoint.inc):
+ *     grad_perm_exact [(3,3,Nc)]   d/dK of z^T (T p + B bc + V g) at fixed p, bc, g: the exact gradient of J with respect
+ *                                  to the permeability of the discrete problem, layout of perm_33n, all nine entries
+ *                                  independent (on a 2-D grid only the 2 x 2 block is non-zero); NULL: not formed.
+ * pfv_mpfa_discretize: K enters the interaction region of a node only through nK_h = n_h^T K_c.  One pass over the
+ * regions (one per wavefront, the condensed system of the discretization set up afresh in LDS, ONE pivoted inverse)
+ * solves the region for the actual p, bc and g (u_j = g_j - gamma_j per sub-cell), solves its transposed system for the
+ * load -z_f(s) omega_{h*(s)} of the sub-face fluxes (nu), and leaves per sub-half-face h = (j, l) of cell c
+ *     ( -z_f(s) [h = h*(s)] - nu_l sgn_h [row l not Dirichlet] ) n_h[r] u_j[b]        in grad[r][b][c];
+ * the sub-cells of a cell are summed by a second kernel in the fixed order of a cell -> sub-cell map kept with the
+ * sub-cell topology (no floating-point atomics; two calls give the same bits).  The table rows and sub-face records of
+ * the discretization are not touched.  pfv_tpfa_discretize: grad_perm_exact = grad_perm.
+ *   Further statuses: PFV_ERR_UNSUPPORTED names the node whose interaction region does not fit the LDS (found before the solve);
+ * PFV_ERR_SINGULAR names the node as pfv_mpfa_discretize does.  A refused call writes no output.
+ * pfv_stats: flow_adjoint_exact_*. */
+pfv_status pfv_flow_adjoint_exact(pfv_ctx* h, const double* p, const double* bc_values, const double* vector_source,
+                                  const double* load_flux, const double* load_pressure, int method, double rtol,
+                                  int maxit, int restart, double* mu_out, double* grad_perm, double* grad_perm_exact,
+                                  double* grad_bc_values, double* grad_source, pfv_solve_info* info);
 
 /* ---- Advection-diffusion step on the device (csrc/advdiff.inc) ---------------------------------------------------
  * One handle carries the transport keyword: its diffusion discretization (pfv_mpfa_discretize or pfv_tpfa_discretize

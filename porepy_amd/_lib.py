@@ -52,7 +52,8 @@ EXPORTS = [
     "pfv_advdiff_assemble", "pfv_advdiff_advance", "pfv_advdiff_face_flux", "pfv_resident_flux",
     "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl", "pfv_transport_advance_nl_multi",
     "pfv_transport_advance_react", "pfv_transport_adjoint_multi", "pfv_transport_adjoint_react",
-    "pfv_transport_adjoint_nl", "pfv_transport_adjoint_nl_multi", "pfv_flow_adjoint", "pfv_advdiff_adjoint",
+    "pfv_transport_adjoint_nl", "pfv_transport_adjoint_nl_multi", "pfv_flow_adjoint", "pfv_flow_adjoint_exact",
+    "pfv_advdiff_adjoint",
 ]
 
 
@@ -105,7 +106,9 @@ class Stats(C.Structure):
                 ("flow_adjoint_gradient_ms", C.c_double),
                 ("advdiff_adjoint_ms", C.c_double), ("advdiff_adjoint_steps", C.c_int64),
                 ("advdiff_adjoint_iterations", C.c_int64), ("advdiff_adjoint_gmres_retries", C.c_int64),
-                ("advdiff_adjoint_precond_fallbacks", C.c_int64), ("advdiff_adjoint_accumulate_ms", C.c_double)]
+                ("advdiff_adjoint_precond_fallbacks", C.c_int64), ("advdiff_adjoint_accumulate_ms", C.c_double),
+                ("flow_adjoint_exact_calls", C.c_int64), ("flow_adjoint_exact_map_builds", C.c_int64),
+                ("flow_adjoint_exact_map_ms", C.c_double), ("flow_adjoint_exact_ms", C.c_double)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -355,6 +358,9 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_flow_adjoint.argtypes = [_h, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp,
                                      _dp, C.POINTER(SolveInfo)]
     lib.pfv_flow_adjoint.restype = C.c_int
+    lib.pfv_flow_adjoint_exact.argtypes = [_h, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp,
+                                           _dp, _dp, _dp, C.POINTER(SolveInfo)]
+    lib.pfv_flow_adjoint_exact.restype = C.c_int
     lib.pfv_advdiff_assemble.argtypes = [_h, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pfv_advdiff_assemble.restype = C.c_int
     lib.pfv_advdiff_advance.argtypes = [_h, C.c_int, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(C.c_int32),
@@ -1928,7 +1934,7 @@ class Context:
         return grads, out
 
     # ---- the adjoint of the flow solve (include/porefv.h: pfv_flow_adjoint) ----
-    FLOW_ADJOINT_GRADIENTS = ("permeability", "bc_values", "source", "multiplier")
+    FLOW_ADJOINT_GRADIENTS = ("permeability", "bc_values", "source", "multiplier", "permeability_exact")
 
     def flow_adjoint(self, p, bc_values, vector_source=None, load_flux=None, load_pressure=None,
                      want=("permeability", "bc_values", "source"), method="bicgstab", rtol=1e-12, maxit=20000, restart=0,
@@ -1937,8 +1943,10 @@ class Context:
         (Nf) and ``load_pressure`` = dJ/dp (Nc), at least one of them, become the gradients named in ``want`` --
         "permeability" (3, 3, Nc), "bc_values" (Nf), "source" (Nc) and "multiplier" (Nc, the solution of the transposed
         system) -- at the cost of one transposed solve.  ``p`` is the forward solution, ``bc_values`` / ``vector_source``
-        as in ``assemble``.  For a TPFA discretization the permeability gradient is exact; for MPFA it is the two-point
-        product rule of ``ad_flux_system``, not the derivative of the MPFA matrices.  Returns (grads, info).  A solve that
+        as in ``assemble``.  For a TPFA discretization the permeability gradient is exact; for MPFA "permeability" is the
+        two-point product rule of ``ad_flux_system``, not the derivative of the MPFA matrices: that one is
+        "permeability_exact" (3, 3, Nc; pfv_flow_adjoint_exact: one more pass over the interaction regions, from the same
+        multiplier; equal to "permeability" for TPFA).  Returns (grads, info).  A solve that
         does not converge leaves the gradients zero.  ``device``: every vector argument is the address of a device
         buffer and the wanted outputs go to the addresses in ``out_ptrs`` (name -> address); grads is then empty."""
         code = {"cg": SOLVE_CG, "bicgstab": SOLVE_BICGSTAB, "gmres": SOLVE_GMRES}[method]
@@ -1952,7 +1960,8 @@ class Context:
         k3, pv = self._vec(vector_source, nvs, "vector_source", device)
         k4, pq = self._vec(load_flux, self.nf, "load_flux", device)
         k5, pl = self._vec(load_pressure, self.nc, "load_pressure", device)
-        shapes = {"permeability": (3, 3, self.nc), "bc_values": (self.nf,), "source": (self.nc,), "multiplier": (self.nc,)}
+        shapes = {"permeability": (3, 3, self.nc), "bc_values": (self.nf,), "source": (self.nc,), "multiplier": (self.nc,),
+                  "permeability_exact": (3, 3, self.nc)}
         if device:
             grads = {}
             outs = {name: C.cast(int((out_ptrs or {})[name]), _dp) for name in want}
@@ -1964,9 +1973,15 @@ class Context:
         if device:
             self._dev(True)
         try:
-            st = self.lib.pfv_flow_adjoint(self._h, pp_, pb, pv, pq, pl, code, float(rtol), int(maxit), int(restart),
-                                           outs.get("multiplier"), outs.get("permeability"), outs.get("bc_values"),
-                                           outs.get("source"), C.byref(info))
+            if "permeability_exact" in want:
+                st = self.lib.pfv_flow_adjoint_exact(self._h, pp_, pb, pv, pq, pl, code, float(rtol), int(maxit),
+                                                     int(restart), outs.get("multiplier"), outs.get("permeability"),
+                                                     outs.get("permeability_exact"), outs.get("bc_values"),
+                                                     outs.get("source"), C.byref(info))
+            else:
+                st = self.lib.pfv_flow_adjoint(self._h, pp_, pb, pv, pq, pl, code, float(rtol), int(maxit), int(restart),
+                                               outs.get("multiplier"), outs.get("permeability"), outs.get("bc_values"),
+                                               outs.get("source"), C.byref(info))
         finally:
             if device:
                 self._dev(False)

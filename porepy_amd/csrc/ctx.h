@@ -393,6 +393,12 @@ struct pfv_ctx_impl {
   Buf<int32_t> tpos_A;
   Buf<int32_t> fa_half;  // the call's half-face lists: first [nf] | last [nf] | cell of every cell_faces entry [ncf]
   Buf<double> fa_valT, fa_rhs, fa_in, fa_mu;
+  // the exact permeability gradient (pfv_flow_adjoint_exact, mpfa_adjoint.inc): the cell -> sub-cell map (adj_cptr
+  // [nc + 1], adj_csub [nh / nd]), a property of the sub-cell topology kept under its digest adj_map_key (0: none);
+  // adj_sub: the regions' contributions per sub-cell [nh / nd][nd^2]
+  Buf<int32_t> adj_cptr, adj_csub;
+  unsigned long long adj_map_key = 0;
+  Buf<double> adj_sub;
 
   // ---- advection-diffusion (advdiff.inc): S = diag(acc) + div flux_D + w div diag(q) U on pat_A -------------------
   bool have_advdiff = false;         // val[PFV_MAT_ADVDIFF_SYSTEM], adv_diag, adv_rhs hold a system of the discretization

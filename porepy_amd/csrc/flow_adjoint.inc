@@ -11,7 +11,8 @@
 // with w_f = d q_f / d t_f as ad_flux.inc defines it and the half-face derivative of tpfa.inc
 // (tpfa_transmissibility_ad).  For a TPFA discretization grad_perm is the exact gradient of the discrete problem; for
 // MPFA it is the two-point product rule of the reference's AdTpfaFlux -- the approximation ad_flux_system makes for its
-// Jacobian --, NOT the derivative of the MPFA matrices.
+// Jacobian --, NOT the derivative of the MPFA matrices: that one is grad_perm_exact of pfv_flow_adjoint_exact
+// (mpfa_adjoint.inc), formed from the same mu and z.
 //
 // The transposed products gather over a column map of the CSR pattern (entries sorted by (column, row)); nothing here
 // uses floating-point atomics, every sum has a fixed order.

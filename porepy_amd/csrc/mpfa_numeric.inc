@@ -242,10 +242,13 @@ PFV_FN void node_carve(char* lds, int n, int ld, int nh, int nd, NodeLds& L) {
 }
 
 // classification, geometry, coefficient tables, the sub-face records, and the row-scaled matrix A in
-// LDS (ND is a template parameter so that the small per-sub-cell matrices live in registers)
-template <int ND>
+// LDS (ND is a template parameter so that the small per-sub-cell matrices live in registers).
+// ADJ (mpfa_adjoint.inc): the same geometry and coefficients for the exact permeability gradient -- nothing is written
+// outside the LDS block (no table row, no sub-face record), and the sub-cell's D^-1 (adj_di, [j][i][k]) and the
+// sub-half-faces' normals n_h (adj_nrm, [hh][i]) are kept in LDS beside the rest.
+template <int ND, bool ADJ = false>
 PFV_FN void node_setup(const NodeArgs& a, const WaveCtx& w, const NodeLds& L, int v, int h0, int nh,
-                              int f0, int n, int ld, int64_t t0) {
+                              int f0, int n, int ld, int64_t t0, double* adj_di = nullptr, double* adj_nrm = nullptr) {
   constexpr int nd = ND;
   const int deg = nh / nd;
   const int ldt = (nh + 1) & ~1;
@@ -295,6 +298,8 @@ PFV_FN void node_setup(const NodeArgs& a, const WaveCtx& w, const NodeLds& L, in
       const double inn = 1.0 / (a.fn_ptr[f + 1] - a.fn_ptr[f]);
       double nrm[3];
       for (int i = 0; i < nd; ++i) nrm[i] = a.fnorm[i * nf + f] * inn;
+      if constexpr (ADJ)
+        for (int i = 0; i < nd; ++i) adj_nrm[(nd * j + k) * nd + i] = nrm[i];
       for (int b = 0; b < nd; ++b) {
         double t = 0.0;
         for (int i = 0; i < nd; ++i) t += nrm[i] * K[i][b];
@@ -307,11 +312,16 @@ PFV_FN void node_setup(const NodeArgs& a, const WaveCtx& w, const NodeLds& L, in
       }
     }
     if (!invert_small(nd, D, Di)) atomic_max_i32(a.st + 0, v + 1);
-    // e_j = D^-1 1: row n of the node's table
-    for (int i = 0; i < nd; ++i) {
-      double e = 0.0;
-      for (int k2 = 0; k2 < nd; ++k2) e += Di[i][k2];
-      a.tab[t0 + (int64_t)n * ldt + nd * j + i] = e;
+    if constexpr (ADJ) {
+      for (int i = 0; i < nd; ++i)
+        for (int k2 = 0; k2 < nd; ++k2) adj_di[(nd * j + i) * nd + k2] = Di[i][k2];
+    } else {
+      // e_j = D^-1 1: row n of the node's table
+      for (int i = 0; i < nd; ++i) {
+        double e = 0.0;
+        for (int k2 = 0; k2 < nd; ++k2) e += Di[i][k2];
+        a.tab[t0 + (int64_t)n * ldt + nd * j + i] = e;
+      }
     }
     for (int k = 0; k < nd; ++k) {
       const int hh = nd * j + k;
@@ -330,7 +340,8 @@ PFV_FN void node_setup(const NodeArgs& a, const WaveCtx& w, const NodeLds& L, in
       L.fsL[hh] = a.h_first[h];
       const bool isdir = L.type[l] == 1;
       for (int b = 0; b < nd; ++b) L.bg[(j * nd + k) * nd + b] = isdir ? 0.0 : sg * nK[k][b];
-      if (a.h_first[h]) {
+      if (a.h_first[h]) L.firstjk[l] = hh;
+      if constexpr (!ADJ) if (a.h_first[h]) {
         SfRec R;
         R.toff = t0;
         R.n = (uint8_t)n;
@@ -344,7 +355,6 @@ PFV_FN void node_setup(const NodeArgs& a, const WaveCtx& w, const NodeLds& L, in
           R.nk[k2] = k2 < nd ? nK[k][k2] : 0.0;
         }
         a.rec[L.sfid[l]] = R;
-        L.firstjk[l] = hh;
       }
     }
   }

@@ -25,6 +25,7 @@ static int rccl_exchange_halo(void* user, double* d_x, void* stream);  // rccl_h
 #include "advdiff.inc"
 #include "sweep.inc"
 #include "flow_adjoint.inc"
+#include "mpfa_adjoint.inc"
 #include "advdiff_adjoint.inc"
 
 namespace pfv {
@@ -337,6 +338,7 @@ pfv_status pfv_set_grid(pfv_ctx* h, int nd, int64_t nc, int64_t nf, int64_t nn, 
     h->win_for = h->win_rows_for = nullptr;
     h->have_topology = h->have_symbolic = h->have_numeric = h->have_system = false;
     h->topo_key = h->symb_key = 0;
+    h->adj_map_key = 0;
     h->win_sys_prebuilt = h->win_rows_prebuilt = false;
     h->biot_rows_complete = false;
     h->rows_complete = false;
@@ -4223,10 +4225,12 @@ pfv_status pfv_solve(pfv_ctx* h, int method, double rtol, int maxit, int restart
 
 // ---- the adjoint of the flow solve (flow_adjoint.inc).  Three parts: the checks, the maps, A^T and the right-hand side,
 // ending with (A^T, g_p + T^T g_q) as the active system; pfv_solve itself; the gradients from mu.
-pfv_status pfv_flow_adjoint(pfv_ctx* h, const double* p, const double* bc_values, const double* vector_source,
-                            const double* load_flux, const double* load_pressure, int method, double rtol, int maxit,
-                            int restart, double* mu_out, double* grad_perm, double* grad_bc_values,
-                            double* grad_source, pfv_solve_info* info) {
+// (grad_perm_exact: the additional output of pfv_flow_adjoint_exact, nullptr for pfv_flow_adjoint -- whose path through
+// this body is the one it always took)
+static pfv_status flow_adjoint_call(pfv_ctx* h, const double* p, const double* bc_values, const double* vector_source,
+                                    const double* load_flux, const double* load_pressure, int method, double rtol,
+                                    int maxit, int restart, double* mu_out, double* grad_perm, double* grad_perm_exact,
+                                    double* grad_bc_values, double* grad_source, pfv_solve_info* info) {
   if (info) *info = pfv_solve_info{};
   const int none = 0x7f7f7f7f;
   double *d_p = nullptr, *d_bc = nullptr, *d_gq = nullptr, *d_gp = nullptr, *d_vs = nullptr, *d_mu = nullptr;
@@ -4251,6 +4255,7 @@ pfv_status pfv_flow_adjoint(pfv_ctx* h, const double* p, const double* bc_values
     if (h->pat_flux.nnz >= (int64_t(1) << 31))
       throw pfv::Error(PFV_ERR_UNSUPPORTED, "the flow adjoint needs a flux pattern below 2^31 entries");
     require(!vector_source || h->filled[PFV_MAT_VECTOR_SOURCE], "vector_source matrix was skipped");
+    if (grad_perm_exact && !h->tpfa_mode) pfv::adj_check_lds(*h);  // (a region too large for the LDS: refused before the solve)
     auto s = h->stream;
     const size_t nf = (size_t)h->nf, nc = (size_t)h->nc, ncf = (size_t)h->ncf;
     vd = (int)(h->pat_vs.ncols / h->nc);
@@ -4348,19 +4353,40 @@ pfv_status pfv_flow_adjoint(pfv_ctx* h, const double* p, const double* bc_values
     auto s = h->stream;
     const size_t nf = (size_t)h->nf, nc = (size_t)h->nc, ncf = (size_t)h->ncf;
     pfv::Timer tm;
-    if (grad_perm || grad_bc_values) {
-      pfv::Buf<double> z_, zw_, inv_, gk_, gb_;
+    h->stats.flow_adjoint_exact_map_ms = h->stats.flow_adjoint_exact_ms = 0.0;
+    if (grad_perm || grad_bc_values || grad_perm_exact) {
+      pfv::Buf<double> z_, zw_, inv_, gk_, gb_, ge_;
       double* z = z_.ensure(nf);
       double* zw = zw_.ensure(nf);
+      // (for a TPFA discretization the two-point gradient is the exact one)
+      const bool two_point = grad_perm || (grad_perm_exact && h->tpfa_mode);
       tm.start(s);
       pfv::flow_adjoint_faces(*h, first, last, ecell, d_p, d_bc, d_vs, vd, d_gq, d_mu, z, zw);
       double* gk = nullptr;
-      if (grad_perm) {
+      if (two_point) {
         gk = gk_.ensure(9 * nc);
         pfv::flow_adjoint_grad_perm(*h, first, last, zw, inv_.ensure(std::max<size_t>(ncf, 1)), gk);
       }
       h->stats.flow_adjoint_gradient_ms = tm.stop(s);
-      if (gk) vec_out(h, grad_perm, gk, 9 * nc);
+      double* ge = nullptr;
+      if (grad_perm_exact && !h->tpfa_mode) {
+        const unsigned long long key = h->topo_key ? h->topo_key : pfv::topology_digest(*h);
+        if (h->adj_map_key == 0 || h->adj_map_key != key) {
+          tm.start(s);
+          h->adj_map_key = 0;
+          pfv::adj_cell_map(*h);
+          h->adj_map_key = key;
+          ++h->stats.flow_adjoint_exact_map_builds;
+          h->stats.flow_adjoint_exact_map_ms = tm.stop(s);
+        }
+        ge = ge_.ensure(9 * nc);
+        tm.start(s);
+        pfv::flow_adjoint_grad_perm_exact(*h, d_p, d_bc, d_vs, vd, z, ge);
+        h->stats.flow_adjoint_exact_ms = tm.stop(s);
+        ++h->stats.flow_adjoint_exact_calls;
+      }
+      if (grad_perm) vec_out(h, grad_perm, gk, 9 * nc);
+      if (grad_perm_exact) vec_out(h, grad_perm_exact, ge ? ge : gk, 9 * nc);
       if (grad_bc_values) {
         double* gb = gb_.ensure(nf);
         tm.start(s);
@@ -4374,6 +4400,22 @@ pfv_status pfv_flow_adjoint(pfv_ctx* h, const double* p, const double* bc_values
     if (grad_source) vec_out(h, grad_source, d_mu, nc);
     pfv::be_sync(s);
   });
+}
+
+pfv_status pfv_flow_adjoint(pfv_ctx* h, const double* p, const double* bc_values, const double* vector_source,
+                            const double* load_flux, const double* load_pressure, int method, double rtol, int maxit,
+                            int restart, double* mu_out, double* grad_perm, double* grad_bc_values,
+                            double* grad_source, pfv_solve_info* info) {
+  return flow_adjoint_call(h, p, bc_values, vector_source, load_flux, load_pressure, method, rtol, maxit, restart, mu_out,
+                           grad_perm, nullptr, grad_bc_values, grad_source, info);
+}
+
+pfv_status pfv_flow_adjoint_exact(pfv_ctx* h, const double* p, const double* bc_values, const double* vector_source,
+                                  const double* load_flux, const double* load_pressure, int method, double rtol,
+                                  int maxit, int restart, double* mu_out, double* grad_perm, double* grad_perm_exact,
+                                  double* grad_bc_values, double* grad_source, pfv_solve_info* info) {
+  return flow_adjoint_call(h, p, bc_values, vector_source, load_flux, load_pressure, method, rtol, maxit, restart, mu_out,
+                           grad_perm, grad_perm_exact, grad_bc_values, grad_source, info);
 }
 
 

@@ -899,12 +899,18 @@ class Mpfa:
         - ``"bc_values"`` (Nf): ``bound_flux^T z`` with ``z = grad_flux - cell_faces mu``; zero off the boundary;
         - ``"permeability"`` (3, 3, Nc), all nine entries independent: ``sum_f z_f w_f dt_f/dK_rs(c)`` with the two-point
           transmissibility derivative of ``DifferentiableTpfa`` and ``w_f = dq_f/dt_f`` of ``ad_flux_system``;
-        - ``"multiplier"`` (Nc): mu itself.
+        - ``"multiplier"`` (Nc): mu itself;
+        - ``"permeability_exact"`` (3, 3, Nc), all nine entries independent (2-D grids: the 2 x 2 block): the derivative
+          of the MPFA matrices themselves, ``d/dK z^T (flux p + bound_flux bc_values + vector_source g)`` at fixed p --
+          one more pass over the interaction regions from the same mu (pfv_flow_adjoint_exact).
 
-        ``"source"``, ``"bc_values"`` and mu are exact.  ``"permeability"`` is, for this MPFA discretization, the
+        ``"source"``, ``"bc_values"``, mu and ``"permeability_exact"`` are exact: the latter is the gradient to hand to
+        an optimiser that inverts for K.  ``"permeability"`` keeps its meaning: for this MPFA discretization the
         two-point product rule of the reference's ``AdTpfaFlux`` -- the same approximation ``ad_flux_system`` makes for
-        its Jacobian --, NOT the derivative of the MPFA matrices; ``Tpfa.adjoint_flow`` gives the exact gradient of its
-        discrete problem.  Robin and internal-boundary faces, conditions per sub-face, partial discretizations: status 5.
+        its Jacobian --, NOT the derivative of the MPFA matrices (the two agree on K-orthogonal grids; on tetrahedra with
+        a full tensor they differ by order one, and the entries K_rs, r != s, have no meaningful two-point
+        derivative).  ``Tpfa.adjoint_flow`` gives the exact gradient of its discrete problem under both keys.  Robin
+        and internal-boundary faces, conditions per sub-face, partial discretizations: status 5.
         Returns (grads, info); afterwards the handle holds no active system."""
         if sd.dim < 2:
             return self._tpfa().adjoint_flow(sd, data, p, grad_flux=grad_flux, grad_pressure=grad_pressure, want=want,

@@ -137,7 +137,8 @@ class Tpfa:
                      want=("permeability", "bc_values", "source"), method: str = "cg", rtol: float = 1e-12,
                      maxit: int = 20000, restart: int = 0, precond: str = "amg"):
         """The adjoint of the flow solve of this discretization on the device; see ``Mpfa.adjoint_flow``.  Here
-        ``"permeability"`` is the exact gradient of the discrete problem."""
+        ``"permeability"`` is the exact gradient of the discrete problem, and ``"permeability_exact"`` returns the same
+        numbers."""
         if self._periodic.get(id(sd)) is not None:
             raise NotImplementedError("tilted or periodic grids are not covered by the flow adjoint")
         pd = data[PARAMETERS][self.keyword]

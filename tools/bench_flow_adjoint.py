@@ -6,7 +6,10 @@ tetrahedra; n = 35: 257 250 cells), with the same method, rtol and preconditione
 Device times are HIP-event times from pfv_stats (solve_ms of the forward solve; flow_adjoint_map_ms / _products_ms /
 _solve_ms / _gradient_ms of the adjoint), the call times are a host clock around calls that end in a device
 synchronise.  The first repeat (which builds the column maps and loads the code objects) is reported apart and dropped
-from best / median.  Prints one JSON line.  A measurement, not a test: no thresholds.
+from best / median.  With --scheme mpfa the adjoint also asks for "permeability_exact": exact_ms is the kernel pair of
+the exact gradient (the interaction-region pass and the cell sum, flow_adjoint_exact_ms), to be read next to node_ms --
+the interaction-region kernel of the discretize call on the same grid, reported once -- and gradient_ms, the face and
+cell kernels of the two-point grad_perm.  Prints one JSON line.  A measurement, not a test: no thresholds.
 
     python tools/bench_flow_adjoint.py [--n-side 35] [--scheme mpfa|tpfa] [--reps 6] [--rtol 1e-10] [--precond amg]
 """
@@ -56,6 +59,9 @@ def main():
     method = a.method or ("bicgstab" if a.scheme == "mpfa" else "cg")
     flow.discretize(g, data)
     ctx = flow.context(g)
+    st0 = ctx.stats()
+    discretize = {"node_ms": st0["node_ms"], "discretize_ms": st0["discretize_ms"]}
+    want = ("permeability", "bc_values", "source") + (("permeability_exact",) if a.scheme == "mpfa" else ())
     source = g.cell_volumes * rng.standard_normal(nc)
     gq, gp = rng.standard_normal(nf), rng.standard_normal(nc)
     kw = dict(method=method, rtol=a.rtol, precond=a.precond)
@@ -70,12 +76,13 @@ def main():
         fwd.append({"call_ms": wall, "solve_ms": st["solve_ms"], "assemble_ms": st["assemble_ms"],
                     "amg_setup_ms": st["amg_setup_ms"], "iterations": info["iterations"]})
         t0 = time.perf_counter()
-        _, info = flow.adjoint_flow(g, data, p, grad_flux=gq, grad_pressure=gp, **kw)
+        _, info = flow.adjoint_flow(g, data, p, grad_flux=gq, grad_pressure=gp, want=want, **kw)
         ctx.sync()
         wall = (time.perf_counter() - t0) * 1e3
         st = ctx.stats()
         adj.append({"call_ms": wall, "map_ms": st["flow_adjoint_map_ms"], "products_ms": st["flow_adjoint_products_ms"],
                     "solve_ms": st["flow_adjoint_solve_ms"], "gradient_ms": st["flow_adjoint_gradient_ms"],
+                    "exact_ms": st["flow_adjoint_exact_ms"], "exact_map_ms": st["flow_adjoint_exact_map_ms"],
                     "amg_setup_ms": st["amg_setup_ms"], "iterations": info["iterations"],
                     "map_builds": st["flow_adjoint_map_builds"]})
 
@@ -88,7 +95,7 @@ def main():
 
     print(json.dumps({"scheme": a.scheme, "cells": int(nc), "faces": int(nf), "flux_nnz": int(ctx.matrix_info(0)[2]),
                       "method": method, "rtol": a.rtol, "precond": a.precond, "device_build": lib is None,
-                      "forward": summary(fwd), "adjoint": summary(adj)}))
+                      "discretize": discretize, "forward": summary(fwd), "adjoint": summary(adj)}))
 
 
 if __name__ == "__main__":

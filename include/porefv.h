@@ -507,6 +507,10 @@ pfv_status pfv_amg_level(pfv_ctx* h, int level, int64_t* info, double* params, i
                          int32_t* op_indices, double* op_val, double* dinv, int32_t* agg, int32_t* mptr, int32_t* mem,
                          double* dense);
 
+/* Right-hand side level `level` >= 1 of that hierarchy worked on in its last first visit (tests): out [n_l] on the host,
+ * the restricted residual of the level above as the last cycle left it.  Errors as pfv_amg_level. */
+pfv_status pfv_amg_level_rhs(pfv_ctx* h, int level, double* out);
+
 /* Block preconditioner (PFV_PRECOND_BLOCK) for the coupled Jacobians of mixed-dimensional / multi-physics models
  * that the reference solves directly (models/solution_strategy.py:830-884; mortar coupling
  * models/constitutive_laws.py:987-1000): the unknowns of the system given to pfv_set_system are grouped in

@@ -53,7 +53,7 @@ EXPORTS = [
     "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl", "pfv_transport_advance_nl_multi",
     "pfv_transport_advance_react", "pfv_transport_adjoint_multi", "pfv_transport_adjoint_react",
     "pfv_transport_adjoint_nl", "pfv_transport_adjoint_nl_multi", "pfv_flow_adjoint", "pfv_flow_adjoint_exact",
-    "pfv_advdiff_adjoint",
+    "pfv_advdiff_adjoint", "pfv_amg_level_rhs",
 ]
 
 
@@ -264,6 +264,8 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_amg_level.argtypes = [_h, C.c_int, _lp, _dp, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _ip, _dp, _dp, _ip, _ip, _ip,
                                   _dp]
     lib.pfv_amg_level.restype = C.c_int
+    lib.pfv_amg_level_rhs.argtypes = [_h, C.c_int, _dp]
+    lib.pfv_amg_level_rhs.restype = C.c_int
     lib.pfv_get_stats_n.argtypes = [_h, C.c_void_p, C.c_size_t]
     lib.pfv_get_stats_n.restype = C.c_int
     lib.pfv_time_kernel.argtypes = [_h, C.c_int, C.c_int, _dp]
@@ -1239,6 +1241,14 @@ class Context:
 
     def copy_device_vector(self, which: int, dst_ptr: int, count: int):
         self._check(self.lib.pfv_copy_device_vector(self._h, which, C.c_void_p(dst_ptr), int(count)))
+
+    def amg_level_rhs(self, level: int) -> np.ndarray:
+        """Right-hand side of level ``level`` >= 1 of the plain AMG hierarchy as its last cycle left it
+        (pfv_amg_level_rhs): the restricted residual of the level above."""
+        n = int(self.amg_level(level)["n"])
+        out = np.zeros(n)
+        self._check(self.lib.pfv_amg_level_rhs(self._h, int(level), out.ctypes.data_as(_dp)))
+        return out
 
     def amg_setup(self, n_own: int = 0):
         """AMG hierarchy of the leading n_own x n_own block of the assembled system (0 = all of it)."""

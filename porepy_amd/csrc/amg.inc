@@ -94,6 +94,10 @@ struct AmgSwitches {
   int64_t gather_rows = kAmgGatherRowsDefault;  // PFV_AMG_GATHER_ROWS, >= 1
   bool post_ap = true;               // PFV_AMG_POST_AP: finest post-smoothing through A_s P (amg_build_ap / amg_post_ap)
   bool galerkin_ap = true;           // PFV_AMG_GALERKIN_AP: kept maps: the first coarse operator as P^T (A_s P) (amg_coarsen_level)
+  // level 0 on the AP path (amg_cycle): the product leaves d = b - A_s x0 (PFV_AMG_L0_RESIDUAL), formed by 4 lanes per
+  // row where the level has windows and short rows (PFV_AMG_L0_LANES4), the BiCGStab updates write the first smoothing
+  // step (PFV_AMG_KRYLOV_PRESMOOTH)
+  bool l0_residual = true, l0_lanes4 = true, krylov_presmooth = true;
 };
 
 static AmgSwitches amg_read_switches(int bs) {
@@ -142,6 +146,9 @@ static AmgSwitches amg_read_switches(int bs) {
   w.gather_rows = std::max<int64_t>(1, env_int("PFV_AMG_GATHER_ROWS", (int)kAmgGatherRowsDefault));
   w.post_ap = on("PFV_AMG_POST_AP", 1);
   w.galerkin_ap = on("PFV_AMG_GALERKIN_AP", 1);
+  w.l0_residual = on("PFV_AMG_L0_RESIDUAL", 1);
+  w.l0_lanes4 = on("PFV_AMG_L0_LANES4", 1);
+  w.krylov_presmooth = on("PFV_AMG_KRYLOV_PRESMOOTH", 1);
   return w;
 }
 
@@ -1649,7 +1656,9 @@ static void amg_build_ap(pfv_ctx_impl& c, Amg& amg, bool want64) {
 // lanes per row, as the short-row products do it, issued 13 memory instructions per 8 rows with an eighth of the lanes
 // active in half of them, and ran 145 us on 160 MB: bound by the issue of loads, not by bytes.)  Rows of any length:
 // the stretch goes through LDS in chunks of CH products.
-template <int CH>
+// RES: t holds d = b - A_s x0 (the residual form of the level's product): y = tt + omega D^-1 (d - alpha AP xs), and
+// neither b nor a separate t is read.
+template <int CH, bool RES>
 __global__ void __launch_bounds__(256) k_amg_post_ap(int64_t nrows, const int32_t* __restrict__ ap,
                                                      const int32_t* __restrict__ ax, const double* __restrict__ av,
                                                      const int32_t* __restrict__ agg, const double* __restrict__ xc,
@@ -1670,7 +1679,7 @@ __global__ void __launch_bounds__(256) k_amg_post_ap(int64_t nrows, const int32_
     const int k = agg[row];
     x0 = x[row];
     tr = t[row];
-    br = b[row];
+    if (!RES) br = b[row];
     dr = dinv[row];
     xr = xc[k];
     if (xc2) xr += xc2[k];
@@ -1701,10 +1710,11 @@ __global__ void __launch_bounds__(256) k_amg_post_ap(int64_t nrows, const int32_
   }
   if (live) {
     const double tt = x0 + alpha * xr;
-    x[row] = tt + omega * dr * (br - (tr + alpha * sum));
+    x[row] = RES ? tt + omega * dr * (tr - alpha * sum) : tt + omega * dr * (br - (tr + alpha * sum));
   }
 }
 #endif
+// b == nullptr: t holds d = b - A_s x0 (PFV_AMG_L0_RESIDUAL)
 static void amg_post_ap(pfv_ctx_impl& c, const Amg& amg, const AmgLevel& L, const double* b, const double* t,
                         const double* xc, const double* xc2, double* x) {
   stream_t s = c.stream;
@@ -1721,12 +1731,16 @@ static void amg_post_ap(pfv_ctx_impl& c, const Amg& amg, const AmgLevel& L, cons
     for (int p = ap[r]; p < ap[r + 1]; ++p) sum += av[p] * (xc2 ? xc[ax[p]] + xc2[ax[p]] : xc[ax[p]]);
     const int k = agg[r];
     const double tt = x[r] + alpha * (xc2 ? xc[k] + xc2[k] : xc[k]);
-    x[r] = tt + omega * dinv[r] * (b[r] - (t[r] + alpha * sum));
+    x[r] = b ? tt + omega * dinv[r] * (b[r] - (t[r] + alpha * sum)) : tt + omega * dinv[r] * (t[r] - alpha * sum);
   });
 #else
   const unsigned blocks = (unsigned)((n + 255) / 256);
-  PFV_LAUNCH(HIP_KERNEL_NAME(k_amg_post_ap<2048>), dim3(blocks), dim3(256), 0, s, n, ap, ax, av, agg, xc, xc2, t, b, dinv,
-             omega, alpha, x);
+  if (b)
+    PFV_LAUNCH(HIP_KERNEL_NAME(k_amg_post_ap<2048, false>), dim3(blocks), dim3(256), 0, s, n, ap, ax, av, agg, xc, xc2, t, b,
+               dinv, omega, alpha, x);
+  else
+    PFV_LAUNCH(HIP_KERNEL_NAME(k_amg_post_ap<2048, true>), dim3(blocks), dim3(256), 0, s, n, ap, ax, av, agg, xc, xc2, t, b,
+               dinv, omega, alpha, x);
   PFV_HIP_CHECK(hipGetLastError());
 #endif
 }
@@ -1761,7 +1775,8 @@ static void amg_setup_finish(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, dou
                  (long long)amg.filt_nnz);
     for (size_t k = 0; k < amg.nlev; ++k)
       std::fprintf(stderr, " %lld/%lld(w%.3f)", (long long)amg.lev[k]->n, (long long)amg.lev[k]->P->nnz, amg.lev[k]->omega);
-    std::fprintf(stderr, " reuse %d\n", (int)amg.reused);
+    const AmgLevel& L0 = *amg.lev[0];
+    std::fprintf(stderr, " reuse %d window0 %d\n", (int)amg.reused, (L0.win && L0.win->ok) ? L0.win->wmax : -1);
   }
   amg.gal_for_sum = D ? 0ull : level0_sum;
   if (w.reuse && (!D || csum != 0)) {
@@ -1859,7 +1874,8 @@ static void amg_setup(pfv_ctx_impl& c, Amg& amg, const CsrPattern& A, const doub
 // matrix values are streamed in single precision (8 instead of 12 bytes per entry; the vectors and
 // the accumulation stay double) -- the Krylov loop around it works on the double matrix.
 #ifndef PFV_EMULATE
-// MODE 0: y = A x;  1: y = x + omega dinv (b - A x);  4 / 5: the fused forms of the cycle (SpmvFuse, spmv_win.inc)
+// MODE 0: y = A x;  1: y = x + omega dinv (b - A x);  4 / 5: the fused forms of the cycle (SpmvFuse, spmv_win.inc);
+// 6: y = b - A x
 template <int L, int U, class VT, int MODE>
 __global__ void __launch_bounds__(256) k_amg_spmv(int64_t nrows, const int32_t* __restrict__ indptr,
                                                   const int32_t* __restrict__ indices,
@@ -1895,7 +1911,8 @@ __global__ void __launch_bounds__(256) k_amg_spmv(int64_t nrows, const int32_t* 
       const double res = b[row] - sum;
       y[row] = res;
       F.y2[row] = omega * dinv[row] * res;
-    } else y[row] = sum;
+    } else if (MODE == 6) y[row] = b[row] - sum;
+    else y[row] = sum;
   }
 }
 template <int L, class VT, int MODE>
@@ -1933,7 +1950,8 @@ static void amg_spmv_t(pfv_ctx_impl& c, const CsrPattern& P, const VT* val, cons
       const double res = b[r] - sum;
       y[r] = res;
       F.y2[r] = omega * dinv[r] * res;
-    } else y[r] = sum;
+    } else if (MODE == 6) y[r] = b[r] - sum;
+    else y[r] = sum;
   });
 #else
   const double avg = (double)P.nnz / (double)nrows;
@@ -1985,6 +2003,24 @@ static void amg_spmv_fused(pfv_ctx_impl& c, const AmgLevel& L, const double* x, 
 #endif
   if (L.v32) amg_spmv_t<float, MODE>(c, *L.P, L.v32, x, y, b, dinv, L.omega, F);
   else amg_spmv_t<double, MODE>(c, *L.P, L.val, x, y, b, dinv, L.omega, F);
+}
+// d = b - A_s x on level 0 of the AP path: MODE 6 of the lane-group products.  Windowed rows of up to 22 entries on
+// average (the filtered operator of a flow system: 18) take FOUR lanes per row: a 64-row block is one pass of its 256
+// threads where 8 lanes make two, 18 entries fill 18 of 20 lane slots where 8 x 3 fill 18 of 24, and the shuffle tree
+// has two steps -- 100.8 -> 86.6 us on the 2 M-cell grid (5 or 6 chunks per lane alike; 3 chunks, i.e. a second trip for
+// most rows: 88.8).  Another summation order than the 8-lane form: a switch of its own.
+static void amg_residual_l0(pfv_ctx_impl& c, const Amg& amg, const AmgLevel& L, const double* x, const double* b,
+                            double* d) {
+#ifndef PFV_EMULATE
+  const double avg = (double)L.P->nnz / (double)std::max<int64_t>(L.n, 1);
+  if (amg.sw.l0_lanes4 && L.win && L.win->ok && L.v32 && avg <= 22.0) {
+    const int U = std::max(1, std::min(6, (int)std::ceil(1.1 * avg / 4)));
+    launch_spmv_win_u<4, float, 6>(c.stream, U, *L.win, L.P->indptr.p, L.v32, x, d, b, L.dinv, L.omega, Reduce{});
+    PFV_HIP_CHECK(hipGetLastError());
+    return;
+  }
+#endif
+  amg_spmv_fused<6>(c, L, x, d, b, SpmvFuse{});
 }
 
 // Damping of the Jacobi smoother per level: omega_l = sigma / rho_l with rho_l ~ rho(D^-1 A_l) from a power iteration.
@@ -2160,7 +2196,8 @@ static void amg_prolong_smooth(pfv_ctx_impl& c, const Amg& amg, const AmgLevel& 
 }
 
 // bc[R] = sum over the members of R of (b - t),  t = A_l x;  the next level's first smoothing step (from a zero guess)
-// rides along: xn[R] = omega_n dn[R] bc[R]
+// rides along: xn[R] = omega_n dn[R] bc[R].  b == nullptr: t holds d = b - A_l x already (one gather per member, the
+// same numbers added in the same order)
 static void amg_restrict(pfv_ctx_impl& c, const Amg& amg, const AmgLevel& L, const AmgLevel& Ln, const double* b,
                          const double* t, bool next_smooths) {
   stream_t s = c.stream;
@@ -2182,7 +2219,7 @@ static void amg_restrict(pfv_ctx_impl& c, const Amg& amg, const AmgLevel& L, con
         double sum = 0.0;
         for (int q = mptr[I]; q < mptr[I + 1]; ++q) {
           const int64_t r = (int64_t)mem[q] * bs + a;
-          sum += b[r] - t[r];
+          sum += b ? b[r] - t[r] : t[r];
         }
         bc[R] = sum;
         if (next_smooths) xn[R] = omega_n * dn[R] * sum;
@@ -2197,7 +2234,7 @@ static void amg_restrict(pfv_ctx_impl& c, const Amg& amg, const AmgLevel& L, con
       double part = 0.0;
       PFV_LANES(q, nm) {
         const int64_t r = (int64_t)mem[q0 + q] * bs + a;
-        part += b[r] - t[r];
+        part += b ? b[r] - t[r] : t[r];
       }
       sh[w.lane] = part;
       w.lsync();
@@ -2248,12 +2285,17 @@ static double* amg_cycle(pfv_ctx_impl& c, Amg& amg, size_t l, const double* b, d
   // visited twice, in u, which the second visit (whose scratch t is) leaves alone.  Level 0 keeps the two launches: its
   // result belongs in the caller's x, and forming t per WINDOW column there would cost more bytes than t's round trip.
   const bool fuse_big = path.fuse_big;
+  // level 0 on the AP path: the product leaves d = b - A_s x0 in t, all the restriction and amg_post_ap read of b and t
+  const bool res0 = l == 0 && amg.ap_ok && !small && amg.sw.l0_residual;
   if (!x_is_presmoothed) parallel_for(s, n, PFV_LAMBDA(int64_t i) { x[i] = omega * dinv[i] * b[i]; });
   // restriction; the first smoothing step of the next level (from a zero guess) rides along
   const bool next_smooths = l + 2 < amg.nlev;
   if (small) {
     if (L.v32) amg_restrict_residual<float>(c, amg, L, Ln, L.v32, b, x, next_smooths);
     else amg_restrict_residual<double>(c, amg, L, Ln, L.val, b, x, next_smooths);
+  } else if (res0) {
+    amg_residual_l0(c, amg, L, x, b, t);
+    amg_restrict(c, amg, L, Ln, nullptr, t, next_smooths);
   } else {
     amg_spmv(c, amg, L, x, t, nullptr);
     amg_restrict(c, amg, L, Ln, b, t, next_smooths);
@@ -2299,9 +2341,10 @@ static double* amg_cycle(pfv_ctx_impl& c, Amg& amg, size_t l, const double* b, d
     return out;
   }
   if (l == 0 && amg.ap_ok && !small) {
-    // level 0 with AP: t = A_s x0 of the restriction is still in L.t (the coarse visits work in the vectors of their own
-    // levels; nothing above has written it), x still holds x0 -- prolongation and post-smoothing in one launch
-    amg_post_ap(c, amg, L, b, t, xc, xc2, x);
+    // level 0 with AP: t = A_s x0 of the restriction (res0: d = b - A_s x0) is still in L.t (the coarse visits work in
+    // the vectors of their own levels; nothing above has written it), x still holds x0 -- prolongation and
+    // post-smoothing in one launch
+    amg_post_ap(c, amg, L, res0 ? nullptr : b, t, xc, xc2, x);
     return x;
   }
   {
@@ -2485,6 +2528,17 @@ static void precond_apply(pfv_ctx_impl& c, const Precond& M, int64_t n, const do
     const double* d = M.diag;
     parallel_for(c.stream, n, PFV_LAMBDA(int64_t i) { out[i] = in[i] / d[i]; });
   }
+}
+// The first smoothing step of the plain AMG's cycle, x0 = omega D^-1 in with the finest level's omega and dinv, for a
+// caller that forms it in the kernel that writes `in` and then calls amg_cycle with x_is_presmoothed (krylov_solve:
+// the two updates of BiCGStab; PFV_AMG_KRYLOV_PRESMOOTH).  false: M is no such preconditioner -- precond_apply.
+static bool precond_presmooth(const Precond& M, const double*& dinv, double& omega) {
+  if (M.sweep || M.blocks || M.nns || !M.amg || M.amg->dist || !M.amg->valid) return false;
+  const Amg& amg = *M.amg;
+  if (!amg.sw.krylov_presmooth || !amg.ap_ok || amg.nlev < 2 || amg_level_path(amg, 0).small) return false;
+  dinv = amg.lev[0]->dinv;
+  omega = amg.lev[0]->omega;
+  return true;
 }
 
 }  // namespace pfv

@@ -945,6 +945,12 @@ static SolveResult krylov_solve(pfv_ctx_impl& c, const LinSys& sys, int method, 
   constexpr int kTrueResidualRestarts = 3;
   int restarts = 0;
   int it = 1;
+  // plain AMG on its AP path: the first smoothing step of the cycle's finest level, x0 = omega_0 D_0^-1 in, is written
+  // by the update that forms `in` (the vector is in registers there; the cycle's own launch read it back), the same
+  // expression on the same numbers
+  const double* dinv0 = nullptr;
+  double omega0 = 0.0;
+  const bool presmooth = M && !sharded && precond_presmooth(*M, dinv0, omega0);
 restart_bicgstab:
   be_d2d(rhat, r, sizeof(double) * n, s);
   be_memset(p, 0, sizeof(double) * n, s);
@@ -952,7 +958,14 @@ restart_bicgstab:
   dot2(c, n, r, r, rhat, r, R, M_START);
   for (; it <= maxit; ++it) {
     // p = r + beta (p - omega v); y = M^-1 p
-    if (M) {
+    if (presmooth) {
+      parallel_for(s, n, PFV_LAMBDA(int64_t i) {
+        const double pi = r[i] + S[S_BETA] * (p[i] - S[S_OMEGA] * v[i]);
+        p[i] = pi;
+        y[i] = omega0 * dinv0[i] * pi;
+      });
+      amg_cycle(c, *M->amg, 0, p, y, true);
+    } else if (M) {
       parallel_for(s, n, PFV_LAMBDA(int64_t i) { p[i] = r[i] + S[S_BETA] * (p[i] - S[S_OMEGA] * v[i]); });
       precond_apply(c, *M, n, p, y);
     } else {
@@ -964,7 +977,14 @@ restart_bicgstab:
     }
     shard_spmv(c, P, Aval, y, v, rhat, 1, R, M_ALPHA, sys.win);  // v = A y, alpha = rho / (rhat, v)
     // s = r - alpha v (stored in r); z = M^-1 s
-    if (M) {
+    if (presmooth) {
+      parallel_for(s, n, PFV_LAMBDA(int64_t i) {
+        const double si = r[i] - S[S_ALPHA] * v[i];
+        r[i] = si;
+        z[i] = omega0 * dinv0[i] * si;
+      });
+      amg_cycle(c, *M->amg, 0, r, z, true);
+    } else if (M) {
       parallel_for(s, n, PFV_LAMBDA(int64_t i) { r[i] -= S[S_ALPHA] * v[i]; });
       precond_apply(c, *M, n, r, z);
     } else {

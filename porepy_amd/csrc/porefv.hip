@@ -4041,6 +4041,20 @@ pfv_status pfv_amg_level(pfv_ctx* h, int level, int64_t* info, double* params, i
   });
 }
 
+pfv_status pfv_amg_level_rhs(pfv_ctx* h, int level, double* out) {
+  return guarded(h, [&] {
+    require(out != nullptr, "out is required");
+    const pfv::Amg* ap = h->amg_last == 1 ? h->amg.get() : (h->amg_last == 2 ? h->amg_block.get() : nullptr);
+    require(ap && ap->valid, "no AMG hierarchy (pfv_amg_setup or a solve with PFV_PRECOND_AMG first)");
+    if (ap->dist) throw pfv::Error(PFV_ERR_UNSUPPORTED, "pfv_amg_level_rhs does not read the coupled hierarchy of a sharded solve");
+    require(level >= 1 && (size_t)level < ap->nlev, "level out of range");
+    const pfv::AmgLevel& L = *ap->lev[(size_t)level];
+    require(L.b.p != nullptr, "the level has no right-hand side yet");
+    be_d2h(out, L.b.p, sizeof(double) * (size_t)L.n, h->stream);
+    pfv::be_sync(h->stream);
+  });
+}
+
 // The system the Krylov loop works on: the active one, renumbered along the cell order when it is a
 // grid system (reorder.inc), with the SpMV windows of its pattern (spmv_win.inc).  Copies and
 // windows are kept until the matrix is assembled again.

@@ -216,6 +216,7 @@ __global__ void __launch_bounds__(256) k_win_derive(int64_t nrows, const int32_t
 //         the prolongation kernel and its round trip through memory are gone);
 // MODE 5: y = w - A x and y2 = omega dinv y (the residual a second coarse visit works on, and that visit's first
 //         smoothing step from a zero guess, in the launch of the product)
+// MODE 6: y = w - A x alone (level 0 of the cycle: the restriction and the post-smoothing through AP read only b - A_s x0)
 template <int L, int U, class VT, int MODE>
 __global__ void __launch_bounds__(256) k_spmv_win(int64_t nrows, const int32_t* __restrict__ indptr,
                                                   const int64_t* __restrict__ wptr, const int32_t* __restrict__ wcol,
@@ -274,7 +275,8 @@ __global__ void __launch_bounds__(256) k_spmv_win(int64_t nrows, const int32_t* 
         const double res = wrow - sum;
         y[row] = res;
         F.y2[row] = omega * drow * res;
-      } else y[row] = sum;
+      } else if (MODE == 6) y[row] = wrow - sum;
+      else y[row] = sum;
       if (MODE == 2) acc1 += wrow * sum;
       if (MODE == 3) { acc1 += sum * wrow; acc2 += sum * sum; }
     }

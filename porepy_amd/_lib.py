@@ -1631,6 +1631,52 @@ class Context:
                 raise
         return c, out
 
+    # ---- what the adjoint methods share ----
+    def _adjoint_obs(self, obs_cells):
+        """(obs, n_obs): ``obs_cells`` as int32, or None for every cell"""
+        if obs_cells is None:
+            return None, self.nc
+        obs = np.ascontiguousarray(obs_cells)
+        if obs.ndim != 1 or not np.issubdtype(obs.dtype, np.integer):
+            raise ValueError("obs_cells must be a one-dimensional array of cell indices")
+        big = obs[(obs < -2 ** 31) | (obs >= 2 ** 31)]
+        if big.size:
+            raise ValueError(f"obs_cells: {int(big[0])} is out of range (0 .. {self.nc - 1})")
+        return obs.astype(np.int32), obs.size
+
+    @staticmethod
+    def _adjoint_grads(want, known, shapes, refused):
+        """The zeroed outputs of ``want`` in the order of ``known``; ``refused``: the names this call cannot give, each
+        with the reason."""
+        want = tuple(want)
+        for name in want:
+            if name not in known:
+                raise ValueError(f"want: unknown gradient {name!r} (known: {', '.join(known)})")
+            if name in refused:
+                raise ValueError(refused[name])
+        return {name: np.zeros(shapes[name]) for name in known if name in want}
+
+    @staticmethod
+    def _need_states(names, states):
+        return {} if states is not None else {m: f'the gradient "{m}" needs states (c^0 .. c^N)' for m in names}
+
+    @staticmethod
+    def _need_corey(fluxfn_kind):
+        return {} if int(fluxfn_kind) == FLUXFN_COREY else {
+            "flux_function": 'the gradient "flux_function" is that of the six Corey parameters: it needs a '
+                             'CoreyFractionalFlow'}
+
+    def _adjoint_result(self, st, grads, out, raise_on_fail):
+        """(grads, out); a failed call raises with ``out`` as the error's ``info``, but for a refused step (6) that the
+        caller asked to have returned"""
+        if st != 0 and (raise_on_fail or st != 6):
+            try:
+                self._check(st)
+            except PorefvError as e:
+                e.info = out
+                raise
+        return grads, out
+
     ADJOINT_GRADIENTS = ("c0", "source", "bc_values", "accumulation", "flux")
 
     def transport_adjoint_multi(self, n_steps: int, accumulation, bc_values, loads, obs_cells=None, states=None, q=None,
@@ -1656,16 +1702,7 @@ class Context:
         n_steps = int(n_steps)
         if n_steps < 0:
             raise ValueError("n_steps must not be negative")
-        obs = None
-        if obs_cells is not None:
-            obs = np.ascontiguousarray(obs_cells)
-            if obs.ndim != 1 or not np.issubdtype(obs.dtype, np.integer):
-                raise ValueError("obs_cells must be a one-dimensional array of cell indices")
-            big = obs[(obs < -2 ** 31) | (obs >= 2 ** 31)]
-            if big.size:
-                raise ValueError(f"obs_cells: {int(big[0])} is out of range (0 .. {self.nc - 1})")
-            obs = obs.astype(np.int32)
-        n_obs = self.nc if obs is None else obs.size
+        obs, n_obs = self._adjoint_obs(obs_cells)
         ld = _f64(loads)
         if ld.shape != (n_steps, k, n_obs):
             raise ValueError(f"loads must have shape ({n_steps}, {k}, {n_obs}), not {ld.shape}")
@@ -1674,16 +1711,11 @@ class Context:
             stt = _f64(states)
             if stt.shape != (n_steps + 1, k, self.nc):
                 raise ValueError(f"states must have shape ({n_steps + 1}, {k}, {self.nc}), not {stt.shape}")
-        want = tuple(want)
-        for name in want:
-            if name not in self.ADJOINT_GRADIENTS:
-                raise ValueError(f"want: unknown gradient {name!r} (known: {', '.join(self.ADJOINT_GRADIENTS)})")
-            if name in ("accumulation", "flux") and stt is None:
-                raise ValueError(f'the gradient "{name}" needs states (c^0 .. c^N)')
-        kq, pq = self._vec(q, self.nf, "the flux array", False)
         shapes = {"c0": (k, self.nc), "source": (k, self.nc), "bc_values": (k, self.nf), "accumulation": (k, self.nc),
                   "flux": (self.nf,)}
-        grads = {name: np.zeros(shapes[name]) for name in self.ADJOINT_GRADIENTS if name in want}
+        grads = self._adjoint_grads(want, self.ADJOINT_GRADIENTS, shapes,
+                                    self._need_states(("accumulation", "flux"), stt))
+        kq, pq = self._vec(q, self.nf, "the flux array", False)
         done, infos = C.c_int32(0), (SolveInfo * k)()
         st = self.lib.pfv_transport_adjoint_multi(
             self._h, pq, k, _ptr(bv, _dp), _ptr(acc, _dp), n_steps, n_obs, _ptr(obs, _ip), _ptr(ld, _dp), _ptr(stt, _dp),
@@ -1693,13 +1725,7 @@ class Context:
         out = {"steps_done": done.value, "converged": all(bool(i.converged) for i in infos),
                "iterations": [i.iterations for i in infos], "rel_residual": [i.rel_residual for i in infos],
                "solve_ms": [i.solve_ms for i in infos]}
-        if st != 0 and (raise_on_fail or st != 6):
-            try:
-                self._check(st)
-            except PorefvError as e:
-                e.info = out
-                raise
-        return grads, out
+        return self._adjoint_result(st, grads, out, raise_on_fail)
 
     REACT_ADJOINT_GRADIENTS = ADJOINT_GRADIENTS + ("rate_matrix", "rate_weight")
 
@@ -1734,16 +1760,7 @@ class Context:
         n_steps = int(n_steps)
         if n_steps < 0:
             raise ValueError("n_steps must not be negative")
-        obs = None
-        if obs_cells is not None:
-            obs = np.ascontiguousarray(obs_cells)
-            if obs.ndim != 1 or not np.issubdtype(obs.dtype, np.integer):
-                raise ValueError("obs_cells must be a one-dimensional array of cell indices")
-            big = obs[(obs < -2 ** 31) | (obs >= 2 ** 31)]
-            if big.size:
-                raise ValueError(f"obs_cells: {int(big[0])} is out of range (0 .. {self.nc - 1})")
-            obs = obs.astype(np.int32)
-        n_obs = self.nc if obs is None else obs.size
+        obs, n_obs = self._adjoint_obs(obs_cells)
         ld = _f64(loads)
         if ld.shape != (n_steps, k, n_obs):
             raise ValueError(f"loads must have shape ({n_steps}, {k}, {n_obs}), not {ld.shape}")
@@ -1752,17 +1769,12 @@ class Context:
             stt = _f64(states)
             if stt.shape != (n_steps + 1, k, self.nc):
                 raise ValueError(f"states must have shape ({n_steps + 1}, {k}, {self.nc}), not {stt.shape}")
-        want = tuple(want)
-        for name in want:
-            if name not in self.REACT_ADJOINT_GRADIENTS:
-                raise ValueError(f"want: unknown gradient {name!r} (known: {', '.join(self.REACT_ADJOINT_GRADIENTS)})")
-            if name in ("accumulation", "flux", "rate_matrix", "rate_weight") and stt is None:
-                raise ValueError(f'the gradient "{name}" needs states (c^0 .. c^N)')
-        kq, pq = self._vec(q, self.nf, "the flux array", False)
-        kr, pr = self._vec(rate_weight, self.nc, "rate_weight", False)
         shapes = {"c0": (k, self.nc), "source": (k, self.nc), "bc_values": (k, self.nf), "accumulation": (k, self.nc),
                   "flux": (self.nf,), "rate_matrix": (k, k), "rate_weight": (self.nc,)}
-        grads = {name: np.zeros(shapes[name]) for name in self.REACT_ADJOINT_GRADIENTS if name in want}
+        grads = self._adjoint_grads(want, self.REACT_ADJOINT_GRADIENTS, shapes,
+                                    self._need_states(("accumulation", "flux", "rate_matrix", "rate_weight"), stt))
+        kq, pq = self._vec(q, self.nf, "the flux array", False)
+        kr, pr = self._vec(rate_weight, self.nc, "rate_weight", False)
         done, infos = C.c_int32(0), (SolveInfo * k)()
         st = self.lib.pfv_transport_adjoint_react(
             self._h, pq, k, _ptr(bv, _dp), _ptr(acc, _dp), _ptr(w, _dp), _ptr(K, _dp), pr, n_steps, n_obs,
@@ -1771,13 +1783,7 @@ class Context:
         out = {"steps_done": done.value, "converged": all(bool(i.converged) for i in infos),
                "iterations": [i.iterations for i in infos], "rel_residual": [i.rel_residual for i in infos],
                "solve_ms": [i.solve_ms for i in infos]}
-        if st != 0 and (raise_on_fail or st != 6):
-            try:
-                self._check(st)
-            except PorefvError as e:
-                e.info = out
-                raise
-        return grads, out
+        return self._adjoint_result(st, grads, out, raise_on_fail)
 
     NL_ADJOINT_GRADIENTS = ("s0", "source", "bc_values", "accumulation", "sink", "flux", "flux_function")
 
@@ -1803,16 +1809,7 @@ class Context:
         if bv.shape != (self.nf,):
             raise ValueError(f"bc_values must have shape ({self.nf},), not {bv.shape}")
         par = np.ascontiguousarray(fluxfn_params, dtype=np.float64).ravel()
-        obs = None
-        if obs_cells is not None:
-            obs = np.ascontiguousarray(obs_cells)
-            if obs.ndim != 1 or not np.issubdtype(obs.dtype, np.integer):
-                raise ValueError("obs_cells must be a one-dimensional array of cell indices")
-            big = obs[(obs < -2 ** 31) | (obs >= 2 ** 31)]
-            if big.size:
-                raise ValueError(f"obs_cells: {int(big[0])} is out of range (0 .. {self.nc - 1})")
-            obs = obs.astype(np.int32)
-        n_obs = self.nc if obs is None else obs.size
+        obs, n_obs = self._adjoint_obs(obs_cells)
         ld = _f64(loads)
         if ld.shape != (n_steps, n_obs):
             raise ValueError(f"loads must have shape ({n_steps}, {n_obs}), not {ld.shape}")
@@ -1821,18 +1818,11 @@ class Context:
         stt = _f64(states)
         if stt.shape != (n_steps + 1, self.nc):
             raise ValueError(f"states must have shape ({n_steps + 1}, {self.nc}), not {stt.shape}")
-        want = tuple(want)
-        for name in want:
-            if name not in self.NL_ADJOINT_GRADIENTS:
-                raise ValueError(f"want: unknown gradient {name!r} (known: {', '.join(self.NL_ADJOINT_GRADIENTS)})")
-            if name == "flux_function" and int(fluxfn_kind) != FLUXFN_COREY:
-                raise ValueError('the gradient "flux_function" is that of the six Corey parameters: it needs a '
-                                 'CoreyFractionalFlow')
-        kq, pq = self._vec(q, self.nf, "the flux array", False)
-        kk, pk = self._vec(sink, self.nc, "sink", False)
         shapes = {"s0": (self.nc,), "source": (self.nc,), "bc_values": (self.nf,), "accumulation": (self.nc,),
                   "sink": (self.nc,), "flux": (self.nf,), "flux_function": (6,)}
-        grads = {name: np.zeros(shapes[name]) for name in self.NL_ADJOINT_GRADIENTS if name in want}
+        grads = self._adjoint_grads(want, self.NL_ADJOINT_GRADIENTS, shapes, self._need_corey(fluxfn_kind))
+        kq, pq = self._vec(q, self.nf, "the flux array", False)
+        kk, pk = self._vec(sink, self.nc, "sink", False)
         done, info = C.c_int32(0), SolveInfo()
         st = self.lib.pfv_transport_adjoint_nl(
             self._h, pq, int(fluxfn_kind), _ptr(par, _dp) if par.size else None, int(par.size), _ptr(bv, _dp),
@@ -1840,13 +1830,7 @@ class Context:
             *[_ptr(grads.get(name), _dp) for name in self.NL_ADJOINT_GRADIENTS], C.byref(done), C.byref(info))
         out = {"steps_done": done.value, "iterations": info.iterations, "converged": bool(info.converged),
                "rel_residual": info.rel_residual, "solve_ms": info.solve_ms}
-        if st != 0 and (raise_on_fail or st != 6):
-            try:
-                self._check(st)
-            except PorefvError as e:
-                e.info = out
-                raise
-        return grads, out
+        return self._adjoint_result(st, grads, out, raise_on_fail)
 
     NLC_ADJOINT_GRADIENTS = ("s0", "c0", "source", "c_source", "accumulation", "sorption", "sink", "bc_values",
                              "c_bc_values", "flux", "flux_function")
@@ -1894,16 +1878,7 @@ class Context:
         if ads is not None and ads.shape != (k, self.nc):
             raise ValueError(f"sorption must have shape ({k}, {self.nc}), not {ads.shape}")
         par = np.ascontiguousarray(fluxfn_params, dtype=np.float64).ravel()
-        obs = None
-        if obs_cells is not None:
-            obs = np.ascontiguousarray(obs_cells)
-            if obs.ndim != 1 or not np.issubdtype(obs.dtype, np.integer):
-                raise ValueError("obs_cells must be a one-dimensional array of cell indices")
-            big = obs[(obs < -2 ** 31) | (obs >= 2 ** 31)]
-            if big.size:
-                raise ValueError(f"obs_cells: {int(big[0])} is out of range (0 .. {self.nc - 1})")
-            obs = obs.astype(np.int32)
-        n_obs = self.nc if obs is None else obs.size
+        obs, n_obs = self._adjoint_obs(obs_cells)
         if s_loads is None and c_loads is None:
             raise ValueError("s_loads or c_loads is required (a missing one is zeros)")
         sld = None if s_loads is None else _f64(s_loads)
@@ -1912,20 +1887,13 @@ class Context:
         cld = None if c_loads is None else _f64(c_loads)
         if cld is not None and cld.shape != (n_steps, k, n_obs):
             raise ValueError(f"c_loads must have shape ({n_steps}, {k}, {n_obs}), not {cld.shape}")
-        want = tuple(want)
-        for name in want:
-            if name not in self.NLC_ADJOINT_GRADIENTS:
-                raise ValueError(f"want: unknown gradient {name!r} (known: {', '.join(self.NLC_ADJOINT_GRADIENTS)})")
-            if name == "flux_function" and int(fluxfn_kind) != FLUXFN_COREY:
-                raise ValueError('the gradient "flux_function" is that of the six Corey parameters: it needs a '
-                                 'CoreyFractionalFlow')
-        kq, pq = self._vec(q, self.nf, "the flux array", False)
-        kk, pk = self._vec(sink, self.nc, "sink", False)
         nc, nf = self.nc, self.nf
         shapes = {"s0": (nc,), "c0": (k, nc), "source": (nc,), "c_source": (k, nc), "accumulation": (nc,),
                   "sorption": (k, nc), "sink": (nc,), "bc_values": (nf,), "c_bc_values": (k, nf), "flux": (nf,),
                   "flux_function": (6,)}
-        grads = {name: np.zeros(shapes[name]) for name in self.NLC_ADJOINT_GRADIENTS if name in want}
+        grads = self._adjoint_grads(want, self.NLC_ADJOINT_GRADIENTS, shapes, self._need_corey(fluxfn_kind))
+        kq, pq = self._vec(q, self.nf, "the flux array", False)
+        kk, pk = self._vec(sink, self.nc, "sink", False)
         done, infos = C.c_int32(0), (SolveInfo * (k + 1))()
         st = self.lib.pfv_transport_adjoint_nl_multi(
             self._h, pq, int(fluxfn_kind), _ptr(par, _dp) if par.size else None, int(par.size), _ptr(bv, _dp),
@@ -1935,13 +1903,7 @@ class Context:
         out = {"steps_done": done.value, "iterations": infos[0].iterations,
                "converged": all(bool(i.converged) for i in infos), "rel_residual": infos[0].rel_residual,
                "c_rel_residual": [i.rel_residual for i in infos[1:]], "solve_ms": infos[0].solve_ms}
-        if st != 0 and (raise_on_fail or st != 6):
-            try:
-                self._check(st)
-            except PorefvError as e:
-                e.info = out
-                raise
-        return grads, out
+        return self._adjoint_result(st, grads, out, raise_on_fail)
 
     # ---- the adjoint of the flow solve (include/porefv.h: pfv_flow_adjoint) ----
     FLOW_ADJOINT_GRADIENTS = ("permeability", "bc_values", "source", "multiplier", "permeability_exact")
@@ -1997,13 +1959,7 @@ class Context:
                 self._dev(False)
         out = {"iterations": info.iterations, "converged": bool(info.converged),
                "rel_residual": info.rel_residual, "solve_ms": info.solve_ms}
-        if st != 0 and (raise_on_fail or st != 6):
-            try:
-                self._check(st)
-            except PorefvError as e:
-                e.info = out
-                raise
-        return grads, out
+        return self._adjoint_result(st, grads, out, raise_on_fail)
 
     # ---- advection-diffusion on one handle (include/porefv.h: pfv_advdiff_*) ----
     def resident_flux_ptr(self) -> int:
@@ -2112,16 +2068,7 @@ class Context:
         n_steps = int(n_steps)
         if n_steps < 0:
             raise ValueError("n_steps must not be negative")
-        obs = None
-        if obs_cells is not None:
-            obs = np.ascontiguousarray(obs_cells)
-            if obs.ndim != 1 or not np.issubdtype(obs.dtype, np.integer):
-                raise ValueError("obs_cells must be a one-dimensional array of cell indices")
-            big = obs[(obs < -2 ** 31) | (obs >= 2 ** 31)]
-            if big.size:
-                raise ValueError(f"obs_cells: {int(big[0])} is out of range (0 .. {self.nc - 1})")
-            obs = obs.astype(np.int32)
-        n_obs = self.nc if obs is None else obs.size
+        obs, n_obs = self._adjoint_obs(obs_cells)
         want = tuple(want)
         for name in want:
             if name not in self.ADVDIFF_ADJOINT_GRADIENTS:
@@ -2168,13 +2115,7 @@ class Context:
             grads["flux_scale"] = float(scale[0])
         out = {"steps_done": done.value, "iterations": info.iterations, "converged": bool(info.converged),
                "rel_residual": info.rel_residual, "solve_ms": info.solve_ms}
-        if st != 0 and (raise_on_fail or st != 6):
-            try:
-                self._check(st)
-            except PorefvError as e:
-                e.info = out
-                raise
-        return grads, out
+        return self._adjoint_result(st, grads, out, raise_on_fail)
 
     def tpfa_transmissibility_ad(self, perm):
         """Two-point face transmissibilities and their derivatives with respect to the permeability entries

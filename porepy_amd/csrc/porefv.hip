@@ -1349,6 +1349,36 @@ pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, 
   return step_status(h, st, err, st2);
 }
 
+// ---- what the input-check kernels found, as the error of the call ---------------------------------------------------
+// off[m]: the lowest offender of check m, or kNoOffender.  The checks are judged in their order.  by_component: one bit
+// per check of a [k][n] array, whose offender is named by item and component; skip: one bit per check whose array the
+// caller has put a stand-in for (the adjoints have no state to be checked).
+constexpr int32_t kNoOffender = 0x7f7f7f7f;
+static void inputs_refused(const int32_t* off, int n_checks, const char* const* what, unsigned by_component, int k,
+                           unsigned skip) {
+  for (int m = 0; m < n_checks; ++m) {
+    if ((skip >> m & 1u) || off[m] == kNoOffender) continue;
+    if (by_component >> m & 1u)
+      throw Error(PFV_ERR_ARGUMENT, what[m] + std::to_string(off[m] / k) + ", component " + std::to_string(off[m] % k));
+    throw Error(PFV_ERR_ARGUMENT, what[m] + std::to_string(off[m]));
+  }
+}
+constexpr unsigned kNlStates = 1u << 2 | 1u << 6;  // s and c of sweep_nl_check_inputs
+static void nl_inputs_refused(const int32_t (&off)[pfv::kNlChecks], int k, unsigned skip = 0) {
+  static const char* const what[pfv::kNlChecks] = {
+      "accumulation must be positive: cell ", "negative sink in cell ", "s outside [0, 1] in cell ",
+      "Dirichlet inflow value outside [0, 1] on face ", pfv::kUnmarkedInflowFace,
+      "sorption must not be negative: cell ", "c is not finite in cell ", "c_bc_values is not finite on face "};
+  inputs_refused(off, pfv::kNlChecks, what, 7u << 5, k, skip);
+}
+constexpr unsigned kReactState = 1u << 2;  // c of sweep_react_check_inputs
+static void react_inputs_refused(const int32_t (&off)[pfv::kReactChecks], int k, unsigned skip = 0) {
+  static const char* const what[pfv::kReactChecks] = {
+      "accumulation must be positive: cell ", "rate_weight must not be negative: cell ", "c is not finite in cell ",
+      "bc_values is not finite on face ", pfv::kUnmarkedInflowFace};
+  inputs_refused(off, pfv::kReactChecks, what, 1u << 0 | 1u << 2 | 1u << 3, k, skip);
+}
+
 // ---- the saturation step: q f(s) in flow order (sweep.inc: sweep_row_nl) -----------------------------------------------
 // Per step: rhs, the forward levels, the core level iterated by nonlinear Jacobi (a host read every kNlCoreCheck-th
 // iteration), the backward levels, F(s) over all rows and ONE host read of its norms and the status words.  The state
@@ -1401,17 +1431,7 @@ static pfv_status advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const
     int32_t off[pfv::kNlChecks];
     pfv::sweep_nl_check_inputs(*h, d_q, h->nl_bc.p, h->nl_acc.p, sink ? h->nl_sink.p : nullptr, h->nl_s.p, k,
                                sorption ? h->nlc_ads_in.p : nullptr, h->nlc_c_in.p, h->nlc_cbc.p, off);
-    static const char* what[5] = {"accumulation must be positive: cell ", "negative sink in cell ",
-                                  "s outside [0, 1] in cell ", "Dirichlet inflow value outside [0, 1] on face ",
-                                  pfv::kUnmarkedInflowFace};
-    for (int m = 0; m < 5; ++m)
-      if (off[m] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, what[m] + std::to_string(off[m]));
-    static const char* whatc[3] = {"sorption must not be negative: cell ", "c is not finite in cell ",
-                                   "c_bc_values is not finite on face "};
-    for (int m = 0; m < 3; ++m)
-      if (off[5 + m] != 0x7f7f7f7f)
-        throw Error(PFV_ERR_ARGUMENT, whatc[m] + std::to_string(off[5 + m] / k) + ", component " +
-                                          std::to_string(off[5 + m] % k));
+    nl_inputs_refused(off, k);
     if (fluxfn_kind == PFV_FLUXFN_TABLE)
       be_h2d(h->nl_table.ensure((size_t)n_params), fluxfn_params, sizeof(double) * (size_t)n_params, h->stream);
     F = pfv::fluxfn_make(fluxfn_kind, fluxfn_params, n_params, h->nl_table.p);
@@ -1678,13 +1698,7 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
     int32_t off[pfv::kReactChecks];
     pfv::sweep_react_check_inputs(*h, d_q, k, h->rc_bc.p, h->rc_acc_in.p, rate_weight ? h->rc_rho.p : nullptr,
                                   h->rc_c_in.p, h->rc_par.p, off);
-    auto comp = [&](int32_t v) { return std::to_string(v / k) + ", component " + std::to_string(v % k); };
-    if (off[0] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, "accumulation must be positive: cell " + comp(off[0]));
-    if (off[1] != 0x7f7f7f7f)
-      throw Error(PFV_ERR_ARGUMENT, "rate_weight must not be negative: cell " + std::to_string(off[1]));
-    if (off[2] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, "c is not finite in cell " + comp(off[2]));
-    if (off[3] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, "bc_values is not finite on face " + comp(off[3]));
-    if (off[4] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, pfv::kUnmarkedInflowFace + std::to_string(off[4]));
+    react_inputs_refused(off, k);
     tm = std::make_unique<pfv::Timer>();
     tm->start(h->stream);
     // A = div diag(q) U without accumulation (its diagonal: the outflow of the cell), once per call.  (The boundary
@@ -1862,27 +1876,97 @@ static void adjoint_take_slots(pfv_ctx* h, int64_t n_obs, const int32_t* obs_cel
   }
 }
 
-// ---- the step frame of the two adjoint calls (after their set-up, with the timer running) -------------------------------
-// Per step n = N .. 1: one slab of states (when given), the right-hand side g^n + acc o lambda^{n+1} fused with what
-// lambda^{n+1} adds to grad_source and grad_accumulation (adjoint_step_rhs), the call's own solve -- sweep, core,
-// acceptance --, its gradients of the accepted step, the swap of the two lambda and the two slab buffers.  After the
-// last step the right-hand-side kernel runs once more without loads: it leaves acc o lambda^1 = grad_c0.  Then the three
-// cell gradients go out, the call's other outputs, and the transport system is dropped.
-struct AdjointCall {  // what the two calls share, by the callers' names
+// ---- the set-up the four adjoint calls share ---------------------------------------------------------------------------
+// the counts of a call; loads: whether the observation has its loads
+static void adjoint_check_counts(int n_steps, double rtol, int maxit, bool loads,
+                                 const char* loads_text = "loads is required") {
+  require(n_steps >= 0, "bad argument");
+  require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
+  require(loads || n_steps == 0, loads_text);
+}
+
+struct AdjointSetup {
+  std::unique_ptr<pfv::Timer> tm;  // running from adjoint_system on
+  bool touched = false;            // the transport system on the handle is the call's
+  double order_ms = 0.0;
+};
+
+// The system of an adjoint call, with the timer started: A = div diag(q) U without accumulation, once per call (own_rows:
+// what the call checks or prepares on A's rows), its transposed values beside it, the observation's slots, the flow order.
+static void adjoint_system(pfv_ctx* h, AdjointSetup& S, const double* d_q, const double* d_bc, int64_t n_obs,
+                           const int32_t* obs_cells, const std::function<void()>& own_rows = nullptr) {
+  S.tm = std::make_unique<pfv::Timer>();
+  S.tm->start(h->stream);
+  upwind_drop_transport(h, true);
+  S.touched = true;
+  pfv::upwind_assemble(*h, d_q, d_bc, nullptr, nullptr, nullptr);
+  values_changed(h, Windows::drop);
+  if (own_rows) own_rows();
+  const size_t nnz = (size_t)std::max<int64_t>(h->pat_T.nnz, 1);
+  if (!h->have_tpos_T) {
+    pfv::sweep_transpose_positions(*h, h->pat_T, h->tpos_T.ensure(nnz));
+    h->have_tpos_T = true;
+  }
+  pfv::sweep_transpose_values(*h, h->pat_T.nnz, h->tpos_T.p, h->val[PFV_MAT_TRANSPORT_SYSTEM].p, h->valT_T.ensure(nnz));
+  adjoint_take_slots(h, n_obs, obs_cells);
+  transport_order(h, d_q, S.order_ms);
+}
+
+// the set-up of a call: its checks, its uploads, adjoint_system, its work buffers.  A set-up that fails leaves no system
+// behind (A without accumulation: not a system to be solved with).
+static pfv_status adjoint_setup(pfv_ctx* h, AdjointSetup& S, const std::function<void()>& body) {
+  const pfv_status st = guarded(h, body);
+  if (st != PFV_OK && S.touched) upwind_drop_transport(h, true);
+  return st;
+}
+
+// the two slabs of the states [k][nc] a step reads, and where a slab in host memory lands
+static void adjoint_slab_buffers(pfv_ctx* h, int k) {
+  const size_t n = (size_t)k * (size_t)h->nc;
+  h->aj_sA.ensure(n);
+  h->aj_sB.ensure(n);
+  if (!h->vectors_on_device) h->aj_state_in.ensure(n);
+}
+
+// ---- the step frame of the adjoint calls (after their set-up, with the timer running) -----------------------------------
+// Per step n = N .. 1: one slab of states (stage), the right-hand side fused with what the multipliers of step n + 1 add
+// to the cell gradients (rhs), the call's own solve -- sweep, core, acceptance --, its gradients of the accepted step,
+// the swap of the multipliers and the slabs.  After the last step the right-hand-side pass runs once more without loads
+// (rhs with n = 0): what it leaves is the gradient with respect to the start.  Then the gradients go out, and the
+// transport system is dropped.
+enum class GradLayout { plain, by_cell, host };  // by_cell: [cell][k] on the device, [k][cell] for the caller
+struct AdjointGrad {  // one output of a call
+  double* to;             // the caller's array; nullptr: not wanted
+  pfv::Buf<double>* buf;  // where it is summed on the device
+  size_t n;               // elements
+  GradLayout layout;      // host: `to` is host memory whatever the handle's vectors are (as its parameters are)
+  bool summed = true;     // over the steps, from zero; false: what the last right-hand-side pass leaves in buf
+};
+struct AdjointCall {  // what the calls share, by the callers' names
   int k, n_steps;
   int64_t n_obs;
   const int32_t* obs_cells;
+  // what the default hooks read: the states [N + 1][k][nc] or nullptr, the accumulation on the device, interleaved,
+  // and whether these two gradients are wanted
   const double* states;
-  const double* acc;  // the accumulation on the device, interleaved
-  double *grad_c0, *grad_source, *grad_accumulation;
+  const double* acc;
+  const double *grad_source, *grad_accumulation;
   int32_t* steps_done;
   pfv_solve_info* last;
+  std::vector<AdjointGrad> grads;
+  int saturation = -1;  // the index of the saturation's norms behind the k components' (reported first), or none
+  // The hooks; the defaults are those of one multiplier per component: lambda in aj_lam / aj_lam2, the slabs in aj_sA /
+  // aj_sB.
+  std::function<void(int)> stage;      // slab n into the buffers of the step at hand (n = 0: for the last pass)
+  std::function<void(int, bool)> rhs;  // the right-hand side(s) of step n, or of the last pass; whether step n + 1 ran
+  std::function<void()> swap;          // the accepted step becomes step n + 1
 };
 struct AdjointRun {
   int32_t completed = 0;
   int64_t core_total = 0, launches = 0;
   double ms = 0.0;
   std::vector<pfv_solve_info> info;
+  std::vector<double> hst;  // the norms of the last host read
 };
 
 // info from hst: (scale_a, scale_a), (residual_a, residual_a)
@@ -1902,104 +1986,176 @@ static bool adjoint_norms_pass(const std::vector<double>& hst, int k, double tol
   return pass;
 }
 
-// the acceptance of step n from the norms in hst (after adjoint_component_info)
+// the acceptance of step n from the k pairs of norms in hst (after adjoint_component_info): the first component whose
+// check fails is named; the saturation's, where there is one, before any component's
 static pfv_status adjoint_accept(pfv_ctx* h, std::vector<pfv_solve_info>& info, const std::vector<double>& hst, int k,
-                                 double rtol, int n) {
-  int bad = -1;  // the first component whose check fails
+                                 double rtol, int n, int saturation) {
+  int bad = -1;
   for (int a = k - 1; a >= 0; --a) {
     info[(size_t)a].converged = hst[(size_t)k + a] <= rtol * rtol * hst[(size_t)a] ? 1 : 0;  // (0 <= 0 counts)
     if (!info[(size_t)a].converged) bad = a;
   }
+  if (saturation >= 0 && !info[(size_t)saturation].converged) bad = saturation;
   if (bad < 0) return PFV_OK;
   h->err = "adjoint step " + std::to_string(n) + ": relative residual " + std::to_string(info[(size_t)bad].rel_residual) +
-           " of component " + std::to_string(bad) +
+           (bad == saturation ? std::string() : " of component " + std::to_string(bad)) +
            " after the transposed sweep (a flux that contradicts the discretization's?)";
   return PFV_ERR_NOT_CONVERGED;
 }
 
-// solve(n, z) -> PFV_OK or the verdict of a refused step (its text in h->err): lambda^n into z from the right-hand side
-// aj_r; it fills run.info and counts run.launches / run.core_total.  step_grads(z): what the accepted step adds to the
-// call's other gradients (c^n in aj_sB).  rest_out(): the outputs beyond the three cell gradients.
-static pfv_status adjoint_steps(pfv_ctx* h, std::unique_ptr<pfv::Timer>& tm, const AdjointCall& A, AdjointRun& run,
+// solve(n, z) -> PFV_OK or the verdict of a refused step (its text in h->err): the multipliers of step n, lambda^n into
+// z, from the right-hand side(s); it fills run.info and counts run.launches / run.core_total (adjoint_sweep_solve).
+// step_grads(z): what the accepted step adds to the gradients the right-hand-side pass does not sum.
+static pfv_status adjoint_steps(pfv_ctx* h, AdjointSetup& S, const AdjointCall& A, AdjointRun& run,
                                 const std::function<pfv_status(int, double*)>& solve,
-                                const std::function<void(double*)>& step_grads, const std::function<void()>& rest_out) {
+                                const std::function<void(double*)>& step_grads) {
+  pfv::pfv_ctx_impl& cx = *h;
   const int k = A.k;
   const size_t nc = (size_t)h->nc;
-  const int32_t* slot = A.obs_cells ? h->aj_slot.p : nullptr;
-  // slab n of the states, interleaved into `to`
-  auto stage_slab = [&](int n, double* to) {
+  const auto stage = A.stage ? A.stage : [&](int n) {  // (c^0 only where the last pass reads it)
+    if (!A.states || (n == 0 && !A.grad_accumulation)) return;
     const double* src = A.states + (size_t)n * k * nc;
     if (!h->vectors_on_device) {
-      be_h2d(h->aj_state_in.p, src, sizeof(double) * k * nc, h->stream);
-      src = h->aj_state_in.p;
+      be_h2d(cx.aj_state_in.p, src, sizeof(double) * k * nc, cx.stream);
+      src = cx.aj_state_in.p;
     }
-    pfv::multi_interleave(*h, (int64_t)nc, k, src, to);
+    pfv::multi_interleave(cx, (int64_t)nc, k, src, cx.aj_sB.p);  // c^n; aj_sA holds c^{n+1}
   };
-  run.info.assign((size_t)k, pfv_solve_info{});
-  pfv_status st = PFV_OK;
+  // g^n + acc o lambda^{n+1}, fused with what lambda^{n+1} adds to grad_source and grad_accumulation (adjoint_step_rhs);
+  // the last pass leaves acc o lambda^1
+  const auto rhs = A.rhs ? A.rhs : [&](int n, bool have_next) {
+    if (n == 0 && !have_next) {
+      pfv::be_memset(cx.aj_r.p, 0, sizeof(double) * k * nc, cx.stream);
+      return;
+    }
+    pfv::adjoint_step_rhs(cx, k, A.acc, have_next ? cx.aj_lam.p : nullptr, n > 0 && A.obs_cells ? cx.aj_slot.p : nullptr,
+                          n > 0 ? cx.aj_loads.p + (size_t)(n - 1) * k * (size_t)A.n_obs : nullptr, n > 0 ? A.n_obs : 0,
+                          cx.aj_sB.p, cx.aj_sA.p, A.grad_source ? cx.aj_gsrc.p : nullptr,
+                          A.grad_accumulation ? cx.aj_gacc.p : nullptr, cx.aj_r.p);
+  };
+  const auto swap = A.swap ? A.swap : [&] {
+    cx.aj_lam.swap(cx.aj_lam2);
+    cx.aj_sA.swap(cx.aj_sB);
+  };
+  run.info.assign((size_t)k + (A.saturation >= 0 ? 1 : 0), pfv_solve_info{});
+  pfv_status st = guarded(h, [&] {
+    for (const AdjointGrad& g : A.grads)
+      if (g.to && g.summed) pfv::be_memset(g.buf->ensure(g.n), 0, sizeof(double) * g.n, cx.stream);
+  });
   std::string err;
-  bool have_lam = false;  // aj_lam holds lambda^{n+1}
+  bool have_next = false;  // the multipliers of step n + 1 are there
   for (int n = A.n_steps; n >= 1 && st == PFV_OK; --n) {
     pfv_status verdict = PFV_OK;
     st = guarded(h, [&] {
-      pfv::pfv_ctx_impl& cx = *h;
-      if (A.states) stage_slab(n, cx.aj_sB.p);  // c^n; aj_sA holds c^{n+1}
-      pfv::adjoint_step_rhs(cx, k, A.acc, have_lam ? cx.aj_lam.p : nullptr, slot,
-                            cx.aj_loads.p + (size_t)(n - 1) * k * (size_t)A.n_obs, A.n_obs, cx.aj_sB.p, cx.aj_sA.p,
-                            A.grad_source ? cx.aj_gsrc.p : nullptr, A.grad_accumulation ? cx.aj_gacc.p : nullptr,
-                            cx.aj_r.p);
+      stage(n);
+      rhs(n, have_next);
       double* z = cx.aj_lam2.p;
       verdict = solve(n, z);
       if (verdict != PFV_OK) return;
       step_grads(z);
-      cx.aj_lam.swap(cx.aj_lam2);
-      cx.aj_sA.swap(cx.aj_sB);
-      have_lam = true;
+      swap();
+      have_next = true;
       ++run.completed;
     });
     if (st == PFV_OK) st = verdict;
   }
   if (st != PFV_OK) err = h->err;
   const pfv_status st2 = guarded(h, [&] {
-    pfv::pfv_ctx_impl& cx = *h;
     if (st == PFV_OK) {
-      // lambda^1 into the cell gradients; the right-hand side it leaves is acc o lambda^1
-      if (have_lam && A.grad_accumulation) stage_slab(0, cx.aj_sB.p);  // c^0
-      if (have_lam)
-        pfv::adjoint_step_rhs(cx, k, A.acc, cx.aj_lam.p, nullptr, nullptr, 0, cx.aj_sB.p, cx.aj_sA.p,
-                              A.grad_source ? cx.aj_gsrc.p : nullptr, A.grad_accumulation ? cx.aj_gacc.p : nullptr,
-                              cx.aj_r.p);
-      else
-        pfv::be_memset(cx.aj_r.p, 0, sizeof(double) * k * nc, cx.stream);
+      if (have_next) stage(0);
+      rhs(0, have_next);
     }
-    run.ms = tm->stop(cx.stream);
-    tm.reset();
-    if (st == PFV_OK) {
-      auto cells_out = [&](double* to, const double* from) {
-        pfv::multi_deinterleave(cx, (int64_t)nc, k, from, cx.mc_c.p);
-        vec_out(h, to, cx.mc_c.p, k * nc);
-      };
-      if (A.grad_c0) cells_out(A.grad_c0, cx.aj_r.p);
-      if (A.grad_source) cells_out(A.grad_source, cx.aj_gsrc.p);
-      if (A.grad_accumulation) cells_out(A.grad_accumulation, cx.aj_gacc.p);
-      rest_out();
-    }
+    run.ms = S.tm->stop(cx.stream);
+    S.tm.reset();
+    if (st == PFV_OK)
+      for (const AdjointGrad& g : A.grads) {
+        if (!g.to) continue;
+        if (g.layout == GradLayout::host) {
+          be_d2h(g.to, g.buf->p, sizeof(double) * g.n, cx.stream);
+        } else if (g.layout == GradLayout::by_cell) {
+          pfv::multi_deinterleave(cx, (int64_t)nc, k, g.buf->p, cx.mc_c.p);
+          vec_out(h, g.to, cx.mc_c.p, g.n);
+        } else {
+          vec_out(h, g.to, g.buf->p, g.n);
+        }
+      }
     pfv::be_sync(cx.stream);
     upwind_drop_transport(h, true);
   });
   if (A.steps_done) *A.steps_done = run.completed;
-  if (A.last)
-    for (int a = 0; a < k; ++a) {
-      A.last[a] = run.info[(size_t)a];
-      if (run.completed > 0) A.last[a].solve_ms = run.ms / run.completed;
-    }
+  if (A.last) {
+    int to = 0;
+    if (A.saturation >= 0) A.last[to++] = run.info[(size_t)A.saturation];
+    for (int a = 0; a < (int)run.info.size(); ++a)
+      if (a != A.saturation) A.last[to++] = run.info[(size_t)a];
+    if (run.completed > 0)
+      for (int a = 0; a < to; ++a) A.last[a].solve_ms = run.ms / run.completed;
+  }
   return step_status(h, st, err, st2);
 }
 
+// ---- the solve of one adjoint step --------------------------------------------------------------------------------------
+// The backward-peel levels from last to first, the core level iterated by Jacobi on its transposed rows (a host read
+// every kNlCoreCheck-th iteration), the forward-peel levels, the residual norms of all rows and ONE host read; then the
+// acceptance.  The calls differ in their rows and their norms:
+struct AdjointSolve {
+  int pairs;        // of norms in out: (scale_a, scale_a) for all a, then (residual_a, residual_a)
+  int saturation;   // adjoint_accept's
+  const double* out;
+  std::function<int64_t(int, int)> levels;  // the levels [from, to), from last to first; returns its launches
+  std::function<void()> core_zero;          // the unknowns of the core to zero
+  std::function<void()> core_step;          // one iteration on the core: the copy, then its rows
+  std::function<void(bool)> norms;          // into out: of the core's rows only, or of all
+  // A word behind the norms that the kernels set to an index (kNoOffender: not set), and what it means for step n: a
+  // verdict, or an Error thrown.  flag_ends_core: the word says that the input admits no solution -- it ends the core's
+  // iteration and is judged before anything else; otherwise it is judged on the finished sweep, before the acceptance.
+  std::function<pfv_status(int, int32_t)> flagged;
+  bool flag_ends_core = false;
+};
+static pfv_status adjoint_sweep_solve(pfv_ctx* h, const AdjointSolve& V, AdjointRun& run, double rtol, int maxit,
+                                      int n) {
+  pfv::pfv_ctx_impl& cx = *h;
+  const pfv::Sweep& sw = *cx.sweep;
+  const int K = V.pairs;
+  std::vector<double>& hst = run.hst;
+  hst.resize(2 * (size_t)K + (V.flagged ? 1 : 0));
+  auto flag = [&] {
+    int32_t w = kNoOffender;
+    if (V.flagged) std::memcpy(&w, hst.data() + 2 * K, sizeof(w));
+    return w;
+  };
+  const bool has_core = sw.n_core > 0;
+  const int core = has_core ? sw.core_level : -1;
+  run.launches = V.levels(core + 1, sw.nlev);
+  int core_it = 0;
+  if (has_core) {
+    V.core_zero();
+    const CoreRun cr = core_iterate(h, maxit, V.out, hst, V.core_step, [&] { V.norms(true); }, [&] {
+      return (V.flag_ends_core && flag() != kNoOffender) || adjoint_norms_pass(hst, K, 0.5 * rtol);
+    });
+    core_it = cr.iterations;
+    run.core_total += core_it;
+    run.launches += 2;
+    if (V.flag_ends_core && flag() != kNoOffender) return V.flagged(n, flag());
+    if (!cr.settled) {  // (what the forward-peel levels would compute from this core is not judged)
+      adjoint_component_info(run.info, hst, K, core_it);
+      cx.err = "adjoint step " + std::to_string(n) + ": the cyclic core of " + std::to_string(sw.n_core) +
+               " cells did not settle in " + std::to_string(core_it) + " iterations";
+      return PFV_ERR_NOT_CONVERGED;
+    }
+    run.launches += V.levels(0, core);
+  }
+  V.norms(false);
+  be_d2h(hst.data(), V.out, sizeof(double) * hst.size(), cx.stream);
+  if (V.flag_ends_core && flag() != kNoOffender) return V.flagged(n, flag());
+  adjoint_component_info(run.info, hst, K, has_core ? core_it : 1);
+  if (flag() != kNoOffender) return V.flagged(n, flag());
+  return adjoint_accept(h, run.info, hst, K, rtol, n, V.saturation);
+}
+
 // ---- the adjoint of the k-component step: one transposed sweep in reverse flow order per step (sweep.inc) -------------
-// In the frame of adjoint_steps, the solve of a step: the backward-peel levels from last to first, the core level
-// iterated by Jacobi on its transposed rows (a host read every kNlCoreCheck-th iteration), the forward-peel levels, the
-// residual norms of all components and ONE host read; then the two face kernels (grad_bc_values, grad_flux).
+// In the frame of adjoint_steps with the solve of adjoint_sweep_solve on the rows of sweep_row_multi_t; after an accepted
+// step the two face kernels (grad_bc_values, grad_flux).
 pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, const double* bc_values,
                                        const double* accumulation, int n_steps, int64_t n_obs, const int32_t* obs_cells,
                                        const double* loads, const double* states, double rtol, int maxit,
@@ -2008,20 +2164,16 @@ pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, 
                                        pfv_solve_info* last) {
   if (steps_done) *steps_done = 0;
   const int k = n_comp;
-  std::unique_ptr<pfv::Timer> tm;
-  bool touched = false;
-  double order_ms = 0.0;
+  AdjointSetup S;
   const double* d_q = nullptr;
   size_t nc = 0, nf = 0;
-  pfv_status st = guarded(h, [&] {
+  pfv_status st = adjoint_setup(h, S, [&] {
     upwind_supported(h);
     require(h->have_upwind, "pfv_upwind_discretize first");
     require(h->upw_ncomp == 1, "the components share one discretization: pfv_upwind_discretize with num_components = 1");
     require(n_comp >= 1 && n_comp <= 64, "n_comp must lie in 1 .. 64");
     require(bc_values && accumulation, "bc_values and accumulation are required");
-    require(n_steps >= 0, "bad argument");
-    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
-    require(loads != nullptr || n_steps == 0, "loads is required");
+    adjoint_check_counts(n_steps, rtol, maxit, loads != nullptr);
     require(states || !grad_accumulation, "grad_accumulation needs states (c^0 .. c^N)");
     require(states || !grad_flux, "grad_flux needs states (c^0 .. c^N)");
     nc = (size_t)h->nc;
@@ -2033,98 +2185,59 @@ pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, 
     vec_in(h, h->mc_bc.ensure(k * nf), bc_values, k * nf);
     vec_in(h, h->mc_acc.ensure(k * nc), accumulation, k * nc);
     d_q = q ? h->mc_q.p : h->upw_q.p;
-    tm = std::make_unique<pfv::Timer>();
-    tm->start(h->stream);
-    // A = div diag(q) U without accumulation, once per call; its transposed values beside it
-    upwind_drop_transport(h, true);
-    touched = true;
-    pfv::upwind_assemble(*h, d_q, h->mc_bc.p, nullptr, nullptr, nullptr);
-    values_changed(h, Windows::drop);
-    pfv::multi_interleave(*h, (int64_t)nc, k, h->mc_acc.p, h->mc_acc_i.ensure(k * nc));
-    const int64_t zd = pfv::upwind_zero_diag_multi(*h, k, h->diag_t.p, h->mc_acc_i.p);
-    if (zd >= 0)
-      throw Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(zd / k) + ", component " +
-                                           std::to_string(zd % k) + " of the transport system (a cell without outflow "
-                                           "and without an accumulation term): the solvers do not apply");
-    const size_t nnz = (size_t)std::max<int64_t>(h->pat_T.nnz, 1);
-    if (!h->have_tpos_T) {
-      pfv::sweep_transpose_positions(*h, h->pat_T, h->tpos_T.ensure(nnz));
-      h->have_tpos_T = true;
-    }
-    pfv::sweep_transpose_values(*h, h->pat_T.nnz, h->tpos_T.p, h->val[PFV_MAT_TRANSPORT_SYSTEM].p, h->valT_T.ensure(nnz));
-    adjoint_take_slots(h, n_obs, obs_cells);
-    for (pfv::Buf<double>* b : {&h->aj_lam, &h->aj_lam2, &h->aj_prev, &h->aj_r}) b->ensure(k * nc);
-    if (states) {
-      h->aj_sA.ensure(k * nc);
-      h->aj_sB.ensure(k * nc);
-      if (!h->vectors_on_device) h->aj_state_in.ensure(k * nc);
-    }
-    if (grad_source) pfv::be_memset(h->aj_gsrc.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
-    if (grad_accumulation) pfv::be_memset(h->aj_gacc.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
-    if (grad_bc_values) pfv::be_memset(h->aj_gbc.ensure(k * nf), 0, sizeof(double) * k * nf, h->stream);
-    if (grad_flux) pfv::be_memset(h->aj_gq.ensure(nf), 0, sizeof(double) * nf, h->stream);
+    adjoint_system(h, S, d_q, h->mc_bc.p, n_obs, obs_cells, [&] {
+      pfv::multi_interleave(*h, (int64_t)nc, k, h->mc_acc.p, h->mc_acc_i.ensure(k * nc));
+      const int64_t zd = pfv::upwind_zero_diag_multi(*h, k, h->diag_t.p, h->mc_acc_i.p);
+      if (zd >= 0)
+        throw Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(zd / k) + ", component " +
+                                             std::to_string(zd % k) + " of the transport system (a cell without outflow "
+                                             "and without an accumulation term): the solvers do not apply");
+    });
+    for (pfv::Buf<double>* b : {&h->aj_lam, &h->aj_lam2, &h->aj_prev, &h->aj_r, &h->mc_c}) b->ensure(k * nc);
+    if (states) adjoint_slab_buffers(h, k);
     h->mc_nrm.ensure(2 * (size_t)k);
-    h->mc_c.ensure(k * nc);
-    transport_order(h, d_q, order_ms);
   });
-  if (st != PFV_OK) {
-    if (touched) upwind_drop_transport(h, true);  // (A without accumulation: not a system to be solved with)
-    return st;
-  }
+  if (st != PFV_OK) return st;
 
   AdjointRun run;
-  std::vector<double> hst(2 * (size_t)k);
-  const AdjointCall call{k, n_steps, n_obs, obs_cells, states, h->mc_acc_i.p, grad_c0, grad_source, grad_accumulation,
-                         steps_done, last};
-  st = adjoint_steps(h, tm, call, run, [&](int n, double* z) -> pfv_status {
+  AdjointCall call{k, n_steps, n_obs, obs_cells, states, h->mc_acc_i.p, grad_source, grad_accumulation, steps_done,
+                   last};
+  call.grads = {{grad_c0, &h->aj_r, k * nc, GradLayout::by_cell, false},
+                {grad_source, &h->aj_gsrc, k * nc, GradLayout::by_cell},
+                {grad_accumulation, &h->aj_gacc, k * nc, GradLayout::by_cell},
+                {grad_bc_values, &h->aj_gbc, k * nf, GradLayout::plain},
+                {grad_flux, &h->aj_gq, nf, GradLayout::plain}};
+  st = adjoint_steps(h, S, call, run, [&](int n, double* z) -> pfv_status {
     pfv::pfv_ctx_impl& cx = *h;
     const pfv::Sweep& sw = *cx.sweep;
-    const double* valT = cx.valT_T.p;
-    const double* acc = cx.mc_acc_i.p;
-    double* out = cx.mc_nrm.p;
-    const bool has_core = sw.n_core > 0;
-    const int core = has_core ? sw.core_level : -1;
-    run.launches = pfv::sweep_apply_multi_t(cx, sw, core + 1, sw.nlev, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, z);
-    int core_it = 0;
-    if (has_core) {
-      pfv::sweep_core_zero(cx, sw, k, z);
-      const CoreRun cr = core_iterate(h, maxit, out, hst, [&] {
-        pfv::sweep_core_copy(cx, sw, k, z, cx.aj_prev.p);
-        pfv::sweep_core_multi_t(cx, sw, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, cx.aj_prev.p, z);
-      }, [&] {
-        pfv::sweep_core_norms_multi_t(cx, sw, cx.pat_T, valT, acc, k, cx.aj_r.p, z, out);
-      }, [&] { return adjoint_norms_pass(hst, k, 0.5 * rtol); });
-      core_it = cr.iterations;
-      run.core_total += core_it;
-      run.launches += 2;
-      if (!cr.settled) {  // (what the forward-peel levels would compute from this core is not judged)
-        adjoint_component_info(run.info, hst, k, core_it);
-        cx.err = "adjoint step " + std::to_string(n) + ": the cyclic core of " + std::to_string(sw.n_core) +
-                 " cells did not settle in " + std::to_string(core_it) + " iterations";
-        return PFV_ERR_NOT_CONVERGED;
-      }
-      run.launches += pfv::sweep_apply_multi_t(cx, sw, 0, core, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, z);
-    }
-    pfv::sweep_residual_norms_multi(cx, cx.pat_T, valT, acc, k, cx.aj_r.p, z, out);  // (valT: the image under S^T)
-    be_d2h(hst.data(), out, sizeof(double) * hst.size(), cx.stream);
-    adjoint_component_info(run.info, hst, k, has_core ? core_it : 1);
-    return adjoint_accept(h, run.info, hst, k, rtol, n);
+    const double *valT = cx.valT_T.p, *acc = cx.mc_acc_i.p;
+    AdjointSolve V{k, -1, cx.mc_nrm.p};
+    V.levels = [&](int from, int to) {
+      return pfv::sweep_apply_multi_t(cx, sw, from, to, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, z);
+    };
+    V.core_zero = [&] { pfv::sweep_core_zero(cx, sw, k, z); };
+    V.core_step = [&] {
+      pfv::sweep_core_copy(cx, sw, k, z, cx.aj_prev.p);
+      pfv::sweep_core_multi_t(cx, sw, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, cx.aj_prev.p, z);
+    };
+    V.norms = [&](bool core_only) {  // (valT: the image under S^T)
+      if (core_only) pfv::sweep_core_norms_multi_t(cx, sw, cx.pat_T, valT, acc, k, cx.aj_r.p, z, cx.mc_nrm.p);
+      else pfv::sweep_residual_norms_multi(cx, cx.pat_T, valT, acc, k, cx.aj_r.p, z, cx.mc_nrm.p);
+    };
+    return adjoint_sweep_solve(h, V, run, rtol, maxit, n);
   }, [&](double* z) {
     if (grad_bc_values) pfv::adjoint_grad_bc(*h, k, d_q, z, h->aj_gbc.p);
     if (grad_flux) pfv::adjoint_grad_flux(*h, k, h->mc_bc.p, z, h->aj_sB.p, h->aj_gq.p);
-  }, [&] {
-    if (grad_bc_values) vec_out(h, grad_bc_values, h->aj_gbc.p, k * nf);
-    if (grad_flux) vec_out(h, grad_flux, h->aj_gq.p, nf);
   });
   h->stats.transport_adjoint_ms = run.ms;
   h->stats.transport_adjoint_steps = run.completed;
   h->stats.transport_adjoint_core_iterations = run.core_total;
-  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, order_ms);
+  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, S.order_ms);
   return st;
 }
 
 // ---- the adjoint of the reactive step: one transposed k x k sweep in reverse flow order per step (sweep.inc) ----------
-// The frame is that of pfv_transport_adjoint_multi with the row, the acceptance test and the core of
+// The frame and the solve are those of pfv_transport_adjoint_multi with the row, the norms and the core of
 // pfv_transport_advance_react in the transposed system M^T lambda^n = g^n + acc o lambda^{n+1}: the rows read valT and a
 // ReactPar that holds K^T (sweep_row_react<K, Descending>), the image and the scale g~_a = r_a - rho sum_{b != a} K_ba
 // lambda_b come from sweep_react_image on the same two.  After an accepted step the face kernels take the mobility and
@@ -2137,13 +2250,11 @@ pfv_status pfv_transport_adjoint_react(pfv_ctx* h, const double* q, int k, const
                                        double* grad_accumulation, double* grad_flux, double* grad_rate,
                                        double* grad_rate_weight, int32_t* steps_done, pfv_solve_info* last) {
   if (steps_done) *steps_done = 0;
-  std::unique_ptr<pfv::Timer> tm;
-  bool touched = false;
-  double order_ms = 0.0;
+  AdjointSetup S;
   const double* d_q = nullptr;
   size_t nc = 0, nf = 0;
   pfv::ReactPar par, parT;
-  pfv_status st = guarded(h, [&] {
+  pfv_status st = adjoint_setup(h, S, [&] {
     upwind_supported(h);
     if (h->subface_bc) throw Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
     require(h->have_upwind, "pfv_upwind_discretize first");
@@ -2151,9 +2262,7 @@ pfv_status pfv_transport_adjoint_react(pfv_ctx* h, const double* q, int k, const
     const std::string bad = pfv::react_check(k, rate, mobility);  // (the caller's K, not its transpose)
     if (!bad.empty()) throw Error(PFV_ERR_ARGUMENT, bad);
     require(bc_values && accumulation, "bc_values and accumulation are required");
-    require(n_steps >= 0, "bad argument");
-    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
-    require(loads != nullptr || n_steps == 0, "loads is required");
+    adjoint_check_counts(n_steps, rtol, maxit, loads != nullptr);
     require(states || !grad_accumulation, "grad_accumulation needs states (c^0 .. c^N)");
     require(states || !grad_flux, "grad_flux needs states (c^0 .. c^N)");
     require(states || !grad_rate, "grad_rate needs states (c^0 .. c^N)");
@@ -2175,106 +2284,61 @@ pfv_status pfv_transport_adjoint_react(pfv_ctx* h, const double* q, int k, const
     if (rate_weight) vec_in(h, h->rc_rho.ensure(nc), rate_weight, nc);
     d_q = q ? h->rc_q.p : h->upw_q.p;
     pfv::upwind_face_cells(*h);
-    int32_t off[pfv::kReactChecks];  // (the call has no state to check: the accumulation stands in, off[2] says nothing)
+    int32_t off[pfv::kReactChecks];  // (the call has no state to check: the accumulation stands in)
     pfv::sweep_react_check_inputs(*h, d_q, k, h->rc_bc.p, h->rc_acc_in.p, rate_weight ? h->rc_rho.p : nullptr,
                                   h->rc_acc_in.p, h->rc_par.p, off);
-    auto comp = [&](int32_t v) { return std::to_string(v / k) + ", component " + std::to_string(v % k); };
-    if (off[0] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, "accumulation must be positive: cell " + comp(off[0]));
-    if (off[1] != 0x7f7f7f7f)
-      throw Error(PFV_ERR_ARGUMENT, "rate_weight must not be negative: cell " + std::to_string(off[1]));
-    if (off[3] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, "bc_values is not finite on face " + comp(off[3]));
-    if (off[4] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, pfv::kUnmarkedInflowFace + std::to_string(off[4]));
-    tm = std::make_unique<pfv::Timer>();
-    tm->start(h->stream);
-    // A = div diag(q) U without accumulation, once per call; its transposed values beside it
-    upwind_drop_transport(h, true);
-    touched = true;
-    pfv::upwind_assemble(*h, d_q, h->rc_bc.p, nullptr, nullptr, nullptr);
-    values_changed(h, Windows::drop);
-    pfv::multi_interleave(*h, (int64_t)nc, k, h->rc_acc_in.p, h->rc_acc.ensure(k * nc));
-    const size_t nnz = (size_t)std::max<int64_t>(h->pat_T.nnz, 1);
-    if (!h->have_tpos_T) {
-      pfv::sweep_transpose_positions(*h, h->pat_T, h->tpos_T.ensure(nnz));
-      h->have_tpos_T = true;
-    }
-    pfv::sweep_transpose_values(*h, h->pat_T.nnz, h->tpos_T.p, h->val[PFV_MAT_TRANSPORT_SYSTEM].p, h->valT_T.ensure(nnz));
-    adjoint_take_slots(h, n_obs, obs_cells);
+    react_inputs_refused(off, k, kReactState);
+    adjoint_system(h, S, d_q, h->rc_bc.p, n_obs, obs_cells, [&] {
+      pfv::multi_interleave(*h, (int64_t)nc, k, h->rc_acc_in.p, h->rc_acc.ensure(k * nc));
+    });
     for (pfv::Buf<double>* b : {&h->aj_lam, &h->aj_lam2, &h->aj_r, &h->rc_prev, &h->rc_g, &h->rc_F, &h->mc_c})
       b->ensure(k * nc);
-    if (states) {
-      h->aj_sA.ensure(k * nc);
-      h->aj_sB.ensure(k * nc);
-      if (!h->vectors_on_device) h->aj_state_in.ensure(k * nc);
-    }
-    if (grad_source) pfv::be_memset(h->aj_gsrc.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
-    if (grad_accumulation) pfv::be_memset(h->aj_gacc.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
-    if (grad_bc_values) pfv::be_memset(h->aj_gbc.ensure(k * nf), 0, sizeof(double) * k * nf, h->stream);
-    if (grad_flux) pfv::be_memset(h->aj_gq.ensure(nf), 0, sizeof(double) * nf, h->stream);
-    if (grad_rate) pfv::be_memset(h->aj_gK.ensure((size_t)k * k), 0, sizeof(double) * k * k, h->stream);
-    if (grad_rate_weight) pfv::be_memset(h->aj_grho.ensure(nc), 0, sizeof(double) * nc, h->stream);
+    if (states) adjoint_slab_buffers(h, k);
     h->rc_out.ensure(2 * (size_t)k + 1);
-    transport_order(h, d_q, order_ms);
   });
-  if (st != PFV_OK) {
-    if (touched) upwind_drop_transport(h, true);  // (A without accumulation: not a system to be solved with)
-    return st;
-  }
+  if (st != PFV_OK) return st;
 
   AdjointRun run;
-  std::vector<double> hst(2 * (size_t)k + 1);
   const double* rho = rate_weight ? h->rc_rho.p : nullptr;
-  const AdjointCall call{k, n_steps, n_obs, obs_cells, states, h->rc_acc.p, grad_c0, grad_source, grad_accumulation,
-                         steps_done, last};
-  st = adjoint_steps(h, tm, call, run, [&](int n, double* z) -> pfv_status {
+  AdjointCall call{k, n_steps, n_obs, obs_cells, states, h->rc_acc.p, grad_source, grad_accumulation, steps_done, last};
+  call.grads = {{grad_c0, &h->aj_r, k * nc, GradLayout::by_cell, false},
+                {grad_source, &h->aj_gsrc, k * nc, GradLayout::by_cell},
+                {grad_accumulation, &h->aj_gacc, k * nc, GradLayout::by_cell},
+                {grad_bc_values, &h->aj_gbc, k * nf, GradLayout::plain},
+                {grad_flux, &h->aj_gq, nf, GradLayout::plain},
+                {grad_rate_weight, &h->aj_grho, nc, GradLayout::plain},
+                {grad_rate, &h->aj_gK, (size_t)k * k, GradLayout::host}};
+  st = adjoint_steps(h, S, call, run, [&](int n, double* z) -> pfv_status {
     pfv::pfv_ctx_impl& cx = *h;
     const pfv::Sweep& sw = *cx.sweep;
-    const double* valT = cx.valT_T.p;
-    const double* acc = cx.rc_acc.p;
+    const double *valT = cx.valT_T.p, *acc = cx.rc_acc.p;
     double* out = cx.rc_out.p;
     int32_t* status = reinterpret_cast<int32_t*>(out + 2 * k);
-    const bool has_core = sw.n_core > 0;
-    const int core = has_core ? sw.core_level : -1;
     pfv::ReactRow A{cx.pat_T.indptr, cx.pat_T.indices, sw.lev(false), valT, cx.diag_t.p, acc, rho,
                     cx.aj_r.p, nullptr, z, status};
     pfv::ReactRow Ac = A;  // the core level, with the previous iterate
     Ac.c_prev = cx.rc_prev.p;
     pfv::be_memset(status, 0x7f, sizeof(double), cx.stream);
-    run.launches = pfv::sweep_apply_react(cx, sw, core + 1, sw.nlev, k, A, parT, pfv::Descending{});
-    int core_it = 0;
-    if (has_core) {
-      pfv::sweep_core_zero(cx, sw, k, z);
-      const CoreRun cr = core_iterate(h, maxit, out, hst, [&] {
-        pfv::sweep_core_copy(cx, sw, k, z, cx.rc_prev.p);
-        pfv::sweep_levels_react(cx, sw, core, core + 1, k, Ac, parT, pfv::Descending{});
-      }, [&] {
-        pfv::sweep_react_image(cx, cx.pat_T, valT, k, acc, rho, cx.aj_r.p, cx.rc_parT.p, z, A.lev, core, cx.rc_g.p,
-                               cx.rc_F.p, true);
-        pfv::sweep_react_norms(cx, cx.nc, k, cx.rc_g.p, cx.rc_F.p, out);
-      }, [&] { return adjoint_norms_pass(hst, k, 0.5 * rtol); });
-      core_it = cr.iterations;
-      run.core_total += core_it;
-      run.launches += 2;
-      if (!cr.settled) {  // (what the forward-peel levels would compute from this core is not judged)
-        adjoint_component_info(run.info, hst, k, core_it);
-        cx.err = "adjoint step " + std::to_string(n) + ": the cyclic core of " + std::to_string(sw.n_core) +
-                 " cells did not settle in " + std::to_string(core_it) + " iterations";
-        return PFV_ERR_NOT_CONVERGED;
-      }
-      run.launches += pfv::sweep_apply_react(cx, sw, 0, core, k, A, parT, pfv::Descending{});
-    }
-    pfv::sweep_react_image(cx, cx.pat_T, valT, k, acc, rho, cx.aj_r.p, cx.rc_parT.p, z, A.lev, -1, cx.rc_g.p, cx.rc_F.p,
-                           true);
-    pfv::sweep_react_norms(cx, cx.nc, k, cx.rc_g.p, cx.rc_F.p, out);
-    be_d2h(hst.data(), out, sizeof(double) * hst.size(), cx.stream);
-    adjoint_component_info(run.info, hst, k, has_core ? core_it : 1);  // from hst: (g~_a, g~_a), (F_a, F_a)
-    int32_t cell;
-    std::memcpy(&cell, hst.data() + 2 * k, sizeof(cell));
-    if (cell != 0x7f7f7f7f) {
-      cx.err = "adjoint step " + std::to_string(n) + ": the block of cell " + std::to_string(cell) +
+    AdjointSolve V{k, -1, out};
+    V.levels = [&](int from, int to) {
+      return pfv::sweep_apply_react(cx, sw, from, to, k, A, parT, pfv::Descending{});
+    };
+    V.core_zero = [&] { pfv::sweep_core_zero(cx, sw, k, z); };
+    V.core_step = [&] {
+      pfv::sweep_core_copy(cx, sw, k, z, cx.rc_prev.p);
+      pfv::sweep_levels_react(cx, sw, sw.core_level, sw.core_level + 1, k, Ac, parT, pfv::Descending{});
+    };
+    V.norms = [&](bool core_only) {  // from hst: (g~_a, g~_a), (F_a, F_a)
+      pfv::sweep_react_image(cx, cx.pat_T, valT, k, acc, rho, cx.aj_r.p, cx.rc_parT.p, z, A.lev,
+                             core_only ? sw.core_level : -1, cx.rc_g.p, cx.rc_F.p, true);
+      pfv::sweep_react_norms(cx, cx.nc, k, cx.rc_g.p, cx.rc_F.p, out);
+    };
+    V.flagged = [&](int step, int32_t cell) {
+      cx.err = "adjoint step " + std::to_string(step) + ": the block of cell " + std::to_string(cell) +
                " has a pivot that is not positive and finite";
       return PFV_ERR_NOT_CONVERGED;
-    }
-    return adjoint_accept(h, run.info, hst, k, rtol, n);
+    };
+    return adjoint_sweep_solve(h, V, run, rtol, maxit, n);
   }, [&](double* z) {
     pfv::pfv_ctx_impl& cx = *h;
     if (grad_bc_values) pfv::adjoint_grad_bc(cx, k, d_q, z, cx.aj_gbc.p, cx.rc_par.p);
@@ -2282,25 +2346,33 @@ pfv_status pfv_transport_adjoint_react(pfv_ctx* h, const double* q, int k, const
     if (grad_rate) pfv::adjoint_grad_rate(cx, k, rho, z, cx.aj_sB.p, cx.aj_gK.p);
     if (grad_rate_weight)
       pfv::adjoint_grad_rate_weight(cx, k, cx.rc_par.p + pfv::kReactMax, z, cx.aj_sB.p, cx.aj_grho.p);
-  }, [&] {
-    if (grad_bc_values) vec_out(h, grad_bc_values, h->aj_gbc.p, k * nf);
-    if (grad_flux) vec_out(h, grad_flux, h->aj_gq.p, nf);
-    if (grad_rate_weight) vec_out(h, grad_rate_weight, h->aj_grho.p, nc);
-    if (grad_rate) be_d2h(grad_rate, h->aj_gK.p, sizeof(double) * k * k, h->stream);  // (host memory, as rate is)
   });
   h->stats.transport_react_adjoint_ms = run.ms;
   h->stats.transport_react_adjoint_steps = run.completed;
   h->stats.transport_react_adjoint_core_iterations = run.core_total;
-  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, order_ms);
+  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, S.order_ms);
   return st;
+}
+
+// what the two saturation adjoints check before any array is read
+static void adjoint_nl_supported(pfv_ctx* h, int fluxfn_kind, const double* fluxfn_params, int n_params,
+                                 const double* grad_fluxfn, const double* bc_values, const double* accumulation) {
+  upwind_supported(h);
+  if (h->subface_bc) throw Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
+  require(h->have_upwind, "pfv_upwind_discretize first");
+  require(h->upw_ncomp == 1, "the saturation step needs pfv_upwind_discretize with num_components = 1");
+  const std::string bad = pfv::fluxfn_check(fluxfn_kind, fluxfn_params, n_params);
+  if (!bad.empty()) throw Error(PFV_ERR_ARGUMENT, bad);
+  require(!grad_fluxfn || fluxfn_kind == PFV_FLUXFN_COREY,
+          "grad_fluxfn is the gradient with respect to the six Corey parameters: PFV_FLUXFN_COREY only");
+  require(bc_values && accumulation, "bc_values and accumulation are required");
 }
 
 // ---- the adjoint of the saturation step: one transposed sweep on the step's slopes per step (sweep.inc) ---------------
 // In the frame of adjoint_steps with k = 1.  The solve of step n: d = f'(s^n) and phi = f(s^n) from the slab the frame
-// has staged (one streaming pass), then the frame of pfv_transport_adjoint_multi on the rows of J^T = diag(acc) +
-// diag(d) M^T (sweep_row_nl_t): the backward-peel levels from last to first, the core level iterated by Jacobi, the
-// forward-peel levels, the residual norms and ONE host read.  After an accepted step the two face kernels, the sink's
-// cell kernel and the six Corey sums, which are added in step order.
+// has staged (one streaming pass), then adjoint_sweep_solve on the rows of J^T = diag(acc) + diag(d) M^T
+// (sweep_row_nl_t).  After an accepted step the two face kernels, the sink's cell kernel and the six Corey sums, which
+// are added in step order.
 pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
                                     int n_params, const double* bc_values, const double* accumulation,
                                     const double* sink, int n_steps, int64_t n_obs, const int32_t* obs_cells,
@@ -2309,25 +2381,13 @@ pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind
                                     double* grad_sink, double* grad_flux, double* grad_fluxfn, int32_t* steps_done,
                                     pfv_solve_info* last) {
   if (steps_done) *steps_done = 0;
-  std::unique_ptr<pfv::Timer> tm;
-  bool touched = false;
-  double order_ms = 0.0;
+  AdjointSetup S;
   const double* d_q = nullptr;
   size_t nc = 0, nf = 0;
   pfv::FluxFn F;
-  pfv_status st = guarded(h, [&] {
-    upwind_supported(h);
-    if (h->subface_bc) throw Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
-    require(h->have_upwind, "pfv_upwind_discretize first");
-    require(h->upw_ncomp == 1, "the saturation step needs pfv_upwind_discretize with num_components = 1");
-    const std::string bad = pfv::fluxfn_check(fluxfn_kind, fluxfn_params, n_params);
-    if (!bad.empty()) throw Error(PFV_ERR_ARGUMENT, bad);
-    require(!grad_fluxfn || fluxfn_kind == PFV_FLUXFN_COREY,
-            "grad_fluxfn is the gradient with respect to the six Corey parameters: PFV_FLUXFN_COREY only");
-    require(bc_values && accumulation, "bc_values and accumulation are required");
-    require(n_steps >= 0, "bad argument");
-    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
-    require(loads != nullptr || n_steps == 0, "loads is required");
+  pfv_status st = adjoint_setup(h, S, [&] {
+    adjoint_nl_supported(h, fluxfn_kind, fluxfn_params, n_params, grad_fluxfn, bc_values, accumulation);
+    adjoint_check_counts(n_steps, rtol, maxit, loads != nullptr);
     require(states != nullptr || n_steps == 0, "states (s^0 .. s^N) is required: the step is linearised about them");
     nc = (size_t)h->nc;
     nf = (size_t)h->nf;
@@ -2338,87 +2398,49 @@ pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind
     if (sink) vec_in(h, h->nl_sink.ensure(nc), sink, nc);
     d_q = q ? h->nl_q.p : h->upw_q.p;
     pfv::upwind_face_cells(*h);
-    int32_t off[pfv::kNlChecks];  // (the states are not checked: the accumulation stands in, off[2] says nothing)
+    int32_t off[pfv::kNlChecks];  // (the states are not checked: the accumulation stands in)
     pfv::sweep_nl_check_inputs(*h, d_q, h->nl_bc.p, h->nl_acc.p, sink ? h->nl_sink.p : nullptr, h->nl_acc.p, 0, nullptr,
                                nullptr, nullptr, off);
-    static const char* what[5] = {"accumulation must be positive: cell ", "negative sink in cell ", nullptr,
-                                  "Dirichlet inflow value outside [0, 1] on face ", pfv::kUnmarkedInflowFace};
-    for (int m = 0; m < 5; ++m)
-      if (what[m] && off[m] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, what[m] + std::to_string(off[m]));
+    nl_inputs_refused(off, 0, kNlStates);
     if (fluxfn_kind == PFV_FLUXFN_TABLE)
       be_h2d(h->nl_table.ensure((size_t)n_params), fluxfn_params, sizeof(double) * (size_t)n_params, h->stream);
     F = pfv::fluxfn_make(fluxfn_kind, fluxfn_params, n_params, h->nl_table.p);
-    tm = std::make_unique<pfv::Timer>();
-    tm->start(h->stream);
-    // A = div diag(q) U without accumulation, once per call; its transposed values beside it
-    upwind_drop_transport(h, true);
-    touched = true;
-    pfv::upwind_assemble(*h, d_q, h->nl_bc.p, nullptr, nullptr, nullptr);
-    values_changed(h, Windows::drop);
-    const size_t nnz = (size_t)std::max<int64_t>(h->pat_T.nnz, 1);
-    if (!h->have_tpos_T) {
-      pfv::sweep_transpose_positions(*h, h->pat_T, h->tpos_T.ensure(nnz));
-      h->have_tpos_T = true;
-    }
-    pfv::sweep_transpose_values(*h, h->pat_T.nnz, h->tpos_T.p, h->val[PFV_MAT_TRANSPORT_SYSTEM].p, h->valT_T.ensure(nnz));
-    adjoint_take_slots(h, n_obs, obs_cells);
-    for (pfv::Buf<double>* b : {&h->aj_lam, &h->aj_lam2, &h->aj_prev, &h->aj_r, &h->aj_sA, &h->aj_sB, &h->aj_d, &h->aj_phi,
-                                &h->mc_c})
+    adjoint_system(h, S, d_q, h->nl_bc.p, n_obs, obs_cells);
+    for (pfv::Buf<double>* b : {&h->aj_lam, &h->aj_lam2, &h->aj_prev, &h->aj_r, &h->aj_d, &h->aj_phi, &h->mc_c})
       b->ensure(nc);
-    if (!h->vectors_on_device) h->aj_state_in.ensure(nc);
-    if (grad_source) pfv::be_memset(h->aj_gsrc.ensure(nc), 0, sizeof(double) * nc, h->stream);
-    if (grad_accumulation) pfv::be_memset(h->aj_gacc.ensure(nc), 0, sizeof(double) * nc, h->stream);
-    if (grad_sink) pfv::be_memset(h->aj_gsink.ensure(nc), 0, sizeof(double) * nc, h->stream);
-    if (grad_bc_values) pfv::be_memset(h->aj_gbc.ensure(nf), 0, sizeof(double) * nf, h->stream);
-    if (grad_flux) pfv::be_memset(h->aj_gq.ensure(nf), 0, sizeof(double) * nf, h->stream);
-    if (grad_fluxfn) pfv::be_memset(h->aj_gF.ensure(6), 0, sizeof(double) * 6, h->stream);
+    adjoint_slab_buffers(h, 1);
     h->mc_nrm.ensure(2);
-    transport_order(h, d_q, order_ms);
   });
-  if (st != PFV_OK) {
-    if (touched) upwind_drop_transport(h, true);  // (A without accumulation: not a system to be solved with)
-    return st;
-  }
+  if (st != PFV_OK) return st;
 
   AdjointRun run;
-  std::vector<double> hst(2);
   const double* d_sink = sink ? h->nl_sink.p : nullptr;
-  const AdjointCall call{1, n_steps, n_obs, obs_cells, states, h->nl_acc.p, grad_s0, grad_source, grad_accumulation,
-                         steps_done, last};
-  st = adjoint_steps(h, tm, call, run, [&](int n, double* z) -> pfv_status {
+  AdjointCall call{1, n_steps, n_obs, obs_cells, states, h->nl_acc.p, grad_source, grad_accumulation, steps_done, last};
+  call.grads = {{grad_s0, &h->aj_r, nc, GradLayout::by_cell, false},
+                {grad_source, &h->aj_gsrc, nc, GradLayout::by_cell},
+                {grad_accumulation, &h->aj_gacc, nc, GradLayout::by_cell},
+                {grad_bc_values, &h->aj_gbc, nf, GradLayout::plain},
+                {grad_flux, &h->aj_gq, nf, GradLayout::plain},
+                {grad_sink, &h->aj_gsink, nc, GradLayout::plain},
+                {grad_fluxfn, &h->aj_gF, 6, GradLayout::host}};
+  st = adjoint_steps(h, S, call, run, [&](int n, double* z) -> pfv_status {
     pfv::pfv_ctx_impl& cx = *h;
     const pfv::Sweep& sw = *cx.sweep;
-    const double* valT = cx.valT_T.p;
-    const double *acc = cx.nl_acc.p, *d = cx.aj_d.p, *diag = cx.diag_t.p;
-    double* out = cx.mc_nrm.p;
-    const bool has_core = sw.n_core > 0;
-    const int core = has_core ? sw.core_level : -1;
+    const double *valT = cx.valT_T.p, *acc = cx.nl_acc.p, *d = cx.aj_d.p, *diag = cx.diag_t.p;
     pfv::adjoint_nl_slopes(cx, F, cx.aj_sB.p, cx.aj_d.p, cx.aj_phi.p);  // of s^n
-    run.launches = pfv::sweep_apply_nl_t(cx, sw, core + 1, sw.nlev, cx.pat_T, valT, diag, d_sink, acc, d, cx.aj_r.p, z);
-    int core_it = 0;
-    if (has_core) {
-      pfv::sweep_core_zero(cx, sw, 1, z);
-      const CoreRun cr = core_iterate(h, maxit, out, hst, [&] {
-        pfv::sweep_core_copy(cx, sw, 1, z, cx.aj_prev.p);
-        pfv::sweep_core_nl_t(cx, sw, cx.pat_T, valT, diag, d_sink, acc, d, cx.aj_r.p, cx.aj_prev.p, z);
-      }, [&] {
-        pfv::sweep_norms_nl_t(cx, sw, cx.pat_T, valT, d_sink, acc, d, cx.aj_r.p, z, true, out);
-      }, [&] { return adjoint_norms_pass(hst, 1, 0.5 * rtol); });
-      core_it = cr.iterations;
-      run.core_total += core_it;
-      run.launches += 2;
-      if (!cr.settled) {  // (what the forward-peel levels would compute from this core is not judged)
-        adjoint_component_info(run.info, hst, 1, core_it);
-        cx.err = "adjoint step " + std::to_string(n) + ": the cyclic core of " + std::to_string(sw.n_core) +
-                 " cells did not settle in " + std::to_string(core_it) + " iterations";
-        return PFV_ERR_NOT_CONVERGED;
-      }
-      run.launches += pfv::sweep_apply_nl_t(cx, sw, 0, core, cx.pat_T, valT, diag, d_sink, acc, d, cx.aj_r.p, z);
-    }
-    pfv::sweep_norms_nl_t(cx, sw, cx.pat_T, valT, d_sink, acc, d, cx.aj_r.p, z, false, out);
-    be_d2h(hst.data(), out, sizeof(double) * hst.size(), cx.stream);
-    adjoint_component_info(run.info, hst, 1, has_core ? core_it : 1);
-    return adjoint_accept(h, run.info, hst, 1, rtol, n);
+    AdjointSolve V{1, -1, cx.mc_nrm.p};
+    V.levels = [&](int from, int to) {
+      return pfv::sweep_apply_nl_t(cx, sw, from, to, cx.pat_T, valT, diag, d_sink, acc, d, cx.aj_r.p, z);
+    };
+    V.core_zero = [&] { pfv::sweep_core_zero(cx, sw, 1, z); };
+    V.core_step = [&] {
+      pfv::sweep_core_copy(cx, sw, 1, z, cx.aj_prev.p);
+      pfv::sweep_core_nl_t(cx, sw, cx.pat_T, valT, diag, d_sink, acc, d, cx.aj_r.p, cx.aj_prev.p, z);
+    };
+    V.norms = [&](bool core_only) {
+      pfv::sweep_norms_nl_t(cx, sw, cx.pat_T, valT, d_sink, acc, d, cx.aj_r.p, z, core_only, cx.mc_nrm.p);
+    };
+    return adjoint_sweep_solve(h, V, run, rtol, maxit, n);
   }, [&](double* z) {
     pfv::pfv_ctx_impl& cx = *h;
     if (grad_sink) pfv::adjoint_nl_grad_sink(cx, z, cx.aj_phi.p, cx.aj_gsink.p);
@@ -2426,26 +2448,20 @@ pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind
     if (grad_flux) pfv::adjoint_nl_grad_flux(cx, F, cx.nl_bc.p, z, cx.aj_phi.p, cx.aj_gq.p);
     if (grad_fluxfn)
       pfv::adjoint_nl_grad_fluxfn(cx, F, cx.pat_T, cx.valT_T.p, d_sink, d_q, cx.nl_bc.p, z, cx.aj_sB.p, cx.aj_gF.p);
-  }, [&] {
-    if (grad_bc_values) vec_out(h, grad_bc_values, h->aj_gbc.p, nf);
-    if (grad_flux) vec_out(h, grad_flux, h->aj_gq.p, nf);
-    if (grad_sink) vec_out(h, grad_sink, h->aj_gsink.p, nc);
-    if (grad_fluxfn) be_d2h(grad_fluxfn, h->aj_gF.p, sizeof(double) * 6, h->stream);  // (host memory, as the parameters are)
   });
   h->stats.transport_nl_adjoint_ms = run.ms;
   h->stats.transport_nl_adjoint_steps = run.completed;
   h->stats.transport_nl_adjoint_core_iterations = run.core_total;
-  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, order_ms);
+  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, S.order_ms);
   return st;
 }
 
 // ---- the adjoint of the saturation step with phase-carried components: one fused transposed sweep per step ------------
-// Its own loop in the order of adjoint_steps (whose right-hand side g + acc o lambda+ has one kind of multiplier): per
-// step n = N .. 1 the slab (s^n, c^n), the slopes with the dry-row flag, the two right-hand sides fused with what the
-// multipliers of step n + 1 add to the cell gradients, the backward-peel levels from last to first (sweep_row_nlc_t),
-// the core level iterated by Jacobi on mu and lambda jointly, the forward-peel levels, the k + 1 pairs of norms and ONE
-// host read that brings the flag with them; then the gradients of the accepted step and the swap.  After the last step
-// slab 0 is staged and the right-hand-side kernel runs once more: it leaves grad_s0 and grad_c0.
+// In the frame of adjoint_steps with its own hooks, for it has two kinds of multipliers (lambda of the saturation in
+// aj_lam / aj_lam2, mu of the components in aj_mu / aj_mu2) and two slabs (s in aj_sA / aj_sB, c in aj_cA / aj_cB): per
+// step the slab (s^n, c^n), the slopes with the dry-row flag and the two right-hand sides fused with what the
+// multipliers of step n + 1 add to the cell gradients; adjoint_sweep_solve on mu and lambda jointly (sweep_row_nlc_t),
+// the k + 1 pairs of norms and the flag in its ONE host read.  The last pass on slab 0 leaves grad_s0 and grad_c0.
 pfv_status pfv_transport_adjoint_nl_multi(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
                                           int n_params, const double* bc_values, const double* accumulation,
                                           const double* sink, int k, const double* c_bc_values, const double* sorption,
@@ -2458,26 +2474,14 @@ pfv_status pfv_transport_adjoint_nl_multi(pfv_ctx* h, const double* q, int fluxf
                                           pfv_solve_info* last) {
   if (steps_done) *steps_done = 0;
   if (k < 1 || k > 64) return guarded(h, [&] { require(false, "k must lie in 1 .. 64"); });
-  std::unique_ptr<pfv::Timer> tm;
-  bool touched = false;
-  double order_ms = 0.0;
+  AdjointSetup S;
   const double* d_q = nullptr;
   size_t nc = 0, nf = 0;
   pfv::FluxFn F;
-  pfv_status st = guarded(h, [&] {
-    upwind_supported(h);
-    if (h->subface_bc) throw Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
-    require(h->have_upwind, "pfv_upwind_discretize first");
-    require(h->upw_ncomp == 1, "the saturation step needs pfv_upwind_discretize with num_components = 1");
-    const std::string bad = pfv::fluxfn_check(fluxfn_kind, fluxfn_params, n_params);
-    if (!bad.empty()) throw Error(PFV_ERR_ARGUMENT, bad);
-    require(!grad_fluxfn || fluxfn_kind == PFV_FLUXFN_COREY,
-            "grad_fluxfn is the gradient with respect to the six Corey parameters: PFV_FLUXFN_COREY only");
-    require(bc_values && accumulation, "bc_values and accumulation are required");
+  pfv_status st = adjoint_setup(h, S, [&] {
+    adjoint_nl_supported(h, fluxfn_kind, fluxfn_params, n_params, grad_fluxfn, bc_values, accumulation);
     require(c_bc_values, "c_bc_values is required");
-    require(n_steps >= 0, "bad argument");
-    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
-    require(s_loads || c_loads || n_steps == 0, "s_loads or c_loads is required");
+    adjoint_check_counts(n_steps, rtol, maxit, s_loads || c_loads, "s_loads or c_loads is required");
     require((s_states && c_states) || n_steps == 0,
             "s_states (s^0 .. s^N) and c_states (c^0 .. c^N) are required: the step is linearised about them");
     nc = (size_t)h->nc;
@@ -2499,37 +2503,16 @@ pfv_status pfv_transport_adjoint_nl_multi(pfv_ctx* h, const double* q, int fluxf
     if (sorption) vec_in(h, h->nlc_ads_in.ensure(k * nc), sorption, k * nc);
     d_q = q ? h->nl_q.p : h->upw_q.p;
     pfv::upwind_face_cells(*h);
-    // (the states are not checked: the accumulation stands in for s, zeros for c -- off[2] and off[6] say nothing)
+    // (the states are not checked: the accumulation stands in for s, zeros for c)
     pfv::be_memset(h->nlc_c_in.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
     int32_t off[pfv::kNlChecks];
     pfv::sweep_nl_check_inputs(*h, d_q, h->nl_bc.p, h->nl_acc.p, sink ? h->nl_sink.p : nullptr, h->nl_acc.p, k,
                                sorption ? h->nlc_ads_in.p : nullptr, h->nlc_c_in.p, h->nlc_cbc.p, off);
-    static const char* what[5] = {"accumulation must be positive: cell ", "negative sink in cell ", nullptr,
-                                  "Dirichlet inflow value outside [0, 1] on face ", pfv::kUnmarkedInflowFace};
-    for (int m = 0; m < 5; ++m)
-      if (what[m] && off[m] != 0x7f7f7f7f) throw Error(PFV_ERR_ARGUMENT, what[m] + std::to_string(off[m]));
-    static const char* whatc[3] = {"sorption must not be negative: cell ", nullptr, "c_bc_values is not finite on face "};
-    for (int m = 0; m < 3; ++m)
-      if (whatc[m] && off[5 + m] != 0x7f7f7f7f)
-        throw Error(PFV_ERR_ARGUMENT, whatc[m] + std::to_string(off[5 + m] / k) + ", component " +
-                                          std::to_string(off[5 + m] % k));
+    nl_inputs_refused(off, k, kNlStates);
     if (fluxfn_kind == PFV_FLUXFN_TABLE)
       be_h2d(h->nl_table.ensure((size_t)n_params), fluxfn_params, sizeof(double) * (size_t)n_params, h->stream);
     F = pfv::fluxfn_make(fluxfn_kind, fluxfn_params, n_params, h->nl_table.p);
-    tm = std::make_unique<pfv::Timer>();
-    tm->start(h->stream);
-    // A = div diag(q) U without accumulation, once per call; its transposed values beside it
-    upwind_drop_transport(h, true);
-    touched = true;
-    pfv::upwind_assemble(*h, d_q, h->nl_bc.p, nullptr, nullptr, nullptr);
-    values_changed(h, Windows::drop);
-    const size_t nnz = (size_t)std::max<int64_t>(h->pat_T.nnz, 1);
-    if (!h->have_tpos_T) {
-      pfv::sweep_transpose_positions(*h, h->pat_T, h->tpos_T.ensure(nnz));
-      h->have_tpos_T = true;
-    }
-    pfv::sweep_transpose_values(*h, h->pat_T.nnz, h->tpos_T.p, h->val[PFV_MAT_TRANSPORT_SYSTEM].p, h->valT_T.ensure(nnz));
-    adjoint_take_slots(h, n_obs, obs_cells);
+    adjoint_system(h, S, d_q, h->nl_bc.p, n_obs, obs_cells);
     if (sorption) pfv::multi_interleave(*h, (int64_t)nc, k, h->nlc_ads_in.p, h->nlc_ads.ensure(k * nc));
     for (pfv::Buf<double>* b : {&h->aj_lam, &h->aj_lam2, &h->aj_prev, &h->aj_r, &h->aj_sA, &h->aj_sB, &h->aj_d, &h->aj_phi})
       b->ensure(nc);
@@ -2537,197 +2520,114 @@ pfv_status pfv_transport_adjoint_nl_multi(pfv_ctx* h, const double* q, int fluxf
                                 &h->mc_c})
       b->ensure(k * nc);
     pfv::be_memset(h->aj_mu.p, 0, sizeof(double) * k * nc, h->stream);  // mu^{N+1} = 0
-    if (grad_source) pfv::be_memset(h->aj_gsrc.ensure(nc), 0, sizeof(double) * nc, h->stream);
-    if (grad_accumulation) pfv::be_memset(h->aj_gacc.ensure(nc), 0, sizeof(double) * nc, h->stream);
-    if (grad_sink) pfv::be_memset(h->aj_gsink.ensure(nc), 0, sizeof(double) * nc, h->stream);
-    if (grad_c_source) pfv::be_memset(h->aj_gcsrc.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
-    if (grad_sorption) pfv::be_memset(h->aj_gads.ensure(k * nc), 0, sizeof(double) * k * nc, h->stream);
-    if (grad_bc_values) pfv::be_memset(h->aj_gbc.ensure(nf), 0, sizeof(double) * nf, h->stream);
-    if (grad_c_bc_values) pfv::be_memset(h->aj_gcbc.ensure(k * nf), 0, sizeof(double) * k * nf, h->stream);
-    if (grad_flux) pfv::be_memset(h->aj_gq.ensure(nf), 0, sizeof(double) * nf, h->stream);
-    if (grad_fluxfn) pfv::be_memset(h->aj_gF.ensure(6), 0, sizeof(double) * 6, h->stream);
     h->mc_nrm.ensure(2 * (size_t)(k + 1) + 1);  // the k + 1 pairs, then the word of the dry rows
-    transport_order(h, d_q, order_ms);
   });
-  if (st != PFV_OK) {
-    if (touched) upwind_drop_transport(h, true);  // (A without accumulation: not a system to be solved with)
-    return st;
-  }
+  if (st != PFV_OK) return st;
 
   const int K = k + 1;  // the norms' pairs: components 0 .. k - 1, then the saturation
   AdjointRun run;
-  run.info.assign((size_t)K, pfv_solve_info{});
-  std::vector<double> hst(2 * (size_t)K + 1);
   const double* d_sink = sink ? h->nl_sink.p : nullptr;
   const double* d_ads = sorption ? h->nlc_ads.p : nullptr;
-  const int32_t* slot = obs_cells ? h->aj_slot.p : nullptr;
-  // slab n of the states: s into `ts`, c interleaved into `tc`
-  auto stage_slab = [&](int n, double* ts, double* tc) {
-    vec_in(h, ts, s_states + (size_t)n * nc, nc);
+  AdjointCall call{k, n_steps, n_obs, obs_cells, nullptr, nullptr, nullptr, nullptr, steps_done, last};
+  call.saturation = k;
+  call.grads = {{grad_s0, &h->aj_r, nc, GradLayout::plain, false},
+                {grad_c0, &h->aj_rmu, k * nc, GradLayout::by_cell, false},
+                {grad_source, &h->aj_gsrc, nc, GradLayout::plain},
+                {grad_c_source, &h->aj_gcsrc, k * nc, GradLayout::by_cell},
+                {grad_accumulation, &h->aj_gacc, nc, GradLayout::plain},
+                {grad_sorption, &h->aj_gads, k * nc, GradLayout::by_cell},
+                {grad_sink, &h->aj_gsink, nc, GradLayout::plain},
+                {grad_bc_values, &h->aj_gbc, nf, GradLayout::plain},
+                {grad_c_bc_values, &h->aj_gcbc, k * nf, GradLayout::plain},
+                {grad_flux, &h->aj_gq, nf, GradLayout::plain},
+                {grad_fluxfn, &h->aj_gF, 6, GradLayout::host}};
+  call.stage = [&](int n) {  // s^n into aj_sB, c^n interleaved into aj_cB; aj_sA / aj_cA hold slab n + 1
+    vec_in(h, h->aj_sB.p, s_states + (size_t)n * nc, nc);
     vec_in(h, h->aj_state_in.p, c_states + (size_t)n * k * nc, k * nc);
-    pfv::multi_interleave(*h, (int64_t)nc, k, h->aj_state_in.p, tc);
+    pfv::multi_interleave(*h, (int64_t)nc, k, h->aj_state_in.p, h->aj_cB.p);
   };
-  std::string err;
-  bool have_next = false;  // aj_lam / aj_mu hold the multipliers of step n + 1
-  for (int n = n_steps; n >= 1 && st == PFV_OK; --n) {
-    pfv_status verdict = PFV_OK;
-    st = guarded(h, [&] {
-      pfv::pfv_ctx_impl& cx = *h;
-      const pfv::Sweep& sw = *cx.sweep;
-      const double* valT = cx.valT_T.p;
-      const double *acc = cx.nl_acc.p, *d = cx.aj_d.p, *phi = cx.aj_phi.p, *diag = cx.diag_t.p;
-      double* out = cx.mc_nrm.p;
-      int32_t* dry = reinterpret_cast<int32_t*>(out + 2 * K);
-      const bool has_core = sw.n_core > 0;
-      const int core = has_core ? sw.core_level : -1;
-      stage_slab(n, cx.aj_sB.p, cx.aj_cB.p);  // (s^n, c^n); aj_sA / aj_cA hold slab n + 1
-      const double *s_n = cx.aj_sB.p, *c_n = cx.aj_cB.p;
-      pfv::be_memset(dry, 0x7f, sizeof(double), cx.stream);
-      pfv::adjoint_nlc_slopes(cx, F, k, s_n, diag, d_sink, acc, d_ads, cx.aj_d.p, cx.aj_phi.p, dry);
-      pfv::adjoint_nlc_step_rhs(cx, k, acc, d_ads, s_n, c_n, cx.aj_sA.p, cx.aj_cA.p, have_next ? cx.aj_lam.p : nullptr,
-                                cx.aj_mu.p, slot, s_loads ? cx.aj_sloads.p + (size_t)(n - 1) * (size_t)n_obs : nullptr,
-                                c_loads ? cx.aj_loads.p + (size_t)(n - 1) * k * (size_t)n_obs : nullptr, n_obs, false,
-                                grad_source ? cx.aj_gsrc.p : nullptr, grad_c_source ? cx.aj_gcsrc.p : nullptr,
-                                grad_accumulation ? cx.aj_gacc.p : nullptr, grad_sorption ? cx.aj_gads.p : nullptr,
-                                cx.aj_r.p, cx.aj_rmu.p);
-      double* z = cx.aj_lam2.p;
-      pfv::NlCompT C;  // the levels outside the core; Cc: the core level, with the previous iterate
-      C.k = k;
-      C.ads = d_ads;
-      C.r = cx.aj_rmu.p;
-      C.mu_next = cx.aj_mu.p;
-      C.c = c_n;
-      C.mu = cx.aj_mu2.p;
-      pfv::NlCompT Cc = C;
-      Cc.mu_prev = cx.aj_muprev.p;
-      Cc.lam_prev = cx.aj_prev.p;
-      auto dry_row = [&]() -> bool {
-        int32_t w;
-        std::memcpy(&w, hst.data() + 2 * K, sizeof(w));
-        if (w == 0x7f7f7f7f) return false;
-        cx.err = "adjoint step " + std::to_string(n) + ": cell " + std::to_string(w / k) + ", component " +
-                 std::to_string(w % k) + " is dry (accumulation x s + sorption + f(s) x outflow is zero: the step does "
-                 "not determine the component there)";
-        return true;
-      };
-      run.launches = pfv::sweep_apply_nlc_t(cx, sw, core + 1, sw.nlev, cx.pat_T, valT, diag, d_sink, acc, d, phi, s_n,
-                                            cx.aj_r.p, z, C);
-      int core_it = 0;
-      if (has_core) {
-        pfv::sweep_core_zero(cx, sw, 1, z);
-        pfv::sweep_core_zero(cx, sw, k, C.mu);
-        const CoreRun cr = core_iterate(h, maxit, out, hst, [&] {
-          pfv::sweep_core_copy(cx, sw, 1, z, cx.aj_prev.p);
-          pfv::sweep_core_copy(cx, sw, k, C.mu, cx.aj_muprev.p);
-          pfv::sweep_core_nlc_t(cx, sw, cx.pat_T, valT, diag, d_sink, acc, d, phi, s_n, cx.aj_r.p, z, Cc);
-        }, [&] {
-          pfv::sweep_norms_nlc_t(cx, sw, cx.pat_T, valT, d_sink, acc, d, phi, s_n, cx.aj_r.p, z, C, true, out);
-        }, [&] {  // (a dry row never settles: it ends the iteration and is reported below)
-          int32_t w;
-          std::memcpy(&w, hst.data() + 2 * K, sizeof(w));
-          return w != 0x7f7f7f7f || adjoint_norms_pass(hst, K, 0.5 * rtol);
-        });
-        core_it = cr.iterations;
-        run.core_total += core_it;
-        run.launches += 2;
-        if (dry_row()) throw Error(PFV_ERR_ARGUMENT, cx.err);
-        if (!cr.settled) {  // (what the forward-peel levels would compute from this core is not judged)
-          adjoint_component_info(run.info, hst, K, core_it);
-          cx.err = "adjoint step " + std::to_string(n) + ": the cyclic core of " + std::to_string(sw.n_core) +
-                   " cells did not settle in " + std::to_string(core_it) + " iterations";
-          verdict = PFV_ERR_NOT_CONVERGED;
-          return;
-        }
-        run.launches += pfv::sweep_apply_nlc_t(cx, sw, 0, core, cx.pat_T, valT, diag, d_sink, acc, d, phi, s_n, cx.aj_r.p,
-                                               z, C);
-      }
-      pfv::sweep_norms_nlc_t(cx, sw, cx.pat_T, valT, d_sink, acc, d, phi, s_n, cx.aj_r.p, z, C, false, out);
-      be_d2h(hst.data(), out, sizeof(double) * hst.size(), cx.stream);
-      if (dry_row()) throw Error(PFV_ERR_ARGUMENT, cx.err);
-      adjoint_component_info(run.info, hst, K, has_core ? core_it : 1);
-      int bad = -1;  // the first check that fails; k: the saturation's (judged first)
-      for (int a = k - 1; a >= 0; --a) {
-        run.info[(size_t)a].converged = hst[(size_t)K + a] <= rtol * rtol * hst[(size_t)a] ? 1 : 0;  // (0 <= 0 counts)
-        if (!run.info[(size_t)a].converged) bad = a;
-      }
-      run.info[(size_t)k].converged = hst[(size_t)K + k] <= rtol * rtol * hst[(size_t)k] ? 1 : 0;
-      if (!run.info[(size_t)k].converged) bad = k;
-      if (bad >= 0) {
-        cx.err = "adjoint step " + std::to_string(n) + ": relative residual " +
-                 std::to_string(run.info[(size_t)bad].rel_residual) +
-                 (bad == k ? std::string() : " of component " + std::to_string(bad)) +
-                 " after the transposed sweep (a flux that contradicts the discretization's?)";
-        verdict = PFV_ERR_NOT_CONVERGED;
-        return;
-      }
-      const double* mu = C.mu;
-      if (grad_sink) pfv::adjoint_nlc_grad_sink(cx, k, z, mu, c_n, phi, cx.aj_gsink.p);
-      if (grad_bc_values) pfv::adjoint_nlc_grad_bc(cx, F, k, d_q, cx.nl_bc.p, cx.nlc_cbc.p, z, mu, cx.aj_gbc.p);
-      if (grad_c_bc_values) pfv::adjoint_nlc_grad_cbc(cx, F, k, d_q, cx.nl_bc.p, mu, cx.aj_gcbc.p);
-      if (grad_flux) pfv::adjoint_nlc_grad_flux(cx, F, k, cx.nl_bc.p, cx.nlc_cbc.p, z, mu, phi, c_n, cx.aj_gq.p);
-      if (grad_fluxfn)
-        pfv::adjoint_nlc_grad_fluxfn(cx, F, cx.pat_T, valT, d_sink, k, d_q, cx.nl_bc.p, cx.nlc_cbc.p, z, mu, s_n, c_n,
-                                     cx.aj_gF.p);
-      cx.aj_lam.swap(cx.aj_lam2);
-      cx.aj_mu.swap(cx.aj_mu2);
-      cx.aj_sA.swap(cx.aj_sB);
-      cx.aj_cA.swap(cx.aj_cB);
-      have_next = true;
-      ++run.completed;
-    });
-    if (st == PFV_OK) st = verdict;
-  }
-  if (st != PFV_OK) err = h->err;
-  const pfv_status st2 = guarded(h, [&] {
+  call.rhs = [&](int n, bool have_next) {
     pfv::pfv_ctx_impl& cx = *h;
-    if (st == PFV_OK) {
-      // lambda^1 and mu^1 into the cell gradients on slab 0; the right-hand sides they leave are grad_s0 and grad_c0
-      if (have_next) {
-        stage_slab(0, cx.aj_sB.p, cx.aj_cB.p);
-        pfv::adjoint_nlc_step_rhs(cx, k, cx.nl_acc.p, d_ads, cx.aj_sB.p, cx.aj_cB.p, cx.aj_sA.p, cx.aj_cA.p, cx.aj_lam.p,
-                                  cx.aj_mu.p, nullptr, nullptr, nullptr, 0, true, grad_source ? cx.aj_gsrc.p : nullptr,
-                                  grad_c_source ? cx.aj_gcsrc.p : nullptr, grad_accumulation ? cx.aj_gacc.p : nullptr,
-                                  grad_sorption ? cx.aj_gads.p : nullptr, cx.aj_r.p, cx.aj_rmu.p);
-      } else {
-        pfv::be_memset(cx.aj_r.p, 0, sizeof(double) * nc, cx.stream);
-        pfv::be_memset(cx.aj_rmu.p, 0, sizeof(double) * k * nc, cx.stream);
-      }
+    if (n == 0 && !have_next) {
+      pfv::be_memset(cx.aj_r.p, 0, sizeof(double) * nc, cx.stream);
+      pfv::be_memset(cx.aj_rmu.p, 0, sizeof(double) * k * nc, cx.stream);
+      return;
     }
-    run.ms = tm->stop(cx.stream);
-    tm.reset();
-    if (st == PFV_OK) {
-      auto cells_out = [&](double* to, const double* from) {
-        pfv::multi_deinterleave(cx, (int64_t)nc, k, from, cx.mc_c.p);
-        vec_out(h, to, cx.mc_c.p, k * nc);
-      };
-      if (grad_s0) vec_out(h, grad_s0, cx.aj_r.p, nc);
-      if (grad_c0) cells_out(grad_c0, cx.aj_rmu.p);
-      if (grad_source) vec_out(h, grad_source, cx.aj_gsrc.p, nc);
-      if (grad_c_source) cells_out(grad_c_source, cx.aj_gcsrc.p);
-      if (grad_accumulation) vec_out(h, grad_accumulation, cx.aj_gacc.p, nc);
-      if (grad_sorption) cells_out(grad_sorption, cx.aj_gads.p);
-      if (grad_sink) vec_out(h, grad_sink, cx.aj_gsink.p, nc);
-      if (grad_bc_values) vec_out(h, grad_bc_values, cx.aj_gbc.p, nf);
-      if (grad_c_bc_values) vec_out(h, grad_c_bc_values, cx.aj_gcbc.p, k * nf);
-      if (grad_flux) vec_out(h, grad_flux, cx.aj_gq.p, nf);
-      if (grad_fluxfn) be_d2h(grad_fluxfn, cx.aj_gF.p, sizeof(double) * 6, cx.stream);  // (host memory, as the parameters are)
+    if (n > 0) {
+      int32_t* dry = reinterpret_cast<int32_t*>(cx.mc_nrm.p + 2 * K);
+      pfv::be_memset(dry, 0x7f, sizeof(double), cx.stream);
+      pfv::adjoint_nlc_slopes(cx, F, k, cx.aj_sB.p, cx.diag_t.p, d_sink, cx.nl_acc.p, d_ads, cx.aj_d.p, cx.aj_phi.p, dry);
     }
-    pfv::be_sync(cx.stream);
-    upwind_drop_transport(h, true);
+    pfv::adjoint_nlc_step_rhs(cx, k, cx.nl_acc.p, d_ads, cx.aj_sB.p, cx.aj_cB.p, cx.aj_sA.p, cx.aj_cA.p,
+                              have_next ? cx.aj_lam.p : nullptr, cx.aj_mu.p, n > 0 && obs_cells ? cx.aj_slot.p : nullptr,
+                              n > 0 && s_loads ? cx.aj_sloads.p + (size_t)(n - 1) * (size_t)n_obs : nullptr,
+                              n > 0 && c_loads ? cx.aj_loads.p + (size_t)(n - 1) * k * (size_t)n_obs : nullptr,
+                              n > 0 ? n_obs : 0, n == 0, grad_source ? cx.aj_gsrc.p : nullptr,
+                              grad_c_source ? cx.aj_gcsrc.p : nullptr, grad_accumulation ? cx.aj_gacc.p : nullptr,
+                              grad_sorption ? cx.aj_gads.p : nullptr, cx.aj_r.p, cx.aj_rmu.p);
+  };
+  call.swap = [&] {
+    h->aj_lam.swap(h->aj_lam2);
+    h->aj_mu.swap(h->aj_mu2);
+    h->aj_sA.swap(h->aj_sB);
+    h->aj_cA.swap(h->aj_cB);
+  };
+  st = adjoint_steps(h, S, call, run, [&](int n, double* z) -> pfv_status {
+    pfv::pfv_ctx_impl& cx = *h;
+    const pfv::Sweep& sw = *cx.sweep;
+    const double* valT = cx.valT_T.p;
+    const double *acc = cx.nl_acc.p, *d = cx.aj_d.p, *phi = cx.aj_phi.p, *diag = cx.diag_t.p, *s_n = cx.aj_sB.p;
+    pfv::NlCompT C;  // the levels outside the core; Cc: the core level, with the previous iterate
+    C.k = k;
+    C.ads = d_ads;
+    C.r = cx.aj_rmu.p;
+    C.mu_next = cx.aj_mu.p;
+    C.c = cx.aj_cB.p;
+    C.mu = cx.aj_mu2.p;
+    pfv::NlCompT Cc = C;
+    Cc.mu_prev = cx.aj_muprev.p;
+    Cc.lam_prev = cx.aj_prev.p;
+    AdjointSolve V{K, k, cx.mc_nrm.p};
+    V.levels = [&](int from, int to) {
+      return pfv::sweep_apply_nlc_t(cx, sw, from, to, cx.pat_T, valT, diag, d_sink, acc, d, phi, s_n, cx.aj_r.p, z, C);
+    };
+    V.core_zero = [&] {
+      pfv::sweep_core_zero(cx, sw, 1, z);
+      pfv::sweep_core_zero(cx, sw, k, C.mu);
+    };
+    V.core_step = [&] {
+      pfv::sweep_core_copy(cx, sw, 1, z, cx.aj_prev.p);
+      pfv::sweep_core_copy(cx, sw, k, C.mu, cx.aj_muprev.p);
+      pfv::sweep_core_nlc_t(cx, sw, cx.pat_T, valT, diag, d_sink, acc, d, phi, s_n, cx.aj_r.p, z, Cc);
+    };
+    V.norms = [&](bool core_only) {
+      pfv::sweep_norms_nlc_t(cx, sw, cx.pat_T, valT, d_sink, acc, d, phi, s_n, cx.aj_r.p, z, C, core_only, cx.mc_nrm.p);
+    };
+    V.flag_ends_core = true;  // (a dry row never settles)
+    V.flagged = [&](int step, int32_t w) -> pfv_status {
+      throw Error(PFV_ERR_ARGUMENT, "adjoint step " + std::to_string(step) + ": cell " + std::to_string(w / k) +
+                                        ", component " + std::to_string(w % k) + " is dry (accumulation x s + sorption + "
+                                        "f(s) x outflow is zero: the step does not determine the component there)");
+    };
+    return adjoint_sweep_solve(h, V, run, rtol, maxit, n);
+  }, [&](double* z) {
+    pfv::pfv_ctx_impl& cx = *h;
+    const double *mu = cx.aj_mu2.p, *s_n = cx.aj_sB.p, *c_n = cx.aj_cB.p, *phi = cx.aj_phi.p;
+    if (grad_sink) pfv::adjoint_nlc_grad_sink(cx, k, z, mu, c_n, phi, cx.aj_gsink.p);
+    if (grad_bc_values) pfv::adjoint_nlc_grad_bc(cx, F, k, d_q, cx.nl_bc.p, cx.nlc_cbc.p, z, mu, cx.aj_gbc.p);
+    if (grad_c_bc_values) pfv::adjoint_nlc_grad_cbc(cx, F, k, d_q, cx.nl_bc.p, mu, cx.aj_gcbc.p);
+    if (grad_flux) pfv::adjoint_nlc_grad_flux(cx, F, k, cx.nl_bc.p, cx.nlc_cbc.p, z, mu, phi, c_n, cx.aj_gq.p);
+    if (grad_fluxfn)
+      pfv::adjoint_nlc_grad_fluxfn(cx, F, cx.pat_T, cx.valT_T.p, d_sink, k, d_q, cx.nl_bc.p, cx.nlc_cbc.p, z, mu, s_n,
+                                   c_n, cx.aj_gF.p);
   });
-  if (steps_done) *steps_done = run.completed;
-  if (last) {
-    last[0] = run.info[(size_t)k];
-    for (int a = 0; a < k; ++a) last[1 + a] = run.info[(size_t)a];
-    if (run.completed > 0)
-      for (int a = 0; a <= k; ++a) last[a].solve_ms = run.ms / run.completed;
-  }
   h->stats.transport_nlc_adjoint_ms = run.ms;
   h->stats.transport_nlc_adjoint_steps = run.completed;
   h->stats.transport_nlc_adjoint_core_iterations = run.core_total;
-  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, order_ms);
-  return step_status(h, st, err, st2);
+  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, S.order_ms);
+  return st;
 }
+
 
 // ---- advection-diffusion on one handle (advdiff.inc) -----------------------------------------------------------
 static void advdiff_supported(pfv_ctx* h) {

@@ -8,12 +8,39 @@ flux divergence -- not a solver right-hand side.  The balance reads ``acc * (c -
 ``solve`` / ``advance`` solve ``(diag(acc) + A) c = acc * c_old - b_ref + source``."""
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 import scipy.sparse as sps
 
 from . import _lib
 from .grid import grid_to_raw
 from .params import DISCRETIZATION_MATRICES, PARAMETERS, bc_flags
+
+
+def per_component(name, a, k, n):
+    """``a`` as a (k, n) array: one row shared by the k components, or a row for each"""
+    a = np.asarray(a, dtype=np.float64)
+    if a.shape == (n,):
+        return np.broadcast_to(a, (k, n))
+    if a.shape != (k, n):
+        raise ValueError(f"{name} must have shape ({n},) or ({k}, {n}), not {a.shape}")
+    return a
+
+
+@contextlib.contextmanager
+def _argument_errors(with_state=False):
+    """An argument the library refuses (status 4) is a ValueError with the library's words; ``with_state``: it carries
+    the ``state`` and ``info`` of the library's error."""
+    try:
+        yield
+    except _lib.PorefvError as e:
+        if e.status != 4:
+            raise
+        err = ValueError(e.message)
+        if with_state:
+            err.state, err.info = getattr(e, "state", None), getattr(e, "info", None)
+        raise err from None
 
 
 class ResidentFlux:
@@ -151,12 +178,8 @@ class Upwind:
         q = self._flux(sd, pd)
         ctx = self.context(sd)
         ctx.upwind_set_bc(bc_flags(pd["bc"]) if "bc" in pd else None)
-        try:
+        with _argument_errors():  # (the reference fails in scipy's coo -> csr conversion with the same words)
             ctx.upwind_discretize(q, k)
-        except _lib.PorefvError as e:
-            if e.status == 4:  # (the reference fails in scipy's coo -> csr conversion with the same words)
-                raise ValueError(e.message) from None
-            raise
         for key, which in ((self.upwind_matrix_key, _lib.MAT_UPWIND),
                            (self.bound_transport_dir_matrix_key, _lib.MAT_UPWIND_RHS_DIR),
                            (self.bound_transport_neu_matrix_key, _lib.MAT_UPWIND_RHS_NEU)):
@@ -165,13 +188,9 @@ class Upwind:
     def _assemble(self, sd, data, accumulation=None, c_old=None, source=None, bound_rhs=False):
         pd = data[PARAMETERS][self.keyword]
         ctx = self.context(sd)
-        try:
+        with _argument_errors():
             return ctx.upwind_assemble(np.asarray(pd["bc_values"], dtype=float), self._flux(sd, pd), accumulation, c_old,
                                        source, bound_rhs=bound_rhs)
-        except _lib.PorefvError as e:
-            if e.status == 4:
-                raise ValueError(e.message) from None
-            raise
 
     def assemble_matrix_rhs(self, sd, data: dict):
         """``(A, b_ref)`` as the reference returns them (see the module text for the sign of ``b_ref``)."""
@@ -247,27 +266,15 @@ class Upwind:
         if not 1 <= k <= 64:
             raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (c0 has shape {c0.shape})")
 
-        def per_component(name, a, n):
-            a = np.asarray(a, dtype=np.float64)
-            if a.shape == (n,):
-                return np.broadcast_to(a, (k, n))
-            if a.shape != (k, n):
-                raise ValueError(f"{name} must have shape ({n},) or ({k}, {n}), not {a.shape}")
-            return a
-
         if accumulation is None:
             raise ValueError("accumulation is required")
-        acc = per_component("accumulation", accumulation, nc)
-        bv = per_component("bc_values", pd["bc_values"] if bc_values is None else bc_values, nf)
-        src = None if source is None else per_component("source", source, nc)
-        try:
+        acc = per_component("accumulation", accumulation, k, nc)
+        bv = per_component("bc_values", pd["bc_values"] if bc_values is None else bc_values, k, nf)
+        src = None if source is None else per_component("source", source, k, nc)
+        with _argument_errors():
             return self.context(sd).transport_advance_multi(c0, n_steps, acc, bv, q=self._flux(sd, pd), source=src,
                                                             method=method, rtol=rtol, maxit=maxit,
                                                             raise_on_fail=raise_on_fail, precond=precond)
-        except _lib.PorefvError as e:
-            if e.status == 4:
-                raise ValueError(e.message) from None
-            raise
 
     def adjoint_components(self, sd, data: dict, n_steps: int, accumulation, loads, obs_cells=None, states=None,
                            bc_values=None, want=("c0", "source", "bc_values"), rtol: float = 1e-12, maxit: int = 500,
@@ -307,26 +314,14 @@ class Upwind:
         if not 1 <= k <= 64:
             raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (loads has shape {loads.shape})")
 
-        def per_component(name, a, n):
-            a = np.asarray(a, dtype=np.float64)
-            if a.shape == (n,):
-                return np.broadcast_to(a, (k, n))
-            if a.shape != (k, n):
-                raise ValueError(f"{name} must have shape ({n},) or ({k}, {n}), not {a.shape}")
-            return a
-
         if accumulation is None:
             raise ValueError("accumulation is required")
-        acc = per_component("accumulation", accumulation, nc)
-        bv = per_component("bc_values", pd["bc_values"] if bc_values is None else bc_values, nf)
-        try:
+        acc = per_component("accumulation", accumulation, k, nc)
+        bv = per_component("bc_values", pd["bc_values"] if bc_values is None else bc_values, k, nf)
+        with _argument_errors():
             return self.context(sd).transport_adjoint_multi(n_steps, acc, bv, loads, obs_cells=obs_cells, states=states,
                                                             q=self._flux(sd, pd), want=want, rtol=rtol, maxit=maxit,
                                                             raise_on_fail=raise_on_fail)
-        except _lib.PorefvError as e:
-            if e.status == 4:
-                raise ValueError(e.message) from None
-            raise
 
     def advance_saturation(self, sd, data: dict, s0, n_steps: int, accumulation, flux_function, source=None, sink=None,
                            rtol: float = 1e-12, maxit: int = 500, raise_on_fail: bool = True):
@@ -347,16 +342,10 @@ class Upwind:
         kind, params = _flux_function(flux_function)
         if accumulation is None:
             raise ValueError("accumulation is required")
-        try:
+        with _argument_errors(with_state=True):
             s, info = self.context(sd).transport_advance_nl(
                 s0, n_steps, accumulation, np.asarray(pd["bc_values"], dtype=float), kind, params, q=self._flux(sd, pd),
                 source=source, sink=sink, rtol=rtol, maxit=maxit, raise_on_fail=raise_on_fail)
-        except _lib.PorefvError as e:
-            if e.status == 4:
-                err = ValueError(e.message)
-                err.state, err.info = getattr(e, "state", None), getattr(e, "info", None)
-                raise err from None
-            raise
         return s, info
 
     def advance_saturation_components(self, sd, data: dict, s0, c0, n_steps: int, accumulation, flux_function,
@@ -389,28 +378,14 @@ class Upwind:
         if not 1 <= k <= 64:
             raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (c0 has shape {c0.shape})")
 
-        def per_component(name, a, n):
-            a = np.asarray(a, dtype=np.float64)
-            if a.shape == (n,):
-                return np.broadcast_to(a, (k, n))
-            if a.shape != (k, n):
-                raise ValueError(f"{name} must have shape ({n},) or ({k}, {n}), not {a.shape}")
-            return a
-
-        cbv = np.zeros((k, nf)) if c_bc_values is None else per_component("c_bc_values", c_bc_values, nf)
-        ads = None if sorption is None else per_component("sorption", sorption, nc)
-        csrc = None if c_source is None else per_component("c_source", c_source, nc)
-        try:
+        cbv = np.zeros((k, nf)) if c_bc_values is None else per_component("c_bc_values", c_bc_values, k, nf)
+        ads = None if sorption is None else per_component("sorption", sorption, k, nc)
+        csrc = None if c_source is None else per_component("c_source", c_source, k, nc)
+        with _argument_errors(with_state=True):
             return self.context(sd).transport_advance_nl_multi(
                 s0, c0, n_steps, accumulation, np.asarray(pd["bc_values"], dtype=float), cbv, kind, params,
                 q=self._flux(sd, pd), sorption=ads, source=source, sink=sink, c_source=csrc, rtol=rtol, maxit=maxit,
                 raise_on_fail=raise_on_fail)
-        except _lib.PorefvError as e:
-            if e.status == 4:
-                err = ValueError(e.message)
-                err.state, err.info = getattr(e, "state", None), getattr(e, "info", None)
-                raise err from None
-            raise
 
     def advance_reactive_components(self, sd, data: dict, c0, n_steps: int, accumulation, rate_matrix, rate_weight=None,
                                     mobility=None, bc_values=None, source=None, rtol: float = 1e-12, maxit: int = 500,
@@ -442,29 +417,15 @@ class Upwind:
         if not 1 <= k <= 8:
             raise ValueError(f"the number of coupled components must lie in 1 .. 8, not {k} (c0 has shape {c0.shape})")
 
-        def per_component(name, a, n):
-            a = np.asarray(a, dtype=np.float64)
-            if a.shape == (n,):
-                return np.broadcast_to(a, (k, n))
-            if a.shape != (k, n):
-                raise ValueError(f"{name} must have shape ({n},) or ({k}, {n}), not {a.shape}")
-            return a
-
         if accumulation is None:
             raise ValueError("accumulation is required")
-        acc = per_component("accumulation", accumulation, nc)
-        bv = per_component("bc_values", pd["bc_values"] if bc_values is None else bc_values, nf)
-        src = None if source is None else per_component("source", source, nc)
-        try:
+        acc = per_component("accumulation", accumulation, k, nc)
+        bv = per_component("bc_values", pd["bc_values"] if bc_values is None else bc_values, k, nf)
+        src = None if source is None else per_component("source", source, k, nc)
+        with _argument_errors(with_state=True):
             return self.context(sd).transport_advance_react(c0, n_steps, acc, bv, rate_matrix, rate_weight=rate_weight,
                                                             mobility=mobility, q=self._flux(sd, pd), source=src,
                                                             rtol=rtol, maxit=maxit, raise_on_fail=raise_on_fail)
-        except _lib.PorefvError as e:
-            if e.status == 4:
-                err = ValueError(e.message)
-                err.state, err.info = getattr(e, "state", None), getattr(e, "info", None)
-                raise err from None
-            raise
 
 
     def adjoint_reactive_components(self, sd, data: dict, n_steps: int, accumulation, rate_matrix, loads,
@@ -505,27 +466,15 @@ class Upwind:
         if not 1 <= k <= 8:
             raise ValueError(f"the number of coupled components must lie in 1 .. 8, not {k} (loads has shape {loads.shape})")
 
-        def per_component(name, a, n):
-            a = np.asarray(a, dtype=np.float64)
-            if a.shape == (n,):
-                return np.broadcast_to(a, (k, n))
-            if a.shape != (k, n):
-                raise ValueError(f"{name} must have shape ({n},) or ({k}, {n}), not {a.shape}")
-            return a
-
         if accumulation is None:
             raise ValueError("accumulation is required")
-        acc = per_component("accumulation", accumulation, nc)
-        bv = per_component("bc_values", pd["bc_values"] if bc_values is None else bc_values, nf)
-        try:
+        acc = per_component("accumulation", accumulation, k, nc)
+        bv = per_component("bc_values", pd["bc_values"] if bc_values is None else bc_values, k, nf)
+        with _argument_errors():
             return self.context(sd).transport_adjoint_react(n_steps, acc, bv, rate_matrix, loads, rate_weight=rate_weight,
                                                             mobility=mobility, obs_cells=obs_cells, states=states,
                                                             q=self._flux(sd, pd), want=want, rtol=rtol, maxit=maxit,
                                                             raise_on_fail=raise_on_fail)
-        except _lib.PorefvError as e:
-            if e.status == 4:
-                raise ValueError(e.message) from None
-            raise
 
     def adjoint_saturation(self, sd, data: dict, n_steps: int, accumulation, flux_function, loads, states, sink=None,
                            obs_cells=None, want=("s0", "source", "bc_values"), rtol: float = 1e-12, maxit: int = 500,
@@ -568,14 +517,10 @@ class Upwind:
         kind, params = _flux_function(flux_function)
         if accumulation is None:
             raise ValueError("accumulation is required")
-        try:
+        with _argument_errors():
             return self.context(sd).transport_adjoint_nl(
                 n_steps, accumulation, np.asarray(pd["bc_values"], dtype=float), kind, params, loads, states, sink=sink,
                 obs_cells=obs_cells, q=self._flux(sd, pd), want=want, rtol=rtol, maxit=maxit, raise_on_fail=raise_on_fail)
-        except _lib.PorefvError as e:
-            if e.status == 4:
-                raise ValueError(e.message) from None
-            raise
 
 
     def adjoint_saturation_components(self, sd, data: dict, n_steps: int, accumulation, flux_function, s_states,
@@ -641,25 +586,13 @@ class Upwind:
             raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (c_states has shape "
                              f"{c_states.shape})")
 
-        def per_component(name, a, n):
-            a = np.asarray(a, dtype=np.float64)
-            if a.shape == (n,):
-                return np.broadcast_to(a, (k, n))
-            if a.shape != (k, n):
-                raise ValueError(f"{name} must have shape ({n},) or ({k}, {n}), not {a.shape}")
-            return a
-
-        cbv = np.zeros((k, nf)) if c_bc_values is None else per_component("c_bc_values", c_bc_values, nf)
-        ads = None if sorption is None else per_component("sorption", sorption, nc)
-        try:
+        cbv = np.zeros((k, nf)) if c_bc_values is None else per_component("c_bc_values", c_bc_values, k, nf)
+        ads = None if sorption is None else per_component("sorption", sorption, k, nc)
+        with _argument_errors():
             return self.context(sd).transport_adjoint_nl_multi(
                 n_steps, accumulation, np.asarray(pd["bc_values"], dtype=float), cbv, kind, params, s_states, c_states,
                 s_loads=s_loads, c_loads=c_loads, sorption=ads, sink=sink, obs_cells=obs_cells, q=self._flux(sd, pd),
                 want=want, rtol=rtol, maxit=maxit, raise_on_fail=raise_on_fail)
-        except _lib.PorefvError as e:
-            if e.status == 4:
-                raise ValueError(e.message) from None
-            raise
 
 
 def _flux_function(flux_function):

@@ -240,6 +240,15 @@ typedef struct {
   int64_t flow_adjoint_exact_map_builds; /* times the cell -> sub-cell map was built (kept with the sub-cell topology) */
   double flow_adjoint_exact_map_ms; /* last pfv_flow_adjoint / pfv_flow_adjoint_exact: that map (0: kept or not needed) */
   double flow_adjoint_exact_ms;     /* ... the interaction-region kernel and the cell sum of grad_perm_exact (0: none) */
+  int64_t spgemm_path;             /* path of the last pfv_csr_matmul on this handle (csrc/csr_algebra.inc; tests): 0 none
+                                      yet, 16 / 32 / 64 the sort in LDS with that many lanes per row (up to 64, up to 160,
+                                      more products feeding the longest row), 1 the global radix sorts (a row fed by more
+                                      than 4096 products, too little LDS, PFV_SPGEMM_GENERIC=1).  The host emulation
+                                      reports the width the device would take */
+  int64_t spgemm_lds_bytes;        /* ... dynamic LDS per workgroup of its sort-in-LDS launch (64 / width rows of
+                                      8 capP + 8 capL + 8 (capP / 64 + 1) + 64 bytes each, rounded up to 16; capL the
+                                      products of the longest row, capP the power of two from capL on); 0 on the global
+                                      path.  Beyond 48 KiB the launch opts in to the larger LDS */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -1219,6 +1228,9 @@ void pfv_rccl_comm_destroy(pfv_rccl_comm* c);
  * entries that come out exactly zero are not stored.  A pfv_csr belongs to the handle it was created on (same
  * device for all operands) and must be freed before that handle is destroyed. */
 typedef struct pfv_csr pfv_csr;
+/* indptr is checked on the host before anything is uploaded (indptr[0] = 0, non-decreasing, every entry within
+ * [0, nnz = indptr[nrows]]), the rows on the device (sorted by column, no duplicates, 0 <= column < ncols):
+ * PFV_ERR_ARGUMENT otherwise */
 pfv_status pfv_csr_from_host(pfv_ctx* h, int64_t nrows, int64_t ncols, const int32_t* indptr, const int32_t* indices,
                              const double* values, pfv_csr** out);
 /* device-to-device copy of matrix `which` (pfv_matrix_id) of handle src */
@@ -1232,7 +1244,9 @@ pfv_status pfv_csr_transpose(pfv_ctx* h, const pfv_csr* A, pfv_csr** out);
 pfv_status pfv_csr_bmat(pfv_ctx* h, int nbr, int nbc, const pfv_csr* const* blocks, const int64_t* row_sizes,
                         const int64_t* col_sizes, pfv_csr** out);
 pfv_status pfv_csr_scale(pfv_csr* A, const double* row_scale, const double* col_scale);   /* in place; host arrays or NULL */
-pfv_status pfv_csr_divide(pfv_csr* A, double s);   /* in place: every value divided by s (scipy's A / s) */
+pfv_status pfv_csr_divide(pfv_csr* A, double s);   /* in place, scipy's A / s: every value MULTIPLIED by the rounded
+                                                      reciprocal 1.0 / s (scipy's _divide is _mul_scalar(1. / s)), which
+                                                      differs from a true division in the last bit */
 pfv_status pfv_csr_spmv(const pfv_csr* A, const double* x, double* y);                     /* host vectors */
 pfv_status pfv_csr_spmv_device(const pfv_csr* A, const double* d_x, double* d_y);
 pfv_status pfv_csr_info(const pfv_csr* A, int64_t* nrows, int64_t* ncols, int64_t* nnz);

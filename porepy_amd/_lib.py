@@ -108,7 +108,8 @@ class Stats(C.Structure):
                 ("advdiff_adjoint_iterations", C.c_int64), ("advdiff_adjoint_gmres_retries", C.c_int64),
                 ("advdiff_adjoint_precond_fallbacks", C.c_int64), ("advdiff_adjoint_accumulate_ms", C.c_double),
                 ("flow_adjoint_exact_calls", C.c_int64), ("flow_adjoint_exact_map_builds", C.c_int64),
-                ("flow_adjoint_exact_map_ms", C.c_double), ("flow_adjoint_exact_ms", C.c_double)]
+                ("flow_adjoint_exact_map_ms", C.c_double), ("flow_adjoint_exact_ms", C.c_double),
+                ("spgemm_path", C.c_int64), ("spgemm_lds_bytes", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

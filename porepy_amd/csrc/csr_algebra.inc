@@ -118,8 +118,10 @@ static void csr_spgemm(pfv_ctx_impl& c, const pfv_csr& A, const pfv_csr& B, pfv_
   const int64_t ttot = read_scalar<int64_t>(s, tptr + n);
   // LDS path: keys + values + run masks of the longest row must fit the workgroup's share of the LDS of THIS device
   // (160 KB on gfx950; 64 KB parts take the global-sort path from ~2600 products per row on)
+#ifdef PFV_EMULATE
+  size_t lds_limit = 160 * 1024;  // (the host emulation stands for gfx950: it selects the path the product takes there)
+#else
   size_t lds_limit = 64 * 1024;
-#ifndef PFV_EMULATE
   {
     int smem = 0;
     if (hipDeviceGetAttribute(&smem, hipDeviceAttributeMaxSharedMemoryPerBlock, c.device) == hipSuccess && smem > 0)
@@ -133,6 +135,8 @@ static void csr_spgemm(pfv_ctx_impl& c, const pfv_csr& A, const pfv_csr& B, pfv_
     lds_need = 8 * (size_t)capP_ + 8 * (size_t)std::max<int64_t>(maxcap, 1) + 8 * (size_t)(capP_ / 64 + 1) + 64;
   }
   if (maxcap > kSpgemmMaxRow || lds_need + 256 > lds_limit || env_int("PFV_SPGEMM_GENERIC", 0) != 0) {
+    c.stats.spgemm_path = 1;
+    c.stats.spgemm_lds_bytes = 0;
     // Rows too long for the LDS sort: all products as (row, column, value) triplets in gather order, two stable radix
     // sorts (by column, then by row) leave them grouped by (row, column) with the gather order kept inside every group,
     // every group summed in that order by the thread of its first element -- the same sums, slower.
@@ -220,6 +224,8 @@ static void csr_spgemm(pfv_ctx_impl& c, const pfv_csr& A, const pfv_csr& B, pfv_
   while (capP < capL) capP <<= 1;
   const int nw = capP / 64 + 1;
   const size_t lds = 8 * (size_t)capP + 8 * (size_t)capL + 8 * (size_t)nw + 64;
+  c.stats.spgemm_path = G;  // (what the launch below takes: wave_for rounds the row's share up to 16 bytes, 64 / G rows a block)
+  c.stats.spgemm_lds_bytes = (int64_t)(((lds + 15) & ~size_t(15)) * (size_t)(64 / G));
   wave_for_g(G, s, n, lds, PFV_LAMBDA(const WaveCtx& w) {
     const int64_t r = w.item;
     unsigned long long* key = reinterpret_cast<unsigned long long*>(w.lds);
@@ -523,8 +529,13 @@ pfv_status pfv_csr_from_host(pfv_ctx* h, int64_t nrows, int64_t ncols, const int
     m->P.nrows = nrows;
     m->P.ncols = ncols;
     m->P.nnz = nnz;
+    // (the kernels that follow, csr_check_sorted first, walk [indptr[r], indptr[r + 1]) of the uploaded arrays: an indptr
+    // that decreases or leaves [0, nnz] is refused here, on the host, before anything is uploaded or launched)
     int mr = 0;
-    for (int64_t r = 0; r < nrows; ++r) mr = std::max(mr, indptr[r + 1] - indptr[r]);
+    for (int64_t r = 0; r < nrows; ++r) {
+      require(indptr[r + 1] >= indptr[r] && indptr[r + 1] <= nnz, "indptr must be non-decreasing and within [0, nnz]");
+      mr = std::max(mr, indptr[r + 1] - indptr[r]);
+    }
     m->P.max_row = mr;
     auto s = h->stream;
     be_h2d(m->P.indptr.ensure((size_t)nrows + 1), indptr, sizeof(int32_t) * (size_t)(nrows + 1), s);
@@ -658,13 +669,15 @@ pfv_status pfv_csr_scale(pfv_csr* A, const double* row_scale, const double* col_
   });
 }
 
-// in place: A <- A / s, every value divided (scipy's ``A / s``: a true division, not a product with the reciprocal)
+// in place: A <- A / s as scipy computes it: ``_divide`` is ``_mul_scalar(1. / s)``, every value multiplied by the rounded
+// reciprocal -- not a true division, from which it differs in the last bit for most s
 pfv_status pfv_csr_divide(pfv_csr* A, double s_) {
   if (!A) return PFV_ERR_ARGUMENT;
   return guarded(A->h, [&] {
     auto s = A->h->stream;
     double* v = A->val;
-    pfv::parallel_for(s, A->P.nnz, PFV_LAMBDA(int64_t e) { v[e] = v[e] / s_; });
+    const double inv = 1.0 / s_;
+    pfv::parallel_for(s, A->P.nnz, PFV_LAMBDA(int64_t e) { v[e] = v[e] * inv; });
     pfv::be_sync(s);
   });
 }

@@ -36,15 +36,21 @@ except ImportError:  # pragma: no cover - the fallback digests the same bytes, j
 
 
 def _content_key(m):
-    """What a remembered upload of the host matrix ``m`` is valid for: shape, nnz and a 64-bit digest of ALL of its
-    VALUES (one pass over the buffer without a copy), so that a matrix changed in place (``m.data[:] = ...``,
-    ``m *= s``, a single entry) is uploaded again instead of being served from the stale device copy.
-    ``DeviceCsr.invalidate(m)`` forgets one matrix explicitly."""
+    """What a remembered upload of the host matrix ``m`` is valid for: shape, nnz, format and a 64-bit digest of each of
+    its arrays -- ALL of its VALUES and, for the compressed formats, ``indices`` and ``indptr`` (one pass over every
+    buffer without a copy) -- so that a matrix changed in place (``m.data[:] = ...``, ``m *= s``, a single entry; the
+    columns of a selection, projection or divergence matrix, whose values are all +-1 and stay what they were) is
+    uploaded again instead of being served from the stale device copy.  ``DeviceCsr.invalidate(m)`` forgets one matrix
+    explicitly."""
     data = getattr(m, "data", None)
     if not isinstance(data, np.ndarray) or data.ndim != 1:
         return (getattr(m, "shape", None), getattr(m, "nnz", None), None)
-    buf = data if data.flags.c_contiguous else np.ascontiguousarray(data)
-    return (m.shape, m.nnz, data.dtype.str, _digest64(memoryview(buf).cast("B")))
+    key = [m.shape, m.nnz, getattr(m, "format", None)]
+    for a in (data, getattr(m, "indices", None), getattr(m, "indptr", None), getattr(m, "row", None), getattr(m, "col", None)):
+        if isinstance(a, np.ndarray):  # (row / col: the coordinate format's index arrays)
+            buf = a if a.flags.c_contiguous else np.ascontiguousarray(a)
+            key += [a.dtype.str, _digest64(memoryview(buf).cast("B"))]
+    return tuple(key)
 
 
 def clear_upload_cache() -> None:
@@ -326,7 +332,7 @@ class DeviceCsr:
         return f"<DeviceCsr {r}x{c}, {z} stored entries, on device>"
 
 
-_UPLOADS: dict = {}  # id(host matrix) -> (weakref to it, its DeviceCsr, (shape, nnz)); see DeviceCsr.from_any
+_UPLOADS: dict = {}  # id(host matrix) -> (weakref to it, its DeviceCsr, _content_key of it); see DeviceCsr.from_any
 
 
 def vstack(mats, context: "_lib.Context | None" = None) -> DeviceCsr:

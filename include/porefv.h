@@ -249,6 +249,11 @@ typedef struct {
                                       8 capP + 8 capL + 8 (capP / 64 + 1) + 64 bytes each, rounded up to 16; capL the
                                       products of the longest row, capP the power of two from capL on); 0 on the global
                                       path.  Beyond 48 KiB the launch opts in to the larger LDS */
+  double advdiff_adjoint_exact_ms;  /* last pfv_advdiff_adjoint / pfv_advdiff_adjoint_exact: the interaction-region passes
+                                      and the cell sum of grad_conductivity_exact, HIP events read after the loop (0: none) */
+  int64_t advdiff_adjoint_exact_passes; /* ... region-kernel launches: ceil(N / B) batches times the non-empty node
+                                      classes (0: no step, a TPFA diffusion, or not asked for) */
+  int64_t advdiff_adjoint_exact_batch; /* ... the B used: exact_batch (0: the default, 32) clipped to N (0: no region pass) */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -1104,7 +1109,8 @@ pfv_status pfv_advdiff_face_flux(pfv_ctx* h, const double* c, double* out);
  * w^n_f = filter_f (c^n difference) - dir_f sgn_f bc_f and dt_f/dK are those of pfv_flow_adjoint for p = c^n, mu =
  * lambda^n, and grad_conductivity has the meaning grad_perm has there: for pfv_tpfa_discretize it is the exact gradient of
  * the discrete problem; for pfv_mpfa_discretize it is the two-point product rule of the reference's AdTpfaFlux, NOT the
- * derivative of the MPFA matrices.  All other gradients are exact for both schemes.  Nothing uses floating-point
+ * derivative of the MPFA matrices: that derivative is the grad_conductivity_exact of pfv_advdiff_adjoint_exact below.
+ * All other gradients are exact for both schemes.  Nothing uses floating-point
  * atomics: two calls give the same bits.
  *   steps_done: the adjoint steps accepted.  A step that does not converge returns PFV_ERR_NOT_CONVERGED and writes NO
  * gradient.  last (may be NULL): the info of the last solve.
@@ -1122,6 +1128,38 @@ pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int
                                double* grad_source, double* grad_bc_values, double* grad_accumulation,
                                double* grad_flux, double* grad_flux_scale, double* grad_conductivity,
                                double* multipliers_out, int32_t* steps_done, pfv_solve_info* last);
+/* The same call -- the same checks and refusals with the same status and text, the same solves, the same bits in every
+ * output of pfv_advdiff_adjoint -- with one more output (csrc/mpfa_adjoint.inc, adj_batch_body):
+ *     grad_conductivity_exact [(3,3,Nc)]  sum_{n=1..N} d/dK [ (z^n)^T (T_D c^n + B_D bc) ] at fixed c^n, bc,
+ *                                  z^n_f = -y^n_f: the exact gradient of J with respect to the conductivity of the discrete
+ *                                  problem, layout of perm_33n, all nine entries independent (on a 2-D grid only the
+ *                                  2 x 2 block is non-zero); needs states; NULL: not formed, the call is
+ *                                  pfv_advdiff_adjoint.
+ * The conductivity enters a step only through div (T_D c^n + B_D bc), and y^n o c^n is not linear in a sum over n, so
+ * every step needs its own solve of every interaction region; the region's geometry, its condensed matrix and its inverse
+ * do not depend on n.  After an accepted step the call writes z^n into slab m of a ring of B = exact_batch slabs (0: the
+ * default, 32; above N: N; negative: PFV_ERR_ARGUMENT) and notes c^n -- read in place when the states are device memory,
+ * staged into a ring of B slabs when they are host memory.  Every B steps, and after the last step for what is pending,
+ * ONE pass over the regions (one per wavefront) sets a region up and inverts it ONCE as pfv_flow_adjoint_exact does, then
+ * runs that call's three stages per pending state with p = c^n, z = z^n and no vector source, the region's vectors reused
+ * (the LDS need is that of pfv_flow_adjoint_exact).  The nd x nd numbers of a sub-cell start from the running sum in
+ * memory (zeros before the first pass), stay in registers across the batch and take the states strictly in the order
+ * n = N, N - 1, .., 1, each state's term summed from zero as in pfv_flow_adjoint_exact: the result has the same bits for
+ * every B.  The cell sum of pfv_flow_adjoint_exact runs once, after the last pass.  No floating-point atomics; no step
+ * adds a host read; the status words of the passes are read once, after the loop.  pfv_tpfa_discretize (the 1-D
+ * delegate of MPFA included): grad_conductivity_exact = the two-point gradient, formed whether or not grad_conductivity
+ * was asked for.  N = 0: zeros, no pass.
+ *   Further statuses: PFV_ERR_ARGUMENT: grad_conductivity_exact without states, a negative exact_batch.
+ * PFV_ERR_UNSUPPORTED names the node whose interaction region does not fit the LDS (found before the first solve);
+ * PFV_ERR_SINGULAR names the node as pfv_mpfa_discretize does.  A refused or failed call writes no output.
+ * pfv_stats: advdiff_adjoint_exact_* (and flow_adjoint_exact_map_* for the cell -> sub-cell map, kept with the sub-cell
+ * topology and shared with pfv_flow_adjoint_exact). */
+pfv_status pfv_advdiff_adjoint_exact(pfv_ctx* h, int n_steps, int64_t n_obs, const int32_t* obs_cells, const double* loads,
+                                     const double* states, int method, double rtol, int maxit, double* grad_c0,
+                                     double* grad_source, double* grad_bc_values, double* grad_accumulation,
+                                     double* grad_flux, double* grad_flux_scale, double* grad_conductivity,
+                                     double* multipliers_out, int32_t* steps_done, pfv_solve_info* last,
+                                     double* grad_conductivity_exact, int exact_batch);
 /* The resident face flux (pfv_mpfa_face_flux) of this handle: d_q (may be NULL) receives its device address -- Nf
  * doubles, valid until the next pfv_mpfa_face_flux or pfv_set_grid on the handle --, q_out (Nf, may be NULL) a copy,
  * in host or device memory as selected by pfv_set_vectors_on_device.  PFV_ERR_ARGUMENT when there is none. */

@@ -53,7 +53,7 @@ EXPORTS = [
     "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl", "pfv_transport_advance_nl_multi",
     "pfv_transport_advance_react", "pfv_transport_adjoint_multi", "pfv_transport_adjoint_react",
     "pfv_transport_adjoint_nl", "pfv_transport_adjoint_nl_multi", "pfv_flow_adjoint", "pfv_flow_adjoint_exact",
-    "pfv_advdiff_adjoint", "pfv_amg_level_rhs",
+    "pfv_advdiff_adjoint", "pfv_advdiff_adjoint_exact", "pfv_amg_level_rhs",
 ]
 
 
@@ -109,7 +109,9 @@ class Stats(C.Structure):
                 ("advdiff_adjoint_precond_fallbacks", C.c_int64), ("advdiff_adjoint_accumulate_ms", C.c_double),
                 ("flow_adjoint_exact_calls", C.c_int64), ("flow_adjoint_exact_map_builds", C.c_int64),
                 ("flow_adjoint_exact_map_ms", C.c_double), ("flow_adjoint_exact_ms", C.c_double),
-                ("spgemm_path", C.c_int64), ("spgemm_lds_bytes", C.c_int64)]
+                ("spgemm_path", C.c_int64), ("spgemm_lds_bytes", C.c_int64),
+                ("advdiff_adjoint_exact_ms", C.c_double), ("advdiff_adjoint_exact_passes", C.c_int64),
+                ("advdiff_adjoint_exact_batch", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -374,6 +376,10 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_advdiff_adjoint.argtypes = [_h, C.c_int, C.c_int64, _ip, _dp, _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp,
                                         _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
     lib.pfv_advdiff_adjoint.restype = C.c_int
+    lib.pfv_advdiff_adjoint_exact.argtypes = [_h, C.c_int, C.c_int64, _ip, _dp, _dp, C.c_int, C.c_double, C.c_int, _dp, _dp,
+                                              _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(SolveInfo),
+                                              _dp, C.c_int]
+    lib.pfv_advdiff_adjoint_exact.restype = C.c_int
     lib.pfv_resident_flux.argtypes = [_h, C.POINTER(C.c_void_p), _dp]
     lib.pfv_sweep_info.argtypes = [_h, _lp, _ip, _ip]
     lib.pfv_sweep_info.restype = C.c_int
@@ -2051,17 +2057,22 @@ class Context:
 
     ADVDIFF_ADJOINT_GRADIENTS = ("c0", "source", "bc_values", "accumulation", "flux", "flux_scale", "conductivity",
                                  "multipliers")
+    ADVDIFF_ADJOINT_EXACT = ("conductivity_exact",)
 
     def advdiff_adjoint(self, n_steps: int, loads, states=None, obs_cells=None, want=("c0", "source", "bc_values"),
                         method="bicgstab", rtol=1e-12, maxit=20000, precond="amg", raise_on_fail=True, device=False,
-                        out_ptrs=None):
+                        out_ptrs=None, exact_batch=0):
         """The adjoint of ``advdiff_advance`` on the system of the last ``advdiff_assemble`` (pfv_advdiff_adjoint): the
         gradients of ``J = sum_n <loads[n-1], c^n[obs_cells]>`` through ``n_steps`` forward steps, one transposed Krylov
         solve per step.  ``loads``: N x n_obs, ``obs_cells``: n_obs cell indices (host) or None (every cell),
         ``states``: (N + 1) x Nc (c^0 .. c^N) or None.  ``want``: names out of ``ADVDIFF_ADJOINT_GRADIENTS`` -- "c0",
         "source", "accumulation" (Nc), "bc_values", "flux" (Nf), "flux_scale" (a float), "conductivity" (3, 3, Nc; exact
         for a TPFA diffusion, for MPFA the two-point product rule of ``ad_flux_system``, not the derivative of the MPFA
-        matrices) and "multipliers" (N x Nc); "accumulation", "flux", "flux_scale" and "conductivity" need ``states``.
+        matrices: that one is "conductivity_exact") and "multipliers" (N x Nc) -- or out of ``ADVDIFF_ADJOINT_EXACT``:
+        "conductivity_exact" (3, 3, Nc; pfv_advdiff_adjoint_exact: the derivative of the MPFA matrices, one pass over the
+        interaction regions per ``exact_batch`` steps, 0: the default; the same bits for every ``exact_batch``; for a TPFA
+        diffusion the bits of "conductivity").  Without that name the call is pfv_advdiff_adjoint.  "accumulation",
+        "flux", "flux_scale", "conductivity" and "conductivity_exact" need ``states``.
         Returns (grads, info).  A step that does not converge leaves the gradients zero.  ``device``: ``loads`` and
         ``states`` are addresses of device buffers and the wanted outputs go to the addresses in ``out_ptrs`` (name ->
         address; "flux_scale" is returned in grads all the same: it is host memory)."""
@@ -2072,9 +2083,10 @@ class Context:
         obs, n_obs = self._adjoint_obs(obs_cells)
         want = tuple(want)
         for name in want:
-            if name not in self.ADVDIFF_ADJOINT_GRADIENTS:
-                raise ValueError(f"want: unknown gradient {name!r} (known: {', '.join(self.ADVDIFF_ADJOINT_GRADIENTS)})")
-            if name in ("accumulation", "flux", "flux_scale", "conductivity") and states is None:
+            if name not in self.ADVDIFF_ADJOINT_GRADIENTS + self.ADVDIFF_ADJOINT_EXACT:
+                raise ValueError(f"want: unknown gradient {name!r} (known: "
+                                 f"{', '.join(self.ADVDIFF_ADJOINT_GRADIENTS + self.ADVDIFF_ADJOINT_EXACT)})")
+            if name in ("accumulation", "flux", "flux_scale", "conductivity", "conductivity_exact") and states is None:
                 raise ValueError(f'the gradient "{name}" needs states (c^0 .. c^N)')
         if device:
             pl = C.cast(int(loads), _dp)
@@ -2091,13 +2103,14 @@ class Context:
                     raise ValueError(f"states must have shape ({n_steps + 1}, {self.nc}), not {stt.shape}")
             ps = _ptr(stt, _dp)
         shapes = {"c0": (self.nc,), "source": (self.nc,), "bc_values": (self.nf,), "accumulation": (self.nc,),
-                  "flux": (self.nf,), "conductivity": (3, 3, self.nc), "multipliers": (n_steps, self.nc)}
+                  "flux": (self.nf,), "conductivity": (3, 3, self.nc), "multipliers": (n_steps, self.nc),
+                  "conductivity_exact": (3, 3, self.nc)}
         scale = np.zeros(1) if "flux_scale" in want else None
         if device:
             grads = {}
             outs = {name: C.cast(int((out_ptrs or {})[name]), _dp) for name in want if name != "flux_scale"}
         else:
-            grads = {name: np.zeros(shapes[name]) for name in self.ADVDIFF_ADJOINT_GRADIENTS
+            grads = {name: np.zeros(shapes[name]) for name in self.ADVDIFF_ADJOINT_GRADIENTS + self.ADVDIFF_ADJOINT_EXACT
                      if name in want and name != "flux_scale"}
             outs = {name: _ptr(a, _dp) for name, a in grads.items()}
         self._select_precond(precond)
@@ -2105,10 +2118,13 @@ class Context:
         if device:
             self._dev(True)
         try:
-            st = self.lib.pfv_advdiff_adjoint(
-                self._h, n_steps, n_obs, _ptr(obs, _ip), pl, ps, code, float(rtol), int(maxit), outs.get("c0"),
-                outs.get("source"), outs.get("bc_values"), outs.get("accumulation"), outs.get("flux"), _ptr(scale, _dp),
-                outs.get("conductivity"), outs.get("multipliers"), C.byref(done), C.byref(info))
+            args = (self._h, n_steps, n_obs, _ptr(obs, _ip), pl, ps, code, float(rtol), int(maxit), outs.get("c0"),
+                    outs.get("source"), outs.get("bc_values"), outs.get("accumulation"), outs.get("flux"), _ptr(scale, _dp),
+                    outs.get("conductivity"), outs.get("multipliers"), C.byref(done), C.byref(info))
+            if "conductivity_exact" in want:
+                st = self.lib.pfv_advdiff_adjoint_exact(*args, outs["conductivity_exact"], int(exact_batch))
+            else:
+                st = self.lib.pfv_advdiff_adjoint(*args)
         finally:
             if device:
                 self._dev(False)

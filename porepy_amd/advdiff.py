@@ -178,7 +178,7 @@ class AdvectionDiffusion:
 
     def adjoint(self, sd, data: dict, n_steps: int, accumulation, loads, states, obs_cells=None, source=None,
                 want=("c0", "source", "bc_values"), method: str = "bicgstab", precond: str = "amg",
-                rtol: float = 1e-12, maxit: int = 20000, raise_on_fail: bool = True):
+                rtol: float = 1e-12, maxit: int = 20000, raise_on_fail: bool = True, exact_batch=None):
         """The adjoint of ``advance``: the gradients of ``J = sum_{n=1..N} <loads[n-1], c^n[obs_cells]>`` through
         ``n_steps`` = N steps ``S c^n = acc o c^{n-1} - b_ref + b_D + source`` (csrc/advdiff_adjoint.inc).  The system is
         assembled exactly as ``advance`` assembles it; then, backwards in time, ``S^T lambda^n = g^n + acc o lambda^{n+1}``
@@ -202,12 +202,18 @@ class AdvectionDiffusion:
         "flux_scale"      float     ``(1/w) sum_f q_f grad_flux_f``                            (needs states)
         "conductivity"    3,3,Nc    ``sum_e zw_f dt_f/dK_rs(c)``, ``zw_f = -sum_n y^n_f w^n_f`` with the face weight
                                     ``w^n_f`` and the two-point ``dt_f/dK`` of ``adjoint_flow``  (needs states)
+        "conductivity_exact"  3,3,Nc  ``sum_n d/dK [(z^n)^T (T_D c^n + B_D bc)]`` at fixed ``c^n``, ``z^n = -y^n``: the
+                                    derivative of the MPFA matrices themselves                (needs states)
         "multipliers"     N,Nc      every ``lambda^n``
         ================  ========  ======================================================================
 
         "conductivity" has the meaning ``grad_perm`` has in ``adjoint_flow``: it is exact for a TPFA diffusion; for MPFA
-        it is the two-point product rule of ``AdTpfaFlux``, NOT the derivative of the MPFA matrices.  All other gradients
-        are exact for both schemes.  ``grads["flux"]`` is what ``Mpfa.adjoint_flow(..., grad_flux=grads["flux"])`` /
+        it is the two-point product rule of ``AdTpfaFlux``, NOT the derivative of the MPFA matrices.  That derivative is
+        "conductivity_exact" (``Context.ADVDIFF_ADJOINT_EXACT``; pfv_advdiff_adjoint_exact, csrc/mpfa_adjoint.inc): the
+        exact gradient of the discrete problem with respect to the tensor of every cell, all nine entries independent --
+        one pass over the interaction regions per ``exact_batch`` steps (None: the library's default), each region set up
+        and inverted once per pass; the bits do not depend on ``exact_batch``.  For a TPFA diffusion (a 1-D grid
+        included) it has the bits of "conductivity".  All other gradients are exact for both schemes.  ``grads["flux"]`` is what ``Mpfa.adjoint_flow(..., grad_flux=grads["flux"])`` /
         ``Tpfa.adjoint_flow`` of the flow problem that produced ``darcy_flux`` takes: the chain ends at the permeability
         of the flow.
 
@@ -218,7 +224,8 @@ class AdvectionDiffusion:
         try:
             return self.context(sd).advdiff_adjoint(n_steps, loads, states=states, obs_cells=obs_cells, want=want,
                                                     method=method, rtol=rtol, maxit=maxit, precond=precond,
-                                                    raise_on_fail=raise_on_fail)
+                                                    raise_on_fail=raise_on_fail,
+                                                    exact_batch=0 if exact_batch is None else exact_batch)
         except _lib.PorefvError as e:
             if e.status == 4:
                 raise ValueError(e.message) from None

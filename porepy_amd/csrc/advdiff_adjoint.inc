@@ -13,7 +13,9 @@
 //
 // cup is the value the upwind rule takes at f (upstream c^n; bc on a Dirichlet inflow face; 0 on a Neumann face), w^n_f
 // the face weight of flow_adjoint_faces for p = c^n.  grad_conductivity is exact for a TPFA diffusion; for MPFA it is the
-// two-point product rule of the reference's AdTpfaFlux, NOT the derivative of the MPFA matrices.
+// two-point product rule of the reference's AdTpfaFlux, NOT the derivative of the MPFA matrices.  That derivative is
+//   grad_conductivity_exact = sum_n d/dK [ (z^n)^T (T_D c^n + B_D bc) ] at fixed c^n, bc,   z^n_f = -y^n_f
+// (pfv_advdiff_adjoint_exact): the load z^n is formed here, the region passes are mpfa_adjoint.inc's adj_batch_body.
 //
 // Per step: one right-hand-side kernel, the solve (the caller), ONE pass over the faces and ONE over the cells.  No
 // floating-point atomics; every sum has a fixed order; the PFV_EMULATE build runs the same bodies.
@@ -129,6 +131,22 @@ static void advdiff_adjoint_face_sum(pfv_ctx_impl& c, const int32_t* first, cons
       if (e2 != e1) y += (double)cf_sgn[e2] * Lam[ecell[e2]];
     }
     Y[f] = y;
+  });
+}
+
+// z^n_f = -y^n_f = -(cell_faces lambda^n)_f, the load of the exact conductivity gradient (mpfa_adjoint.inc:
+// adj_batch_body) for step n; the sides in the order of the half-face lists, a face without cells gets zero
+static void advdiff_adjoint_exact_load(pfv_ctx_impl& c, const int32_t* first, const int32_t* last, const int32_t* ecell,
+                                       const double* lam, double* z) {
+  const int8_t* cf_sgn = c.cf_sgn;
+  parallel_for(c.stream, c.nf, PFV_LAMBDA(int64_t f) {
+    const int e1 = first[f], e2 = last[f];
+    double y = 0.0;
+    if (e1 != 0x7f7f7f7f && e2 >= 0) {
+      y = (double)cf_sgn[e1] * lam[ecell[e1]];
+      if (e2 != e1) y += (double)cf_sgn[e2] * lam[ecell[e2]];
+    }
+    z[f] = -y;
   });
 }
 

@@ -415,6 +415,10 @@ struct pfv_ctx_impl {
   // ada_sB two slabs of states staged from the host; the accumulators Lambda [nc], grad_accumulation [nc], sum y cup
   // [nf], zw [nf]; ada_mult the multipliers [N][nc]; ada_work: Y [nf] | gb [nf] | partial sums | total
   Buf<double> ada_lam, ada_keep, ada_rhs, ada_sA, ada_sB, ada_Lam, ada_gacc, ada_sq, ada_zw, ada_mult, ada_work;
+  // pfv_advdiff_adjoint_exact: the ring of loads z^n = -cell_faces lambda^n [B][nf], the ring of states staged from the
+  // host [B][nc], the status words of its region passes (read once, after the loop); the sums per sub-cell: adj_sub
+  Buf<double> ada_zr, ada_sr;
+  Buf<int32_t> ada_st;
 
   // ---- flow-ordered sweep (sweep.inc): levels of the flux graph of the transport / advection-diffusion system -----
   std::unique_ptr<Sweep> sweep;      // the order and what it was built from (nullptr / !valid: none)

@@ -2745,21 +2745,44 @@ pfv_status pfv_advdiff_face_flux(pfv_ctx* h, const double* c, double* out) {
   });
 }
 
+// The cell -> sub-cell map of the exact gradients (mpfa_adjoint.inc), kept under the topology digest.  true: built now.
+static bool adj_ensure_cell_map(pfv_ctx* h) {
+  const unsigned long long key = h->topo_key ? h->topo_key : pfv::topology_digest(*h);
+  if (h->adj_map_key != 0 && h->adj_map_key == key) return false;
+  h->adj_map_key = 0;
+  pfv::adj_cell_map(*h);
+  h->adj_map_key = key;
+  ++h->stats.flow_adjoint_exact_map_builds;
+  return true;
+}
+
 // ---- the adjoint of the advection-diffusion step (advdiff_adjoint.inc) ---------------------------------------------
 // The checks and the set-up run as the `checks` of advance_steps and end with (pat_A, S^T, diag, ada_rhs) as the active
 // system; the loop is advance_steps itself -- the state is lambda, step `step` is n = N - step --, with the right-hand
 // side and the two accumulation passes as its hooks; the products that need the sums over the steps follow the loop.
-pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int32_t* obs_cells, const double* loads,
-                               const double* states, int method, double rtol, int maxit, double* grad_c0,
-                               double* grad_source, double* grad_bc_values, double* grad_accumulation,
-                               double* grad_flux, double* grad_flux_scale, double* grad_conductivity,
-                               double* multipliers_out, int32_t* steps_done, pfv_solve_info* last) {
+// (grad_exact: the additional output of pfv_advdiff_adjoint_exact, nullptr for pfv_advdiff_adjoint -- whose path through
+// this body is the one it always took.  With an MPFA diffusion the after hook also writes z^n = -cell_faces lambda^n into
+// slab m of a ring of B = exact_batch slabs and notes c^n; every B accepted steps, and after the last one, ONE pass over
+// the interaction regions (pfv::advdiff_adjoint_exact_batch) adds the pending states to the running sums per sub-cell.)
+enum { kAdvdiffExactBatch = 32 };  // the default B
+static pfv_status advdiff_adjoint_call(pfv_ctx* h, int n_steps, int64_t n_obs, const int32_t* obs_cells,
+                                       const double* loads, const double* states, int method, double rtol, int maxit,
+                                       double* grad_c0, double* grad_source, double* grad_bc_values,
+                                       double* grad_accumulation, double* grad_flux, double* grad_flux_scale,
+                                       double* grad_conductivity, double* multipliers_out, int32_t* steps_done,
+                                       pfv_solve_info* last, double* grad_exact, int exact_batch) {
   static const StepLoop loop{&pfv_ctx::ada_lam, &pfv_ctx::ada_keep, nullptr, false, true};
   const int none = 0x7f7f7f7f;
   const int N = n_steps;
-  const bool want_sq = grad_flux || grad_flux_scale, want_zw = grad_conductivity != nullptr;
+  const bool want_sq = grad_flux || grad_flux_scale;
   const bool want_Lam = grad_source || grad_bc_values;
-  const bool face_pass = want_sq || want_zw, cell_pass = want_Lam || grad_accumulation || multipliers_out;
+  const bool cell_pass = want_Lam || grad_accumulation || multipliers_out;
+  // (a TPFA diffusion: the two-point gradient is the exact one, formed whether or not grad_conductivity was asked for)
+  bool want_zw = grad_conductivity != nullptr, face_pass = want_sq || want_zw;
+  bool region = false;  // the interaction-region passes run
+  int B = 0, pend = 0, n_first = 0, passes = 0;
+  std::vector<std::unique_ptr<pfv::Timer>> exact_tm;
+  double exact_ms = 0.0;
   bool activated = false, on_dev = false;
   size_t nc = 0, nf = 0;
   int32_t *first = nullptr, *last_hf = nullptr, *ecell = nullptr;
@@ -2774,7 +2797,7 @@ pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int
   hooks.rhs = [&](int step) {
     const int n = N - step;
     pfv::pfv_ctx_impl& cx = *h;
-    if (states && (face_pass || grad_accumulation)) {  // c^n and c^{n-1}: in place on the device, else one slab per step
+    if (states && (face_pass || grad_accumulation || region)) {  // c^n and c^{n-1}: in place on the device, else one slab per step
       if (on_dev) {
         cn = states + (size_t)n * nc;
         cprev = states + (size_t)(n - 1) * nc;
@@ -2782,9 +2805,10 @@ pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int
         be_h2d(cx.ada_sB.p, states + (size_t)(n - 1) * nc, sizeof(double) * nc, cx.stream);
         cn = cx.ada_sA.p;
         cprev = cx.ada_sB.p;
-      } else {
-        be_h2d(cx.ada_sA.p, states + (size_t)n * nc, sizeof(double) * nc, cx.stream);
-        cn = cx.ada_sA.p;
+      } else {  // (with the region passes: staged where the batch reads it)
+        double* slab = region ? cx.ada_sr.p + (size_t)pend * nc : cx.ada_sA.p;
+        be_h2d(slab, states + (size_t)n * nc, sizeof(double) * nc, cx.stream);
+        cn = slab;
       }
     }
     pfv::advdiff_adjoint_rhs(cx, slot, cx.aj_loads.p + (size_t)(n - 1) * (size_t)n_obs, acc, cx.ada_lam.p, cx.ada_rhs.p);
@@ -2802,11 +2826,29 @@ pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int
       pfv::advdiff_adjoint_cells(cx, cx.ada_lam.p, cprev, cn, want_Lam ? cx.ada_Lam.p : nullptr,
                                  grad_accumulation ? cx.ada_gacc.p : nullptr,
                                  multipliers_out ? cx.ada_mult.p + (size_t)(n - 1) * nc : nullptr);
+    if (region) pfv::advdiff_adjoint_exact_load(cx, first, last_hf, ecell, cx.ada_lam.p, cx.ada_zr.p + (size_t)pend * nf);
 #ifdef PFV_EMULATE
     pass_ms += tm.stop(cx.stream);
 #else
     tm.mark(cx.stream);  // (read after the loop: the step adds no host read)
 #endif
+    if (region) {  // state m = pend of the batch is step n = n_first - m
+      if (!on_dev && grad_accumulation) pfv::be_d2d(cx.ada_sr.p + (size_t)pend * nc, cn, sizeof(double) * nc, cx.stream);
+      if (pend == 0) n_first = n;
+      if (++pend == B || n == 1) {
+        exact_tm.emplace_back(std::make_unique<pfv::Timer>());
+        pfv::Timer& te = *exact_tm.back();
+        te.start(cx.stream);
+        passes += pfv::advdiff_adjoint_exact_batch(cx, cx.ada_st.p, on_dev ? states + (size_t)n_first * nc : cx.ada_sr.p,
+                                                   on_dev ? -(int64_t)nc : (int64_t)nc, cx.ada_zr.p, cx.adv_bc.p, pend);
+#ifdef PFV_EMULATE
+        exact_ms += te.stop(cx.stream);
+#else
+        te.mark(cx.stream);
+#endif
+        pend = 0;
+      }
+    }
     if (states && !on_dev && grad_accumulation) cx.ada_sA.swap(cx.ada_sB);
     ++done;
   };
@@ -2827,6 +2869,8 @@ pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int
     require(states || !grad_flux, "grad_flux needs states (c^0 .. c^N)");
     require(states || !grad_flux_scale, "grad_flux_scale needs states (c^0 .. c^N)");
     require(states || !grad_conductivity, "grad_conductivity needs states (c^0 .. c^N)");
+    require(states || !grad_exact, "grad_conductivity_exact needs states (c^0 .. c^N)");
+    require(exact_batch >= 0, "exact_batch must not be negative");
     require(loads || n_steps == 0 || n_obs == 0, "loads is required");
     if (!h->tpfa_mode && !h->rows_complete)
       throw pfv::Error(PFV_ERR_UNSUPPORTED, "the advection-diffusion adjoint does not cover a partial discretization "
@@ -2851,6 +2895,15 @@ pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int
     adjoint_take_slots(h, n_obs, obs_cells);
     slot = obs_cells ? h->aj_slot.p : nullptr;
     acc = h->have_adv_acc ? h->adv_acc.p : nullptr;
+    if (grad_exact && h->tpfa_mode) want_zw = face_pass = true;
+    region = grad_exact && !h->tpfa_mode;
+    if (region) {  // (a region too large for the LDS: refused before anything runs)
+      pfv::adj_check_lds(*h);
+      pfv::Timer tm;
+      tm.start(s);
+      if (adj_ensure_cell_map(h)) h->stats.flow_adjoint_exact_map_ms = tm.stop(s);
+      B = std::max(1, std::min(exact_batch ? exact_batch : (int)kAdvdiffExactBatch, N));
+    }
     whole = std::make_unique<pfv::Timer>();
     whole->start(s);
     // ---- what belongs to the patterns and the grid: the half-face lists, the column maps, the transposed positions
@@ -2879,7 +2932,14 @@ pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int
     if (want_sq) zeros(h->ada_sq, nf);
     if (want_zw) zeros(h->ada_zw, nf);
     if (multipliers_out) zeros(h->ada_mult, (size_t)N * nc);
-    if (states && !on_dev && (face_pass || grad_accumulation)) {
+    if (region) {  // the ring of loads, the ring of staged states, the running sums per sub-cell, the status words
+      const size_t nsub = (size_t)std::max<int64_t>(h->nh / h->nd * h->nd * h->nd, 1);
+      h->ada_zr.ensure((size_t)B * std::max<size_t>(nf, 1));
+      if (!on_dev) h->ada_sr.ensure((size_t)B * std::max<size_t>(nc, 1));
+      pfv::be_memset(h->adj_sub.ensure(nsub), 0, sizeof(double) * nsub, s);
+      pfv::be_memset(h->ada_st.ensure(16), 0, sizeof(int32_t) * 4, s);
+    }
+    if (states && !on_dev && (face_pass || grad_accumulation || region)) {
       h->ada_sA.ensure(nc);
       h->ada_sB.ensure(nc);
       if (grad_accumulation && N > 0) be_h2d(h->ada_sA.p, states + (size_t)N * nc, sizeof(double) * nc, s);  // c^N
@@ -2904,9 +2964,24 @@ pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int
     for (auto& t : pass_tm) pass_ms += t->elapsed_after_sync();
 #endif
     pass_tm.clear();
+#ifndef PFV_EMULATE
+    for (auto& t : exact_tm) exact_ms += t->elapsed_after_sync();
+#endif
+    exact_tm.clear();
     if (st == PFV_OK) {
       const size_t ncf = (size_t)cx.ncf;
-      pfv::Buf<double> inv_, gk_;
+      pfv::Buf<double> inv_, gk_, ge_;
+      double* ge = nullptr;
+      if (region) {  // the status words of all passes, read once; then the cell sum
+        int32_t sth[4];
+        be_d2h(sth, cx.ada_st.p, sizeof(sth), s);
+        pfv::adj_throw_status(sth);
+        pfv::Timer tm;
+        tm.start(s);
+        ge = ge_.ensure(9 * nc);
+        pfv::adj_cell_sum(cx, cx.adj_sub.p, ge);
+        exact_ms += tm.stop(s);
+      }
       double* work = cx.ada_work.ensure(2 * nf + pfv::kAdaParts + 1);
       double *Y = work, *gb = work + nf, *parts = work + 2 * nf, *total = parts + pfv::kAdaParts;
       if (grad_bc_values) {
@@ -2915,7 +2990,7 @@ pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int
         pfv::advdiff_adjoint_grad_bc(cx, cx.adv_q.p, cx.adv_w, Y, gb);
       }
       double* gk = nullptr;
-      if (grad_conductivity) {
+      if (want_zw) {
         gk = gk_.ensure(9 * nc);
         pfv::flow_adjoint_grad_perm(cx, first, last_hf, cx.ada_zw.p, inv_.ensure(std::max<size_t>(ncf, 1)), gk);
       }
@@ -2928,7 +3003,8 @@ pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int
       if (grad_accumulation) vec_out(h, grad_accumulation, cx.ada_gacc.p, nc);
       if (grad_flux) vec_out(h, grad_flux, cx.ada_sq.p, nf);
       if (grad_flux_scale) be_d2h(grad_flux_scale, total, sizeof(double), s);  // (host memory, as the scale itself is)
-      if (gk) vec_out(h, grad_conductivity, gk, 9 * nc);
+      if (grad_conductivity) vec_out(h, grad_conductivity, gk, 9 * nc);
+      if (grad_exact) vec_out(h, grad_exact, ge ? ge : gk, 9 * nc);
       if (multipliers_out) vec_out(h, multipliers_out, cx.ada_mult.p, (size_t)N * nc);
     } else {
       h->stats.advdiff_adjoint_ms = whole->stop(s);
@@ -2941,7 +3017,31 @@ pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int
   h->stats.advdiff_adjoint_gmres_retries = tot.gmres_retries;
   h->stats.advdiff_adjoint_precond_fallbacks = tot.precond_fallbacks;
   h->stats.advdiff_adjoint_accumulate_ms = pass_ms;
+  h->stats.advdiff_adjoint_exact_ms = exact_ms;
+  h->stats.advdiff_adjoint_exact_passes = passes;
+  h->stats.advdiff_adjoint_exact_batch = B;
   return step_status(h, st, err, st2);
+}
+
+pfv_status pfv_advdiff_adjoint(pfv_ctx* h, int n_steps, int64_t n_obs, const int32_t* obs_cells, const double* loads,
+                               const double* states, int method, double rtol, int maxit, double* grad_c0,
+                               double* grad_source, double* grad_bc_values, double* grad_accumulation,
+                               double* grad_flux, double* grad_flux_scale, double* grad_conductivity,
+                               double* multipliers_out, int32_t* steps_done, pfv_solve_info* last) {
+  return advdiff_adjoint_call(h, n_steps, n_obs, obs_cells, loads, states, method, rtol, maxit, grad_c0, grad_source,
+                              grad_bc_values, grad_accumulation, grad_flux, grad_flux_scale, grad_conductivity,
+                              multipliers_out, steps_done, last, nullptr, 0);
+}
+
+pfv_status pfv_advdiff_adjoint_exact(pfv_ctx* h, int n_steps, int64_t n_obs, const int32_t* obs_cells, const double* loads,
+                                     const double* states, int method, double rtol, int maxit, double* grad_c0,
+                                     double* grad_source, double* grad_bc_values, double* grad_accumulation,
+                                     double* grad_flux, double* grad_flux_scale, double* grad_conductivity,
+                                     double* multipliers_out, int32_t* steps_done, pfv_solve_info* last,
+                                     double* grad_conductivity_exact, int exact_batch) {
+  return advdiff_adjoint_call(h, n_steps, n_obs, obs_cells, loads, states, method, rtol, maxit, grad_c0, grad_source,
+                              grad_bc_values, grad_accumulation, grad_flux, grad_flux_scale, grad_conductivity,
+                              multipliers_out, steps_done, last, grad_conductivity_exact, exact_batch);
 }
 
 pfv_status pfv_mpsa_set_params(pfv_ctx* h, const double* stiffness_99n, const double* cell_volumes,
@@ -4284,15 +4384,8 @@ static pfv_status flow_adjoint_call(pfv_ctx* h, const double* p, const double* b
       h->stats.flow_adjoint_gradient_ms = tm.stop(s);
       double* ge = nullptr;
       if (grad_perm_exact && !h->tpfa_mode) {
-        const unsigned long long key = h->topo_key ? h->topo_key : pfv::topology_digest(*h);
-        if (h->adj_map_key == 0 || h->adj_map_key != key) {
-          tm.start(s);
-          h->adj_map_key = 0;
-          pfv::adj_cell_map(*h);
-          h->adj_map_key = key;
-          ++h->stats.flow_adjoint_exact_map_builds;
-          h->stats.flow_adjoint_exact_map_ms = tm.stop(s);
-        }
+        tm.start(s);
+        if (adj_ensure_cell_map(h)) h->stats.flow_adjoint_exact_map_ms = tm.stop(s);
         ge = ge_.ensure(9 * nc);
         tm.start(s);
         pfv::flow_adjoint_grad_perm_exact(*h, d_p, d_bc, d_vs, vd, z, ge);

@@ -1456,6 +1456,41 @@ class Context:
             self._check(st)
         return c, out
 
+    # ---- what the step methods share (the forward ones here, the adjoints below) ----
+    def _component_state(self, c0, most, what):
+        """(c, k): a copy of ``c0`` as a k x Nc array, k in 1 .. ``most``"""
+        c = np.array(c0, dtype=np.float64, copy=True, order="C")
+        if c.ndim != 2 or c.shape[1] != self.nc:
+            raise ValueError(f"c0 must have shape (k, {self.nc}), not {c.shape}")
+        k = c.shape[0]
+        if not 1 <= k <= most:
+            raise ValueError(f"the number of {what} must lie in 1 .. {most}, not {k} (c0 has shape {c.shape})")
+        return c, k
+
+    @staticmethod
+    def _per_component(k, *arrays):
+        """Each of (name, array, n, needed) as a k x n array; None for one that is absent and not needed"""
+        out = []
+        for name, a, n, needed in arrays:
+            if a is None and needed:
+                raise ValueError(f"{name} is required")
+            a = None if a is None else _f64(a)
+            if a is not None and a.shape != (k, n):
+                raise ValueError(f"{name} must have shape ({k}, {n}), not {a.shape}")
+            out.append(a)
+        return out
+
+    def _step_result(self, st, raise_on_fail, **carried):
+        """A failed call raises, but for a refused step (6) that the caller asked to have returned; the error carries
+        ``carried``: the ``state`` before the refused step, the ``info`` of what was done until then."""
+        if st != 0 and (raise_on_fail or st != 6):
+            try:
+                self._check(st)
+            except PorefvError as e:
+                for name, value in carried.items():
+                    setattr(e, name, value)
+                raise
+
     def transport_advance_multi(self, c0, n_steps: int, accumulation, bc_values, q=None, source=None,
                                 method="bicgstab", rtol=1e-12, maxit=10000, raise_on_fail=True, precond="jacobi"):
         """``n_steps`` implicit Euler steps of k quantities on the flux of the one-component upwind discretization on
@@ -1466,25 +1501,9 @@ class Context:
         code = {"bicgstab": SOLVE_BICGSTAB, "gmres": SOLVE_GMRES}[method]
         if precond not in ("jacobi", "sweep"):
             raise ValueError('precond must be "jacobi" or "sweep"')
-        c = np.array(c0, dtype=np.float64, copy=True, order="C")
-        if c.ndim != 2 or c.shape[1] != self.nc:
-            raise ValueError(f"c0 must have shape (k, {self.nc}), not {c.shape}")
-        k = c.shape[0]
-        if not 1 <= k <= 64:
-            raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (c0 has shape {c.shape})")
-        arrays = []
-        for name, a, n, needed in (("accumulation", accumulation, self.nc, True), ("bc_values", bc_values, self.nf, True),
-                                   ("source", source, self.nc, False)):
-            if a is None:
-                if needed:
-                    raise ValueError(f"{name} is required")
-                arrays.append(None)
-                continue
-            a = _f64(a)
-            if a.shape != (k, n):
-                raise ValueError(f"{name} must have shape ({k}, {n}), not {a.shape}")
-            arrays.append(a)
-        acc, bv, src = arrays
+        c, k = self._component_state(c0, 64, "components")
+        acc, bv, src = self._per_component(k, ("accumulation", accumulation, self.nc, True),
+                                           ("bc_values", bc_values, self.nf, True), ("source", source, self.nc, False))
         kq, pq = self._vec(q, self.nf, "the flux array", False)
         self._select_precond(precond)
         done, infos = C.c_int32(0), (SolveInfo * k)()
@@ -1494,8 +1513,7 @@ class Context:
         out = {"steps_done": done.value, "iterations": [i.iterations for i in infos],
                "converged": [bool(i.converged) for i in infos], "rel_residual": [i.rel_residual for i in infos],
                "solve_ms": [i.solve_ms for i in infos]}
-        if st != 0 and (raise_on_fail or st != 6):
-            self._check(st)
+        self._step_result(st, raise_on_fail)
         return c, out
 
     def transport_advance_nl(self, s0, n_steps: int, accumulation, bc_values, fluxfn_kind: int, fluxfn_params=(),
@@ -1523,12 +1541,7 @@ class Context:
                                                _ptr(s, _dp), C.byref(done), C.byref(info))
         out = {"steps_done": done.value, "iterations": info.iterations, "converged": bool(info.converged),
                "rel_residual": info.rel_residual, "solve_ms": info.solve_ms}
-        if st != 0 and (raise_on_fail or st != 6):
-            try:
-                self._check(st)
-            except PorefvError as e:  # (the state before the refused step and what was done until then)
-                e.state, e.info = s, out
-                raise
+        self._step_result(st, raise_on_fail, state=s, info=out)
         return s, out
 
     def transport_advance_nl_multi(self, s0, c0, n_steps: int, accumulation, bc_values, c_bc_values, fluxfn_kind: int,
@@ -1544,25 +1557,9 @@ class Context:
         s = np.array(s0, dtype=np.float64, copy=True).ravel()
         if s.shape != (self.nc,):
             raise ValueError("s0 must have one entry per cell")
-        c = np.array(c0, dtype=np.float64, copy=True, order="C")
-        if c.ndim != 2 or c.shape[1] != self.nc:
-            raise ValueError(f"c0 must have shape (k, {self.nc}), not {c.shape}")
-        k = c.shape[0]
-        if not 1 <= k <= 64:
-            raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (c0 has shape {c.shape})")
-        arrays = []
-        for name, a, n, needed in (("c_bc_values", c_bc_values, self.nf, True), ("sorption", sorption, self.nc, False),
-                                   ("c_source", c_source, self.nc, False)):
-            if a is None:
-                if needed:
-                    raise ValueError(f"{name} is required")
-                arrays.append(None)
-                continue
-            a = _f64(a)
-            if a.shape != (k, n):
-                raise ValueError(f"{name} must have shape ({k}, {n}), not {a.shape}")
-            arrays.append(a)
-        cbv, ads, csrc = arrays
+        c, k = self._component_state(c0, 64, "components")
+        cbv, ads, csrc = self._per_component(k, ("c_bc_values", c_bc_values, self.nf, True),
+                                             ("sorption", sorption, self.nc, False), ("c_source", c_source, self.nc, False))
         par = np.ascontiguousarray(fluxfn_params, dtype=np.float64).ravel()
         kq, pq = self._vec(q, self.nf, "the flux array", False)
         kb, pb = self._vec(bc_values, self.nf, "bc_values", False)
@@ -1579,12 +1576,7 @@ class Context:
         out = {"steps_done": done.value, "iterations": infos[0].iterations, "converged": bool(infos[0].converged),
                "rel_residual": infos[0].rel_residual, "solve_ms": infos[0].solve_ms,
                "c_rel_residual": [i.rel_residual for i in infos[1:]], "c_converged": [bool(i.converged) for i in infos[1:]]}
-        if st != 0 and (raise_on_fail or st != 6):
-            try:
-                self._check(st)
-            except PorefvError as e:  # (the state before the refused step and what was done until then)
-                e.state, e.info = (s, c), out
-                raise
+        self._step_result(st, raise_on_fail, state=(s, c), info=out)
         return s, c, out
 
     def transport_advance_react(self, c0, n_steps: int, accumulation, bc_values, rate, rate_weight=None, mobility=None,
@@ -1596,25 +1588,9 @@ class Context:
         ``mobility``: k values >= 0 or None (1), 0 = an immobile component.  Returns (c, info) with ``steps_done``,
         ``converged`` and the per-component lists ``iterations`` and ``rel_residual``.  An error raised for a refused
         step carries ``state`` (c before that step) and ``info``."""
-        c = np.array(c0, dtype=np.float64, copy=True, order="C")
-        if c.ndim != 2 or c.shape[1] != self.nc:
-            raise ValueError(f"c0 must have shape (k, {self.nc}), not {c.shape}")
-        k = c.shape[0]
-        if not 1 <= k <= 8:
-            raise ValueError(f"the number of coupled components must lie in 1 .. 8, not {k} (c0 has shape {c.shape})")
-        arrays = []
-        for name, a, n, needed in (("accumulation", accumulation, self.nc, True), ("bc_values", bc_values, self.nf, True),
-                                   ("source", source, self.nc, False)):
-            if a is None:
-                if needed:
-                    raise ValueError(f"{name} is required")
-                arrays.append(None)
-                continue
-            a = _f64(a)
-            if a.shape != (k, n):
-                raise ValueError(f"{name} must have shape ({k}, {n}), not {a.shape}")
-            arrays.append(a)
-        acc, bv, src = arrays
+        c, k = self._component_state(c0, 8, "coupled components")
+        acc, bv, src = self._per_component(k, ("accumulation", accumulation, self.nc, True),
+                                           ("bc_values", bc_values, self.nf, True), ("source", source, self.nc, False))
         K = _f64(rate)
         if K.shape != (k, k):
             raise ValueError(f"rate_matrix must have shape ({k}, {k}), not {K.shape}")
@@ -1630,12 +1606,7 @@ class Context:
         out = {"steps_done": done.value, "converged": all(bool(i.converged) for i in infos),
                "iterations": [i.iterations for i in infos], "rel_residual": [i.rel_residual for i in infos],
                "solve_ms": [i.solve_ms for i in infos]}
-        if st != 0 and (raise_on_fail or st != 6):
-            try:
-                self._check(st)
-            except PorefvError as e:  # (the state before the refused step and what was done until then)
-                e.state, e.info = c, out
-                raise
+        self._step_result(st, raise_on_fail, state=c, info=out)
         return c, out
 
     # ---- what the adjoint methods share ----
@@ -1676,12 +1647,7 @@ class Context:
     def _adjoint_result(self, st, grads, out, raise_on_fail):
         """(grads, out); a failed call raises with ``out`` as the error's ``info``, but for a refused step (6) that the
         caller asked to have returned"""
-        if st != 0 and (raise_on_fail or st != 6):
-            try:
-                self._check(st)
-            except PorefvError as e:
-                e.info = out
-                raise
+        self._step_result(st, raise_on_fail, info=out)
         return grads, out
 
     ADJOINT_GRADIENTS = ("c0", "source", "bc_values", "accumulation", "flux")

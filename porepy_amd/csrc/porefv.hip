@@ -1042,6 +1042,74 @@ static pfv_status step_status(pfv_ctx* h, pfv_status st, const std::string& err,
   return st;
 }
 
+// ---- the set-up and the frame of the flow-ordered step calls: the three forward ones and the four adjoints ---------------
+struct StepSetup {
+  std::unique_ptr<pfv::Timer> tm;  // running from transport_system on
+  bool touched = false;            // the transport system on the handle is the call's
+  double order_ms = 0.0;
+};
+
+// The system of a step call, with the timer started: A = div diag(q) U without accumulation (its diagonal: the outflow
+// of the cell), once per call; own_rows: what the call checks or prepares on A's rows; then the flow order, unless the
+// call may do without one.  (The boundary term that upwind_assemble forms beside A is not used: every call has its own.)
+static void transport_system(pfv_ctx* h, StepSetup& S, const double* d_q, const double* d_bc,
+                             const std::function<void()>& own_rows = nullptr, bool order = true) {
+  S.tm = std::make_unique<pfv::Timer>();
+  S.tm->start(h->stream);
+  upwind_drop_transport(h, true);
+  S.touched = true;
+  pfv::upwind_assemble(*h, d_q, d_bc, nullptr, nullptr, nullptr);
+  values_changed(h, Windows::drop);
+  if (own_rows) own_rows();
+  if (order) transport_order(h, d_q, S.order_ms);
+}
+
+// the set-up of a call: its checks, its uploads, transport_system, its work buffers.  A set-up that fails leaves no system
+// behind (A without accumulation: not a system to be solved with).
+static pfv_status step_setup(pfv_ctx* h, StepSetup& S, int32_t* steps_done, const std::function<void()>& body) {
+  if (steps_done) *steps_done = 0;
+  const pfv_status st = guarded(h, body);
+  if (st != PFV_OK && S.touched) upwind_drop_transport(h, true);
+  return st;
+}
+
+struct StepRun {
+  int32_t completed = 0;  // the steps accepted
+  int64_t core_total = 0, launches = 0;
+  double ms = 0.0;
+  std::vector<pfv_solve_info> info;
+  std::vector<double> hst;  // the norms of the last host read
+};
+
+// The end of a call whose steps ended in (st, err): the timer stopped into run.ms, the call's outputs(st), the transport
+// system dropped; *steps_done.  The error of a failed step is what the call reports, whatever happens here.
+static pfv_status step_finish(pfv_ctx* h, StepSetup& S, StepRun& run, pfv_status st, const std::string& err,
+                              int32_t* steps_done, const std::function<void(pfv_status)>& outputs) {
+  const pfv_status st2 = guarded(h, [&] {
+    run.ms = S.tm->stop(h->stream);
+    S.tm.reset();
+    outputs(st);
+    pfv::be_sync(h->stream);
+    upwind_drop_transport(h, true);
+  });
+  if (steps_done) *steps_done = run.completed;
+  return step_status(h, st, err, st2);
+}
+
+// The frame of a call after its set-up: body(step) for step = 0 .. n_steps - 1 until one fails, then step_finish.
+// body returns PFV_OK, having counted run.completed, or the verdict of a refused step with its text in h->err.
+static pfv_status step_frame(pfv_ctx* h, StepSetup& S, StepRun& run, int n_steps, int32_t* steps_done,
+                             const std::function<pfv_status(int)>& body,
+                             const std::function<void(pfv_status)>& outputs) {
+  pfv_status st = PFV_OK;
+  for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
+    pfv_status verdict = PFV_OK;
+    st = guarded(h, [&] { verdict = body(step); });
+    if (st == PFV_OK) st = verdict;
+  }
+  return step_finish(h, S, run, st, st != PFV_OK ? h->err : std::string(), steps_done, outputs);
+}
+
 // ---- the step loop of pfv_transport_advance and pfv_advdiff_advance --------------------------------------------------
 struct StepLoop {  // what differs between the two
   pfv::Buf<double> pfv::pfv_ctx_impl::*state;  // the state between the steps
@@ -1161,17 +1229,49 @@ pfv_status pfv_transport_advance(pfv_ctx* h, int n_steps, int method, double rto
 // components, in the caller's numbering on pat_T, one host read of 2k numbers.  Everything else -- another
 // preconditioner, a cyclic core, a component whose check fails -- is pfv_upwind_assemble + pfv_transport_advance on
 // that component's arrays, which lie on the device component by component as the caller passed them.
+static std::string zero_diagonal_text(int64_t zd, int k) {  // zd: what upwind_zero_diag_multi found
+  return "zero diagonal entry in row " + std::to_string(zd / k) + ", component " + std::to_string(zd % k) +
+         " of the transport system (a cell without outflow and without an accumulation term): the solvers do not apply";
+}
+
+// Component by component: component_steps(a, steps, done) takes component a `steps` steps from mc_x to mc_z.  Should one
+// stop early, all are taken again from the start to the step it reached, so that c is one state of all components.
+// Returns the first failure with its text in err; completed: the step all have reached, their state in mc_x.
+using MultiComponent = std::function<pfv_status(int, int, int32_t&)>;
+static pfv_status multi_by_component(pfv_ctx* h, int k, int n_steps, const MultiComponent& component_steps,
+                                     int32_t& completed, std::string& err) {
+  pfv_status st = PFV_OK;
+  int target = n_steps;
+  for (;;) {
+    int32_t least = target;
+    for (int a = 0; a < k; ++a) {
+      int32_t done = 0;
+      const pfv_status r = component_steps(a, target, done);
+      if (r == PFV_OK) continue;
+      if (st == PFV_OK) {
+        st = r;
+        err = h->err;
+      }
+      least = std::min(least, done);
+      break;
+    }
+    if (least == target) break;
+    target = least;
+  }
+  completed = target;
+  if (target > 0) h->mc_x.swap(h->mc_z);
+  return st;
+}
+
 pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, const double* bc_values,
                                        const double* accumulation, const double* source, int n_steps, int method,
                                        double rtol, int maxit, double* c, int32_t* steps_done, pfv_solve_info* last) {
-  if (steps_done) *steps_done = 0;
   const int k = n_comp;
-  std::unique_ptr<pfv::Timer> tm;
-  bool fast = false, touched = false;
-  double order_ms = 0.0;
+  StepSetup S;
+  bool fast = false;
   const double* d_q = nullptr;
   size_t nc = 0, nf = 0;
-  pfv_status st = guarded(h, [&] {
+  pfv_status st = step_setup(h, S, steps_done, [&] {
     upwind_supported(h);
     require(h->have_upwind, "pfv_upwind_discretize first");
     require(h->upw_ncomp == 1, "the components share one discretization: pfv_upwind_discretize with num_components = 1");
@@ -1191,81 +1291,73 @@ pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, 
     if (source) vec_in(h, h->mc_src.ensure(k * nc), source, k * nc);
     vec_in(h, h->mc_c.ensure(k * nc), c, k * nc);
     d_q = q ? h->mc_q.p : h->upw_q.p;
-    tm = std::make_unique<pfv::Timer>();
-    tm->start(h->stream);
-    // the values every component shares, without accumulation: once per call
-    upwind_drop_transport(h, true);
-    touched = true;
-    pfv::upwind_assemble(*h, d_q, h->mc_bc.p, nullptr, nullptr, nullptr);
-    values_changed(h, Windows::drop);
-    pfv::multi_interleave(*h, (int64_t)nc, k, h->mc_acc.p, h->mc_acc_i.ensure(k * nc));
-    if (source) pfv::multi_interleave(*h, (int64_t)nc, k, h->mc_src.p, h->mc_src_i.ensure(k * nc));
-    pfv::multi_interleave(*h, (int64_t)nc, k, h->mc_c.p, h->mc_x.ensure(k * nc));
-    h->mc_z.ensure(k * nc);
-    h->mc_r.ensure(k * nc);
-    h->mc_col.ensure(nc);
-    h->mc_nrm.ensure(2 * (size_t)k);
-    const int64_t zd = pfv::upwind_zero_diag_multi(*h, k, h->diag_t.p, h->mc_acc_i.p);
-    if (zd >= 0)
-      throw Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(zd / k) + ", component " +
-                                           std::to_string(zd % k) + " of the transport system (a cell without outflow "
-                                           "and without an accumulation term): the solvers do not apply");
-    pfv::upwind_bref_multi(*h, k, d_q, h->mc_bc.p, h->mc_bref_i.ensure(k * nc));
-    if (h->precond == PFV_PRECOND_SWEEP) {
-      fast = transport_order(h, d_q, order_ms).n_core == 0;
-    }
+    const bool sweep = h->precond == PFV_PRECOND_SWEEP;  // (any other preconditioner: no order is built)
+    transport_system(h, S, d_q, h->mc_bc.p, [&] {
+      pfv::multi_interleave(*h, (int64_t)nc, k, h->mc_acc.p, h->mc_acc_i.ensure(k * nc));
+      if (source) pfv::multi_interleave(*h, (int64_t)nc, k, h->mc_src.p, h->mc_src_i.ensure(k * nc));
+      pfv::multi_interleave(*h, (int64_t)nc, k, h->mc_c.p, h->mc_x.ensure(k * nc));
+      h->mc_z.ensure(k * nc);
+      h->mc_r.ensure(k * nc);
+      h->mc_col.ensure(nc);
+      h->mc_nrm.ensure(2 * (size_t)k);
+      const int64_t zd = pfv::upwind_zero_diag_multi(*h, k, h->diag_t.p, h->mc_acc_i.p);
+      if (zd >= 0) throw Error(PFV_ERR_UNSUPPORTED, zero_diagonal_text(zd, k));
+      pfv::upwind_bref_multi(*h, k, d_q, h->mc_bc.p, h->mc_bref_i.ensure(k * nc));
+    }, sweep);
+    fast = sweep && h->sweep->n_core == 0;
   });
-  if (st != PFV_OK) {
-    if (touched) upwind_drop_transport(h, true);  // (the values of no component's system: not to be solved with)
-    return st;
-  }
+  if (st != PFV_OK) return st;
 
   const bool caller_on_device = h->vectors_on_device;
   const double* src_i = source ? h->mc_src_i.p : nullptr;
   int64_t direct_steps = 0, fallback = 0, iterations = 0, retries = 0;
-  std::vector<pfv_solve_info> info((size_t)k);
-  // `steps` steps of component a alone, from and to `col`, as pfv_upwind_assemble + pfv_transport_advance do them
-  auto component_steps = [&](int a, int steps, int32_t& done) {
-    h->vectors_on_device = true;
-    pfv_status r = pfv_upwind_assemble(h, q ? h->mc_q.p : nullptr, h->mc_bc.p + (size_t)a * nf,
-                                       h->mc_acc.p + (size_t)a * nc, nullptr,
-                                       source ? h->mc_src.p + (size_t)a * nc : nullptr, nullptr);
+  StepRun run;
+  run.info.assign((size_t)k, pfv_solve_info{});
+  // `steps` steps of component a alone, from mc_x to mc_z, as pfv_upwind_assemble + pfv_transport_advance do them
+  const MultiComponent component_steps = [&](int a, int steps, int32_t& done) {
     done = 0;
+    pfv_status r = guarded(h, [&] { pfv::multi_get_column(*h, (int64_t)nc, k, a, h->mc_x.p, h->mc_col.p); });
+    if (r != PFV_OK) return r;
+    h->vectors_on_device = true;
+    r = pfv_upwind_assemble(h, q ? h->mc_q.p : nullptr, h->mc_bc.p + (size_t)a * nf, h->mc_acc.p + (size_t)a * nc,
+                            nullptr, source ? h->mc_src.p + (size_t)a * nc : nullptr, nullptr);
     if (r == PFV_OK) {
-      r = pfv_transport_advance(h, steps, method, rtol, maxit, h->mc_col.p, &done, &info[(size_t)a]);
+      r = pfv_transport_advance(h, steps, method, rtol, maxit, h->mc_col.p, &done, &run.info[(size_t)a]);
       iterations += h->stats.transport_iterations;
       retries += h->stats.transport_gmres_retries;
-      order_ms += h->stats.sweep_order_ms;
+      S.order_ms += h->stats.sweep_order_ms;
     }
     h->vectors_on_device = caller_on_device;
-    return r;
+    if (r != PFV_OK) return r;
+    return guarded(h, [&] { pfv::multi_set_column(*h, (int64_t)nc, k, a, h->mc_col.p, h->mc_z.p); });
   };
-  int32_t completed = 0;
-  std::string err;
+  const auto outputs = [&](pfv_status) {
+    pfv::multi_deinterleave(*h, (int64_t)nc, k, h->mc_x.p, h->mc_c.p);
+    vec_out(h, c, h->mc_c.p, k * nc);
+  };
   if (fast) {
     bool shared_values = true;  // PFV_MAT_TRANSPORT_SYSTEM holds A without accumulation
-    std::vector<double> nrm(2 * (size_t)k);
-    for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
-      st = guarded(h, [&] {
-        if (!shared_values) {
-          upwind_drop_transport(h, true);
-          pfv::upwind_assemble(*h, d_q, h->mc_bc.p, nullptr, nullptr, nullptr);
-          values_changed(h, Windows::drop);
-          shared_values = true;
-        }
-        // (a component's own solve in between works in the renumbered system, and its assembly can drop the order)
-        const pfv::Sweep& sw = transport_order(h, d_q, order_ms, true);
-        const double* val = h->val[PFV_MAT_TRANSPORT_SYSTEM].p;
-        pfv::upwind_step_rhs_multi(*h, k, h->mc_acc_i.p, src_i, h->mc_bref_i.p, h->mc_x.p, h->mc_r.p);
-        pfv::sweep_apply_multi(*h, sw, h->pat_T, val, h->diag_t.p, h->mc_acc_i.p, k, h->mc_r.p, h->mc_z.p);
-        pfv::sweep_residual_norms_multi(*h, h->pat_T, val, h->mc_acc_i.p, k, h->mc_r.p, h->mc_z.p, h->mc_nrm.p);
-        be_d2h(nrm.data(), h->mc_nrm.p, sizeof(double) * 2 * (size_t)k, h->stream);
-      });
-      if (st != PFV_OK) break;
+    st = step_frame(h, S, run, n_steps, steps_done, [&](int) -> pfv_status {
+      if (!shared_values) {
+        upwind_drop_transport(h, true);
+        pfv::upwind_assemble(*h, d_q, h->mc_bc.p, nullptr, nullptr, nullptr);
+        values_changed(h, Windows::drop);
+        shared_values = true;
+      }
+      // (a component's own solve in between works in the renumbered system, and its assembly can drop the order)
+      const pfv::Sweep& sw = transport_order(h, d_q, S.order_ms, true);
+      const double* val = h->val[PFV_MAT_TRANSPORT_SYSTEM].p;
+      run.hst.resize(2 * (size_t)k);
+      pfv::upwind_step_rhs_multi(*h, k, h->mc_acc_i.p, src_i, h->mc_bref_i.p, h->mc_x.p, h->mc_r.p);
+      pfv::sweep_apply_multi(*h, sw, h->pat_T, val, h->diag_t.p, h->mc_acc_i.p, k, h->mc_r.p, h->mc_z.p);
+      pfv::sweep_residual_norms_multi(*h, h->pat_T, val, h->mc_acc_i.p, k, h->mc_r.p, h->mc_z.p, h->mc_nrm.p);
+      be_d2h(run.hst.data(), h->mc_nrm.p, sizeof(double) * 2 * (size_t)k, h->stream);
+      // The acceptance is this call's own: a right-hand side that is zero counts as converged whatever the sweep left,
+      // and a component whose check fails is not refused but solved alone, from the state at the start of the step.
       int failed = 0;
-      for (int a = 0; a < k && st == PFV_OK; ++a) {
-        const double bb = nrm[(size_t)a], rr = nrm[(size_t)k + a];
-        pfv_solve_info& ia = info[(size_t)a];
+      for (int a = 0; a < k; ++a) {
+        const double bb = run.hst[(size_t)a], rr = run.hst[(size_t)k + a];
+        pfv_solve_info& ia = run.info[(size_t)a];
         ia = pfv_solve_info{};
         ia.iterations = 1;
         if (!(bb > 0.0)) {  // r_a = 0 -> the sweep has left 0
@@ -1278,75 +1370,39 @@ pfv_status pfv_transport_advance_multi(pfv_ctx* h, const double* q, int n_comp, 
           ++iterations;
           continue;
         }
-        // this component alone, from the state at the start of the step
         ++failed;
         ++fallback;
         shared_values = false;
-        st = guarded(h, [&] { pfv::multi_get_column(*h, (int64_t)nc, k, a, h->mc_x.p, h->mc_col.p); });
         int32_t done = 0;
-        if (st == PFV_OK) st = component_steps(a, 1, done);
-        if (st == PFV_OK) st = guarded(h, [&] { pfv::multi_set_column(*h, (int64_t)nc, k, a, h->mc_col.p, h->mc_z.p); });
+        const pfv_status r = component_steps(a, 1, done);
+        if (r != PFV_OK) return r;
       }
-      if (st != PFV_OK) break;
       h->mc_x.swap(h->mc_z);
-      ++completed;
+      ++run.completed;
       if (!failed) ++direct_steps;
-    }
-    if (st != PFV_OK) err = h->err;
+      return PFV_OK;
+    }, outputs);
   } else {
-    // component by component; should one stop early, all are taken again from the start to the step it reached, so
-    // that c is one state of all components
-    int target = n_steps;
-    for (;;) {
-      int32_t least = target;
-      pfv_status first = PFV_OK;
-      for (int a = 0; a < k; ++a) {
-        pfv_status r = guarded(h, [&] { pfv::multi_get_column(*h, (int64_t)nc, k, a, h->mc_x.p, h->mc_col.p); });
-        int32_t done = 0;
-        if (r == PFV_OK) r = component_steps(a, target, done);
-        if (r == PFV_OK) r = guarded(h, [&] { pfv::multi_set_column(*h, (int64_t)nc, k, a, h->mc_col.p, h->mc_z.p); });
-        if (r != PFV_OK) {
-          if (first == PFV_OK && st == PFV_OK) {
-            first = r;
-            err = h->err;
-          }
-          least = std::min(least, done);
-          break;
-        }
-      }
-      if (first != PFV_OK) st = first;
-      if (least == target) break;
-      target = least;
-    }
-    completed = target;
-    fallback = (int64_t)k * target;
-    if (target > 0) h->mc_x.swap(h->mc_z);
+    std::string err;
+    st = multi_by_component(h, k, n_steps, component_steps, run.completed, err);
+    fallback = (int64_t)k * run.completed;
+    st = step_finish(h, S, run, st, err, steps_done, outputs);
   }
-  double ms = 0.0;
-  const pfv_status st2 = guarded(h, [&] {
-    ms = tm->stop(h->stream);
-    tm.reset();
-    pfv::multi_deinterleave(*h, (int64_t)nc, k, h->mc_x.p, h->mc_c.p);
-    vec_out(h, c, h->mc_c.p, k * nc);
-    pfv::be_sync(h->stream);
-    upwind_drop_transport(h, true);
-  });
-  if (steps_done) *steps_done = completed;
   if (last) {
     for (int a = 0; a < k; ++a) {
-      last[a] = info[(size_t)a];
-      if (fast && last[a].solve_ms == 0.0 && completed > 0) last[a].solve_ms = ms / completed;
+      last[a] = run.info[(size_t)a];
+      if (fast && last[a].solve_ms == 0.0 && run.completed > 0) last[a].solve_ms = run.ms / run.completed;
     }
   }
-  h->stats.transport_advance_ms = ms;
+  h->stats.transport_advance_ms = run.ms;
   h->stats.transport_iterations = iterations;
   h->stats.transport_gmres_retries = retries;
   h->stats.transport_multi_components = k;
   h->stats.transport_multi_direct_steps = direct_steps;
   h->stats.transport_multi_fallback_components = fallback;
   h->stats.sweep_direct_steps = direct_steps;
-  if (h->precond == PFV_PRECOND_SWEEP) sweep_step_stats(h, -1, order_ms);
-  return step_status(h, st, err, st2);
+  if (h->precond == PFV_PRECOND_SWEEP) sweep_step_stats(h, -1, S.order_ms);
+  return st;
 }
 
 // ---- what the input-check kernels found, as the error of the call ---------------------------------------------------
@@ -1392,14 +1448,11 @@ static pfv_status advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const
                              const double* sink, int k, const double* c_bc_values, const double* sorption,
                              const double* c_source, int n_steps, double rtol, int maxit, double* s, double* cc,
                              int32_t* steps_done, pfv_solve_info* last) {
-  if (steps_done) *steps_done = 0;
-  std::unique_ptr<pfv::Timer> tm;
-  bool touched = false;
-  double order_ms = 0.0;
+  StepSetup S;
   const double* d_q = nullptr;
   size_t nc = 0, nf = 0;
   pfv::FluxFn F;
-  pfv_status st = guarded(h, [&] {
+  pfv_status st = step_setup(h, S, steps_done, [&] {
     upwind_supported(h);
     if (h->subface_bc) throw Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
     require(h->have_upwind, "pfv_upwind_discretize first");
@@ -1435,24 +1488,19 @@ static pfv_status advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const
     if (fluxfn_kind == PFV_FLUXFN_TABLE)
       be_h2d(h->nl_table.ensure((size_t)n_params), fluxfn_params, sizeof(double) * (size_t)n_params, h->stream);
     F = pfv::fluxfn_make(fluxfn_kind, fluxfn_params, n_params, h->nl_table.p);
-    tm = std::make_unique<pfv::Timer>();
-    tm->start(h->stream);
-    // A = div diag(q) U without accumulation (its diagonal: the outflow of the cell), once per call
-    upwind_drop_transport(h, true);
-    touched = true;
-    pfv::upwind_assemble(*h, d_q, h->nl_bc.p, nullptr, nullptr, nullptr);
-    values_changed(h, Windows::drop);
-    pfv::upwind_bref_nl(*h, F, d_q, h->nl_bc.p, h->nl_bref.ensure(nc));
-    for (pfv::Buf<double>* b : {&h->nl_s2, &h->nl_phi, &h->nl_phi2, &h->nl_rhs, &h->nl_t}) b->ensure(nc);
-    h->nl_out.ensure(8 + 4 * (size_t)k);
-    if (k > 0) {  // the vectors of the step, cell-major interleaved
+    transport_system(h, S, d_q, h->nl_bc.p, [&] {
+      pfv::upwind_bref_nl(*h, F, d_q, h->nl_bc.p, h->nl_bref.ensure(nc));
+      for (pfv::Buf<double>* b : {&h->nl_s2, &h->nl_phi, &h->nl_phi2, &h->nl_rhs, &h->nl_t}) b->ensure(nc);
+      h->nl_out.ensure(8 + 4 * (size_t)k);
+      if (k == 0) return;
+      // the vectors of the step, cell-major interleaved
       if (sorption) pfv::multi_interleave(*h, (int64_t)nc, k, h->nlc_ads_in.p, h->nlc_ads.ensure(k * nc));
       if (c_source) pfv::multi_interleave(*h, (int64_t)nc, k, h->nlc_src_in.p, h->nlc_src.ensure(k * nc));
       pfv::multi_interleave(*h, (int64_t)nc, k, h->nlc_c_in.p, h->nlc_x.ensure(k * nc));
       pfv::upwind_bref_nlc(*h, F, k, d_q, h->nl_bc.p, h->nlc_cbc.p, h->nlc_bref.ensure(k * nc));
       for (pfv::Buf<double>* b : {&h->nlc_z, &h->nlc_psi, &h->nlc_psi2, &h->nlc_rhs, &h->nlc_t}) b->ensure(k * nc);
-    }
-    const pfv::Sweep& sw = transport_order(h, d_q, order_ms);
+    });
+    const pfv::Sweep& sw = *h->sweep;
     if (sw.n_core > 0) {
       h->nl_cb.ensure((size_t)sw.n_core);
       h->nl_ct.ensure((size_t)sw.n_core);
@@ -1462,177 +1510,161 @@ static pfv_status advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const
       }
     }
   });
-  if (st != PFV_OK) {
-    if (touched) upwind_drop_transport(h, true);  // (A without accumulation: not a system to be solved with)
-    return st;
-  }
+  if (st != PFV_OK) return st;
 
   const double* d_src = source ? h->nl_src.p : nullptr;
   const double* d_sink = sink ? h->nl_sink.p : nullptr;
-  int32_t completed = 0;
-  int64_t core_total = 0, launches = 0;
+  StepRun run;  // (the solve of the step is this call's own: the saturation's info beside the components' in cinfo)
   pfv_solve_info info{};
   std::vector<pfv_solve_info> cinfo((size_t)k);
-  std::vector<double> hst(5 + 4 * (size_t)k);
-  std::string err;
-  for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
-    pfv_status verdict = PFV_OK;
-    st = guarded(h, [&] {
-      pfv::pfv_ctx_impl& c = *h;
-      const pfv::Sweep& sw = *c.sweep;
-      const double* val = c.val[PFV_MAT_TRANSPORT_SYSTEM].p;
-      const double* diag = c.diag_t.p;
-      const double *acc = c.nl_acc.p, *rhs = c.nl_rhs.p, *s_old = c.nl_s.p;
-      double *s_new = c.nl_s2.p, *phi = c.nl_phi.p, *out = c.nl_out.p;
-      int32_t* status = reinterpret_cast<int32_t*>(out + 4);  // [0] the levels outside the core, [1] the core
-      const bool has_core = sw.n_core > 0;
-      const int core = has_core ? sw.core_level : sw.nlev;
-      pfv::NlComp C;  // the levels outside the core; Cc: the core level, with psi of the previous iterate
+  std::vector<double>& hst = run.hst;
+  hst.resize(5 + 4 * (size_t)k);
+  st = step_frame(h, S, run, n_steps, steps_done, [&](int step) -> pfv_status {
+    pfv::pfv_ctx_impl& c = *h;
+    const pfv::Sweep& sw = *c.sweep;
+    const double* val = c.val[PFV_MAT_TRANSPORT_SYSTEM].p;
+    const double* diag = c.diag_t.p;
+    const double *acc = c.nl_acc.p, *rhs = c.nl_rhs.p, *s_old = c.nl_s.p;
+    double *s_new = c.nl_s2.p, *phi = c.nl_phi.p, *out = c.nl_out.p;
+    int32_t* status = reinterpret_cast<int32_t*>(out + 4);  // [0] the levels outside the core, [1] the core
+    const bool has_core = sw.n_core > 0;
+    const int core = has_core ? sw.core_level : sw.nlev;
+    pfv::NlComp C;  // the levels outside the core; Cc: the core level, with psi of the previous iterate
+    if (k > 0) {
+      C.k = k;
+      C.ads = sorption ? c.nlc_ads.p : nullptr;
+      C.rhs = c.nlc_rhs.p;
+      C.c_start = c.nlc_x.p;
+      C.c = c.nlc_z.p;
+      C.psi = c.nlc_psi.p;
+    }
+    pfv::NlComp Cc = C;
+    Cc.psi_prev = k > 0 ? c.nlc_psi2.p : nullptr;
+    double* cout = out + 5;
+    pfv::upwind_step_rhs_multi(c, 1, acc, d_src, c.nl_bref.p, s_old, c.nl_rhs.p);
+    if (k > 0)
+      pfv::upwind_step_rhs_nlc(c, k, acc, s_old, C.ads, c_source ? c.nlc_src.p : nullptr, c.nlc_bref.p, c.nlc_x.p,
+                               c.nlc_rhs.p);
+    pfv::be_memset(out, 0, 4 * sizeof(double), c.stream);
+    pfv::be_memset(status, 0x7f, 2 * sizeof(int32_t), c.stream);
+    if (k > 0) pfv::be_memset(cout, 0, 4 * (size_t)k * sizeof(double), c.stream);
+    run.launches = pfv::sweep_apply_nl(c, sw, 0, core, c.pat_T, val, diag, d_sink, acc, rhs, F, s_old, s_new, phi, status,
+                                       C);
+    auto flagged = [&](bool core_too, int32_t& cell) {
+      int32_t w[2];
+      std::memcpy(w, hst.data() + 4, sizeof(w));
+      cell = core_too ? std::min(w[0], w[1]) : w[0];
+      return cell != 0x7f7f7f7f;
+    };
+    int core_it = 0;
+    if (has_core) {
+      pfv::sweep_residual_norms(c, c.nc, rhs, rhs, out);  // out[0] = (rhs, rhs)
+      pfv::sweep_nl_core_init(c, sw, F, s_old, s_new, phi);
       if (k > 0) {
-        C.k = k;
-        C.ads = sorption ? c.nlc_ads.p : nullptr;
-        C.rhs = c.nlc_rhs.p;
-        C.c_start = c.nlc_x.p;
-        C.c = c.nlc_z.p;
-        C.psi = c.nlc_psi.p;
+        pfv::sweep_norms_interleaved(c, c.nc, k, C.rhs, C.rhs, cout);  // cout[a] = (rhs_a, rhs_a)
+        pfv::sweep_nlc_core_init(c, sw, phi, C);
       }
-      pfv::NlComp Cc = C;
-      Cc.psi_prev = k > 0 ? c.nlc_psi2.p : nullptr;
-      double* cout = out + 5;
-      pfv::upwind_step_rhs_multi(c, 1, acc, d_src, c.nl_bref.p, s_old, c.nl_rhs.p);
-      if (k > 0)
-        pfv::upwind_step_rhs_nlc(c, k, acc, s_old, C.ads, c_source ? c.nlc_src.p : nullptr, c.nlc_bref.p, c.nlc_x.p,
-                                 c.nlc_rhs.p);
-      pfv::be_memset(out, 0, 4 * sizeof(double), c.stream);
-      pfv::be_memset(status, 0x7f, 2 * sizeof(int32_t), c.stream);
-      if (k > 0) pfv::be_memset(cout, 0, 4 * (size_t)k * sizeof(double), c.stream);
-      launches = pfv::sweep_apply_nl(c, sw, 0, core, c.pat_T, val, diag, d_sink, acc, rhs, F, s_old, s_new, phi, status, C);
-      auto flagged = [&](bool core_too, int32_t& cell) {
-        int32_t w[2];
-        std::memcpy(w, hst.data() + 4, sizeof(w));
-        cell = core_too ? std::min(w[0], w[1]) : w[0];
-        return cell != 0x7f7f7f7f;
-      };
-      int core_it = 0;
-      if (has_core) {
-        pfv::sweep_residual_norms(c, c.nc, rhs, rhs, out);  // out[0] = (rhs, rhs)
-        pfv::sweep_nl_core_init(c, sw, F, s_old, s_new, phi);
+      const CoreRun cr = core_iterate(h, maxit, out, hst, [&] {
+        // (once the saturation has passed its own test it stays, with its status word: the components alone go on)
+        if (!Cc.frozen) pfv::sweep_nl_core_keep(c, sw, phi, c.nl_phi2.p, status + 1);
+        if (k > 0) pfv::sweep_core_copy(c, sw, k, C.psi, c.nlc_psi2.p);
+        pfv::sweep_levels_nl(c, sw, core, core + 1, c.pat_T, val, diag, d_sink, acc, rhs, F, s_new, c.nl_phi2.p, s_new,
+                             phi, status + 1, Cc);
+      }, [&] {
+        if (!Cc.frozen) {
+          pfv::sweep_nl_core_image(c, sw, c.pat_T, val, d_sink, acc, rhs, s_new, phi, c.nl_cb.p, c.nl_ct.p);
+          pfv::sweep_residual_norms(c, sw.n_core, c.nl_cb.p, c.nl_ct.p, out + 2);  // out[3] = (F_core, F_core)
+        }
         if (k > 0) {
-          pfv::sweep_norms_interleaved(c, c.nc, k, C.rhs, C.rhs, cout);  // cout[a] = (rhs_a, rhs_a)
-          pfv::sweep_nlc_core_init(c, sw, phi, C);
+          pfv::sweep_nlc_core_image(c, sw, c.pat_T, val, d_sink, acc, s_new, C, c.nlc_cb.p, c.nlc_ct.p);
+          pfv::sweep_norms_interleaved(c, sw.n_core, k, c.nlc_cb.p, c.nlc_ct.p, cout + 2 * k);
         }
-        const CoreRun run = core_iterate(h, maxit, out, hst, [&] {
-          // (once the saturation has passed its own test it stays, with its status word: the components alone go on)
-          if (!Cc.frozen) pfv::sweep_nl_core_keep(c, sw, phi, c.nl_phi2.p, status + 1);
-          if (k > 0) pfv::sweep_core_copy(c, sw, k, C.psi, c.nlc_psi2.p);
-          pfv::sweep_levels_nl(c, sw, core, core + 1, c.pat_T, val, diag, d_sink, acc, rhs, F, s_new, c.nl_phi2.p, s_new,
-                               phi, status + 1, Cc);
-        }, [&] {
-          if (!Cc.frozen) {
-            pfv::sweep_nl_core_image(c, sw, c.pat_T, val, d_sink, acc, rhs, s_new, phi, c.nl_cb.p, c.nl_ct.p);
-            pfv::sweep_residual_norms(c, sw.n_core, c.nl_cb.p, c.nl_ct.p, out + 2);  // out[3] = (F_core, F_core)
-          }
-          if (k > 0) {
-            pfv::sweep_nlc_core_image(c, sw, c.pat_T, val, d_sink, acc, s_new, C, c.nlc_cb.p, c.nlc_ct.p);
-            pfv::sweep_norms_interleaved(c, sw.n_core, k, c.nlc_cb.p, c.nlc_ct.p, cout + 2 * k);
-          }
-        }, [&] {
-          bool settled = hst[3] <= 0.25 * rtol * rtol * hst[0];
-          Cc.frozen = settled;
-          for (int a = 0; a < k; ++a)  // (F_core_a, F_core_a) against (rhs_a, rhs_a)
-            settled = settled && hst[5 + 3 * (size_t)k + a] <= 0.25 * rtol * rtol * hst[5 + (size_t)a];
-          return settled;
-        });
-        core_it = run.iterations;
-        core_total += core_it;
-        launches += 2;
-        if (!run.settled) {  // (what the backward levels would compute from this core is not judged)
-          info = pfv_solve_info{};
-          info.iterations = core_it;
-          info.rel_residual = hst[0] > 0.0 ? std::sqrt(hst[3] / hst[0]) : 0.0;
-          for (int a = 0; a < k; ++a) {
-            const double bb = hst[5 + (size_t)a], rr = hst[5 + 3 * (size_t)k + a];
-            cinfo[(size_t)a] = pfv_solve_info{};
-            cinfo[(size_t)a].iterations = core_it;
-            cinfo[(size_t)a].rel_residual = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
-          }
-          int32_t cell;  // (the core's word belongs to an iterate that has not settled: the other levels' alone)
-          if (flagged(false, cell))
-            throw Error(PFV_ERR_ARGUMENT, "step " + std::to_string(step) + " leaves [0, 1]: no root in cell " +
-                                              std::to_string(cell));
-          verdict = PFV_ERR_NOT_CONVERGED;
-          c.err = "step " + std::to_string(step) + ": the cyclic core of " + std::to_string(sw.n_core) +
-                  " cells did not settle in " + std::to_string(core_it) + " iterations";
-          return;
+      }, [&] {
+        bool settled = hst[3] <= 0.25 * rtol * rtol * hst[0];
+        Cc.frozen = settled;
+        for (int a = 0; a < k; ++a)  // (F_core_a, F_core_a) against (rhs_a, rhs_a)
+          settled = settled && hst[5 + 3 * (size_t)k + a] <= 0.25 * rtol * rtol * hst[5 + (size_t)a];
+        return settled;
+      });
+      core_it = cr.iterations;
+      run.core_total += core_it;
+      run.launches += 2;
+      if (!cr.settled) {  // (what the backward levels would compute from this core is not judged)
+        info = pfv_solve_info{};
+        info.iterations = core_it;
+        info.rel_residual = hst[0] > 0.0 ? std::sqrt(hst[3] / hst[0]) : 0.0;
+        for (int a = 0; a < k; ++a) {
+          const double bb = hst[5 + (size_t)a], rr = hst[5 + 3 * (size_t)k + a];
+          cinfo[(size_t)a] = pfv_solve_info{};
+          cinfo[(size_t)a].iterations = core_it;
+          cinfo[(size_t)a].rel_residual = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
         }
-        launches += pfv::sweep_apply_nl(c, sw, core + 1, sw.nlev, c.pat_T, val, diag, d_sink, acc, rhs, F, s_old, s_new, phi,
-                                        status, C);
+        int32_t cell;  // (the core's word belongs to an iterate that has not settled: the other levels' alone)
+        if (flagged(false, cell))
+          throw Error(PFV_ERR_ARGUMENT, "step " + std::to_string(step) + " leaves [0, 1]: no root in cell " +
+                                            std::to_string(cell));
+        c.err = "step " + std::to_string(step) + ": the cyclic core of " + std::to_string(sw.n_core) +
+                " cells did not settle in " + std::to_string(core_it) + " iterations";
+        return PFV_ERR_NOT_CONVERGED;
       }
-      if (k > 0) pfv::sweep_nlc_image(c, c.pat_T, val, d_sink, acc, s_new, phi, c.nl_t.p, C, c.nlc_t.p);
-      else pfv::sweep_nl_image(c, c.pat_T, val, d_sink, acc, s_new, phi, c.nl_t.p);
-      pfv::sweep_residual_norms(c, c.nc, rhs, c.nl_t.p, out);
-      if (k > 0) pfv::sweep_norms_interleaved(c, c.nc, k, C.rhs, c.nlc_t.p, cout);
-      be_d2h(hst.data(), out, sizeof(double) * hst.size(), c.stream);
-      info = pfv_solve_info{};
-      info.iterations = has_core ? core_it : 1;
-      info.rel_residual = hst[0] > 0.0 ? std::sqrt(hst[1] / hst[0]) : 0.0;
-      int32_t cell;
-      if (flagged(true, cell))
-        throw Error(PFV_ERR_ARGUMENT, "step " + std::to_string(step) + " leaves [0, 1]: no root in cell " +
-                                          std::to_string(cell));
-      info.converged = hst[1] <= rtol * rtol * hst[0] ? 1 : 0;
-      int bad = info.converged ? -1 : k;  // the first component whose check fails; k: the saturation
-      for (int a = k - 1; a >= 0; --a) {
-        const double bb = hst[5 + (size_t)a], rr = hst[5 + (size_t)k + a];
-        pfv_solve_info& ia = cinfo[(size_t)a];
-        ia = pfv_solve_info{};
-        ia.iterations = info.iterations;
-        ia.rel_residual = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
-        ia.converged = rr <= rtol * rtol * bb ? 1 : 0;  // (0 <= 0: a component that is absent everywhere is valid)
-        if (!ia.converged && info.converged) bad = a;
-      }
-      if (bad >= 0) {
-        verdict = PFV_ERR_NOT_CONVERGED;
-        const double rel = bad == k ? info.rel_residual : cinfo[(size_t)bad].rel_residual;
-        c.err = "step " + std::to_string(step) + ": relative residual " + std::to_string(rel) +
-                (bad == k ? std::string() : " of component " + std::to_string(bad)) +
-                " after the sweep (a flux that contradicts the discretization's?)";
-        return;
-      }
-      c.nl_s.swap(c.nl_s2);
-      if (k > 0) c.nlc_x.swap(c.nlc_z);
-      ++completed;
-    });
-    if (st == PFV_OK) st = verdict;
-  }
-  if (st != PFV_OK) err = h->err;
-  double ms = 0.0;
-  const pfv_status st2 = guarded(h, [&] {
-    ms = tm->stop(h->stream);
-    tm.reset();
+      run.launches += pfv::sweep_apply_nl(c, sw, core + 1, sw.nlev, c.pat_T, val, diag, d_sink, acc, rhs, F, s_old, s_new,
+                                          phi, status, C);
+    }
+    if (k > 0) pfv::sweep_nlc_image(c, c.pat_T, val, d_sink, acc, s_new, phi, c.nl_t.p, C, c.nlc_t.p);
+    else pfv::sweep_nl_image(c, c.pat_T, val, d_sink, acc, s_new, phi, c.nl_t.p);
+    pfv::sweep_residual_norms(c, c.nc, rhs, c.nl_t.p, out);
+    if (k > 0) pfv::sweep_norms_interleaved(c, c.nc, k, C.rhs, c.nlc_t.p, cout);
+    be_d2h(hst.data(), out, sizeof(double) * hst.size(), c.stream);
+    info = pfv_solve_info{};
+    info.iterations = has_core ? core_it : 1;
+    info.rel_residual = hst[0] > 0.0 ? std::sqrt(hst[1] / hst[0]) : 0.0;
+    int32_t cell;
+    if (flagged(true, cell))
+      throw Error(PFV_ERR_ARGUMENT, "step " + std::to_string(step) + " leaves [0, 1]: no root in cell " +
+                                        std::to_string(cell));
+    info.converged = hst[1] <= rtol * rtol * hst[0] ? 1 : 0;
+    int bad = info.converged ? -1 : k;  // the first component whose check fails; k: the saturation
+    for (int a = k - 1; a >= 0; --a) {
+      const double bb = hst[5 + (size_t)a], rr = hst[5 + (size_t)k + a];
+      pfv_solve_info& ia = cinfo[(size_t)a];
+      ia = pfv_solve_info{};
+      ia.iterations = info.iterations;
+      ia.rel_residual = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
+      ia.converged = rr <= rtol * rtol * bb ? 1 : 0;  // (0 <= 0: a component that is absent everywhere is valid)
+      if (!ia.converged && info.converged) bad = a;
+    }
+    if (bad >= 0) {
+      const double rel = bad == k ? info.rel_residual : cinfo[(size_t)bad].rel_residual;
+      c.err = "step " + std::to_string(step) + ": relative residual " + std::to_string(rel) +
+              (bad == k ? std::string() : " of component " + std::to_string(bad)) +
+              " after the sweep (a flux that contradicts the discretization's?)";
+      return PFV_ERR_NOT_CONVERGED;
+    }
+    c.nl_s.swap(c.nl_s2);
+    if (k > 0) c.nlc_x.swap(c.nlc_z);
+    ++run.completed;
+    return PFV_OK;
+  }, [&](pfv_status) {
     vec_out(h, s, h->nl_s.p, nc);
     if (k > 0) {
       pfv::multi_deinterleave(*h, (int64_t)nc, k, h->nlc_x.p, h->nlc_c_in.p);
       vec_out(h, cc, h->nlc_c_in.p, k * nc);
     }
-    pfv::be_sync(h->stream);
-    upwind_drop_transport(h, true);
   });
-  if (steps_done) *steps_done = completed;
   if (last) {
     *last = info;
-    if (completed > 0) last->solve_ms = ms / completed;
+    if (run.completed > 0) last->solve_ms = run.ms / run.completed;
     for (int a = 0; a < k; ++a) {
       last[1 + a] = cinfo[(size_t)a];
       last[1 + a].solve_ms = last->solve_ms;
     }
   }
-  h->stats.transport_nl_ms = ms;
-  h->stats.transport_nl_steps = completed;
-  h->stats.transport_nl_core_iterations = core_total;
+  h->stats.transport_nl_ms = run.ms;
+  h->stats.transport_nl_steps = run.completed;
+  h->stats.transport_nl_core_iterations = run.core_total;
   h->stats.transport_nl_components = k;
-  sweep_step_stats(h, n_steps > 0 ? launches : -1, order_ms);
-  return step_status(h, st, err, st2);
+  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, S.order_ms);
+  return st;
 }
 
 pfv_status pfv_transport_advance_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
@@ -1656,22 +1688,121 @@ pfv_status pfv_transport_advance_nl_multi(pfv_ctx* h, const double* q, int fluxf
                     sorption, c_source, n_steps, rtol, maxit, s, c, steps_done, last);
 }
 
+// ---- the solve of one step by a sweep: pfv_transport_advance_react and the four adjoints ---------------------------------
+// The levels before the core, the core level iterated by Jacobi on its rows (a host read every kNlCoreCheck-th
+// iteration), the levels after it, the residual norms of all rows and ONE host read; then the acceptance.  A forward
+// step walks the levels from first to last, an adjoint step from last to first.  The calls differ in their rows and
+// their norms:
+struct SweepWay {
+  bool ascending;                       // the levels from first to last; otherwise from last to first
+  const char *step_word, *sweep_word;  // what the messages call the step and the sweep
+};
+constexpr SweepWay kForwardSweep{true, "step ", "sweep"}, kAdjointSweep{false, "adjoint step ", "transposed sweep"};
+struct SweepSolve {
+  int pairs;        // of norms in out: (scale_a, scale_a) for all a, then (residual_a, residual_a)
+  int saturation;   // sweep_accept's
+  const double* out;
+  SweepWay way;     // kForwardSweep or kAdjointSweep: every call names its own
+  std::function<int64_t(int, int)> levels;  // the levels [from, to) in the call's direction; returns its launches
+  std::function<void()> core_start;         // the unknowns of the core before the first iteration
+  std::function<void()> core_step;          // one iteration on the core: the copy, then its rows
+  std::function<void(bool)> norms;          // into out: of the core's rows only, or of all
+  // A word behind the norms that the kernels set to an index (kNoOffender: not set), and what it means for step n: a
+  // verdict, or an Error thrown.  flag_ends_core: the word says that the input admits no solution -- it ends the core's
+  // iteration and is judged before anything else; otherwise it is judged on the finished sweep, before the acceptance.
+  std::function<pfv_status(int, int32_t)> flagged;
+  bool flag_ends_core = false;
+};
+
+// info from hst: (scale_a, scale_a), (residual_a, residual_a)
+static void component_info(std::vector<pfv_solve_info>& info, const std::vector<double>& hst, int k, int it) {
+  for (int a = 0; a < k; ++a) {
+    const double bb = hst[(size_t)a], rr = hst[(size_t)k + a];
+    info[(size_t)a] = pfv_solve_info{};
+    info[(size_t)a].iterations = it;
+    info[(size_t)a].rel_residual = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
+  }
+}
+
+// ||residual_a|| <= tol ||scale_a|| for every component (0 <= 0 counts)
+static bool norms_pass(const std::vector<double>& hst, int k, double tol) {
+  bool pass = true;
+  for (int a = 0; a < k; ++a) pass = pass && hst[(size_t)k + a] <= tol * tol * hst[(size_t)a];
+  return pass;
+}
+
+// the acceptance of step n from the pairs of norms in hst (after component_info): the first component whose check fails
+// is named; the saturation's, where there is one, before any component's
+static pfv_status sweep_accept(pfv_ctx* h, const SweepSolve& V, std::vector<pfv_solve_info>& info,
+                               const std::vector<double>& hst, double rtol, int n) {
+  int bad = -1;
+  for (int a = V.pairs - 1; a >= 0; --a) {
+    info[(size_t)a].converged = hst[(size_t)V.pairs + a] <= rtol * rtol * hst[(size_t)a] ? 1 : 0;  // (0 <= 0 counts)
+    if (!info[(size_t)a].converged) bad = a;
+  }
+  if (V.saturation >= 0 && !info[(size_t)V.saturation].converged) bad = V.saturation;
+  if (bad < 0) return PFV_OK;
+  h->err = V.way.step_word + std::to_string(n) + ": relative residual " + std::to_string(info[(size_t)bad].rel_residual) +
+           (bad == V.saturation ? std::string() : " of component " + std::to_string(bad)) + " after the " +
+           V.way.sweep_word + " (a flux that contradicts the discretization's?)";
+  return PFV_ERR_NOT_CONVERGED;
+}
+
+// -> PFV_OK or the verdict of a refused step n (its text in h->err); it fills run.info and run.hst and counts
+// run.launches (of this step) and run.core_total.  The core has settled at half the tolerance of the acceptance.
+static pfv_status sweep_step_solve(pfv_ctx* h, const SweepSolve& V, StepRun& run, double rtol, int maxit, int n) {
+  pfv::pfv_ctx_impl& cx = *h;
+  const pfv::Sweep& sw = *cx.sweep;
+  const int K = V.pairs;
+  std::vector<double>& hst = run.hst;
+  hst.resize(2 * (size_t)K + (V.flagged ? 1 : 0));
+  auto flag = [&] {
+    int32_t w = kNoOffender;
+    if (V.flagged) std::memcpy(&w, hst.data() + 2 * K, sizeof(w));
+    return w;
+  };
+  const bool has_core = sw.n_core > 0;
+  const int core = has_core ? sw.core_level : V.way.ascending ? sw.nlev : -1;
+  run.launches = V.way.ascending ? V.levels(0, core) : V.levels(core + 1, sw.nlev);
+  int core_it = 0;
+  if (has_core) {
+    V.core_start();
+    const CoreRun cr = core_iterate(h, maxit, V.out, hst, V.core_step, [&] { V.norms(true); }, [&] {
+      return (V.flag_ends_core && flag() != kNoOffender) || norms_pass(hst, K, 0.5 * rtol);
+    });
+    core_it = cr.iterations;
+    run.core_total += core_it;
+    run.launches += 2;
+    if (V.flag_ends_core && flag() != kNoOffender) return V.flagged(n, flag());
+    if (!cr.settled) {  // (what the levels after the core would compute from it is not judged)
+      component_info(run.info, hst, K, core_it);
+      cx.err = V.way.step_word + std::to_string(n) + ": the cyclic core of " + std::to_string(sw.n_core) +
+               " cells did not settle in " + std::to_string(core_it) + " iterations";
+      return PFV_ERR_NOT_CONVERGED;
+    }
+    run.launches += V.way.ascending ? V.levels(core + 1, sw.nlev) : V.levels(0, core);
+  }
+  V.norms(false);
+  be_d2h(hst.data(), V.out, sizeof(double) * hst.size(), cx.stream);
+  if (V.flag_ends_core && flag() != kNoOffender) return V.flagged(n, flag());
+  component_info(run.info, hst, K, has_core ? core_it : 1);
+  if (flag() != kNoOffender) return V.flagged(n, flag());
+  return sweep_accept(h, V, run.info, hst, rtol, n);
+}
+
 // ---- k coupled components: one k x k solve per cell in flow order (sweep.inc: sweep_row_react) -------------------------
-// Per step: rhs, the forward levels, the core level iterated by block Jacobi (a host read every kNlCoreCheck-th
-// iteration), the backward levels, then g and F = rhs - image over all rows and ONE host read of their 2k norms and the
-// status word.  The state of the step's start stays in its own buffer until the step is accepted.
+// In step_frame with the solve of sweep_step_solve, ascending: per step rhs, the forward levels, the core level iterated
+// by block Jacobi, the backward levels, then g and F = rhs - image over all rows and ONE host read of their 2k norms and
+// the status word.  The state of the step's start stays in its own buffer until the step is accepted.
 pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const double* bc_values,
                                        const double* accumulation, const double* source, const double* mobility,
                                        const double* rate, const double* rate_weight, int n_steps, double rtol,
                                        int maxit, double* c, int32_t* steps_done, pfv_solve_info* last) {
-  if (steps_done) *steps_done = 0;
-  std::unique_ptr<pfv::Timer> tm;
-  bool touched = false;
-  double order_ms = 0.0;
+  StepSetup S;
   const double* d_q = nullptr;
   size_t nc = 0, nf = 0;
   pfv::ReactPar par;
-  pfv_status st = guarded(h, [&] {
+  pfv_status st = step_setup(h, S, steps_done, [&] {
     upwind_supported(h);
     if (h->subface_bc) throw Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
     require(h->have_upwind, "pfv_upwind_discretize first");
@@ -1699,136 +1830,69 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
     pfv::sweep_react_check_inputs(*h, d_q, k, h->rc_bc.p, h->rc_acc_in.p, rate_weight ? h->rc_rho.p : nullptr,
                                   h->rc_c_in.p, h->rc_par.p, off);
     react_inputs_refused(off, k);
-    tm = std::make_unique<pfv::Timer>();
-    tm->start(h->stream);
-    // A = div diag(q) U without accumulation (its diagonal: the outflow of the cell), once per call.  (The boundary
-    // term that upwind_assemble forms beside it is not used: b_ref of every component comes from upwind_bref_react.)
-    upwind_drop_transport(h, true);
-    touched = true;
-    pfv::upwind_assemble(*h, d_q, h->rc_bc.p, nullptr, nullptr, nullptr);
-    values_changed(h, Windows::drop);
-    pfv::multi_interleave(*h, (int64_t)nc, k, h->rc_acc_in.p, h->rc_acc.ensure(k * nc));
-    if (source) pfv::multi_interleave(*h, (int64_t)nc, k, h->rc_src_in.p, h->rc_src.ensure(k * nc));
-    pfv::multi_interleave(*h, (int64_t)nc, k, h->rc_c_in.p, h->rc_x.ensure(k * nc));
-    pfv::upwind_bref_react(*h, k, d_q, h->rc_bc.p, h->rc_par.p, h->rc_bref.ensure(k * nc));
-    for (pfv::Buf<double>* b : {&h->rc_z, &h->rc_prev, &h->rc_rhs, &h->rc_g, &h->rc_F}) b->ensure(k * nc);
-    h->rc_out.ensure(2 * (size_t)k + 1);
-    transport_order(h, d_q, order_ms);
-  });
-  if (st != PFV_OK) {
-    if (touched) upwind_drop_transport(h, true);  // (A without accumulation: not a system to be solved with)
-    return st;
-  }
-
-  int32_t completed = 0;
-  int64_t core_total = 0, launches = 0;
-  std::vector<pfv_solve_info> info((size_t)k);
-  std::vector<double> hst(2 * (size_t)k + 1);
-  std::string err;
-  for (int step = 0; step < n_steps && st == PFV_OK; ++step) {
-    pfv_status verdict = PFV_OK;
-    st = guarded(h, [&] {
-      pfv::pfv_ctx_impl& cx = *h;
-      const pfv::Sweep& sw = *cx.sweep;
-      const double* val = cx.val[PFV_MAT_TRANSPORT_SYSTEM].p;
-      const double* rho = rate_weight ? cx.rc_rho.p : nullptr;
-      double* out = cx.rc_out.p;
-      int32_t* status = reinterpret_cast<int32_t*>(out + 2 * k);
-      const bool has_core = sw.n_core > 0;
-      const int core = has_core ? sw.core_level : sw.nlev;
-      pfv::ReactRow A{cx.pat_T.indptr, cx.pat_T.indices, sw.lev(false), val, cx.diag_t.p, cx.rc_acc.p, rho,
-                      cx.rc_rhs.p, nullptr, cx.rc_z.p, status};
-      pfv::ReactRow Ac = A;  // the core level, with the state of the previous iterate
-      Ac.c_prev = cx.rc_prev.p;
-      auto component_info = [&](int it) {  // from hst: (g_a, g_a), (F_a, F_a)
-        for (int a = 0; a < k; ++a) {
-          const double gg = hst[(size_t)a], ff = hst[(size_t)k + a];
-          info[(size_t)a] = pfv_solve_info{};
-          info[(size_t)a].iterations = it;
-          info[(size_t)a].rel_residual = gg > 0.0 ? std::sqrt(ff / gg) : 0.0;
-        }
-      };
-      pfv::upwind_step_rhs_multi(cx, k, cx.rc_acc.p, source ? cx.rc_src.p : nullptr, cx.rc_bref.p, cx.rc_x.p, cx.rc_rhs.p);
-      pfv::be_memset(status, 0x7f, sizeof(double), cx.stream);
-      launches = pfv::sweep_apply_react(cx, sw, 0, core, k, A, par);
-      int core_it = 0;
-      if (has_core) {
-        pfv::sweep_core_copy(cx, sw, k, cx.rc_x.p, cx.rc_z.p);  // the core rows start from the state of the step's start
-        const CoreRun run = core_iterate(h, maxit, out, hst, [&] {
-          pfv::sweep_core_copy(cx, sw, k, cx.rc_z.p, cx.rc_prev.p);
-          pfv::sweep_levels_react(cx, sw, core, core + 1, k, Ac, par);
-        }, [&] {
-          pfv::sweep_react_image(cx, cx.pat_T, val, k, cx.rc_acc.p, rho, cx.rc_rhs.p, cx.rc_par.p, cx.rc_z.p, A.lev, core,
-                                 cx.rc_g.p, cx.rc_F.p);
-          pfv::sweep_react_norms(cx, cx.nc, k, cx.rc_g.p, cx.rc_F.p, out);
-        }, [&] {
-          bool settled = true;
-          for (int a = 0; a < k; ++a) settled = settled && hst[(size_t)k + a] <= 0.25 * rtol * rtol * hst[(size_t)a];
-          return settled;
-        });
-        core_it = run.iterations;
-        core_total += core_it;
-        launches += 2;
-        if (!run.settled) {  // (what the backward levels would compute from this core is not judged)
-          component_info(core_it);
-          verdict = PFV_ERR_NOT_CONVERGED;
-          cx.err = "step " + std::to_string(step) + ": the cyclic core of " + std::to_string(sw.n_core) +
-                   " cells did not settle in " + std::to_string(core_it) + " iterations";
-          return;
-        }
-        launches += pfv::sweep_apply_react(cx, sw, core + 1, sw.nlev, k, A, par);
-      }
-      pfv::sweep_react_image(cx, cx.pat_T, val, k, cx.rc_acc.p, rho, cx.rc_rhs.p, cx.rc_par.p, cx.rc_z.p, A.lev, -1,
-                             cx.rc_g.p, cx.rc_F.p);
-      pfv::sweep_react_norms(cx, cx.nc, k, cx.rc_g.p, cx.rc_F.p, out);
-      be_d2h(hst.data(), out, sizeof(double) * hst.size(), cx.stream);
-      component_info(has_core ? core_it : 1);
-      int32_t cell;
-      std::memcpy(&cell, hst.data() + 2 * k, sizeof(cell));
-      if (cell != 0x7f7f7f7f) {
-        verdict = PFV_ERR_NOT_CONVERGED;
-        cx.err = "step " + std::to_string(step) + ": the block of cell " + std::to_string(cell) +
-                 " has a pivot that is not positive and finite";
-        return;
-      }
-      int bad = -1;  // the first component whose check fails
-      for (int a = k - 1; a >= 0; --a) {
-        info[(size_t)a].converged = hst[(size_t)k + a] <= rtol * rtol * hst[(size_t)a] ? 1 : 0;  // (0 <= 0 counts)
-        if (!info[(size_t)a].converged) bad = a;
-      }
-      if (bad >= 0) {
-        verdict = PFV_ERR_NOT_CONVERGED;
-        cx.err = "step " + std::to_string(step) + ": relative residual " + std::to_string(info[(size_t)bad].rel_residual) +
-                 " of component " + std::to_string(bad) + " after the sweep (a flux that contradicts the discretization's?)";
-        return;
-      }
-      cx.rc_x.swap(cx.rc_z);
-      ++completed;
+    transport_system(h, S, d_q, h->rc_bc.p, [&] {
+      pfv::multi_interleave(*h, (int64_t)nc, k, h->rc_acc_in.p, h->rc_acc.ensure(k * nc));
+      if (source) pfv::multi_interleave(*h, (int64_t)nc, k, h->rc_src_in.p, h->rc_src.ensure(k * nc));
+      pfv::multi_interleave(*h, (int64_t)nc, k, h->rc_c_in.p, h->rc_x.ensure(k * nc));
+      pfv::upwind_bref_react(*h, k, d_q, h->rc_bc.p, h->rc_par.p, h->rc_bref.ensure(k * nc));
+      for (pfv::Buf<double>* b : {&h->rc_z, &h->rc_prev, &h->rc_rhs, &h->rc_g, &h->rc_F}) b->ensure(k * nc);
+      h->rc_out.ensure(2 * (size_t)k + 1);
     });
-    if (st == PFV_OK) st = verdict;
-  }
-  if (st != PFV_OK) err = h->err;
-  double ms = 0.0;
-  const pfv_status st2 = guarded(h, [&] {
-    ms = tm->stop(h->stream);
-    tm.reset();
+  });
+  if (st != PFV_OK) return st;
+
+  StepRun run;
+  run.info.assign((size_t)k, pfv_solve_info{});
+  st = step_frame(h, S, run, n_steps, steps_done, [&](int step) -> pfv_status {
+    pfv::pfv_ctx_impl& cx = *h;
+    const pfv::Sweep& sw = *cx.sweep;
+    const double* val = cx.val[PFV_MAT_TRANSPORT_SYSTEM].p;
+    const double* rho = rate_weight ? cx.rc_rho.p : nullptr;
+    double* out = cx.rc_out.p;
+    int32_t* status = reinterpret_cast<int32_t*>(out + 2 * k);
+    pfv::ReactRow A{cx.pat_T.indptr, cx.pat_T.indices, sw.lev(false), val, cx.diag_t.p, cx.rc_acc.p, rho,
+                    cx.rc_rhs.p, nullptr, cx.rc_z.p, status};
+    pfv::ReactRow Ac = A;  // the core level, with the state of the previous iterate
+    Ac.c_prev = cx.rc_prev.p;
+    pfv::upwind_step_rhs_multi(cx, k, cx.rc_acc.p, source ? cx.rc_src.p : nullptr, cx.rc_bref.p, cx.rc_x.p, cx.rc_rhs.p);
+    pfv::be_memset(status, 0x7f, sizeof(double), cx.stream);
+    SweepSolve V{k, -1, out, kForwardSweep};
+    V.levels = [&](int from, int to) { return pfv::sweep_apply_react(cx, sw, from, to, k, A, par); };
+    V.core_start = [&] { pfv::sweep_core_copy(cx, sw, k, cx.rc_x.p, cx.rc_z.p); };  // the state of the step's start
+    V.core_step = [&] {
+      pfv::sweep_core_copy(cx, sw, k, cx.rc_z.p, cx.rc_prev.p);
+      pfv::sweep_levels_react(cx, sw, sw.core_level, sw.core_level + 1, k, Ac, par);
+    };
+    V.norms = [&](bool core_only) {  // from hst: (g_a, g_a), (F_a, F_a)
+      pfv::sweep_react_image(cx, cx.pat_T, val, k, cx.rc_acc.p, rho, cx.rc_rhs.p, cx.rc_par.p, cx.rc_z.p, A.lev,
+                             core_only ? sw.core_level : -1, cx.rc_g.p, cx.rc_F.p);
+      pfv::sweep_react_norms(cx, cx.nc, k, cx.rc_g.p, cx.rc_F.p, out);
+    };
+    V.flagged = [&](int n, int32_t cell) {
+      cx.err = "step " + std::to_string(n) + ": the block of cell " + std::to_string(cell) +
+               " has a pivot that is not positive and finite";
+      return PFV_ERR_NOT_CONVERGED;
+    };
+    const pfv_status verdict = sweep_step_solve(h, V, run, rtol, maxit, step);
+    if (verdict != PFV_OK) return verdict;
+    cx.rc_x.swap(cx.rc_z);
+    ++run.completed;
+    return PFV_OK;
+  }, [&](pfv_status) {
     pfv::multi_deinterleave(*h, (int64_t)nc, k, h->rc_x.p, h->rc_c_in.p);
     vec_out(h, c, h->rc_c_in.p, k * nc);
-    pfv::be_sync(h->stream);
-    upwind_drop_transport(h, true);
   });
-  if (steps_done) *steps_done = completed;
   if (last)
     for (int a = 0; a < k; ++a) {
-      last[a] = info[(size_t)a];
-      if (completed > 0) last[a].solve_ms = ms / completed;
+      last[a] = run.info[(size_t)a];
+      if (run.completed > 0) last[a].solve_ms = run.ms / run.completed;
     }
-  h->stats.transport_react_ms = ms;
-  h->stats.transport_react_steps = completed;
-  h->stats.transport_react_core_iterations = core_total;
+  h->stats.transport_react_ms = run.ms;
+  h->stats.transport_react_steps = run.completed;
+  h->stats.transport_react_core_iterations = run.core_total;
   h->stats.transport_react_components = k;
-  sweep_step_stats(h, n_steps > 0 ? launches : -1, order_ms);
-  return step_status(h, st, err, st2);
+  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, S.order_ms);
+  return st;
 }
 
 // ---- the observation of an adjoint call, shared by pfv_transport_adjoint_multi and pfv_transport_adjoint_react --------
@@ -1885,39 +1949,20 @@ static void adjoint_check_counts(int n_steps, double rtol, int maxit, bool loads
   require(loads || n_steps == 0, loads_text);
 }
 
-struct AdjointSetup {
-  std::unique_ptr<pfv::Timer> tm;  // running from adjoint_system on
-  bool touched = false;            // the transport system on the handle is the call's
-  double order_ms = 0.0;
-};
-
-// The system of an adjoint call, with the timer started: A = div diag(q) U without accumulation, once per call (own_rows:
-// what the call checks or prepares on A's rows), its transposed values beside it, the observation's slots, the flow order.
-static void adjoint_system(pfv_ctx* h, AdjointSetup& S, const double* d_q, const double* d_bc, int64_t n_obs,
+// The system of an adjoint call: transport_system, where what the call does on A's rows (own_rows) is followed by A's
+// transposed values and the observation's slots; the flow order comes last.
+static void adjoint_system(pfv_ctx* h, StepSetup& S, const double* d_q, const double* d_bc, int64_t n_obs,
                            const int32_t* obs_cells, const std::function<void()>& own_rows = nullptr) {
-  S.tm = std::make_unique<pfv::Timer>();
-  S.tm->start(h->stream);
-  upwind_drop_transport(h, true);
-  S.touched = true;
-  pfv::upwind_assemble(*h, d_q, d_bc, nullptr, nullptr, nullptr);
-  values_changed(h, Windows::drop);
-  if (own_rows) own_rows();
-  const size_t nnz = (size_t)std::max<int64_t>(h->pat_T.nnz, 1);
-  if (!h->have_tpos_T) {
-    pfv::sweep_transpose_positions(*h, h->pat_T, h->tpos_T.ensure(nnz));
-    h->have_tpos_T = true;
-  }
-  pfv::sweep_transpose_values(*h, h->pat_T.nnz, h->tpos_T.p, h->val[PFV_MAT_TRANSPORT_SYSTEM].p, h->valT_T.ensure(nnz));
-  adjoint_take_slots(h, n_obs, obs_cells);
-  transport_order(h, d_q, S.order_ms);
-}
-
-// the set-up of a call: its checks, its uploads, adjoint_system, its work buffers.  A set-up that fails leaves no system
-// behind (A without accumulation: not a system to be solved with).
-static pfv_status adjoint_setup(pfv_ctx* h, AdjointSetup& S, const std::function<void()>& body) {
-  const pfv_status st = guarded(h, body);
-  if (st != PFV_OK && S.touched) upwind_drop_transport(h, true);
-  return st;
+  transport_system(h, S, d_q, d_bc, [&] {
+    if (own_rows) own_rows();
+    const size_t nnz = (size_t)std::max<int64_t>(h->pat_T.nnz, 1);
+    if (!h->have_tpos_T) {
+      pfv::sweep_transpose_positions(*h, h->pat_T, h->tpos_T.ensure(nnz));
+      h->have_tpos_T = true;
+    }
+    pfv::sweep_transpose_values(*h, h->pat_T.nnz, h->tpos_T.p, h->val[PFV_MAT_TRANSPORT_SYSTEM].p, h->valT_T.ensure(nnz));
+    adjoint_take_slots(h, n_obs, obs_cells);
+  });
 }
 
 // the two slabs of the states [k][nc] a step reads, and where a slab in host memory lands
@@ -1928,7 +1973,7 @@ static void adjoint_slab_buffers(pfv_ctx* h, int k) {
   if (!h->vectors_on_device) h->aj_state_in.ensure(n);
 }
 
-// ---- the step frame of the adjoint calls (after their set-up, with the timer running) -----------------------------------
+// ---- the steps of the adjoint calls, in step_frame (after their set-up, with the timer running) --------------------------
 // Per step n = N .. 1: one slab of states (stage), the right-hand side fused with what the multipliers of step n + 1 add
 // to the cell gradients (rhs), the call's own solve -- sweep, core, acceptance --, its gradients of the accepted step,
 // the swap of the multipliers and the slabs.  After the last step the right-hand-side pass runs once more without loads
@@ -1961,52 +2006,10 @@ struct AdjointCall {  // what the calls share, by the callers' names
   std::function<void(int, bool)> rhs;  // the right-hand side(s) of step n, or of the last pass; whether step n + 1 ran
   std::function<void()> swap;          // the accepted step becomes step n + 1
 };
-struct AdjointRun {
-  int32_t completed = 0;
-  int64_t core_total = 0, launches = 0;
-  double ms = 0.0;
-  std::vector<pfv_solve_info> info;
-  std::vector<double> hst;  // the norms of the last host read
-};
-
-// info from hst: (scale_a, scale_a), (residual_a, residual_a)
-static void adjoint_component_info(std::vector<pfv_solve_info>& info, const std::vector<double>& hst, int k, int it) {
-  for (int a = 0; a < k; ++a) {
-    const double bb = hst[(size_t)a], rr = hst[(size_t)k + a];
-    info[(size_t)a] = pfv_solve_info{};
-    info[(size_t)a].iterations = it;
-    info[(size_t)a].rel_residual = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
-  }
-}
-
-// ||residual_a|| <= tol ||scale_a|| for every component (0 <= 0 counts)
-static bool adjoint_norms_pass(const std::vector<double>& hst, int k, double tol) {
-  bool pass = true;
-  for (int a = 0; a < k; ++a) pass = pass && hst[(size_t)k + a] <= tol * tol * hst[(size_t)a];
-  return pass;
-}
-
-// the acceptance of step n from the k pairs of norms in hst (after adjoint_component_info): the first component whose
-// check fails is named; the saturation's, where there is one, before any component's
-static pfv_status adjoint_accept(pfv_ctx* h, std::vector<pfv_solve_info>& info, const std::vector<double>& hst, int k,
-                                 double rtol, int n, int saturation) {
-  int bad = -1;
-  for (int a = k - 1; a >= 0; --a) {
-    info[(size_t)a].converged = hst[(size_t)k + a] <= rtol * rtol * hst[(size_t)a] ? 1 : 0;  // (0 <= 0 counts)
-    if (!info[(size_t)a].converged) bad = a;
-  }
-  if (saturation >= 0 && !info[(size_t)saturation].converged) bad = saturation;
-  if (bad < 0) return PFV_OK;
-  h->err = "adjoint step " + std::to_string(n) + ": relative residual " + std::to_string(info[(size_t)bad].rel_residual) +
-           (bad == saturation ? std::string() : " of component " + std::to_string(bad)) +
-           " after the transposed sweep (a flux that contradicts the discretization's?)";
-  return PFV_ERR_NOT_CONVERGED;
-}
-
 // solve(n, z) -> PFV_OK or the verdict of a refused step (its text in h->err): the multipliers of step n, lambda^n into
-// z, from the right-hand side(s); it fills run.info and counts run.launches / run.core_total (adjoint_sweep_solve).
+// z, from the right-hand side(s); it fills run.info and counts run.launches / run.core_total (sweep_step_solve).
 // step_grads(z): what the accepted step adds to the gradients the right-hand-side pass does not sum.
-static pfv_status adjoint_steps(pfv_ctx* h, AdjointSetup& S, const AdjointCall& A, AdjointRun& run,
+static pfv_status adjoint_steps(pfv_ctx* h, StepSetup& S, const AdjointCall& A, StepRun& run,
                                 const std::function<pfv_status(int, double*)>& solve,
                                 const std::function<void(double*)>& step_grads) {
   pfv::pfv_ctx_impl& cx = *h;
@@ -2038,51 +2041,42 @@ static pfv_status adjoint_steps(pfv_ctx* h, AdjointSetup& S, const AdjointCall& 
     cx.aj_sA.swap(cx.aj_sB);
   };
   run.info.assign((size_t)k + (A.saturation >= 0 ? 1 : 0), pfv_solve_info{});
-  pfv_status st = guarded(h, [&] {
-    for (const AdjointGrad& g : A.grads)
-      if (g.to && g.summed) pfv::be_memset(g.buf->ensure(g.n), 0, sizeof(double) * g.n, cx.stream);
-  });
-  std::string err;
   bool have_next = false;  // the multipliers of step n + 1 are there
-  for (int n = A.n_steps; n >= 1 && st == PFV_OK; --n) {
-    pfv_status verdict = PFV_OK;
-    st = guarded(h, [&] {
-      stage(n);
-      rhs(n, have_next);
-      double* z = cx.aj_lam2.p;
-      verdict = solve(n, z);
-      if (verdict != PFV_OK) return;
-      step_grads(z);
-      swap();
-      have_next = true;
-      ++run.completed;
-    });
-    if (st == PFV_OK) st = verdict;
-  }
-  if (st != PFV_OK) err = h->err;
-  const pfv_status st2 = guarded(h, [&] {
-    if (st == PFV_OK) {
+  // (the frame counts upwards: its step is N - n, and the last pass, n = 0, is one more step that completes none)
+  const pfv_status st = step_frame(h, S, run, A.n_steps + 1, A.steps_done, [&](int step) -> pfv_status {
+    const int n = A.n_steps - step;
+    if (step == 0)
+      for (const AdjointGrad& g : A.grads)
+        if (g.to && g.summed) pfv::be_memset(g.buf->ensure(g.n), 0, sizeof(double) * g.n, cx.stream);
+    if (n == 0) {
       if (have_next) stage(0);
       rhs(0, have_next);
+      return PFV_OK;
     }
-    run.ms = S.tm->stop(cx.stream);
-    S.tm.reset();
-    if (st == PFV_OK)
-      for (const AdjointGrad& g : A.grads) {
-        if (!g.to) continue;
-        if (g.layout == GradLayout::host) {
-          be_d2h(g.to, g.buf->p, sizeof(double) * g.n, cx.stream);
-        } else if (g.layout == GradLayout::by_cell) {
-          pfv::multi_deinterleave(cx, (int64_t)nc, k, g.buf->p, cx.mc_c.p);
-          vec_out(h, g.to, cx.mc_c.p, g.n);
-        } else {
-          vec_out(h, g.to, g.buf->p, g.n);
-        }
+    stage(n);
+    rhs(n, have_next);
+    double* z = cx.aj_lam2.p;
+    const pfv_status verdict = solve(n, z);
+    if (verdict != PFV_OK) return verdict;
+    step_grads(z);
+    swap();
+    have_next = true;
+    ++run.completed;
+    return PFV_OK;
+  }, [&](pfv_status ended) {  // a call that failed or was refused hands no gradient out
+    if (ended != PFV_OK) return;
+    for (const AdjointGrad& g : A.grads) {
+      if (!g.to) continue;
+      if (g.layout == GradLayout::host) {
+        be_d2h(g.to, g.buf->p, sizeof(double) * g.n, cx.stream);
+      } else if (g.layout == GradLayout::by_cell) {
+        pfv::multi_deinterleave(cx, (int64_t)nc, k, g.buf->p, cx.mc_c.p);
+        vec_out(h, g.to, cx.mc_c.p, g.n);
+      } else {
+        vec_out(h, g.to, g.buf->p, g.n);
       }
-    pfv::be_sync(cx.stream);
-    upwind_drop_transport(h, true);
+    }
   });
-  if (A.steps_done) *A.steps_done = run.completed;
   if (A.last) {
     int to = 0;
     if (A.saturation >= 0) A.last[to++] = run.info[(size_t)A.saturation];
@@ -2091,70 +2085,11 @@ static pfv_status adjoint_steps(pfv_ctx* h, AdjointSetup& S, const AdjointCall& 
     if (run.completed > 0)
       for (int a = 0; a < to; ++a) A.last[a].solve_ms = run.ms / run.completed;
   }
-  return step_status(h, st, err, st2);
-}
-
-// ---- the solve of one adjoint step --------------------------------------------------------------------------------------
-// The backward-peel levels from last to first, the core level iterated by Jacobi on its transposed rows (a host read
-// every kNlCoreCheck-th iteration), the forward-peel levels, the residual norms of all rows and ONE host read; then the
-// acceptance.  The calls differ in their rows and their norms:
-struct AdjointSolve {
-  int pairs;        // of norms in out: (scale_a, scale_a) for all a, then (residual_a, residual_a)
-  int saturation;   // adjoint_accept's
-  const double* out;
-  std::function<int64_t(int, int)> levels;  // the levels [from, to), from last to first; returns its launches
-  std::function<void()> core_zero;          // the unknowns of the core to zero
-  std::function<void()> core_step;          // one iteration on the core: the copy, then its rows
-  std::function<void(bool)> norms;          // into out: of the core's rows only, or of all
-  // A word behind the norms that the kernels set to an index (kNoOffender: not set), and what it means for step n: a
-  // verdict, or an Error thrown.  flag_ends_core: the word says that the input admits no solution -- it ends the core's
-  // iteration and is judged before anything else; otherwise it is judged on the finished sweep, before the acceptance.
-  std::function<pfv_status(int, int32_t)> flagged;
-  bool flag_ends_core = false;
-};
-static pfv_status adjoint_sweep_solve(pfv_ctx* h, const AdjointSolve& V, AdjointRun& run, double rtol, int maxit,
-                                      int n) {
-  pfv::pfv_ctx_impl& cx = *h;
-  const pfv::Sweep& sw = *cx.sweep;
-  const int K = V.pairs;
-  std::vector<double>& hst = run.hst;
-  hst.resize(2 * (size_t)K + (V.flagged ? 1 : 0));
-  auto flag = [&] {
-    int32_t w = kNoOffender;
-    if (V.flagged) std::memcpy(&w, hst.data() + 2 * K, sizeof(w));
-    return w;
-  };
-  const bool has_core = sw.n_core > 0;
-  const int core = has_core ? sw.core_level : -1;
-  run.launches = V.levels(core + 1, sw.nlev);
-  int core_it = 0;
-  if (has_core) {
-    V.core_zero();
-    const CoreRun cr = core_iterate(h, maxit, V.out, hst, V.core_step, [&] { V.norms(true); }, [&] {
-      return (V.flag_ends_core && flag() != kNoOffender) || adjoint_norms_pass(hst, K, 0.5 * rtol);
-    });
-    core_it = cr.iterations;
-    run.core_total += core_it;
-    run.launches += 2;
-    if (V.flag_ends_core && flag() != kNoOffender) return V.flagged(n, flag());
-    if (!cr.settled) {  // (what the forward-peel levels would compute from this core is not judged)
-      adjoint_component_info(run.info, hst, K, core_it);
-      cx.err = "adjoint step " + std::to_string(n) + ": the cyclic core of " + std::to_string(sw.n_core) +
-               " cells did not settle in " + std::to_string(core_it) + " iterations";
-      return PFV_ERR_NOT_CONVERGED;
-    }
-    run.launches += V.levels(0, core);
-  }
-  V.norms(false);
-  be_d2h(hst.data(), V.out, sizeof(double) * hst.size(), cx.stream);
-  if (V.flag_ends_core && flag() != kNoOffender) return V.flagged(n, flag());
-  adjoint_component_info(run.info, hst, K, has_core ? core_it : 1);
-  if (flag() != kNoOffender) return V.flagged(n, flag());
-  return adjoint_accept(h, run.info, hst, K, rtol, n, V.saturation);
+  return st;
 }
 
 // ---- the adjoint of the k-component step: one transposed sweep in reverse flow order per step (sweep.inc) -------------
-// In the frame of adjoint_steps with the solve of adjoint_sweep_solve on the rows of sweep_row_multi_t; after an accepted
+// In the frame of adjoint_steps with the solve of sweep_step_solve on the rows of sweep_row_multi_t; after an accepted
 // step the two face kernels (grad_bc_values, grad_flux).
 pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, const double* bc_values,
                                        const double* accumulation, int n_steps, int64_t n_obs, const int32_t* obs_cells,
@@ -2162,12 +2097,11 @@ pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, 
                                        double* grad_c0, double* grad_source, double* grad_bc_values,
                                        double* grad_accumulation, double* grad_flux, int32_t* steps_done,
                                        pfv_solve_info* last) {
-  if (steps_done) *steps_done = 0;
   const int k = n_comp;
-  AdjointSetup S;
+  StepSetup S;
   const double* d_q = nullptr;
   size_t nc = 0, nf = 0;
-  pfv_status st = adjoint_setup(h, S, [&] {
+  pfv_status st = step_setup(h, S, steps_done, [&] {
     upwind_supported(h);
     require(h->have_upwind, "pfv_upwind_discretize first");
     require(h->upw_ncomp == 1, "the components share one discretization: pfv_upwind_discretize with num_components = 1");
@@ -2188,10 +2122,7 @@ pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, 
     adjoint_system(h, S, d_q, h->mc_bc.p, n_obs, obs_cells, [&] {
       pfv::multi_interleave(*h, (int64_t)nc, k, h->mc_acc.p, h->mc_acc_i.ensure(k * nc));
       const int64_t zd = pfv::upwind_zero_diag_multi(*h, k, h->diag_t.p, h->mc_acc_i.p);
-      if (zd >= 0)
-        throw Error(PFV_ERR_UNSUPPORTED, "zero diagonal entry in row " + std::to_string(zd / k) + ", component " +
-                                             std::to_string(zd % k) + " of the transport system (a cell without outflow "
-                                             "and without an accumulation term): the solvers do not apply");
+      if (zd >= 0) throw Error(PFV_ERR_UNSUPPORTED, zero_diagonal_text(zd, k));
     });
     for (pfv::Buf<double>* b : {&h->aj_lam, &h->aj_lam2, &h->aj_prev, &h->aj_r, &h->mc_c}) b->ensure(k * nc);
     if (states) adjoint_slab_buffers(h, k);
@@ -2199,7 +2130,7 @@ pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, 
   });
   if (st != PFV_OK) return st;
 
-  AdjointRun run;
+  StepRun run;
   AdjointCall call{k, n_steps, n_obs, obs_cells, states, h->mc_acc_i.p, grad_source, grad_accumulation, steps_done,
                    last};
   call.grads = {{grad_c0, &h->aj_r, k * nc, GradLayout::by_cell, false},
@@ -2211,11 +2142,11 @@ pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, 
     pfv::pfv_ctx_impl& cx = *h;
     const pfv::Sweep& sw = *cx.sweep;
     const double *valT = cx.valT_T.p, *acc = cx.mc_acc_i.p;
-    AdjointSolve V{k, -1, cx.mc_nrm.p};
+    SweepSolve V{k, -1, cx.mc_nrm.p, kAdjointSweep};
     V.levels = [&](int from, int to) {
       return pfv::sweep_apply_multi_t(cx, sw, from, to, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, z);
     };
-    V.core_zero = [&] { pfv::sweep_core_zero(cx, sw, k, z); };
+    V.core_start = [&] { pfv::sweep_core_zero(cx, sw, k, z); };
     V.core_step = [&] {
       pfv::sweep_core_copy(cx, sw, k, z, cx.aj_prev.p);
       pfv::sweep_core_multi_t(cx, sw, cx.pat_T, valT, cx.diag_t.p, acc, k, cx.aj_r.p, cx.aj_prev.p, z);
@@ -2224,7 +2155,7 @@ pfv_status pfv_transport_adjoint_multi(pfv_ctx* h, const double* q, int n_comp, 
       if (core_only) pfv::sweep_core_norms_multi_t(cx, sw, cx.pat_T, valT, acc, k, cx.aj_r.p, z, cx.mc_nrm.p);
       else pfv::sweep_residual_norms_multi(cx, cx.pat_T, valT, acc, k, cx.aj_r.p, z, cx.mc_nrm.p);
     };
-    return adjoint_sweep_solve(h, V, run, rtol, maxit, n);
+    return sweep_step_solve(h, V, run, rtol, maxit, n);
   }, [&](double* z) {
     if (grad_bc_values) pfv::adjoint_grad_bc(*h, k, d_q, z, h->aj_gbc.p);
     if (grad_flux) pfv::adjoint_grad_flux(*h, k, h->mc_bc.p, z, h->aj_sB.p, h->aj_gq.p);
@@ -2249,12 +2180,11 @@ pfv_status pfv_transport_adjoint_react(pfv_ctx* h, const double* q, int k, const
                                        double* grad_c0, double* grad_source, double* grad_bc_values,
                                        double* grad_accumulation, double* grad_flux, double* grad_rate,
                                        double* grad_rate_weight, int32_t* steps_done, pfv_solve_info* last) {
-  if (steps_done) *steps_done = 0;
-  AdjointSetup S;
+  StepSetup S;
   const double* d_q = nullptr;
   size_t nc = 0, nf = 0;
   pfv::ReactPar par, parT;
-  pfv_status st = adjoint_setup(h, S, [&] {
+  pfv_status st = step_setup(h, S, steps_done, [&] {
     upwind_supported(h);
     if (h->subface_bc) throw Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
     require(h->have_upwind, "pfv_upwind_discretize first");
@@ -2298,7 +2228,7 @@ pfv_status pfv_transport_adjoint_react(pfv_ctx* h, const double* q, int k, const
   });
   if (st != PFV_OK) return st;
 
-  AdjointRun run;
+  StepRun run;
   const double* rho = rate_weight ? h->rc_rho.p : nullptr;
   AdjointCall call{k, n_steps, n_obs, obs_cells, states, h->rc_acc.p, grad_source, grad_accumulation, steps_done, last};
   call.grads = {{grad_c0, &h->aj_r, k * nc, GradLayout::by_cell, false},
@@ -2319,11 +2249,11 @@ pfv_status pfv_transport_adjoint_react(pfv_ctx* h, const double* q, int k, const
     pfv::ReactRow Ac = A;  // the core level, with the previous iterate
     Ac.c_prev = cx.rc_prev.p;
     pfv::be_memset(status, 0x7f, sizeof(double), cx.stream);
-    AdjointSolve V{k, -1, out};
+    SweepSolve V{k, -1, out, kAdjointSweep};
     V.levels = [&](int from, int to) {
       return pfv::sweep_apply_react(cx, sw, from, to, k, A, parT, pfv::Descending{});
     };
-    V.core_zero = [&] { pfv::sweep_core_zero(cx, sw, k, z); };
+    V.core_start = [&] { pfv::sweep_core_zero(cx, sw, k, z); };
     V.core_step = [&] {
       pfv::sweep_core_copy(cx, sw, k, z, cx.rc_prev.p);
       pfv::sweep_levels_react(cx, sw, sw.core_level, sw.core_level + 1, k, Ac, parT, pfv::Descending{});
@@ -2338,7 +2268,7 @@ pfv_status pfv_transport_adjoint_react(pfv_ctx* h, const double* q, int k, const
                " has a pivot that is not positive and finite";
       return PFV_ERR_NOT_CONVERGED;
     };
-    return adjoint_sweep_solve(h, V, run, rtol, maxit, n);
+    return sweep_step_solve(h, V, run, rtol, maxit, n);
   }, [&](double* z) {
     pfv::pfv_ctx_impl& cx = *h;
     if (grad_bc_values) pfv::adjoint_grad_bc(cx, k, d_q, z, cx.aj_gbc.p, cx.rc_par.p);
@@ -2370,7 +2300,7 @@ static void adjoint_nl_supported(pfv_ctx* h, int fluxfn_kind, const double* flux
 
 // ---- the adjoint of the saturation step: one transposed sweep on the step's slopes per step (sweep.inc) ---------------
 // In the frame of adjoint_steps with k = 1.  The solve of step n: d = f'(s^n) and phi = f(s^n) from the slab the frame
-// has staged (one streaming pass), then adjoint_sweep_solve on the rows of J^T = diag(acc) + diag(d) M^T
+// has staged (one streaming pass), then sweep_step_solve on the rows of J^T = diag(acc) + diag(d) M^T
 // (sweep_row_nl_t).  After an accepted step the two face kernels, the sink's cell kernel and the six Corey sums, which
 // are added in step order.
 pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
@@ -2380,12 +2310,11 @@ pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind
                                     double* grad_source, double* grad_bc_values, double* grad_accumulation,
                                     double* grad_sink, double* grad_flux, double* grad_fluxfn, int32_t* steps_done,
                                     pfv_solve_info* last) {
-  if (steps_done) *steps_done = 0;
-  AdjointSetup S;
+  StepSetup S;
   const double* d_q = nullptr;
   size_t nc = 0, nf = 0;
   pfv::FluxFn F;
-  pfv_status st = adjoint_setup(h, S, [&] {
+  pfv_status st = step_setup(h, S, steps_done, [&] {
     adjoint_nl_supported(h, fluxfn_kind, fluxfn_params, n_params, grad_fluxfn, bc_values, accumulation);
     adjoint_check_counts(n_steps, rtol, maxit, loads != nullptr);
     require(states != nullptr || n_steps == 0, "states (s^0 .. s^N) is required: the step is linearised about them");
@@ -2413,7 +2342,7 @@ pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind
   });
   if (st != PFV_OK) return st;
 
-  AdjointRun run;
+  StepRun run;
   const double* d_sink = sink ? h->nl_sink.p : nullptr;
   AdjointCall call{1, n_steps, n_obs, obs_cells, states, h->nl_acc.p, grad_source, grad_accumulation, steps_done, last};
   call.grads = {{grad_s0, &h->aj_r, nc, GradLayout::by_cell, false},
@@ -2428,11 +2357,11 @@ pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind
     const pfv::Sweep& sw = *cx.sweep;
     const double *valT = cx.valT_T.p, *acc = cx.nl_acc.p, *d = cx.aj_d.p, *diag = cx.diag_t.p;
     pfv::adjoint_nl_slopes(cx, F, cx.aj_sB.p, cx.aj_d.p, cx.aj_phi.p);  // of s^n
-    AdjointSolve V{1, -1, cx.mc_nrm.p};
+    SweepSolve V{1, -1, cx.mc_nrm.p, kAdjointSweep};
     V.levels = [&](int from, int to) {
       return pfv::sweep_apply_nl_t(cx, sw, from, to, cx.pat_T, valT, diag, d_sink, acc, d, cx.aj_r.p, z);
     };
-    V.core_zero = [&] { pfv::sweep_core_zero(cx, sw, 1, z); };
+    V.core_start = [&] { pfv::sweep_core_zero(cx, sw, 1, z); };
     V.core_step = [&] {
       pfv::sweep_core_copy(cx, sw, 1, z, cx.aj_prev.p);
       pfv::sweep_core_nl_t(cx, sw, cx.pat_T, valT, diag, d_sink, acc, d, cx.aj_r.p, cx.aj_prev.p, z);
@@ -2440,7 +2369,7 @@ pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind
     V.norms = [&](bool core_only) {
       pfv::sweep_norms_nl_t(cx, sw, cx.pat_T, valT, d_sink, acc, d, cx.aj_r.p, z, core_only, cx.mc_nrm.p);
     };
-    return adjoint_sweep_solve(h, V, run, rtol, maxit, n);
+    return sweep_step_solve(h, V, run, rtol, maxit, n);
   }, [&](double* z) {
     pfv::pfv_ctx_impl& cx = *h;
     if (grad_sink) pfv::adjoint_nl_grad_sink(cx, z, cx.aj_phi.p, cx.aj_gsink.p);
@@ -2460,7 +2389,7 @@ pfv_status pfv_transport_adjoint_nl(pfv_ctx* h, const double* q, int fluxfn_kind
 // In the frame of adjoint_steps with its own hooks, for it has two kinds of multipliers (lambda of the saturation in
 // aj_lam / aj_lam2, mu of the components in aj_mu / aj_mu2) and two slabs (s in aj_sA / aj_sB, c in aj_cA / aj_cB): per
 // step the slab (s^n, c^n), the slopes with the dry-row flag and the two right-hand sides fused with what the
-// multipliers of step n + 1 add to the cell gradients; adjoint_sweep_solve on mu and lambda jointly (sweep_row_nlc_t),
+// multipliers of step n + 1 add to the cell gradients; sweep_step_solve on mu and lambda jointly (sweep_row_nlc_t),
 // the k + 1 pairs of norms and the flag in its ONE host read.  The last pass on slab 0 leaves grad_s0 and grad_c0.
 pfv_status pfv_transport_adjoint_nl_multi(pfv_ctx* h, const double* q, int fluxfn_kind, const double* fluxfn_params,
                                           int n_params, const double* bc_values, const double* accumulation,
@@ -2474,11 +2403,11 @@ pfv_status pfv_transport_adjoint_nl_multi(pfv_ctx* h, const double* q, int fluxf
                                           pfv_solve_info* last) {
   if (steps_done) *steps_done = 0;
   if (k < 1 || k > 64) return guarded(h, [&] { require(false, "k must lie in 1 .. 64"); });
-  AdjointSetup S;
+  StepSetup S;
   const double* d_q = nullptr;
   size_t nc = 0, nf = 0;
   pfv::FluxFn F;
-  pfv_status st = adjoint_setup(h, S, [&] {
+  pfv_status st = step_setup(h, S, steps_done, [&] {
     adjoint_nl_supported(h, fluxfn_kind, fluxfn_params, n_params, grad_fluxfn, bc_values, accumulation);
     require(c_bc_values, "c_bc_values is required");
     adjoint_check_counts(n_steps, rtol, maxit, s_loads || c_loads, "s_loads or c_loads is required");
@@ -2525,7 +2454,7 @@ pfv_status pfv_transport_adjoint_nl_multi(pfv_ctx* h, const double* q, int fluxf
   if (st != PFV_OK) return st;
 
   const int K = k + 1;  // the norms' pairs: components 0 .. k - 1, then the saturation
-  AdjointRun run;
+  StepRun run;
   const double* d_sink = sink ? h->nl_sink.p : nullptr;
   const double* d_ads = sorption ? h->nlc_ads.p : nullptr;
   AdjointCall call{k, n_steps, n_obs, obs_cells, nullptr, nullptr, nullptr, nullptr, steps_done, last};
@@ -2587,11 +2516,11 @@ pfv_status pfv_transport_adjoint_nl_multi(pfv_ctx* h, const double* q, int fluxf
     pfv::NlCompT Cc = C;
     Cc.mu_prev = cx.aj_muprev.p;
     Cc.lam_prev = cx.aj_prev.p;
-    AdjointSolve V{K, k, cx.mc_nrm.p};
+    SweepSolve V{K, k, cx.mc_nrm.p, kAdjointSweep};
     V.levels = [&](int from, int to) {
       return pfv::sweep_apply_nlc_t(cx, sw, from, to, cx.pat_T, valT, diag, d_sink, acc, d, phi, s_n, cx.aj_r.p, z, C);
     };
-    V.core_zero = [&] {
+    V.core_start = [&] {
       pfv::sweep_core_zero(cx, sw, 1, z);
       pfv::sweep_core_zero(cx, sw, k, C.mu);
     };
@@ -2609,7 +2538,7 @@ pfv_status pfv_transport_adjoint_nl_multi(pfv_ctx* h, const double* q, int fluxf
                                         ", component " + std::to_string(w % k) + " is dry (accumulation x s + sorption + "
                                         "f(s) x outflow is zero: the step does not determine the component there)");
     };
-    return adjoint_sweep_solve(h, V, run, rtol, maxit, n);
+    return sweep_step_solve(h, V, run, rtol, maxit, n);
   }, [&](double* z) {
     pfv::pfv_ctx_impl& cx = *h;
     const double *mu = cx.aj_mu2.p, *s_n = cx.aj_sB.p, *c_n = cx.aj_cB.p, *phi = cx.aj_phi.p;

@@ -92,6 +92,14 @@ enum {
   PFV_FLUXFN_TABLE = 2   /* m = 2 .. 1024 finite, nondecreasing values on uniform knots over [0, 1], piecewise linear */
 };
 
+/* sorption isotherms S(c), c >= 0, of pfv_transport_advance_sorb (csrc/isotherm.h): two parameters each, S(0) = 0,
+ * nondecreasing */
+enum {
+  PFV_ISOTHERM_LINEAR = 0,     /* S = Kd c: Kd >= 0, the second parameter is not read */
+  PFV_ISOTHERM_FREUNDLICH = 1, /* S = Kf c^n: Kf >= 0, n > 0 (n < 1: an infinite slope at c = 0, taken from c = 0 on) */
+  PFV_ISOTHERM_LANGMUIR = 2    /* S = q_max b c / (1 + b c): q_max >= 0, b >= 0 */
+};
+
 /* flags for pfv_mpfa_discretize */
 enum {
   PFV_DISCR_REBUILD_TOPOLOGY = 1, /* redo sub-cell topology + CSR symbolic phase even if
@@ -254,6 +262,10 @@ typedef struct {
   int64_t advdiff_adjoint_exact_passes; /* ... region-kernel launches: ceil(N / B) batches times the non-empty node
                                       classes (0: no step, a TPFA diffusion, or not asked for) */
   int64_t advdiff_adjoint_exact_batch; /* ... the B used: exact_batch (0: the default, 32) clipped to N (0: no region pass) */
+  double transport_sorb_ms;        /* last pfv_transport_advance_sorb, all steps (HIP events) */
+  int64_t transport_sorb_steps;    /* ... accepted steps */
+  int64_t transport_sorb_core_iterations; /* ... nonlinear Jacobi iterations of the cyclic core, summed over the steps */
+  int64_t transport_sorb_components; /* ... its k */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -776,6 +788,50 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
                                        const double* accumulation, const double* source, const double* mobility,
                                        const double* rate, const double* rate_weight, int n_steps, double rtol,
                                        int maxit, double* c, int32_t* steps_done, pfv_solve_info* last);
+
+/* Sorbing transport: n_steps implicit Euler steps of k (1 .. 64) concentrations c >= 0 in equilibrium with a sorbed
+ * amount on a NONLINEAR isotherm, on the flux q -- Freundlich or Langmuir retardation.  Per cell i and component a
+ *     acc_ia (c_ia - c_old_ia) + cap_ia (S_a(c_ia) - S_a(c_old_ia)) + sum_j A_ij c_ja + b_ref_ia = src_ia
+ *     b_ref_a = div (rhs_neu + rhs_dir diag(q)) bc_values[a]                         (as pfv_transport_advance_multi)
+ * with A = div diag(q) U of the one-component discretization on the handle (pfv_upwind_discretize with
+ * num_components = 1; no pfv_upwind_assemble is needed).  accumulation = acc > 0 is porosity x volume / dt; capacity =
+ * cap >= 0 ([k][Nc], NULL: no sorption) is bulk density x volume / dt and carries whatever scales the isotherm per cell.
+ * isotherm_kind (k values, host memory) names a PFV_ISOTHERM_* per component, isotherm_params ([k][2], host memory) its
+ * two parameters.  The call is for c >= 0; pfv_transport_advance_multi remains the call for signed quantities.
+ *   In flow order the step is one scalar monotone root-finding per cell and component (csrc/sweep.inc: sweep_row_sorb):
+ * with d = A_ii and R = rhs - sum_upstream A_ij c_j the unknown solves g(x) = (acc + d) x + cap S(x) - R = 0 on the
+ * bracket [0, R / (acc + d)], by Newton from the state of the step's start, safeguarded by bisection; the transport
+ * part stays linear, so there is no Jacobian, no Krylov loop and no damping, and an acyclic flux is solved exactly.  A
+ * linear component is folded into the accumulation, acc + cap Kd, and is the division of pfv_transport_advance_multi:
+ * with Kd = 1 its bits are those of that call with accumulation = acc + cap and PFV_PRECOND_SWEEP on an acyclic flux.
+ * S(c) of a row is carried beside c for the next step's right-hand side rhs = acc c_old + cap S(c_old) - b_ref + src: no
+ * power is evaluated outside the root-finder.  All k components go in the launches of one: pfv_stats.sweep_launches
+ * is that of pfv_transport_advance with PFV_PRECOND_SWEEP on the same flux, and a component's result on an acyclic flux
+ * does not depend on which other components ride in the call.  The cells of a cyclic core are iterated by nonlinear
+ * Jacobi until every component has ||F_core,a|| <= rtol ||rhs_a|| / 2, or maxit iterations.  A step is accepted when
+ * every component has ||F_a|| <= rtol ||rhs_a|| (0 <= 0 counts), F_a = rhs_a - (acc c + cap S(c) + A c); one host read
+ * per step brings the 2 k norms and the flag word.  There is no per-component fallback.
+ *   bc_values [k][Nf], accumulation, capacity (may be NULL), source (may be NULL), c (in and out) and sorbed_out (may be
+ * NULL: S_a(c_a) of the returned state) [k][Nc] are component-major and follow pfv_set_vectors_on_device, as q (Nf,
+ * NULL = the flux of the discretization) does.  c holds the state after the last accepted step.  last (k entries, may
+ * be NULL): iterations = 1 for an acyclic flux, else the core iterations of the last step; rel_residual the measured
+ * ||F_a|| / ||rhs_a||.
+ *   A row with R < 0 beyond rounding has no root c >= 0 (a sink that takes more than the cell holds): the step is refused
+ * with PFV_ERR_ARGUMENT and the text "step N leaves c >= 0: no root in cell I, component A" (the lowest such cell, its
+ * lowest component); c is the state before that step.  PFV_ERR_ARGUMENT too, the text naming the lowest offender: no
+ * discretization or num_components != 1; k outside 1 .. 64; an unknown isotherm kind, a non-finite parameter, a
+ * negative Kd, Kf, q_max or b, n <= 0; accumulation <= 0 or NaN; a negative or NaN capacity; a c that is negative or
+ * not finite; a negative or non-finite bc_values[a] on a Dirichlet inflow face, a non-finite one on a Neumann face; a
+ * boundary face with inflow that is neither Dirichlet nor Neumann.  PFV_ERR_NOT_CONVERGED: a core that did not settle,
+ * a step whose check fails; c is the state of that step's start.  PFV_ERR_UNSUPPORTED and the handle rules are those
+ * of pfv_transport_advance_react: the flow order is built if the handle has none for this flux and stays; the
+ * preconditioner selection and the flow system are left alone; no transport system is left behind.  pfv_stats:
+ * transport_sorb_* and the sweep_* fields. */
+pfv_status pfv_transport_advance_sorb(pfv_ctx* h, const double* q, int k, const int32_t* isotherm_kind,
+                                      const double* isotherm_params, const double* bc_values,
+                                      const double* accumulation, const double* capacity, const double* source,
+                                      int n_steps, double rtol, int maxit, double* c, double* sorbed_out,
+                                      int32_t* steps_done, pfv_solve_info* last);
 
 /* The adjoint of pfv_transport_advance_multi: every gradient of J = sum_{n=1..N} sum_a <g_a^n, c_a^n> through n_steps = N
  * forward steps (diag(acc_a) + A(q)) c_a^n = acc_a o c_a^{n-1} - b_ref(q, bv_a) + src_a, for the cost of about one more

@@ -18,7 +18,8 @@ from .device_csr import DeviceCsr, block_diag, bmat, merged_matrix, vstack
 from . import ad
 from . import md_sharding
 from .tpfa import DifferentiableTpfa, Tpfa, as_porepy_ad_tpfa_flux
-from .upwind import CoreyFractionalFlow, ResidentFlux, TabulatedFractionalFlow, Upwind, as_porepy_upwind
+from .upwind import (CoreyFractionalFlow, FreundlichIsotherm, LangmuirIsotherm, LinearIsotherm, ResidentFlux,
+                     TabulatedFractionalFlow, Upwind, as_porepy_upwind)
 from .advdiff import AdvectionDiffusion
 from .params import (DISCRETIZATION_MATRICES, PARAMETERS, BoundaryCondition, BoundaryConditionVectorial,
                      FourthOrderTensor, SecondOrderTensor, bc_flags, bc_to_raw, initialize_data)
@@ -29,5 +30,6 @@ __all__ = [
     "as_porepy_discretization", "determine_eta", "SecondOrderTensor", "BoundaryCondition", "Mpsa", "rigid_body_modes",
     "FourthOrderTensor", "BoundaryConditionVectorial",
     "initialize_data", "bc_to_raw", "bc_flags", "PARAMETERS", "DISCRETIZATION_MATRICES", "_lib", "active_indices", "HipLinearSolver", "solve_csr", "Tpfa", "DifferentiableTpfa", "as_porepy_ad_tpfa_flux", "Biot", "as_porepy_mpsa", "as_porepy_biot", "DeviceCsr", "block_diag", "bmat", "merged_matrix", "vstack", "ad", "solve_block_system", "md_sharding", "DeviceAssembly",
-    "Upwind", "ResidentFlux", "as_porepy_upwind", "CoreyFractionalFlow", "TabulatedFractionalFlow", "AdvectionDiffusion",
+    "Upwind", "ResidentFlux", "as_porepy_upwind", "CoreyFractionalFlow", "TabulatedFractionalFlow",
+    "LinearIsotherm", "FreundlichIsotherm", "LangmuirIsotherm", "AdvectionDiffusion",
 ]

@@ -26,6 +26,7 @@ BC_DIR, BC_NEU, BC_ROB, BC_INTERNAL = 1, 2, 4, 8
 SOLVE_CG, SOLVE_BICGSTAB, SOLVE_GMRES = 0, 1, 2
 PRECOND_JACOBI, PRECOND_AMG, PRECOND_BLOCK, PRECOND_AMG_NNS, PRECOND_SWEEP = 0, 1, 2, 3, 4
 FLUXFN_LINEAR, FLUXFN_COREY, FLUXFN_TABLE = 0, 1, 2
+ISOTHERM_LINEAR, ISOTHERM_FREUNDLICH, ISOTHERM_LANGMUIR = 0, 1, 2
 DISCR_REBUILD_TOPOLOGY, DISCR_SKIP_VECTOR_SOURCE = 1, 2
 
 STATUS_NAMES = {
@@ -53,7 +54,7 @@ EXPORTS = [
     "pfv_sweep_info", "pfv_transport_advance_multi", "pfv_transport_advance_nl", "pfv_transport_advance_nl_multi",
     "pfv_transport_advance_react", "pfv_transport_adjoint_multi", "pfv_transport_adjoint_react",
     "pfv_transport_adjoint_nl", "pfv_transport_adjoint_nl_multi", "pfv_flow_adjoint", "pfv_flow_adjoint_exact",
-    "pfv_advdiff_adjoint", "pfv_advdiff_adjoint_exact", "pfv_amg_level_rhs",
+    "pfv_advdiff_adjoint", "pfv_advdiff_adjoint_exact", "pfv_amg_level_rhs", "pfv_transport_advance_sorb",
 ]
 
 
@@ -111,7 +112,9 @@ class Stats(C.Structure):
                 ("flow_adjoint_exact_map_ms", C.c_double), ("flow_adjoint_exact_ms", C.c_double),
                 ("spgemm_path", C.c_int64), ("spgemm_lds_bytes", C.c_int64),
                 ("advdiff_adjoint_exact_ms", C.c_double), ("advdiff_adjoint_exact_passes", C.c_int64),
-                ("advdiff_adjoint_exact_batch", C.c_int64)]
+                ("advdiff_adjoint_exact_batch", C.c_int64),
+                ("transport_sorb_ms", C.c_double), ("transport_sorb_steps", C.c_int64),
+                ("transport_sorb_core_iterations", C.c_int64), ("transport_sorb_components", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -343,6 +346,9 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_transport_advance_react.argtypes = [_h, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double,
                                                 C.c_int, _dp, C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
     lib.pfv_transport_advance_react.restype = C.c_int
+    lib.pfv_transport_advance_sorb.argtypes = [_h, _dp, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double,
+                                               C.c_int, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(SolveInfo)]
+    lib.pfv_transport_advance_sorb.restype = C.c_int
     lib.pfv_transport_adjoint_multi.argtypes = [_h, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int64, _ip, _dp, _dp, C.c_double,
                                                 C.c_int, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32),
                                                 C.POINTER(SolveInfo)]
@@ -1606,6 +1612,38 @@ class Context:
         out = {"steps_done": done.value, "converged": all(bool(i.converged) for i in infos),
                "iterations": [i.iterations for i in infos], "rel_residual": [i.rel_residual for i in infos],
                "solve_ms": [i.solve_ms for i in infos]}
+        self._step_result(st, raise_on_fail, state=c, info=out)
+        return c, out
+
+    def transport_advance_sorb(self, c0, n_steps: int, accumulation, bc_values, isotherm_kinds, isotherm_params,
+                               capacity=None, q=None, source=None, rtol=1e-12, maxit=500, raise_on_fail=True):
+        """``n_steps`` implicit Euler steps of k concentrations ``c >= 0`` in equilibrium with a sorbed amount on a
+        nonlinear isotherm, on the flux of the one-component upwind discretization on this handle
+        (pfv_transport_advance_sorb): in flow order every (cell, component) is one scalar root-finding.  ``c0``,
+        ``accumulation``, ``capacity`` (may be None: no sorption) and ``source`` (may be None): k x Nc; ``bc_values``:
+        k x Nf; ``isotherm_kinds``: k ISOTHERM_* codes; ``isotherm_params``: k x 2.  Returns (c, info) with
+        ``steps_done``, ``converged``, the per-component lists ``iterations`` and ``rel_residual``, and ``sorbed``
+        (k x Nc): S_a(c_a) of the returned state.  An error raised for a refused step carries ``state`` (c before that
+        step) and ``info``."""
+        c, k = self._component_state(c0, 64, "components")
+        acc, bv, cap, src = self._per_component(k, ("accumulation", accumulation, self.nc, True),
+                                                ("bc_values", bc_values, self.nf, True),
+                                                ("capacity", capacity, self.nc, False), ("source", source, self.nc, False))
+        kinds = np.ascontiguousarray(isotherm_kinds, dtype=np.int32)
+        par = _f64(isotherm_params)
+        if kinds.shape != (k,) or par.shape != (k, 2):
+            raise ValueError(f"isotherm_kinds must have shape ({k},) and isotherm_params ({k}, 2), not {kinds.shape} "
+                             f"and {par.shape}")
+        kq, pq = self._vec(q, self.nf, "the flux array", False)
+        sorbed = np.zeros((k, self.nc))
+        done, infos = C.c_int32(0), (SolveInfo * k)()
+        st = self.lib.pfv_transport_advance_sorb(self._h, pq, k, _ptr(kinds, _ip), _ptr(par, _dp), _ptr(bv, _dp),
+                                                 _ptr(acc, _dp), _ptr(cap, _dp), _ptr(src, _dp), int(n_steps),
+                                                 float(rtol), int(maxit), _ptr(c, _dp), _ptr(sorbed, _dp),
+                                                 C.byref(done), infos)
+        out = {"steps_done": done.value, "converged": all(bool(i.converged) for i in infos),
+               "iterations": [i.iterations for i in infos], "rel_residual": [i.rel_residual for i in infos],
+               "solve_ms": [i.solve_ms for i in infos], "sorbed": sorbed}
         self._step_result(st, raise_on_fail, state=c, info=out)
         return c, out
 

@@ -358,6 +358,13 @@ struct pfv_ctx_impl {
   // the copy of the state for the core, rhs, the scale g and F = rhs - image; rc_par: ReactPar (w, K) for the kernels
   // that index it at run time; rc_out: 2 k norms, then the status word
   Buf<double> rc_acc, rc_src, rc_bref, rc_x, rc_z, rc_prev, rc_rhs, rc_g, rc_F, rc_par, rc_out;
+  // sorbing transport (pfv_transport_advance_sorb): the caller's arrays as they came, component-major [k][n] ...
+  Buf<double> sb_q, sb_bc, sb_acc_in, sb_cap_in, sb_src_in, sb_c_in;
+  // ... the vectors of the step, cell-major interleaved v[i * k + a]: accumulation and capacity as they came, the folded
+  // accumulation (acc + cap Kd of a linear component), the capacity of the root-finder (0 for a linear component),
+  // source, b_ref, the two states, sigma = S(c) of the two states, the copy of the state for the core, rhs; sb_par: k
+  // Isotherm records for the kernels; sb_out: 2 k norms, then the flag word
+  Buf<double> sb_acc, sb_cap, sb_accf, sb_capn, sb_src, sb_bref, sb_x, sb_z, sb_sx, sb_sz, sb_prev, sb_rhs, sb_par, sb_out;
   // the adjoint of the k-component step (pfv_transport_adjoint_multi; q, bc and accumulation in mc_q, mc_bc, mc_acc,
   // mc_acc_i).  tpos_T: position of the transposed partner of every entry of pat_T -- a property of that pattern, valid
   // while have_tpos_T (dropped wherever pat_T is rebuilt); valT_T: the transposed values of the call's assembly

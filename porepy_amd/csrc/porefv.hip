@@ -8,6 +8,7 @@
 
 #include "ctx.h"
 #include "fluxfn.h"
+#include "isotherm.h"
 #include "react.h"
 namespace pfv {
 static int rccl_exchange_halo(void* user, double* d_x, void* stream);  // rccl_hooks.inc
@@ -1688,7 +1689,7 @@ pfv_status pfv_transport_advance_nl_multi(pfv_ctx* h, const double* q, int fluxf
                     sorption, c_source, n_steps, rtol, maxit, s, c, steps_done, last);
 }
 
-// ---- the solve of one step by a sweep: pfv_transport_advance_react and the four adjoints ---------------------------------
+// ---- the solve of one step by a sweep: pfv_transport_advance_react, pfv_transport_advance_sorb and the four adjoints ------
 // The levels before the core, the core level iterated by Jacobi on its rows (a host read every kNlCoreCheck-th
 // iteration), the levels after it, the residual norms of all rows and ONE host read; then the acceptance.  A forward
 // step walks the levels from first to last, an adjoint step from last to first.  The calls differ in their rows and
@@ -1891,6 +1892,135 @@ pfv_status pfv_transport_advance_react(pfv_ctx* h, const double* q, int k, const
   h->stats.transport_react_steps = run.completed;
   h->stats.transport_react_core_iterations = run.core_total;
   h->stats.transport_react_components = k;
+  sweep_step_stats(h, n_steps > 0 ? run.launches : -1, S.order_ms);
+  return st;
+}
+
+// ---- sorbing transport: one scalar root per cell and component in flow order (sweep.inc: sweep_row_sorb) ----------------
+// In step_frame with the solve of sweep_step_solve, ascending: per step rhs, the forward levels, the core level iterated
+// by nonlinear Jacobi, the backward levels, then the image and its 2k norms over all rows and ONE host read of them and
+// the flag word.  The state of the step's start and its sigma = S(c) stay in their own buffers until the step is accepted.
+static void sorb_inputs_refused(const int32_t (&off)[pfv::kSorbChecks], int k) {
+  static const char* const what[pfv::kSorbChecks] = {
+      "accumulation must be positive: cell ", "capacity must not be negative: cell ",
+      "c must be non-negative and finite: cell ", "Dirichlet inflow value must be non-negative and finite: face ",
+      "Neumann value is not finite on face ", pfv::kUnmarkedInflowFace};
+  inputs_refused(off, pfv::kSorbChecks, what, 0x1fu, k, 0);
+}
+
+pfv_status pfv_transport_advance_sorb(pfv_ctx* h, const double* q, int k, const int32_t* isotherm_kind,
+                                      const double* isotherm_params, const double* bc_values,
+                                      const double* accumulation, const double* capacity, const double* source,
+                                      int n_steps, double rtol, int maxit, double* c, double* sorbed_out,
+                                      int32_t* steps_done, pfv_solve_info* last) {
+  StepSetup S;
+  const double* d_q = nullptr;
+  size_t nc = 0, nf = 0;
+  std::vector<pfv::Isotherm> iso;
+  pfv_status st = step_setup(h, S, steps_done, [&] {
+    upwind_supported(h);
+    if (h->subface_bc) throw Error(PFV_ERR_UNSUPPORTED, "conditions per sub-face are not covered");
+    require(h->have_upwind, "pfv_upwind_discretize first");
+    require(h->upw_ncomp == 1, "the components share one discretization: pfv_upwind_discretize with num_components = 1");
+    if (k < 1 || k > 64) throw Error(PFV_ERR_ARGUMENT, "k must lie in 1 .. 64 (k = " + std::to_string(k) + ")");
+    require(isotherm_kind && isotherm_params, "isotherm_kind and isotherm_params are required");
+    iso.resize((size_t)k);
+    for (int a = 0; a < k; ++a) {
+      const double p0 = isotherm_params[2 * a], p1 = isotherm_params[2 * a + 1];
+      const std::string bad = pfv::isotherm_check(isotherm_kind[a], p0, p1);
+      if (!bad.empty()) throw Error(PFV_ERR_ARGUMENT, "isotherm of component " + std::to_string(a) + ": " + bad);
+      iso[(size_t)a] = pfv::isotherm_make(isotherm_kind[a], p0, p1);
+    }
+    require(bc_values && accumulation && c, "bc_values, accumulation and c are required");
+    require(n_steps >= 0, "bad argument");
+    require(rtol > 0 && maxit > 0, "rtol and maxit must be positive");
+    nc = (size_t)h->nc;
+    nf = (size_t)h->nf;
+    if ((int64_t)(k + 1) * (int64_t)std::max(nc, nf) >= (int64_t(1) << 31))
+      throw Error(PFV_ERR_UNSUPPORTED, "(k + 1) x cells (faces) beyond int32 indices");
+    be_h2d(h->sb_par.ensure(3 * (size_t)k), iso.data(), sizeof(pfv::Isotherm) * (size_t)k, h->stream);
+    if (q) vec_in(h, h->sb_q.ensure(nf), q, nf);
+    vec_in(h, h->sb_bc.ensure(k * nf), bc_values, k * nf);  // component-major, as they came
+    vec_in(h, h->sb_acc_in.ensure(k * nc), accumulation, k * nc);
+    if (capacity) vec_in(h, h->sb_cap_in.ensure(k * nc), capacity, k * nc);
+    if (source) vec_in(h, h->sb_src_in.ensure(k * nc), source, k * nc);
+    vec_in(h, h->sb_c_in.ensure(k * nc), c, k * nc);
+    d_q = q ? h->sb_q.p : h->upw_q.p;
+    pfv::upwind_face_cells(*h);
+    int32_t off[pfv::kSorbChecks];
+    pfv::sweep_sorb_check_inputs(*h, d_q, k, h->sb_bc.p, h->sb_acc_in.p, capacity ? h->sb_cap_in.p : nullptr,
+                                 h->sb_c_in.p, off);
+    sorb_inputs_refused(off, k);
+    transport_system(h, S, d_q, h->sb_bc.p, [&] {
+      pfv::multi_interleave(*h, (int64_t)nc, k, h->sb_acc_in.p, h->sb_acc.ensure(k * nc));
+      if (capacity) pfv::multi_interleave(*h, (int64_t)nc, k, h->sb_cap_in.p, h->sb_cap.ensure(k * nc));
+      if (source) pfv::multi_interleave(*h, (int64_t)nc, k, h->sb_src_in.p, h->sb_src.ensure(k * nc));
+      pfv::multi_interleave(*h, (int64_t)nc, k, h->sb_c_in.p, h->sb_x.ensure(k * nc));
+      pfv::upwind_bref_multi(*h, k, d_q, h->sb_bc.p, h->sb_bref.ensure(k * nc));
+      for (pfv::Buf<double>* b : {&h->sb_accf, &h->sb_capn, &h->sb_sx, &h->sb_z, &h->sb_sz, &h->sb_prev, &h->sb_rhs})
+        b->ensure(k * nc);
+      h->sb_out.ensure(2 * (size_t)k + 1);
+      pfv::sweep_sorb_setup(*h, k, reinterpret_cast<const pfv::Isotherm*>(h->sb_par.p), h->sb_acc.p,
+                            capacity ? h->sb_cap.p : nullptr, h->sb_x.p, h->sb_accf.p, h->sb_capn.p, h->sb_sx.p);
+    });
+  });
+  if (st != PFV_OK) return st;
+
+  StepRun run;
+  run.info.assign((size_t)k, pfv_solve_info{});
+  st = step_frame(h, S, run, n_steps, steps_done, [&](int step) -> pfv_status {
+    pfv::pfv_ctx_impl& cx = *h;
+    const pfv::Sweep& sw = *cx.sweep;
+    const double* val = cx.val[PFV_MAT_TRANSPORT_SYSTEM].p;
+    const double* capn = capacity ? cx.sb_capn.p : nullptr;
+    double* out = cx.sb_out.p;
+    int32_t* status = reinterpret_cast<int32_t*>(out + 2 * k);
+    pfv::SorbRow A{cx.pat_T.indptr, cx.pat_T.indices, sw.lev(false), val, cx.diag_t.p, cx.sb_accf.p, capn, cx.sb_rhs.p,
+                   reinterpret_cast<const pfv::Isotherm*>(cx.sb_par.p), cx.sb_x.p, nullptr, cx.sb_z.p, cx.sb_sz.p, status};
+    pfv::SorbRow Ac = A;  // the core level: the previous iterate for the in-core neighbours and as the start value
+    Ac.c_prev = Ac.c_start = cx.sb_prev.p;
+    pfv::upwind_step_rhs_sorb(cx, k, cx.sb_accf.p, capn, source ? cx.sb_src.p : nullptr, cx.sb_bref.p, cx.sb_x.p,
+                              cx.sb_sx.p, cx.sb_rhs.p);
+    pfv::be_memset(status, 0x7f, sizeof(double), cx.stream);
+    SweepSolve V{k, -1, out, kForwardSweep};
+    V.levels = [&](int from, int to) { return pfv::sweep_apply_sorb(cx, sw, from, to, k, A); };
+    V.core_start = [&] { pfv::sweep_core_copy(cx, sw, k, cx.sb_x.p, cx.sb_z.p); };  // the state of the step's start
+    V.core_step = [&] {
+      pfv::sweep_core_copy(cx, sw, k, cx.sb_z.p, cx.sb_prev.p);
+      pfv::sweep_levels_sorb(cx, sw, sw.core_level, sw.core_level + 1, k, Ac);
+    };
+    V.norms = [&](bool core_only) {  // from hst: (rhs_a, rhs_a), (F_a, F_a)
+      pfv::sweep_sorb_norms(cx, cx.pat_T, val, k, cx.sb_accf.p, capn, cx.sb_rhs.p, cx.sb_z.p, cx.sb_sz.p, A.lev,
+                            core_only ? sw.core_level : -1, out);
+    };
+    V.flag_ends_core = true;  // (a row without a root c >= 0: the input admits no solution)
+    V.flagged = [&](int n, int32_t at) -> pfv_status {
+      throw Error(PFV_ERR_ARGUMENT, "step " + std::to_string(n) + " leaves c >= 0: no root in cell " +
+                                        std::to_string(at / k) + ", component " + std::to_string(at % k));
+    };
+    const pfv_status verdict = sweep_step_solve(h, V, run, rtol, maxit, step);
+    if (verdict != PFV_OK) return verdict;
+    cx.sb_x.swap(cx.sb_z);
+    cx.sb_sx.swap(cx.sb_sz);
+    ++run.completed;
+    return PFV_OK;
+  }, [&](pfv_status) {
+    pfv::multi_deinterleave(*h, (int64_t)nc, k, h->sb_x.p, h->sb_c_in.p);
+    vec_out(h, c, h->sb_c_in.p, k * nc);
+    if (sorbed_out) {
+      pfv::multi_deinterleave(*h, (int64_t)nc, k, h->sb_sx.p, h->sb_c_in.p);
+      vec_out(h, sorbed_out, h->sb_c_in.p, k * nc);
+    }
+  });
+  if (last)
+    for (int a = 0; a < k; ++a) {
+      last[a] = run.info[(size_t)a];
+      if (run.completed > 0) last[a].solve_ms = run.ms / run.completed;
+    }
+  h->stats.transport_sorb_ms = run.ms;
+  h->stats.transport_sorb_steps = run.completed;
+  h->stats.transport_sorb_core_iterations = run.core_total;
+  h->stats.transport_sorb_components = k;
   sweep_step_stats(h, n_steps > 0 ? run.launches : -1, S.order_ms);
   return st;
 }

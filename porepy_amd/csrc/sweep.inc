@@ -1175,6 +1175,192 @@ static void upwind_bref_react(pfv_ctx_impl& c, int k, const double* d_q, const d
   });
 }
 
+// ---- sorbing transport (pfv_transport_advance_sorb): per cell and component
+//     acc_ia (c_ia - c_old_ia) + cap_ia (S_a(c_ia) - S_a(c_old_ia)) + sum_j A_ij c_ja + b_ref_ia = src_ia
+// with the isotherm S_a of the component (isotherm.h).  The nonlinearity sits in the accumulation, the transport part is
+// linear: once the upstream cells of a row are known, with D = acc + A_ii and R = rhs - sum_{lev[j] < lev[i]} A_ij c_j,
+// the unknown of (row, component) is the root of  g(x) = D x + cap S(x) - R,  strictly increasing.  S(0) = 0 and S >= 0
+// put the root into [0, R / D]; the right end has g = cap S >= 0, so the caller gives no upper bound.
+//   items  one work item per (row, component), as sweep_row_multi: the k items of a row load val[e], ix[e] and lev[j]
+//          from the same address and c[j, 0..k) as one run.  The sum runs in stored order.  Lanes of a wavefront need
+//          different numbers of evaluations (and a linear component none); they wait for the slowest.
+//   root   Newton from the start value clipped into the bracket; an iterate that leaves the bracket, or a |g| that did
+//          not halve, is replaced by the midpoint -- an infinite slope (Freundlich n < 1 at 0) gives a step of 0, or a
+//          NaN where cap S' is 0 * inf, and both fail the bracket test.  Stop: |g| <= 2^-50 (|rhs| + |sum|), the
+//          magnitudes that enter R and, at the root, bound D x and cap S(x) --, or a bracket of one ulp of its upper
+//          end, or kNlEvals evaluations.  (sweep_row_nl measures its bracket in [0, 1]; here the root has no scale but
+//          its own, and one as small as 1e-8 is still found to rounding.)
+//   leave  R < -2^-50 (|rhs| + |sum|): g(0) > 0, no root c >= 0.  The row takes 0 and records i * k + a with an integer
+//          atomic minimum.  A linear component that comes out negative beyond that tolerance is recorded too.
+//   sigma  the row writes sigma = S(c) beside c: the right-hand side of the next step and the image read it, so that no
+//          power is evaluated outside the root-finder.
+//   fold   a linear component is folded at set-up into accf = acc + cap Kd with capn = 0: its row is the division of
+//          sweep_row_multi, (rhs - sum) / (A_ii + accf), and no isotherm is evaluated for it but sigma = Kd c.  So is a
+//          row without capacity.
+//   core   rows of the core level (c_prev != nullptr) take their in-core neighbours from c_prev, the previous iterate:
+//          nonlinear Jacobi, independent of the scheduling.
+struct SorbRow {
+  const int32_t *ip, *ix, *lev;
+  const double *val, *diag, *accf, *capn, *rhs;  // capn may be nullptr (no sorption)
+  const Isotherm* iso;                           // [k], device memory
+  const double* c_start;                         // the start values of the root-finder
+  const double* c_prev;
+  double *c, *sig;
+  int32_t* status;
+};
+
+PFV_FN void sweep_row_sorb(int32_t i, int a, int k, const SorbRow& A) {
+  const int32_t li = A.lev[i];
+  double sum = 0.0;
+  for (int e = A.ip[i]; e < A.ip[i + 1]; ++e) {
+    const int32_t j = A.ix[e];
+    const int32_t lj = A.lev[j];
+    if (lj < li) sum += A.val[e] * A.c[(int64_t)j * k + a];
+    else if (A.c_prev && lj == li && j != i) sum += A.val[e] * A.c_prev[(int64_t)j * k + a];
+  }
+  const int64_t p = (int64_t)i * k + a;
+  const Isotherm I = A.iso[a];
+  const double r = A.rhs[p], D = A.diag[i] + A.accf[p];
+  const double cp = A.capn ? A.capn[p] : 0.0;
+  const double tol = kNlGTol * (fabs(r) + fabs(sum));
+  const double R = r - sum;
+  double dS;
+  if (I.kind == PFV_ISOTHERM_LINEAR) {  // folded: the division of sweep_row_multi
+    const double x = (r - sum) / D;
+    A.c[p] = x;
+    A.sig[p] = I.p0 * x;
+    if (R < -tol) atomic_min_i32(A.status, (int32_t)p);
+    return;
+  }
+  if (!(R > 0.0)) {  // g(0) >= 0: the root is 0, or there is none
+    if (R < -tol) atomic_min_i32(A.status, (int32_t)p);
+    A.c[p] = 0.0;
+    A.sig[p] = 0.0;
+    return;
+  }
+  double lo = 0.0, hi = R / D;
+  double x = hi, S;
+  if (cp > 0.0) {
+    double g_prev = 1.79769313486231570e308;
+    x = A.c_start[p];
+    x = x < lo ? lo : (x > hi ? hi : x);
+    for (int it = 0;; ++it) {
+      S = isotherm_eval(I, x, &dS);
+      const double g = D * x + cp * S - R;
+      if (fabs(g) <= tol || it == kNlEvals - 1) break;
+      if (g > 0.0) hi = x;
+      else lo = x;
+      if (hi - lo <= 2.220446049250313e-16 * hi) break;
+      double xn = x - g / (D + cp * dS);
+      if (!(xn > lo && xn < hi) || fabs(g) > 0.5 * g_prev) xn = 0.5 * (lo + hi);
+      g_prev = fabs(g);
+      x = xn;
+    }
+  } else {
+    S = isotherm_eval(I, x, &dS);
+  }
+  A.c[p] = x;
+  A.sig[p] = S;
+}
+
+// levels [l0, l1) of the order by the launch rule (sweep_levels), k work items per row; the kernel holds SorbRow by value
+static void sweep_levels_sorb(pfv_ctx_impl& c, const Sweep& sw, int l0, int l1, int k, const SorbRow& A_) {
+  const SorbRow A = A_;
+  sweep_levels(c, sw, false, l0, l1, k, PFV_LAMBDA(int32_t i, int a) { sweep_row_sorb(i, a, k, A); });
+}
+
+// the launch plan's levels in [from, to), outside the core.  Returns the launches.
+static int sweep_apply_sorb(pfv_ctx_impl& c, const Sweep& sw, int from, int to, int k, const SorbRow& A) {
+  return sweep_plan_range(sw, from, to, [&](int l0, int l1) { sweep_levels_sorb(c, sw, l0, l1, k, A); });
+}
+
+// The image and the norms in one pass: t[i, a] = sum_e A[i, e] x[j, a] + accf x + capn sigma in stored order, sigma the
+// carried S(x); out[a] = (rhs_a, rhs_a) over all rows, out[k + a] = (F_a, F_a), F = rhs - t.  core >= 0 (the core's stop
+// test, before the levels behind it have a value): F of the core rows alone, from the entries up to the core level.
+static void sweep_sorb_norms(pfv_ctx_impl& c, const CsrPattern& P, const double* val, int k, const double* accf,
+                             const double* capn, const double* rhs, const double* x, const double* sig,
+                             const int32_t* lev, int32_t core, double* out) {
+  const int32_t* ip = P.indptr;
+  const int32_t* ix = P.indices;
+  sweep_norms_pairs(c, P.nrows, k, out, PFV_LAMBDA(int64_t i, int a) {
+    const int64_t p = i * k + a;
+    const double ri = rhs[p];
+    if (core >= 0 && lev[i] != core) return NormPair{ri, 0.0};
+    double t = 0.0;
+    for (int e = ip[i]; e < ip[i + 1]; ++e) {
+      const int32_t j = ix[e];
+      if (core < 0 || lev[j] <= core) t += val[e] * x[(int64_t)j * k + a];
+    }
+    t += accf[p] * x[p];
+    if (capn) t += capn[p] * sig[p];
+    return NormPair{ri, ri - t};
+  });
+}
+
+// The set-up on the interleaved vectors: the folded accumulation accf and the root-finder's capacity capn (cap may be
+// nullptr: then capn is not written), and sigma = S(c0) of the state the call starts from.
+static void sweep_sorb_setup(pfv_ctx_impl& c, int k, const Isotherm* iso, const double* acc, const double* cap,
+                             const double* x, double* accf, double* capn, double* sig) {
+  parallel_for(c.stream, c.nc * k, PFV_LAMBDA(int64_t t) {
+    const Isotherm I = iso[t % k];
+    const bool lin = I.kind == PFV_ISOTHERM_LINEAR;
+    double dS;
+    accf[t] = lin && cap ? acc[t] + cap[t] * I.p0 : acc[t];
+    if (cap) capn[t] = lin ? 0.0 : cap[t];
+    sig[t] = isotherm_eval(I, x[t], &dS);
+  });
+}
+
+// right-hand side of the step: rhs = accf c_old - b_ref + src + capn sigma_old (interleaved).  Up to the last term it is
+// the expression of upwind_step_rhs_multi, which a linear component (capn = 0) then has bit for bit.
+static void upwind_step_rhs_sorb(pfv_ctx_impl& c, int k, const double* accf, const double* capn, const double* src,
+                                 const double* bref, const double* x, const double* sig, double* rhs) {
+  parallel_for(c.stream, c.nc * k, PFV_LAMBDA(int64_t t) {
+    double r = accf[t] * x[t];
+    r -= bref[t];
+    if (src) r += src[t];
+    if (capn) r += capn[t] * sig[t];
+    rhs[t] = r;
+  });
+}
+
+// What the call refuses in its arrays, each with the lowest index (component-major arrays as the caller passed them; an
+// offender is reported as index * k + component, so the lowest cell or face comes first): st[0] accumulation <= 0 or
+// NaN, st[1] a negative or NaN capacity, st[2] a c that is negative or not finite, st[3] a Dirichlet inflow value that
+// is negative or not finite, st[4] a non-finite Neumann value, st[5] a boundary face with inflow under q that is neither
+// Dirichlet nor Neumann.  (0x7f7f7f7f: none.)
+constexpr int kSorbChecks = 6;
+static void sweep_sorb_check_inputs(pfv_ctx_impl& c, const double* d_q, int k, const double* bc, const double* acc,
+                                    const double* cap, const double* cc, int32_t out[kSorbChecks]) {
+  stream_t st_ = c.stream;
+  const int64_t nc = c.nc, nf = c.nf;
+  const uint8_t* cls = c.upw_cls;
+  const int32_t* side = c.upw_side;
+  const int32_t* cnt = c.upw_cnt;
+  const uint8_t* flag = c.have_upw_bc ? c.upw_bc.p : nullptr;
+  int32_t* st = c.status.ensure(16);
+  be_memset(st, 0x7f, sizeof(int32_t) * kSorbChecks, st_);
+  parallel_for(st_, std::max(nc, nf), PFV_LAMBDA(int64_t t) {
+    const double big = 1.79769313486231570e308;
+    if (t < nc) {
+      for (int a = 0; a < k; ++a) {
+        if (!(acc[a * nc + t] > 0.0)) atomic_min_i32(st, (int32_t)(t * k + a));
+        if (cap && !(cap[a * nc + t] >= 0.0)) atomic_min_i32(st + 1, (int32_t)(t * k + a));
+        if (!(cc[a * nc + t] >= 0.0 && cc[a * nc + t] <= big)) atomic_min_i32(st + 2, (int32_t)(t * k + a));
+      }
+    }
+    if (t < nf) {
+      for (int a = 0; a < k; ++a) {
+        const double v = bc[a * nf + t];
+        if ((cls[t] & UPW_DIRIN) && !(v >= 0.0 && v <= big)) atomic_min_i32(st + 3, (int32_t)(t * k + a));
+        if ((cls[t] & UPW_NEU) && !(fabs(v) <= big)) atomic_min_i32(st + 4, (int32_t)(t * k + a));
+      }
+      if (upwind_unmarked_inflow(t, nf, cnt, flag, side, d_q)) atomic_min_i32(st + 5, (int32_t)t);
+    }
+  });
+  be_d2h(out, st, sizeof(int32_t) * kSorbChecks, st_);
+}
+
 // ---- the adjoint of the k-component step (pfv_transport_adjoint_multi): S_a^T lambda_a = r_a.  S_a = diag(acc_a) + A is
 // triangular in flow order, S_a^T in reverse flow order: one substitution over the same levels from last to first.
 //   tpos    the pattern of A (a cell and its face neighbours) is structurally symmetric: tpos[e] is the position of

@@ -106,6 +106,64 @@ class TabulatedFractionalFlow:
         return f"TabulatedFractionalFlow(<{self.values.size} values>)"
 
 
+class LinearIsotherm:
+    """Linear sorption isotherm ``S = kd c`` (``kd >= 0``).  Calling it evaluates the curve with numpy -- the curve
+    ``Upwind.advance_sorbing_components`` steps with on the device."""
+
+    kind = _lib.ISOTHERM_LINEAR
+
+    def __init__(self, kd=1.0):
+        self.kd = float(kd)
+
+    def params(self) -> np.ndarray:
+        return np.array([self.kd, 0.0])
+
+    def __call__(self, c):
+        return self.kd * np.asarray(c, dtype=np.float64)
+
+    def __repr__(self):
+        return f"LinearIsotherm(kd={self.kd})"
+
+
+class FreundlichIsotherm:
+    """Freundlich sorption isotherm ``S = kf c**n`` for ``c >= 0`` (``kf >= 0``, ``n > 0``; ``n < 1`` has an infinite slope
+    at 0).  Calling it evaluates the curve with numpy."""
+
+    kind = _lib.ISOTHERM_FREUNDLICH
+
+    def __init__(self, kf=1.0, n=1.0):
+        self.kf, self.n = float(kf), float(n)
+
+    def params(self) -> np.ndarray:
+        return np.array([self.kf, self.n])
+
+    def __call__(self, c):
+        return self.kf * np.asarray(c, dtype=np.float64) ** self.n
+
+    def __repr__(self):
+        return f"FreundlichIsotherm(kf={self.kf}, n={self.n})"
+
+
+class LangmuirIsotherm:
+    """Langmuir sorption isotherm ``S = q_max b c / (1 + b c)`` for ``c >= 0`` (``q_max >= 0``, ``b >= 0``).  Calling it
+    evaluates the curve with numpy."""
+
+    kind = _lib.ISOTHERM_LANGMUIR
+
+    def __init__(self, q_max=1.0, b=1.0):
+        self.q_max, self.b = float(q_max), float(b)
+
+    def params(self) -> np.ndarray:
+        return np.array([self.q_max, self.b])
+
+    def __call__(self, c):
+        c = np.asarray(c, dtype=np.float64)
+        return self.q_max * self.b * c / (1.0 + self.b * c)
+
+    def __repr__(self):
+        return f"LangmuirIsotherm(q_max={self.q_max}, b={self.b})"
+
+
 class Upwind:
     """Upwind discretization of ``keyword`` on the device.  ``flow``: an ``Mpfa`` / ``Tpfa`` object whose device
     handle of a grid is shared, so that the flux it left resident can be taken without a copy."""
@@ -427,6 +485,52 @@ class Upwind:
                                                             mobility=mobility, q=self._flux(sd, pd), source=src,
                                                             rtol=rtol, maxit=maxit, raise_on_fail=raise_on_fail)
 
+    def advance_sorbing_components(self, sd, data: dict, c0, n_steps: int, accumulation, isotherms, capacity=None,
+                                   bc_values=None, source=None, rtol: float = 1e-12, maxit: int = 500,
+                                   raise_on_fail: bool = True):
+        """``n_steps`` implicit Euler steps of k (1 .. 64) concentrations ``c >= 0`` in equilibrium with a sorbed amount
+        on a NONLINEAR isotherm, on the one flux of the (one-component) discretization -- Freundlich or Langmuir
+        retardation: concentration-dependent retardation, self-sharpening fronts, tailing:
+        ``acc_a (c_a - c_old_a) + capacity_a (S_a(c_a) - S_a(c_old_a)) + A c_a + b_ref_a = source_a``.
+        ``isotherms``: a ``LinearIsotherm``, ``FreundlichIsotherm`` or ``LangmuirIsotherm`` for all components, or a
+        list of k.  ``accumulation`` (positive) = porosity x volume / dt; ``capacity`` (>= 0, None = no sorption) = bulk
+        density x volume / dt, with whatever scales the isotherm per cell.  ``c0``: (k, Nc), non-negative;
+        ``accumulation``, ``capacity``, ``bc_values`` and ``source`` broadcast as in ``advance_components``, which
+        remains the call for signed quantities.
+
+        In flow order the step is one scalar monotone root-finding per cell and component, exact given its upstream
+        cells: no Jacobian, no Krylov loop, no damping; the matrix, the levels and the launches are those of one
+        component.  A linear isotherm is folded into the accumulation and is the division of ``advance_components``.
+        The cells of a cyclic core are iterated by nonlinear Jacobi, at most ``maxit`` times per step.  Returns
+        (c, info): info["steps_done"], "converged", the per-component lists "iterations" (1, or the core iterations of
+        the last step) and "rel_residual", and "sorbed" (k, Nc), ``S_a(c_a)`` of the returned state.  A step in which a
+        cell has no root ``c >= 0`` (a sink that takes more than the cell holds) raises ``ValueError`` naming the step,
+        the cell and the component; the error of a refused step carries ``state``, c before that step, and ``info``."""
+        pd = data[PARAMETERS][self.keyword]
+        c0 = np.asarray(c0, dtype=np.float64)
+        nc, nf = sd.num_cells, sd.num_faces
+        if c0.ndim != 2 or c0.shape[1] != nc:
+            raise ValueError(f"c0 must have shape (k, {nc}), not {c0.shape}")
+        k = c0.shape[0]
+        if not 1 <= k <= 64:
+            raise ValueError(f"the number of components must lie in 1 .. 64, not {k} (c0 has shape {c0.shape})")
+        iso = list(isotherms) if isinstance(isotherms, (list, tuple)) else [isotherms] * k
+        if len(iso) != k:
+            raise ValueError(f"isotherms must be one isotherm or a list of {k}, not {len(iso)}")
+        for a, one in enumerate(iso):
+            if not isinstance(one, (LinearIsotherm, FreundlichIsotherm, LangmuirIsotherm)):
+                raise ValueError(f"isotherms[{a}] must be a LinearIsotherm, a FreundlichIsotherm or a LangmuirIsotherm, "
+                                 f"not {one!r}")
+        if accumulation is None:
+            raise ValueError("accumulation is required")
+        acc = per_component("accumulation", accumulation, k, nc)
+        cap = None if capacity is None else per_component("capacity", capacity, k, nc)
+        bv = per_component("bc_values", pd["bc_values"] if bc_values is None else bc_values, k, nf)
+        src = None if source is None else per_component("source", source, k, nc)
+        with _argument_errors(with_state=True):
+            return self.context(sd).transport_advance_sorb(
+                c0, n_steps, acc, bv, [one.kind for one in iso], np.array([one.params() for one in iso]), capacity=cap,
+                q=self._flux(sd, pd), source=src, rtol=rtol, maxit=maxit, raise_on_fail=raise_on_fail)
 
     def adjoint_reactive_components(self, sd, data: dict, n_steps: int, accumulation, rate_matrix, loads,
                                     rate_weight=None, mobility=None, obs_cells=None, states=None, bc_values=None,

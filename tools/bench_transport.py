@@ -8,7 +8,7 @@ not a test: no thresholds.
 
     python tools/bench_transport.py [--n-side 69] [--steps 20] [--no-host] [--precond sweep] [--components 8]
                                     [--saturation [--components 4]] [--reactive] [--adjoint]
-                                    [--reactive --adjoint] [--saturation --adjoint]
+                                    [--reactive --adjoint] [--saturation --adjoint] [--sorbing [--components 1,4,16]]
 
 --precond sweep: after the Jacobi-BiCGStab steps, the same steps from the same state with the flow-ordered sweep
 (PFV_PRECOND_SWEEP) -- order-build ms, levels, core cells, launches per sweep, ms per step -- and again with one launch
@@ -33,6 +33,14 @@ precond="sweep"): ms per step of the three (best and median of --reps, the first
 (transport_advance_multi with precond="sweep") and the same number of reactive k = 4 steps (transport_advance_react):
 the chain 0 -> 1 -> 2 plus the exchange 0 <-> 3 with component 3 immobile, the reaction term weighted by the pore
 volume.  ms per step of both from pfv_stats (best and median of --reps, the first repeat dropped), levels, launches.
+
+--sorbing (JSON key "sorbing"): alternating in one loop from the same non-negative state, the k = 4 steps of the linear
+multi-component sweep (transport_advance_multi with precond="sweep"), the same number of sorbing k = 4 steps
+(transport_advance_sorb) with the components Freundlich n = 0.5, Freundlich n = 0.7, Langmuir and linear and a capacity
+of half the accumulation, and the sorbing call with four LINEAR components (Kd = 1: the linear step with the folded
+accumulation).  ms per step of the three from pfv_stats (best and median of --reps, the first repeat dropped), levels,
+launches.  --sorbing --components K (a list runs several K): in addition the sorbing step with K components that cycle
+those four isotherms, ms per step.
 
 --adjoint: in the same process and on the same flux, alternating in one loop, the forward k = 4 sweep step
 (transport_advance_multi with precond="sweep") and the adjoint k = 4 step (transport_adjoint_multi) on 16 observation
@@ -91,6 +99,9 @@ def main():
                     help="linear sweep steps against Corey saturation steps on the same flux and state")
     ap.add_argument("--reactive", action="store_true",
                     help="the linear k = 4 sweep steps against k = 4 coupled (reactive) steps on the same flux and state")
+    ap.add_argument("--sorbing", action="store_true",
+                    help="the linear k = 4 sweep steps against k = 4 sorbing steps (nonlinear isotherms) on the same flux "
+                         "and state; with --components: also the sorbing step at those k")
     ap.add_argument("--adjoint", action="store_true",
                     help="the forward k = 4 sweep step against the adjoint k = 4 step on the same flux; with --saturation: "
                          "the forward Corey step against its adjoint")
@@ -431,6 +442,60 @@ def main():
             entry["error"] = e.message
         out["reactive"] = entry
         ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the reactive call leaves no system behind)
+    if a.sorbing:
+        kc = 4
+        four = [(_lib.ISOTHERM_FREUNDLICH, (1.0, 0.5)), (_lib.ISOTHERM_FREUNDLICH, (0.8, 0.7)),
+                (_lib.ISOTHERM_LANGMUIR, (2.0, 3.0)), (_lib.ISOTHERM_LINEAR, (1.0, 0.0))]
+
+        def problem(kk):
+            iso = [four[j % 4] for j in range(kk)]
+            acc_k = np.array([(1.0 + 0.5 * (j % 4)) * acc for j in range(kk)])
+            bv_k = np.array([tbv * (j % 4 + 1) / 4 for j in range(kk)])
+            state = np.random.default_rng(7).random((kk, nc))
+            return [m for m, _ in iso], np.array([p for _, p in iso]), acc_k, bv_k, 0.5 * acc_k, state
+
+        kinds, par, acc_k, bv_k, cap_k, c0_k = problem(kc)
+        lin_ms, sorb_ms, fold_ms = [], [], []
+        entry = {"k": kc}
+        try:
+            for _ in range(a.reps + 1):  # (the first repeat builds the order and warms up: dropped)
+                cm, minfo = ctx.transport_advance_multi(c0_k, a.steps, acc_k, bv_k, rtol=1e-10, raise_on_fail=False,
+                                                        precond="sweep")
+                multi = ctx.stats()
+                lin_ms.append(multi["transport_advance_ms"] / max(a.steps, 1))
+                cs, sinfo = ctx.transport_advance_sorb(c0_k, a.steps, acc_k, bv_k, kinds, par, capacity=cap_k, rtol=1e-10,
+                                                       raise_on_fail=False)
+                sorb = ctx.stats()
+                sorb_ms.append(sorb["transport_sorb_ms"] / max(a.steps, 1))
+                cf, finfo = ctx.transport_advance_sorb(c0_k, a.steps, acc_k, bv_k, [_lib.ISOTHERM_LINEAR] * kc,
+                                                       np.array([[1.0, 0.0]] * kc), capacity=cap_k, rtol=1e-10,
+                                                       raise_on_fail=False)
+                fold_ms.append(ctx.stats()["transport_sorb_ms"] / max(a.steps, 1))
+            entry.update({
+                "steps_done": sinfo["steps_done"], "linear_steps_done": minfo["steps_done"],
+                "all_linear_steps_done": finfo["steps_done"],
+                "linear_components_ms_per_step": (min(lin_ms[1:]), float(np.median(lin_ms[1:]))),
+                "sorbing_ms_per_step": (min(sorb_ms[1:]), float(np.median(sorb_ms[1:]))),
+                "sorbing_all_linear_ms_per_step": (min(fold_ms[1:]), float(np.median(fold_ms[1:]))),
+                "levels": sorb["sweep_levels"], "core_cells": sorb["sweep_core_cells"],
+                "launches_per_step": sorb["sweep_launches"], "launches_per_sweep_linear": multi["sweep_launches"],
+                "linear_direct_steps": multi["transport_multi_direct_steps"],
+                "core_iterations": sorb["transport_sorb_core_iterations"],
+                "max_rel_residual_last_step": max(sinfo["rel_residual"]),
+                "c_min": float(cs.min()), "c_max": float(cs.max())})
+            for kk in [int(t) for t in a.components.split(",") if t]:
+                kinds, par, acc_k, bv_k, cap_k, c0_k = problem(kk)
+                ms = []
+                for _ in range(a.reps + 1):
+                    cs, sinfo = ctx.transport_advance_sorb(c0_k, a.steps, acc_k, bv_k, kinds, par, capacity=cap_k,
+                                                           rtol=1e-10, raise_on_fail=False)
+                    ms.append(ctx.stats()["transport_sorb_ms"] / max(a.steps, 1))
+                entry[f"k{kk}_sorbing_ms_per_step"] = (min(ms[1:]), float(np.median(ms[1:])))
+                entry[f"k{kk}_steps_done"] = sinfo["steps_done"]
+        except pa.PorefvError as e:
+            entry["error"] = e.message
+        out["sorbing"] = entry
+        ctx.upwind_assemble(tbv, None, accumulation=acc)  # (the sorbing call leaves no system behind)
     if a.adjoint and not a.reactive and not a.saturation:
         kc, n_obs = 4, 16
         acc_k = np.array([(1.0 + 0.5 * j) * acc for j in range(kc)])

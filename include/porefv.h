@@ -266,6 +266,8 @@ typedef struct {
   int64_t transport_sorb_steps;    /* ... accepted steps */
   int64_t transport_sorb_core_iterations; /* ... nonlinear Jacobi iterations of the cyclic core, summed over the steps */
   int64_t transport_sorb_components; /* ... its k */
+  int64_t topology_reference_path;   /* 1: the last topology rebuild ran the reference construction (PFV_TOPO_LEGACY=1, or
+                                        an input the node-cooperative one hands over), 0: the node-cooperative one */
 } pfv_stats;
 
 pfv_status pfv_create(int device, pfv_ctx** out);
@@ -1378,6 +1380,16 @@ pfv_status pfv_time_kernel(pfv_ctx* h, int kernel, int reps, double* avg_ms);
 /* Test hook: copy the leading `count` entries of an internal FP64 device array to the host (0 = the
  * per-node response tables, 1 = the boundary columns of the nodes on the boundary). */
 pfv_status pfv_debug_copy(pfv_ctx* h, int which, double* dst, int64_t count);
+
+/* Test hook: the integer arrays and scalars of the sub-cell topology on the handle.  `which` names the array, in this
+ * order: 0 node_hptr (i32), 1 h_cell (i32), 2 h_lf (u8), 3 h_sgn (i8), 4 h_first (u8), 5 node_fptr (i32), 6 node_sf (i32),
+ * 7 sf_face (i32), 8 sf_ls (u8), 9 face_nsides (i32), 10 node_face (i32), 11 node_bptr (i32), 12 node_bfaces (i32),
+ * 13 node_bls (u8), 14 node_tptr (i64), 15 node_tbptr (i64), 16 node_cells (i32), 17 face_order (i32),
+ * 18 node_order (i32), 19 class_begin (i64), 20 the scalars as 17 x i64 (nh, max_face_nodes, max_cell_faces, max_block,
+ * max_deg, max_bnd_per_node, sum_block_sq, tab_len, tabb_len, the bits of stats.node_flops, stats.num_nodes,
+ * stats.num_sub_half_faces, stats.sum_block_sq, stats.max_block, stats.node_table_doubles, the topology digest, the construction that ran: 1 node-cooperative, 0 reference).
+ * *bytes receives the size of the array in bytes; it is copied to dst when dst is not NULL and capacity >= *bytes. */
+pfv_status pfv_debug_topology(pfv_ctx* h, int which, void* dst, int64_t capacity, int64_t* bytes);
 
 #ifdef __cplusplus
 }

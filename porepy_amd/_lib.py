@@ -55,6 +55,7 @@ EXPORTS = [
     "pfv_transport_advance_react", "pfv_transport_adjoint_multi", "pfv_transport_adjoint_react",
     "pfv_transport_adjoint_nl", "pfv_transport_adjoint_nl_multi", "pfv_flow_adjoint", "pfv_flow_adjoint_exact",
     "pfv_advdiff_adjoint", "pfv_advdiff_adjoint_exact", "pfv_amg_level_rhs", "pfv_transport_advance_sorb",
+    "pfv_debug_topology",
 ]
 
 
@@ -114,7 +115,8 @@ class Stats(C.Structure):
                 ("advdiff_adjoint_exact_ms", C.c_double), ("advdiff_adjoint_exact_passes", C.c_int64),
                 ("advdiff_adjoint_exact_batch", C.c_int64),
                 ("transport_sorb_ms", C.c_double), ("transport_sorb_steps", C.c_int64),
-                ("transport_sorb_core_iterations", C.c_int64), ("transport_sorb_components", C.c_int64)]
+                ("transport_sorb_core_iterations", C.c_int64), ("transport_sorb_components", C.c_int64),
+                ("topology_reference_path", C.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -305,6 +307,8 @@ def _bind(lib: C.CDLL) -> C.CDLL:
     lib.pfv_get_matrix_rows.restype = C.c_int
     lib.pfv_debug_copy.argtypes = [_h, C.c_int, _dp, C.c_int64]
     lib.pfv_debug_copy.restype = C.c_int
+    lib.pfv_debug_topology.argtypes = [_h, C.c_int, C.c_void_p, C.c_int64, _lp]
+    lib.pfv_debug_topology.restype = C.c_int
     lib.pfv_spmv_device_rows.argtypes = [_h, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
     lib.pfv_spmv_device_rows.restype = C.c_int
     lib.pfv_copy_device_vector.argtypes = [_h, C.c_int, C.c_void_p, C.c_int64]
@@ -2161,6 +2165,32 @@ class Context:
         """Leading n entries of an internal per-node array (0: response tables, 1: boundary columns), for tests."""
         out = np.empty(n, dtype=np.float64)
         self._check(self.lib.pfv_debug_copy(self._h, int(which), _ptr(out, _dp), n))
+        return out
+
+    TOPOLOGY_ARRAYS = (
+        ("node_hptr", np.int32), ("h_cell", np.int32), ("h_lf", np.uint8), ("h_sgn", np.int8), ("h_first", np.uint8),
+        ("node_fptr", np.int32), ("node_sf", np.int32), ("sf_face", np.int32), ("sf_ls", np.uint8),
+        ("face_nsides", np.int32), ("node_face", np.int32), ("node_bptr", np.int32), ("node_bfaces", np.int32),
+        ("node_bls", np.uint8), ("node_tptr", np.int64), ("node_tbptr", np.int64), ("node_cells", np.int32),
+        ("face_order", np.int32), ("node_order", np.int32), ("class_begin", np.int64))
+    TOPOLOGY_SCALARS = ("nh", "max_face_nodes", "max_cell_faces", "max_block", "max_deg", "max_bnd_per_node",
+                        "sum_block_sq", "tab_len", "tabb_len", "node_flops_bits", "stats_num_nodes",
+                        "stats_num_sub_half_faces", "stats_sum_block_sq", "stats_max_block",
+                        "stats_node_table_doubles", "topology_digest", "topology_path")
+
+    def debug_topology(self) -> dict:
+        """The integer arrays and scalars of the sub-cell topology on the handle (pfv_debug_topology), for tests."""
+        out = {}
+        nbytes = C.c_int64()
+        for which, (name, dtype) in enumerate(self.TOPOLOGY_ARRAYS + (("scalars", np.int64),)):
+            self._check(self.lib.pfv_debug_topology(self._h, which, None, 0, C.byref(nbytes)))
+            arr = np.empty(nbytes.value // np.dtype(dtype).itemsize, dtype=dtype)
+            if arr.size:
+                self._check(self.lib.pfv_debug_topology(self._h, which, arr.ctypes.data_as(C.c_void_p), arr.nbytes,
+                                                        C.byref(nbytes)))
+            out[name] = arr
+        for name, v in zip(self.TOPOLOGY_SCALARS, out.pop("scalars")):
+            out[name] = int(v)
         return out
 
     def time_kernel(self, kernel: int, reps: int = 10) -> float:

@@ -552,6 +552,47 @@ inline void parallel_for(stream_t s, int64_t n, F f) {
 #endif
 }
 
+// One thread per index, plus NM running maxima of NON-NEGATIVE int32 values: f(i, m) raises m[0 .. NM) of its own
+// thread; the workgroup combines them in LDS and touches out[k] once (out zeroed by the caller).  A thread that calls
+// track_max_i32 per element reads ONE address per element instead (23 M volatile reads for two small integers).
+#ifndef PFV_EMULATE
+template <int NM, class F>
+__global__ void __launch_bounds__(256) k_parallel_for_max(int64_t n, int32_t* out, F f) {
+  __shared__ int32_t red[NM];
+  if ((int)threadIdx.x < NM) red[threadIdx.x] = 0;
+  __syncthreads();
+  int32_t m[NM];
+#pragma unroll
+  for (int k = 0; k < NM; ++k) m[k] = 0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) f(i, m);
+#pragma unroll
+  for (int k = 0; k < NM; ++k) {
+    if (m[k] > 0) atomicMax(&red[k], m[k]);
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < NM && red[threadIdx.x] > 0) atomicMax(out + threadIdx.x, red[threadIdx.x]);
+}
+#endif
+template <int NM, class F>
+inline void parallel_for_max(stream_t s, int64_t n, int32_t* out, F f) {
+  if (n <= 0) return;
+#ifdef PFV_EMULATE
+  (void)s;
+  int32_t m[NM];
+  for (int k = 0; k < NM; ++k) m[k] = 0;
+  for (int64_t i = 0; i < n; ++i) f(i, m);
+  for (int k = 0; k < NM; ++k) {
+    if (m[k] > out[k]) out[k] = m[k];
+  }
+#else
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 16384) blocks = 16384;
+  PFV_LAUNCH(HIP_KERNEL_NAME(k_parallel_for_max<NM, F>), dim3((unsigned)blocks), dim3(256), 0, s, n, out, f);
+  PFV_HIP_CHECK(hipGetLastError());
+#endif
+}
+
 // G lanes (default: one 64-lane wavefront) per work item, `lds_bytes` of LDS per item.
 template <int G = 64, class F>
 inline void wave_for(stream_t s, int64_t n, size_t lds_bytes, F f) {
@@ -761,6 +802,32 @@ inline void exclusive_scan(stream_t s, Scratch& sc, const TI* in, TO* out, size_
 #endif
 }
 
+// The same for a record type T with operator+ whose inputs are computed, not stored: out[i] = sum_{j<i} gen(j) for
+// i in [0, n]; gen(j) is called for j < n only.  One scan of a k-field record instead of k scans.
+template <class T>
+struct PlusOp {
+  PFV_HD T operator()(const T& a, const T& b) const { return a + b; }
+};
+template <class T, class Gen>
+inline void exclusive_scan_gen(stream_t s, Scratch& sc, Gen gen, T* out, size_t n) {
+#ifdef PFV_EMULATE
+  (void)s; (void)sc;
+  T acc = T();
+  for (size_t i = 0; i < n; ++i) {
+    out[i] = acc;
+    acc = acc + gen((int64_t)i);
+  }
+  out[n] = acc;
+#else
+  auto it = rocprim::make_transform_iterator(rocprim::make_counting_iterator<size_t>(0),
+                                             [gen, n] __device__(size_t i) -> T { return i < n ? gen((int64_t)i) : T(); });
+  size_t bytes = 0;
+  PFV_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, it, out, T(), n + 1, PlusOp<T>(), s));
+  sc.tmp.ensure(bytes);
+  PFV_HIP_CHECK(rocprim::exclusive_scan(sc.tmp.p, bytes, it, out, T(), n + 1, PlusOp<T>(), s));
+#endif
+}
+
 template <class T>
 inline T read_scalar(stream_t s, const T* dptr) {
   T v;
@@ -827,6 +894,14 @@ PFV_HD inline void atomic_min_i32(int* addr, int v) {
 #else
   (void)addr; (void)v;
 #endif
+#endif
+}
+// plain store that other threads may race with (any one of the stored values stays)
+PFV_HD inline void store_relaxed_i32(int* addr, int v) {
+#if !defined(PFV_EMULATE) && defined(__HIP_DEVICE_COMPILE__)
+  __hip_atomic_store(addr, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  *addr = v;
 #endif
 }
 PFV_HD inline int atomic_fetch_add_i32(int* addr, int v) {

@@ -164,6 +164,7 @@ struct pfv_ctx_impl {
   int max_block = 0, max_deg = 0, max_face_nodes = 0, max_cell_faces = 0, max_bnd_per_node = 0;
   int64_t sum_block_sq = 0;   // sum of n(v)^2 (statistics)
   int64_t tab_len = 0, tabb_len = 0;
+  int topo_path = 0;          // construction that built the topology: 1 node-cooperative, 0 reference (topology.inc)
 
   // ---- per-node numeric results consumed by the face kernel ---------------------
   // Response table of node v (n sub-faces, nh = nd * deg sub-half-faces, row stride ldt = nh rounded up

@@ -4737,6 +4737,59 @@ pfv_status pfv_debug_copy(pfv_ctx* h, int which, double* dst, int64_t count) {
   });
 }
 
+pfv_status pfv_debug_topology(pfv_ctx* h, int which, void* dst, int64_t capacity, int64_t* bytes) {
+  return guarded(h, [&] {
+    require(h->have_topology && bytes && which >= 0 && which <= 20, "bad argument");
+    auto s = h->stream;
+    const int64_t nn = h->nn, nf = h->nf, nsf = h->nsf, nh = h->nh;
+    const void* src = nullptr;
+    int64_t n = 0;
+    std::vector<int64_t> host;
+    switch (which) {
+      case 0: src = h->node_hptr.p; n = 4 * (nn + 1); break;
+      case 1: src = h->h_cell.p; n = 4 * nh; break;
+      case 2: src = h->h_lf.p; n = nh; break;
+      case 3: src = h->h_sgn.p; n = nh; break;
+      case 4: src = h->h_first.p; n = nh; break;
+      case 5: src = h->node_fptr.p; n = 4 * (nn + 1); break;
+      case 6: src = h->node_sf.p; n = 4 * nsf; break;
+      case 7: src = h->sf_face.p; n = 4 * nsf; break;
+      case 8: src = h->sf_ls.p; n = nsf; break;
+      case 9: src = h->face_nsides.p; n = 4 * nf; break;
+      case 10: src = h->node_face.p; n = 4 * nsf; break;
+      case 11: src = h->node_bptr.p; n = 4 * (nn + 1); break;
+      case 12:
+      case 13: {
+        const int64_t nb = pfv::read_scalar<int32_t>(s, h->node_bptr.p + nn);
+        src = which == 12 ? (const void*)h->node_bfaces.p : (const void*)h->node_bls.p;
+        n = which == 12 ? 4 * nb : nb;
+        break;
+      }
+      case 14: src = h->node_tptr.p; n = 8 * (nn + 1); break;
+      case 15: src = h->node_tbptr.p; n = 8 * (nn + 1); break;
+      case 16: src = h->node_cells.p; n = 4 * (nh / h->nd); break;
+      case 17: src = h->face_order.p; n = 4 * nf; break;
+      case 18: src = h->node_order.p; n = 4 * nn; break;
+      case 19: host.assign(h->class_begin.begin(), h->class_begin.end()); break;
+      default: {
+        int64_t flops_bits = 0;
+        std::memcpy(&flops_bits, &h->stats.node_flops, sizeof(double));
+        host = {nh, h->max_face_nodes, h->max_cell_faces, h->max_block, h->max_deg, h->max_bnd_per_node,
+                h->sum_block_sq, h->tab_len, h->tabb_len, flops_bits, (int64_t)h->stats.num_nodes,
+                (int64_t)h->stats.num_sub_half_faces, (int64_t)h->stats.sum_block_sq, (int64_t)h->stats.max_block,
+                (int64_t)h->stats.node_table_doubles, (int64_t)pfv::topology_digest(*h), (int64_t)h->topo_path};
+        break;
+      }
+    }
+    if (which >= 19) n = 8 * (int64_t)host.size();
+    *bytes = n;
+    if (dst && capacity >= n && n > 0) {
+      if (which >= 19) std::memcpy(dst, host.data(), (size_t)n);
+      else be_d2h(dst, src, (size_t)n, s);
+    }
+  });
+}
+
 }  // extern "C"
 
 #include "rccl_hooks.inc"

@@ -9,7 +9,9 @@
 
 namespace pfv {
 
-static void build_topology(pfv_ctx_impl& c) {
+// The reference construction (PFV_TOPO_LEGACY=1, and the path that reports what build_topology_nodes cannot represent):
+// one global sort of the (node, entry) pairs.
+static void build_topology_legacy(pfv_ctx_impl& c) {
   stream_t s = c.stream;
   const int nd = c.nd;
   const int64_t nc = c.nc, nf = c.nf, nn = c.nn, ncf = c.ncf, nsf = c.nsf;
@@ -412,6 +414,438 @@ static void build_topology(pfv_ctx_impl& c) {
   c.stats.sum_block_sq = c.sum_block_sq;
   c.stats.max_block = c.max_block;
   c.stats.node_table_doubles = c.tab_len + c.tabb_len;
+}
+
+// ------------------------------------------------------------------------------------
+// Node-cooperative construction (the default).  The half-face records of a node are, in the stable order of the global
+// sort above, simply its (face, side) pairs by ascending cell-face entry e -- at most 2 * 255 of them -- so every node
+// orders its own records in LDS (rank = number of smaller keys) instead of 24 M pairs going through a radix sort, a
+// gather, a copy and a binary search each.  Phases:
+//   1  the sort keys of the sub-faces; then one pass over faces and cells: face of every sub-face, cell of every
+//      cell-face entry, max nodes per face / faces per cell with one atomic per workgroup.  The (at most two) entries that
+//      name a face are found WITHOUT atomics: every entry stores itself into slot[f] (any one of them stays), a second
+//      pass stores every entry that is not slot[f] into other[f], a third flags an entry that is in neither (a third
+//      side).  Which entry lands where depends on the order, the pair {slot, other} does not -- and only its minimum
+//      and maximum are used.  (Three atomics per entry, 24 M of them, took 0.5 ms.)
+//   2  sub-faces by node: the stable sort of the nsf (node, sub-face) pairs, as in the reference path
+//   3  per node (16 lanes): face id and local index of its sub-faces, number of records and of boundary faces
+//   4  ONE scan of the 6-field record (records, boundary faces, n^2, table sizes, flops) over the nodes
+//   5  per node (one wavefront): keys = entries of its faces, ranked in LDS; cells of the records through LDS in
+//      record order (validation, coalesced stores), their bytes straight to their rank; maxima, boundary-face lists,
+//      cells around the node
+//   6  face order and node order as in the reference path; everything the host needs comes back in ONE packed read.
+// Buffers whose size the reference path reads back are sized by host-known bounds (nh <= 2 nsf, boundary faces <= nsf).
+// What this construction cannot represent -- a face with more than two sides, more than 255 faces in a node, 2^31
+// records -- raises a flag and returns false: the caller runs the reference path, which reports it.
+struct TopoRec {
+  int64_t h, nb, sq, tab, tabb;
+  double fl;  // (a sum of integers below 2^53: exact in any order of summation)
+};
+PFV_HD inline TopoRec operator+(const TopoRec& a, const TopoRec& b) {
+  return TopoRec{a.h + b.h, a.nb + b.nb, a.sq + b.sq, a.tab + b.tab, a.tabb + b.tabb, a.fl + b.fl};
+}
+struct alignas(16) TopoI4 {
+  int32_t x, y, z, w;
+};
+struct TopoClassBounds {
+  int b[kNumClasses];
+};
+constexpr int kTopoKeyCap = 512;           // key slots per node: 2 * kMaxBlock rounded up to a multiple of 4
+constexpr int32_t kTopoNoKey = 0x7fffffff;  // key of an empty slot: never smaller than an entry
+
+static bool build_topology_nodes(pfv_ctx_impl& c) {
+  stream_t s = c.stream;
+  const int nd = c.nd;
+  const int64_t nc = c.nc, nf = c.nf, nn = c.nn, ncf = c.ncf, nsf = c.nsf;
+  const int32_t* cf_ptr = c.cf_ptr;
+  const int32_t* cf_idx = c.cf_idx;
+  const int8_t* cf_sgn = c.cf_sgn;
+  const int32_t* fn_ptr = c.fn_ptr;
+  const int32_t* fn_idx = c.fn_idx;
+  const int64_t hcap = 2 * nsf;  // bound on the number of records: a face has at most two sides
+  if (hcap >= (int64_t(1) << 31)) return false;
+
+  int bits = 1;
+  while ((int64_t(1) << bits) < nn + 1 && bits < 32) ++bits;
+
+  Buf<uint32_t> key_in, key_out;
+  Buf<int32_t> val_in, val_out, cell_of_e, face_ends, cnt_n_, nb_n_;
+  const int64_t nkey = std::max(nsf, std::max(nf, nn));
+  key_in.ensure(nkey);
+  key_out.ensure(nkey);
+  val_in.ensure(nkey);
+  int32_t* coe = cell_of_e.ensure(ncf);
+  // [nf] slot, [nf] other: the one or two entries that name a face (-1: none)
+  int32_t* fslot = face_ends.ensure(2 * nf);
+  int32_t* fother = fslot + nf;
+  Buf<int32_t> mx_;
+  int32_t* mx = mx_.ensure(4);  // max nodes per face, max faces per cell, the "not representable" flag
+  int32_t* ns = c.face_nsides.ensure(nf);
+  int32_t* st = c.status.ensure(16);
+  be_memset(fslot, 0xff, sizeof(int32_t) * 2 * nf, s);
+  be_memset(mx, 0, sizeof(int32_t) * 4, s);
+  be_memset(st, 0, sizeof(int32_t) * 16, s);
+
+  c.node_fptr.ensure(nn + 1);
+  c.node_sf.ensure(nsf);
+  c.sf_face.ensure(nsf);
+  c.sf_ls.ensure(nsf);
+  // --- 1: faces and cells
+  {
+    uint32_t* k = key_in;
+    int32_t* v = val_in;
+    int32_t* sff = c.sf_face;
+    parallel_for(s, nsf, PFV_LAMBDA(int64_t i) {
+      k[i] = (uint32_t)fn_idx[i];
+      v[i] = (int32_t)i;
+    });
+    // (the loads of a thread before its first store)
+    parallel_for_max<2>(s, std::max(nc, nf), mx, PFV_LAMBDA(int64_t i, int32_t* m) {
+      int fa = 0, fb = 0, ca = 0, cb = 0;
+      if (i < nf) {
+        fa = fn_ptr[i];
+        fb = fn_ptr[i + 1];
+      }
+      if (i < nc) {
+        ca = cf_ptr[i];
+        cb = cf_ptr[i + 1];
+      }
+      int32_t f4[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) f4[u] = ca + u < cb ? cf_idx[ca + u] : -1;
+      for (int t = fa; t < fb; ++t) sff[t] = (int32_t)i;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (f4[u] >= 0) {
+          coe[ca + u] = (int32_t)i;
+          store_relaxed_i32(fslot + f4[u], ca + u);
+        }
+      }
+      for (int e = ca + 4; e < cb; ++e) {
+        const int f = cf_idx[e];
+        coe[e] = (int32_t)i;
+        store_relaxed_i32(fslot + f, e);
+      }
+      m[0] = fb - fa > m[0] ? fb - fa : m[0];
+      m[1] = cb - ca > m[1] ? cb - ca : m[1];
+    });
+    parallel_for(s, ncf, PFV_LAMBDA(int64_t e) {
+      const int f = cf_idx[e];
+      if (fslot[f] != (int32_t)e) store_relaxed_i32(fother + f, (int32_t)e);
+    });
+    parallel_for(s, ncf, PFV_LAMBDA(int64_t e) {
+      const int f = cf_idx[e];
+      if (fslot[f] != (int32_t)e && fother[f] != (int32_t)e) atomic_max_i32(mx + 2, 1);
+    });
+  }
+  // --- 2: sub-faces (face, node) grouped by node
+  sort_pairs(s, c.scratch, key_in.p, key_out.p, val_in.p, c.node_sf.p, (size_t)nsf, bits);
+  {
+    int32_t* fp = c.node_fptr;
+    const uint32_t* ks = key_out;
+    parallel_for(s, nn + 1, PFV_LAMBDA(int64_t v) {
+      fp[v] = lower_bound_idx<uint32_t>(ks, (int)nsf, (uint32_t)v);
+    });
+  }
+  // --- 3: per node, face id and local index of every sub-face; records and boundary faces counted
+  int32_t* nm_face = c.node_face.ensure(nsf);
+  int32_t* cnt_n = cnt_n_.ensure(nn);
+  int32_t* nb_n = nb_n_.ensure(nn);
+  {
+    const int32_t* fp = c.node_fptr;
+    const int32_t* nsfp = c.node_sf;
+    const int32_t* sff = c.sf_face;
+    uint8_t* ls = c.sf_ls;
+    wave_for<16>(s, nn, 2 * 16 * sizeof(int32_t), PFV_LAMBDA(const WaveCtx& w) {
+      int32_t* part = reinterpret_cast<int32_t*>(w.lds);
+      const int64_t v = w.item;
+      const int a = fp[v], n = fp[v + 1] - a;
+      int cnt = 0, nb = 0;
+      const bool odd = n > kMaxBlock;
+      PFV_LANES(l, n) {
+        const int sfi = nsfp[a + l];
+        const int f = sff[sfi];
+        const int sides = (fslot[f] >= 0 ? 1 : 0) + (fother[f] >= 0 ? 1 : 0);
+        nm_face[a + l] = f;
+        ls[sfi] = (uint8_t)(l & 0xff);
+        cnt += sides;
+        nb += sides == 1 ? 1 : 0;
+      }
+      if (odd) atomic_max_i32(mx + 2, 1);
+      part[w.lane] = cnt;
+      part[16 + w.lane] = nb;
+      w.lsync();
+      if (w.lane0()) {
+        int tc = 0, tb = 0;
+        for (int i = 0; i < w.width; ++i) {
+          tc += part[i];
+          tb += part[16 + i];
+        }
+        cnt_n[v] = tc;
+        nb_n[v] = tb;
+      }
+      w.lsync();
+    });
+  }
+  // --- 4: one scan for the five row pointers / totals of the nodes
+  Buf<TopoRec> rec_;
+  TopoRec* rec = rec_.ensure(nn + 1);
+  {
+    const int32_t* fp = c.node_fptr;
+    exclusive_scan_gen<TopoRec>(s, c.scratch, PFV_LAMBDA(int64_t v) -> TopoRec {
+      const int n = fp[v + 1] - fp[v], cnt = cnt_n[v], nb = nb_n[v], deg = cnt / nd;
+      TopoRec r;
+      r.h = cnt;
+      r.nb = nb;
+      r.sq = (int64_t)n * n;
+      // response table: n rows + the e-row, stride = nh rounded up to even (16-byte rows)
+      r.tab = (int64_t)(n + 1) * ((cnt + 1) & ~1);
+      r.tabb = 2 * (int64_t)n * nb;
+      r.fl = 2.0 * n * n * n + 2.0 * nd * n * cnt + 2.0 * (1 + nd) * n * nb + 60.0 * nd * nd * deg;
+      return r;
+    }, rec, (size_t)nn);
+  }
+  // --- 5: per node, the records in entry order
+  c.node_hptr.ensure(nn + 1);
+  c.node_bptr.ensure(nn + 1);
+  c.node_tptr.ensure(nn + 1);
+  c.node_tbptr.ensure(nn + 1);
+  c.h_cell.ensure(hcap);
+  c.h_lf.ensure(hcap);
+  c.h_sgn.ensure(hcap);
+  c.h_first.ensure(hcap);
+  c.node_bfaces.ensure(nsf);
+  c.node_bls.ensure(nsf);
+  c.node_cells.ensure(hcap / nd + 1);
+  {
+    const int32_t* fp = c.node_fptr;
+    int32_t* hp = c.node_hptr;
+    int32_t* bp = c.node_bptr;
+    int64_t* tp = c.node_tptr;
+    int64_t* tbp = c.node_tbptr;
+    int32_t* hc = c.h_cell;
+    uint8_t* lf = c.h_lf;
+    int8_t* hs = c.h_sgn;
+    uint8_t* first = c.h_first;
+    int32_t* bf = c.node_bfaces;
+    uint8_t* bl = c.node_bls;
+    int32_t* ncl = c.node_cells;
+    // (keys and record cells only: 4.3 KB per node.  With the cells and signs of the entries staged as well it was 9 KB,
+    // 17 nodes in flight per CU, and the kernel -- a chain of dependent loads per node -- took 0.65 ms.)
+    const size_t lds_bytes = (size_t)kTopoKeyCap * 2 * sizeof(int32_t) + 256;
+    // One wavefront per node: a tetrahedral interior node has 36 faces (one pass of the lanes), a hexahedral one 12.
+    // (Narrower lane groups were not measured; the kernel is bound by the rank loop, whose passes per node 32 lanes double
+    // at 36 faces.)  The three maxima below are taken by one lane per node with a read before the atomic -- 1 M reads of
+    // three addresses, not a reduction per workgroup: a wave_for work item has no hook for one.
+    // Precondition of the ranks: the keys of a node are distinct, i.e. a face names a node once.  A face that lists a node
+    // twice gives two sub-faces with equal keys; their records then share slots (in bounds, but which one stays is not
+    // defined, unlike in the reference path).
+    wave_for<64>(s, nn, lds_bytes, PFV_LAMBDA(const WaveCtx& w) {
+      int32_t* keys = reinterpret_cast<int32_t*>(w.lds);   // [2n] lower / higher entry of every face of the node
+      int32_t* cellS = keys + kTopoKeyCap;                 // [cnt] cells of the records, in record order
+      uint8_t* bndL = reinterpret_cast<uint8_t*>(cellS + kTopoKeyCap);  // [n] boundary face
+      const int64_t v = w.item;
+      const int a = fp[v], n = fp[v + 1] - a;
+      const TopoRec r0 = rec[v], r1 = rec[v + 1];
+      const int h0 = (int)r0.h, cnt = (int)(r1.h - r0.h), b0 = (int)r0.nb, nb = (int)(r1.nb - r0.nb);
+      if (w.lane0()) {
+        hp[v] = h0;
+        bp[v] = b0;
+        tp[v] = r0.tab;
+        tbp[v] = r0.tabb;
+        if (v == nn - 1) {
+          hp[nn] = (int32_t)r1.h;
+          bp[nn] = (int32_t)r1.nb;
+          tp[nn] = r1.tab;
+          tbp[nn] = r1.tabb;
+        }
+        track_max_i32(st + 1, n);
+        track_max_i32(st + 2, cnt / nd);
+        track_max_i32(st + 3, nb);
+        if (cnt % nd) atomic_max_i32(st + 0, 2);
+      }
+      if (n <= kMaxBlock) {  // (a larger node has raised the flag in phase 3)
+        PFV_LANES(l, n) {
+          const int f = nm_face[a + l];
+          const int32_t e0 = fslot[f], e1 = fother[f];
+          keys[l] = e0 < 0 ? kTopoNoKey : (e1 < 0 || e0 < e1 ? e0 : e1);
+          keys[n + l] = e1 < 0 ? kTopoNoKey : (e0 < e1 ? e1 : e0);
+          bndL[l] = (e0 >= 0 && e1 < 0) ? 1 : 0;
+        }
+        PFV_LANES(t, (4 - ((2 * n) & 3)) & 3) keys[2 * n + t] = kTopoNoKey;
+        w.lsync();
+        const int n4 = (2 * n + 3) >> 2;
+        const TopoI4* k4 = reinterpret_cast<const TopoI4*>(keys);
+        PFV_LANES(l, n) {
+          const int32_t k0 = keys[l], k1 = keys[n + l];
+          // (cell and sign of the two entries: loads in flight while the ranks are counted)
+          const bool s0 = k0 != kTopoNoKey, s1 = k1 != kTopoNoKey;
+          const int32_t c0 = s0 ? coe[k0] : -1, c1 = s1 ? coe[k1] : -1;
+          const int8_t g0 = s0 ? cf_sgn[k0] : (int8_t)0, g1 = s1 ? cf_sgn[k1] : (int8_t)0;
+          int q0 = 0, q1 = 0;
+          for (int u = 0; u < n4; ++u) {
+            const TopoI4 q = k4[u];
+            q0 += (q.x < k0 ? 1 : 0) + (q.y < k0 ? 1 : 0) + (q.z < k0 ? 1 : 0) + (q.w < k0 ? 1 : 0);
+            q1 += (q.x < k1 ? 1 : 0) + (q.y < k1 ? 1 : 0) + (q.z < k1 ? 1 : 0) + (q.w < k1 ? 1 : 0);
+          }
+          if (s0) {
+            cellS[q0] = c0;
+            lf[h0 + q0] = (uint8_t)l;
+            first[h0 + q0] = 1;
+            hs[h0 + q0] = g0;
+          }
+          if (s1) {
+            cellS[q1] = c1;
+            lf[h0 + q1] = (uint8_t)l;
+            first[h0 + q1] = c1 == c0 ? 1 : 0;
+            hs[h0 + q1] = g1;
+          }
+        }
+        w.lsync();
+        PFV_LANES(p, cnt) {
+          const int32_t cc = cellS[p];
+          hc[h0 + p] = cc;
+          // nd faces of a cell meet here, cells ascending
+          const bool bad = (p % nd) ? (cc != cellS[p - 1]) : (p > 0 && cc <= cellS[p - 1]);
+          if (bad) atomic_max_i32(st + 0, 2);
+          if (p % nd == 0) ncl[(h0 + p) / nd] = cc;
+        }
+        if (nb > 0) {
+          PFV_LANES(l, n) {
+            if (bndL[l]) {
+              int o = b0;
+              for (int t = 0; t < l; ++t) o += bndL[t];
+              bf[o] = nm_face[a + l];
+              bl[o] = (uint8_t)l;
+            }
+          }
+        }
+      }
+      w.lsync();
+    });
+  }
+
+  // --- 6: processing order of the face kernels (Morton curve through the face centres) and launch order of the
+  // interaction-region kernel (nodes bucketed by block size), as in the reference path
+  c.face_order.ensure(nf);
+  {
+    uint32_t* k = key_in;
+    int32_t* v = val_in;
+    const double* fc = c.fcen;
+    double lo[3], sc[3];
+    for (int d = 0; d < 3; ++d) {
+      lo[d] = c.bbox_lo[d];
+      const double ext = c.bbox_hi[d] - c.bbox_lo[d];
+      sc[d] = ext > 0 ? 1023.999 / ext : 0.0;
+    }
+    const double lo0 = lo[0], lo1 = lo[1], lo2 = lo[2], sc0 = sc[0], sc1 = sc[1], sc2 = sc[2];
+    parallel_for(s, nf, PFV_LAMBDA(int64_t f) {
+      uint32_t q[3];
+      q[0] = (uint32_t)((fc[f] - lo0) * sc0);
+      q[1] = (uint32_t)((fc[nf + f] - lo1) * sc1);
+      q[2] = (uint32_t)((fc[2 * nf + f] - lo2) * sc2);
+      uint32_t code = 0;
+      for (int d = 0; d < 3; ++d) {
+        uint32_t x = q[d] & 0x3ffu;  // spread 10 bits to every third position
+        x = (x | (x << 16)) & 0x030000ffu;
+        x = (x | (x << 8)) & 0x0300f00fu;
+        x = (x | (x << 4)) & 0x030c30c3u;
+        x = (x | (x << 2)) & 0x09249249u;
+        code |= x << d;
+      }
+      k[f] = code;
+      v[f] = (int32_t)f;
+      ns[f] = (fslot[f] >= 0 ? 1 : 0) + (fother[f] >= 0 ? 1 : 0);  // (this pass over the faces writes face_nsides too)
+    });
+    sort_pairs(s, c.scratch, key_in.p, key_out.p, val_in.p, c.face_order.p, (size_t)nf, 30);
+  }
+  constexpr int nclass = kNumClasses;
+  constexpr int kPack = 13;  // words of the packed read before the class bounds
+  Buf<int64_t> pack_;
+  int64_t* pk = pack_.ensure(kPack + nclass + 1);
+  {
+    TopoClassBounds bd;
+    for (int i = 0; i < nclass; ++i) bd.b[i] = kClassBounds[i];
+    uint32_t* k = key_in;
+    int32_t* v = val_in;
+    c.node_order.ensure(nn);
+    const int32_t* fp = c.node_fptr;
+    parallel_for(s, nn, PFV_LAMBDA(int64_t node) {
+      const int n = fp[node + 1] - fp[node];
+      int cls = 0;
+      while (cls < nclass - 1 && n > bd.b[cls]) ++cls;
+      k[node] = (uint32_t)cls;
+      v[node] = (int32_t)node;
+    });
+    sort_pairs(s, c.scratch, key_in.p, key_out.p, val_in.p, c.node_order.p, (size_t)nn, 4);
+    const uint32_t* ks = key_out;
+    parallel_for(s, nclass + 2, PFV_LAMBDA(int64_t t) {
+      if (t <= nclass) {
+        pk[kPack + t] = lower_bound_idx<uint32_t>(ks, (int)nn, (uint32_t)t);
+      } else {
+        const TopoRec tot = rec[nn];
+        pk[0] = tot.h;
+        pk[1] = tot.nb;
+        pk[2] = tot.sq;
+        pk[3] = tot.tab;
+        pk[4] = tot.tabb;
+        reinterpret_cast<double*>(pk)[5] = tot.fl;
+        for (int i = 0; i < 4; ++i) pk[6 + i] = st[i];
+        pk[10] = mx[2];
+        pk[11] = mx[0];
+        pk[12] = mx[1];
+      }
+    });
+  }
+  // the one blocking read of the rebuild; the checks in the order the reference path makes them
+  int64_t ph[kPack + nclass + 1];
+  be_d2h(ph, pk, sizeof(ph), s);
+  if (ph[10] != 0) return false;
+  const int64_t nh = ph[0];
+  if (nh >= (int64_t(1) << 31)) throw Error(5, "more than 2^31 sub-half-faces on one device");
+  c.nh = nh;
+  c.max_face_nodes = (int)ph[11];
+  if (c.max_face_nodes > kMaxFaceNodes)
+    throw Error(PFV_ERR_UNSUPPORTED, "faces with more than 8 nodes are not supported");
+  c.max_cell_faces = (int)ph[12];
+  if (c.max_cell_faces > kMaxCellFaces)
+    throw Error(PFV_ERR_UNSUPPORTED, "cells with more than 16 faces are not supported");
+  if (ph[6] == 2)
+    throw Error(PFV_ERR_CELL_SHAPE,
+                "a cell does not have exactly nd faces meeting in one of its nodes (e.g. pyramid)");
+  // (status 1, "cell_faces / face_nodes are inconsistent", is the reference path's alone: here every record comes from
+  // the sub-face list it would be searched in)
+  c.max_block = (int)ph[7];
+  c.max_deg = (int)ph[8];
+  c.max_bnd_per_node = (int)ph[9];
+  if (c.max_block > kMaxBlock || c.max_deg > kMaxBlock)
+    throw Error(PFV_ERR_UNSUPPORTED, "more than 255 faces or cells meet in one node");
+  c.sum_block_sq = ph[2];
+  std::memcpy(&c.stats.node_flops, &ph[5], sizeof(double));
+  c.tab_len = ph[3];
+  c.tabb_len = ph[4];
+  c.class_begin.assign(nclass + 1, nn);
+  for (int cls = 0; cls <= nclass; ++cls) c.class_begin[cls] = ph[kPack + cls];
+  c.have_topology = true;
+  c.topo_key = 0;
+  c.stats.num_nodes = nn;
+  c.stats.num_sub_half_faces = nh;
+  c.stats.sum_block_sq = c.sum_block_sq;
+  c.stats.max_block = c.max_block;
+  c.stats.node_table_doubles = c.tab_len + c.tabb_len;
+  return true;
+}
+
+static void build_topology(pfv_ctx_impl& c) {
+  // PFV_TOPO_LEGACY=1 (read per call): the reference construction, the A/B partner of the node-cooperative one
+  // A hand-over costs both constructions on every rebuild (a grid with a three-sided face is built by the reference path
+  // without an error): pfv_stats.topology_reference_path shows it.
+  c.topo_path = 1;
+  if (env_int("PFV_TOPO_LEGACY", 0) != 0 || !build_topology_nodes(c)) {
+    c.topo_path = 0;
+    build_topology_legacy(c);
+  }
+  c.stats.topology_reference_path = c.topo_path == 0 ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------
